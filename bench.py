@@ -14,13 +14,17 @@ planted sites give every region a few more than 512 windows (~527) and the build
 reference's `callers_per_gpu` (RunInferenceArguments.py:67-74) the host loop keeps CALLERS = 16 steps in
 flight by fusing them into ONE launch chain (16 regions per builder call, 8192 windows per RNN call).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--min-seconds S]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
-Timed region: the K-step pattern is repeated R times back to back (R*K steps as full chains of 16; R is
-the smallest count that makes the region last >= S seconds, default 1 s, and R*K a whole number of
-chains), bracketed by barrier + synchronize on both sides, MAX over ranks. `steps` = K, `repeats` = R,
-`ms_per_step` = time / (R*K), `value` = R*K*512*ranks / time. Every launch in the region has the same
-size, so `roofline.launch_ms` x launches, `flop_per_launch` and `achieved` belong together.
+Timed region: exactly K steps, as launch chains of 16 steps (then one chain of 8 if the rest allows, then the
+remainder), bracketed by barrier + synchronize on both sides, MAX over ranks. `steps` = `timed_steps` = K,
+`ms_per_step` = time / K, `value` = K*512*ranks / time. When K is not a multiple of 16 the last chains are
+shorter, so `roofline.launch_ms`, `windows_per_launch` and `flop_per_launch` are averages over the launches.
+
+--dump-outputs DIR: after the timed region, rank 0 writes what the last timed step computed (its 512 windows
+as the image builder wrote them, their region / position / depth / candidate frequency, and the RNN's
+softmax rows) to DIR/<name>.npy in float32 / float64. The inputs are seeded, so the same arguments give the
+same inputs on every run.
 
 N > 1: either launched by torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE in the env), or — when those are
 absent — this program starts the N ranks itself BEFORE touching the GPU (the fan-out the reference does in
@@ -418,6 +422,29 @@ def graph_secondary(ctx, dev, weights, dbatch, P, pad):
     return out
 
 
+def dump_last_step(out_dir, last, douts, rem_douts, wins, probs):
+    """--dump-outputs: what the last timed step handed its caller. The last launch chain used window buffer k and ran
+    ncall steps; its last step is the chain's last BATCH windows (builder outputs in douts[k] / rem_douts[ncall][k], images
+    in wins[k]) and the last BATCH rows of the flat probability buffer. Integers are stored as float64 (exact), images and
+    probabilities as float32."""
+    k, ncall = last
+    dout = douts[k] if ncall == CALLERS else rem_douts[ncall][k]
+    lo, hi = (ncall - 1) * BATCH, ncall * BATCH
+    assert dout.n_out() >= hi, (dout.n_out(), hi)
+    arrays = {
+        "images": wins[k][lo:hi].float(),
+        "region": dout.region[lo:hi].double(),
+        "position": dout.position[lo:hi].double(),
+        "depth": dout.depth[lo:hi].double(),
+        "cand_freq": dout.cand_freq[lo:hi].double(),
+        "probs": probs[-BATCH:].float(),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    log("wrote %s to %s" % (", ".join("%s%s" % (n, tuple(t.shape)) for n, t in arrays.items()), out_dir))
+
+
 # ------------------------------------------------------------------------------------------------------
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -425,8 +452,8 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--warmup", type=int, default=16)
-    ap.add_argument("--min-seconds", type=float, default=float(os.environ.get("PV_BENCH_MIN_SECONDS", "1.0")),
-                    help="repeat the K-step pattern until the timed region lasts at least this long")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-p2", action="store_true", help="skip the secondary bi-GRU (P2) and single-call figures")
     ap.add_argument("--no-bf16", action="store_true", help="skip the secondary configs[2] (bf16 input GEMM) figure")
@@ -501,6 +528,8 @@ def main(argv=None):
         return out
 
     wchains = chains_for(W)
+    tchains = chains_for(K)                             # the timed region: exactly K steps
+    toffs = [sum(tchains[:g]) * BATCH for g in range(len(tchains))]   # first probability row of each timed chain
 
     # ---- synthetic workload (seeded; rank r gets its own regions: regions shard across GPUs) ---------
     t0 = time.time()
@@ -544,14 +573,17 @@ def main(argv=None):
     if not overlap:
         s_build = s_rnn
 
-    # chains shorter than CALLERS steps (only the warm-up can have them): the first regions of batch 0
-    rem_batches = {n: DeviceBatch(batches[0].select(list(range(n))), dev) for n in set(wchains) if n != CALLERS}
+    # chains shorter than CALLERS steps (warm-up and timed region, when W or K is not a multiple of CALLERS): the first regions of batch 0
+    rem_batches = {n: DeviceBatch(batches[0].select(list(range(n))), dev) for n in set(wchains) | set(tchains) if n != CALLERS}
     rem_douts = {n: [DeviceOut(n * BATCH, n * BATCH * 16, dev, images=w) for w in wins] for n in rem_batches}
     probs_holder = {"t": torch.zeros((1, CALLERS * BATCH, 3), dtype=torch.float32, device=dev)}
 
-    def group(g, ncall=CALLERS, h2d=None):
+    def group(g, ncall=CALLERS, h2d=None, out_ptr=None):
+        """one launch chain of `ncall` steps; probabilities go to out_ptr (default: the untimed scratch rows)"""
         k = state["n"] & 1
         probs = probs_holder["t"]
+        if out_ptr is None:
+            out_ptr = probs[g % probs.shape[0]].data_ptr()
         if state["n"] >= 2:
             s_build.wait_event(ev_used[k])
         if h2d is not None:
@@ -570,9 +602,10 @@ def main(argv=None):
             ctx.summarize_dev(rem_batches[ncall], P, rem_douts[ncall][k], stream=s_build.cuda_stream)
         ev_built[k].record(s_build)
         s_rnn.wait_event(ev_built[k])
-        ctx.forward_p1_dev(wins[k].data_ptr(), ncall * BATCH, probs[g % probs.shape[0]].data_ptr(), stream=s_rnn.cuda_stream)
+        ctx.forward_p1_dev(wins[k].data_ptr(), ncall * BATCH, out_ptr, stream=s_rnn.cuda_stream)
         ev_used[k].record(s_rnn)
         state["n"] += 1
+        state["last"] = (k, ncall)
 
     def drain():
         s_copy.synchronize()
@@ -587,6 +620,13 @@ def main(argv=None):
         assert douts[0].status() == 0, "device status %d" % douts[0].status()
         n_out_batch.append(douts[0].n_out())   # windows the regions yield; those beyond the capacity (512 per step) are dropped
         assert n_out_batch[-1] >= CALLERS * BATCH, "regions yield %d windows < %d: lower PV_BENCH_SITE_EVERY" % (n_out_batch[-1], CALLERS * BATCH)
+    n_out_rem = {}
+    for n, db in rem_batches.items():  # the shorter chains: their first n regions must fill n steps as well
+        ctx.summarize_dev(db, P, rem_douts[n][0], stream=s_build.cuda_stream)
+        s_build.synchronize()
+        assert rem_douts[n][0].status() == 0, "device status %d" % rem_douts[n][0].status()
+        n_out_rem[n] = rem_douts[n][0].n_out()
+        assert n_out_rem[n] >= n * BATCH, "%d regions yield %d windows < %d: lower PV_BENCH_SITE_EVERY" % (n, n_out_rem[n], n * BATCH)
     ctx.forward_p1_dev(wins[0].data_ptr(), CALLERS * BATCH, probs_holder["t"][0].data_ptr(), stream=s_rnn.cuda_stream)  # RNN workspace at full size
     s_rnn.synchronize()
     # image-builder roofline: measured in isolation (16 regions per launch chain), cold inputs (round-robin batches)
@@ -606,32 +646,18 @@ def main(argv=None):
     for g, nc in enumerate(wchains):
         group(g, nc)
     drain()
-    # calibration (untimed): two full chains -> how many repeats of the K-step pattern make >= min_seconds
-    t0 = time.perf_counter()
-    for g in range(2):
-        group(g)
-    drain()
-    est_step = (time.perf_counter() - t0) / (2 * CALLERS)
     # per-kernel breakdown of the chain (untimed: every kernel bracketed by events; the timed region brackets the decoder only)
     ctx.profile_begin()
     for g in range(2):
         group(g)
     drain()
     prof_all = ctx.profile_end()
-    if dist is not None:
-        t_est = torch.tensor([est_step], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
-        dist.all_reduce(t_est, op=dist.ReduceOp.MAX)   # every rank must choose the same repeat count
-        est_step = float(t_est.item())
-    import math
-    unit = CALLERS // math.gcd(K, CALLERS)             # repeats come in multiples of this: R*K is a whole number of chains
-    R = max(1, math.ceil(args.min_seconds / max(est_step * K, 1e-9)))
-    R = ((R + unit - 1) // unit) * unit
-    total_steps = R * K
-    n_chains = total_steps // CALLERS
-    assert n_chains * CALLERS == total_steps
-    probs_holder["t"] = torch.zeros((n_chains, CALLERS * BATCH, 3), dtype=torch.float32, device=dev)
+    total_steps = K
+    n_chains = len(tchains)
+    assert sum(tchains) == total_steps
+    tprobs = torch.zeros((total_steps * BATCH, 3), dtype=torch.float32, device=dev)   # one row per timed window
     chain_ev = [torch.cuda.Event(enable_timing=True) for _ in range(n_chains + 1)]
-    for g in range(2):   # touch the new probs buffer, settle the clocks
+    for g in range(2):   # settle the clocks
         group(g)
     drain()
 
@@ -650,19 +676,19 @@ def main(argv=None):
 
         # untimed warm-up of the one exchange step as well: the first collective of a communicator sets up its channels
         # and loads its kernels (RCCL does that lazily), which must not land inside the timed region
-        exchange(probs_holder["t"].view(-1, 3))
+        exchange(tprobs)
         dist.barrier()
     torch.cuda.synchronize()
     ctx.profile_begin(only="k_lstm_layer_dec")   # the roofline kernel's launch durations, live over the timed region
     t0 = time.perf_counter()
     chain_ev[0].record(s_rnn)
-    for g in range(n_chains):
-        group(g)
+    for g, nc in enumerate(tchains):
+        group(g, nc, out_ptr=tprobs[toffs[g]].data_ptr())
         chain_ev[g + 1].record(s_rnn)
     gathered = None
     if dist is not None:
         drain()
-        gathered = exchange(probs_holder["t"].view(-1, 3))
+        gathered = exchange(tprobs)
     drain()
     torch.cuda.synchronize()
     if dist is not None:
@@ -675,17 +701,23 @@ def main(argv=None):
         dt = float(tmax.item())
         if rank == 0:
             assert gathered is not None and gathered[0].shape[0] == world * total_steps * BATCH, "gather lost rows"
-    chain_ms = sorted(chain_ev[g].elapsed_time(chain_ev[g + 1]) for g in range(n_chains))
+    # the median over the full chains (over all of them when K < 16)
+    med_n = max(tchains)
+    chain_ms = sorted(chain_ev[g].elapsed_time(chain_ev[g + 1]) for g in range(n_chains) if tchains[g] == med_n)
     median_chain_ms = chain_ms[len(chain_ms) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_last_step(args.dump_outputs, state["last"], douts, rem_douts, wins, tprobs)
 
     rc = 0
     if rank == 0:
         total_windows = total_steps * BATCH * world
         value = total_windows / dt
-        builder_windows = sum(min(n_out_batch[g % NBATCH], CALLERS * BATCH) for g in range(n_chains)) * world   # == total_windows
+        builder_windows = sum(min(n_out_batch[g % NBATCH] if nc == CALLERS else n_out_rem[nc], nc * BATCH)
+                              for g, nc in enumerate(tchains)) * world   # == total_windows
         dec_ms, dec_n = prof.get("k_lstm_layer_dec", (0.0, 0))
         dec_launch_ms = dec_ms / max(dec_n, 1)
-        flop_per_launch = FLOP_DEC_PER_WINDOW * CALLERS * BATCH
+        windows_per_launch = total_steps * BATCH / max(dec_n, 1)
+        flop_per_launch = FLOP_DEC_PER_WINDOW * windows_per_launch
         achieved_tf = flop_per_launch / (dec_launch_ms / 1e3) / 1e12 if dec_ms > 0 else 0.0
         sum_ms, sum_n = prof_builder.get("summary_pipeline", (0.0, 0))
         pile_ms, pile_n = prof_builder.get("k_pileup", (0.0, 0))
@@ -696,8 +728,8 @@ def main(argv=None):
             "value": value, "unit": "windows/s", "n_gpus": world, "steps": K, "warmup": W,
             "ms_per_step": dt / total_steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
-            "repeats": R, "timed_steps": total_steps, "timed_seconds": dt,
-            "median_chain_ms": median_chain_ms, "windows_per_s_from_median_chain": CALLERS * BATCH * world / (median_chain_ms / 1e3),
+            "timed_steps": total_steps, "timed_seconds": dt, "chains": {str(n): tchains.count(n) for n in sorted(set(tchains), reverse=True)},
+            "median_chain_ms": median_chain_ms, "windows_per_s_from_median_chain": med_n * BATCH * world / (median_chain_ms / 1e3),
             "windows_from_builder_per_s": builder_windows / dt,
             "windows_note": "every counted window was written by the image builder of the same launch chain (capacity 512 per step; the "
                             "regions yield %.1f per step, the surplus is dropped after the builder's work for it) and inferred" % (n_windows_region / CALLERS),
@@ -712,7 +744,7 @@ def main(argv=None):
                          "achieved": achieved_tf, "peak": PEAK_F32_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved_tf / PEAK_F32_TFLOPS, "traffic": traffic.get("k_lstm_layer<512"),
                          "traffic_note": traffic.get("note"),
-                         "launch_ms": dec_launch_ms, "launches": dec_n, "windows_per_launch": CALLERS * BATCH,
+                         "launch_ms": dec_launch_ms, "launches": dec_n, "windows_per_launch": windows_per_launch,
                          "flop_per_launch": flop_per_launch},
             "roofline_builder": {"bound": "hbm", "kernel": "summary pipeline (k_cigar_scan .. k_write_windows), %d regions/launch" % CALLERS,
                                  "achieved": alg_bytes / (builder_chain_ms / 1e3) / 1e9,

@@ -1,23 +1,11 @@
 """CPU: the image / prediction HDF5 files match the reference's format: round trip through
-this module, and - where a real h5py exists (/opt/conda python) - both directions against h5py itself, with
-the writer script restating DataStore.write_summary's dtypes (DataStore.py:63-68)."""
-import json
+this module, and both directions against a file written by h5py itself with DataStore.write_summary's dtypes
+(DataStore.py:63-68), stored under tests/golden/ (tests/golden/make_hdf5_golden.py)."""
 import os
-import subprocess
-import sys
 
 import numpy as np
-import pytest
 
 from pepper_thesis_amd import hdf5io
-
-CONDA_PY = "/opt/conda/bin/python3.9"
-
-
-def _have_h5py():
-    if not os.path.exists(CONDA_PY):
-        return False
-    return subprocess.run([CONDA_PY, "-c", "import h5py"], capture_output=True).returncode == 0
 
 
 def _sample(n=7):
@@ -60,44 +48,70 @@ def test_interval_rules():
     assert len(k) == 5000 and len(set(k.tolist())) == 5000 and k.max() >= 5000
 
 
-@pytest.mark.skipif(not _have_h5py(), reason="no h5py interpreter in this image")
+def _layout_and_types(path, group):
+    """{dataset: (HDF5 file type id, storage layout, dims)} of one summary group, through libhdf5 itself"""
+    L = hdf5io.lib()
+    L.H5Dget_create_plist.restype = hdf5io.hid_t
+    L.H5Dget_create_plist.argtypes = [hdf5io.hid_t]
+    L.H5Pget_layout.argtypes = [hdf5io.hid_t]
+    out = {}
+    with hdf5io.H5File(path, "r") as f:
+        for name in f.keys(group):
+            did = L.H5Dopen2(f.fid, ("%s/%s" % (group, name)).encode(), hdf5io.H5P_DEFAULT)
+            assert did >= 0, name
+            pl = L.H5Dget_create_plist(did)
+            sid = L.H5Dget_space(did)
+            nd = L.H5Sget_simple_extent_ndims(sid)
+            dims = (hdf5io.hsize_t * max(nd, 1))()
+            L.H5Sget_simple_extent_dims(sid, dims, None)
+            out[name] = (L.H5Dget_type(did), L.H5Pget_layout(pl), tuple(dims[:nd]))
+            L.H5Sclose(sid)
+            L.H5Pclose(pl)
+            L.H5Dclose(did)
+    return out
+
+
 def test_against_real_h5py(tmp_path):
+    """h5py's own file (tests/golden/hdf5_h5py_summary.hdf5: this module's sample written by h5py with the dtypes of
+    DataStore.write_summary, DataStore.py:63-68; tests/golden/make_hdf5_golden.py) (1) has, dataset by dataset, the same
+    HDF5 types (fixed-length byte strings, variable-length UTF-8 strings, int32 / uint8 / int8), storage layout
+    (contiguous) and shapes as the file this module writes for the same sample, so h5py reads ours as it reads its own
+    (dataloader_predict.py:56-61), and (2) is read back by this module."""
     s = _sample()
-    # (1) our file, read by h5py exactly as dataloader_predict.py:56-61 does
+    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hdf5_h5py_summary.hdf5")
+    g = "/summaries/chr20_100_200"
+    # (1) our file, compared with h5py's
     p = str(tmp_path / "ours.hdf5")
     with hdf5io.ImageStore(p, "w") as st:
         st.write_summary("chr20_100_200", s["contigs"], s["positions"], s["depths"], s["candidates"], s["freq"], s["images"])
-    code = (
-        "import h5py, json, numpy as np\n"
-        "f = h5py.File(%r, 'r'); g = f['summaries']['chr20_100_200']\n"
-        "c = g['candidates'][()]\n"
-        "print(json.dumps(dict(keys=sorted(g.keys()), contigs=[x.decode() for x in g['contigs'][()]], positions=g['positions'][()].tolist(),\n"
-        "  cand=[x[0].decode() if isinstance(x[0], bytes) else x[0] for x in c], cshape=list(c.shape), vlen=str(h5py.check_string_dtype(g['candidates'].dtype)),\n"
-        "  img_dtype=str(g['images'].dtype), img_sum=int(g['images'][()].astype(np.int64).sum()), chunks=str(g['images'].chunks),\n"
-        "  dt=[str(g[k].dtype) for k in ('positions','depths','candidate_frequency')])))\n" % p)
-    res = json.loads(subprocess.check_output([CONDA_PY, "-c", code]).decode())
-    assert res["keys"] == ["candidate_frequency", "candidates", "contigs", "depths", "images", "positions"]
-    assert res["contigs"] == ["chr20"] * 7 and res["positions"] == s["positions"].tolist()
-    assert res["cand"] == [c[0] for c in s["candidates"]] and res["cshape"] == [7, 1]
-    assert "utf-8" in res["vlen"] and "None" in res["vlen"]  # variable length UTF-8
-    assert res["img_dtype"] == "int8" and res["img_sum"] == int(s["images"].astype(np.int64).sum()) and res["chunks"] == "None"
-    assert res["dt"] == ["int32", "uint8", "uint8"]
-    # (2) a file written by h5py with the dtypes of DataStore.write_summary, read by this module
-    q = str(tmp_path / "theirs.hdf5")
-    np.savez(str(tmp_path / "s.npz"), positions=s["positions"], depths=s["depths"], freq=s["freq"], images=s["images"])
-    code = (
-        "import h5py, numpy as np\n"
-        "z = np.load(%r)\n"
-        "f = h5py.File(%r, 'w'); dt = h5py.special_dtype(vlen=str); b = 'summaries/chr20_100_200/'\n"
-        "f[b + 'contigs'] = np.array(['chr20'] * 7, dtype='S')\n"
-        "f[b + 'positions'] = np.array(z['positions'], dtype=np.int32)\n"
-        "f[b + 'depths'] = np.array(z['depths'], dtype=np.uint8)\n"
-        "f[b + 'candidates'] = np.array(%r, dtype=dt)\n"
-        "f[b + 'candidate_frequency'] = np.array(z['freq'], dtype=np.uint8)\n"
-        "f[b + 'images'] = np.array(z['images'], dtype=np.int8)\n"
-        "f.close()\n" % (str(tmp_path / "s.npz"), q, s["candidates"]))
-    subprocess.check_call([CONDA_PY, "-c", code])
-    with hdf5io.ImageStore(q, "r") as st:
+    ours, theirs = _layout_and_types(p, g), _layout_and_types(gold, g)
+    L = hdf5io.lib()
+    L.H5Tequal.argtypes = [hdf5io.hid_t, hdf5io.hid_t]
+    L.H5Tget_cset.argtypes = [hdf5io.hid_t]
+    L.H5Tget_strpad.argtypes = [hdf5io.hid_t]
+    try:
+        assert sorted(ours) == sorted(theirs) == ["candidate_frequency", "candidates", "contigs", "depths", "images", "positions"]
+        for name in ours:
+            a, b = ours[name][0], theirs[name][0]
+            assert L.H5Tequal(a, b) > 0, name
+            if L.H5Tget_class(a) == hdf5io.H5T_STRING:   # H5Tequal does not compare these
+                assert (L.H5Tget_cset(a), L.H5Tget_strpad(a)) == (L.H5Tget_cset(b), L.H5Tget_strpad(b)), name
+            assert ours[name][1:] == theirs[name][1:], (name, ours[name][1:], theirs[name][1:])
+        cand = ours["candidates"][0]
+        assert L.H5Tis_variable_str(cand) > 0 and L.H5Tget_cset(cand) == hdf5io.H5T_CSET_UTF8   # variable length UTF-8
+        assert ours["candidates"][2] == (7, 1) and ours["images"][1] == 1                        # H5D_CONTIGUOUS: no chunks
+    finally:
+        for t in list(ours.values()) + list(theirs.values()):
+            L.H5Tclose(t[0])
+    with hdf5io.ImageStore(p, "r") as st:
+        r = st.read_summary("chr20_100_200")
+    assert r["contigs"].dtype == np.dtype("S5") and r["contigs"].tolist() == [b"chr20"] * 7
+    assert r["positions"].dtype == np.int32 and r["positions"].tolist() == s["positions"].tolist()
+    assert r["candidates"][:, 0].tolist() == [c[0] for c in s["candidates"]]
+    assert r["images"].dtype == np.int8 and int(r["images"].astype(np.int64).sum()) == int(s["images"].astype(np.int64).sum())
+    assert [r[k].dtype for k in ("positions", "depths", "candidate_frequency")] == [np.int32, np.uint8, np.uint8]
+    # (2) the file written by h5py, read by this module
+    with hdf5io.ImageStore(gold, "r") as st:
         r = st.read_summary("chr20_100_200")
     assert r["candidates"][:, 0].tolist() == [c[0] for c in s["candidates"]]
     assert np.array_equal(r["images"], s["images"]) and r["positions"].tolist() == s["positions"].tolist()
