@@ -226,6 +226,25 @@ int pv_polish_summarize_regions_dev(pv_ctx* ctx, const pv_batch_in* in, int64_t 
                                     int64_t n_ref_bytes, int seq_length, int seq_overlap, pv_polish_out* out,
                                     int64_t* d_counts, void* stream);
 
+/* The polisher's stitch (pepper/modules/python/Stitch.py:37-86): labels of the chunks above -> polished bases.
+ * chunks: position, index, region and chunk_id of n_chunks chunks as pv_polish_summarize_regions lays them out
+ * (regions ascending; a region's chunks contiguous with chunk ids 0, 1, 2, ...; chunk_capacity >= n_chunks);
+ * labels: uint8 [n_chunks][seq_length] (pv_rnn_forward_p2); region_start: int64 [n_regions] (pv_batch_in.ref_start).
+ * Per region, a column is kept when position >= 0, index >= 0 and not (region_start > 0 and position <=
+ * region_start + 200); a (position, index) two chunks share keeps the label of the chunk whose id is last in
+ * decimal STRING order ("9" after "10"); labels 1..4 give 'A','C','G','T', 0 gives nothing.
+ * Out: region_off int64 [n_regions+1] exclusive offsets of every region's bases in seq; seq uint8 [seq_capacity].
+ * d_counts = {bases, status, first bad chunk (-1 if none), 0}; status PV_ERR_CAPACITY (seq_capacity < bases: nothing
+ * written but region_off), PV_ERR_STATE (a kept label > 4, e.g. the 255 of a poisoned P2 call) or PV_ERR_INVALID
+ * (chunk layout broken). Device-resident and asynchronous on `stream`; no global atomics, no host synchronisation. */
+int pv_polish_stitch_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                         const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap,
+                         int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* d_counts, void* stream);
+/* HOST buffers in and out; counts[4] as d_counts above; returns the status (PV_ERR_CAPACITY with counts[0] = bases needed). */
+int pv_polish_stitch(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                     const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap,
+                     int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* counts);
+
 /* ---- recurrent-network inference ------------------------------------------------------------ */
 
 #define PV_PLAN_P1_LSTM 1 /* pepper_variant: 2x bi-LSTM(256) + 5xLinear(512)/SELU + Linear(3) + softmax */

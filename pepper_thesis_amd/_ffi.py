@@ -162,6 +162,12 @@ SYMBOLS = [
     ("pv_polish_summarize_regions_dev", C.c_int,
      [C.c_void_p, C.POINTER(pv_batch_in), C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,
       C.POINTER(pv_polish_out), C.c_void_p, C.c_void_p]),
+    ("pv_polish_stitch_dev", C.c_int,
+     [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+      C.c_int64, C.c_void_p, C.c_void_p]),
+    ("pv_polish_stitch", C.c_int,
+     [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+      C.c_int64, C.POINTER(C.c_int64)]),
     ("pv_rnn_load_p1", C.c_int, [C.c_void_p, C.POINTER(pv_weights_p1), C.c_int]),
     ("pv_rnn_load_p2", C.c_int, [C.c_void_p, C.POINTER(pv_weights_p2), C.c_int]),
     ("pv_rnn_forward_p1", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

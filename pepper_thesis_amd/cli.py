@@ -126,6 +126,25 @@ def find_candidates_parser(ap=None):
     return ap
 
 
+def polish_parser(ap=None):
+    """the polisher's `polish` (pepper/pepper.py:24-101): same option names; -g and -w are accepted and ignored"""
+    ap = ap or argparse.ArgumentParser(prog="polish")
+    ap.add_argument("-b", "--bam", type=str, required=True)
+    ap.add_argument("-f", "--fasta", type=str, required=True)
+    ap.add_argument("-m", "--model_path", type=str, required=True)
+    ap.add_argument("-o", "--output_file", type=str, required=True,
+                    help="output prefix; made a directory as in the reference: the FASTA is <output_file>/_pepper_polished.fa")
+    ap.add_argument("-t", "--threads", type=int, default=5, help="reader threads")
+    ap.add_argument("-r", "--region", type=str, default=None, help="contig[:start-end]")
+    ap.add_argument("-bs", "--batch_size", type=int, default=2048, help="chunks (1000 columns) per device launch")
+    ap.add_argument("-g", "--gpu", action="store_true", default=False, help="accepted; this build has no CPU path")
+    ap.add_argument("-d_ids", "--device_ids", type=str, default=None, help="the first id is the device used")
+    ap.add_argument("-w", "--num_workers", type=int, default=4, help="accepted and ignored")
+    ap.add_argument("--bf16", action="store_true", default=False,
+                    help="PV_DTYPE_BF16_INPUT_GEMM: matrix products on the bf16 MFMA with 3-term split operands")
+    return ap
+
+
 def preset_of(args) -> str:
     return next(n for n in PRESETS if getattr(args, n, False))
 
@@ -151,6 +170,7 @@ def main(argv=None):
     make_images_parser(sub.add_parser("make_images", help="pileup summary images of the reads aligned to the reference"))
     run_inference_parser(sub.add_parser("run_inference", help="genotype probabilities for generated images"))
     find_candidates_parser(sub.add_parser("find_candidates", help="candidate variants (VCF) from the predictions"))
+    polish_parser(sub.add_parser("polish", help="the polisher: BAM + draft FASTA -> polished FASTA (builder, bi-GRU and stitch on the device)"))
     sub.add_parser("merge_variants", help="not part of this build (merges PEPPER and DeepVariant VCFs downstream of the hot path)")
     args = ap.parse_args(argv)
     if args.version:
@@ -168,6 +188,9 @@ def main(argv=None):
     if args.sub_command == "find_candidates":
         from . import find_candidates
         return find_candidates.run(args)
+    if args.sub_command == "polish":
+        from . import polish
+        return polish.run(args)
     if args.sub_command == "merge_variants":
         sys.stderr.write("ERROR: merge_variants is outside this build (SURVEY 2, row 24): use the reference's own script on the VCFs.\n")
         return 2

@@ -1,0 +1,323 @@
+// polish_stitch.hip — the polisher's stitch step (P2 labels -> polished bases) on the device.
+//
+// Restates pepper/modules/python/Stitch.py:37-86 (small_chunk_stitch) for the chunk batches that
+// pv_polish_summarize_regions[_dev] writes and pv_rnn_forward_p2[_dev] labels:
+//   * a column is dropped when index < 0 or position < 0 (padding), and when region_start > 0 and
+//     position <= region_start + 2*MIN_IMAGE_OVERLAP (the overlap with the previous region);
+//   * the (position, index) pairs shared by two chunks of a region (the seq_overlap columns) keep the label
+//     of the chunk whose id is LAST IN STRING ORDER ("9" after "10"): the reference walks sorted() HDF5 key names;
+//   * label 0 gives no base, 1..4 give A, C, G, T; any other kept label (255 = a poisoned P2 result) is an error.
+// The builder's rows run in (position, index) order inside a region, so emitting the surviving columns in
+// chunk-major order is the reference's sort, and the per-region results concatenated are its per-contig string.
+//
+// Three launches, no global atomics: per-chunk counts (one block per chunk), one block scanning the chunk counts
+// into offsets (+ status, region offsets), then a block-local scan per chunk and a scattered byte write.
+#include "pv_common.hpp"
+
+namespace {
+
+constexpr int ST_THREADS = 256;
+constexpr int ST_MAX_CPT = 16;        // columns per thread: seq_length <= 4096
+constexpr int ST_SCAN_THREADS = 1024;
+constexpr int64_t ST_BUFFER = 200;    // 2 * ImageSizeOptions.MIN_IMAGE_OVERLAP (Stitch.py:42)
+
+enum { BAD_NONE = 0, BAD_LABEL = 1, BAD_ORDER = 2 };
+
+struct StitchArgs {
+    const int64_t* pos;
+    const int32_t* idx;
+    const int32_t* region;
+    const int32_t* cid;
+    const uint8_t* lab;
+    const int64_t* rstart;
+    int64_t n_chunks;
+    int n_regions;
+    int L;
+    int step;      // seq_length - seq_overlap
+    int cpt;       // columns per thread
+    int32_t* chunk_cnt;
+    int32_t* chunk_bad;
+    int64_t* chunk_off;
+    int64_t* region_off;
+    uint8_t* seq;
+    int64_t cap;
+    int64_t* counts;
+};
+
+// str(a) > str(b) for a, b >= 0 (Python string order of the decimal forms)
+__device__ inline bool dec_str_gt(int32_t a, int32_t b) {
+    int na = 1, nb = 1;
+    for (int32_t v = a; v >= 10; v /= 10) na++;
+    for (int32_t v = b; v >= 10; v /= 10) nb++;
+    if (na == nb) return a > b;
+    if (na < nb) {
+        int32_t pb = b;
+        for (int i = na; i < nb; i++) pb /= 10;  // the first na digits of b
+        return a > pb;                            // equal: a is a proper prefix of b, so it sorts first
+    }
+    int32_t pa = a;
+    for (int i = nb; i < na; i++) pa /= 10;
+    return pa >= b;                               // equal: b is a proper prefix of a
+}
+
+// the chunk layout contract: regions ascending, a region's chunks contiguous with ids 0, 1, 2, ...
+__device__ inline bool chunk_in_order(const StitchArgs& a, int64_t k) {
+    const int32_t g = a.region[k], c = a.cid[k];
+    if (g < 0 || g >= a.n_regions || c < 0) return false;
+    if (k == 0) return c == 0;
+    const int32_t pg = a.region[k - 1];
+    return pg == g ? c == a.cid[k - 1] + 1 : (pg < g && c == 0);
+}
+
+struct ChunkView {
+    int64_t base;      // k * L
+    int64_t rs;        // region start
+    bool prev, next;   // the neighbouring chunk of the same region exists
+    int32_t c, cprev, cnext;
+};
+
+__device__ inline ChunkView chunk_view(const StitchArgs& a, int64_t k) {
+    ChunkView v;
+    v.base = k * a.L;
+    const int32_t g = a.region[k];
+    v.rs = a.rstart[g];
+    v.c = a.cid[k];
+    v.prev = k > 0 && a.region[k - 1] == g;
+    v.next = k + 1 < a.n_chunks && a.region[k + 1] == g;
+    v.cprev = v.prev ? a.cid[k - 1] : 0;
+    v.cnext = v.next ? a.cid[k + 1] : 0;
+    return v;
+}
+
+// 0: no base, 1..4: base, -1: a kept column with a label outside 0..4
+__device__ inline int column_label(const StitchArgs& a, const ChunkView& v, int j) {
+    const int64_t t = v.base + j;
+    const int64_t p = a.pos[t];
+    const int32_t x = a.idx[t];
+    if (p < 0 || x < 0) return 0;
+    if (v.rs > 0 && p <= v.rs + ST_BUFFER) return 0;
+    const int lb = a.lab[t];
+    if (lb > 4) return -1;
+    if (lb == 0) return 0;
+    const int ov = a.L - a.step;
+    if (v.prev && j < ov) {   // also column j + step of the previous chunk
+        const int64_t u = t - a.L + a.step;
+        if (a.pos[u] == p && a.idx[u] == x && !dec_str_gt(v.c, v.cprev)) return 0;
+    }
+    if (v.next && j >= a.step) {   // also column j - step of the next chunk
+        const int64_t u = t + a.L - a.step;
+        if (a.pos[u] == p && a.idx[u] == x && !dec_str_gt(v.c, v.cnext)) return 0;
+    }
+    return lb;
+}
+
+// exclusive block scan; *total gets the block's sum. NT threads, NT/64 waves.
+template <int NT, typename T>
+__device__ inline T block_excl_scan(T v, T* lds, T* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    T x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const T y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    if (lane == 63) lds[w] = x;
+    __syncthreads();
+    T off = 0, sum = 0;
+#pragma unroll
+    for (int i = 0; i < NT / 64; i++) {
+        off += i < w ? lds[i] : 0;
+        sum += lds[i];
+    }
+    __syncthreads();   // lds may be reused by the caller's next scan
+    *total = sum;
+    return off + x - v;
+}
+
+// one block per chunk: bases the chunk contributes, and whether it breaks the layout or holds a poisoned label
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_count(StitchArgs a) {
+    __shared__ int32_t lds[ST_THREADS / 64];
+    const int64_t k = blockIdx.x;
+    const bool ordered = chunk_in_order(a, k);
+    int n = 0, bad = 0;
+    if (ordered) {
+        const ChunkView v = chunk_view(a, k);
+        const int j0 = threadIdx.x * a.cpt, j1 = min(a.L, j0 + a.cpt);
+        for (int j = j0; j < j1; j++) {
+            const int lb = column_label(a, v, j);
+            n += lb > 0;
+            bad |= lb < 0;
+        }
+    }
+    int32_t total, nbad;
+    block_excl_scan<ST_THREADS, int32_t>(n, lds, &total);
+    block_excl_scan<ST_THREADS, int32_t>(bad, lds, &nbad);
+    if (threadIdx.x == 0) {
+        a.chunk_cnt[k] = total;
+        a.chunk_bad[k] = !ordered ? BAD_ORDER : (nbad ? BAD_LABEL : BAD_NONE);
+    }
+}
+
+// one block: chunk offsets, region offsets, total, status and the first bad chunk
+__global__ __launch_bounds__(ST_SCAN_THREADS) void k_stitch_scan(StitchArgs a) {
+    __shared__ int64_t lds[ST_SCAN_THREADS / 64];
+    const int64_t n = a.n_chunks;
+    const int64_t per = (n + ST_SCAN_THREADS - 1) / ST_SCAN_THREADS;
+    const int64_t k0 = min<int64_t>(n, threadIdx.x * per), k1 = min<int64_t>(n, k0 + per);
+    int64_t s = 0, first_bad = INT64_MAX, bad_kind = BAD_NONE, n_unordered = 0;
+    for (int64_t k = k0; k < k1; k++) {
+        s += a.chunk_cnt[k];
+        n_unordered += a.chunk_bad[k] == BAD_ORDER;
+        if (a.chunk_bad[k] != BAD_NONE && first_bad == INT64_MAX) { first_bad = k; bad_kind = a.chunk_bad[k]; }
+    }
+    int64_t total, any_unordered;
+    int64_t off = block_excl_scan<ST_SCAN_THREADS, int64_t>(s, lds, &total);
+    block_excl_scan<ST_SCAN_THREADS, int64_t>(n_unordered, lds, &any_unordered);
+    // first bad chunk: the segments are in chunk order, so the first thread with one holds it
+    int64_t nbad_before, nbad;
+    nbad_before = block_excl_scan<ST_SCAN_THREADS, int64_t>(first_bad != INT64_MAX ? 1 : 0, lds, &nbad);
+    __shared__ int64_t s_bad[2];
+    if (nbad == 0 && threadIdx.x == 0) { s_bad[0] = -1; s_bad[1] = BAD_NONE; }
+    if (first_bad != INT64_MAX && nbad_before == 0) { s_bad[0] = first_bad; s_bad[1] = bad_kind; }
+    __syncthreads();
+    const int64_t bad_chunk = s_bad[0], kind = s_bad[1];
+    const int64_t status = kind == BAD_ORDER ? PV_ERR_INVALID : kind == BAD_LABEL ? PV_ERR_STATE
+                   : total > a.cap ? PV_ERR_CAPACITY : PV_OK;
+    for (int64_t k = k0; k < k1; k++) {
+        a.chunk_off[k] = off;
+        if (!any_unordered) {   // (region ids are only known to be in range then)
+            // region g's bases start at its first chunk; regions without chunks take the next one's offset
+            const int32_t g = a.region[k], pg = k > 0 ? a.region[k - 1] : -1;
+            for (int32_t r = pg + 1; r <= g; r++) a.region_off[r] = off;
+        }
+        off += a.chunk_cnt[k];
+    }
+    if (threadIdx.x == 0) {
+        if (!any_unordered) {
+            const int32_t g_last = n > 0 ? a.region[n - 1] : -1;
+            for (int32_t r = g_last + 1; r <= a.n_regions; r++) a.region_off[r] = total;
+        }
+        a.counts[0] = total;
+        a.counts[1] = status;
+        a.counts[2] = bad_chunk;
+        a.counts[3] = 0;
+    }
+}
+
+// one block per chunk: block-local ranks of the emitted columns, then one byte each
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_write(StitchArgs a) {
+    __shared__ int32_t lds[ST_THREADS / 64];
+    if (a.counts[1] != PV_OK) return;
+    const int64_t k = blockIdx.x;
+    const ChunkView v = chunk_view(a, k);
+    const int j0 = threadIdx.x * a.cpt, j1 = min(a.L, j0 + a.cpt);
+    uint8_t lbs[ST_MAX_CPT];
+    int n = 0;
+    for (int j = j0; j < j1; j++) {
+        const int lb = column_label(a, v, j);
+        lbs[j - j0] = (uint8_t)(lb > 0 ? lb : 0);
+        n += lb > 0;
+    }
+    int32_t total;
+    const int32_t r0 = block_excl_scan<ST_THREADS, int32_t>(n, lds, &total);
+    uint8_t* dst = a.seq + a.chunk_off[k] + r0;
+    for (int j = 0; j < j1 - j0; j++)
+        if (lbs[j]) *dst++ = "ACGT"[lbs[j] - 1];
+}
+
+}  // namespace
+
+extern "C" int pv_polish_stitch_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                                    const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap,
+                                    int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* d_counts, void* stream) {
+    PV_CHECK(ctx && chunks && region_off && d_counts, PV_ERR_INVALID, "null argument");
+    PV_CHECK(n_chunks >= 0 && n_regions >= 0 && seq_capacity >= 0, PV_ERR_INVALID, "negative sizes");
+    PV_CHECK(seq_length >= 1 && seq_length <= ST_THREADS * ST_MAX_CPT && seq_overlap >= 0 && seq_overlap < seq_length,
+             PV_ERR_INVALID, "stitch: need 1 <= seq_length <= %d and 0 <= seq_overlap < seq_length (got %d, %d)",
+             ST_THREADS * ST_MAX_CPT, seq_length, seq_overlap);
+    PV_CHECK(2 * seq_overlap <= seq_length, PV_ERR_INVALID, "stitch: a column may overlap one neighbour chunk only (overlap %d)",
+             seq_overlap);
+    PV_CHECK(n_chunks <= chunks->chunk_capacity, PV_ERR_INVALID, "n_chunks %lld exceeds the chunk capacity %lld",
+             (long long)n_chunks, (long long)chunks->chunk_capacity);
+    PV_CHECK(n_chunks < (1ll << 31), PV_ERR_LIMIT, "too many chunks for one launch");
+    PV_CHECK(n_chunks == 0 || (chunks->position && chunks->index && chunks->region && chunks->chunk_id && labels &&
+                               region_start && n_regions > 0),
+             PV_ERR_INVALID, "chunk arrays, labels or region starts missing");
+    PV_CHECK(seq_capacity == 0 || seq, PV_ERR_INVALID, "seq missing");
+    PV_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = pv_pick_stream(ctx, stream);
+    StitchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pos = chunks->position; a.idx = chunks->index; a.region = chunks->region; a.cid = chunks->chunk_id;
+    a.lab = labels; a.rstart = region_start;
+    a.n_chunks = n_chunks; a.n_regions = n_regions;
+    a.L = seq_length; a.step = seq_length - seq_overlap; a.cpt = (seq_length + ST_THREADS - 1) / ST_THREADS;
+    a.region_off = region_off; a.seq = seq; a.cap = seq_capacity; a.counts = d_counts;
+    const size_t nk = (size_t)(n_chunks > 0 ? n_chunks : 1);
+    int rc;
+    if ((rc = pv_get(ctx, "stitch.cnt", nk, &a.chunk_cnt))) return rc;
+    if ((rc = pv_get(ctx, "stitch.bad", nk, &a.chunk_bad))) return rc;
+    if ((rc = pv_get(ctx, "stitch.off", nk, &a.chunk_off))) return rc;
+    pv_prof_scope ps_all(ctx, "polish_stitch", st);
+    if (n_chunks > 0) { pv_prof_scope ps(ctx, "k_stitch_count", st); k_stitch_count<<<(unsigned)n_chunks, ST_THREADS, 0, st>>>(a); }
+    k_stitch_scan<<<1, ST_SCAN_THREADS, 0, st>>>(a);
+    if (n_chunks > 0) { pv_prof_scope ps(ctx, "k_stitch_write", st); k_stitch_write<<<(unsigned)n_chunks, ST_THREADS, 0, st>>>(a); }
+    PV_HIP(hipGetLastError());
+    return PV_OK;
+}
+
+template <typename T>
+static int stage(pv_ctx* ctx, const char* name, const T* src, size_t n, T** dst, hipStream_t st) {
+    int rc = pv_get(ctx, name, n > 0 ? n : 1, dst);
+    if (rc) return rc;
+    if (n > 0) PV_HIP(hipMemcpyAsync(*dst, src, n * sizeof(T), hipMemcpyHostToDevice, st));
+    return PV_OK;
+}
+
+extern "C" int pv_polish_stitch(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                                const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap,
+                                int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* counts) {
+    PV_CHECK(ctx && chunks && region_off && counts, PV_ERR_INVALID, "null argument");
+    PV_CHECK(n_chunks >= 0 && n_regions >= 0 && seq_capacity >= 0 && seq_length >= 1, PV_ERR_INVALID, "negative sizes");
+    PV_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t nc = (size_t)n_chunks, L = (size_t)seq_length;
+    pv_polish_out d;
+    memset(&d, 0, sizeof(d));
+    d.chunk_capacity = n_chunks;
+    const uint8_t* d_lab = nullptr;
+    const int64_t* d_rs = nullptr;
+    int64_t *d_roff = nullptr, *d_counts = nullptr;
+    uint8_t* d_seq = nullptr;
+    int rc;
+    if ((rc = stage(ctx, "st.position", chunks->position, nc * L, &d.position, st))) return rc;
+    if ((rc = stage(ctx, "st.index", chunks->index, nc * L, &d.index, st))) return rc;
+    if ((rc = stage(ctx, "st.region", chunks->region, nc, &d.region, st))) return rc;
+    if ((rc = stage(ctx, "st.chunk_id", chunks->chunk_id, nc, &d.chunk_id, st))) return rc;
+    if ((rc = stage(ctx, "st.labels", labels, nc * L, (uint8_t**)&d_lab, st))) return rc;
+    if ((rc = stage(ctx, "st.region_start", region_start, (size_t)n_regions, (int64_t**)&d_rs, st))) return rc;
+    if ((rc = pv_get(ctx, "st.region_off", (size_t)n_regions + 1, &d_roff))) return rc;
+    if ((rc = pv_get(ctx, "st.seq", (size_t)(seq_capacity > 0 ? seq_capacity : 1), &d_seq))) return rc;
+    if ((rc = pv_get(ctx, "st.counts", (size_t)4, &d_counts))) return rc;
+    rc = pv_polish_stitch_dev(ctx, &d, n_chunks, d_lab, d_rs, n_regions, seq_length, seq_overlap, d_roff, d_seq, seq_capacity,
+                              d_counts, st);
+    if (rc) return rc;
+    PV_HIP(hipMemcpyAsync(counts, d_counts, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    PV_HIP(hipMemcpyAsync(region_off, d_roff, ((size_t)n_regions + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    PV_HIP(hipStreamSynchronize(st));
+    const int64_t status = counts[1];
+    if (status == PV_ERR_CAPACITY) {
+        pv_set_error("stitch: seq capacity too small: need %lld bases", (long long)counts[0]);
+        return PV_ERR_CAPACITY;
+    }
+    PV_CHECK(status != PV_ERR_STATE, PV_ERR_STATE, "stitch: chunk %lld holds a label outside 0..4 (a poisoned network result)",
+             (long long)counts[2]);
+    PV_CHECK(status != PV_ERR_INVALID, PV_ERR_INVALID,
+             "stitch: chunk %lld breaks the layout (regions ascending, chunk ids 0,1,2,... inside a region)", (long long)counts[2]);
+    PV_CHECK(status == PV_OK, (int)status, "stitch: device status %lld", (long long)status);
+    if (counts[0] > 0) {
+        PV_HIP(hipMemcpyAsync(seq, d_seq, (size_t)counts[0], hipMemcpyDeviceToHost, st));
+        PV_HIP(hipStreamSynchronize(st));
+    }
+    return PV_OK;
+}

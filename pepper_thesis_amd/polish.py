@@ -1,0 +1,291 @@
+"""`polish`: BAM + draft FASTA -> polished FASTA, with every stage on the device.
+
+The reference's product (pepper/modules/python/polish.py:14-117) runs make_images -> call_consensus -> stitch through image and
+prediction HDF5 files. Here each batch of regions goes through
+
+  region_from_files (reader threads) -> pv_polish_summarize_regions_dev -> pv_rnn_forward_p2_dev -> pv_polish_stitch_dev
+
+without leaving HBM; only the region offsets and the polished bases (one byte per base) come back to the host.
+
+  python -m pepper_thesis_amd polish -b reads.bam -f draft.fa -m model.pkl -o out/polished [-t 5] [-r ctg:start-end] [--bf16]
+
+Semantics kept from the reference:
+  * regions: ImageGenerationUI.py:257-273 - for pos in range(start, end, 1000): [max(start, pos-100), min(end, pos+1100)],
+    the interval clamped to [0, contig_len-1] (polish_intervals);
+  * reads per region: polish_summary.region_from_files (a region without reads gives no chunks);
+  * stitch: Stitch.py:37-128 (pv_polish_stitch_dev, include/pepper_hip.h);
+  * output: perform_stitch.py:43-84 - one record per contig with a non-empty sequence, contigs in natural-key order, each
+    sequence on one line, at handle_output_directory(-o) + '_pepper_polished.fa' (ImageGenerationUI.py:68-80: -o is made a
+    directory, so `-o out/polished` writes `out/polished/_pepper_polished.fa`).
+-g and -w are accepted and ignored (there is no CPU path; no DataLoader); -d_ids picks the device (its first id). Several
+ranks (WORLD_SIZE > 1) are refused: multi-GPU polishing is not part of this build.
+"""
+import collections
+import concurrent.futures
+import itertools
+import os
+import re
+import sys
+import time
+from datetime import datetime
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+
+from . import _ffi
+
+MAX_SIZE = 1000            # ImageGenerationUI.py:249-252 (inference and training alike)
+MIN_IMAGE_OVERLAP = 100    # ImageSizeOptions.MIN_IMAGE_OVERLAP (pepper/modules/python/Options.py:10)
+HIDDEN_SIZE = 128          # the only polisher shape the kernels implement (TrainOptions, Options.py:19-20)
+GRU_LAYERS = 1
+
+
+def log(msg):
+    sys.stderr.write("[" + datetime.now().strftime("%m-%d-%Y %H:%M:%S") + "] INFO: " + msg + "\n")
+    sys.stderr.flush()
+
+
+def natural_key(s: str):
+    """perform_stitch.py:11-13"""
+    return [int(t) if t.isdigit() else t for t in re.split(r"(\d+)", s)]
+
+
+def polish_intervals(contig_len: int, start: Optional[int] = None, end: Optional[int] = None) -> List[Tuple[int, int]]:
+    """the regions of one contig (ImageGenerationUI.py:257-273); inclusive [start, end] pairs"""
+    if start is None:
+        a, b = 0, contig_len - 1
+    else:
+        a, b = max(0, int(start)), min(int(end), contig_len - 1)
+    return [(max(a, p - MIN_IMAGE_OVERLAP), min(b, p + MAX_SIZE + MIN_IMAGE_OVERLAP)) for p in range(a, b, MAX_SIZE)]
+
+
+def output_fasta_path(output_prefix: str) -> str:
+    """handle_output_directory (ImageGenerationUI.py:68-80) then perform_stitch.py:53; creates the directory"""
+    d = output_prefix if output_prefix.endswith("/") else output_prefix + "/"
+    os.makedirs(d, exist_ok=True)
+    return d + "_pepper_polished.fa"
+
+
+def load_polish_model(model_path: str) -> dict:
+    """the polisher checkpoint (ModelHander.py:80-110: torch.save dict with model_state_dict, hidden_size, gru_layers, keys
+    possibly 'module.'-prefixed) or an .npz of the state dict -> numpy state dict for Context.load_p2"""
+    if model_path.endswith(".npz"):
+        with np.load(model_path, allow_pickle=False) as z:
+            sd = {k: z[k] for k in z.files}
+        hidden, layers = HIDDEN_SIZE, GRU_LAYERS
+    else:
+        import torch
+        ckpt = torch.load(model_path, map_location="cpu", weights_only=True)
+        if isinstance(ckpt, dict) and "model_state_dict" in ckpt:
+            hidden, layers = int(ckpt.get("hidden_size", HIDDEN_SIZE)), int(ckpt.get("gru_layers", GRU_LAYERS))
+            sd = ckpt["model_state_dict"]
+        else:
+            hidden, layers, sd = HIDDEN_SIZE, GRU_LAYERS, ckpt
+        sd = {k: v.detach().cpu().numpy() for k, v in sd.items()}
+    if hidden != HIDDEN_SIZE or layers != GRU_LAYERS:
+        raise ValueError("polisher model with hidden_size=%d, gru_layers=%d: the kernels implement hidden_size=%d, gru_layers=%d only"
+                         % (hidden, layers, HIDDEN_SIZE, GRU_LAYERS))
+    sd = {(k[7:] if k.startswith("module.") else k): np.asarray(v, dtype=np.float32) for k, v in sd.items()}
+    shape = sd.get("gru_encoder.weight_hh_l0", np.zeros(0)).shape
+    if shape != (3 * HIDDEN_SIZE, HIDDEN_SIZE):
+        raise ValueError("polisher model: gru_encoder.weight_hh_l0 has shape %s, expected (%d, %d)" % (shape, 3 * HIDDEN_SIZE, HIDDEN_SIZE))
+    return sd
+
+
+def write_fasta(path: str, seqs: Dict[str, bytes]) -> None:
+    with open(path, "w") as fh:
+        for contig in sorted(seqs, key=natural_key):
+            if seqs[contig]:
+                fh.write(">" + contig + "\n" + seqs[contig].decode() + "\n")
+
+
+def _contig_list(fasta, bam, region: Optional[str]):
+    """[(contig, start|None, end|None)]: -r as make_images parses it, else the contigs common to the FASTA and the BAM"""
+    from .make_images import expand_region_names, parse_region
+    if region:
+        return [parse_region(p) for p in expand_region_names(region)]
+    in_bam = set(bam.get_chromosome_sequence_names())
+    common = [n for n in fasta.get_chromosome_names() if n in in_bam]
+    if not common:
+        raise ValueError("no contigs common to the BAM file and the FASTA file")
+    return [(n, None, None) for n in sorted(common, key=natural_key)]
+
+
+class _DeviceChain:
+    """device buffers of the builder -> GRU -> stitch chain, grown on demand"""
+
+    def __init__(self, ctx):
+        import torch
+        self.ctx, self.dev = ctx, "cuda:%d" % ctx.device_id
+        self.dout = self.labels = self.seq = None
+        self.counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
+
+    def _ensure(self, chunks: int):
+        import torch
+        from .device import DevicePolishOut
+        if self.dout is None or self.dout.capacity < chunks:
+            self.dout = DevicePolishOut(chunks, device=self.dev)
+            self.labels = torch.zeros((chunks, 1000), dtype=torch.uint8, device=self.dev)
+            self.seq = torch.zeros(chunks * 1000, dtype=torch.uint8, device=self.dev)
+            torch.cuda.synchronize()   # the fills ran on torch's stream; the chain runs on the context's
+
+    def _summarize(self, batch, db) -> int:
+        """builder on the device; -> n_chunks. A batch beyond the device form's workspace heuristics (PV_ERR_LIMIT: e.g. a
+        very long insert) runs the host form, which retries with measured bounds, and its chunks are uploaded."""
+        from .polish_summary import polish_summarize
+        cols = int((batch.ref_end - batch.ref_start + 1).sum())
+        want = (cols + cols // 2 + 1024) // 950 + 2 * batch.n_regions + 2
+        for _ in range(2):
+            self._ensure(want)
+            self.ctx.polish_summarize_dev(db, self.dout)
+            self.ctx.synchronize()
+            n, status = self.dout.n_chunks(), self.dout.status()
+            if status == _ffi.PV_ERR_LIMIT:
+                break
+            if status != _ffi.PV_OK:
+                raise _ffi.PepperHipError(status, "polisher image builder: device status %d" % status)
+            if n <= self.dout.capacity:
+                return n
+            want = n
+        import torch
+        out = polish_summarize(self.ctx, batch)
+        n = len(out.chunk_id)
+        self._ensure(n)
+        for name in ("images", "position", "index", "region", "chunk_id"):
+            getattr(self.dout, name)[:n].copy_(torch.from_numpy(getattr(out, name)))
+        return n
+
+    def run(self, batch) -> Tuple[np.ndarray, bytes]:
+        """one batch of regions -> (region_off [n_regions+1], polished bases of all its regions, concatenated)"""
+        from .device import DeviceBatch
+        db = DeviceBatch(batch, self.dev)
+        n = self._summarize(batch, db)
+        region_off = np.zeros(batch.n_regions + 1, np.int64)
+        if n == 0:
+            return region_off, b""
+        import torch
+        roff = torch.empty(batch.n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
+        self.ctx.forward_p2_dev(self.dout.images.data_ptr(), n, self.labels.data_ptr())
+        self.ctx.polish_stitch_dev(self.dout, n, self.labels.data_ptr(), db.t["ref_start"].data_ptr(), batch.n_regions,
+                                   roff.data_ptr(), self.seq.data_ptr(), self.seq.numel(), self.counts.data_ptr())
+        self.ctx.synchronize()   # raises if a split GRU form timed out (its labels are then poisoned)
+        total, status, bad = (int(v) for v in self.counts[:3].tolist())
+        if status != _ffi.PV_OK:   # capacity cannot run short: seq holds a byte for every column
+            raise _ffi.PepperHipError(status, "polisher stitch: device status %d (chunk %d)" % (status, bad))
+        return roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes()
+
+
+def _read_ahead(ex, fn, items, depth):
+    """fn(item) for every item on the executor's threads, results in order, at most `depth` in flight (bounded memory)"""
+    it = iter(items)
+    q = collections.deque(ex.submit(fn, x) for x in itertools.islice(it, depth))
+    while q:
+        f = q.popleft()
+        for x in itertools.islice(it, 1):
+            q.append(ex.submit(fn, x))
+        yield f.result()
+
+
+def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region: Optional[str] = None, batch_size: int = 2048,
+                 threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None) -> str:
+    """-> path of the polished FASTA. batch_size: chunks per device launch (a region of up to 1201 columns gives about two)."""
+    from .bamio import BamHandler, FastaHandler
+    from .batch import pack_regions
+    from .polish_summary import region_from_files
+    from .runtime import Context
+    t_start = time.perf_counter()
+    T = dict(read_s=0.0, device_s=0.0, regions=0, batches=0, bases_in=0, bases_out=0)
+    state_dict = load_polish_model(model_path)
+    own = ctx is None
+    ctx = ctx or Context(0)
+    ctx.load_p2(state_dict, dtype)
+    fa, bm = FastaHandler(fasta), BamHandler(bam)
+    work = []
+    for contig, s, e in _contig_list(fa, bm, region):
+        L = fa.get_chromosome_sequence_length(contig)
+        ivs = polish_intervals(L, s, e)
+        work += [(contig, a, b) for a, b in ivs]
+        T["bases_in"] += ivs[-1][1] - ivs[0][0] + 1 if ivs else 0   # draft bases covered (the regions overlap)
+    out_path = output_fasta_path(out_prefix)
+    log("POLISHING %d REGIONS, OUTPUT: %s" % (len(work), out_path))
+    # one reader per thread: the native BAM/FASTA handles are not shared between threads
+    import threading
+    local = threading.local()
+
+    def read(item):
+        if not hasattr(local, "h"):
+            local.h = (BamHandler(bam), FastaHandler(fasta))
+        return item, region_from_files(local.h[0], local.h[1], *item)
+
+    per_launch = max(1, int(batch_size) // 2)
+    pieces: Dict[str, List[Tuple[int, bytes]]] = {}
+    chain = _DeviceChain(ctx)
+
+    def flush(items):
+        t0 = time.perf_counter()
+        roff, seq = chain.run(pack_regions([r for _, r in items]))
+        for g, ((contig, a, _), _) in enumerate(items):
+            pieces.setdefault(contig, []).append((a, seq[roff[g]:roff[g + 1]]))
+        T["device_s"] += time.perf_counter() - t0
+        T["batches"] += 1
+
+    try:
+        with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, int(threads))) as ex:
+            pending = []
+            t0 = time.perf_counter()
+            for item, reg in _read_ahead(ex, read, work, 2 * per_launch):
+                if reg is None:
+                    continue
+                pending.append((item, reg))
+                T["regions"] += 1
+                if len(pending) == per_launch:
+                    T["read_s"] += time.perf_counter() - t0
+                    flush(pending)
+                    pending = []
+                    t0 = time.perf_counter()
+            T["read_s"] += time.perf_counter() - t0
+            if pending:
+                flush(pending)
+    finally:
+        if own:
+            ctx.close()
+    # regions in start order (create_consensus_sequence): their kept ranges are disjoint, so this is the reference's string
+    seqs = {c: b"".join(s for _, s in sorted(p, key=lambda t: t[0])) for c, p in pieces.items()}
+    write_fasta(out_path, seqs)
+    T["bases_out"] = sum(len(s) for s in seqs.values())
+    T["wall_s"] = time.perf_counter() - t_start
+    for c in sorted(seqs, key=natural_key):
+        log("FINISHED PROCESSING %s, POLISHED SEQUENCE LENGTH: %d." % (c, len(seqs[c])))
+    if timers is not None:
+        timers.update(T)
+    return out_path
+
+
+def run(args) -> int:
+    from . import cli
+    _, world, device = cli.rank_world_device(args)
+    if world > 1:
+        sys.stderr.write("ERROR: polish runs on one process (WORLD_SIZE=%d): multi-rank polishing is not part of this build.\n" % world)
+        return 2
+    for what, path in (("BAM", args.bam), ("FASTA", args.fasta), ("MODEL", args.model_path)):
+        if not os.path.isfile(path):
+            sys.stderr.write("ERROR: CAN NOT LOCATE %s FILE.\n" % what)
+            return 1
+    if args.threads <= 0 or args.batch_size <= 0:
+        sys.stderr.write("ERROR: THREADS AND batch_size NEED TO BE > 0.\n")
+        return 1
+    try:
+        load_polish_model(args.model_path)
+    except ValueError as e:
+        sys.stderr.write("ERROR: %s\n" % e)
+        return 2
+    from .runtime import Context
+    ctx = Context(device)
+    try:
+        T = {}
+        path = polish_fused(args.bam, args.fasta, args.model_path, args.output_file, args.region, args.batch_size, args.threads,
+                            _ffi.PV_DTYPE_BF16_INPUT_GEMM if args.bf16 else _ffi.PV_DTYPE_F32, ctx=ctx, timers=T)
+    finally:
+        ctx.close()
+    log("POLISHED FASTA: %s (%d REGIONS, %d BASES IN %.2f SEC)" % (path, T["regions"], T["bases_out"], T["wall_s"]))
+    return 0

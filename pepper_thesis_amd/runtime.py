@@ -280,6 +280,35 @@ class Context:
             self.handle, C.byref(dbatch.c), dbatch.n_reads, dbatch.n_bases, dbatch.n_cigar, dbatch.n_ref_bytes,
             dout.seq_length, dout.seq_overlap, C.byref(dout.c), dout.counts.data_ptr(), stream or None))
 
+    def polish_stitch_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_region_start: int, n_regions: int,
+                          d_region_off: int, d_seq: int, seq_capacity: int, d_counts: int, stream: int = 0):
+        """asynchronous, device-resident stitch (pv_polish_stitch_dev): the labels of dout's first n_chunks chunks -> polished
+        bases in d_seq, region offsets in d_region_off [n_regions+1], {bases, status, first bad chunk, 0} in d_counts."""
+        _ffi.check(self.lib.pv_polish_stitch_dev(
+            self.handle, C.byref(dout.c), int(n_chunks), d_labels, d_region_start, int(n_regions), dout.seq_length,
+            dout.seq_overlap, d_region_off, d_seq, int(seq_capacity), d_counts, stream or None))
+
+    def polish_stitch(self, out, labels: np.ndarray, region_start: np.ndarray, seq_capacity: int = None,
+                      seq_length: int = 1000, seq_overlap: int = 50):
+        """host-buffer stitch (pv_polish_stitch) of a PolishOut and its labels -> (region_off int64 [n_regions+1], seq bytes).
+        seq_capacity None: every column's worth; a smaller one raises PepperHipError(PV_ERR_CAPACITY)."""
+        n = int(len(out.chunk_id))
+        c = _ffi.pv_polish_out()
+        keep = [np.ascontiguousarray(out.position, np.int64), np.ascontiguousarray(out.index, np.int32),
+                np.ascontiguousarray(out.region, np.int32), np.ascontiguousarray(out.chunk_id, np.int32)]
+        c.chunk_capacity = n
+        c.position, c.index, c.region, c.chunk_id = (_ffi.ptr(a) for a in keep)
+        lab = np.ascontiguousarray(labels, np.uint8)
+        rs = np.ascontiguousarray(region_start, np.int64)
+        assert lab.shape == (n, seq_length), lab.shape
+        cap = n * seq_length if seq_capacity is None else int(seq_capacity)
+        region_off = np.zeros(len(rs) + 1, np.int64)
+        seq = np.zeros(max(cap, 1), np.uint8)
+        counts = (C.c_int64 * 4)()
+        _ffi.check(self.lib.pv_polish_stitch(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rs), len(rs), seq_length,
+                                             seq_overlap, _ffi.ptr(region_off), _ffi.ptr(seq), cap, counts))
+        return region_off, seq[:int(counts[0])].tobytes()
+
     def profile_begin(self, only: str = None):
         """bracket every kernel launch of this context with HIP events (only: just the kernels whose profile name starts
         with it - two events per launch put a few microseconds between kernels)"""
