@@ -245,6 +245,45 @@ int pv_polish_stitch(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks,
                      const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap,
                      int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* counts);
 
+/* The polisher's read realignment (AlignmentSummarizer.reads_to_reference_realignment, pepper/modules/python/
+ * AlignmentSummarizer.py:159-177 -> ReadAligner::align_reads_to_reference, simple_aligner.cpp:66-107): every read of a region
+ * is aligned to the draft with the reference's striped Smith-Waterman rules (match 4, mismatch 6, gap open 8, gap extend 2,
+ * local; ends and CIGAR ties exactly as ssw.c / ssw_cpp.cpp break them).
+ * in: the builder's batch, unchanged (ref_start, read_off, read_pos, base_off, bases, cigar_off, cigar are read);
+ * win_off [n_regions+1], win: region g's realignment window win[win_off[g] .. win_off[g+1]) = draft [ref_start, ref_end + 20),
+ * fewer bases at a contig end (AlingerOptions.ALIGNMENT_SAFE_BASES). It is kept apart from pv_batch_in.ref, whose length
+ * defines the builder's columns.
+ * Per read, in order: read_pos < ref_start: dropped (0 cigar words, state 2); empty query or read_pos at or past the window
+ * end: unchanged (state 0); otherwise aligned against window[read_pos - ref_start ..]: score > 1 gives state 1, pos =
+ * read_pos + ref_begin and the new cigar (S head, '=' and 'X' runs both written as MATCH and kept apart, I, D, S tail);
+ * score <= 1 leaves the read unchanged. Bytes other than A/C/G/T/U (either case) are N; bytes >= 128 too.
+ * The output with the input's bases, quals, flags and mapq is a realigned pv_batch_in for pv_polish_summarize_regions[_dev].
+ * Limits: a query of at most 16384 bases and a window of at most 2047 bases from the read's pos; the direction bytes of the
+ * traceback come from a bounded pool (option realign_scratch_kb, default 512 MB) that reads share in turn. A read beyond
+ * them is status PV_ERR_LIMIT; nothing is truncated. */
+typedef struct pv_realign_out {
+    int64_t cigar_capacity; /* in: words cigar can hold */
+    int64_t* read_pos;      /* [n_reads] new pos */
+    int64_t* cigar_off;     /* [n_reads+1] */
+    uint32_t* cigar;        /* [cigar_capacity] BAM packing */
+    int32_t* score;         /* [n_reads] SSW score (0 for dropped reads and empty queries) */
+    int32_t* ends;          /* [n_reads][4] ref_begin, ref_end, query_begin, query_end (0 unless realigned); ref_* count
+                             * from the read's pos */
+    uint8_t* state;         /* [n_reads] 0 unchanged, 1 realigned, 2 dropped */
+    int32_t* band;          /* optional (may be NULL) [n_reads]: banded_sw's final band width w of a realigned read, else 0 */
+    int64_t n_cigar;        /* out: cigar words produced (or needed on PV_ERR_CAPACITY) */
+    int64_t n_realigned;    /* out */
+    int64_t n_dropped;      /* out */
+} pv_realign_out;
+
+/* HOST buffers in and out (score, ends and state may be NULL). PV_ERR_CAPACITY: out->n_cigar holds the words needed. */
+int pv_polish_realign(pv_ctx* ctx, const pv_batch_in* in, const int64_t* win_off, const uint8_t* win, pv_realign_out* out);
+/* Device-resident, asynchronous form: every array is a DEVICE pointer; max_query_len bounds the longest read (it sizes the
+ * kernels' LDS); d_counts = {n_cigar, status, reads realigned, reads dropped}; status PV_OK, PV_ERR_CAPACITY (nothing but
+ * cigar_off and the per-read records written), PV_ERR_LIMIT or PV_ERR_STATE (a traceback left its band: never expected). */
+int pv_polish_realign_dev(pv_ctx* ctx, const pv_batch_in* in, int64_t n_reads, int64_t n_bases, int64_t max_query_len,
+                          const int64_t* win_off, const uint8_t* win, pv_realign_out* out, int64_t* d_counts, void* stream);
+
 /* ---- recurrent-network inference ------------------------------------------------------------ */
 
 #define PV_PLAN_P1_LSTM 1 /* pepper_variant: 2x bi-LSTM(256) + 5xLinear(512)/SELU + Linear(3) + softmax */
@@ -373,6 +412,7 @@ int pv_rnn_exchange_timeouts(pv_ctx* ctx);
  *   exchange_spin_log2              2..22 (default 18): bounded polls give up after 2^n tries
  *   debug_drop_part                 -1 (off) / 0..3: diagnostic, one part of every unit-split group never runs (tests force a
  *                                   time-out with it and see the poison)
+ *   realign_scratch_kb              1..4194304 (default 524288): the realigner's pool of traceback direction bytes, in KB
  * Unknown names and values outside these sets return PV_ERR_INVALID. */
 int pv_set_option(pv_ctx* ctx, const char* name, int value);
 int pv_get_option(pv_ctx* ctx, const char* name, int* value);

@@ -116,6 +116,22 @@ class pv_polish_out(C.Structure):
     ]
 
 
+class pv_realign_out(C.Structure):
+    _fields_ = [
+        ("cigar_capacity", C.c_int64),
+        ("read_pos", C.c_void_p),
+        ("cigar_off", C.c_void_p),
+        ("cigar", C.c_void_p),
+        ("score", C.c_void_p),
+        ("ends", C.c_void_p),
+        ("state", C.c_void_p),
+        ("band", C.c_void_p),
+        ("n_cigar", C.c_int64),
+        ("n_realigned", C.c_int64),
+        ("n_dropped", C.c_int64),
+    ]
+
+
 class pv_rnn_dir(C.Structure):
     _fields_ = [("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p)]
 
@@ -168,6 +184,10 @@ SYMBOLS = [
     ("pv_polish_stitch", C.c_int,
      [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
       C.c_int64, C.POINTER(C.c_int64)]),
+    ("pv_polish_realign", C.c_int, [C.c_void_p, C.POINTER(pv_batch_in), C.c_void_p, C.c_void_p, C.POINTER(pv_realign_out)]),
+    ("pv_polish_realign_dev", C.c_int,
+     [C.c_void_p, C.POINTER(pv_batch_in), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(pv_realign_out),
+      C.c_void_p, C.c_void_p]),
     ("pv_rnn_load_p1", C.c_int, [C.c_void_p, C.POINTER(pv_weights_p1), C.c_int]),
     ("pv_rnn_load_p2", C.c_int, [C.c_void_p, C.POINTER(pv_weights_p2), C.c_int]),
     ("pv_rnn_forward_p1", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -63,6 +63,7 @@ class Region:
     cand_start: Optional[int] = None
     cand_end: Optional[int] = None
     contig: str = "contig"
+    window: Optional[bytes] = None   # the realigner's draft window [ref_start, ref_end + 20) (polish --realign); not packed
 
 
 @dataclass

@@ -142,6 +142,9 @@ def polish_parser(ap=None):
     ap.add_argument("-w", "--num_workers", type=int, default=4, help="accepted and ignored")
     ap.add_argument("--bf16", action="store_true", default=False,
                     help="PV_DTYPE_BF16_INPUT_GEMM: matrix products on the bf16 MFMA with 3-term split operands")
+    ap.add_argument("--realign", action="store_true", default=False,
+                    help="realign every read to the draft (Smith-Waterman on the device) before the images are built; the "
+                         "reference always does this (AlignmentSummarizer realignment_flag=True). Off by default for now")
     return ap
 
 

@@ -110,6 +110,7 @@ struct pv_opts {
     int debug_drop_part = -1;    // diagnostic: this part of a unit-split launch never runs (forces exchange time-outs)
     int p1_bf16_min_batch = 513; // PV_DTYPE_BF16_INPUT_GEMM, P1: calls with fewer windows run the fp32 kernels (faster there: 0.85 ms against
                                  // 1.0 for 512 windows; results then are the fp32 mode's); 0: always the bf16x3 kernels
+    int realign_scratch_kb = 512 << 10; // bounded pool of the realigner's direction bytes (pv_polish_realign*), in KB
 };
 
 struct pv_ctx {

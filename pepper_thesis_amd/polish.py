@@ -3,16 +3,20 @@
 The reference's product (pepper/modules/python/polish.py:14-117) runs make_images -> call_consensus -> stitch through image and
 prediction HDF5 files. Here each batch of regions goes through
 
-  region_from_files (reader threads) -> pv_polish_summarize_regions_dev -> pv_rnn_forward_p2_dev -> pv_polish_stitch_dev
+  region_from_files (reader threads) [-> pv_polish_realign_dev] -> pv_polish_summarize_regions_dev -> pv_rnn_forward_p2_dev
+  -> pv_polish_stitch_dev
 
 without leaving HBM; only the region offsets and the polished bases (one byte per base) come back to the host.
 
   python -m pepper_thesis_amd polish -b reads.bam -f draft.fa -m model.pkl -o out/polished [-t 5] [-r ctg:start-end] [--bf16]
+      [--realign]
 
 Semantics kept from the reference:
   * regions: ImageGenerationUI.py:257-273 - for pos in range(start, end, 1000): [max(start, pos-100), min(end, pos+1100)],
     the interval clamped to [0, contig_len-1] (polish_intervals);
   * reads per region: polish_summary.region_from_files (a region without reads gives no chunks);
+  * --realign: every read realigned to draft [start, end + 20) first (AlignmentSummarizer.py:159-177, 327-331; the
+    reference always does it; off by default here for now);
   * stitch: Stitch.py:37-128 (pv_polish_stitch_dev, include/pepper_hip.h);
   * output: perform_stitch.py:43-84 - one record per contig with a non-empty sequence, contigs in natural-key order, each
     sequence on one line, at handle_output_directory(-o) + '_pepper_polished.fa' (ImageGenerationUI.py:68-80: -o is made a
@@ -118,6 +122,7 @@ class _DeviceChain:
         import torch
         self.ctx, self.dev = ctx, "cuda:%d" % ctx.device_id
         self.dout = self.labels = self.seq = None
+        self.rout = None
         self.counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
 
     def _ensure(self, chunks: int):
@@ -129,12 +134,14 @@ class _DeviceChain:
             self.seq = torch.zeros(chunks * 1000, dtype=torch.uint8, device=self.dev)
             torch.cuda.synchronize()   # the fills ran on torch's stream; the chain runs on the context's
 
-    def _summarize(self, batch, db) -> int:
+    def _summarize(self, batch, db, host_batch=None) -> int:
         """builder on the device; -> n_chunks. A batch beyond the device form's workspace heuristics (PV_ERR_LIMIT: e.g. a
-        very long insert) runs the host form, which retries with measured bounds, and its chunks are uploaded."""
+        very long insert) runs the host form, which retries with measured bounds, and its chunks are uploaded.
+        host_batch: makes the host batch when `batch` is None (the realigned reads live on the device only)."""
         from .polish_summary import polish_summarize
-        cols = int((batch.ref_end - batch.ref_start + 1).sum())
-        want = (cols + cols // 2 + 1024) // 950 + 2 * batch.n_regions + 2
+        b = batch if batch is not None else db.host
+        cols = int((b.ref_end - b.ref_start + 1).sum())
+        want = (cols + cols // 2 + 1024) // 950 + 2 * b.n_regions + 2
         for _ in range(2):
             self._ensure(want)
             self.ctx.polish_summarize_dev(db, self.dout)
@@ -148,18 +155,59 @@ class _DeviceChain:
                 return n
             want = n
         import torch
-        out = polish_summarize(self.ctx, batch)
+        out = polish_summarize(self.ctx, batch if batch is not None else host_batch())
         n = len(out.chunk_id)
         self._ensure(n)
         for name in ("images", "position", "index", "region", "chunk_id"):
             getattr(self.dout, name)[:n].copy_(torch.from_numpy(getattr(out, name)))
         return n
 
-    def run(self, batch) -> Tuple[np.ndarray, bytes]:
-        """one batch of regions -> (region_off [n_regions+1], polished bases of all its regions, concatenated)"""
+    def _realign(self, batch, db, windows):
+        """reads realigned to the draft on the device -> (host batch maker, device batch for the builder). The only read-back
+        is the counters (cigar total and status); the host batch is fetched only if the builder needs its host form."""
+        import torch
+        from .realign import DeviceRealignOut, RealignResult, device_windows, pack_windows, realigned_batch
+        woff, win = pack_windows(windows)
+        d_woff, d_win = device_windows(woff, win, self.dev)
+        qmax = int(np.diff(batch.base_off).max()) if batch.n_reads else 0
+        want = batch.n_cigar + 4 * batch.n_reads + batch.n_bases // 8 + 16
+        for _ in range(2):
+            if self.rout is None or self.rout.n_reads < batch.n_reads or self.rout.capacity < want:
+                self.rout = DeviceRealignOut(max(batch.n_reads, self.rout.n_reads if self.rout else 0), want, self.dev)
+                torch.cuda.synchronize()   # the fills ran on torch's stream; the chain runs on the context's
+            self.ctx.polish_realign_dev(db, d_woff.data_ptr(), d_win.data_ptr(), qmax, self.rout)
+            self.ctx.synchronize()
+            total, status, _, _ = (int(v) for v in self.rout.counts.tolist())
+            if status == _ffi.PV_ERR_CAPACITY:
+                want = total
+                continue
+            if status != _ffi.PV_OK:
+                raise _ffi.PepperHipError(status, "polisher realignment: device status %d" % status)
+            break
+        ro = self.rout
+        c = _ffi.pv_batch_in()
+        for f, _ in _ffi.pv_batch_in._fields_:
+            setattr(c, f, getattr(db.c, f))
+        c.read_pos, c.cigar_off, c.cigar = ro.read_pos.data_ptr(), ro.cigar_off.data_ptr(), ro.cigar.data_ptr()
+        rdb = _RealignedDeviceBatch(c, db, total, (d_woff, d_win))
+        n = batch.n_reads
+
+        def host():
+            res = RealignResult(ro.read_pos[:n].cpu().numpy(), ro.cigar_off[:n + 1].cpu().numpy(),
+                                ro.cigar[:total].cpu().numpy().view(np.uint32), None, None, None, 0, 0)
+            return realigned_batch(batch, res)
+        return host, rdb
+
+    def run(self, batch, windows=None) -> Tuple[np.ndarray, bytes]:
+        """one batch of regions -> (region_off [n_regions+1], polished bases of all its regions, concatenated).
+        windows: the realignment window of every region (polish --realign), else None."""
         from .device import DeviceBatch
         db = DeviceBatch(batch, self.dev)
-        n = self._summarize(batch, db)
+        if windows is not None:
+            host, db = self._realign(batch, db, windows)
+            n = self._summarize(None, db, host)
+        else:
+            n = self._summarize(batch, db)
         region_off = np.zeros(batch.n_regions + 1, np.int64)
         if n == 0:
             return region_off, b""
@@ -175,6 +223,16 @@ class _DeviceChain:
         return roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes()
 
 
+class _RealignedDeviceBatch:
+    """a DeviceBatch whose positions and cigars are the realigner's output (same bases, quals, flags, mapq, regions)"""
+
+    def __init__(self, c, db, n_cigar, keep):
+        self.c, self.host, self._keep = c, db.host, (db, keep)
+        self.n_reads, self.n_bases, self.n_cigar, self.n_ref_bytes = db.n_reads, db.n_bases, int(n_cigar), db.n_ref_bytes
+        self.max_region_len = db.max_region_len
+        self.t = db.t
+
+
 def _read_ahead(ex, fn, items, depth):
     """fn(item) for every item on the executor's threads, results in order, at most `depth` in flight (bounded memory)"""
     it = iter(items)
@@ -187,8 +245,10 @@ def _read_ahead(ex, fn, items, depth):
 
 
 def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region: Optional[str] = None, batch_size: int = 2048,
-                 threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None) -> str:
-    """-> path of the polished FASTA. batch_size: chunks per device launch (a region of up to 1201 columns gives about two)."""
+                 threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None,
+                 realign: bool = False) -> str:
+    """-> path of the polished FASTA. batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
+    realign: realign every read to the draft on the device before the builder, as the reference always does."""
     from .bamio import BamHandler, FastaHandler
     from .batch import pack_regions
     from .polish_summary import region_from_files
@@ -215,7 +275,7 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
     def read(item):
         if not hasattr(local, "h"):
             local.h = (BamHandler(bam), FastaHandler(fasta))
-        return item, region_from_files(local.h[0], local.h[1], *item)
+        return item, region_from_files(local.h[0], local.h[1], *item, realign=realign)
 
     per_launch = max(1, int(batch_size) // 2)
     pieces: Dict[str, List[Tuple[int, bytes]]] = {}
@@ -223,7 +283,8 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
 
     def flush(items):
         t0 = time.perf_counter()
-        roff, seq = chain.run(pack_regions([r for _, r in items]))
+        regs = [r for _, r in items]
+        roff, seq = chain.run(pack_regions(regs), [r.window for r in regs] if realign else None)
         for g, ((contig, a, _), _) in enumerate(items):
             pieces.setdefault(contig, []).append((a, seq[roff[g]:roff[g + 1]]))
         T["device_s"] += time.perf_counter() - t0
@@ -284,7 +345,8 @@ def run(args) -> int:
     try:
         T = {}
         path = polish_fused(args.bam, args.fasta, args.model_path, args.output_file, args.region, args.batch_size, args.threads,
-                            _ffi.PV_DTYPE_BF16_INPUT_GEMM if args.bf16 else _ffi.PV_DTYPE_F32, ctx=ctx, timers=T)
+                            _ffi.PV_DTYPE_BF16_INPUT_GEMM if args.bf16 else _ffi.PV_DTYPE_F32, ctx=ctx, timers=T,
+                            realign=bool(getattr(args, "realign", False)))
     finally:
         ctx.close()
     log("POLISHED FASTA: %s (%d REGIONS, %d BASES IN %.2f SEC)" % (path, T["regions"], T["bases_out"], T["wall_s"]))

@@ -144,11 +144,14 @@ def chunk_images(summary: SummaryGenerator, chunk_size: int = SEQ_LENGTH, chunk_
 MAX_READS_IN_REGION = 1500  # AlingerOptions.MAX_READS_IN_REGION (pepper/modules/python/Options.py:28)
 
 
-def region_from_files(bam, fasta, contig: str, start: int, end: int) -> Optional[Region]:
+def region_from_files(bam, fasta, contig: str, start: int, end: int, realign: bool = False) -> Optional[Region]:
     """The inference branch of the polisher's AlignmentSummarizer.create_summary up to the builder call
     (pepper/modules/python/AlignmentSummarizer.py:296-347): get_reads(contig, max(0, start), end, no supplementary, mapq 0,
-    baseq 0), reservoir sampling to 1500 reads with RandomState(2719747673), reference fetch [start, end]. The optional SSW
-    realignment (`realignment_flag`) is outside this path. None when the region has no reads (the reference returns empty lists)."""
+    baseq 0), reservoir sampling to 1500 reads with RandomState(2719747673), reference fetch [start, end]. None when the
+    region has no reads (the reference returns empty lists).
+    The reference's polisher then ALWAYS realigns the reads to the draft (create_summary's realignment_flag defaults to True,
+    :179, :327-331) before the builder. That step runs on the device (realign.py); realign=True also fetches its window,
+    draft [start, end + 20) (fewer bases at the contig end), into Region.window. The builder's inputs are the same either way."""
     from .make_images import downsample_indices
     reads = bam.get_reads(contig, max(0, int(start)), int(end), False, 0, 0)
     if not reads:
@@ -159,7 +162,12 @@ def region_from_files(bam, fasta, contig: str, start: int, end: int) -> Optional
     ref = fasta.get_reference_sequence(contig, int(start), int(end) + 1).encode()
     if len(ref) < R:
         ref = ref + b"N" * (R - len(ref))  # past the contig end: columns without reads; the polisher never reads the bytes
-    return Region(int(start), int(end), ref, reads, contig=contig)
+    region = Region(int(start), int(end), ref, reads, contig=contig)
+    if realign:
+        from .realign import SAFE_BASES
+        stop = min(int(end) + SAFE_BASES, fasta.get_chromosome_sequence_length(contig))
+        region.window = fasta.get_reference_sequence(contig, int(start), stop).encode()
+    return region
 
 
 def polish_regions(ctx, regions: Sequence[Region], want_acc: bool = False):

@@ -280,6 +280,18 @@ class Context:
             self.handle, C.byref(dbatch.c), dbatch.n_reads, dbatch.n_bases, dbatch.n_cigar, dbatch.n_ref_bytes,
             dout.seq_length, dout.seq_overlap, C.byref(dout.c), dout.counts.data_ptr(), stream or None))
 
+    def polish_realign(self, batch: RegionBatch, win_off: np.ndarray, win: np.ndarray, cigar_capacity: int = None):
+        """the polisher's read realignment (pv_polish_realign, host buffers) -> realign.RealignResult; see realign.py"""
+        from .realign import realign
+        return realign(self, batch, win_off, win, cigar_capacity)
+
+    def polish_realign_dev(self, dbatch: "DeviceBatch", d_win_off: int, d_win: int, max_query_len: int, dout, stream: int = 0):
+        """asynchronous, device-resident realignment (pv_polish_realign_dev) into a realign.DeviceRealignOut; counters
+        {n_cigar, status, realigned, dropped} in dout.counts"""
+        _ffi.check(self.lib.pv_polish_realign_dev(
+            self.handle, C.byref(dbatch.c), dbatch.n_reads, dbatch.n_bases, int(max_query_len), d_win_off, d_win,
+            C.byref(dout.c), dout.counts.data_ptr(), stream or None))
+
     def polish_stitch_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_region_start: int, n_regions: int,
                           d_region_off: int, d_seq: int, seq_capacity: int, d_counts: int, stream: int = 0):
         """asynchronous, device-resident stitch (pv_polish_stitch_dev): the labels of dout's first n_chunks chunks -> polished

@@ -1,0 +1,130 @@
+"""Host checker of the polisher's read realignment (pepper/modules/python/AlignmentSummarizer.py:159-177 ->
+ReadAligner::align_reads_to_reference over StripedSmithWaterman, match 4 / mismatch 6 / gap open 8 / gap extend 2).
+
+The dynamic programs are a scalar C restatement (tests/realign_ref.c), compiled here with the system C compiler into a
+temporary directory and called through ctypes: a per-cell Python loop would take minutes per 1.2 k x 1.2 k read. The read
+loop (window cut, drop / keep rules, op mapping) is restated here in Python.
+"""
+import ctypes as C
+import hashlib
+import os
+import subprocess
+import tempfile
+from dataclasses import dataclass
+from typing import List, Sequence
+
+import numpy as np
+
+SAFE_BASES = 20            # AlingerOptions.ALIGNMENT_SAFE_BASES (pepper/modules/python/Options.py:25)
+UNCHANGED, REALIGNED, DROPPED = 0, 1, 2
+_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "realign_ref.c")
+_lib = None
+
+
+def _load():
+    global _lib
+    if _lib is None:
+        with open(_SRC, "rb") as fh:
+            tag = hashlib.sha1(fh.read()).hexdigest()[:12]
+        so = os.path.join(tempfile.gettempdir(), "pv_realign_ref_%d_%s.so" % (os.getuid(), tag))
+        if not os.path.exists(so):
+            tmp = so + ".%d" % os.getpid()
+            subprocess.check_call([os.environ.get("CC", "gcc"), "-O2", "-shared", "-fPIC", "-o", tmp, _SRC])
+            os.replace(tmp, so)
+        lib = C.CDLL(so)
+        lib.rl_align.restype = C.c_int
+        lib.rl_align.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int]
+        _lib = lib
+    return _lib
+
+
+def align(window: bytes, query: bytes):
+    """one SSW alignment -> (score, ref_begin, ref_end, query_begin, query_end, cigar uint32 with '='/'X' as ops 7/8).
+    score <= 1: the ends and the cigar are not filled (zeros, empty)."""
+    lib = _load()
+    res = (C.c_int32 * 5)()
+    cap = len(query) + len(window) + 8
+    cig = (C.c_uint32 * cap)()
+    n = lib.rl_align(bytes(window), len(window), bytes(query), len(query), res, cig, cap)
+    if n < 0:
+        raise RuntimeError("realign_ref: rl_align returned %d" % n)
+    return tuple(int(v) for v in res) + (np.frombuffer(cig, dtype=np.uint32, count=n).copy(),)
+
+
+def to_read_cigar(cig: np.ndarray) -> np.ndarray:
+    """CigarOperationFromChar (simple_aligner.cpp): '=' and 'X' -> MATCH(0), runs kept apart; S, I, D keep their codes"""
+    c = np.asarray(cig, dtype=np.uint32).copy()
+    op = c & 15
+    c[(op == 7) | (op == 8)] &= ~np.uint32(15)
+    return c
+
+
+@dataclass
+class Record:
+    state: int
+    score: int = 0
+    ref_begin: int = 0
+    ref_end: int = 0
+    query_begin: int = 0
+    query_end: int = 0
+    new_pos: int = 0
+    cigar: np.ndarray = None   # read cigar (uint32, BAM packing) after realignment; the input's when unchanged
+
+
+def window(contig_seq: bytes, start: int, end: int) -> bytes:
+    """reference bases the realigner sees: FASTA[start, end + 20), fewer at the contig end"""
+    return bytes(contig_seq[int(start):min(len(contig_seq), int(end) + SAFE_BASES)])
+
+
+def realign_reads(start: int, win: bytes, reads: Sequence) -> List[Record]:
+    """ReadAligner::align_reads_to_reference on reads with .pos, .bases, .cigar; one record per input read, in order"""
+    out = []
+    for rd in reads:
+        pos = int(rd.pos)
+        if pos < int(start):
+            out.append(Record(DROPPED, new_pos=pos, cigar=np.zeros(0, np.uint32)))
+            continue
+        off = pos - int(start)
+        if off >= len(win) or len(rd.bases) == 0:
+            out.append(Record(UNCHANGED, new_pos=pos, cigar=np.asarray(rd.cigar, np.uint32)))
+            continue
+        sc, rb, re_, qb, qe, cig = align(win[off:], rd.bases)
+        if sc > 1:
+            out.append(Record(REALIGNED, sc, rb, re_, qb, qe, pos + rb, to_read_cigar(cig)))
+        else:
+            out.append(Record(UNCHANGED, sc, new_pos=pos, cigar=np.asarray(rd.cigar, np.uint32)))
+    return out
+
+
+def realigned_region(region, win: bytes):
+    """a batch.Region whose reads are realigned as the reference does it (dropped reads removed)"""
+    from pepper_thesis_amd.batch import Read, Region
+    recs = realign_reads(region.ref_start, win, region.reads)
+    reads = [Read(r.new_pos, r.cigar, rd.bases, rd.quals, rd.is_reverse, rd.mapq, rd.hp_tag)
+             for r, rd in zip(recs, region.reads) if r.state != DROPPED]
+    return Region(region.ref_start, region.ref_end, region.ref, reads, region.cand_start, region.cand_end, region.contig)
+
+
+def rescore(win: bytes, query: bytes, cigar: np.ndarray, ref_begin: int) -> (int, int, int):
+    """score of a read cigar against window[ref_begin:] with the SSW matrix -> (score, query bases consumed, ref span)"""
+    code = np.full(256, 4, np.int64)
+    for ch, v in zip(b"ACGTUacgtu", (0, 1, 2, 3, 0, 0, 1, 2, 3, 0)):
+        code[ch] = v
+    r, q = code[np.frombuffer(win, np.uint8)], code[np.frombuffer(query, np.uint8)]
+    s, qi, ri = 0, 0, ref_begin
+    for w in np.asarray(cigar, np.uint32).tolist():
+        op, n = w & 15, w >> 4
+        if op == 4:
+            qi += n
+        elif op == 1:
+            s -= 8 + 2 * (n - 1)
+            qi += n
+        elif op == 2:
+            s -= 8 + 2 * (n - 1)
+            ri += n
+        else:
+            a, b = r[ri:ri + n], q[qi:qi + n]
+            s += int(np.where((a == b) & (a < 4), 4, -6).sum())
+            qi += n
+            ri += n
+    return s, qi, ri - ref_begin

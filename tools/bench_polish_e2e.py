@@ -8,7 +8,11 @@
   e2e leg:    a synthetic contig (tools/bench_filepath.make_files: 60x, 10 kb reads) written as BAM + FASTA, then
               polish.polish_fused (readers -> builder -> bi-GRU -> stitch -> FASTA): wall time and draft Mbp/s.
 
-  python tools/bench_polish_e2e.py [--leg stitch|e2e|all] [--mbp 2.0] [--reps 20]
+  --realign: the e2e leg runs twice in one process on the same files, without and with `polish --realign`, then the
+              realigner alone on every region of the workload (launches of the chain's size), its kernels timed with HIP
+              events: forward + reverse DP cells, banded cells (score-only passes + the direction pass) and GCUPS.
+
+  python tools/bench_polish_e2e.py [--leg stitch|e2e|all] [--mbp 2.0] [--reps 20] [--realign]
 For the rocprofv3 row run the stitch leg alone under `rocprofv3 --kernel-trace --stats -d <dir> -- python ... --leg stitch`.
 """
 import argparse
@@ -96,7 +100,76 @@ def stitch_leg(reps=20):
                                      "stitch_ms": round(t_host * 1e3, 1)}}
 
 
-def e2e_leg(mbp=2.0, threads=16):
+def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info):
+    # warm-up on a small region (code objects, allocator), then the timed run
+    polish.polish_fused(bam, fa, model, out + "_warm", region="chr20:0-50000", threads=threads, ctx=ctx, realign=realign)
+    T = {}
+    t0 = time.perf_counter()
+    path = polish.polish_fused(bam, fa, model, out, threads=threads, ctx=ctx, timers=T, realign=realign)
+    wall = time.perf_counter() - t0
+    size = os.path.getsize(path)
+    return {"draft_bp": T["bases_in"], "reads": info["reads"], "regions": T["regions"], "batches": T["batches"],
+            "polished_bp": T["bases_out"], "fasta_bytes": size, "wall_s": round(wall, 3),
+            "read_s": round(T["read_s"], 3), "device_s": round(T["device_s"], 3),
+            "draft_mbp_per_s": round(T["bases_in"] / wall / 1e6, 4), "reader_threads": threads}
+
+
+def realign_stats(ctx, bam, fa, per_launch=1024):
+    """the realigner alone on every region of the workload: kernel time (HIP events) and cells"""
+    import numpy as np
+    from pepper_thesis_amd import bamio, polish, realign
+    from pepper_thesis_amd.batch import pack_regions
+    from pepper_thesis_amd.polish_summary import region_from_files
+    b, f = bamio.BamHandler(bam), bamio.FastaHandler(fa)
+    regs = []
+    for c in f.get_chromosome_names():
+        for s, e in polish.polish_intervals(f.get_chromosome_sequence_length(c)):
+            r = region_from_files(b, f, c, s, e, realign=True)
+            if r is not None:
+                regs.append(r)
+    ms, launches = {}, 0
+    fwd = rev = band = 0
+    n_reads = n_re = 0
+    for i in range(0, len(regs), per_launch):
+        part = regs[i:i + per_launch]
+        batch = pack_regions(part)
+        woff, win = realign.pack_windows([r.window for r in part])
+        ctx.profile_begin("k_rl")
+        res = ctx.polish_realign(batch, woff, win)
+        for k, (t, n) in ctx.profile_end().items():
+            ms[k] = ms.get(k, 0.0) + t
+        launches += 1
+        g = np.searchsorted(batch.read_off, np.arange(batch.n_reads), "right") - 1
+        off = batch.read_pos - batch.ref_start[g]
+        qlen = np.diff(batch.base_off)
+        wlen = woff[g + 1] - woff[g]
+        ok = (off >= 0) & (off < wlen) & (qlen > 0)
+        fwd += int((qlen[ok] * (wlen[ok] - off[ok])).sum())
+        m = res.state == 1
+        rb, re_, qb, qe = (res.ends[m, k].astype(np.int64) for k in range(4))
+        rev += int(((qe + 1) * (re_ + 1)).sum())   # the reverse sweep stops early: an upper bound
+        rs, qs, w = re_ - rb + 1, qe - qb + 1, res.band[m].astype(np.int64)
+        w0 = np.abs(rs - qs) + 1
+        while True:   # score-only passes w0, 2 w0, ..., w, then the direction pass at w
+            live = w0 <= w
+            if not live.any():
+                break
+            band += int((qs[live] * np.minimum(2 * w0[live] + 1, rs[live])).sum())
+            w0 = w0 * 2
+        band += int((qs * np.minimum(2 * w + 1, rs)).sum())
+        n_reads += batch.n_reads
+        n_re += res.n_realigned
+    score_ms = ms.get("k_rl_score_fwd", 0.0) + ms.get("k_rl_score_rev", 0.0)
+    band_ms = sum(v for k, v in ms.items() if k.startswith("k_rl_band"))
+    return {"regions": len(regs), "reads": n_reads, "realigned": n_re, "launches": launches,
+            "kernel_ms": {k: round(v, 3) for k, v in sorted(ms.items())},
+            "score_cells": {"forward": fwd, "reverse_upper_bound": rev},
+            "band_cells_upper_bound": band,
+            "score_gcups": round((fwd + rev) / (score_ms * 1e-3) / 1e9, 1) if score_ms else None,
+            "band_gcups": round(band / (band_ms * 1e-3) / 1e9, 1) if band_ms else None}
+
+
+def e2e_leg(mbp=2.0, threads=16, realign=False):
     import numpy as np
     from bench_filepath import make_files
     from pepper_thesis_amd import polish, runtime, synth
@@ -106,18 +179,19 @@ def e2e_leg(mbp=2.0, threads=16):
         model = os.path.join(d, "model.npz")
         np.savez(model, **synth.make_weights_p2(4321, 3.0))
         ctx = runtime.Context(0)
-        # warm-up on a small region (code objects, allocator), then the timed run
-        polish.polish_fused(bam, fa, model, os.path.join(d, "warm"), region="chr20:0-50000", threads=threads, ctx=ctx)
-        T = {}
-        t0 = time.perf_counter()
-        path = polish.polish_fused(bam, fa, model, os.path.join(d, "out"), threads=threads, ctx=ctx, timers=T)
-        wall = time.perf_counter() - t0
-        ctx.close()
-        size = os.path.getsize(path)
-        return {"draft_bp": T["bases_in"], "reads": info["reads"], "regions": T["regions"], "batches": T["batches"],
-                "polished_bp": T["bases_out"], "fasta_bytes": size, "wall_s": round(wall, 3),
-                "read_s": round(T["read_s"], 3), "device_s": round(T["device_s"], 3),
-                "draft_mbp_per_s": round(T["bases_in"] / wall / 1e6, 4), "reader_threads": threads}
+        try:
+            out = _e2e_run(polish, ctx, bam, fa, model, os.path.join(d, "out"), threads, False, info)
+            if not realign:
+                return out
+            res = {"without_realign": out,
+                   "with_realign": _e2e_run(polish, ctx, bam, fa, model, os.path.join(d, "out_rl"), threads, True, info)}
+            res["realign"] = st = realign_stats(ctx, bam, fa)
+            rl_s = sum(st["kernel_ms"].values()) / 1e3
+            res["realign"]["kernel_s"] = round(rl_s, 3)
+            res["realign"]["share_of_e2e_wall"] = round(rl_s / res["with_realign"]["wall_s"], 3)
+            return res
+        finally:
+            ctx.close()
     finally:
         shutil.rmtree(d, ignore_errors=True)
 
@@ -128,12 +202,13 @@ def main():
     ap.add_argument("--mbp", type=float, default=2.0)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--realign", action="store_true", help="e2e leg without and with polish --realign, plus realigner stats")
     a = ap.parse_args()
     out = {}
     if a.leg in ("stitch", "all"):
         out["stitch"] = stitch_leg(a.reps)
     if a.leg in ("e2e", "all"):
-        out["e2e"] = e2e_leg(a.mbp, a.threads)
+        out["e2e"] = e2e_leg(a.mbp, a.threads, a.realign)
     print(json.dumps(out, indent=1))
 
 
