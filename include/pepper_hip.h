@@ -289,7 +289,12 @@ int pv_polish_realign_dev(pv_ctx* ctx, const pv_batch_in* in, int64_t n_reads, i
 #define PV_PLAN_P1_LSTM 1 /* pepper_variant: 2x bi-LSTM(256) + 5xLinear(512)/SELU + Linear(3) + softmax */
 #define PV_PLAN_P2_GRU 2  /* pepper polisher: bi-GRU(128) encoder+decoder + Linear(256->5), sliding 100/50 over 1000 */
 
-#define PV_DTYPE_F32 0            /* every product in fp32 (f32 MFMA == fmaf chain) */
+/* PV_DTYPE_F32: fp32-accurate products. P1 calls below option p1_f32x6_min_batch (and every call with an explicit lstm_rows)
+ * run on the f32 MFMA (== an fmaf chain). Larger P1 calls run the split-6 chain: each fp32 operand is split into three bf16
+ * pieces (x = x0 + x1 + x2, exact) and a product is the six terms x0y0 + x0y1 + x1y0 + x1y1 + x0y2 + x2y0 on the bf16 MFMA
+ * with fp32 accumulation (dropped terms below 2^-24 relative; byte inputs are one exact piece, three terms); cell updates,
+ * biases, SELU and softmax stay fp32. Results then differ from the f32 MFMA form in the last bits (1e-6 on probabilities). */
+#define PV_DTYPE_F32 0
 #define PV_DTYPE_BF16_INPUT_GEMM 1 /* bf16 operands (fp32 accumulate) for the input-projection GEMMs only */
 
 /* Weights in PyTorch state_dict layout (row-major, fp32), i.e. exactly the tensors
@@ -376,6 +381,10 @@ int pv_gather_counts(pv_ctx* ctx, pv_comm* comm, int64_t n_rows, int64_t* counts
  * *ms (optional) receives the kernel's duration. Has no counterpart in the reference. */
 int pv_debug_gemm_bf16x3(pv_ctx* ctx, const float* A, const float* W, const float* bias, int64_t M, int N, int K,
                          int splits, int quads, float* C, float* ms);
+/* The same through the 6-term GEMM of the PV_DTYPE_F32 split-6 chain (fp32 operands split into three bf16 pieces on the device),
+ * same arguments and shape rules. */
+int pv_debug_gemm_bf16x6(pv_ctx* ctx, const float* A, const float* W, const float* bias, int64_t M, int N, int K,
+                         int splits, int quads, float* C, float* ms);
 
 /* Per-kernel timing for the benchmark's roofline leg: between pv_profile_begin and pv_profile_end every
  * kernel the context launches is bracketed by HIP events on its launch stream. pv_profile_end
@@ -407,6 +416,9 @@ int pv_rnn_exchange_timeouts(pv_ctx* ctx);
  *   gru_split     [PV_GRU_SPLIT]    1 / 0: allow the split GRU forms at all;   gru_usplit [PV_GRU_USPLIT] 1 / 0: the unit-split one
  *   p1_bf16_min_batch                 P1 in the PV_DTYPE_BF16_INPUT_GEMM mode: calls with fewer windows than this (default 513) run the
  *                                   fp32 kernels, which are faster there; 0 = always the bf16x3 kernels
+ *   p1_f32x6_min_batch [PV_P1_F32X6_MIN_BATCH]  P1 in the PV_DTYPE_F32 mode: calls of at least this many windows (1..16777216,
+ *                                   default 2048) and no explicit lstm_rows run the split-6 chain; smaller calls the f32 MFMA
+ *                                   kernels, bit for bit as before. 16777216 (above any batch) turns the chain off
  *   shared_device [PV_SHARED_DEVICE] 0 / 1: other streams or processes keep this GPU busy (e.g. several un-fused callers per
  *                                   GPU, RunInferenceArguments.py:67-74): never choose a form that needs co-resident workgroups
  *   exchange_spin_log2              2..22 (default 18): bounded polls give up after 2^n tries

@@ -54,6 +54,23 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
+// Split-6 operands (PV_DTYPE_F32, large P1 calls): eight fp32 values (lo = elements 0..3, hi = 4..7 of one bf16 MFMA fragment)
+// -> three bf16 pieces x = x0 + x1 + x2, each the round-to-nearest-even bf16 of what the pieces before it left over. The
+// residuals are exact (x - bf16(x) is representable), so the three 8-bit pieces carry all 24 bits of a normal fp32 value.
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void split3_bf16(const f32x4& lo, const f32x4& hi, bf16x8_t& x0, bf16x8_t& x1, bf16x8_t& x2) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const float v = j < 4 ? lo[j] : hi[j - 4];
+        const __bf16 p0 = (__bf16)v;
+        const float r1 = v - (float)p0;
+        const __bf16 p1 = (__bf16)r1;
+        x0[j] = p0;
+        x1[j] = p1;
+        x2[j] = (__bf16)(r1 - (float)p1);
+    }
+}
+
 template <int TR> struct Gate;
 template <> struct Gate<32> { f32x16 v; };      // lane -> unit lane&31, rows (e&3) + 8*(e>>2) + 4*(lane>>5), e = 0..15
 template <> struct Gate<16> { f32x4 v[2]; };    // lane -> unit 16*t + (lane&15), rows 4*(lane>>4) + i, e = 4t + i

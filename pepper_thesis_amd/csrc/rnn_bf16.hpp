@@ -18,6 +18,7 @@ struct pv_gemm_desc {
     int64_t M;
     int N, K, splits, quads;
     const char* prof_name;
+    int terms;   // 0 / 3: split8 operands, 3-term products; 6: plain fp32 operands, 6-term products (split in registers)
 };
 int pv_gemm_bf16x3_async(pv_ctx* ctx, const pv_gemm_desc& g, hipStream_t st);                       // rnn_kernels.hip
 int pv_gemm_bf16x3_prepare();                                                                       // function attributes (once per load)
@@ -50,11 +51,15 @@ struct pv_rec_desc {
                                // multiple of 16, mt unused)
     const unsigned char* dense_w;   // GRU decoder only: fragments of a [5][2 * hidden] dense layer (pv_pack_p2_dense) and ...
     float* dense_part;              // ... its partial logits [T][Bp / 32][2 dirs][4 waves][8][32 rows] (summed by k_p2_combine), or NULL
+    int x6;                    // LSTM only: the split-6 form (PV_DTYPE_F32 large calls): wp packed with pieces = 3, h and the outputs
+                               // out_tm / out_bm as fp32 rows [.][2 * hidden] instead of split8
 };
 int pv_rec_bf16_async(pv_ctx* ctx, const pv_rec_desc& d, hipStream_t st);
 int pv_rec_bf16_prepare();
 // dirs[2] (PyTorch layout) -> device fragment stream(s). kx = real input features (enc) or 0.
-int pv_pack_rec_bf16(const pv_rnn_dir* dirs, int cell, int kx, unsigned char** d_wp, unsigned char** d_wx, std::vector<void*>& owned);
+// pieces = 3 (LSTM only): slots of three bf16 pieces x0 | x1 | x2 (1 KB each, split3_bf16's rule) for the split-6 form
+int pv_pack_rec_bf16(const pv_rnn_dir* dirs, int cell, int kx, unsigned char** d_wp, unsigned char** d_wx, std::vector<void*>& owned,
+                     int pieces = 2);
 int pv_pack_gru16_bf16(const pv_rnn_dir* dirs, int kx, unsigned char** d_wp, unsigned char** d_wx, std::vector<void*>& owned);
 
 // ---- k_tail_bf16: the tail of the P1 head (sum of linear_1 slabs + bias + SELU, linear_2..5 + SELU, output layer, softmax) with

@@ -759,8 +759,8 @@ __global__ __launch_bounds__(256, 1) void k_head_tail(TailArgs a) {
 // G[b,t,:] = W_ih . enc_out[b,t,:] + b (both directions, N = 2048, K = 512) and for linear_1 (N = 512, K = 16896);
 // the recurrent h-part, the cell update and linear_2..5 stay fp32.
 struct GemmArgs {
-    const unsigned char* A;  // activations, split8 rows of K*4 bytes, [M][K]
-    const unsigned char* W;  // weights, split8 rows, [N][K]
+    const unsigned char* A;  // activations, split8 rows of K*4 bytes, [M][K] (k_gemm_bf16x6: fp32 rows)
+    const unsigned char* W;  // weights, split8 rows, [N][K] (k_gemm_bf16x6: fp32 rows)
     const float* bias;    // [N] or NULL
     float* C;             // [splits][M][N] row-major, or (c_quads) [M/4][N][4]: four consecutive rows of a column adjacent
     int64_t M;
@@ -794,7 +794,15 @@ __device__ unsigned long long g_gemm_stamps[8];
 #else
 #define GSTAMP(i)
 #endif
-__global__ __launch_bounds__(512, 2) void k_gemm_bf16x3(GemmArgs g) {
+// TERMS = 6 (k_gemm_bf16x6, PV_DTYPE_F32 split-6 chain): A and W are plain fp32 rows [M][K] / [N][K]. An fp32 8-group is 32
+// bytes like a split8 group, so the transfers and the LDS image are byte for byte those of the 3-term form: the "hi" image
+// holds elements 0..3 of every 8-group, the "lo" image elements 4..7. Each wave reads its 8 + 4 fragments as fp32, splits
+// them into three bf16 pieces in registers (split3_bf16) and runs six MFMAs per output tile: a0.b0 + a0.b1 + a1.b0 + a1.b1
+// + a0.b2 + a2.b0 (the dropped a1.b2, a2.b1, a2.b2 are below 2^-24 relative). The LDS image stays 128 KB; the cost of the
+// third piece is VALU work that issues between the MFMAs.
+template <int TERMS>
+__device__ __forceinline__ void gemm_body(const GemmArgs& g) {
+    static_assert(TERMS == 3 || TERMS == 6, "3-term (split8 operands) or 6-term (fp32 operands)");
     constexpr int BM = 256, BN = 256, BK = 32;
     constexpr int ARR = BM * BK * 2;          // bytes of one bf16 operand image (16 KB); buffer = [A_hi | A_lo | W_hi | W_lo]
     extern __shared__ __attribute__((aligned(16))) unsigned char smg[];
@@ -950,16 +958,29 @@ __global__ __launch_bounds__(512, 2) void k_gemm_bf16x3(GemmArgs g) {
             {
                 const unsigned ch16 = (unsigned)((((lane >> 4)) ^ (((lane & 15) >> 2) & 3)) * 16);
                 const unsigned fa16 = (unsigned)((128 * wr + (lane & 15)) * 64), fb16 = (unsigned)(2 * ARR + (64 * wc + (lane & 15)) * 64);
-                bf16x8 bh[4], bl[4];
+                // TERMS = 3: {hi, lo} pieces; TERMS = 6: {x0, x1, x2} split from the fp32 image
+                constexpr int NP = TERMS == 6 ? 3 : 2;
+                bf16x8 bp[NP][4];
 #pragma unroll
                 for (int ni = 0; ni < 4; ni++) {
-                    bh[ni] = *reinterpret_cast<const bf16x8*>(base + fb16 + ni * 16 * 64 + ch16);
-                    bl[ni] = *reinterpret_cast<const bf16x8*>(base + ARR + fb16 + ni * 16 * 64 + ch16);
+                    if constexpr (TERMS == 6) {
+                        split3_bf16(*reinterpret_cast<const f32x4*>(base + fb16 + ni * 16 * 64 + ch16),
+                                    *reinterpret_cast<const f32x4*>(base + ARR + fb16 + ni * 16 * 64 + ch16), bp[0][ni], bp[1][ni], bp[2][ni]);
+                    } else {
+                        bp[0][ni] = *reinterpret_cast<const bf16x8*>(base + fb16 + ni * 16 * 64 + ch16);
+                        bp[1][ni] = *reinterpret_cast<const bf16x8*>(base + ARR + fb16 + ni * 16 * 64 + ch16);
+                    }
                 }
 #pragma unroll
                 for (int mi = 0; mi < 8; mi++) {
-                    const bf16x8 ah = *reinterpret_cast<const bf16x8*>(base + fa16 + mi * 16 * 64 + ch16);
-                    const bf16x8 al = *reinterpret_cast<const bf16x8*>(base + ARR + fa16 + mi * 16 * 64 + ch16);
+                    bf16x8 ap[NP];
+                    if constexpr (TERMS == 6) {
+                        split3_bf16(*reinterpret_cast<const f32x4*>(base + fa16 + mi * 16 * 64 + ch16),
+                                    *reinterpret_cast<const f32x4*>(base + ARR + fa16 + mi * 16 * 64 + ch16), ap[0], ap[1], ap[2]);
+                    } else {
+                        ap[0] = *reinterpret_cast<const bf16x8*>(base + fa16 + mi * 16 * 64 + ch16);
+                        ap[1] = *reinterpret_cast<const bf16x8*>(base + ARR + fa16 + mi * 16 * 64 + ch16);
+                    }
                     if (issue && mi < 4) {   // two pieces in front of each of the first four blocks
                         dma_piece(S, s_kt, buf ^ 1, 2 * mi);
                         dma_piece(S, s_kt, buf ^ 1, 2 * mi + 1);
@@ -970,9 +991,14 @@ __global__ __launch_bounds__(512, 2) void k_gemm_bf16x3(GemmArgs g) {
                     }
 #pragma unroll
                     for (int ni = 0; ni < 4; ni++) {
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[ni], acc[mi][ni], 0, 0, 0);
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[ni], acc[mi][ni], 0, 0, 0);
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[ni], acc[mi][ni], 0, 0, 0);
+                        if constexpr (TERMS == 6) {   // the small terms first
+                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[2], bp[0][ni], acc[mi][ni], 0, 0, 0);
+                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[2][ni], acc[mi][ni], 0, 0, 0);
+                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[1], bp[1][ni], acc[mi][ni], 0, 0, 0);
+                        }
+                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[0][ni], acc[mi][ni], 0, 0, 0);
+                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[1][ni], acc[mi][ni], 0, 0, 0);
+                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[1], bp[0][ni], acc[mi][ni], 0, 0, 0);
                     }
                 }
             }
@@ -1039,6 +1065,10 @@ __global__ __launch_bounds__(512, 2) void k_gemm_bf16x3(GemmArgs g) {
         for (int i = 0; i < 8; i++) atomicAdd(&g_gemm_stamps[i], gs_acc[i]);
 #endif
 }
+
+// (two kernels over one body: a __launch_bounds__(512, 2) kernel template loses its host stub in this compiler)
+__global__ __launch_bounds__(512, 2) void k_gemm_bf16x3(GemmArgs g) { gemm_body<3>(g); }
+__global__ __launch_bounds__(512, 2) void k_gemm_bf16x6(GemmArgs g) { gemm_body<6>(g); }
 
 // ---- host-side weight packing -----------------------------------------------------------------------
 // LSTM layer, 8 waves per workgroup, wave w owns hidden units [32w, 32w+32) of the gates i,f,g,o (nt).
@@ -1143,6 +1173,10 @@ struct pv_rnn_p1 {
     unsigned char* w1_s = nullptr;
     unsigned char* enc_rb = nullptr; unsigned char* dec_rb = nullptr;    // bf16 fragment streams of k_rec_bf16 (encoder: W_ih | W_hh; decoder: W_hh)
     unsigned char* tail_wb = nullptr;                                    // bf16 fragment stream of k_tail_bf16 (linear_2..5)
+    // PV_DTYPE_F32, split-6 chain: three-piece fragment streams of k_rec_bf16<X6> and the fp32 operands of k_gemm_bf16x6
+    unsigned char* enc_r6 = nullptr; unsigned char* dec_r6 = nullptr;
+    float* dec_wih_f = nullptr;   // decoder W_ih of both directions [2048][512] (biases: dec_bias_cat)
+    float* w1_f = nullptr;        // linear_1 [512][16896]
     std::vector<void*> owned;
 };
 
@@ -1260,14 +1294,21 @@ extern "C" int pv_rnn_load_p1(pv_ctx* ctx, const pv_weights_p1* w, int dtype) {
         if ((rc = dev_upload(w->linear_b[i + 1], HEAD_N, &m->bl[i], m->owned))) return rc;
     }
     if ((rc = dev_upload(w->out_w, 3 * HEAD_N, &m->wo, m->owned)) || (rc = dev_upload(w->out_b, 3, &m->bo, m->owned))) return rc;
+    std::vector<float> wcat((size_t)2048 * 512), bcat(2048);   // decoder W_ih of both directions, b_ih + b_hh
+    for (int d = 0; d < 2; d++) {
+        memcpy(&wcat[(size_t)d * 1024 * 512], w->decoder[d].w_ih, (size_t)1024 * 512 * sizeof(float));
+        for (int n = 0; n < 1024; n++) bcat[d * 1024 + n] = w->decoder[d].b_ih[n] + w->decoder[d].b_hh[n];
+    }
+    if ((rc = dev_upload(bcat, &m->dec_bias_cat, m->owned))) return rc;
+    if (dtype == PV_DTYPE_F32) {   // the split-6 chain of large calls: 3.4 + 3.4 MB of fragments, 4 + 34.6 MB of fp32 weights
+        if ((rc = pv_pack_rec_bf16(w->encoder, 4, F_IN, &m->enc_r6, nullptr, m->owned, 3))) return rc;
+        if ((rc = pv_pack_rec_bf16(w->decoder, 4, 0, &m->dec_r6, nullptr, m->owned, 3))) return rc;
+        if ((rc = dev_upload(wcat, &m->dec_wih_f, m->owned))) return rc;
+        if ((rc = dev_upload(w->linear_w[0], (size_t)HEAD_N * HEAD_K, &m->w1_f, m->owned))) return rc;
+        if ((rc = pv_gemm_bf16x3_prepare()) || (rc = pv_rec_bf16_prepare())) return rc;
+    }
     if (dtype == PV_DTYPE_BF16_INPUT_GEMM) {
-        std::vector<float> wcat((size_t)2048 * 512), bcat(2048);
-        for (int d = 0; d < 2; d++) {
-            memcpy(&wcat[(size_t)d * 1024 * 512], w->decoder[d].w_ih, (size_t)1024 * 512 * sizeof(float));
-            for (int n = 0; n < 1024; n++) bcat[d * 1024 + n] = w->decoder[d].b_ih[n] + w->decoder[d].b_hh[n];
-        }
         if ((rc = dev_upload_split(wcat.data(), 2048, 512, &m->dec_wih_s, m->owned))) return rc;
-        if ((rc = dev_upload(bcat, &m->dec_bias_cat, m->owned))) return rc;
         if ((rc = dev_upload_split(w->linear_w[0], HEAD_N, HEAD_K, &m->w1_s, m->owned))) return rc;
         if ((rc = pv_pack_rec_bf16(w->encoder, 4, F_IN, &m->enc_rb, nullptr, m->owned))) return rc;
         if ((rc = pv_pack_rec_bf16(w->decoder, 4, 0, &m->dec_rb, nullptr, m->owned))) return rc;
@@ -1300,9 +1341,68 @@ static void launch_tail(pv_ctx* ctx, pv_rnn_p1* m, TailArgs& t, int n_tiles32, h
     else k_head_tail<16><<<(unsigned)(2 * n_tiles32), 256, lds_tail<16>(), st>>>(t);
 }
 
+// PV_DTYPE_F32 calls that take the split-6 chain: large enough (option p1_f32x6_min_batch) and no tile form forced
+static bool p1_use_x6(const pv_ctx* ctx, int64_t B) {
+    return ctx->p1->dtype == PV_DTYPE_F32 && !ctx->opt.lstm_rows && B >= ctx->opt.p1_f32x6_min_batch;
+}
+
+// The split-6 chain (PV_DTYPE_F32, large calls): every matrix product of the RNN on the bf16 MFMA as six terms of three-piece
+// operands (fp32-class: the dropped terms are below 2^-24 relative), fp32 accumulation, fp32 cell updates, fp32 tail.
+//   encoder   k_rec_bf16<LSTM, enc, X6>: byte x-part (3 terms) + h-part (6 terms) per step -> fp32 rows, time-major
+//   decoder   k_gemm_bf16x6 (G = enc . W_ih^T + b, quads) + k_rec_bf16<LSTM, dec, X6> on G -> fp32 rows, batch-major (dec_out)
+//   head      linear_1 as a split-K k_gemm_bf16x6 -> k_head_tail (sum of slabs, linear_2..5, output layer, softmax in fp32)
+// The decoder's two launches form ONE profile scope "k_lstm_layer_dec" (the fp32 chain's fused decoder kernel), so per-layer
+// figures compare across the two chains; the launches inside carry names outside that prefix.
+static int p1_forward_x6(pv_ctx* ctx, const int8_t* d_images, int64_t B, float* d_probs, float* enc_out, float* dec_out, float* part,
+                         hipStream_t st, bool taps) {
+    pv_rnn_p1* m = ctx->p1;
+    const int n_tiles = (int)((B + ROWS - 1) / ROWS);
+    const int64_t Bp = (int64_t)n_tiles * ROWS, M = Bp * T_STEPS;
+    float *enc_tm = nullptr, *G = nullptr;
+    int rc;
+    if ((rc = pv_get(ctx, "p1.enc_tm", (size_t)M * 2 * H, &enc_tm)) || (rc = pv_get(ctx, "p1.G", (size_t)M * 2048, &G))) return rc;
+    pv_rec_desc re = {};
+    re.cell = 4; re.enc = 1; re.wp = m->enc_r6; re.bias = m->enc_bias; re.x = d_images; re.x_row_bytes = PV_WINDOW_BYTES; re.x_t0 = 0;
+    re.xf = F_IN; re.x_signed = 1; re.B = B; re.Bp = Bp; re.T = T_STEPS; re.out_tm = reinterpret_cast<unsigned char*>(enc_tm);
+    re.out_f32 = taps ? enc_out : nullptr; re.mt = 1; re.x6 = 1; re.prof_name = "k_rec_x6_lstm_enc";
+    if ((rc = pv_rec_bf16_async(ctx, re, st))) return rc;
+    {
+        pv_prof_scope ps(ctx, "k_lstm_layer_dec", st);
+        pv_gemm_desc ga = {};
+        ga.A = reinterpret_cast<const unsigned char*>(enc_tm); ga.W = reinterpret_cast<const unsigned char*>(m->dec_wih_f);
+        ga.bias = m->dec_bias_cat; ga.C = G; ga.M = M; ga.N = 2048; ga.K = 2 * H; ga.splits = 1; ga.quads = 1; ga.terms = 6;
+        ga.prof_name = "k_gemm_bf16x6_dec";
+        if ((rc = pv_gemm_bf16x3_async(ctx, ga, st))) return rc;
+        pv_rec_desc rd = {};
+        rd.cell = 4; rd.enc = 0; rd.G = G; rd.wp = m->dec_r6; rd.B = B; rd.Bp = Bp; rd.T = T_STEPS;
+        rd.out_bm = reinterpret_cast<unsigned char*>(dec_out);   // fp32 [Bp][T][2H]: the head's operand and the decoder tap
+        rd.mt = 1; rd.x6 = 1; rd.prof_name = "k_rec_x6_lstm_dec";
+        if ((rc = pv_rec_bf16_async(ctx, rd, st))) return rc;
+    }
+    // linear_1 (K = 16896) as a split-K GEMM into slabs [splits][Bp][512]: at least the 11 slabs of k_head_splitk (shorter fp32
+    // accumulation chains: with 4 slabs of 4224 the probabilities drift 1.8e-6 from the f32 kernels), more while the work
+    // items do not fill the chip
+    static const int divs[] = {11, 12, 16, 22, 24, 33};
+    const int tiles = (int)((Bp + 255) / 256) * (HEAD_N / 256);
+    int gs = 33;
+    for (int dv : divs) if (tiles * dv >= ctx->num_cu) { gs = dv; break; }
+    pv_gemm_desc gl = {};
+    gl.A = reinterpret_cast<const unsigned char*>(dec_out); gl.W = reinterpret_cast<const unsigned char*>(m->w1_f); gl.bias = nullptr;
+    gl.C = part; gl.M = Bp; gl.N = HEAD_N; gl.K = HEAD_K; gl.splits = gs; gl.quads = 0; gl.terms = 6;
+    gl.prof_name = "k_gemm_bf16x6_lin1";
+    if ((rc = pv_gemm_bf16x3_async(ctx, gl, st))) return rc;
+    TailArgs tf;
+    tf.part = part; tf.b1 = m->b1; tf.splits = gs; tf.part_rows = Bp;
+    tf.wo = m->wo; tf.bo = m->bo; tf.probs = d_probs; tf.B = B; tf.epoch = m->sp_epoch; tf.err = m->sp_err;
+    launch_tail(ctx, m, tf, n_tiles, st);
+    PV_HIP(hipGetLastError());
+    return PV_OK;
+}
+
 static int p1_forward_launch(pv_ctx* ctx, const int8_t* d_images, int64_t B, float* d_probs, float* enc_out,
                              float* dec_out, float* part, hipStream_t st, bool taps = false) {
     pv_rnn_p1* m = ctx->p1;
+    if (p1_use_x6(ctx, B)) return p1_forward_x6(ctx, d_images, B, d_probs, enc_out, dec_out, part, st, taps);
     const int n_tiles = (int)((B + ROWS - 1) / ROWS);   // 32-row tiles: the granularity of every buffer and of the head
     // LSTM tile form: 32-row tiles once (tile, direction) workgroups fill the chip, else 16-row tiles: twice the workgroups,
     // half the MFMA cycles per time step (the bf16x3 mode has its own layer kernel, below)
@@ -1436,7 +1536,8 @@ extern "C" int pv_rnn_forward_p1_dev(pv_ctx* ctx, const int8_t* d_images, int64_
     PV_HIP(hipSetDevice(ctx->device));
     // the bf16x3 mode materialises the decoder's input projections (33 x 8 KB per window: 4.4 GB at 16384 windows): larger
     // batches run as chunks of P1_BF16_MAX_BATCH windows on the same stream
-    const int64_t chunk = ctx->p1->dtype == PV_DTYPE_BF16_INPUT_GEMM ? P1_BF16_MAX_BATCH : B;
+    // (and so does the split-6 chain of the fp32 mode)
+    const int64_t chunk = (ctx->p1->dtype == PV_DTYPE_BF16_INPUT_GEMM || p1_use_x6(ctx, B)) ? P1_BF16_MAX_BATCH : B;
     float *enc, *dec, *part;
     int rc = p1_workspace(ctx, std::min(B, chunk), &enc, &dec, &part);
     if (rc) return rc;
@@ -1453,8 +1554,8 @@ extern "C" int pv_rnn_forward_p1_debug(pv_ctx* ctx, const int8_t* images, int64_
     PV_CHECK(ctx->p1, PV_ERR_STATE, "pv_rnn_load_p1 has not been called on this context");
     PV_CHECK(B >= 0 && B < (1ll << 24), PV_ERR_INVALID, "batch %lld out of range", (long long)B);
     if (B == 0) return PV_OK;
-    if (ctx->p1->dtype == PV_DTYPE_BF16_INPUT_GEMM && B > P1_BF16_MAX_BATCH) {
-        // host-buffer form in the bf16x3 mode: chunks (the taps are per-window, so chunking does not change them)
+    if ((ctx->p1->dtype == PV_DTYPE_BF16_INPUT_GEMM || p1_use_x6(ctx, B)) && B > P1_BF16_MAX_BATCH) {
+        // host-buffer form in the bf16x3 mode and the split-6 chain: chunks (the taps are per-window, so chunking does not change them)
         for (int64_t b0 = 0; b0 < B; b0 += P1_BF16_MAX_BATCH) {
             const int64_t nb = std::min<int64_t>(P1_BF16_MAX_BATCH, B - b0);
             const size_t tap = (size_t)b0 * T_STEPS * 2 * H;
@@ -1527,14 +1628,16 @@ static const unsigned* gemm_iota() {
     return d;
 }
 
-static void gemm_launch(pv_ctx* ctx, GemmArgs& g, hipStream_t st) {
+static void gemm_launch(pv_ctx* ctx, GemmArgs& g, hipStream_t st, int terms = 3) {
     g.tiles_m = (int)((g.M + 255) / 256); g.tiles_n = g.N / 256; g.items = g.tiles_m * g.tiles_n * g.splits;
     const unsigned grid = (unsigned)(std::min((g.items + 7) / 8 * 8, (ctx->num_cu + 7) / 8 * 8));
-    k_gemm_bf16x3<<<grid, 512, LDS_GEMM, st>>>(g);
+    if (terms == 6) k_gemm_bf16x6<<<grid, 512, LDS_GEMM, st>>>(g);
+    else k_gemm_bf16x3<<<grid, 512, LDS_GEMM, st>>>(g);
 }
 
 int pv_gemm_bf16x3_prepare() {
     PV_HIP(hipFuncSetAttribute((const void*)k_gemm_bf16x3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_GEMM));
+    PV_HIP(hipFuncSetAttribute((const void*)k_gemm_bf16x6, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_GEMM));
     PV_CHECK(gemm_iota() != nullptr, PV_ERR_HIP, "allocation of the GEMM's flag table failed");
     return PV_OK;
 }
@@ -1545,14 +1648,14 @@ int pv_upload_split8(const float* w, size_t N, size_t K, unsigned char** d_split
 
 int pv_gemm_bf16x3_async(pv_ctx* ctx, const pv_gemm_desc& d, hipStream_t st) {
     PV_CHECK(d.A && d.W && d.C && d.M > 0 && d.M % 4 == 0 && d.N % 256 == 0 && d.splits >= 1 && d.K % (32 * d.splits) == 0 &&
-                 (!d.quads || d.splits == 1), PV_ERR_INVALID, "bad GEMM shape");
+                 (!d.quads || d.splits == 1) && (d.terms == 0 || d.terms == 3 || d.terms == 6), PV_ERR_INVALID, "bad GEMM shape");
     GemmArgs g;
     g.A = d.A; g.W = d.W; g.bias = d.bias; g.C = d.C; g.M = d.M; g.N = d.N; g.K = d.K; g.splits = d.splits;
     g.c_quads = d.quads;
     g.iota = gemm_iota();
     PV_CHECK(g.iota, PV_ERR_HIP, "GEMM flag table missing");
-    pv_prof_scope ps(ctx, d.prof_name ? d.prof_name : "k_gemm_bf16x3", st);
-    gemm_launch(ctx, g, st);
+    pv_prof_scope ps(ctx, d.prof_name ? d.prof_name : (d.terms == 6 ? "k_gemm_bf16x6" : "k_gemm_bf16x3"), st);
+    gemm_launch(ctx, g, st, d.terms == 6 ? 6 : 3);
     PV_HIP(hipGetLastError());
     return PV_OK;
 }
@@ -1560,8 +1663,8 @@ int pv_gemm_bf16x3_async(pv_ctx* ctx, const pv_gemm_desc& d, hipStream_t st) {
 // Diagnostic entry (tests, tuning): C = A . W^T + bias through k_gemm_bf16x3 alone. HOST pointers, fp32 row-major A [M,K],
 // W [N,K], bias [N] or NULL, C [splits][M][N] row-major (quads = 0) or [M/4][N][4] (quads = 1, splits must be 1).
 // M % 4 == 0, N % 256 == 0, K % (32 * splits) == 0. Returns the kernel time in ms through *ms when non-NULL.
-extern "C" int pv_debug_gemm_bf16x3(pv_ctx* ctx, const float* A, const float* W, const float* bias, int64_t M, int N, int K,
-                                    int splits, int quads, float* C, float* ms) {
+static int debug_gemm(pv_ctx* ctx, const float* A, const float* W, const float* bias, int64_t M, int N, int K, int splits, int quads,
+                      float* C, float* ms, int terms) {
     PV_CHECK(ctx && A && W && C, PV_ERR_INVALID, "null argument");
     PV_CHECK(M > 0 && M % 4 == 0 && N % 256 == 0 && splits >= 1 && K % (32 * splits) == 0 && (!quads || splits == 1), PV_ERR_INVALID, "bad GEMM shape");
     PV_HIP(hipSetDevice(ctx->device));
@@ -1570,7 +1673,15 @@ extern "C" int pv_debug_gemm_bf16x3(pv_ctx* ctx, const float* A, const float* W,
     float *dB = nullptr, *dC = nullptr;
     int rc;
     auto cleanup = [&]() { for (void* p : owned) (void)hipFree(p); };
-    if ((rc = dev_upload_split(A, (size_t)M, (size_t)K, &dA, owned)) || (rc = dev_upload_split(W, (size_t)N, (size_t)K, &dW, owned))) { cleanup(); return rc; }
+    if (terms == 6) {   // plain fp32 operands
+        float *fA = nullptr, *fW = nullptr;
+        if ((rc = dev_upload(A, (size_t)M * K, &fA, owned)) || (rc = dev_upload(W, (size_t)N * K, &fW, owned))) { cleanup(); return rc; }
+        dA = reinterpret_cast<unsigned char*>(fA);
+        dW = reinterpret_cast<unsigned char*>(fW);
+    } else if ((rc = dev_upload_split(A, (size_t)M, (size_t)K, &dA, owned)) || (rc = dev_upload_split(W, (size_t)N, (size_t)K, &dW, owned))) {
+        cleanup();
+        return rc;
+    }
     if (bias && (rc = dev_upload(bias, (size_t)N, &dB, owned))) { cleanup(); return rc; }
     const size_t nc = (size_t)splits * M * N;
     if (hipMalloc((void**)&dC, nc * sizeof(float)) != hipSuccess) { cleanup(); pv_set_error("hipMalloc failed"); return PV_ERR_HIP; }
@@ -1583,9 +1694,9 @@ extern "C" int pv_debug_gemm_bf16x3(pv_ctx* ctx, const float* A, const float* W,
     if (!g.iota) { cleanup(); pv_set_error("GEMM flag table missing"); return PV_ERR_HIP; }
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    gemm_launch(ctx, g, ctx->stream);   // warm
+    gemm_launch(ctx, g, ctx->stream, terms);   // warm
     (void)hipEventRecord(e0, ctx->stream);
-    gemm_launch(ctx, g, ctx->stream);
+    gemm_launch(ctx, g, ctx->stream, terms);
     (void)hipEventRecord(e1, ctx->stream);
     hipError_t er = hipStreamSynchronize(ctx->stream);
     float t = 0.f;
@@ -1596,6 +1707,16 @@ extern "C" int pv_debug_gemm_bf16x3(pv_ctx* ctx, const float* A, const float* W,
     cleanup();
     if (er != hipSuccess) { pv_set_error("GEMM failed: %s", hipGetErrorString(er)); return PV_ERR_HIP; }
     return PV_OK;
+}
+
+extern "C" int pv_debug_gemm_bf16x3(pv_ctx* ctx, const float* A, const float* W, const float* bias, int64_t M, int N, int K,
+                                    int splits, int quads, float* C, float* ms) {
+    return debug_gemm(ctx, A, W, bias, M, N, K, splits, quads, C, ms, 3);
+}
+// the same through the 6-term form (k_gemm_bf16x6: fp32 operands, split into three bf16 pieces in registers)
+extern "C" int pv_debug_gemm_bf16x6(pv_ctx* ctx, const float* A, const float* W, const float* bias, int64_t M, int N, int K,
+                                    int splits, int quads, float* C, float* ms) {
+    return debug_gemm(ctx, A, W, bias, M, N, K, splits, quads, C, ms, 6);
 }
 
 // ---- P2 (bi-GRU polisher model): see rnn_gru.hip ----------------------------------------------------

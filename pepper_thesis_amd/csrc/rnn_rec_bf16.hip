@@ -35,7 +35,7 @@ __device__ __forceinline__ float tanhf_(float x) {
 }
 __device__ __forceinline__ unsigned split8_off(unsigned k) { return (k >> 3) * 32u + (k & 7u) * 2u; }
 
-template <int NG, bool ENC, int MT = 1> struct RecCfg {
+template <int NG, bool ENC, int MT = 1, bool X6 = false> struct RecCfg {
     static constexpr int HID = NG == 4 ? 256 : 128;
     static constexpr int NW = HID / 32, NTHR = 64 * NW;
     static constexpr int KS_H = HID / 16;                       // k-steps (K = 16) of the recurrent product
@@ -49,7 +49,8 @@ template <int NG, bool ENC, int MT = 1> struct RecCfg {
     static constexpr int NSLOT = (XRES ? 0 : KS_X * NG) + KS_H * NG;   // (gate, k-step) slots of the weight stream per step
     // ring depth (NSLOT % D == 0): 8 register sets where they fit; 4 for the 64-row LSTM forms (128 accumulator + 32 state
     // registers of 256) and the GRU encoder (its x-part fragments stay resident)
-    static constexpr int D = ((NG == 3 && ENC) || (NG == 4 && MT == 2)) ? 4 : 8;   // (8 sets in the 64-row decoder: 14 spills, no faster)
+    // (8 sets in the 64-row decoder: 14 spills, no faster). Split-6 form: 4 sets of three pieces (8 spill in the 32-row encoder)
+    static constexpr int D = ((NG == 3 && ENC) || (NG == 4 && MT == 2) || X6) ? 4 : 8;
     static constexpr int NA = NG + ((NG == 3 && ENC) ? 1 : 0);  // accumulators per M-tile (GRU keeps the n gate's x-part apart)
     static constexpr int HS = HID * 4 + 16;                     // LDS row stride of the split8 h tile: (HS / 4) % 64 == 4
     static constexpr int XS = XK * 2 + 16;                      // LDS row stride of the bf16 x tile
@@ -81,24 +82,32 @@ struct RecArgs {
 // At = this lane's A-fragment address of M-tile 0, k-step 0; XP: x-part (plain bf16 rows, exact operand, two terms).
 // hook(i) runs behind the MFMAs of slot i (vector / LDS / store instructions of the caller that have nothing to do with the
 // product issue there while the matrix pipe works).
-template <int NG, int MT, int NA, int D, int NTOT, int I0, int NKS, bool XP, typename Hook>
+// X6 (split-6 chain of PV_DTYPE_F32): slots of three 1 KB pieces (x0 | x1 | x2); the h-part's A rows are fp32 (8 values = 32
+// bytes per lane and k-step, split into three pieces in registers) and take six terms, the exact x-part three.
+template <int NG, int MT, int NA, int D, int NTOT, int I0, int NKS, bool XP, bool X6 = false, typename Hook>
 __device__ __forceinline__ void ring_bf16(f32x16 (&acc)[MT][NA], const unsigned char* __restrict__ At, int m_stride,
-                                          __amdgpu_buffer_rsrc_t wr, f32x4 (&bq)[D][2], unsigned lane16, Hook&& hook) {
+                                          __amdgpu_buffer_rsrc_t wr, f32x4 (&bq)[D][X6 ? 3 : 2], unsigned lane16, Hook&& hook) {
     constexpr int KSB = XP ? 32 : 64;   // bytes of one k-step inside an A row
-    bf16x8 ah[MT], al[MT];
+    constexpr int NP = X6 ? 3 : 2, SB = NP * 1024;
+    bf16x8 ap[X6 && !XP ? 3 : 2][MT];
 #pragma unroll
     for (int i = 0; i < NKS * NG; i++) {
         {   // request slot i + D - 1 (wrapping into the next step's first slots: same weights every step)
             const int sv = (I0 + i + D - 1) % NTOT, rs = (I0 + i + D - 1) % D;
-            bq[rs][0] = buf_load4(wr, lane16, (unsigned)(sv * 2048));
-            bq[rs][1] = buf_load4(wr, lane16, (unsigned)(sv * 2048 + 1024));
+#pragma unroll
+            for (int p = 0; p < NP; p++) bq[rs][p] = buf_load4(wr, lane16, (unsigned)(sv * SB + p * 1024));
         }
         const int ks = i / NG, g = i % NG;
         if (g == 0) {
 #pragma unroll
             for (int m = 0; m < MT; m++) {
-                ah[m] = *reinterpret_cast<const bf16x8*>(At + m * m_stride + ks * KSB);
-                if (!XP) al[m] = *reinterpret_cast<const bf16x8*>(At + m * m_stride + ks * KSB + 16);
+                if constexpr (X6 && !XP) {
+                    split3_bf16(*reinterpret_cast<const f32x4*>(At + m * m_stride + ks * KSB),
+                                *reinterpret_cast<const f32x4*>(At + m * m_stride + ks * KSB + 16), ap[0][m], ap[1][m], ap[2][m]);
+                } else {
+                    ap[0][m] = *reinterpret_cast<const bf16x8*>(At + m * m_stride + ks * KSB);
+                    if (!XP) ap[1][m] = *reinterpret_cast<const bf16x8*>(At + m * m_stride + ks * KSB + 16);
+                }
             }
         }
         __builtin_amdgcn_sched_barrier(0);   // keep hipcc from sinking the prefetches next to their uses
@@ -108,9 +117,17 @@ __device__ __forceinline__ void ring_bf16(f32x16 (&acc)[MT][NA], const unsigned 
             const bf16x8 bh = __builtin_bit_cast(bf16x8, bq[rs][0]), bl = __builtin_bit_cast(bf16x8, bq[rs][1]);
 #pragma unroll
             for (int m = 0; m < MT; m++) {
-                acc[m][ai] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[m], bh, acc[m][ai], 0, 0, 0);
-                acc[m][ai] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[m], bl, acc[m][ai], 0, 0, 0);
-                if (!XP) acc[m][ai] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[m], bh, acc[m][ai], 0, 0, 0);
+                if constexpr (X6) {   // the small terms first
+                    const bf16x8 b2 = __builtin_bit_cast(bf16x8, bq[rs][2]);
+                    if constexpr (!XP) {
+                        acc[m][ai] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[2][m], bh, acc[m][ai], 0, 0, 0);
+                        acc[m][ai] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[1][m], bl, acc[m][ai], 0, 0, 0);
+                    }
+                    acc[m][ai] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[0][m], b2, acc[m][ai], 0, 0, 0);
+                }
+                acc[m][ai] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[0][m], bh, acc[m][ai], 0, 0, 0);
+                acc[m][ai] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[0][m], bl, acc[m][ai], 0, 0, 0);
+                if (!XP) acc[m][ai] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[1][m], bh, acc[m][ai], 0, 0, 0);
             }
         }
         hook(i);
@@ -129,9 +146,14 @@ __device__ unsigned long long g_rec_stamps[8];
 #define RSTAMP(i)
 #endif
 
-template <int NG, bool ENC, int MT>
+// X6: the LSTM of the split-6 chain (PV_DTYPE_F32): h_{t-1} lives in LDS as fp32 rows (the same 4 bytes per unit and the same
+// fragment addresses as split8: an fp32 8-group is 32 bytes too), the weight slots carry three pieces, the h-part takes six
+// terms and the byte x-part three (ring_bf16); the layer's outputs (the tile copies below) leave as fp32 rows.
+template <int NG, bool ENC, int MT, bool X6 = false>
 __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) {
-    typedef RecCfg<NG, ENC, MT> C;
+    static_assert(!X6 || NG == 4, "split-6 form: LSTM only");
+    typedef RecCfg<NG, ENC, MT, X6> C;
+    constexpr int NP = X6 ? 3 : 2, SB = NP * 1024;   // weight pieces, bytes of a stream slot
     constexpr int HID = C::HID, NW = C::NW, NTHR = C::NTHR, ROWS = 32 * MT, HS = C::HS, XS = C::XS, D = C::D, NA = C::NA;
     constexpr int NSLOT = C::NSLOT, NXS = C::XRES ? 0 : C::KS_X * NG;   // x slots at the head of the stream
     constexpr int NCOL = 2 * NG * HID;                                  // columns of a G row
@@ -147,9 +169,9 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
     const int64_t b0 = (int64_t)tile * ROWS;
     const int unit = 32 * wv + (lane & 31), rg = lane >> 5;
     const int T = a.T;
-    const __amdgpu_buffer_rsrc_t wr = make_rsrc(a.wp + (size_t)(dir * NW + wv) * NSLOT * 2048);
+    const __amdgpu_buffer_rsrc_t wr = make_rsrc(a.wp + (size_t)(dir * NW + wv) * NSLOT * SB);
     const unsigned lane16 = (unsigned)lane * 16u;
-    f32x4 bq[C::WRES ? 1 : D][2];
+    f32x4 bq[C::WRES ? 1 : D][NP];
     bf16x8 wres[C::WRES ? NSLOT : 1][2];
     if constexpr (C::WRES) {
 #pragma unroll
@@ -159,10 +181,9 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
         }
     } else {
 #pragma unroll
-        for (int k = 0; k < D - 1; k++) {
-            bq[k][0] = buf_load4(wr, lane16, (unsigned)(k * 2048));
-            bq[k][1] = buf_load4(wr, lane16, (unsigned)(k * 2048 + 1024));
-        }
+        for (int k = 0; k < D - 1; k++)
+#pragma unroll
+            for (int p = 0; p < NP; p++) bq[k][p] = buf_load4(wr, lane16, (unsigned)(k * SB + p * 1024));
     }
     // GRU encoder: resident x-part fragments [dir][wave][gate][hi, lo][lane][16 B]
     bf16x8 xw[C::XRES ? 3 : 1][2];
@@ -189,7 +210,7 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
     for (int m = 0; m < MT; m++)
 #pragma unroll
         for (int e = 0; e < 16; e++) st[m][e] = 0.0f;
-    const unsigned hl = (unsigned)(4 * rg * HS) + split8_off((unsigned)unit);   // lane part of an h element's LDS offset
+    const unsigned hl = (unsigned)(4 * rg * HS) + (X6 ? (unsigned)unit * 4u : split8_off((unsigned)unit));   // lane part of an h element's LDS offset
     __syncthreads();
     if (NG == 3 && a.h0) {
 #pragma unroll
@@ -414,7 +435,7 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
                     acc[m][ai] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ax[m], xw[g][1], acc[m][ai], 0, 0, 0);
                 }
         } else if constexpr (ENC) {
-            ring_bf16<NG, MT, NA, D, NSLOT, 0, C::KS_X, true>(acc, a_x + (s & 1) * ROWS * XS, 32 * XS, wr, bq, lane16, no_hook);
+            ring_bf16<NG, MT, NA, D, NSLOT, 0, C::KS_X, true, X6>(acc, a_x + (s & 1) * ROWS * XS, 32 * XS, wr, bq, lane16, no_hook);
         }
         // ---- h-part: h_{t-1} . W_hh^T, three terms ----------------------------------------------------------------------------
         if constexpr (C::WRES) {
@@ -438,7 +459,7 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
                     }
             }
         } else {
-            ring_bf16<NG, MT, NA, D, NSLOT, NXS, C::KS_H, false>(acc, a_h + cur * ROWS * HS, 32 * HS, wr, bq, lane16, copy_hook);
+            ring_bf16<NG, MT, NA, D, NSLOT, NXS, C::KS_H, false, X6>(acc, a_h + cur * ROWS * HS, 32 * HS, wr, bq, lane16, copy_hook);
         }
         if (dense && s > 0) dense_out(t_prev, tile_prev);   // (the previous step's h tile: this step's A operand)
         if (NW == 8) { if (wv < 4) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1); }
@@ -467,11 +488,15 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
                     st[m][e] = h;
                 }
                 const int row = 32 * m + 8 * (e >> 2) + (e & 3);   // + 4 * rg (lane part)
-                const __bf16 hi = (__bf16)h;
-                const __bf16 lo = (__bf16)(h - (float)hi);
 #if PV_REC_ABL != 2
-                *reinterpret_cast<__bf16*>(hn + row * HS + hl) = hi;
-                *reinterpret_cast<__bf16*>(hn + row * HS + hl + 16) = lo;
+                if constexpr (X6) {
+                    *reinterpret_cast<float*>(hn + row * HS + hl) = h;
+                } else {
+                    const __bf16 hi = (__bf16)h;
+                    const __bf16 lo = (__bf16)(h - (float)hi);
+                    *reinterpret_cast<__bf16*>(hn + row * HS + hl) = hi;
+                    *reinterpret_cast<__bf16*>(hn + row * HS + hl + 16) = lo;
+                }
 #endif
 #if PV_REC_ABL == 1
                 if (h == 123.456f)
@@ -946,12 +971,15 @@ constexpr size_t LDS_TAIL_BF = (size_t)TL_ROWS * TL_HS;
 // Fragment stream of one (direction, wave): slots [x-part k-steps x gates | h-part k-steps x gates]; a slot is 1 KB of hi
 // fragments followed by 1 KB of lo fragments; lane -> weight row gate * HID + 32 * wave + (lane & 31), 8 consecutive K values
 // 16 * ks + 8 * (lane >> 5) + j (the B operand of v_mfma_f32_32x32x16_bf16). GRU encoder: the x-part goes to a stream of its own.
-int pv_pack_rec_bf16(const pv_rnn_dir* dirs, int cell, int kx, unsigned char** d_wp, unsigned char** d_wx, std::vector<void*>& owned) {
+int pv_pack_rec_bf16(const pv_rnn_dir* dirs, int cell, int kx, unsigned char** d_wp, unsigned char** d_wx, std::vector<void*>& owned,
+                     int pieces) {
     const int NG = cell, HID = cell == 4 ? 256 : 128, NW = HID / 32, KS_H = HID / 16;
     const int KS_X = kx ? (cell == 4 ? 2 : 1) : 0;
     const bool xres = kx && cell == 3;
     const int nslot = (xres ? 0 : KS_X * NG) + KS_H * NG;
-    std::vector<uint16_t> wp((size_t)2 * NW * nslot * 1024), wx(xres ? (size_t)2 * NW * NG * 1024 : 0);
+    PV_CHECK(pieces == 2 || (pieces == 3 && cell == 4), PV_ERR_INVALID, "three-piece fragments exist for the LSTM only");
+    const size_t SL = (size_t)pieces * 512;   // 2-byte units of one slot: a 1 KB fragment per piece
+    std::vector<uint16_t> wp((size_t)2 * NW * nslot * SL), wx(xres ? (size_t)2 * NW * NG * 1024 : 0);
     for (int d = 0; d < 2; d++)
         for (int w = 0; w < NW; w++) {
             auto fill = [&](uint16_t* dst, bool xpart, int ks, int g) {
@@ -961,18 +989,22 @@ int pv_pack_rec_bf16(const pv_rnn_dir* dirs, int cell, int kx, unsigned char** d
                         float v;
                         if (xpart) v = k < kx ? dirs[d].w_ih[(size_t)n * kx + k] : 0.0f;
                         else v = dirs[d].w_hh[(size_t)n * HID + k];
+                        // pieces: v ~= hi + lo (2), or v = x0 + x1 + x2 (3: the split3_bf16 rule)
                         const uint16_t hi = f2bf_bits(v);
+                        const float r1 = v - bf_bits2f(hi);
+                        const uint16_t lo = f2bf_bits(r1);
                         dst[lane * 8 + j] = hi;
-                        dst[512 + lane * 8 + j] = f2bf_bits(v - bf_bits2f(hi));
+                        dst[512 + lane * 8 + j] = lo;
+                        if (pieces == 3) dst[1024 + lane * 8 + j] = f2bf_bits(r1 - bf_bits2f(lo));
                     }
             };
-            uint16_t* base = wp.data() + (size_t)(d * NW + w) * nslot * 1024;
+            uint16_t* base = wp.data() + (size_t)(d * NW + w) * nslot * SL;
             int slot = 0;
             if (!xres)
                 for (int ks = 0; ks < KS_X; ks++)
-                    for (int g = 0; g < NG; g++) fill(base + (size_t)(slot++) * 1024, true, ks, g);
+                    for (int g = 0; g < NG; g++) fill(base + (size_t)(slot++) * SL, true, ks, g);
             for (int ks = 0; ks < KS_H; ks++)
-                for (int g = 0; g < NG; g++) fill(base + (size_t)(slot++) * 1024, false, ks, g);
+                for (int g = 0; g < NG; g++) fill(base + (size_t)(slot++) * SL, false, ks, g);
             if (xres)
                 for (int g = 0; g < NG; g++) fill(wx.data() + ((size_t)(d * NW + w) * NG + g) * 1024, true, 0, g);
         }
@@ -1069,11 +1101,16 @@ int pv_rec_bf16_prepare() {
     PV_REC_ATTR(4, true, 1); PV_REC_ATTR(4, true, 2); PV_REC_ATTR(4, false, 1); PV_REC_ATTR(4, false, 2);
     PV_REC_ATTR(3, true, 1); PV_REC_ATTR(3, true, 2); PV_REC_ATTR(3, false, 1); PV_REC_ATTR(3, false, 2);
 #undef PV_REC_ATTR
+#define PV_REC_ATTR6(ENC, MT) \
+    PV_HIP(hipFuncSetAttribute((const void*)k_rec_bf16<4, ENC, MT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rec<4, ENC, MT>()))
+    PV_REC_ATTR6(true, 1); PV_REC_ATTR6(false, 1);
+#undef PV_REC_ATTR6
     return PV_OK;
 }
 
 int pv_rec_bf16_async(pv_ctx* ctx, const pv_rec_desc& d, hipStream_t st) {
     PV_CHECK((d.cell == 3 || d.cell == 4) && d.T > 0 && (d.tr16 || ((d.mt == 1 || d.mt == 2) && d.Bp % (32 * d.mt) == 0)), PV_ERR_INVALID, "bad recurrent-layer launch");
+    PV_CHECK(!d.x6 || (d.cell == 4 && !d.tr16 && d.mt == 1), PV_ERR_INVALID, "the split-6 form is an LSTM layer on 32-row tiles");
     RecArgs a;
     a.G = d.G; a.wp = d.wp; a.wx = d.wx; a.bias = d.bias; a.bias_hn = d.bias_hn; a.x = (const unsigned char*)d.x;
     a.x_row_bytes = d.x_row_bytes; a.x_t0 = d.x_t0; a.xf = d.xf; a.x_signed = d.x_signed; a.B = d.B; a.Bp = d.Bp; a.T = d.T;
@@ -1096,7 +1133,11 @@ int pv_rec_bf16_async(pv_ctx* ctx, const pv_rec_desc& d, hipStream_t st) {
     const unsigned grid = (unsigned)(((a.n_tiles + 3) / 4) * 8);
     pv_prof_scope ps(ctx, d.prof_name, st);
 #define PV_REC_GO(NG, ENC, MT) k_rec_bf16<NG, ENC, MT><<<grid, RecCfg<NG, ENC>::NTHR, lds_rec<NG, ENC, MT>(), st>>>(a)
-    if (d.cell == 4) {
+#define PV_REC_GO6(ENC, MT) k_rec_bf16<4, ENC, MT, true><<<grid, RecCfg<4, ENC>::NTHR, lds_rec<4, ENC, MT>(), st>>>(a)
+    if (d.x6) {   // (32-row tiles only: the 64-row form spills 14 / 42 registers with three weight pieces)
+        if (d.enc) PV_REC_GO6(true, 1);
+        else PV_REC_GO6(false, 1);
+    } else if (d.cell == 4) {
         if (d.enc) { if (d.mt == 2) PV_REC_GO(4, true, 2); else PV_REC_GO(4, true, 1); }
         else { if (d.mt == 2) PV_REC_GO(4, false, 2); else PV_REC_GO(4, false, 1); }
     } else {
@@ -1104,6 +1145,7 @@ int pv_rec_bf16_async(pv_ctx* ctx, const pv_rec_desc& d, hipStream_t st) {
         else { if (d.mt == 2) PV_REC_GO(3, false, 2); else PV_REC_GO(3, false, 1); }
     }
 #undef PV_REC_GO
+#undef PV_REC_GO6
     PV_HIP(hipGetLastError());
     return PV_OK;
 }
