@@ -284,6 +284,39 @@ int pv_polish_realign(pv_ctx* ctx, const pv_batch_in* in, const int64_t* win_off
 int pv_polish_realign_dev(pv_ctx* ctx, const pv_batch_in* in, int64_t n_reads, int64_t n_bases, int64_t max_query_len,
                           const int64_t* win_off, const uint8_t* win, pv_realign_out* out, int64_t* d_counts, void* stream);
 
+/* ---- BGZF block inflate (the BAM readers' opt-in GPU mode) ---------------------------------------------------------
+ * A batch of BGZF blocks, one wavefront each: the raw-DEFLATE payloads (RFC 1951: stored, fixed and dynamic Huffman
+ * blocks, any BFINAL chain) concatenated in `payload`; per block the payload offset in_off, its length clen, the gzip
+ * trailer's ISIZE (<= 65536) and CRC32, and the output offset out_off. A block writes exactly isize bytes at out_off and
+ * nothing outside [out_off, out_off + isize); it reads nothing outside [in_off, in_off + clen). status[i] is one of the
+ * PV_BGZF_* codes below: the output length and the CRC32 are checked as the host reader checks them.
+ * d_counts / counts = {bytes of the good blocks, PV_OK or PV_ERR_INVALID, first bad block (-1 if none), its status}. */
+#define PV_BGZF_OK 0
+#define PV_BGZF_BAD_BTYPE 1          /* BTYPE = 3 */
+#define PV_BGZF_STORED_LEN 2         /* stored block: LEN != ~NLEN */
+#define PV_BGZF_BAD_CODE_LENGTHS 3   /* dynamic header: over-subscribed / incomplete code, bad repeat, no end-of-block code */
+#define PV_BGZF_BAD_SYMBOL 4         /* literal/length 286/287, distance 30/31, or bits that match no code */
+#define PV_BGZF_DIST_TOO_FAR 5       /* a distance reaching before the block's first output byte */
+#define PV_BGZF_OUTPUT_OVERFLOW 6    /* more output than isize */
+#define PV_BGZF_OUTPUT_SHORT 7       /* the final block ended before isize bytes */
+#define PV_BGZF_INPUT_OVERRUN 8      /* the stream needs bits past clen */
+#define PV_BGZF_CRC_MISMATCH 9
+#define PV_BGZF_BAD_ARGS 10          /* the block's entry lies outside the payload / output buffers or isize > 65536 */
+/* Device-resident and asynchronous on `stream` (NULL = the context's own); every pointer is a DEVICE pointer. It uses no
+ * context workspace, so it may run on a stream of its own while builder, RNN or other calls of the same context run on
+ * theirs; two of these calls may overlap too as long as their outputs, status and d_counts arrays are distinct. A call on a
+ * stream other than the context's own is not recorded in the context's event profile (pv_profile_begin), which is not
+ * thread-safe; one on the context's own stream is, and then must not overlap other calls of the context. */
+int pv_bgzf_inflate_dev(pv_ctx* ctx, const uint8_t* payload, int64_t payload_bytes, int64_t n_blocks, const int64_t* in_off,
+                        const int32_t* clen, const int32_t* isize, const uint32_t* crc, const int64_t* out_off, uint8_t* out,
+                        int64_t out_bytes, int32_t* status, int64_t* d_counts, void* stream);
+/* HOST buffers in and out, staged through the context's workspace (so, like the other host forms, it must not overlap other
+ * calls on the context). Bytes of `out` outside every block's range are left as they were. Returns PV_OK, or PV_ERR_INVALID
+ * when a block failed (counts and status say which and why) or an argument is bad. */
+int pv_bgzf_inflate(pv_ctx* ctx, const uint8_t* payload, int64_t payload_bytes, int64_t n_blocks, const int64_t* in_off,
+                    const int32_t* clen, const int32_t* isize, const uint32_t* crc, const int64_t* out_off, uint8_t* out,
+                    int64_t out_bytes, int32_t* status, int64_t* counts);
+
 /* ---- recurrent-network inference ------------------------------------------------------------ */
 
 #define PV_PLAN_P1_LSTM 1 /* pepper_variant: 2x bi-LSTM(256) + 5xLinear(512)/SELU + Linear(3) + softmax */

@@ -88,11 +88,42 @@ typedef struct pvio_batch {
     int64_t bytes_inflated;
     const int32_t* read_hp;        /* [n_reads] HP aux tag or 0: the `read_hp` argument of pv_summarize_regions_hp */
     double t_helpers;              /* seconds the handle's helper threads spent inflating during the call (pvio_bam_set_threads) */
+    int64_t blocks_host;           /* pvio_fill_batch_blocks: non-empty blocks missing from the table, read and inflated by this call */
 } pvio_batch;
 int pvio_fill_batch(pv_bam* bam, pv_fasta* fa, int n_intervals, const char* const* contigs, const int64_t* starts,
                     const int64_t* ends, int safe_bases, int include_supplementary, int min_mapq, double downsample_rate,
                     int64_t max_reads, uint32_t seed, pvio_batch** out);
 void pvio_batch_free(pvio_batch* batch);
+
+/* BGZF blocks inflated elsewhere (include/pepper_hip.h pv_bgzf_inflate on the GPU). pvio_plan_blocks walks, for every BAI
+ * chunk pvio_fill_batch would read for these intervals (same safe_bases), the BGZF headers from the chunk's first block to
+ * the block holding its end plus margin_blocks more (records span blocks), deduplicated across the intervals, and returns
+ * the raw-DEFLATE payloads concatenated with the block table of pv_bgzf_inflate (in_off, clen, isize, crc, out_off: the
+ * blocks laid end to end in file order) plus every block's compressed offset and that of the block after it. Headers are
+ * validated as the reader validates them (a corrupt or truncated one fails with the same message). A chunk's walk also
+ * stops at the block of the BAI linear index two 16 kb windows past the region (the reader stops at the first record past
+ * the region; reads longer than 32 kb may then need a block from the host fallback). The handle must run no
+ * helper threads. pvio_fill_batch_blocks is pvio_fill_batch with such a table of inflated blocks (coffset ascending; block
+ * i's bytes at data + out_off[i]): a block found there is not read from the file; a block not found (a record running past
+ * the planned range) is read and inflated here and counted in blocks_host. Its result equals pvio_fill_batch's. */
+typedef struct pvio_block_plan {
+    void* owner;
+    int64_t n_blocks, payload_bytes, out_bytes;
+    const uint8_t* payload;
+    const int64_t *coffset, *next_coffset, *in_off;
+    const int32_t *clen, *isize;
+    const uint32_t* crc;
+    const int64_t* out_off;
+    double t_plan;                 /* seconds in the call */
+} pvio_block_plan;
+int pvio_plan_blocks(pv_bam* bam, int n_intervals, const char* const* contigs, const int64_t* starts, const int64_t* ends,
+                     int safe_bases, int margin_blocks, pvio_block_plan** out);
+void pvio_plan_free(pvio_block_plan* plan);
+int pvio_fill_batch_blocks(pv_bam* bam, pv_fasta* fa, int n_intervals, const char* const* contigs, const int64_t* starts,
+                           const int64_t* ends, int safe_bases, int include_supplementary, int min_mapq, double downsample_rate,
+                           int64_t max_reads, uint32_t seed, int64_t n_blocks, const int64_t* coffset,
+                           const int64_t* next_coffset, const int32_t* isize, const int64_t* out_off, const uint8_t* data,
+                           pvio_batch** out);
 /* kept read indices, in output order, of the reservoir sampling above; returns their number (out holds n_reads slots) */
 int64_t pvio_reservoir_indices(int64_t n_reads, double downsample_rate, int64_t max_reads, uint32_t seed, int64_t* out);
 

@@ -35,6 +35,22 @@ PV_HP_WINDOW_ROWS = 21
 PV_HP_FEATURES = 48
 PV_HP_WINDOW_BYTES = PV_HP_WINDOW_ROWS * PV_HP_FEATURES
 
+# per-block statuses of pv_bgzf_inflate[_dev]
+PV_BGZF_OK = 0
+PV_BGZF_BAD_BTYPE = 1
+PV_BGZF_STORED_LEN = 2
+PV_BGZF_BAD_CODE_LENGTHS = 3
+PV_BGZF_BAD_SYMBOL = 4
+PV_BGZF_DIST_TOO_FAR = 5
+PV_BGZF_OUTPUT_OVERFLOW = 6
+PV_BGZF_OUTPUT_SHORT = 7
+PV_BGZF_INPUT_OVERRUN = 8
+PV_BGZF_CRC_MISMATCH = 9
+PV_BGZF_BAD_ARGS = 10
+BGZF_STATUS_NAMES = {0: "ok", 1: "BTYPE 3", 2: "stored LEN/NLEN mismatch", 3: "invalid code lengths", 4: "invalid symbol",
+                     5: "distance too far back", 6: "output exceeds ISIZE", 7: "output shorter than ISIZE",
+                     8: "payload read past its end", 9: "CRC32 mismatch", 10: "bad block table entry"}
+
 PV_PLAN_P1_LSTM = 1
 PV_PLAN_P2_GRU = 2
 PV_DTYPE_F32 = 0
@@ -188,6 +204,12 @@ SYMBOLS = [
     ("pv_polish_realign_dev", C.c_int,
      [C.c_void_p, C.POINTER(pv_batch_in), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(pv_realign_out),
       C.c_void_p, C.c_void_p]),
+    ("pv_bgzf_inflate_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pv_bgzf_inflate", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+      C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
     ("pv_rnn_load_p1", C.c_int, [C.c_void_p, C.POINTER(pv_weights_p1), C.c_int]),
     ("pv_rnn_load_p2", C.c_int, [C.c_void_p, C.POINTER(pv_weights_p2), C.c_int]),
     ("pv_rnn_forward_p1", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

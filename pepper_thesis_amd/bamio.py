@@ -36,7 +36,14 @@ class pvio_batch(C.Structure):
                 ("cigar_off", C.POINTER(C.c_int64)), ("cigar", C.POINTER(C.c_uint32)),
                 ("interval_index", C.POINTER(C.c_int64)), ("reads_seen", C.POINTER(C.c_int64)),
                 ("t_inflate", C.c_double), ("t_total", C.c_double), ("bytes_inflated", C.c_int64),
-                ("read_hp", C.POINTER(C.c_int32)), ("t_helpers", C.c_double)]
+                ("read_hp", C.POINTER(C.c_int32)), ("t_helpers", C.c_double), ("blocks_host", C.c_int64)]
+
+
+class pvio_block_plan(C.Structure):
+    _fields_ = [("owner", C.c_void_p), ("n_blocks", C.c_int64), ("payload_bytes", C.c_int64), ("out_bytes", C.c_int64),
+                ("payload", C.POINTER(C.c_uint8)), ("coffset", C.POINTER(C.c_int64)), ("next_coffset", C.POINTER(C.c_int64)),
+                ("in_off", C.POINTER(C.c_int64)), ("clen", C.POINTER(C.c_int32)), ("isize", C.POINTER(C.c_int32)),
+                ("crc", C.POINTER(C.c_uint32)), ("out_off", C.POINTER(C.c_int64)), ("t_plan", C.c_double)]
 
 
 IO_SYMBOLS = [
@@ -53,6 +60,13 @@ IO_SYMBOLS = [
     ("pvio_fill_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                   C.c_int, C.c_int, C.c_int, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.POINTER(pvio_batch))]),
     ("pvio_batch_free", None, [C.POINTER(pvio_batch)]),
+    ("pvio_plan_blocks", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
+                                   C.c_int, C.POINTER(C.POINTER(pvio_block_plan))]),
+    ("pvio_plan_free", None, [C.POINTER(pvio_block_plan)]),
+    ("pvio_fill_batch_blocks", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int64, C.c_uint32,
+                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.POINTER(pvio_batch))]),
     ("pvio_reservoir_indices", C.c_int64, [C.c_int64, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_int64)]),
     ("pvio_write_bam", C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
@@ -221,6 +235,7 @@ class FilledBatch:
         self.reads_seen = view(v.reads_seen, G, np.int64).copy()
         self.t_inflate, self.t_total, self.bytes_inflated = float(v.t_inflate), float(v.t_total), int(v.bytes_inflated)
         self.t_helpers = float(v.t_helpers)
+        self.blocks_host = int(v.blocks_host)
         self.batch = RegionBatch(
             G, view(v.ref_start, G, np.int64), view(v.ref_end, G, np.int64), view(v.cand_start, G, np.int64),
             view(v.cand_end, G, np.int64), view(v.ref_off, G + 1, np.int64), view(v.ref, int(v.n_ref_bytes), np.uint8),
@@ -257,6 +272,74 @@ def fill_batch(bam: BamHandler, fasta: FastaHandler, intervals, min_mapq: int = 
                                 int(min_mapq), float(downsample_rate), MAX_READS_IN_REGION, RANDOM_SEED, C.byref(out))
     if rc:
         raise IOError("fill_batch: " + _err())
+    return FilledBatch(out, intervals)
+
+
+def _interval_args(intervals):
+    n = len(intervals)
+    names = (C.c_char_p * max(n, 1))(*[iv[0].encode() for iv in intervals])
+    starts = (C.c_int64 * max(n, 1))(*[int(iv[1]) for iv in intervals])
+    ends = (C.c_int64 * max(n, 1))(*[int(iv[2]) for iv in intervals])
+    return n, names, starts, ends
+
+
+class BlockPlan:
+    """The BGZF blocks fill_batch would read for a list of intervals (pvio_plan_blocks): raw-DEFLATE payloads concatenated
+    in `payload` and the block table of Context.bgzf_inflate (in_off, clen, isize, crc, out_off: blocks end to end in file
+    order), plus every block's compressed offset and that of the next block. Arrays are copies owned by this object."""
+
+    def __init__(self, ptr):
+        v = ptr.contents
+        n = int(v.n_blocks)
+        self.n_blocks, self.out_bytes, self.t_plan = n, int(v.out_bytes), float(v.t_plan)
+        self.payload = _np(v.payload, int(v.payload_bytes), np.uint8)
+        self.coffset = _np(v.coffset, n, np.int64)
+        self.next_coffset = _np(v.next_coffset, n, np.int64)
+        self.in_off = _np(v.in_off, n, np.int64)
+        self.clen = _np(v.clen, n, np.int32)
+        self.isize = _np(v.isize, n, np.int32)
+        self.crc = _np(v.crc, n, np.uint32)
+        self.out_off = _np(v.out_off, n, np.int64)
+
+
+def plan_blocks(bam: BamHandler, intervals, safe_bases: int = 100, margin_blocks: int = 2) -> BlockPlan:
+    """the block plan of fill_batch(bam, ..., intervals, safe_bases=safe_bases) with margin_blocks blocks past every BAI
+    chunk's last block (records span blocks; one missing is read and inflated on the host by fill_batch_blocks)"""
+    n, names, starts, ends = _interval_args(intervals)
+    out = C.POINTER(pvio_block_plan)()
+    if load().pvio_plan_blocks(bam.h, n, names, starts, ends, int(safe_bases), int(margin_blocks), C.byref(out)):
+        raise IOError("plan_blocks: " + _err())
+    try:
+        return BlockPlan(out)
+    finally:
+        load().pvio_plan_free(out)
+
+
+def fill_batch_blocks(bam: BamHandler, fasta: FastaHandler, intervals, coffset, next_coffset, isize, out_off, data,
+                      min_mapq: int = 5, include_supplementary: bool = False, downsample_rate: float = 1.0,
+                      safe_bases: int = 100) -> FilledBatch:
+    """fill_batch with a table of BGZF blocks inflated elsewhere (pvio_fill_batch_blocks): block i (compressed offset
+    coffset[i], ascending; the next block at next_coffset[i]) is the isize[i] bytes at data[out_off[i]:]. Blocks missing
+    from the table are read and inflated on the host (FilledBatch.blocks_host). Same arrays as fill_batch."""
+    n, names, starts, ends = _interval_args(intervals)
+    co = np.ascontiguousarray(coffset, np.int64)
+    nx = np.ascontiguousarray(next_coffset, np.int64)
+    isz = np.ascontiguousarray(isize, np.int32)
+    oo = np.ascontiguousarray(out_off, np.int64)
+    assert len(nx) == len(co) and len(isz) == len(co) and len(oo) == len(co)
+    if isinstance(data, np.ndarray):
+        d = np.ascontiguousarray(data, np.uint8)
+        assert len(co) == 0 or int((oo + isz).max()) <= d.size
+        dptr = d.ctypes.data
+    else:   # an address (pinned host buffer)
+        d, dptr = None, int(data)
+    out = C.POINTER(pvio_batch)()
+    rc = load().pvio_fill_batch_blocks(bam.h, fasta.h, n, names, starts, ends, int(safe_bases), int(bool(include_supplementary)),
+                                       int(min_mapq), float(downsample_rate), MAX_READS_IN_REGION, RANDOM_SEED, len(co),
+                                       co.ctypes.data, nx.ctypes.data, isz.ctypes.data, oo.ctypes.data, dptr or None,
+                                       C.byref(out))
+    if rc:
+        raise IOError("fill_batch_blocks: " + _err())
     return FilledBatch(out, intervals)
 
 

@@ -83,7 +83,13 @@ def call_variant_parser(ap=None):
                     help="(default) windows stay in HBM between the image builder and the network; no image files")
     ap.add_argument("--no_fused", dest="fused", action="store_false", help="the reference's three steps through image HDF5 files")
     ap.add_argument("--keep_images", action="store_true", default=False, help="with --fused: also write the image HDF5 files")
+    _gpu_inflate_flag(ap)
     return ap
+
+
+def _gpu_inflate_flag(ap):
+    ap.add_argument("--gpu_inflate", action="store_true", default=False,
+                    help="inflate the BAM's BGZF blocks on the GPU (opt-in; same output as the default host inflate)")
 
 
 def make_images_parser(ap=None):
@@ -94,6 +100,7 @@ def make_images_parser(ap=None):
     ap.add_argument("-t", "--threads", type=int, required=False, default=None)
     add_image_options(ap)
     _platform_group(ap)
+    _gpu_inflate_flag(ap)
     return ap
 
 

@@ -133,6 +133,16 @@ struct Bgzf {
     std::vector<char> iobuf;     // 1 MB stdio buffer (set on the first block)
     void* ld = nullptr;          // libdeflate decompressor of the consuming thread
     int64_t ahead_limit = INT64_MAX;   // blocks STARTING beyond this compressed offset are not read ahead
+    // pvio_fill_batch_blocks: blocks inflated elsewhere (the GPU), consulted before a block is read and inflated here.
+    // coffset ascending; data + out_off[i] holds isize[i] bytes. Blocks not in it are read and inflated as usual (counted).
+    struct Table {
+        int64_t n = 0;
+        const int64_t *coffset = nullptr, *next = nullptr, *out_off = nullptr;
+        const int32_t* isize = nullptr;
+        const uint8_t* data = nullptr;
+    };
+    const Table* table = nullptr;
+    int64_t blocks_host = 0;     // non-empty blocks this handle inflated itself while a table was set
 
     struct Slot {
         int64_t coffset = -1, next = -1;
@@ -321,6 +331,17 @@ struct Bgzf {
         return ok;
     }
     bool load_block_(int64_t coffset) {
+        if (table) {
+            const int64_t* e = table->coffset + table->n;
+            const int64_t* it = std::lower_bound(table->coffset, e, coffset);
+            if (it != e && *it == coffset) {
+                const int64_t i = it - table->coffset;
+                const uint8_t* p = table->data + table->out_off[i];
+                buf.assign(p, p + table->isize[i]);
+                block_coffset = coffset; next_coffset = table->next[i]; pos = 0;
+                return true;
+            }
+        }
         if (ring.empty()) ring.resize(1);
         if (iobuf.empty()) { iobuf.resize(1 << 20); setvbuf(f, iobuf.data(), _IOFBF, iobuf.size()); fpos = -1; }
         if (count > 0 && at(0).coffset < coffset && coffset < file_next) {   // a forward skip inside what is buffered
@@ -361,6 +382,7 @@ struct Bgzf {
             buf.swap(s.buf);
             block_coffset = s.coffset; next_coffset = s.next; pos = 0;
             bytes_inflated += s.isize;
+            if (table && s.isize > 0) blocks_host++;   // a block the table lacked, inflated here (empty EOF blocks not counted)
             pop_locked();
         }
         if (!helpers.empty() && count * 2 <= ring.size()) refill(false);   // top up in batches, half a ring at a time: the helpers
@@ -891,10 +913,10 @@ static int clip_append(const RecView& v, int64_t start, int64_t stop, ReadSink& 
     return 1;
 }
 
-// BAM_handler::get_reads body: every record of [start, stop) on `tid`, filtered and clipped, appended to the sink
-static int query_region(pv_bam* b, int tid, int64_t start, int64_t stop, int include_supplementary, int min_mapq, ReadSink& sink) {
-    const int64_t qbeg = start < 0 ? 0 : start, qend = stop;  // sam_itr_queryi(idx, tid, start, stop): [start, stop)
-    std::vector<Chunk> chunks;
+// the BAI chunks of [qbeg, qend) on `tid`: chunks of the overlapping bins that end past the linear index's minimum offset,
+// sorted and merged
+static void region_chunks(const pv_bam* b, int tid, int64_t qbeg, int64_t qend, std::vector<Chunk>& chunks) {
+    chunks.clear();
     if (tid < (int)b->index.size() && qend > qbeg) {
         const RefIndex& ri = b->index[tid];
         uint64_t min_off = 0;
@@ -916,6 +938,13 @@ static int query_region(pv_bam* b, int tid, int64_t start, int64_t stop, int inc
         }
         chunks.swap(m);
     }
+}
+
+// BAM_handler::get_reads body: every record of [start, stop) on `tid`, filtered and clipped, appended to the sink
+static int query_region(pv_bam* b, int tid, int64_t start, int64_t stop, int include_supplementary, int min_mapq, ReadSink& sink) {
+    const int64_t qbeg = start < 0 ? 0 : start, qend = stop;  // sam_itr_queryi(idx, tid, start, stop): [start, stop)
+    std::vector<Chunk> chunks;
+    region_chunks(b, tid, qbeg, qend, chunks);
     std::vector<uint8_t> rec;
     std::vector<uint32_t> cigbuf;
     bool done = false;
@@ -1137,11 +1166,53 @@ extern "C" void pvio_batch_free(pvio_batch* bt) {
     delete (pvio_batch_store*)bt->owner;
 }
 
+static int fill_batch(pv_bam* b, pv_fasta* fa, int n_intervals, const char* const* contigs, const int64_t* starts,
+                      const int64_t* ends, int safe_bases, int include_supplementary, int min_mapq, double downsample_rate,
+                      int64_t max_reads, uint32_t seed, pvio_batch** out);
+
 extern "C" int pvio_fill_batch(pv_bam* b, pv_fasta* fa, int n_intervals, const char* const* contigs, const int64_t* starts,
                                const int64_t* ends, int safe_bases, int include_supplementary, int min_mapq,
                                double downsample_rate, int64_t max_reads, uint32_t seed, pvio_batch** out) {
     if (!b || !fa || !out || (n_intervals > 0 && (!contigs || !starts || !ends))) { io_err("null argument"); return -1; }
     *out = nullptr;
+    return fill_batch(b, fa, n_intervals, contigs, starts, ends, safe_bases, include_supplementary, min_mapq, downsample_rate,
+                      max_reads, seed, out);
+}
+
+extern "C" int pvio_fill_batch_blocks(pv_bam* b, pv_fasta* fa, int n_intervals, const char* const* contigs,
+                                      const int64_t* starts, const int64_t* ends, int safe_bases, int include_supplementary,
+                                      int min_mapq, double downsample_rate, int64_t max_reads, uint32_t seed, int64_t n_blocks,
+                                      const int64_t* coffset, const int64_t* next_coffset, const int32_t* isize,
+                                      const int64_t* out_off, const uint8_t* data, pvio_batch** out) {
+    if (!b || !fa || !out || (n_intervals > 0 && (!contigs || !starts || !ends))) { io_err("null argument"); return -1; }
+    *out = nullptr;
+    if (n_blocks < 0 || (n_blocks > 0 && (!coffset || !next_coffset || !isize || !out_off || !data))) { io_err("bad block table"); return -1; }
+    if (!b->z.helpers.empty()) {
+        io_err("fill_batch_blocks: the handle runs helper threads (pvio_bam_set_threads); set 0 helpers to use inflated blocks");
+        return -1;
+    }
+    for (int64_t i = 0; i < n_blocks; i++)
+        if ((i > 0 && coffset[i] <= coffset[i - 1]) || isize[i] < 0 || isize[i] > 65536 || out_off[i] < 0) {
+            io_err("fill_batch_blocks: block table entry %lld is not ascending or out of range", (long long)i);
+            return -1;
+        }
+    Bgzf::Table t;
+    t.n = n_blocks; t.coffset = coffset; t.next = next_coffset; t.out_off = out_off; t.isize = isize; t.data = data;
+    // the block the handle holds may be stale with respect to the table: forget it so that the first seek goes through it
+    b->z.block_coffset = -1; b->z.buf.clear(); b->z.pos = 0;
+    b->z.table = &t;
+    const int64_t host0 = b->z.blocks_host;
+    const int rc = fill_batch(b, fa, n_intervals, contigs, starts, ends, safe_bases, include_supplementary, min_mapq,
+                              downsample_rate, max_reads, seed, out);
+    b->z.table = nullptr;
+    b->z.block_coffset = -1; b->z.buf.clear(); b->z.pos = 0;
+    if (rc == 0) (*out)->blocks_host = b->z.blocks_host - host0;
+    return rc;
+}
+
+static int fill_batch(pv_bam* b, pv_fasta* fa, int n_intervals, const char* const* contigs, const int64_t* starts,
+                      const int64_t* ends, int safe_bases, int include_supplementary, int min_mapq, double downsample_rate,
+                      int64_t max_reads, uint32_t seed, pvio_batch** out) {
     const double t_begin = now_s();
     const double infl0 = b->z.t_inflate;
     double help0;
@@ -1238,6 +1309,98 @@ extern "C" int pvio_fill_batch(pv_bam* b, pv_fasta* fa, int n_intervals, const c
     v.t_total = now_s() - t_begin;
     v.bytes_inflated = b->z.bytes_inflated - inflb0;
     v.read_hp = s.hp.data();
+    *out = &st->view;
+    return 0;
+}
+
+// ---- block plan for an inflate done elsewhere (the GPU) ----------------------------------------------------------------
+static const int PLAN_LOOKAHEAD = 2;   // 16 kb linear-index windows past a region: reads up to 32 kb are planned in full
+struct pvio_plan_store {
+    std::vector<uint8_t> payload;
+    std::vector<int64_t> coffset, next, in_off, out_off;
+    std::vector<int32_t> clen, isize;
+    std::vector<uint32_t> crc;
+    pvio_block_plan view;
+};
+
+extern "C" void pvio_plan_free(pvio_block_plan* p) {
+    if (!p) return;
+    delete (pvio_plan_store*)p->owner;
+}
+
+extern "C" int pvio_plan_blocks(pv_bam* b, int n_intervals, const char* const* contigs, const int64_t* starts,
+                                const int64_t* ends, int safe_bases, int margin_blocks, pvio_block_plan** out) {
+    if (!b || !out || (n_intervals > 0 && (!contigs || !starts || !ends))) { io_err("null argument"); return -1; }
+    *out = nullptr;
+    if (margin_blocks < 0) { io_err("plan_blocks: negative margin"); return -1; }
+    if (!b->z.helpers.empty()) {
+        io_err("plan_blocks: the handle runs helper threads (pvio_bam_set_threads); set 0 helpers to plan blocks");
+        return -1;
+    }
+    const double t0 = now_s();
+    // [first block, last block] of every chunk of every interval (the region fill_batch reads), then the union of the ranges
+    std::vector<std::pair<int64_t, int64_t>> ranges;
+    std::vector<Chunk> chunks;
+    for (int iv = 0; iv < n_intervals; iv++) {
+        const int tid = find_tid(b, contigs[iv]);
+        if (tid < 0) { io_err("contig %s not in the BAM header", contigs[iv]); return -1; }
+        const int64_t rs = std::max<int64_t>(0, starts[iv] - safe_bases), re = ends[iv] + safe_bases;
+        region_chunks(b, tid, rs, re, chunks);
+        // The reader stops at the first record that starts at or past `re`, long before the end of a merged chunk of a large
+        // bin. Records are sorted, so the linear index PLAN_LOOKAHEAD windows past the region's last one (the first record
+        // overlapping that window) is at or after that record when no read that starts inside the region is longer than the
+        // look-ahead: its block bounds the walk. Longer reads only cost blocks inflated on the host, never a different result.
+        // (a BAI with fewer references than the header has no chunks for this contig: region_chunks returned none)
+        int64_t bound = INT64_MAX;
+        if (tid < (int)b->index.size()) {
+            const RefIndex& ri = b->index[tid];
+            const size_t w = (size_t)(((re - 1) >> 14) + 1 + PLAN_LOOKAHEAD);
+            if (re > rs && w < ri.linear.size() && ri.linear[w] != 0) bound = (int64_t)(ri.linear[w] >> 16);
+        }
+        for (const Chunk& c : chunks) {   // (chunks of large bins that start past the bound are never reached by the reader)
+            const int64_t first = (int64_t)(c.beg >> 16);
+            if (first <= bound) ranges.emplace_back(first, std::min((int64_t)(c.end >> 16), bound));
+        }
+    }
+    std::sort(ranges.begin(), ranges.end());
+    pvio_plan_store* st = new pvio_plan_store();
+    Bgzf& z = b->z;
+    Bgzf::Slot s;
+    int64_t done_to = -1;   // blocks starting before this offset are planned already (ranges are sorted by their start)
+    for (const auto& r : ranges) {
+        int64_t co = std::max(r.first, done_to);
+        for (int after = 0;;) {   // the blocks up to the one holding the chunk end, then margin_blocks more
+            if (co > r.second && after++ >= margin_blocks) break;
+            if (co != z.fpos && fseeko(z.f, co, SEEK_SET) != 0) { io_err("seek to BGZF block at %lld failed", (long long)co); z.fpos = -1; delete st; return -1; }
+            z.fpos = co;
+            const int rc = z.read_raw(co, s);   // validates the header, BSIZE, ISIZE and truncation as the reader does
+            if (rc < 0) { z.fpos = -1; delete st; return -1; }
+            if (rc == 0) break;                 // clean end of file
+            st->coffset.push_back(co);
+            st->next.push_back(s.next);
+            st->in_off.push_back((int64_t)st->payload.size());
+            st->clen.push_back(s.clen);
+            st->isize.push_back((int32_t)s.isize);
+            st->crc.push_back(rd32(&s.cbuf[s.clen]));
+            st->payload.insert(st->payload.end(), s.cbuf.begin(), s.cbuf.begin() + s.clen);
+            co = s.next;
+            done_to = co;
+        }
+    }
+    z.fpos = -1;   // the reader's own position is not known any more
+    int64_t o = 0;
+    for (int32_t v : st->isize) { st->out_off.push_back(o); o += v; }
+    pvio_block_plan& v = st->view;
+    memset(&v, 0, sizeof(v));
+    v.owner = st;
+    v.n_blocks = (int64_t)st->coffset.size();
+    v.payload_bytes = (int64_t)st->payload.size();
+    v.out_bytes = o;
+    v.payload = st->payload.data();
+    v.coffset = st->coffset.data(); v.next_coffset = st->next.data();
+    v.in_off = st->in_off.data(); v.clen = st->clen.data(); v.isize = st->isize.data(); v.crc = st->crc.data();
+    v.out_off = st->out_off.data();
+    v.t_plan = now_s() - t0;
     *out = &st->view;
     return 0;
 }

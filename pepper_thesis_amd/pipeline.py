@@ -87,11 +87,13 @@ def call_variant_fused(ctx, state_dict: dict, bam_path: str, fasta_path: str, pr
                        region_size: int = 100_000, min_mapq: int = 5, include_supplementary: bool = False,
                        downsample_rate: float = 1.0, batch_size: int = 512, intervals_per_call: int = 16, rank: int = 0,
                        world: int = 1, reader_threads: int = None, keep_images_path: Optional[str] = None, timers: dict = None,
-                       dtype: int = _ffi.PV_DTYPE_F32, region_bed: str = None, inflate_helpers: int = None, on_rows=None) -> int:
+                       dtype: int = _ffi.PV_DTYPE_F32, region_bed: str = None, inflate_helpers: int = None, on_rows=None,
+                       gpu_inflate: bool = False) -> int:
     """-> number of windows predicted. One prediction file at `pred_path` (and one image file at `keep_images_path`, if given)
     for the intervals of this rank. state_dict None = images only (make_images): no model, no prediction file.
     on_rows (optional): called on the writer thread with every call's windows as the arrays of a prediction batch (what
-    PredictionStore.batches() would read back) - call_variant selects its candidates there, while the device works on."""
+    PredictionStore.batches() would read back) - call_variant selects its candidates there, while the device works on.
+    gpu_inflate: the readers' BGZF blocks are inflated on this context's device (make_images.region_batches); same output."""
     import torch
     from .device import DeviceOut
     from .make_images import region_batches
@@ -102,7 +104,7 @@ def call_variant_fused(ctx, state_dict: dict, bam_path: str, fasta_path: str, pr
     # the readers start on the first intervals here; the model is loaded while they read
     batches = region_batches(bam_path, fasta_path, region, region_size, min_mapq, include_supplementary, downsample_rate,
                              intervals_per_call, rank, world, reader_threads, 1, T, region_bed, merge=False,
-                             inflate_helpers=inflate_helpers)
+                             inflate_helpers=inflate_helpers, gpu_inflate=gpu_inflate, ctx=ctx)
     t0 = time.perf_counter()
     predict = state_dict is not None
     if predict:

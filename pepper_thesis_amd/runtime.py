@@ -292,6 +292,37 @@ class Context:
             self.handle, C.byref(dbatch.c), dbatch.n_reads, dbatch.n_bases, int(max_query_len), d_win_off, d_win,
             C.byref(dout.c), dout.counts.data_ptr(), stream or None))
 
+    def bgzf_inflate(self, payload: np.ndarray, in_off, clen, isize, crc, out_off, out: np.ndarray = None):
+        """host-buffer BGZF inflate (pv_bgzf_inflate) of a block table -> (out uint8, status int32 [n], counts (bytes,
+        status, first bad block, its status)). A failed block does not raise: its status says why (the PV_BGZF_* codes).
+        out None: a zeroed buffer of max(out_off + isize) bytes; bytes outside every block's range are left as given."""
+        pay = np.ascontiguousarray(payload, np.uint8)
+        ioff, ooff = np.ascontiguousarray(in_off, np.int64), np.ascontiguousarray(out_off, np.int64)
+        cl, isz = np.ascontiguousarray(clen, np.int32), np.ascontiguousarray(isize, np.int32)
+        cr = np.ascontiguousarray(crc, np.uint32)
+        n = len(ioff)
+        assert len(cl) == n and len(isz) == n and len(cr) == n and len(ooff) == n
+        if out is None:
+            out = np.zeros(int((ooff + isz).max()) if n else 0, np.uint8)
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"]
+        status = np.zeros(max(n, 1), np.int32)
+        counts = (C.c_int64 * 4)()
+        rc = self.lib.pv_bgzf_inflate(self.handle, _ffi.ptr(pay), pay.size, n, _ffi.ptr(ioff), _ffi.ptr(cl), _ffi.ptr(isz),
+                                      _ffi.ptr(cr), _ffi.ptr(ooff), _ffi.ptr(out) if out.size else None, out.size,
+                                      _ffi.ptr(status), counts)
+        if rc != _ffi.PV_OK and not (rc == _ffi.PV_ERR_INVALID and counts[1] == _ffi.PV_ERR_INVALID):
+            _ffi.check(rc)
+        return out, status[:n], tuple(int(v) for v in counts)
+
+    def bgzf_inflate_dev(self, d_payload: int, payload_bytes: int, n_blocks: int, d_in_off: int, d_clen: int, d_isize: int,
+                         d_crc: int, d_out_off: int, d_out: int, out_bytes: int, d_status: int, d_counts: int, stream: int = 0):
+        """asynchronous, device-resident BGZF inflate (pv_bgzf_inflate_dev): every argument a device address; statuses in
+        d_status [n_blocks], {bytes, status, first bad block, its status} in d_counts (int64 [4]). Uses no workspace: it may
+        run on its own stream beside the builder / RNN calls of this context."""
+        _ffi.check(self.lib.pv_bgzf_inflate_dev(self.handle, d_payload, int(payload_bytes), int(n_blocks), d_in_off, d_clen,
+                                                d_isize, d_crc, d_out_off, d_out, int(out_bytes), d_status, d_counts,
+                                                stream or None))
+
     def polish_stitch_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_region_start: int, n_regions: int,
                           d_region_off: int, d_seq: int, seq_capacity: int, d_counts: int, stream: int = 0):
         """asynchronous, device-resident stitch (pv_polish_stitch_dev): the labels of dout's first n_chunks chunks -> polished

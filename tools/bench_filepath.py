@@ -6,6 +6,9 @@ The BAM is synthetic (SURVEY 8(d) shape: one contig of >= 1 Mbp at 60x, 10 kb re
 with the library's own BAM writer (pvio_write_bam); nothing under oracle/ is used. Not part of `value`.
 
   python tools/bench_filepath.py [--mbp 3.2]   (32 intervals of 100 kb: two per reader thread of a 16-core share)
+  python tools/bench_filepath.py --gpu_inflate [--out result.json]
+        the fused path with the host inflate (default) and with `gpu_inflate=True`, alternating, three runs each: wall and
+        Mbp/s of both modes, the inflate kernel's time and output GB/s, H2D / D2H time. (bench.py calls run() only.)
 """
 import argparse
 import json
@@ -127,10 +130,73 @@ def run(ctx, weights, dev=None, mbp=3.2, keep_dir=None):
             shutil.rmtree(d, ignore_errors=True)
 
 
+def run_gpu_inflate(ctx, weights, mbp=3.2, runs=3):
+    """host vs GPU BGZF inflate on the fused call_variant path: alternating runs, `runs` of each"""
+    from pepper_thesis_amd import pipeline
+    from pepper_thesis_amd.batch import PRESETS
+    d = tempfile.mkdtemp(prefix="pv_filepath_gi_")
+    try:
+        contig_len = int(mbp * 1_000_000)
+        bam, fa, info = make_files(d, contig_len)
+        P = PRESETS["ont_r9_guppy5_sup"]
+        swept = contig_len / 1e6
+        for gi in (False, True):   # warm the page cache, the workspaces and the pinned host pool (untimed)
+            pipeline.call_variant_fused(ctx, weights, bam, fa, os.path.join(d, "warm", "p.hdf"), P, min_mapq=5, gpu_inflate=gi)
+        res = {False: [], True: []}
+        for k in range(runs):
+            for gi in (False, True):
+                t_k = {}
+                n = pipeline.call_variant_fused(ctx, weights, bam, fa, os.path.join(d, "pred_%d" % gi, "pepper_prediction.hdf"), P,
+                                                min_mapq=5, timers=t_k, gpu_inflate=gi)
+                t_k["windows"] = n
+                res[gi].append(t_k)
+
+        def leg(rs, gi):
+            walls = [r["wall_s"] for r in rs]
+            med = sorted(rs, key=lambda r: r["wall_s"])[len(rs) // 2]
+            o = {"wall_s_median": med["wall_s"], "wall_s_runs": walls, "mbp_per_s_median": swept / med["wall_s"],
+                 "mbp_per_s_runs": [swept / w for w in walls], "windows": med["windows"],
+                 "reader_threads": med["reader_threads"], "reader_in_bgzf_cpu_s": med["read_inflate_cpu_s"],
+                 "record_decode_clip_cpu_s": med["read_decode_cpu_s"], "main_thread_waiting_for_readers_s": med["reader_stall_s"],
+                 "device_call_s(builder+rnn)": med["device_call_s"], "upload_s": med["upload_s"], "readback_s": med["readback_s"]}
+            if gi:
+                kms = [r["gpu_inflate_kernel_ms"] for r in rs]
+                o.update({
+                    "inflate_kernel_ms_runs": kms, "inflate_kernel_ms_median": med["gpu_inflate_kernel_ms"],
+                    "inflate_output_GB": med["gpu_inflate_bytes"] / 1e9,
+                    "inflate_output_GB_per_s": med["gpu_inflate_bytes"] / 1e6 / max(med["gpu_inflate_kernel_ms"], 1e-9),
+                    "inflate_launches": med["gpu_inflate_launches"], "blocks_gpu": med["gpu_inflate_blocks"],
+                    "blocks_inflated_on_host": med["gpu_inflate_blocks_host"],
+                    "h2d_ms": med["gpu_inflate_h2d_ms"], "d2h_ms": med["gpu_inflate_d2h_ms"],
+                    "plan_cpu_s": med["gpu_inflate_plan_cpu_s"],
+                    "note": "kernel / H2D / D2H ms are summed over the launches (HIP events on the inflate stream); the copies "
+                            "and kernels of concurrent launches are not serialized against the builder's stream"})
+            return o
+        return {"workload": "synthetic chr20 of %.2f Mbp at 60x (10 kb reads): %d reads, BAM %.1f MB"
+                            % (swept, info["reads"], info["bam_bytes"] / 1e6),
+                "form": "fused call_variant path, host inflate (default) vs gpu_inflate=True, alternating runs",
+                "host_inflate": leg(res[False], False), "gpu_inflate": leg(res[True], True),
+                "host_over_gpu_wall_median": sorted(r["wall_s"] for r in res[False])[runs // 2] /
+                sorted(r["wall_s"] for r in res[True])[runs // 2]}
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--mbp", type=float, default=3.2)
+    ap.add_argument("--gpu_inflate", action="store_true", help="the host-vs-GPU BGZF inflate comparison instead of the default leg")
+    ap.add_argument("--out", type=str, default=None, help="also write the JSON result here")
     a = ap.parse_args()
     from pepper_thesis_amd import runtime, synth
     c = runtime.Context(0)
-    print(json.dumps(run(c, synth.make_weights_p1(1234), mbp=a.mbp), indent=1))
+    if a.gpu_inflate:
+        r = run_gpu_inflate(c, synth.make_weights_p1(1234), mbp=a.mbp)
+    else:
+        r = run(c, synth.make_weights_p1(1234), mbp=a.mbp)
+    txt = json.dumps(r, indent=1)
+    print(txt)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(txt + "\n")
