@@ -141,11 +141,13 @@ def polish_parser(ap=None):
     ap.add_argument("-m", "--model_path", type=str, required=True)
     ap.add_argument("-o", "--output_file", type=str, required=True,
                     help="output prefix; made a directory as in the reference: the FASTA is <output_file>/_pepper_polished.fa")
-    ap.add_argument("-t", "--threads", type=int, default=5, help="reader threads")
+    ap.add_argument("-t", "--threads", type=int, default=5, help="reader threads (with several -d_ids: the total over the ranks)")
     ap.add_argument("-r", "--region", type=str, default=None, help="contig[:start-end]")
     ap.add_argument("-bs", "--batch_size", type=int, default=2048, help="chunks (1000 columns) per device launch")
     ap.add_argument("-g", "--gpu", action="store_true", default=False, help="accepted; this build has no CPU path")
-    ap.add_argument("-d_ids", "--device_ids", type=str, default=None, help="the first id is the device used")
+    ap.add_argument("-d_ids", "--device_ids", type=str, default=None,
+                    help="comma list of device ids: one id picks the device; several ids (at most 16, repeats allowed) start "
+                         "one rank per id, rank r on the r-th id, and rank 0 writes the FASTA")
     ap.add_argument("-w", "--num_workers", type=int, default=4, help="accepted and ignored")
     ap.add_argument("--bf16", action="store_true", default=False,
                     help="PV_DTYPE_BF16_INPUT_GEMM: matrix products on the bf16 MFMA with 3-term split operands")

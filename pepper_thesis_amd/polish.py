@@ -21,8 +21,11 @@ Semantics kept from the reference:
   * output: perform_stitch.py:43-84 - one record per contig with a non-empty sequence, contigs in natural-key order, each
     sequence on one line, at handle_output_directory(-o) + '_pepper_polished.fa' (ImageGenerationUI.py:68-80: -o is made a
     directory, so `-o out/polished` writes `out/polished/_pepper_polished.fa`).
--g and -w are accepted and ignored (there is no CPU path; no DataLoader); -d_ids picks the device (its first id). Several
-ranks (WORLD_SIZE > 1) are refused: multi-GPU polishing is not part of this build.
+-g and -w are accepted and ignored (there is no CPU path; no DataLoader; -g alone means one device). -d_ids with one id picks
+the device. -d_ids with several ids (up to 16, repeats allowed) starts one rank per id in fresh child processes
+(polish_rank.py, as the reference's call_consensus starts one caller per device id): rank r polishes regions i % world == r
+on device ids[r] and rank 0 writes the one FASTA; -t is the total of reader threads over the ranks. A bare WORLD_SIZE > 1
+launch of `polish` (torchrun without this parent) is refused.
 """
 import collections
 import concurrent.futures
@@ -32,7 +35,7 @@ import re
 import sys
 import time
 from datetime import datetime
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -103,6 +106,44 @@ def write_fasta(path: str, seqs: Dict[str, bytes]) -> None:
                 fh.write(">" + contig + "\n" + seqs[contig].decode() + "\n")
 
 
+class Work(NamedTuple):
+    """one region of a run: its place in the run's region list, the -r / contig entry it belongs to, the inclusive interval"""
+    index: int
+    contig_index: int
+    contig: str
+    start: int
+    end: int
+
+
+def polish_work(fasta, bam, region: Optional[str]) -> Tuple[List[Work], int]:
+    """the regions of a run in contig order (the list every rank derives alike) and the draft bases they cover"""
+    work, bases_in = [], 0
+    for ci, (contig, s, e) in enumerate(_contig_list(fasta, bam, region)):
+        ivs = polish_intervals(fasta.get_chromosome_sequence_length(contig), s, e)
+        work += [Work(len(work) + k, ci, contig, a, b) for k, (a, b) in enumerate(ivs)]
+        bases_in += ivs[-1][1] - ivs[0][0] + 1 if ivs else 0   # draft bases covered (the regions overlap)
+    return work, bases_in
+
+
+def merge_pieces(pieces) -> Dict[str, bytes]:
+    """(contig, region start, region index, polished bases) pieces, in any order -> one sequence per contig: the regions in
+    start order (create_consensus_sequence; their kept ranges are disjoint, so this is the reference's string), equal starts
+    (a region listed twice by -r) in region-list order"""
+    by: Dict[str, list] = {}
+    for contig, start, index, seq in pieces:
+        by.setdefault(contig, []).append((start, index, seq))
+    return {c: b"".join(s for _, _, s in sorted(p, key=lambda t: (t[0], t[1]))) for c, p in by.items()}
+
+
+def write_polished_fasta(path: str, pieces) -> Dict[str, bytes]:
+    """merge_pieces, then the FASTA (perform_stitch.py:43-84); -> the sequences"""
+    seqs = merge_pieces(pieces)
+    write_fasta(path, seqs)
+    for c in sorted(seqs, key=natural_key):
+        log("FINISHED PROCESSING %s, POLISHED SEQUENCE LENGTH: %d." % (c, len(seqs[c])))
+    return seqs
+
+
 def _contig_list(fasta, bam, region: Optional[str]):
     """[(contig, start|None, end|None)]: -r as make_images parses it, else the contigs common to the FASTA and the BAM"""
     from .make_images import expand_region_names, parse_region
@@ -118,12 +159,16 @@ def _contig_list(fasta, bam, region: Optional[str]):
 class _DeviceChain:
     """device buffers of the builder -> GRU -> stitch chain, grown on demand"""
 
-    def __init__(self, ctx):
+    def __init__(self, ctx, own_ctx: bool = False):
         import torch
-        self.ctx, self.dev = ctx, "cuda:%d" % ctx.device_id
+        self.ctx, self.dev, self.own_ctx = ctx, "cuda:%d" % ctx.device_id, own_ctx
         self.dout = self.labels = self.seq = None
         self.rout = None
         self.counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
+
+    def close(self):
+        if self.own_ctx:
+            self.ctx.close()
 
     def _ensure(self, chunks: int):
         import torch
@@ -223,6 +268,24 @@ class _DeviceChain:
         return roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes()
 
 
+def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int) -> _DeviceChain:
+    """a context on `device` with the polisher weights loaded, and the chain on it (closing the chain closes the context).
+    shared_device: other ranks use this GPU too, so the option is set before the first device call (the split GRU forms need
+    co-resident workgroups and would time out, poisoning the labels). False leaves the create-time default (PV_SHARED_DEVICE).
+    This is the default `open_chain` of run and polish_rank.run; CPU tests pass a stub with the same signature, whose result
+    has run(batch, windows) -> (region_off, bases) and close()."""
+    from .runtime import Context
+    ctx = Context(device)
+    try:
+        if shared_device:
+            ctx.set_option("shared_device", 1)
+        ctx.load_p2(state_dict, dtype)
+        return _DeviceChain(ctx, own_ctx=True)
+    except BaseException:
+        ctx.close()
+        raise
+
+
 class _RealignedDeviceBatch:
     """a DeviceBatch whose positions and cigars are the realigner's output (same bases, quals, flags, mapq, regions)"""
 
@@ -244,89 +307,103 @@ def _read_ahead(ex, fn, items, depth):
         yield f.result()
 
 
-def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region: Optional[str] = None, batch_size: int = 2048,
-                 threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None,
-                 realign: bool = False) -> str:
-    """-> path of the polished FASTA. batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
-    realign: realign every read to the draft on the device before the builder, as the reference always does."""
-    from .bamio import BamHandler, FastaHandler
+def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int = 2048, threads: int = 5, realign: bool = False,
+                  timers: Optional[dict] = None):
+    """the regions of `work` through the chain -> (contig, region start, region index, polished bases) for every region with
+    reads, in `work` order. This is the whole device part of a run: the single-rank run passes every region, a rank of a
+    multi-device run its share. chain.run(batch, windows) -> (region_off, bases) (_DeviceChain or a CPU test's stub).
+    timers (optional) accumulates read_s, device_s, regions, batches."""
     from .batch import pack_regions
+    from .bamio import BamHandler, FastaHandler
     from .polish_summary import region_from_files
-    from .runtime import Context
-    t_start = time.perf_counter()
-    T = dict(read_s=0.0, device_s=0.0, regions=0, batches=0, bases_in=0, bases_out=0)
-    state_dict = load_polish_model(model_path)
-    own = ctx is None
-    ctx = ctx or Context(0)
-    ctx.load_p2(state_dict, dtype)
-    fa, bm = FastaHandler(fasta), BamHandler(bam)
-    work = []
-    for contig, s, e in _contig_list(fa, bm, region):
-        L = fa.get_chromosome_sequence_length(contig)
-        ivs = polish_intervals(L, s, e)
-        work += [(contig, a, b) for a, b in ivs]
-        T["bases_in"] += ivs[-1][1] - ivs[0][0] + 1 if ivs else 0   # draft bases covered (the regions overlap)
-    out_path = output_fasta_path(out_prefix)
-    log("POLISHING %d REGIONS, OUTPUT: %s" % (len(work), out_path))
+    T = timers if timers is not None else {}
+    for k in ("read_s", "device_s", "regions", "batches"):
+        T.setdefault(k, 0)
     # one reader per thread: the native BAM/FASTA handles are not shared between threads
     import threading
     local = threading.local()
 
-    def read(item):
+    def read(w):
         if not hasattr(local, "h"):
             local.h = (BamHandler(bam), FastaHandler(fasta))
-        return item, region_from_files(local.h[0], local.h[1], *item, realign=realign)
+        return w, region_from_files(local.h[0], local.h[1], w.contig, w.start, w.end, realign=realign)
 
     per_launch = max(1, int(batch_size) // 2)
-    pieces: Dict[str, List[Tuple[int, bytes]]] = {}
-    chain = _DeviceChain(ctx)
 
     def flush(items):
         t0 = time.perf_counter()
         regs = [r for _, r in items]
         roff, seq = chain.run(pack_regions(regs), [r.window for r in regs] if realign else None)
-        for g, ((contig, a, _), _) in enumerate(items):
-            pieces.setdefault(contig, []).append((a, seq[roff[g]:roff[g + 1]]))
+        out = [(w.contig, w.start, w.index, seq[roff[g]:roff[g + 1]]) for g, (w, _) in enumerate(items)]
         T["device_s"] += time.perf_counter() - t0
         T["batches"] += 1
+        return out
 
+    with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, int(threads))) as ex:
+        pending = []
+        t0 = time.perf_counter()
+        for w, reg in _read_ahead(ex, read, work, 2 * per_launch):
+            if reg is None:
+                continue
+            pending.append((w, reg))
+            T["regions"] += 1
+            if len(pending) == per_launch:
+                T["read_s"] += time.perf_counter() - t0
+                yield from flush(pending)
+                pending = []
+                t0 = time.perf_counter()
+        T["read_s"] += time.perf_counter() - t0
+        if pending:
+            yield from flush(pending)
+
+
+def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region: Optional[str] = None, batch_size: int = 2048,
+                 threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None,
+                 realign: bool = False, chain=None) -> str:
+    """-> path of the polished FASTA. batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
+    realign: realign every read to the draft on the device before the builder, as the reference always does.
+    chain: a chain with the weights already loaded (open_device_chain; the caller closes it), else one is made on `ctx`
+    (default: a context on device 0) from model_path."""
+    from .bamio import BamHandler, FastaHandler
+    from .runtime import Context
+    t_start = time.perf_counter()
+    T = dict(read_s=0.0, device_s=0.0, regions=0, batches=0, bases_in=0, bases_out=0)
+    own = None
+    if chain is None:
+        state_dict = load_polish_model(model_path)
+        if ctx is None:
+            ctx = own = Context(0)
+        ctx.load_p2(state_dict, dtype)
+        chain = _DeviceChain(ctx)
     try:
-        with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, int(threads))) as ex:
-            pending = []
-            t0 = time.perf_counter()
-            for item, reg in _read_ahead(ex, read, work, 2 * per_launch):
-                if reg is None:
-                    continue
-                pending.append((item, reg))
-                T["regions"] += 1
-                if len(pending) == per_launch:
-                    T["read_s"] += time.perf_counter() - t0
-                    flush(pending)
-                    pending = []
-                    t0 = time.perf_counter()
-            T["read_s"] += time.perf_counter() - t0
-            if pending:
-                flush(pending)
+        fa, bm = FastaHandler(fasta), BamHandler(bam)
+        work, T["bases_in"] = polish_work(fa, bm, region)
+        out_path = output_fasta_path(out_prefix)
+        log("POLISHING %d REGIONS, OUTPUT: %s" % (len(work), out_path))
+        pieces = list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T))
     finally:
-        if own:
-            ctx.close()
-    # regions in start order (create_consensus_sequence): their kept ranges are disjoint, so this is the reference's string
-    seqs = {c: b"".join(s for _, s in sorted(p, key=lambda t: t[0])) for c, p in pieces.items()}
-    write_fasta(out_path, seqs)
+        if own is not None:
+            own.close()
+    seqs = write_polished_fasta(out_path, pieces)
     T["bases_out"] = sum(len(s) for s in seqs.values())
     T["wall_s"] = time.perf_counter() - t_start
-    for c in sorted(seqs, key=natural_key):
-        log("FINISHED PROCESSING %s, POLISHED SEQUENCE LENGTH: %d." % (c, len(seqs[c])))
     if timers is not None:
         timers.update(T)
     return out_path
 
 
-def run(args) -> int:
-    from . import cli
+def run(args, open_chain=open_device_chain) -> int:
+    """the `polish` command. With several -d_ids: check the inputs here (no GPU API is touched), then start one rank per id
+    and wait for them (polish_rank.launch). open_chain: see open_device_chain (CPU tests pass a stub)."""
+    from . import cli, polish_rank
     _, world, device = cli.rank_world_device(args)
     if world > 1:
         sys.stderr.write("ERROR: polish runs on one process (WORLD_SIZE=%d): multi-rank polishing is not part of this build.\n" % world)
+        return 2
+    try:
+        plan = polish_rank.plan_ranks(args.device_ids, args.threads)
+    except ValueError as e:
+        sys.stderr.write("ERROR: %s\n" % e)
         return 2
     for what, path in (("BAM", args.bam), ("FASTA", args.fasta), ("MODEL", args.model_path)):
         if not os.path.isfile(path):
@@ -336,18 +413,18 @@ def run(args) -> int:
         sys.stderr.write("ERROR: THREADS AND batch_size NEED TO BE > 0.\n")
         return 1
     try:
-        load_polish_model(args.model_path)
+        state_dict = load_polish_model(args.model_path)
     except ValueError as e:
         sys.stderr.write("ERROR: %s\n" % e)
         return 2
-    from .runtime import Context
-    ctx = Context(device)
+    if len(plan) > 1:
+        return polish_rank.launch(args, plan)
+    chain = open_chain(device, False, state_dict, _ffi.PV_DTYPE_BF16_INPUT_GEMM if args.bf16 else _ffi.PV_DTYPE_F32)
     try:
         T = {}
         path = polish_fused(args.bam, args.fasta, args.model_path, args.output_file, args.region, args.batch_size, args.threads,
-                            _ffi.PV_DTYPE_BF16_INPUT_GEMM if args.bf16 else _ffi.PV_DTYPE_F32, ctx=ctx, timers=T,
-                            realign=bool(getattr(args, "realign", False)))
+                            timers=T, realign=bool(getattr(args, "realign", False)), chain=chain)
     finally:
-        ctx.close()
+        chain.close()
     log("POLISHED FASTA: %s (%d REGIONS, %d BASES IN %.2f SEC)" % (path, T["regions"], T["bases_out"], T["wall_s"]))
     return 0

@@ -12,7 +12,12 @@
               realigner alone on every region of the workload (launches of the chain's size), its kernels timed with HIP
               events: forward + reverse DP cells, banded cells (score-only passes + the direction pass) and GCUPS.
 
-  python tools/bench_polish_e2e.py [--leg stitch|e2e|all] [--mbp 2.0] [--reps 20] [--realign]
+  --d_ids a,b,...: the e2e leg runs the `polish` command instead, in fresh processes: once with `-d_ids a,b,...` (one rank per
+              id) and once on device a alone with PV_SHARED_DEVICE=1 (the kernel forms the ranks use when they share a device);
+              wall times of both and whether the two FASTA files are byte-identical. Ranks that share one card split its CPUs
+              and its device: such a wall time is a correctness rehearsal, not a scaling figure.
+
+  python tools/bench_polish_e2e.py [--leg stitch|e2e|all] [--mbp 2.0] [--reps 20] [--realign] [--d_ids 0,0]
 For the rocprofv3 row run the stitch leg alone under `rocprofv3 --kernel-trace --stats -d <dir> -- python ... --leg stitch`.
 """
 import argparse
@@ -196,6 +201,46 @@ def e2e_leg(mbp=2.0, threads=16, realign=False):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def _polish_command(bam, fa, model, out, threads, d_ids, realign, shared_env):
+    import subprocess
+    env = dict(os.environ, PYTHONPATH=ROOT + (os.pathsep + os.environ["PYTHONPATH"] if os.environ.get("PYTHONPATH") else ""))
+    env.pop("PV_SHARED_DEVICE", None)
+    if shared_env:
+        env["PV_SHARED_DEVICE"] = "1"
+    cmd = [sys.executable, "-m", "pepper_thesis_amd", "polish", "-b", bam, "-f", fa, "-m", model, "-o", out, "-t", str(threads),
+           "-d_ids", d_ids] + (["--realign"] if realign else [])
+    t0 = time.perf_counter()
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1800)
+    wall = time.perf_counter() - t0
+    if r.returncode != 0:
+        raise RuntimeError("polish -d_ids %s: exit status %d\n%s" % (d_ids, r.returncode, r.stderr[-3000:]))
+    with open(os.path.join(out, "_pepper_polished.fa"), "rb") as fh:
+        return fh.read(), round(wall, 3)
+
+
+def ranks_leg(mbp=2.0, threads=16, d_ids="0,0", realign=False):
+    """`polish -d_ids <d_ids>` against `polish -d_ids <first id>` with PV_SHARED_DEVICE=1, each a fresh process (start-up, context
+    creation and model load included in the wall time)"""
+    import numpy as np
+    from bench_filepath import make_files
+    from pepper_thesis_amd import synth
+    d = tempfile.mkdtemp(prefix="pv_polish_ranks_")
+    try:
+        bam, fa, info = make_files(d, int(mbp * 1_000_000))
+        model = os.path.join(d, "model.npz")
+        np.savez(model, **synth.make_weights_p2(4321, 3.0))
+        first = d_ids.split(",")[0]
+        one, wall_one = _polish_command(bam, fa, model, os.path.join(d, "one"), threads, first, realign, True)
+        many, wall_many = _polish_command(bam, fa, model, os.path.join(d, "many"), threads, d_ids, realign, False)
+        return {"draft_bp": int(mbp * 1_000_000), "reads": info["reads"], "realign": realign, "reader_threads_total": threads,
+                "single": {"d_ids": first, "env": "PV_SHARED_DEVICE=1", "wall_s": wall_one, "fasta_bytes": len(one)},
+                "ranks": {"d_ids": d_ids, "wall_s": wall_many, "fasta_bytes": len(many)},
+                "identical": one == many,
+                "note": "ranks sharing a device split its CPUs and the card: a correctness rehearsal, not a scaling figure"}
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--leg", choices=("stitch", "e2e", "all"), default="all")
@@ -203,12 +248,14 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--realign", action="store_true", help="e2e leg without and with polish --realign, plus realigner stats")
+    ap.add_argument("--d_ids", type=str, default=None,
+                    help="e2e leg: the polish command with these -d_ids against the first id alone with PV_SHARED_DEVICE=1")
     a = ap.parse_args()
     out = {}
     if a.leg in ("stitch", "all"):
         out["stitch"] = stitch_leg(a.reps)
     if a.leg in ("e2e", "all"):
-        out["e2e"] = e2e_leg(a.mbp, a.threads, a.realign)
+        out["e2e"] = ranks_leg(a.mbp, a.threads, a.d_ids, a.realign) if a.d_ids else e2e_leg(a.mbp, a.threads, a.realign)
     print(json.dumps(out, indent=1))
 
 
