@@ -6,7 +6,8 @@ FindCandidates.py:157-166. h5py is not installed for this interpreter, so this m
 C library itself (libhdf5, present in the image under /opt/conda/lib) through ctypes; files are
 therefore real HDF5 written by the same library h5py wraps: contiguous datasets, fixed-length byte
 strings for `contigs`, variable-length UTF-8 strings of shape (N,1) for `candidates`
-(h5py.special_dtype(vlen=str)), int32/uint8/int8/float64 numerics.
+(h5py.special_dtype(vlen=str)), int32/uint8/int8/float64 numerics, and scalar datasets (H5S_SCALAR, what h5py
+makes of `f[path] = 5` or `f[path] = "ctg"`) for the polisher's per-chunk metadata.
 
 Fails loudly (ImportError) if no libhdf5 can be found; set PEPPER_HDF5_LIB to point at one.
 """
@@ -27,6 +28,7 @@ H5T_CSET_ASCII, H5T_CSET_UTF8 = 0, 1
 H5T_STR_NULLTERM, H5T_STR_NULLPAD = 0, 1
 H5T_INTEGER, H5T_FLOAT, H5T_STRING = 0, 1, 3
 H5T_SGN_NONE = 0
+H5S_SCALAR, H5S_SIMPLE = 0, 1
 
 _lib = None
 
@@ -63,7 +65,7 @@ def lib():
     else:
         raise ImportError("libhdf5 not found (looked in PEPPER_HDF5_LIB, the linker path, /opt/conda/lib): %r" % (err,))
     hid_fns = ["H5Fcreate", "H5Fopen", "H5Pcreate", "H5Gcreate2", "H5Gopen2", "H5Screate_simple", "H5Tcopy",
-               "H5Dcreate2", "H5Dopen2", "H5Dget_space", "H5Dget_type", "H5Tget_native_type"]
+               "H5Dcreate2", "H5Dopen2", "H5Dget_space", "H5Dget_type", "H5Tget_native_type", "H5Screate"]
     for f in hid_fns:
         getattr(L, f).restype = hid_t
     L.H5Fcreate.argtypes = [C.c_char_p, C.c_uint, hid_t, hid_t]
@@ -81,6 +83,8 @@ def lib():
     L.H5Lget_name_by_idx.restype = C.c_ssize_t
     L.H5Screate_simple.argtypes = [C.c_int, C.POINTER(hsize_t), C.POINTER(hsize_t)]
     L.H5Sclose.argtypes = [hid_t]
+    L.H5Screate.argtypes = [C.c_int]
+    L.H5Sget_simple_extent_type.argtypes = [hid_t]
     L.H5Sget_simple_extent_ndims.argtypes = [hid_t]
     L.H5Sget_simple_extent_dims.argtypes = [hid_t, C.POINTER(hsize_t), C.POINTER(hsize_t)]
     L.H5Tcopy.argtypes = [hid_t]
@@ -180,8 +184,14 @@ class H5File:
         self.write(path, value)
 
     def write(self, path: str, value, vlen_str: bool = False):
-        """numeric / fixed 'S' numpy arrays, or (vlen_str=True) a nested list / object array of str"""
+        """numeric / fixed 'S' numpy arrays, or (vlen_str=True) a nested list / object array of str.
+        A scalar goes to a scalar dataspace (H5S_SCALAR) as h5py writes it: a Python int as int64, a str as a variable-length
+        UTF-8 string, bytes or a 0-d array in its own type (bytes: a fixed-length string)."""
         L = lib()
+        scalar = np.ndim(value) == 0 and not vlen_str
+        if scalar:
+            vlen_str = isinstance(value, str)
+            value = [value] if vlen_str else np.asarray(value, dtype=np.int64 if isinstance(value, int) else None).reshape(1)
         if vlen_str:
             arr = np.asarray(value, dtype=object)
             flat = [s if isinstance(s, bytes) else str(s).encode("utf-8") for s in arr.ravel()]
@@ -204,8 +214,12 @@ class H5File:
             else:
                 raise TypeError("unsupported dtype %s" % arr.dtype)
             shape, buf = arr.shape, C.c_void_p(arr.ctypes.data)
-        dims = (hsize_t * max(len(shape), 1))(*shape)
-        sid = _chk(L.H5Screate_simple(len(shape), dims, None), "H5Screate_simple")
+        if scalar:
+            shape = ()
+            sid = _chk(L.H5Screate(H5S_SCALAR), "H5Screate")
+        else:
+            dims = (hsize_t * max(len(shape), 1))(*shape)
+            sid = _chk(L.H5Screate_simple(len(shape), dims, None), "H5Screate_simple")
         did = _chk(L.H5Dcreate2(self.fid, path.encode(), ftid, sid, self.lcpl, H5P_DEFAULT, H5P_DEFAULT), "H5Dcreate2 " + path)
         if int(np.prod(shape)) > 0:
             _chk(L.H5Dwrite(did, mtid, H5S_ALL, H5S_ALL, H5P_DEFAULT, buf), "H5Dwrite " + path)
@@ -215,8 +229,24 @@ class H5File:
             L.H5Tclose(ftid)
 
     # ---- read ------------------------------------------------------------------------------------------
+    def space_class(self, path: str) -> int:
+        """the dataspace class of a dataset: H5S_SCALAR or H5S_SIMPLE (H5S_NULL = 2)"""
+        L = lib()
+        did = _chk(L.H5Dopen2(self.fid, path.encode(), H5P_DEFAULT), "H5Dopen2 " + path)
+        sid = L.H5Dget_space(did)
+        try:
+            return int(L.H5Sget_simple_extent_type(sid))
+        finally:
+            L.H5Sclose(sid)
+            L.H5Dclose(did)
+
     def read(self, path: str):
-        """-> numpy array; variable-length strings come back as an object array of str (decoded UTF-8)"""
+        """-> numpy array; variable-length strings come back as an object array of str (decoded UTF-8). A scalar dataspace
+        gives a scalar: a str for a variable-length string, numpy bytes for a fixed-length one, a numpy number otherwise."""
+        out = self._read(path)
+        return out[()] if out.ndim == 0 else out
+
+    def _read(self, path: str) -> np.ndarray:
         L = lib()
         did = _chk(L.H5Dopen2(self.fid, path.encode(), H5P_DEFAULT), "H5Dopen2 " + path)
         sid = L.H5Dget_space(did)
@@ -357,3 +387,132 @@ class PredictionStore:
             base = "%s/%s/" % (self._prediction_path_, name)
             yield name, {k: self.f.read(base + k) for k in
                          ("contigs", "positions", "depths", "candidates", "candidate_frequency", "base_prediction")}
+
+
+# ---- the polisher's two stores (pepper/modules/python/DataStore.py, DataStorePredict.py) -------------------------------
+
+def _str_scalar(v) -> str:
+    """a contig name as h5py readers may have stored it: variable-length str or fixed-length bytes"""
+    if isinstance(v, (bytes, np.bytes_)):
+        return bytes(v).rstrip(b"\0").decode("utf-8")
+    return str(v)
+
+
+class PolishImageStore:
+    """the polisher's image file (pepper/modules/python/DataStore.py:53-67), inference mode: one group per chunk,
+    summaries/<contig>_<region_start>_<region_end>_<chunk_id>/ holding image uint8 [L,10], label uint8 [L] (all zero),
+    position int64 [L], index int64 [L] (-1 on padding rows), and the scalars contig (variable-length UTF-8 str),
+    region_start, region_end, chunk_id (int64), each in a scalar dataspace as h5py writes `f[path] = value`."""
+    _summary_path_ = "summaries"
+
+    def __init__(self, filename: str, mode: str = "r"):
+        self.f = H5File(filename, mode)
+        self._written = set()
+
+    def close(self):
+        self.f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @staticmethod
+    def summary_name(contig: str, region_start: int, region_end: int, chunk_id: int) -> str:
+        """ImageGenerationUI.py:219"""
+        return "%s_%d_%d_%d" % (contig, region_start, region_end, chunk_id)
+
+    def write_chunk(self, contig: str, region_start: int, region_end: int, chunk_id: int, image, position, index):
+        name = self.summary_name(contig, region_start, region_end, chunk_id)
+        if name in self._written:   # DataStore.write_summary keeps the first
+            return
+        self._written.add(name)
+        base = "%s/%s/" % (self._summary_path_, name)
+        image = np.asarray(image, dtype=np.uint8)
+        self.f.write(base + "image", image)
+        self.f.write(base + "label", np.zeros(image.shape[0], dtype=np.uint8))
+        self.f.write(base + "position", np.asarray(position, dtype=np.int64))
+        self.f.write(base + "index", np.asarray(index, dtype=np.int64))
+        self.f.write(base + "contig", str(contig))
+        self.f.write(base + "region_start", int(region_start))
+        self.f.write(base + "region_end", int(region_end))
+        self.f.write(base + "chunk_id", int(chunk_id))
+
+    def summaries(self) -> List[str]:
+        """the chunk group names in HDF5 name order (h5py's keys() order)"""
+        return self.f.keys("/" + self._summary_path_) if self._summary_path_ in self.f else []
+
+    def read_chunk(self, name: str) -> dict:
+        """-> contig str, region_start / region_end / chunk_id int, image uint8, position / index int64. Accepts what the
+        reference's h5py writes too: fixed-length contig strings, int32 index or position."""
+        base = "%s/%s/" % (self._summary_path_, name)
+        r = self.f.read
+        return dict(contig=_str_scalar(r(base + "contig")), region_start=int(r(base + "region_start")),
+                    region_end=int(r(base + "region_end")), chunk_id=int(r(base + "chunk_id")),
+                    image=np.asarray(r(base + "image"), dtype=np.uint8),
+                    position=np.asarray(r(base + "position"), dtype=np.int64),
+                    index=np.asarray(r(base + "index"), dtype=np.int64))
+
+
+class PolishPredictionStore:
+    """the polisher's prediction file (pepper/modules/python/DataStorePredict.py:49-78): per region
+    predictions/<contig>/<contig>-<start>-<end>/{contig_start, contig_end} (int64 scalars) and per chunk, under that group,
+    <chunk_id>/{position int64 [L], index int64 [L], bases uint8 [L], phred_score uint8 [L]}."""
+    _prediction_path_ = "predictions"
+
+    def __init__(self, filename: str, mode: str = "r"):
+        self.f = H5File(filename, mode)
+        self._regions, self._chunks = set(), set()
+
+    def close(self):
+        self.f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @staticmethod
+    def region_name(contig: str, start: int, end: int) -> str:
+        return "%s-%d-%d" % (contig, start, end)
+
+    def write_prediction(self, contig: str, contig_start: int, contig_end: int, chunk_id: int, position, index, bases,
+                         phred_score):
+        region = self.region_name(contig, contig_start, contig_end)
+        base = "%s/%s/%s/" % (self._prediction_path_, contig, region)
+        if region not in self._regions:
+            self._regions.add(region)
+            self.f.write(base + "contig_start", int(contig_start))
+            self.f.write(base + "contig_end", int(contig_end))
+        if (region, int(chunk_id)) in self._chunks:   # write_prediction keeps the first
+            return
+        self._chunks.add((region, int(chunk_id)))
+        base += "%d/" % int(chunk_id)
+        self.f.write(base + "position", np.asarray(position, dtype=np.int64))
+        self.f.write(base + "index", np.asarray(index, dtype=np.int64))
+        self.f.write(base + "bases", np.asarray(bases, dtype=np.uint8))
+        self.f.write(base + "phred_score", np.asarray(phred_score, dtype=np.uint8))
+
+    def contigs(self) -> List[str]:
+        return self.f.keys("/" + self._prediction_path_) if self._prediction_path_ in self.f else []
+
+    def regions(self, contig: str) -> List[str]:
+        return self.f.keys("/%s/%s" % (self._prediction_path_, contig))
+
+    def region_span(self, contig: str, region: str) -> Tuple[int, int]:
+        base = "%s/%s/%s/" % (self._prediction_path_, contig, region)
+        return int(self.f.read(base + "contig_start")), int(self.f.read(base + "contig_end"))
+
+    def chunk_names(self, contig: str, region: str) -> List[str]:
+        """the chunk groups of a region (every key but contig_start / contig_end, Stitch.py:51), in HDF5 name order"""
+        return [k for k in self.f.keys("/%s/%s/%s" % (self._prediction_path_, contig, region))
+                if k not in ("contig_start", "contig_end")]
+
+    def read_chunk(self, contig: str, region: str, chunk: str) -> dict:
+        """-> position / index int64, bases uint8 (int32 index of other writers is widened)"""
+        base = "%s/%s/%s/%s/" % (self._prediction_path_, contig, region, chunk)
+        r = self.f.read
+        return dict(position=np.asarray(r(base + "position"), dtype=np.int64), index=np.asarray(r(base + "index"), dtype=np.int64),
+                    bases=np.asarray(r(base + "bases"), dtype=np.uint8))

@@ -1,0 +1,99 @@
+"""The polisher's command line (pepper/pepper.py:24-260): `python -m pepper_thesis_amd.pepper <sub-command> ...`.
+
+  polish          BAM + draft -> polished FASTA, every stage on the device (polish.py; the parser of `python -m
+                  pepper_thesis_amd polish`, unchanged)
+  make_images     BAM + draft -> image HDF5 files              (polish_steps.make_images_run)
+  call_consensus  image files -> prediction HDF5 files         (polish_steps.call_consensus_run)
+  stitch          prediction files -> polished FASTA           (polish_steps.stitch_run)
+
+A program of its own, as in the reference: its `make_images` is the polisher's, not the variant caller's sub-command of the
+same name (`python -m pepper_thesis_amd make_images`). download_models and torch_stat are not part of this build.
+"""
+import argparse
+import sys
+
+from . import cli
+
+
+def make_images_parser(ap=None):
+    """add_make_images_arguments (pepper/pepper.py:104-147), plus --realign as in polish"""
+    ap = ap or argparse.ArgumentParser(prog="make_images")
+    ap.add_argument("-b", "--bam", type=str, required=True, help="BAM file of the reads aligned to the draft assembly")
+    ap.add_argument("-f", "--fasta", type=str, required=True, help="FASTA file of the draft assembly")
+    ap.add_argument("-r", "--region", type=str, default=None, help="contig[:start-end]")
+    ap.add_argument("-o", "--output_dir", type=str, required=True, default="make_image_output/",
+                    help="output directory, created if missing")
+    ap.add_argument("-t", "--threads", type=int, default=5,
+                    help="reader threads, and the number of image files (region i goes to file i %% threads)")
+    ap.add_argument("--realign", action="store_true", default=False,
+                    help="realign every read to the draft (Smith-Waterman on the device) before the images are built, as "
+                         "polish --realign; the reference always does this. Off by default")
+    return ap
+
+
+def call_consensus_parser(ap=None):
+    """add_call_consensus_arguments (pepper/pepper.py:150-218), plus --bf16 as in polish"""
+    ap = ap or argparse.ArgumentParser(prog="call_consensus")
+    ap.add_argument("-i", "--image_dir", type=str, required=True, help="directory of the image HDF5 files")
+    ap.add_argument("-m", "--model_path", type=str, required=True, help="the polisher model")
+    ap.add_argument("-o", "--output_dir", type=str, required=True, default="output", help="output directory")
+    ap.add_argument("-bs", "--batch_size", type=int, default=2048,
+                    help="chunks (1000 columns) per device launch; default 2048 as in polish (the reference's is 128)")
+    ap.add_argument("-g", "--gpu", action="store_true", default=False, help="accepted; this build has no CPU path")
+    ap.add_argument("-d_ids", "--device_ids", type=str, default=None,
+                    help="comma list of device ids: one id picks the device; several ids (at most 16, repeats allowed) start "
+                         "one caller per id, caller r on the r-th id writing pepper_prediction_<id>.hdf (<id>_<r> for a "
+                         "repeated id)")
+    ap.add_argument("-w", "--num_workers", type=int, default=4, help="accepted and ignored")
+    ap.add_argument("-t", "--threads", type=int, default=8, help="accepted and ignored (there is no CPU path)")
+    ap.add_argument("--bf16", action="store_true", default=False,
+                    help="PV_DTYPE_BF16_INPUT_GEMM: matrix products on the bf16 MFMA with 3-term split operands")
+    return ap
+
+
+def stitch_parser(ap=None):
+    """add_stitch_arguments (pepper/pepper.py:221-253)"""
+    ap = ap or argparse.ArgumentParser(prog="stitch")
+    ap.add_argument("-i", "--input_dir", type=str, required=True, help="directory of the prediction HDF5 files")
+    ap.add_argument("-o", "--output_file", type=str, required=True,
+                    help="output prefix: the FASTA is <output_file>_pepper_polished.fa (parent directories are created)")
+    ap.add_argument("-t", "--threads", type=int, default=5, help="accepted and ignored (the stitch runs on the device)")
+    return ap
+
+
+def parser():
+    ap = argparse.ArgumentParser(prog="pepper", description="PEPPER polisher on the MI355X-native hot path: polish, or its three "
+                                                            "steps make_images -> call_consensus -> stitch through files")
+    ap.add_argument("--version", action="store_true", default=False)
+    sub = ap.add_subparsers(dest="sub_command")
+    cli.polish_parser(sub.add_parser("polish", help="make_images -> call_consensus -> stitch on the device, without files"))
+    make_images_parser(sub.add_parser("make_images", help="image HDF5 files of the reads aligned to the draft"))
+    call_consensus_parser(sub.add_parser("call_consensus", help="prediction HDF5 files from the image files and a model"))
+    stitch_parser(sub.add_parser("stitch", help="the polished FASTA from the prediction files"))
+    return ap
+
+
+def main(argv=None) -> int:
+    ap = parser()
+    args = ap.parse_args(argv)
+    if args.version:
+        print("PEPPER VERSION: ", cli.__version__)
+        return 0
+    if args.sub_command == "polish":
+        from . import polish
+        return polish.run(args)
+    from . import polish_steps
+    if args.sub_command == "make_images":
+        return polish_steps.make_images_run(args)
+    if args.sub_command == "call_consensus":
+        return polish_steps.call_consensus_run(args)
+    if args.sub_command == "stitch":
+        return polish_steps.stitch_run(args)
+    sys.stderr.write("ERROR: NO SUBCOMMAND SELECTED. PLEASE SELECT ONE OF THE AVAIABLE SUB-COMMANDS.\n")
+    ap.print_help()
+    return 2
+
+
+if __name__ == "__main__":
+    rc = main()
+    sys.exit(rc if isinstance(rc, int) else 0)

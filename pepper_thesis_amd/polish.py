@@ -243,16 +243,25 @@ class _DeviceChain:
             return realigned_batch(batch, res)
         return host, rdb
 
-    def run(self, batch, windows=None) -> Tuple[np.ndarray, bytes]:
-        """one batch of regions -> (region_off [n_regions+1], polished bases of all its regions, concatenated).
+    def p2_labels(self, images: np.ndarray) -> np.ndarray:
+        """P2 labels uint8 [B,1000] of host images uint8 [B,1000,10] (pv_rnn_forward_p2: PV_ERR_STATE if the call was
+        poisoned); the chain of `call_consensus`"""
+        return self.ctx.forward_p2(images)
+
+    def build(self, batch, windows=None):
+        """[realignment ->] builder for one batch of regions -> (device batch, n_chunks); the chunks are in self.dout.
         windows: the realignment window of every region (polish --realign), else None."""
         from .device import DeviceBatch
         db = DeviceBatch(batch, self.dev)
         if windows is not None:
             host, db = self._realign(batch, db, windows)
-            n = self._summarize(None, db, host)
-        else:
-            n = self._summarize(batch, db)
+            return db, self._summarize(None, db, host)
+        return db, self._summarize(batch, db)
+
+    def run(self, batch, windows=None) -> Tuple[np.ndarray, bytes]:
+        """one batch of regions -> (region_off [n_regions+1], polished bases of all its regions, concatenated).
+        windows: the realignment window of every region (polish --realign), else None."""
+        db, n = self.build(batch, windows)
         region_off = np.zeros(batch.n_regions + 1, np.int64)
         if n == 0:
             return region_off, b""

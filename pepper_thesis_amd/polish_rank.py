@@ -50,12 +50,12 @@ def parse_device_ids(device_ids: Optional[str]) -> List[int]:
         raise ValueError("-d_ids %r: expected a comma list of device ids" % device_ids) from None
 
 
-def plan_ranks(device_ids: Optional[str], threads: int) -> List[RankPlan]:
+def plan_ranks(device_ids: Optional[str], threads: int, what: str = "polish") -> List[RankPlan]:
     """-d_ids -> one RankPlan per listed id (rank r on ids[r]); no -d_ids is one rank on device 0. A pure function: no GPU
-    API is touched. More than MAX_RANKS ids are refused (ValueError)."""
+    API is touched. More than MAX_RANKS ids are refused (ValueError). what: the command, for the message."""
     ids = parse_device_ids(device_ids) or [0]
     if len(ids) > MAX_RANKS:
-        raise ValueError("-d_ids lists %d ids: polish starts at most %d ranks" % (len(ids), MAX_RANKS))
+        raise ValueError("-d_ids lists %d ids: %s starts at most %d ranks" % (len(ids), what, MAX_RANKS))
     world = len(ids)
     return [RankPlan(r, d, ids.count(d) > 1, max(1, int(threads) // world)) for r, d in enumerate(ids)]
 
@@ -85,10 +85,11 @@ def _describe(rc: int) -> str:
     return "signal %d" % -rc if rc < 0 else "exit status %d" % rc
 
 
-def supervise(cmds: List[List[str]], envs: List[dict], poll_s: float = 0.2) -> int:
+def supervise(cmds: List[List[str]], envs: List[dict], poll_s: float = 0.2, what: str = "polish",
+              lost: str = "no FASTA written") -> int:
     """start one child per command and wait for all of them -> 0 when every child exits 0. The first child that exits
     non-zero or dies on a signal stops the others (SIGTERM, then SIGKILL after 10 s); its status is returned (1 for a
-    signal). Nothing is restarted."""
+    signal). Nothing is restarted. what / lost: the command and what its failure leaves out, for the message."""
     from .polish import log
     procs = []
     failed = None
@@ -120,20 +121,23 @@ def supervise(cmds: List[List[str]], envs: List[dict], poll_s: float = 0.2) -> i
                 p.wait()
     if failed is not None:
         r, rc = failed
-        sys.stderr.write("ERROR: polish: rank %d ended with %s%s; no FASTA written.\n"
-                         % (r, _describe(rc), "; %d other rank(s) stopped" % len(stopped) if stopped else ""))
+        sys.stderr.write("ERROR: %s: rank %d ended with %s%s; %s.\n"
+                         % (what, r, _describe(rc), "; %d other rank(s) stopped" % len(stopped) if stopped else "", lost))
         return rc if rc > 0 else 1
     log("ALL %d RANKS FINISHED" % len(procs))
     return 0
 
 
-def launch(args, plan: List[RankPlan]) -> int:
-    """the parent of a multi-device run: one `python -m pepper_thesis_amd.polish_rank` child per plan entry. Touches no GPU API
-    (a process that has initialised the GPU must not be forked into ranks)."""
+def launch(args, plan: List[RankPlan], cmd: Optional[List[str]] = None, what: str = "polish",
+           lost: str = "no FASTA written") -> int:
+    """the parent of a multi-device run: one child per plan entry, by default `python -m pepper_thesis_amd.polish_rank`
+    with the polish options (cmd: another rank command, the same for every rank; the rank reads RANK / WORLD_SIZE). Touches
+    no GPU API (a process that has initialised the GPU must not be forked into ranks)."""
     from .polish import log
     world = len(plan)
     pkg_root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, "-m", "pepper_thesis_amd.polish_rank"] + rank_argv(args, plan)
+    if cmd is None:
+        cmd = [sys.executable, "-m", "pepper_thesis_amd.polish_rank"] + rank_argv(args, plan)
     port = str(_free_port())
     envs = []
     for p in plan:
@@ -142,7 +146,7 @@ def launch(args, plan: List[RankPlan]) -> int:
         env["PYTHONPATH"] = pkg_root + (os.pathsep + os.environ["PYTHONPATH"] if os.environ.get("PYTHONPATH") else "")
         envs.append(env)
     log("STARTING %d RANKS ON DEVICES %s" % (world, ",".join(str(p.device) for p in plan)))
-    return supervise([cmd] * world, envs)
+    return supervise([cmd] * world, envs, what=what, lost=lost)
 
 
 def _polish_share(args, me: RankPlan, world: int, open_chain, T: dict):

@@ -332,9 +332,10 @@ class Context:
             dout.seq_overlap, d_region_off, d_seq, int(seq_capacity), d_counts, stream or None))
 
     def polish_stitch(self, out, labels: np.ndarray, region_start: np.ndarray, seq_capacity: int = None,
-                      seq_length: int = 1000, seq_overlap: int = 50):
+                      seq_length: int = 1000, seq_overlap: int = 50, counts=None):
         """host-buffer stitch (pv_polish_stitch) of a PolishOut and its labels -> (region_off int64 [n_regions+1], seq bytes).
-        seq_capacity None: every column's worth; a smaller one raises PepperHipError(PV_ERR_CAPACITY)."""
+        seq_capacity None: every column's worth; a smaller one raises PepperHipError(PV_ERR_CAPACITY).
+        counts: optional ctypes int64[4] that receives {bases, status, first bad chunk, 0}, also when the call raises."""
         n = int(len(out.chunk_id))
         c = _ffi.pv_polish_out()
         keep = [np.ascontiguousarray(out.position, np.int64), np.ascontiguousarray(out.index, np.int32),
@@ -347,7 +348,8 @@ class Context:
         cap = n * seq_length if seq_capacity is None else int(seq_capacity)
         region_off = np.zeros(len(rs) + 1, np.int64)
         seq = np.zeros(max(cap, 1), np.uint8)
-        counts = (C.c_int64 * 4)()
+        if counts is None:
+            counts = (C.c_int64 * 4)()
         _ffi.check(self.lib.pv_polish_stitch(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rs), len(rs), seq_length,
                                              seq_overlap, _ffi.ptr(region_off), _ffi.ptr(seq), cap, counts))
         return region_off, seq[:int(counts[0])].tobytes()

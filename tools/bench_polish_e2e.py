@@ -17,7 +17,12 @@
               wall times of both and whether the two FASTA files are byte-identical. Ranks that share one card split its CPUs
               and its device: such a wall time is a correctness rehearsal, not a scaling figure.
 
-  python tools/bench_polish_e2e.py [--leg stitch|e2e|all] [--mbp 2.0] [--reps 20] [--realign] [--d_ids 0,0]
+  steps leg:  the same synthetic contig through `python -m pepper_thesis_amd.pepper make_images -> call_consensus -> stitch`
+              and through `pepper polish`, each command a fresh process with PV_SHARED_DEVICE=1 (start-up, context creation
+              and model load included): wall time of every command, the sizes of the image and prediction files, and whether
+              the two FASTA files are byte-identical. Written to profiles/polish_steps_bench.json with --out.
+
+  python tools/bench_polish_e2e.py [--leg stitch|e2e|steps|all] [--mbp 2.0] [--reps 20] [--realign] [--d_ids 0,0] [--out f]
 For the rocprofv3 row run the stitch leg alone under `rocprofv3 --kernel-trace --stats -d <dir> -- python ... --leg stitch`.
 """
 import argparse
@@ -241,22 +246,74 @@ def ranks_leg(mbp=2.0, threads=16, d_ids="0,0", realign=False):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def _pepper_command(argv, what):
+    import subprocess
+    env = dict(os.environ, PYTHONPATH=ROOT + (os.pathsep + os.environ["PYTHONPATH"] if os.environ.get("PYTHONPATH") else ""),
+               PV_SHARED_DEVICE="1")
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, "-m", "pepper_thesis_amd.pepper"] + argv, cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=1800)
+    wall = time.perf_counter() - t0
+    if r.returncode != 0:
+        raise RuntimeError("%s: exit status %d\n%s" % (what, r.returncode, r.stderr[-3000:]))
+    return round(wall, 3)
+
+
+def _dir_bytes(d):
+    return sum(os.path.getsize(os.path.join(d, n)) for n in os.listdir(d))
+
+
+def steps_leg(mbp=3.0, threads=16):
+    """make_images -> call_consensus -> stitch against the fused polish on one synthetic contig, each a fresh process"""
+    import numpy as np
+    from bench_filepath import make_files
+    from pepper_thesis_amd import synth
+    d = tempfile.mkdtemp(prefix="pv_polish_steps_")
+    try:
+        bam, fa, info = make_files(d, int(mbp * 1_000_000))
+        model = os.path.join(d, "model.npz")
+        np.savez(model, **synth.make_weights_p2(4321, 3.0))
+        img, pred = os.path.join(d, "img"), os.path.join(d, "pred")
+        res = {"draft_bp": int(mbp * 1_000_000), "reads": info["reads"], "threads": threads, "env": "PV_SHARED_DEVICE=1"}
+        res["polish_s"] = _pepper_command(["polish", "-b", bam, "-f", fa, "-m", model, "-o", os.path.join(d, "fused"), "-t",
+                                           str(threads)], "polish")
+        res["make_images_s"] = _pepper_command(["make_images", "-b", bam, "-f", fa, "-o", img, "-t", str(threads)], "make_images")
+        res["call_consensus_s"] = _pepper_command(["call_consensus", "-i", img, "-m", model, "-o", pred], "call_consensus")
+        res["stitch_s"] = _pepper_command(["stitch", "-i", pred, "-o", os.path.join(d, "steps", "p")], "stitch")
+        res["steps_total_s"] = round(res["make_images_s"] + res["call_consensus_s"] + res["stitch_s"], 3)
+        res["image_files"], res["image_bytes"] = len(os.listdir(img)), _dir_bytes(img)
+        res["prediction_files"], res["prediction_bytes"] = len(os.listdir(pred)), _dir_bytes(pred)
+        with open(os.path.join(d, "fused", "_pepper_polished.fa"), "rb") as a, open(os.path.join(d, "steps", "p_pepper_polished.fa"),
+                                                                                     "rb") as b:
+            fused, steps = a.read(), b.read()
+        res["fasta_bytes"], res["identical"] = len(fused), fused == steps
+        return res
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("stitch", "e2e", "all"), default="all")
+    ap.add_argument("--leg", choices=("stitch", "e2e", "steps", "all"), default="all")
     ap.add_argument("--mbp", type=float, default=2.0)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--realign", action="store_true", help="e2e leg without and with polish --realign, plus realigner stats")
     ap.add_argument("--d_ids", type=str, default=None,
                     help="e2e leg: the polish command with these -d_ids against the first id alone with PV_SHARED_DEVICE=1")
+    ap.add_argument("--out", type=str, default=None, help="also write the JSON to this file")
     a = ap.parse_args()
     out = {}
     if a.leg in ("stitch", "all"):
         out["stitch"] = stitch_leg(a.reps)
     if a.leg in ("e2e", "all"):
         out["e2e"] = ranks_leg(a.mbp, a.threads, a.d_ids, a.realign) if a.d_ids else e2e_leg(a.mbp, a.threads, a.realign)
+    if a.leg == "steps":
+        out["steps"] = steps_leg(a.mbp, a.threads)
     print(json.dumps(out, indent=1))
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(json.dumps(out, indent=1) + "\n")
 
 
 if __name__ == "__main__":
