@@ -14,7 +14,14 @@ planted sites give every region a few more than 512 windows (~527) and the build
 reference's `callers_per_gpu` (RunInferenceArguments.py:67-74) the host loop keeps CALLERS = 16 steps in
 flight by fusing them into ONE launch chain (16 regions per builder call, 8192 windows per RNN call).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it generates the inputs, sizes the workspaces, warms up, times the K
+steps, dumps (if asked) and prints the result line (`value`, `ms_per_step`, the decoder `roofline` from the events of
+the timed region). --full adds what takes runs of its own: before the timed region the isolated image-builder
+measurement (`roofline_builder`) and two chains with every kernel bracketed (`kernel_ms`); after it, on one rank, the
+secondary figures (`h2d_overlapped`, `config2_bf16_input_gemm`, `p1_single_call`, `p2_bigru`, `hipgraph`, `hp_builder`,
+`file_path`, `cpu_baseline`; the --no-* options drop single ones). The timed region is the same in both.
 
 Timed region: exactly K steps, as launch chains of 16 steps (then one chain of 8 if the rest allows, then the
 remainder), bracketed by barrier + synchronize on both sides, MAX over ranks. `steps` = `timed_steps` = K,
@@ -454,6 +461,9 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed step's outputs (rank 0) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the isolated image-builder roofline, the per-kernel "
+                         "breakdown and (one rank) the secondary figures; the --no-* options below pick among the latter")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-p2", action="store_true", help="skip the secondary bi-GRU (P2) and single-call figures")
     ap.add_argument("--no-bf16", action="store_true", help="skip the secondary configs[2] (bf16 input GEMM) figure")
@@ -629,29 +639,32 @@ def main(argv=None):
         assert n_out_rem[n] >= n * BATCH, "%d regions yield %d windows < %d: lower PV_BENCH_SITE_EVERY" % (n, n_out_rem[n], n * BATCH)
     ctx.forward_p1_dev(wins[0].data_ptr(), CALLERS * BATCH, probs_holder["t"][0].data_ptr(), stream=s_rnn.cuda_stream)  # RNN workspace at full size
     s_rnn.synchronize()
-    # image-builder roofline: measured in isolation (16 regions per launch chain), cold inputs (round-robin batches)
-    ctx.profile_begin()
-    for i in range(12):
-        ctx.summarize_dev(dbatches[i % NBATCH], P, douts[0], stream=s_build.cuda_stream)
-    prof_builder = ctx.profile_end()
-    # the same 12 launch chains without the per-kernel events (two events per kernel put a few microseconds between kernels)
-    eb0, eb1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    eb0.record(s_build)
-    for i in range(12):
-        ctx.summarize_dev(dbatches[i % NBATCH], P, douts[0], stream=s_build.cuda_stream)
-    eb1.record(s_build)
-    eb1.synchronize()
-    builder_chain_ms = eb0.elapsed_time(eb1) / 12
+    if args.full:
+        # image-builder roofline: measured in isolation (16 regions per launch chain), cold inputs (round-robin batches)
+        ctx.profile_begin()
+        for i in range(12):
+            ctx.summarize_dev(dbatches[i % NBATCH], P, douts[0], stream=s_build.cuda_stream)
+        prof_builder = ctx.profile_end()
+        # the same 12 launch chains without the per-kernel events (two events per kernel put a few microseconds between kernels)
+        eb0, eb1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        eb0.record(s_build)
+        for i in range(12):
+            ctx.summarize_dev(dbatches[i % NBATCH], P, douts[0], stream=s_build.cuda_stream)
+        eb1.record(s_build)
+        eb1.synchronize()
+        builder_chain_ms = eb0.elapsed_time(eb1) / 12
     n_windows_region = n_out_batch[0]                    # yielded by the 16 regions of batch 0 (written: at most 512 per step)
     for g, nc in enumerate(wchains):
         group(g, nc)
     drain()
-    # per-kernel breakdown of the chain (untimed: every kernel bracketed by events; the timed region brackets the decoder only)
-    ctx.profile_begin()
-    for g in range(2):
-        group(g)
-    drain()
-    prof_all = ctx.profile_end()
+    prof_all = {}
+    if args.full:
+        # per-kernel breakdown of the chain (untimed: every kernel bracketed by events; the timed region brackets the decoder only)
+        ctx.profile_begin()
+        for g in range(2):
+            group(g)
+        drain()
+        prof_all = ctx.profile_end()
     total_steps = K
     n_chains = len(tchains)
     assert sum(tchains) == total_steps
@@ -719,10 +732,7 @@ def main(argv=None):
         windows_per_launch = total_steps * BATCH / max(dec_n, 1)
         flop_per_launch = FLOP_DEC_PER_WINDOW * windows_per_launch
         achieved_tf = flop_per_launch / (dec_launch_ms / 1e3) / 1e12 if dec_ms > 0 else 0.0
-        sum_ms, sum_n = prof_builder.get("summary_pipeline", (0.0, 0))
-        pile_ms, pile_n = prof_builder.get("k_pileup", (0.0, 0))
         traffic = pmc_traffic()
-        alg_bytes = batch.algorithmic_bytes(min(n_windows_region, CALLERS * BATCH))
         out = {
             "metric": "pileup windows/sec (whole node) + Mbp/sec inferred, HG003 chr20 ONT R9",
             "value": value, "unit": "windows/s", "n_gpus": world, "steps": K, "warmup": W,
@@ -746,25 +756,32 @@ def main(argv=None):
                          "traffic_note": traffic.get("note"),
                          "launch_ms": dec_launch_ms, "launches": dec_n, "windows_per_launch": windows_per_launch,
                          "flop_per_launch": flop_per_launch},
-            "roofline_builder": {"bound": "hbm", "kernel": "summary pipeline (k_cigar_scan .. k_write_windows), %d regions/launch" % CALLERS,
-                                 "achieved": alg_bytes / (builder_chain_ms / 1e3) / 1e9,
-                                 "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                 "frac": alg_bytes / (builder_chain_ms / 1e3) / 1e9 / PEAK_HBM_GBS,
-                                 "traffic": traffic.get("builder"), "traffic_raw": traffic.get("builder_raw"),
-                                 "traffic_raw_note": "FETCH_SIZE as counted + WRITE_SIZE (the builder's loads are dwords and bytes, for which the guide's "
-                                                     "x2 of wide coalesced loads does not apply)",
-                                 "launch_ms": builder_chain_ms,
-                                 "launch_ms_with_kernel_events": sum_ms / max(sum_n, 1),
-                                 "k_pileup_ms": pile_ms / max(pile_n, 1),
-                                 "measured": "in isolation, before the timed region: 12 launch chains back to back (launch_ms), and the "
-                                             "same with every kernel bracketed by events (launch_ms_with_kernel_events, k_pileup_ms)",
-                                 "algorithmic_bytes_per_launch": alg_bytes},
             "kernel_ms": dict({k: v[0] / max(v[1], 1) for k, v in prof_all.items()},
                               **{k: v[0] / max(v[1], 1) for k, v in prof.items()}),
-            "kernel_ms_note": "k_lstm_layer_dec: HIP events over the timed region; the others: two untimed chains with every kernel bracketed",
+            "kernel_ms_note": "k_lstm_layer_dec: HIP events over the timed region; the others (--full only): two untimed chains with "
+                              "every kernel bracketed",
             "rnn_model_tflops": FLOP_PER_WINDOW * value / 1e12,
+            "full": bool(args.full),
         }
-        secondary = world == 1
+        if args.full:
+            sum_ms, sum_n = prof_builder.get("summary_pipeline", (0.0, 0))
+            pile_ms, pile_n = prof_builder.get("k_pileup", (0.0, 0))
+            alg_bytes = batch.algorithmic_bytes(min(n_windows_region, CALLERS * BATCH))
+            out["roofline_builder"] = {
+                "bound": "hbm", "kernel": "summary pipeline (k_cigar_scan .. k_write_windows), %d regions/launch" % CALLERS,
+                "achieved": alg_bytes / (builder_chain_ms / 1e3) / 1e9,
+                "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                "frac": alg_bytes / (builder_chain_ms / 1e3) / 1e9 / PEAK_HBM_GBS,
+                "traffic": traffic.get("builder"), "traffic_raw": traffic.get("builder_raw"),
+                "traffic_raw_note": "FETCH_SIZE as counted + WRITE_SIZE (the builder's loads are dwords and bytes, for which the x2 "
+                                    "correction of wide coalesced loads does not apply)",
+                "launch_ms": builder_chain_ms,
+                "launch_ms_with_kernel_events": sum_ms / max(sum_n, 1),
+                "k_pileup_ms": pile_ms / max(pile_n, 1),
+                "measured": "in isolation, before the timed region: 12 launch chains back to back (launch_ms), and the "
+                            "same with every kernel bracketed by events (launch_ms_with_kernel_events, k_pileup_ms)",
+                "algorithmic_bytes_per_launch": alg_bytes}
+        secondary = world == 1 and args.full
         if secondary and not args.no_h2d:
             try:
                 # PCIe-inclusive secondary: every chain's 16 regions are copied from page-locked host memory on a second
