@@ -6,14 +6,14 @@
  *   SummaryGenerator::generate_summary    ... :371-392
  *   AlignmentSummarizer.chunk_images      pepper/modules/python/AlignmentSummarizer.py:19-56
  *
- * PARITY UNPINNED: summary_generator.cpp cannot be compiled in this container (summary_generator.h:11 includes
- * dataio/bam_handler.h, which includes htslib's sam.h/hts.h/cram.h/hts_endian.h; htslib is fetched from a URL by the
- * reference's cmake and is absent), and the reference holds no test or fixture for it. This file follows the source
- * statement by statement; the std::map containers become dense arrays indexed by position - ref_start.
+ * Pinned to the reference: summary_generator.cpp, built in place with the stub htslib headers of oracle/hts_stub/ into
+ * oracle/_ref/libref_polish.so (oracle/ref_driver_polish.cpp), made the golden vectors tests/golden/polish_golden.npz;
+ * tests/test_oracle_polish_ref.py compares this file with both. It follows the source statement by statement; the
+ * std::map containers become dense arrays indexed by position - ref_start.
  *
  * One deliberate reading: `uint8_t pixel_value = <double>` (:281, :293) is undefined for values > 255, which happen
- * when deletions cover a column that no aligned base covers (count / max(1, 0) * 254). The x86-64 build converts with
- * cvttsd2si and keeps the low byte; that is what is restated here and in the HIP kernel.
+ * when deletions cover a column that no aligned base covers (count / max(1, 0) * 254). The x86-64 g++ -O3 build converts
+ * with cvttsd2si and keeps the low byte; that is what is restated here and in the HIP kernel, and what the golden pins.
  */
 #include <stdint.h>
 #include <stdlib.h>

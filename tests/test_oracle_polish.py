@@ -1,9 +1,9 @@
 """CPU: the polisher (P2) summary oracle (oracle/polish_summary_oracle.c).
 
-PARITY UNPINNED - the reference's summary_generator.cpp cannot be built here (htslib headers) and has no fixtures. The C
-oracle is checked against (a) hand-computed known answers and (b) a second, independent, dictionary-based restatement
-below that keeps the reference's containers (maps keyed by position) literally; both follow
-pepper/modules/src/pileup_summary/summary_generator.cpp:47-121, 274-304, 371-392 and AlignmentSummarizer.py:19-56.
+The C oracle is checked here against (a) hand-computed known answers and (b) a second, independent, dictionary-based
+restatement below that keeps the reference's containers (maps keyed by position) literally; both follow
+pepper/modules/src/pileup_summary/summary_generator.cpp:47-121, 274-304, 371-392 and AlignmentSummarizer.py:19-56. Both
+are pinned to the reference's own code by tests/test_oracle_polish_ref.py (golden vectors tests/golden/polish_golden.npz).
 """
 from collections import defaultdict
 

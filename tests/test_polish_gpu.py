@@ -1,15 +1,19 @@
-"""GPU: the polisher (P2) summary-image builder (k_polish_* through pv_polish_summarize_regions) against the CPU oracle.
-Integer / byte work: bit-exact. The oracle itself is PARITY UNPINNED (see tests/test_oracle_polish.py)."""
+"""GPU: the polisher (P2) summary-image builder (k_polish_* through pv_polish_summarize_regions) against the golden vectors
+the reference's own SummaryGenerator and chunk_images made (tests/golden/polish_golden.npz) and against the CPU oracle.
+Integer / byte work: bit-exact. The oracle is pinned to the reference by tests/test_oracle_polish_ref.py."""
 import numpy as np
 import pytest
 
 import cases
 from oracle import rnn_oracle
 from test_oracle_polish import POLISH_EDGE_REGIONS, _reads_of, dict_summary, py_chunks
+from test_oracle_polish_ref import (assert_matches_golden, builder_params, case_batch, expected, expected_all, load_golden,
+                                    names, sizes)
 from pepper_thesis_amd import polish_summary, synth
 from pepper_thesis_amd.batch import Read, Region, pack_regions
 
 pytestmark = pytest.mark.gpu
+_G = load_golden()
 
 
 def assert_polish_equal(got, exp, tag=""):
@@ -171,3 +175,80 @@ def test_bam_to_polish_labels(hip_ctx, oracle_lib, tmp_path):
     lr, ar = rnn_oracle.p2_forward(w, exp.images[:2], np.float64)
     np.testing.assert_allclose(acc[:2], ar, atol=1e-4, rtol=0)
     assert (labels[:2] != lr).mean() < 2e-3
+
+
+# ---- against the reference's golden vectors -------------------------------------------------------------------------
+
+CHUNK_FIELDS = ("images", "position", "index", "region", "chunk_id")
+
+
+@pytest.mark.parametrize("case,L,O", builder_params(_G))
+def test_golden_case_alone(hip_ctx, case, L, O):
+    b = case_batch(_G, case)
+    exp = expected(_G, case, L, O)
+    assert_matches_golden(hip_ctx.polish_summarize(b, L, O, want_flat=True), exp, case)
+    got = hip_ctx.polish_summarize(b, L, O, want_flat=False)
+    assert got.flat_images is None
+    assert_matches_golden(got, {f: exp[f] for f in CHUNK_FIELDS}, case + " chunks only")
+
+
+@pytest.mark.parametrize("L,O", [(1000, 50), (64, 8), (7, 0)])
+def test_golden_all_cases_in_one_batch(hip_ctx, L, O):
+    from pepper_thesis_amd.batch import merge_batches
+    keys = [n for n in names(_G) if (L, O) in sizes(_G, n)]
+    b = merge_batches([case_batch(_G, k) for k in keys])
+    exp = expected_all(_G, keys, L, O)
+    assert_matches_golden(hip_ctx.polish_summarize(b, L, O, want_flat=True), exp, "all")
+    assert_matches_golden(hip_ctx.polish_summarize(b, L, O, want_flat=False), {f: exp[f] for f in CHUNK_FIELDS}, "all")
+
+
+def _behind_filler(exp, n, L, O):
+    """exp with a leading read-less region of n columns at position 0: n zero rows, then exp shifted by one region"""
+    spans = py_chunks(n, L, O)
+    out = {}
+    out["images"] = np.concatenate([np.zeros((len(spans), L, 10), np.uint8), exp["images"]])
+    pos = np.full((len(spans), L), -1, np.int64)
+    idx = np.full((len(spans), L), -1, np.int32)
+    for k, (s, e) in enumerate(spans):
+        pos[k, :e - s] = np.arange(s, e)
+        idx[k, :e - s] = 0
+    out["position"] = np.concatenate([pos, exp["position"]])
+    out["index"] = np.concatenate([idx, exp["index"]])
+    out["region"] = np.concatenate([np.zeros(len(spans), np.int32), exp["region"] + 1])
+    out["chunk_id"] = np.concatenate([np.arange(len(spans), dtype=np.int32), exp["chunk_id"]])
+    out["flat_images"] = np.concatenate([np.zeros((n, 10), np.uint8), exp["flat_images"]])
+    out["flat_position"] = np.concatenate([np.arange(n, dtype=np.int64), exp["flat_position"]])
+    out["flat_index"] = np.concatenate([np.zeros(n, np.int32), exp["flat_index"]])
+    out["region_row_off"] = np.concatenate([[0], exp["region_row_off"] + n]).astype(np.int64)
+    return out
+
+
+@pytest.mark.parametrize("filler", [1, 255, 511])
+def test_golden_cases_behind_a_filler_region(hip_ctx, filler):
+    """a leading region of 1, 255 or 511 columns moves every 512-column tile edge and 1024-column scan block boundary of
+    the batch's global column index to another place in each case"""
+    from pepper_thesis_amd.batch import merge_batches
+    fill = pack_regions([Region(0, filler - 1, b"A" * filler, [])])
+    for case in names(_G):
+        b = merge_batches([fill, case_batch(_G, case)])
+        for L, O in sizes(_G, case):
+            exp = _behind_filler(expected(_G, case, L, O), filler, L, O)
+            assert_matches_golden(hip_ctx.polish_summarize(b, L, O, want_flat=True), exp, "%s behind %d" % (case, filler))
+
+
+def test_golden_device_form_equals_host_form(hip_ctx):
+    from pepper_thesis_amd.batch import merge_batches
+    from pepper_thesis_amd.device import DeviceBatch, DevicePolishOut
+    keys = names(_G)
+    b = merge_batches([case_batch(_G, k) for k in keys])
+    exp = expected_all(_G, keys, 1000, 50)
+    host = hip_ctx.polish_summarize(b, 1000, 50, want_flat=False)
+    n = len(exp["images"])
+    dout = DevicePolishOut(n + 3)
+    hip_ctx.polish_summarize_dev(DeviceBatch(b), dout)
+    hip_ctx.synchronize()
+    assert dout.status() == 0 and dout.n_chunks() == n
+    assert int(dout.counts[1].item()) == int(exp["region_row_off"][-1])
+    for f in CHUNK_FIELDS:
+        d = getattr(dout, f)[:n].cpu().numpy()
+        assert np.array_equal(d, getattr(host, f)) and np.array_equal(d, exp[f]), f

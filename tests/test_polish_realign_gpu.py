@@ -249,3 +249,47 @@ def test_polish_realign_end_to_end(hip_ctx, tmp_path):
     p = polish.polish_fused(str(tmp_path / "reads.bam"), str(tmp_path / "ref.fa"), str(tmp_path / "model.pkl"),
                             str(tmp_path / "fused"), ctx=hip_ctx, realign=True)
     assert open(p).read() == exp[True]
+
+
+def _golden_chain(g, name):
+    from test_oracle_polish_ref import case_batch
+    key = "chain/" + name
+    return case_batch(g, key), g[key + "/win_off"], g[key + "/win"]
+
+
+def _check_chain_realign(g, name, res, k0, n):
+    key = "chain/" + name
+    st, pos = g[key + "/realign_state"], g[key + "/realign_pos"]
+    coff, cig = g[key + "/realign_cigar_off"], g[key + "/realign_cigar"]
+    for j in range(n):
+        k = k0 + j
+        assert (int(res.state[k]) == rr.DROPPED) == (int(st[j]) == 2), (name, j)
+        if st[j] == 1:
+            assert int(res.read_pos[k]) == int(pos[j]), (name, j)
+            assert np.array_equal(res.cigar[res.cigar_off[k]:res.cigar_off[k + 1]], cig[coff[j]:coff[j + 1]]), (name, j)
+
+
+def test_golden_chain_realign_build_chunk(hip_ctx):
+    """realign -> realigned_batch -> pv_polish_summarize_regions equals the reference's ReadAligner -> SummaryGenerator ->
+    chunk_images(1000, 50) (create_summary with realignment_flag=True, from the reads onward); each case alone, then all
+    cases in one batch"""
+    from pepper_thesis_amd.batch import merge_batches
+    from test_oracle_polish_ref import assert_matches_golden, expected, expected_all, load_golden, names
+    g = load_golden()
+    chain = names(g, "chain_names")
+    for name in chain:
+        b, woff, win = _golden_chain(g, name)
+        res = realign.realign(hip_ctx, b, woff, win)
+        _check_chain_realign(g, name, res, 0, b.n_reads)
+        out = hip_ctx.polish_summarize(realign.realigned_batch(b, res), 1000, 50, want_flat=True)
+        assert_matches_golden(out, expected(g, "chain/" + name, 1000, 50), name)
+    parts = [_golden_chain(g, n) for n in chain]
+    b = merge_batches([p[0] for p in parts])
+    woff, win = realign.pack_windows([p[2][:int(p[1][-1])].tobytes() for p in parts])
+    res = realign.realign(hip_ctx, b, woff, win)
+    k0 = 0
+    for name, p in zip(chain, parts):
+        _check_chain_realign(g, name, res, k0, p[0].n_reads)
+        k0 += p[0].n_reads
+    out = hip_ctx.polish_summarize(realign.realigned_batch(b, res), 1000, 50, want_flat=True)
+    assert_matches_golden(out, expected_all(g, ["chain/" + n for n in chain], 1000, 50), "all chains")
