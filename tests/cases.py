@@ -256,3 +256,194 @@ def hp_known_answer():
 
 def hp_random_batch(seed, kw):
     return pack_regions(tag_reads([synth.synth_region(seed, **kw)], seed))
+
+
+# ---- deep shapes of the haplotag-aware builder: shared by the GPU limit tests and the oracle-vs-reference pins -----------
+def _acgt(rng, n):
+    return rng.choice(np.frombuffer(b"ACGT", np.uint8), size=n).astype(np.uint8)
+
+
+def mutated(ref, rng, rate):
+    """ref with about `rate` of its bases moved one step along A -> C -> G -> T -> A"""
+    seq = ref.copy()
+    flip = rng.random(len(seq)) < rate
+    seq[flip] = np.frombuffer(b"ACGT", np.uint8)[(np.searchsorted(np.frombuffer(b"ACGT", np.uint8), seq[flip]) + 1) % 4]
+    return seq
+
+
+def hp_depth_5000():
+    """MAX_READS_IN_REGION = 5000 reads over 700 columns, every haplotag"""
+    reg = synth.synth_region(77, region_len=700, depth=5000, read_len=600, site_every=40)
+    return tag_reads([reg], 77)[0]
+
+
+# the reads of hp_many_reads that carry a one-base deletion at column 65 (anchor 64): (hp_tag, is_reverse)
+HP_MANY_DEL_READS = ((0, False), (1, False), (2, False), (3, True), (-1, False), (1, True))
+
+
+def hp_many_reads(n, tags=None, all_forward=False):
+    """n reads over the same 120 columns; one in three carries a SNP at column 60; the reads listed in HP_MANY_DEL_READS
+    (the first six) delete column 65. tags: None = HP_TAG_CHOICES at random, else a function of the read index"""
+    rng = np.random.default_rng(12)
+    R = 120
+    ref = _acgt(rng, R)
+    alt = ref.copy()
+    alt[60] = ord("A") if ref[60] != ord("A") else ord("C")
+    tag_rng = np.random.default_rng(13)
+    reads = []
+    for i in range(n):
+        seq = alt if i % 3 == 0 else ref
+        if i < len(HP_MANY_DEL_READS):
+            hp, rev = HP_MANY_DEL_READS[i]
+            reads.append(Read.make(1000, "65M1D54M", np.concatenate([seq[:65], seq[66:]]).tobytes(), 20, rev, hp_tag=hp))
+            continue
+        hp = int(tag_rng.choice(HP_TAG_CHOICES)) if tags is None else tags(i)
+        reads.append(Read.make(1000, "%dM" % R, seq.tobytes(), 20, False if all_forward else bool(i & 1), hp_tag=hp))
+    return Region(1000, 1000 + R - 1, ref.tobytes(), reads, 1000, 1000 + R - 1)
+
+
+def hp_every_column_a_site(R=40_000):
+    """six reads that each differ from the reference on about half of the R columns: nearly every column is a site"""
+    rng = np.random.default_rng(9)
+    ref = _acgt(rng, R)
+    reads = []
+    for i in range(6):
+        seq = ref.copy()
+        flip = rng.random(R) < 0.5
+        seq[flip] = np.frombuffer(b"ACGT", np.uint8)[(np.searchsorted(np.frombuffer(b"ACGT", np.uint8), seq[flip]) + 1) % 4]
+        reads.append(Read.make(0, "%dM" % R, seq.tobytes(), 20, i % 2 == 0, hp_tag=HP_TAG_CHOICES[i]))
+    return Region(0, R - 1, ref.tobytes(), reads)
+
+
+def hp_many_alleles(n_distinct):
+    """one insertion site (anchor column 14) with n_distinct distinct alleles: n_distinct - 1 six-base inserts seen once
+    each, and a three-base insert seen 200 times (so that the site emits a candidate)"""
+    ref = b"ACGTACGTACGTACGTACGTACGTACGTAC"
+    reads = []
+    for i in range(n_distinct - 1):
+        ins = "".join("ACGT"[(i >> (2 * k)) & 3] for k in range(6))
+        reads.append(Read.make(0, "15M6I15M", ref[:15] + ins.encode() + ref[15:], 30, i % 2 == 0, hp_tag=HP_TAG_CHOICES[i % 8]))
+    for i in range(200):
+        reads.append(Read.make(0, "15M3I15M", ref[:15] + b"GTT" + ref[15:], 30, i % 2 == 1, hp_tag=HP_TAG_CHOICES[(i + 3) % 8]))
+    return Region(0, 29, ref, reads)
+
+
+def hp_long_indels():
+    """a 3000-base insertion, a deletion longer than the region remainder, a reference buffer longer than the region"""
+    rng = np.random.default_rng(4)
+    ref = bytes(_acgt(rng, 400))
+    reads = []
+    for i in range(8):
+        ins = bytes(_acgt(rng, 3000))
+        reads.append(Read.make(100, "50M3000I50M", ref[100:150] + ins + ref[150:200], 12 + i, i % 2 == 0))
+    for i in range(6):
+        reads.append(Read.make(100, "120M500D10M", ref[100:220] + b"ACGTACGTAC", 20, i % 2 == 0))
+    for i in range(6):   # SNPs at columns 152 and 215, next to the two long indels, so that windows cover them
+        seq = _flip(_flip(ref, 152, "T" if ref[152:153] != b"T" else "G"), 215, "T" if ref[215:216] != b"T" else "G")
+        reads.append(Read.make(90, "200M", seq[90:290], 20, i % 2 == 1))
+    return tag_reads([Region(100, 299, ref[100:], reads)], 4)[0]   # 300 reference bytes for a 200-column region
+
+
+# one overlay case: (candidate type 1 SNP / 2 INS / 3 DEL, reads of the candidate allele in the big group, big group)
+# groups: 0 forward set 1, 1 forward set 2, 2 reverse set 1, 3 reverse set 2 (the byte order of the packed counts)
+HP_OVERLAY_COUNTS = (124, 125, 126, 255, 256, 300)
+HP_OVERLAY_CASES = tuple((t, n, (3 * t + k) % 4) for t in (1, 2, 3) for k, n in enumerate(HP_OVERLAY_COUNTS))
+
+
+def _hp_allele_read(t, ref, col, rev, hp):
+    """a 60-base read over ref carrying candidate type t at column col (SNP at col, insert / delete anchored on col)"""
+    if t == 1:
+        return Read.make(0, "60M", _flip(ref, col, "T" if ref[col:col + 1] != b"T" else "G"), 30, rev, hp_tag=hp)
+    if t == 2:
+        return Read.make(0, "%dM2I%dM" % (col + 1, 59 - col), ref[:col + 1] + b"GA" + ref[col + 1:60], 30, rev, hp_tag=hp)
+    return Read.make(0, "%dM2D%dM" % (col + 1, 57 - col), ref[:col + 1] + ref[col + 3:60], 30, rev, hp_tag=hp)
+
+
+def hp_overlay_region(t, n, big, seed=0):
+    """column 30 carries one candidate of type t. Group `big` gets n observations of it: n - 2 from reads tagged with its
+    set and 2 untagged (which join the other set on the same strand as well). The other groups get 3, 5 and 7 more from
+    tagged reads; 2 forward reads tagged 3 and 2 reverse reads tagged -1 carry it too (they join no group's allele
+    counts); 20 reads match. Returns (region, the four expected group counts before the clamp)."""
+    rng = np.random.default_rng(100 + seed)
+    ref = bytes(_acgt(rng, 60))
+    col = 30
+    reads, counts = [], [0, 0, 0, 0]
+
+    def add(rev, hp):
+        reads.append(_hp_allele_read(t, ref, col, rev, hp))
+        for s in (1, 2):
+            if hp == 0 or hp == s:
+                counts[(2 if rev else 0) + (s - 1)] += 1
+    rev_b, set_b = big >= 2, 1 + (big & 1)
+    for i in range(n - 2):
+        add(rev_b, set_b)
+    add(rev_b, 0)
+    add(rev_b, 0)
+    small = iter((3, 5, 7))
+    for g in range(4):
+        if g != big:
+            for i in range(next(small)):
+                add(g >= 2, 1 + (g & 1))
+    for rev, hp in ((False, 3), (False, 3), (True, -1), (True, -1)):
+        add(rev, hp)
+    for i in range(20):
+        reads.append(Read.make(0, "60M", ref, 30, i % 2 == 0, hp_tag=HP_TAG_CHOICES[i % 8]))
+    return Region(0, 59, ref, reads), counts
+
+
+def hp_overlay_batch_regions():
+    """every HP_OVERLAY_CASES region, 1000 columns apart; -> (regions, expected group counts per region)"""
+    regs, counts = [], []
+    for k, (t, n, big) in enumerate(HP_OVERLAY_CASES):
+        r, c = hp_overlay_region(t, n, big, k)
+        off = 1000 * k
+        regs.append(Region(off, off + 59, r.ref, [Read.make(off + x.pos, x.cigar, x.bases, x.quals, x.is_reverse, x.mapq, x.hp_tag)
+                                                  for x in r.reads]))
+        counts.append(c)
+    return regs, counts
+
+
+def hp_failing_inserts():
+    """anchor column 30: 200 reads insert 'GT' with inserted bases of quality 0 (they fail the bar; the anchor, quality 30,
+    passes, so each takes its anchor's coverage back), 40 reads insert 'CA' at quality 30, 30 reads match.
+    Coverage at the anchor: 270 - 200 = 70."""
+    rng = np.random.default_rng(31)
+    ref = bytes(_acgt(rng, 60))
+    reads = []
+    for i in range(270):
+        hp = HP_TAG_CHOICES[i % 8]
+        if i < 200:
+            q = np.full(62, 30, np.uint8)
+            q[31:33] = 0
+            reads.append(Read.make(0, "31M2I29M", ref[:31] + b"GT" + ref[31:], q, i % 2 == 0, hp_tag=hp))
+        elif i < 240:
+            reads.append(Read.make(0, "31M2I29M", ref[:31] + b"CA" + ref[31:], 30, i % 2 == 1, hp_tag=hp))
+        else:
+            reads.append(Read.make(0, "60M", ref, 30, i % 2 == 0, hp_tag=hp))
+    return Region(0, 59, ref, reads)
+
+
+# depths of the allele-table switch: k_site_rank sends a site to the large-table launch when nev + 4 > UM_SMALL (96)
+SWITCH_DEPTHS = tuple(range(88, 98))
+
+
+def switch_regions(kind):
+    """one region per SWITCH_DEPTHS entry d, 2000 columns apart. kind 'snp' (haplotag form): d reads over 80 columns that all
+    mismatch at column 40 (two thirds T / one third G, every tag); kind 'ins' (26-plane form): d reads that all insert 'AC'
+    after column 40"""
+    regs = []
+    for k, d in enumerate(SWITCH_DEPTHS):
+        rng = np.random.default_rng(200 + k)
+        ref = bytearray(_acgt(rng, 80))
+        ref[40] = ord("A")
+        ref = bytes(ref)
+        off = 2000 * k
+        reads = []
+        for i in range(d):
+            if kind == "snp":
+                reads.append(Read.make(off, "80M", _flip(ref, 40, "T" if i % 3 else "G"), 30, i % 2 == 0,
+                                       hp_tag=HP_TAG_CHOICES[(i + k) % 8]))
+            else:
+                reads.append(Read.make(off, "41M2I39M", ref[:41] + b"AC" + ref[41:], 30, i % 2 == 0))
+        regs.append(Region(off, off + 79, ref, reads))
+    return regs

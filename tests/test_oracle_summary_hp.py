@@ -73,3 +73,50 @@ def test_oracle_vs_live_reference(oracle_lib, seed):
 def test_wrong_geometry_is_refused(oracle_lib):
     with pytest.raises(RuntimeError):
         oracle_lib.summarize_hp(cases.hp_edge_batch("kat1_snp"), PRESETS["ont_r9_guppy5_sup"])  # 32 / 26: the other builder
+
+
+# ---- the deep shapes of the GPU limit tests (tests/test_summary_hp_limits_gpu.py), pinned to the reference's own code ------
+def _deep_32767():
+    return [cases.hp_many_reads(32767)]
+
+
+def _deep_overlay():
+    return cases.hp_overlay_batch_regions()[0]
+
+
+DEEP_SHAPES = {
+    "depth_5000": lambda: [cases.hp_depth_5000()],
+    "32767_reads": _deep_32767,
+    "overlay_clamp": _deep_overlay,
+    "failing_inserts": lambda: [cases.hp_failing_inserts()],
+    "long_indels": lambda: [cases.hp_long_indels()],
+    "allele_table_switch": lambda: cases.switch_regions("snp"),
+}
+
+
+@pytest.mark.parametrize("shape", sorted(DEEP_SHAPES))
+def test_oracle_vs_live_reference_deep_shapes(oracle_lib, shape):
+    """past the depth-125 clip, the +-125 plane clamp and the per-group overlay clamp, where the GPU limit tests compare
+    with this oracle: the oracle must be the reference's answer there too"""
+    if not oracle_lib.have_reference_hp():
+        pytest.skip("oracle/_ref not built (no /root/reference here)")
+    batch = pack_regions(DEEP_SHAPES[shape]())
+    presets = ("ont_r9_guppy5_sup", "hifi") if shape == "long_indels" else ("ont_r9_guppy5_sup",)
+    for preset in presets:
+        P = hp_params(PRESETS[preset])
+        o = oracle_lib.summarize_hp(batch, P, True)
+        r = oracle_lib.reference_summarize_hp(batch, P, True)
+        assert_summary_equal(o, summary_as_expected(r), "%s %s" % (shape, preset))
+        assert len(o) > 0
+
+
+def test_overlay_counts_are_clamped_per_group(oracle_lib):
+    """the middle row of each overlay case holds min(count, 125) of each (strand x set) group of the candidate allele"""
+    regs, counts = cases.hp_overlay_batch_regions()
+    o = oracle_lib.summarize_hp(pack_regions(regs), hp_params(PRESETS["ont_r9_guppy5_sup"]), True)
+    for g, ((t, n, big), c) in enumerate(zip(cases.HP_OVERLAY_CASES, counts)):
+        k = [i for i in range(len(o)) if o.region[i] == g and o.candidates[i][0] == str(t)]
+        assert len(k) == 1, (g, t)
+        row = o.images_i32[k[0], 10]
+        assert c[big] == n
+        assert row[[4 + t, 26 + t, 15 + t, 37 + t]].tolist() == [min(v, 125) for v in c], (t, n, big, c)

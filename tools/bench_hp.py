@@ -10,19 +10,30 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(ctx, dev, regions=None, reps=20):
-    import torch
-    from pepper_thesis_amd import _ffi, synth
-    from pepper_thesis_amd.batch import PRESETS, hp_params, pack_regions
-    from pepper_thesis_amd.device import DeviceBatch, DeviceOut
-    if regions is None:
-        regions = [synth.synth_region(1234 + 97 * i, region_len=100_200, depth=60, read_len=10_000, site_every=198,
-                                      ref_start=1_000_000 + i * 100_000) for i in range(16)]   # bench.py's regions
+def workload_regions(n=16):
+    """the first n of bench.py's regions"""
+    from pepper_thesis_amd import synth
+    return [synth.synth_region(1234 + 97 * i, region_len=100_200, depth=60, read_len=10_000, site_every=198,
+                               ref_start=1_000_000 + i * 100_000) for i in range(n)]
+
+
+def tag_regions(regions):
+    """the figure's HP tag per read, drawn in read order (so the first k regions get the same tags whatever follows)"""
     rng = np.random.default_rng(7)
     for r in regions:
         for rd in r.reads:
             rd.hp_tag = int(rng.choice((0, 0, 0, 0, 1, 1, 1, 2, 2, 2)))
-    batch = pack_regions(regions)
+    return regions
+
+
+def run(ctx, dev, regions=None, reps=20):
+    import torch
+    from pepper_thesis_amd import _ffi
+    from pepper_thesis_amd.batch import PRESETS, hp_params, pack_regions
+    from pepper_thesis_amd.device import DeviceBatch, DeviceOut
+    if regions is None:
+        regions = workload_regions()
+    batch = pack_regions(tag_regions(regions))
     P = hp_params(PRESETS["ont_r9_guppy5_sup"])
     db = DeviceBatch(batch, dev)
     cap = 16384
