@@ -317,6 +317,73 @@ int pv_bgzf_inflate(pv_ctx* ctx, const uint8_t* payload, int64_t payload_bytes, 
                     const int32_t* clen, const int32_t* isize, const uint32_t* crc, const int64_t* out_off, uint8_t* out,
                     int64_t out_bytes, int32_t* status, int64_t* counts);
 
+/* ---- BAM record decode and region clipping (the BAM readers' opt-in `--gpu_decode` mode) -----------------------------
+ * From the bytes pv_bgzf_inflate_dev left in HBM to the image builder's flat batch, without the host touching a record:
+ * what pvio_fill_batch (include/pepper_io.h) does on reader threads, byte for byte - records filtered by flag and MAPQ,
+ * clipped to [rs, re] with the reference's rules (bam_handler.cpp:115-451), the CG:B,I long CIGAR resolved, SEQ unpacked to
+ * "=ACMGRSVTWYHKDBN", the HP tag read. Two calls, because the host sizes the outputs (and decides down-sampling with
+ * pvio_reservoir_indices) from the per-interval counts in between:
+ *   pv_bam_scan_dev   walks every interval's records and measures them: d_iv_counts[i] = {reads kept, bases, CIGAR words,
+ *                     status, virtual offset of the first offender (-1: none), detail, detail, records walked};
+ *   pv_bam_fill_dev   writes the read arrays of `out` (read_pos, read_flags, read_mapq, base_off, bases, quals, cigar_off,
+ *                     cigar) and read_hp for the regions the host kept: region g = interval reg_iv[g], output reads
+ *                     [read_off[g], read_off[g+1]); sel_off[g] = -1 takes the interval's kept reads in record order (then
+ *                     read_off[g+1] - read_off[g] must be its count), else output read k of the region is the interval's
+ *                     kept read number sel[sel_off[g] + k] (the reservoir order). d_totals = {reads, bases, CIGAR words,
+ *                     status}: PV_OK, PV_ERR_CAPACITY (bases / words beyond the capacities given; those reads are not
+ *                     written) or PV_ERR_INVALID (an index outside the interval's kept reads).
+ *                     The region arrays of `out` (ref_start .. read_off, ref) are the caller's and are not read.
+ * Input (pv_bam_decode_in, every pointer a DEVICE pointer): the inflated bytes of all blocks (`data`), the block table of
+ * pvio_plan_blocks with out_off made global to `data` (several reader groups may be packed: interval i uses the blocks
+ * [iv_blk0[i], iv_blk1[i]) of its group, coffset ascending inside a group) and pv_bgzf_inflate_dev's per-block status, and
+ * the interval table of pvio_plan_intervals (chunk virtual offsets as int64). iv_rec_off [n_intervals+1] gives every
+ * interval its range of record slots; a range of (bytes of the group's blocks) / 36 + 1 slots always suffices. rec_slots =
+ * iv_rec_off[n_intervals] < 2^31. Cost: the workspace takes 60 bytes per slot, so that worst-case range is about 1.7 bytes of
+ * workspace per inflated byte of the group for EVERY interval of the group (26 MB for a 100 kb interval at 60x), although
+ * real records are kilobytes long; a caller that knows a larger minimum record size may give fewer slots - an interval that
+ * runs out of slots reports PV_BAMDEC_BAD_TABLE, nothing is overwritten.
+ * Per-interval status (nothing is ever read outside `data` or outside a record's own block_size, whatever the file holds): */
+#define PV_BAMDEC_OK 0
+#define PV_BAMDEC_BAD_BLOCK 1     /* a block under a walked record failed to inflate; detail 0 = index of the block */
+#define PV_BAMDEC_BAD_RECORD 2    /* a parse_record check: detail 1 = -1 negative l_seq, else the bytes the fields need; detail 0 = block_size */
+#define PV_BAMDEC_CIGAR_LONGER 3  /* a kept CIGAR operation ends past l_seq */
+#define PV_BAMDEC_BLOCK_SIZE 4    /* block_size outside [32, 2^30]; detail 0 = block_size */
+#define PV_BAMDEC_PAST_PLAN 5     /* the walk needs a block that is not in the table (a record running past the planned bytes, a
+                                   * chunk past the linear-index bound): not an error, the host reader takes that group */
+#define PV_BAMDEC_SEEK 6          /* a chunk begins past the end of its block (the reader's "seek failed") */
+#define PV_BAMDEC_BAD_TABLE 7     /* the block or interval table contradicts itself (ranges outside `data`, too few slots) */
+typedef struct pv_bam_decode_in {
+    const uint8_t* data;
+    int64_t data_bytes;
+    int64_t n_blocks;
+    const int64_t *coffset, *next_coffset, *out_off; /* [n_blocks] */
+    const int32_t *isize, *blk_status;               /* [n_blocks] */
+    int32_t n_intervals;
+    int32_t include_supplementary;
+    int32_t min_mapq;
+    int32_t reserved;
+    const int32_t* iv_tid;                           /* [n_intervals] */
+    const int64_t *iv_rs, *iv_re;                    /* [n_intervals] clip window, both ends inclusive */
+    const int64_t *iv_blk0, *iv_blk1;                /* [n_intervals] block range of the interval's group */
+    const int64_t* iv_chunk_off;                     /* [n_intervals+1] */
+    const int64_t *chunk_beg, *chunk_end;            /* virtual offsets */
+    const uint8_t* iv_dropped;                       /* [n_intervals] pvio_interval_plan.dropped */
+    const int64_t* iv_rec_off;                       /* [n_intervals+1] */
+    int64_t rec_slots;
+    int64_t n_chunks;                                /* entries of chunk_beg / chunk_end */
+} pv_bam_decode_in;
+/* bytes of the caller-owned workspace `ws` (8-byte aligned) both calls take; the fill reads what the scan left there */
+int64_t pv_bam_decode_ws_bytes(int64_t n_intervals, int64_t rec_slots);
+/* Device-resident and asynchronous on `stream` (NULL = the context's own), like pv_bgzf_inflate_dev: no context workspace is
+ * used (only `ws`), so the calls may run on a stream of their own beside builder and RNN calls of the context, and beside
+ * other decodes whose ws and outputs are distinct. pv_bam_fill_dev must follow its pv_bam_scan_dev on the same stream (or
+ * behind an event), with the same `in` and `ws`. No global atomics, no host synchronisation. */
+int pv_bam_scan_dev(pv_ctx* ctx, const pv_bam_decode_in* in, void* ws, int64_t ws_bytes, int64_t* d_iv_counts, void* stream);
+int pv_bam_fill_dev(pv_ctx* ctx, const pv_bam_decode_in* in, void* ws, int64_t ws_bytes, int32_t n_regions,
+                    const int32_t* reg_iv, const int64_t* read_off, const int64_t* sel_off, const int64_t* sel, int64_t n_sel,
+                    int64_t n_reads, int64_t base_capacity, int64_t cigar_capacity, const pv_batch_in* out, int32_t* read_hp,
+                    int64_t* d_totals, void* stream);
+
 /* ---- recurrent-network inference ------------------------------------------------------------ */
 
 #define PV_PLAN_P1_LSTM 1 /* pepper_variant: 2x bi-LSTM(256) + 5xLinear(512)/SELU + Linear(3) + softmax */

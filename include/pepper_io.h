@@ -124,6 +124,26 @@ int pvio_fill_batch_blocks(pv_bam* bam, pv_fasta* fa, int n_intervals, const cha
                            int64_t max_reads, uint32_t seed, int64_t n_blocks, const int64_t* coffset,
                            const int64_t* next_coffset, const int32_t* isize, const int64_t* out_off, const uint8_t* data,
                            pvio_batch** out);
+/* The interval table of a record decode done elsewhere (include/pepper_hip.h pv_bam_scan_dev): what the reader works out for
+ * every interval before it reads a byte. tid; the clip window [rs, re] = [max(0, start - safe_bases), end + safe_bases]; the
+ * merged BAI chunks of that window as (begin, end) virtual offsets in the reader's walk order, interval i owning chunks
+ * [chunk_off[i], chunk_off[i+1]) - only the chunks pvio_plan_blocks keeps (those that start at or before the linear-index
+ * bound); dropped[i] = 1 when some were left out (a walk that has not met a record at or past `re` by the end of the kept
+ * chunks then needs the host reader). The block table stays the one pvio_plan_blocks returns for the same arguments. */
+typedef struct pvio_interval_plan {
+    void* owner;
+    int32_t n_intervals;
+    int32_t reserved;
+    int64_t n_chunks;
+    const int32_t* tid;                    /* [n_intervals] */
+    const int64_t *rs, *re;                /* [n_intervals] */
+    const int64_t* chunk_off;              /* [n_intervals+1] */
+    const int64_t *chunk_beg, *chunk_end;  /* [n_chunks] virtual offsets (coffset << 16 | uoffset) */
+    const uint8_t* dropped;                /* [n_intervals] */
+} pvio_interval_plan;
+int pvio_plan_intervals(pv_bam* bam, int n_intervals, const char* const* contigs, const int64_t* starts, const int64_t* ends,
+                        int safe_bases, pvio_interval_plan** out);
+void pvio_interval_plan_free(pvio_interval_plan* plan);
 /* kept read indices, in output order, of the reservoir sampling above; returns their number (out holds n_reads slots) */
 int64_t pvio_reservoir_indices(int64_t n_reads, double downsample_rate, int64_t max_reads, uint32_t seed, int64_t* out);
 

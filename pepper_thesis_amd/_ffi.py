@@ -51,6 +51,16 @@ BGZF_STATUS_NAMES = {0: "ok", 1: "BTYPE 3", 2: "stored LEN/NLEN mismatch", 3: "i
                      5: "distance too far back", 6: "output exceeds ISIZE", 7: "output shorter than ISIZE",
                      8: "payload read past its end", 9: "CRC32 mismatch", 10: "bad block table entry"}
 
+# per-interval statuses of pv_bam_scan_dev
+PV_BAMDEC_OK = 0
+PV_BAMDEC_BAD_BLOCK = 1
+PV_BAMDEC_BAD_RECORD = 2
+PV_BAMDEC_CIGAR_LONGER = 3
+PV_BAMDEC_BLOCK_SIZE = 4
+PV_BAMDEC_PAST_PLAN = 5
+PV_BAMDEC_SEEK = 6
+PV_BAMDEC_BAD_TABLE = 7
+
 PV_PLAN_P1_LSTM = 1
 PV_PLAN_P2_GRU = 2
 PV_DTYPE_F32 = 0
@@ -94,6 +104,18 @@ class pv_batch_in(C.Structure):
         ("quals", C.c_void_p),
         ("cigar_off", C.c_void_p),
         ("cigar", C.c_void_p),
+    ]
+
+
+class pv_bam_decode_in(C.Structure):
+    _fields_ = [
+        ("data", C.c_void_p), ("data_bytes", C.c_int64), ("n_blocks", C.c_int64),
+        ("coffset", C.c_void_p), ("next_coffset", C.c_void_p), ("out_off", C.c_void_p),
+        ("isize", C.c_void_p), ("blk_status", C.c_void_p),
+        ("n_intervals", C.c_int32), ("include_supplementary", C.c_int32), ("min_mapq", C.c_int32), ("reserved", C.c_int32),
+        ("iv_tid", C.c_void_p), ("iv_rs", C.c_void_p), ("iv_re", C.c_void_p), ("iv_blk0", C.c_void_p), ("iv_blk1", C.c_void_p),
+        ("iv_chunk_off", C.c_void_p), ("chunk_beg", C.c_void_p), ("chunk_end", C.c_void_p), ("iv_dropped", C.c_void_p),
+        ("iv_rec_off", C.c_void_p), ("rec_slots", C.c_int64), ("n_chunks", C.c_int64),
     ]
 
 
@@ -210,6 +232,11 @@ SYMBOLS = [
     ("pv_bgzf_inflate", C.c_int,
      [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
       C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
+    ("pv_bam_decode_ws_bytes", C.c_int64, [C.c_int64, C.c_int64]),
+    ("pv_bam_scan_dev", C.c_int, [C.c_void_p, C.POINTER(pv_bam_decode_in), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("pv_bam_fill_dev", C.c_int,
+     [C.c_void_p, C.POINTER(pv_bam_decode_in), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+      C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(pv_batch_in), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pv_rnn_load_p1", C.c_int, [C.c_void_p, C.POINTER(pv_weights_p1), C.c_int]),
     ("pv_rnn_load_p2", C.c_int, [C.c_void_p, C.POINTER(pv_weights_p2), C.c_int]),
     ("pv_rnn_forward_p1", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

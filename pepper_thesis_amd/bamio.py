@@ -46,6 +46,13 @@ class pvio_block_plan(C.Structure):
                 ("crc", C.POINTER(C.c_uint32)), ("out_off", C.POINTER(C.c_int64)), ("t_plan", C.c_double)]
 
 
+class pvio_interval_plan(C.Structure):
+    _fields_ = [("owner", C.c_void_p), ("n_intervals", C.c_int32), ("reserved", C.c_int32), ("n_chunks", C.c_int64),
+                ("tid", C.POINTER(C.c_int32)), ("rs", C.POINTER(C.c_int64)), ("re", C.POINTER(C.c_int64)),
+                ("chunk_off", C.POINTER(C.c_int64)), ("chunk_beg", C.POINTER(C.c_int64)), ("chunk_end", C.POINTER(C.c_int64)),
+                ("dropped", C.POINTER(C.c_uint8))]
+
+
 IO_SYMBOLS = [
     ("pvio_last_error", C.c_char_p, []),
     ("pvio_inflate_backend", C.c_char_p, []),
@@ -67,6 +74,9 @@ IO_SYMBOLS = [
                                          C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int64, C.c_uint32,
                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.POINTER(pvio_batch))]),
+    ("pvio_plan_intervals", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
+                                      C.POINTER(C.POINTER(pvio_interval_plan))]),
+    ("pvio_interval_plan_free", None, [C.POINTER(pvio_interval_plan)]),
     ("pvio_reservoir_indices", C.c_int64, [C.c_int64, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_int64)]),
     ("pvio_write_bam", C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
@@ -313,6 +323,43 @@ def plan_blocks(bam: BamHandler, intervals, safe_bases: int = 100, margin_blocks
         return BlockPlan(out)
     finally:
         load().pvio_plan_free(out)
+
+
+class IntervalPlan:
+    """What the reader works out per interval before it reads a byte (pvio_plan_intervals): tid, the clip window [rs, re], the
+    merged BAI chunks in walk order (interval i owns chunks [chunk_off[i], chunk_off[i+1]); virtual offsets as int64) limited
+    to those plan_blocks keeps, and dropped[i] = 1 where some were left out. Arrays are copies owned by this object."""
+
+    def __init__(self, ptr):
+        v = ptr.contents
+        n, nc = int(v.n_intervals), int(v.n_chunks)
+        self.n_intervals, self.n_chunks = n, nc
+        self.tid = _np(v.tid, n, np.int32)
+        self.rs, self.re = _np(v.rs, n, np.int64), _np(v.re, n, np.int64)
+        self.chunk_off = _np(v.chunk_off, n + 1, np.int64)
+        self.chunk_beg, self.chunk_end = _np(v.chunk_beg, nc, np.int64), _np(v.chunk_end, nc, np.int64)
+        self.dropped = _np(v.dropped, n, np.uint8)
+
+
+def plan_intervals(bam: BamHandler, intervals, safe_bases: int = 100) -> IntervalPlan:
+    """the interval table that goes with plan_blocks(bam, intervals, safe_bases, ...) for a record decode on the device"""
+    n, names, starts, ends = _interval_args(intervals)
+    out = C.POINTER(pvio_interval_plan)()
+    if load().pvio_plan_intervals(bam.h, n, names, starts, ends, int(safe_bases), C.byref(out)):
+        raise IOError("plan_intervals: " + _err())
+    try:
+        return IntervalPlan(out)
+    finally:
+        load().pvio_interval_plan_free(out)
+
+
+def fetch_reference(fasta: FastaHandler, contig: str, start: int, stop: int) -> np.ndarray:
+    """FASTA_handler.get_reference_sequence as bytes (one pvio_fasta_fetch): upper-cased bases [start, stop), clamped"""
+    buf = np.empty(max(int(stop) - int(start), 1), np.uint8)
+    got = load().pvio_fasta_fetch(fasta.h, contig.encode(), int(start), int(stop), buf.ctypes.data_as(C.c_char_p))
+    if got < 0:
+        raise IOError("fill_batch: " + _err())
+    return buf[:got]
 
 
 def fill_batch_blocks(bam: BamHandler, fasta: FastaHandler, intervals, coffset, next_coffset, isize, out_off, data,

@@ -60,11 +60,11 @@ def _predict_rank(args, rank, world, device, image_dir, pred_dir, params, min_ma
                                                args.region_size, min_mapq, args.include_supplementary, args.downsample_rate,
                                                args.batch_size, max(1, int(args.callers_per_gpu)) * 4, rank, world, args.threads, keep,
                                                dtype=dtype, region_bed=args.region_bed, on_rows=on_rows,
-                                               gpu_inflate=getattr(args, "gpu_inflate", False))
+                                               gpu_inflate=getattr(args, "gpu_inflate", False), gpu_decode=getattr(args, "gpu_decode", False))
         n = make_images.generate_images(ctx, args.bam, args.fasta, image_dir, params, args.region, args.region_size, min_mapq,
                                         args.include_supplementary, args.downsample_rate, rank=rank, world=world,
                                         reader_threads=args.threads, region_bed=args.region_bed,
-                                        gpu_inflate=getattr(args, "gpu_inflate", False))
+                                        gpu_inflate=getattr(args, "gpu_inflate", False), gpu_decode=getattr(args, "gpu_decode", False))
         os.makedirs(pred_dir, exist_ok=True)
         mine = [os.path.join(image_dir, "pepper_variants_images_thread_%d.hdf5" % rank)]
         run_inference.predict_files(ctx, state, [p for p in mine if os.path.exists(p)], os.path.join(pred_dir, pred_name),

@@ -87,9 +87,18 @@ def call_variant_parser(ap=None):
     return ap
 
 
+class _GpuDecodeAction(argparse.Action):
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.gpu_decode = True
+        namespace.gpu_inflate = True   # the decode reads what the inflate kernel left on the device
+
+
 def _gpu_inflate_flag(ap):
     ap.add_argument("--gpu_inflate", action="store_true", default=False,
                     help="inflate the BAM's BGZF blocks on the GPU (opt-in; same output as the default host inflate)")
+    ap.add_argument("--gpu_decode", action=_GpuDecodeAction, nargs=0, default=False,
+                    help="also decode and clip the BAM records on the GPU: the readers only plan blocks and fetch reference bytes "
+                         "(opt-in; implies --gpu_inflate; same output)")
 
 
 def make_images_parser(ap=None):

@@ -1315,6 +1315,15 @@ static int fill_batch(pv_bam* b, pv_fasta* fa, int n_intervals, const char* cons
 
 // ---- block plan for an inflate done elsewhere (the GPU) ----------------------------------------------------------------
 static const int PLAN_LOOKAHEAD = 2;   // 16 kb linear-index windows past a region: reads up to 32 kb are planned in full
+// compressed offset of the block that bounds the walk of [rs, re) on `tid` (see pvio_plan_blocks); INT64_MAX = no bound
+static int64_t plan_bound(const pv_bam* b, int tid, int64_t rs, int64_t re) {
+    if (tid >= (int)b->index.size()) return INT64_MAX;
+    const RefIndex& ri = b->index[tid];
+    const size_t w = (size_t)(((re - 1) >> 14) + 1 + PLAN_LOOKAHEAD);
+    if (re > rs && w < ri.linear.size() && ri.linear[w] != 0) return (int64_t)(ri.linear[w] >> 16);
+    return INT64_MAX;
+}
+
 struct pvio_plan_store {
     std::vector<uint8_t> payload;
     std::vector<int64_t> coffset, next, in_off, out_off;
@@ -1351,12 +1360,7 @@ extern "C" int pvio_plan_blocks(pv_bam* b, int n_intervals, const char* const* c
         // overlapping that window) is at or after that record when no read that starts inside the region is longer than the
         // look-ahead: its block bounds the walk. Longer reads only cost blocks inflated on the host, never a different result.
         // (a BAI with fewer references than the header has no chunks for this contig: region_chunks returned none)
-        int64_t bound = INT64_MAX;
-        if (tid < (int)b->index.size()) {
-            const RefIndex& ri = b->index[tid];
-            const size_t w = (size_t)(((re - 1) >> 14) + 1 + PLAN_LOOKAHEAD);
-            if (re > rs && w < ri.linear.size() && ri.linear[w] != 0) bound = (int64_t)(ri.linear[w] >> 16);
-        }
+        const int64_t bound = plan_bound(b, tid, rs, re);
         for (const Chunk& c : chunks) {   // (chunks of large bins that start past the bound are never reached by the reader)
             const int64_t first = (int64_t)(c.beg >> 16);
             if (first <= bound) ranges.emplace_back(first, std::min((int64_t)(c.end >> 16), bound));
@@ -1401,6 +1405,55 @@ extern "C" int pvio_plan_blocks(pv_bam* b, int n_intervals, const char* const* c
     v.in_off = st->in_off.data(); v.clen = st->clen.data(); v.isize = st->isize.data(); v.crc = st->crc.data();
     v.out_off = st->out_off.data();
     v.t_plan = now_s() - t0;
+    *out = &st->view;
+    return 0;
+}
+
+// ---- interval table for a record decode done elsewhere (the GPU) -------------------------------------------------------
+// What query_region computes before it reads a byte, per interval: tid, the clip window and the merged BAI chunks in walk
+// order - those pvio_plan_blocks keeps (same bound).
+struct pvio_interval_store {
+    std::vector<int32_t> tid;
+    std::vector<int64_t> rs, re, chunk_off, chunk_beg, chunk_end;
+    std::vector<uint8_t> dropped;
+    pvio_interval_plan view;
+};
+
+extern "C" void pvio_interval_plan_free(pvio_interval_plan* p) {
+    if (!p) return;
+    delete (pvio_interval_store*)p->owner;
+}
+
+extern "C" int pvio_plan_intervals(pv_bam* b, int n_intervals, const char* const* contigs, const int64_t* starts,
+                                   const int64_t* ends, int safe_bases, pvio_interval_plan** out) {
+    if (!b || !out || (n_intervals > 0 && (!contigs || !starts || !ends))) { io_err("null argument"); return -1; }
+    *out = nullptr;
+    pvio_interval_store* st = new pvio_interval_store();
+    std::vector<Chunk> chunks;
+    st->chunk_off.push_back(0);
+    for (int iv = 0; iv < n_intervals; iv++) {
+        const int tid = find_tid(b, contigs[iv]);
+        if (tid < 0) { io_err("contig %s not in the BAM header", contigs[iv]); delete st; return -1; }
+        const int64_t rs = std::max<int64_t>(0, starts[iv] - safe_bases), re = ends[iv] + safe_bases;
+        region_chunks(b, tid, rs, re, chunks);
+        const int64_t bound = plan_bound(b, tid, rs, re);   // the same bound as pvio_plan_blocks: the same chunks are kept
+        uint8_t dropped = 0;
+        for (const Chunk& c : chunks) {
+            if ((int64_t)(c.beg >> 16) <= bound) { st->chunk_beg.push_back((int64_t)c.beg); st->chunk_end.push_back((int64_t)c.end); }
+            else dropped = 1;
+        }
+        st->tid.push_back(tid); st->rs.push_back(rs); st->re.push_back(re);
+        st->dropped.push_back(dropped);
+        st->chunk_off.push_back((int64_t)st->chunk_beg.size());
+    }
+    pvio_interval_plan& v = st->view;
+    memset(&v, 0, sizeof(v));
+    v.owner = st;
+    v.n_intervals = n_intervals;
+    v.n_chunks = (int64_t)st->chunk_beg.size();
+    v.tid = st->tid.data(); v.rs = st->rs.data(); v.re = st->re.data();
+    v.chunk_off = st->chunk_off.data(); v.chunk_beg = st->chunk_beg.data(); v.chunk_end = st->chunk_end.data();
+    v.dropped = st->dropped.data();
     *out = &st->view;
     return 0;
 }

@@ -163,7 +163,7 @@ def region_batches(bam_path: str, fasta_path: str, region: str = None, region_si
                    include_supplementary: bool = False, downsample_rate: float = 1.0, intervals_per_call: int = 16,
                    rank: int = 0, world: int = 1, reader_threads: int = None, intervals_per_read: int = 1, T: dict = None,
                    region_bed: str = None, merge: bool = True, inflate_helpers: int = None, gpu_inflate: bool = False,
-                   ctx=None):
+                   ctx=None, gpu_decode: bool = False):
     """The reader side of generate_images (ImageGenerationUI.py:277-345): returns an iterator of (RegionBatch, interval of every
     batch region) pairs, `intervals_per_call` intervals per batch; interval i belongs to rank i % world (:211).
 
@@ -179,7 +179,11 @@ def region_batches(bam_path: str, fasta_path: str, region: str = None, region_si
     gpu_inflate=True (needs `ctx`, a runtime.Context): every reader plans its intervals' BGZF blocks, one service thread
     inflates the waiting plans with one pv_bgzf_inflate_dev launch on a stream of its own, and the reader parses the records
     from the inflated bytes (gpu_inflate.py); same batches as the default, which stays the host inflate. Helper threads
-    (`inflate_helpers`) and this mode exclude each other."""
+    (`inflate_helpers`) and this mode exclude each other.
+    gpu_decode=True (implies gpu_inflate): the records are decoded and clipped on the device as well (gpu_decode.py). The
+    readers only plan blocks and fetch reference bytes, and a batch comes as a gpu_decode.DecodedBatch - device-resident, in
+    the default's layout and order - in place of the host arrays (a group of reads longer than the plan's look-ahead still
+    comes as host arrays). Helper threads are refused here too."""
     import os
     import threading
     import time
@@ -206,11 +210,17 @@ def region_batches(bam_path: str, fasta_path: str, region: str = None, region_si
     # 107-118 ms, 4 x 3 137-260 ms, 8 x 1 160-170 ms - helpers sleep and wake once per few blocks, and threads that hop between
     # the host's CPUs strand the cgroup's quota slices, which starves the thread that feeds the GPU; so it stays opt-in.
     inflate_helpers = max(0, int(inflate_helpers or 0))
+    if gpu_decode and (inflate_helpers or ctx is None):
+        raise ValueError("gpu_decode needs a device context and no inflate helper threads")
     if gpu_inflate and (inflate_helpers or ctx is None):
         raise ValueError("gpu_inflate needs a device context and no inflate helper threads")
     n_thr = max(1, min(budget // (inflate_helpers + 1), max(len(groups), 1)))
     T["reader_threads"], T["inflate_helpers"], T["intervals"] = n_thr, inflate_helpers, len(mine)
     T.setdefault("read_helper_cpu_s", 0.0)
+    if gpu_decode:
+        from .gpu_decode import decoded_batches
+        return decoded_batches(ctx, bam_path, fasta_path, groups, reads_per_call, n_thr, min_mapq, include_supplementary,
+                               downsample_rate, REGION_SAFE_BASES, T, merge)
     tls = threading.local()
 
     def read_group(ivs):
@@ -286,13 +296,15 @@ def generate_images(ctx, bam_path: str, fasta_path: str, output_dir: str, params
                     region_size: int = 100_000, min_mapq: int = 5, include_supplementary: bool = False,
                     downsample_rate: float = 1.0, intervals_per_call: int = 16, rank: int = 0, world: int = 1,
                     reader_threads: int = None, timers: dict = None, intervals_per_read: int = 1,
-                    use_hp_info: bool = False, region_bed: str = None, gpu_inflate: bool = False) -> int:
+                    use_hp_info: bool = False, region_bed: str = None, gpu_inflate: bool = False,
+                    gpu_decode: bool = False) -> int:
     """generate_images (ImageGenerationUI.py:277-345) on the MI355X path: intervals of region_size, interval i handled
     by rank i % world (:211), `intervals_per_call` intervals per builder launch chain, one HDF5 file per rank; the readers
     are `region_batches` above. `timers` (optional dict) receives the stage times in seconds.
     use_hp_info (`-hp`, ImageGenerationUI.py:48-71,206-207): the haplotag-aware builder (AlignmentSummarizerHP.py:176-233:
     the same fetch, RegionalSummaryGeneratorHP with window 20 / 48 planes, the reads' HP tags); the file name gets "_hp".
-    gpu_inflate: the BAM's BGZF blocks are inflated on ctx's device (region_batches); same file."""
+    gpu_inflate: the BAM's BGZF blocks are inflated on ctx's device (region_batches); same file.
+    gpu_decode: the records are decoded and clipped there too and the builder reads the device-resident batch; same file."""
     import os
     import time
     from .hdf5io import ImageStore
@@ -313,7 +325,7 @@ def generate_images(ctx, bam_path: str, fasta_path: str, output_dir: str, params
         n_windows = pipeline.call_variant_fused(ctx, None, bam_path, fasta_path, None, params, region, region_size, min_mapq,
                                                 include_supplementary, downsample_rate, 512, intervals_per_call, rank, world,
                                                 reader_threads, os.path.join(output_dir, fname), T2, region_bed=region_bed,
-                                                gpu_inflate=gpu_inflate)
+                                                gpu_inflate=gpu_inflate, gpu_decode=gpu_decode)
         T2["builder_call_s"] = T2["upload_s"] + T2["device_call_s"] + T2["readback_s"]
         T2["wall_s"] = time.perf_counter() - t_start
         if timers is not None:
@@ -322,9 +334,13 @@ def generate_images(ctx, bam_path: str, fasta_path: str, output_dir: str, params
     with ImageStore(os.path.join(output_dir, fname), "w") as store:
         for batch, names in region_batches(bam_path, fasta_path, region, region_size, min_mapq, include_supplementary,
                                            downsample_rate, intervals_per_call, rank, world, reader_threads, intervals_per_read, T,
-                                           region_bed, gpu_inflate=gpu_inflate, ctx=ctx):
+                                           region_bed, gpu_inflate=gpu_inflate, ctx=ctx, gpu_decode=gpu_decode):
             t0 = time.perf_counter()
-            out = ctx.summarize_hp(batch, params) if use_hp_info else ctx.summarize(batch, params)
+            if gpu_decode and not isinstance(batch, RegionBatch):
+                from .gpu_decode import summarize_decoded
+                out = summarize_decoded(ctx, batch, params, use_hp_info)
+            else:
+                out = ctx.summarize_hp(batch, params) if use_hp_info else ctx.summarize(batch, params)
             T["builder_call_s"] += time.perf_counter() - t0
             t0 = time.perf_counter()
             for g, (contig, start, end) in enumerate(names):
@@ -380,7 +396,7 @@ def run(args):
     n = generate_images(ctx, args.bam, args.fasta, args.output_dir, params, args.region, args.region_size,
                         min_mapq, args.include_supplementary, args.downsample_rate, rank=rank, world=world,
                         reader_threads=args.threads, use_hp_info=args.use_hp_info, region_bed=args.region_bed,
-                        gpu_inflate=getattr(args, "gpu_inflate", False))
+                        gpu_inflate=getattr(args, "gpu_inflate", False), gpu_decode=getattr(args, "gpu_decode", False))
     ctx.close()
     sys.stderr.write("INFO: FINISHED IMAGE GENERATION: %d WINDOWS\n" % n)
     return 0

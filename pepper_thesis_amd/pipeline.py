@@ -88,12 +88,14 @@ def call_variant_fused(ctx, state_dict: dict, bam_path: str, fasta_path: str, pr
                        downsample_rate: float = 1.0, batch_size: int = 512, intervals_per_call: int = 16, rank: int = 0,
                        world: int = 1, reader_threads: int = None, keep_images_path: Optional[str] = None, timers: dict = None,
                        dtype: int = _ffi.PV_DTYPE_F32, region_bed: str = None, inflate_helpers: int = None, on_rows=None,
-                       gpu_inflate: bool = False) -> int:
+                       gpu_inflate: bool = False, gpu_decode: bool = False) -> int:
     """-> number of windows predicted. One prediction file at `pred_path` (and one image file at `keep_images_path`, if given)
     for the intervals of this rank. state_dict None = images only (make_images): no model, no prediction file.
     on_rows (optional): called on the writer thread with every call's windows as the arrays of a prediction batch (what
     PredictionStore.batches() would read back) - call_variant selects its candidates there, while the device works on.
-    gpu_inflate: the readers' BGZF blocks are inflated on this context's device (make_images.region_batches); same output."""
+    gpu_inflate: the readers' BGZF blocks are inflated on this context's device (make_images.region_batches); same output.
+    gpu_decode: the records are decoded and clipped there as well (gpu_decode.py): a call's batch is device-resident when it
+    arrives and nothing is uploaded; same output."""
     import torch
     from .device import DeviceOut
     from .make_images import region_batches
@@ -104,7 +106,7 @@ def call_variant_fused(ctx, state_dict: dict, bam_path: str, fasta_path: str, pr
     # the readers start on the first intervals here; the model is loaded while they read
     batches = region_batches(bam_path, fasta_path, region, region_size, min_mapq, include_supplementary, downsample_rate,
                              intervals_per_call, rank, world, reader_threads, 1, T, region_bed, merge=False,
-                             inflate_helpers=inflate_helpers, gpu_inflate=gpu_inflate, ctx=ctx)
+                             inflate_helpers=inflate_helpers, gpu_inflate=gpu_inflate, ctx=ctx, gpu_decode=gpu_decode)
     t0 = time.perf_counter()
     predict = state_dict is not None
     if predict:
@@ -137,10 +139,14 @@ def call_variant_fused(ctx, state_dict: dict, bam_path: str, fasta_path: str, pr
             if werr:
                 break
             t0 = time.perf_counter()
-            up = ctx.upload_batches(parts)   # the readers' per-interval arrays go straight to their offsets on the device
+            if isinstance(parts, list):
+                up = ctx.upload_batches(parts)   # the readers' per-interval arrays go straight to their offsets on the device
+                max_region_len = max(b.max_region_len for b in parts)
+            else:                                # gpu_decode: the batch was decoded on the device (a gpu_decode.DecodedBatch)
+                parts.wait_on(ctx)
+                up, max_region_len = parts.uploaded(), parts.max_region_len
             T["upload_s"] += time.perf_counter() - t0
             want = max(4096, 1024 * len(names))
-            max_region_len = max(b.max_region_len for b in parts)
             while True:
                 if dout is None or cap < want:
                     cap, scap = want, 16 * want
@@ -179,7 +185,7 @@ def call_variant_fused(ctx, state_dict: dict, bam_path: str, fasta_path: str, pr
             T["readback_s"] += time.perf_counter() - t0
             q.put((names, rec, p, imgs))
             n_windows += n_out
-            del up
+            del up, parts
     finally:
         batches.close()   # (stops the readers if the loop was left early)
         q.put(None)

@@ -323,6 +323,20 @@ class Context:
                                                 d_isize, d_crc, d_out_off, d_out, int(out_bytes), d_status, d_counts,
                                                 stream or None))
 
+    def bam_scan_dev(self, cin: "_ffi.pv_bam_decode_in", d_ws: int, ws_bytes: int, d_iv_counts: int, stream: int = 0):
+        """asynchronous, device-resident scan phase of the BAM record decode (pv_bam_scan_dev): walks and measures the records
+        of every interval of `cin`; int64 [n_intervals][8] counts land in d_iv_counts. Uses only the caller's workspace."""
+        _ffi.check(self.lib.pv_bam_scan_dev(self.handle, C.byref(cin), d_ws, int(ws_bytes), d_iv_counts, stream or None))
+
+    def bam_fill_dev(self, cin: "_ffi.pv_bam_decode_in", d_ws: int, ws_bytes: int, n_regions: int, d_reg_iv: int, d_read_off: int,
+                     d_sel_off: int, d_sel: int, n_sel: int, n_reads: int, base_capacity: int, cigar_capacity: int,
+                     out: "_ffi.pv_batch_in", d_read_hp: int, d_totals: int, stream: int = 0):
+        """asynchronous fill phase (pv_bam_fill_dev) behind bam_scan_dev on the same stream: the read arrays of `out` and
+        read_hp for the regions the host kept; {reads, bases, CIGAR words, status} in d_totals (int64 [4])."""
+        _ffi.check(self.lib.pv_bam_fill_dev(self.handle, C.byref(cin), d_ws, int(ws_bytes), int(n_regions), d_reg_iv, d_read_off,
+                                            d_sel_off, d_sel, int(n_sel), int(n_reads), int(base_capacity), int(cigar_capacity),
+                                            C.byref(out), d_read_hp, d_totals, stream or None))
+
     def polish_stitch_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_region_start: int, n_regions: int,
                           d_region_off: int, d_seq: int, seq_capacity: int, d_counts: int, stream: int = 0):
         """asynchronous, device-resident stitch (pv_polish_stitch_dev): the labels of dout's first n_chunks chunks -> polished

@@ -6,6 +6,8 @@ The BAM is synthetic (SURVEY 8(d) shape: one contig of >= 1 Mbp at 60x, 10 kb re
 with the library's own BAM writer (pvio_write_bam); nothing under oracle/ is used. Not part of `value`.
 
   python tools/bench_filepath.py [--mbp 3.2]   (32 intervals of 100 kb: two per reader thread of a 16-core share)
+  python tools/bench_filepath.py --gpu_decode [--out result.json]
+        host inflate, `gpu_inflate=True` and `gpu_decode=True` alternating, three runs each
   python tools/bench_filepath.py --gpu_inflate [--out result.json]
         the fused path with the host inflate (default) and with `gpu_inflate=True`, alternating, three runs each: wall and
         Mbp/s of both modes, the inflate kernel's time and output GB/s, H2D / D2H time. (bench.py calls run() only.)
@@ -182,15 +184,65 @@ def run_gpu_inflate(ctx, weights, mbp=3.2, runs=3):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def run_gpu_decode(ctx, weights, mbp=3.2, runs=3):
+    """host inflate (default) vs gpu_inflate vs gpu_decode on the fused call_variant path: alternating runs, `runs` of each"""
+    from pepper_thesis_amd import pipeline
+    from pepper_thesis_amd.batch import PRESETS
+    d = tempfile.mkdtemp(prefix="pv_filepath_gd_")
+    modes = {"host_inflate": {}, "gpu_inflate": {"gpu_inflate": True}, "gpu_decode": {"gpu_decode": True}}
+    try:
+        contig_len = int(mbp * 1_000_000)
+        bam, fa, info = make_files(d, contig_len)
+        P = PRESETS["ont_r9_guppy5_sup"]
+        swept = contig_len / 1e6
+        for kw in modes.values():   # warm the page cache, the workspaces and the pinned host pool (untimed)
+            pipeline.call_variant_fused(ctx, weights, bam, fa, os.path.join(d, "warm", "p.hdf"), P, min_mapq=5, **kw)
+        res = {m: [] for m in modes}
+        for k in range(runs):
+            for m, kw in modes.items():
+                t_k = {}
+                t_k["windows"] = pipeline.call_variant_fused(ctx, weights, bam, fa, os.path.join(d, "pred_" + m, "pepper_prediction.hdf"),
+                                                             P, min_mapq=5, timers=t_k, **kw)
+                res[m].append(t_k)
+
+        def leg(rs):
+            walls = [r["wall_s"] for r in rs]
+            med = sorted(rs, key=lambda r: r["wall_s"])[len(rs) // 2]
+            o = {"wall_s_median": med["wall_s"], "wall_s_runs": walls, "wall_s_spread": max(walls) - min(walls),
+                 "mbp_per_s_median": swept / med["wall_s"], "windows": med["windows"]}
+            for k in ("reader_threads", "read_inflate_cpu_s", "read_decode_cpu_s", "reader_stall_s", "device_call_s", "upload_s",
+                      "readback_s", "gpu_inflate_kernel_ms", "gpu_inflate_bytes", "gpu_inflate_launches", "gpu_inflate_h2d_ms",
+                      "gpu_inflate_d2h_ms", "gpu_inflate_plan_cpu_s", "gpu_inflate_blocks_host", "gpu_decode_plan_cpu_s", "gpu_decode_plan_wall_s",
+                      "gpu_decode_scan_ms", "gpu_decode_fill_ms", "gpu_decode_host_s", "gpu_decode_h2d_bytes", "gpu_decode_d2h_bytes",
+                      "gpu_decode_groups", "gpu_decode_groups_host", "gpu_decode_records", "reads", "bases"):
+                if k in med:
+                    o[k] = med[k]
+            if "gpu_decode_scan_ms" in med:
+                gb = med["gpu_inflate_bytes"] / 1e9
+                o["scan_GB_per_s_over_inflated_bytes"] = gb / max(med["gpu_decode_scan_ms"] / 1e3, 1e-12)
+                o["fill_GB_per_s_over_inflated_bytes"] = gb / max(med["gpu_decode_fill_ms"] / 1e3, 1e-12)
+            return o
+        return {"workload": "synthetic chr20 of %.2f Mbp at 60x (10 kb reads): %d reads, BAM %.1f MB"
+                            % (swept, info["reads"], info["bam_bytes"] / 1e6),
+                "form": "fused call_variant path; host inflate (default), gpu_inflate=True, gpu_decode=True; alternating runs; the "
+                        "ms figures are HIP-event sums over the launches of the service stream",
+                **{m: leg(res[m]) for m in modes}}
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--mbp", type=float, default=3.2)
     ap.add_argument("--gpu_inflate", action="store_true", help="the host-vs-GPU BGZF inflate comparison instead of the default leg")
+    ap.add_argument("--gpu_decode", action="store_true", help="host inflate vs --gpu_inflate vs --gpu_decode, three runs each")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON result here")
     a = ap.parse_args()
     from pepper_thesis_amd import runtime, synth
     c = runtime.Context(0)
-    if a.gpu_inflate:
+    if a.gpu_decode:
+        r = run_gpu_decode(c, synth.make_weights_p1(1234), mbp=a.mbp)
+    elif a.gpu_inflate:
         r = run_gpu_inflate(c, synth.make_weights_p1(1234), mbp=a.mbp)
     else:
         r = run(c, synth.make_weights_p1(1234), mbp=a.mbp)
