@@ -7,6 +7,7 @@
 // stay fp32.
 #pragma once
 #include "pv_common.hpp"
+#include "rnn_plan.hpp"
 
 // C = A . W^T (+ bias) through k_gemm_bf16x3. A [M][K], W [N][K] in "split8" rows (per 8 elements: 8 bf16 hi, 8 bf16 lo);
 // C [splits][M][N] fp32 row-major, or (quads) [M/4][N][4]. M % 4 == 0, N % 256 == 0, K % (32 * splits) == 0.
@@ -104,5 +105,6 @@ struct pv_p2_bf16_weights {
 // dense_w [5][256] (host) -> [2 dirs][4 waves][2 k-steps][hi 1 KB | lo 1 KB]
 int pv_pack_p2_dense(const float* dense_w, unsigned char** d_frag, std::vector<void*>& owned);
 int pv_pack_p2_dense16(const float* dense_w, unsigned char** d_frag, std::vector<void*>& owned);
-int pv_p2_bf16_forward(pv_ctx* ctx, const pv_p2_bf16_weights& w, const uint8_t* d_images, int64_t B, uint8_t* d_labels, float* d_acc,
-                       hipStream_t st, int seq, int nwin, const float* d_hidden_in, float* d_hidden_out, float* d_logits);
+// `pl`: the call's plan (pv_plan_p2): PV_P2_GRU16 or PV_P2_REC
+int pv_p2_bf16_forward(pv_ctx* ctx, const pv_p2_plan& pl, const pv_p2_bf16_weights& w, const uint8_t* d_images, int64_t B, uint8_t* d_labels,
+                       float* d_acc, hipStream_t st, int seq, int nwin, const float* d_hidden_in, float* d_hidden_out, float* d_logits);

@@ -1108,61 +1108,48 @@ extern "C" int pv_rnn_load_p2(pv_ctx* ctx, const pv_weights_p2* w, int dtype) {
     return PV_OK;
 }
 
+// the last kernel of every P2 call (k_gru_finish): the pending error word poisons the outputs, the unit-split form's epoch moves on
+static void launch_finish(pv_ctx* ctx, unsigned* epoch, uint8_t* d_labels, float* acc, float* d_logits, float* d_hidden_out, int64_t B,
+                          int seq, hipStream_t st) {
+    GruFinishArgs fin;
+    fin.epoch = epoch; fin.err = ctx->p2->us_err; fin.labels = d_labels; fin.n_labels = d_labels ? B * seq : 0;
+    fin.f[0] = acc; fin.nf[0] = B * seq * NCLS;
+    fin.f[1] = d_logits; fin.nf[1] = d_logits ? B * WIN * NCLS : 0;
+    fin.f[2] = d_hidden_out; fin.nf[2] = d_hidden_out ? B * 2 * HG : 0;
+    k_gru_finish<<<(unsigned)std::min<int64_t>((B * seq + 255) / 256, 4 * ctx->num_cu), 256, 0, st>>>(fin);
+}
+
+// one call of B chunks in the form rnn_plan.hpp names
 static int p2_launch(pv_ctx* ctx, const uint8_t* d_images, int64_t B, uint8_t* d_labels, float* d_acc, hipStream_t st,
                      int seq = SEQ, int nwin = NWIN, const float* d_hidden_in = nullptr, float* d_hidden_out = nullptr,
                      float* d_logits = nullptr) {
     pv_rnn_p2* m = ctx->p2;
+    const pv_p2_plan pl = pv_plan_p2(m->dtype, B, ctx->num_cu, ctx->opt);
+    int rc;
+    GruArgs g;
+    g.acc = d_acc;
+    if (!g.acc && (rc = pv_get(ctx, "p2.acc", (size_t)B * seq * NCLS, &g.acc))) return rc;
     if (m->dtype == PV_DTYPE_BF16_INPUT_GEMM) {
         // the layer-wise path: no split form, no exchange (the finishing kernel still honours a pending error word)
-        float* acc = d_acc;
-        int rcb;
-        if (!acc && (rcb = pv_get(ctx, "p2.acc", (size_t)B * seq * NCLS, &acc))) return rcb;
-        if ((rcb = pv_p2_bf16_forward(ctx, m->bf, d_images, B, d_labels, acc, st, seq, nwin, d_hidden_in, d_hidden_out, d_logits))) return rcb;
-        GruFinishArgs fb;
-        fb.epoch = nullptr; fb.err = m->us_err; fb.labels = d_labels; fb.n_labels = d_labels ? B * seq : 0;
-        fb.f[0] = acc; fb.nf[0] = B * seq * NCLS;
-        fb.f[1] = d_logits; fb.nf[1] = d_logits ? B * WIN * NCLS : 0;
-        fb.f[2] = d_hidden_out; fb.nf[2] = d_hidden_out ? B * 2 * HG : 0;
-        k_gru_finish<<<(unsigned)std::min<int64_t>((B * seq + 255) / 256, 4 * ctx->num_cu), 256, 0, st>>>(fb);
+        if ((rc = pv_p2_bf16_forward(ctx, pl, m->bf, d_images, B, d_labels, g.acc, st, seq, nwin, d_hidden_in, d_hidden_out, d_logits))) return rc;
+        launch_finish(ctx, nullptr, d_labels, g.acc, d_logits, d_hidden_out, B, seq, st);
         PV_HIP(hipGetLastError());
         return PV_OK;
     }
-    // tile form: 32-row tiles once they fill the chip, else 16-row tiles (twice the workgroups, half the time per step)
-    int tr = ((B + 31) / 32 >= ctx->num_cu) ? 32 : 16;
-    if (ctx->opt.gru_rows) tr = ctx->opt.gru_rows;
-    const int f = tr == 16 ? 1 : 0;
-    const int64_t n_tiles = (B + tr - 1) / tr;
-    GruArgs g;
+    const int tr = pl.rows, f = tr == 16 ? 1 : 0;
+    const int64_t n_tiles = pl.Bp / tr;
     g.images = d_images;
     g.enc_wp = m->enc_wp[f]; g.dec_wp = m->dec_wp[f]; g.enc_bias = m->enc_bias; g.dec_bias = m->dec_bias;
     g.dense_w = m->dense_w; g.dense_b = m->dense_b;
-    int rc;
     if ((rc = pv_get(ctx, "p2.enc_out", (size_t)n_tiles * WIN * tr * KPD, &g.enc_out))) return rc;
     if ((rc = pv_get(ctx, "p2.dec_out", (size_t)n_tiles * WIN * tr * KPD, &g.dec_out))) return rc;
-    g.acc = d_acc;
-    if (!g.acc)
-        if ((rc = pv_get(ctx, "p2.acc", (size_t)B * seq * NCLS, &g.acc))) return rc;
-    g.labels = d_labels;
-    g.B = B;
+    g.labels = d_labels; g.B = B;
     g.seq = seq; g.nwin = nwin; g.hidden_in = d_hidden_in; g.hidden_out = d_hidden_out; g.logits = d_logits;
     if ((rc = pv_zero_async(g.acc, (size_t)B * seq * NCLS * sizeof(float), st))) return rc;
-    // the two directions of a tile on two CUs while every (tile, direction) workgroup has a CU of its own: the launch is a
-    // chain of dependent steps, and a step then carries one direction's MFMAs per SIMD instead of two
-    bool split = tr == 16 && 2 * n_tiles <= ctx->num_cu && ctx->opt.gru_split && !ctx->opt.shared_device;
-    g.pair_flags = nullptr;
-    g.hx = nullptr; g.quad_flags = nullptr; g.tag_base = 0; g.err = m->us_err; g.epoch = nullptr;
+    g.pair_flags = nullptr; g.hx = nullptr; g.quad_flags = nullptr; g.tag_base = 0; g.err = m->us_err; g.epoch = nullptr;
     g.spin_limit = 1 << ctx->opt.exchange_spin_log2; g.drop_part = ctx->opt.debug_drop_part;
-    GruFinishArgs fin;
-    fin.epoch = nullptr; fin.err = m->us_err; fin.labels = d_labels; fin.n_labels = d_labels ? B * seq : 0;
-    fin.f[0] = g.acc; fin.nf[0] = B * seq * NCLS;
-    fin.f[1] = d_logits; fin.nf[1] = d_logits ? B * WIN * NCLS : 0;
-    fin.f[2] = d_hidden_out; fin.nf[2] = d_hidden_out ? B * 2 * HG : 0;
-    const unsigned fin_grid = (unsigned)std::min<int64_t>((B * seq + 255) / 256, 4 * ctx->num_cu);
-    // unit-split form: (tile, direction, half of the units) workgroups with a per-step h exchange, while all of them can be
-    // resident at once (up to 1024 chunks on 256 CUs); option gru_usplit = 0 keeps the direction-split form, gru_split = 0 or
-    // shared_device = 1 the one-workgroup form
-    const bool usplit = tr == 16 && 4 * n_tiles <= ctx->num_cu && ctx->opt.gru_usplit && ctx->opt.gru_split && !ctx->opt.shared_device;
-    if (usplit) {
+    if (pl.kind == PV_P2_US) {
+        // (tile, direction, half of the units) workgroups with a per-step h exchange
         g.enc_wp = m->enc_wp[3]; g.dec_wp = m->dec_wp[3];
         const size_t nfl = (size_t)n_tiles * 4 * US_FLAG_STRIDE;
         if ((rc = pv_get(ctx, "p2.quad_flags", nfl, &g.quad_flags))) return rc;
@@ -1176,27 +1163,21 @@ static int p2_launch(pv_ctx* ctx, const uint8_t* d_images, int64_t B, uint8_t* d
             if ((rc = pv_zero_async(g.hx, nhx * sizeof(u32x4), st))) return rc;
         }
         g.epoch = m->us_epoch;
-        {
-            pv_prof_scope ps(ctx, "k_gru_us", st);
-            k_gru_us<<<(unsigned)(((n_tiles + 7) / 8) * 32), 256, LDS_US, st>>>(g);
+        pv_prof_scope ps(ctx, "k_gru_us", st);
+        k_gru_us<<<(unsigned)(((n_tiles + 7) / 8) * 32), 256, LDS_US, st>>>(g);
+    } else {
+        const bool split = pl.kind == PV_P2_DSPLIT;   // the two directions of a tile on two CUs
+        if (split) {
+            g.enc_wp = m->enc_wp[2]; g.dec_wp = m->dec_wp[2];   // [h | x] stream order of the overlapped window form
+            if ((rc = pv_get(ctx, "p2.pair_flags", (size_t)2 * n_tiles + 96, &g.pair_flags))) return rc;
+            if ((rc = pv_zero_async(g.pair_flags, ((size_t)2 * n_tiles + 96) * sizeof(int), st))) return rc;
         }
-        fin.epoch = m->us_epoch;
-        k_gru_finish<<<fin_grid, 256, 0, st>>>(fin);
-        PV_HIP(hipGetLastError());
-        return PV_OK;
-    }
-    if (split) {
-        g.enc_wp = m->enc_wp[2]; g.dec_wp = m->dec_wp[2];   // [h | x] stream order of the overlapped window form
-        if ((rc = pv_get(ctx, "p2.pair_flags", (size_t)2 * n_tiles + 96, &g.pair_flags))) return rc;
-        if ((rc = pv_zero_async(g.pair_flags, ((size_t)2 * n_tiles + 96) * sizeof(int), st))) return rc;
-    }
-    {
         pv_prof_scope ps(ctx, "k_gru_p2", st);
         if (tr == 32) k_gru_p2<32, false><<<(unsigned)n_tiles, 512, lds_p2<32, false>(), st>>>(g);
         else if (split) k_gru_p2<16, true><<<(unsigned)(2 * n_tiles), 256, lds_p2<16, true>(), st>>>(g);
         else k_gru_p2<16, false><<<(unsigned)n_tiles, 512, lds_p2<16, false>(), st>>>(g);
     }
-    k_gru_finish<<<fin_grid, 256, 0, st>>>(fin);
+    launch_finish(ctx, g.epoch, d_labels, g.acc, d_logits, d_hidden_out, B, seq, st);
     PV_HIP(hipGetLastError());
     return PV_OK;
 }

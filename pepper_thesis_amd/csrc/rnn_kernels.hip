@@ -27,6 +27,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <mutex>
+#include <optional>
 
 namespace {
 
@@ -37,10 +38,10 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 constexpr int T_STEPS = 33;
 constexpr int F_IN = 26;
 constexpr int H = 256;            // LSTM hidden
-constexpr int ROWS = 32;          // batch rows per workgroup (one MFMA M-tile)
-constexpr int HEAD_N = 512;
+constexpr int ROWS = PV_P1_ROWS;  // batch rows per workgroup (one MFMA M-tile)
+constexpr int HEAD_N = PV_HEAD_N;
 constexpr int HEAD_K = T_STEPS * 2 * H;  // 16896
-constexpr int HEAD_MAX_SPLITS = 33;      // split-K factor of linear_1 is chosen per launch from {1, 3, 11, 33}
+constexpr int HEAD_MAX_SPLITS = PV_HEAD_MAX_SPLITS;   // split-K factor of linear_1 is chosen per launch from {1, 3, 11, 33}
 
 // v_exp_f32 / v_rcp_f32 (1 ulp) instead of the IEEE division sequence: ~3x fewer VALU instructions in the
 // cell update; absolute error of sigmoid/tanh stays ~1e-7 (tests pin 2e-5 on layer outputs).
@@ -803,7 +804,7 @@ __device__ unsigned long long g_gemm_stamps[8];
 template <int TERMS>
 __device__ __forceinline__ void gemm_body(const GemmArgs& g) {
     static_assert(TERMS == 3 || TERMS == 6, "3-term (split8 operands) or 6-term (fp32 operands)");
-    constexpr int BM = 256, BN = 256, BK = 32;
+    constexpr int BM = PV_GEMM_TILE, BN = PV_GEMM_TILE, BK = 32;
     constexpr int ARR = BM * BK * 2;          // bytes of one bf16 operand image (16 KB); buffer = [A_hi | A_lo | W_hi | W_lo]
     extern __shared__ __attribute__((aligned(16))) unsigned char smg[];
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1146,9 +1147,7 @@ static void pack_linear(const float* W, int K, int TR, std::vector<float>& wp) {
 
 }  // namespace
 
-static constexpr int64_t P1_BF16_MAX_BATCH = 16384;
 template <int KP> constexpr size_t lds_lstm_split() { return (size_t)(16 * (KP + 4) + 2 * 16 * (H + 4)) * sizeof(float); }
-static constexpr int SP_MAX_TILES = 64;   // 16-row tiles the exchange buffers are sized for (1024 windows)
 template <int KP, int TR> constexpr size_t lds_lstm() { return (size_t)(TR * (KP + 4) + 2 * TR * (H + 4)) * sizeof(float); }
 static constexpr size_t LDS_GEMM = (size_t)2 * 4 * 256 * 32 * 2 + 2048 + 2048;   // 2 buffers x {A_hi, A_lo, W_hi, W_lo} x 256 rows x 32 bf16 = 128 KB, + two bias slots + completion flags
 static constexpr size_t LDS_SPLITK = (size_t)ROWS * (2 * H + 4) * sizeof(float);
@@ -1269,8 +1268,8 @@ extern "C" int pv_rnn_load_p1(pv_ctx* ctx, const pv_weights_p1* w, int dtype) {
         if ((rc = dev_upload(wp, &m->dec_wps[f], m->owned))) return rc;
     }
     {
-        const size_t hx_bytes = (size_t)SP_MAX_TILES * 2 * SP_HX_QUADS * sizeof(u32x4);
-        const size_t fl_bytes = (size_t)SP_MAX_TILES * 2 * 4 * SP_FLAG_STRIDE * sizeof(int);
+        const size_t hx_bytes = (size_t)PV_SP_MAX_TILES * 2 * SP_HX_QUADS * sizeof(u32x4);
+        const size_t fl_bytes = (size_t)PV_SP_MAX_TILES * 2 * 4 * SP_FLAG_STRIDE * sizeof(int);
         PV_HIP(hipMalloc((void**)&m->sp_hx, hx_bytes));
         m->owned.push_back(m->sp_hx);
         PV_HIP(hipMalloc((void**)&m->sp_flags, fl_bytes));
@@ -1331,165 +1330,106 @@ extern "C" int pv_rnn_load_p1(pv_ctx* ctx, const pv_weights_p1* w, int dtype) {
     return PV_OK;
 }
 
-// tail of the head: 16-row tiles unless 32-row tiles already fill the chip
-static void launch_tail(pv_ctx* ctx, pv_rnn_p1* m, TailArgs& t, int n_tiles32, hipStream_t st) {
-    int tr = n_tiles32 >= ctx->num_cu ? 32 : 16;
-    if (ctx->opt.tail_rows) tr = ctx->opt.tail_rows;
+// k_head_tail over the linear_1 slabs part [splits][part_rows][512]
+static void launch_tail(pv_ctx* ctx, const pv_p1_plan& pl, const float* part, int64_t part_rows, float* d_probs, int64_t B, hipStream_t st) {
+    const pv_rnn_p1* m = ctx->p1;
+    const int tr = pl.tail_rows, n_tiles32 = (int)((B + ROWS - 1) / ROWS);
+    TailArgs t;
+    t.part = part; t.b1 = m->b1; t.splits = pl.splits; t.part_rows = part_rows;
+    t.wo = m->wo; t.bo = m->bo; t.probs = d_probs; t.B = B; t.epoch = m->sp_epoch; t.err = m->sp_err;
     for (int i = 0; i < 4; i++) { t.wp[i] = m->wlp[tr == 16 ? 1 : 0][i]; t.b[i] = m->bl[i]; }
     pv_prof_scope ps(ctx, "k_head_tail", st);
     if (tr == 32) k_head_tail<32><<<(unsigned)n_tiles32, 256, lds_tail<32>(), st>>>(t);
     else k_head_tail<16><<<(unsigned)(2 * n_tiles32), 256, lds_tail<16>(), st>>>(t);
 }
 
-// PV_DTYPE_F32 calls that take the split-6 chain: large enough (option p1_f32x6_min_batch) and no tile form forced
-static bool p1_use_x6(const pv_ctx* ctx, int64_t B) {
-    return ctx->p1->dtype == PV_DTYPE_F32 && !ctx->opt.lstm_rows && B >= ctx->opt.p1_f32x6_min_batch;
-}
+// What tells the two chains on the bf16 MFMA apart (p1_forward_mfma). Rows of the layer outputs are 2 KB in both: split8
+// (bf16 hi + lo per element) in the bf16x3 chain, fp32 in the split-6 chain.
+struct P1Chain {
+    int terms;                                 // of every product: 3 (split8 operands) or 6 (three-piece operands)
+    const unsigned char *enc_rec, *dec_rec;    // fragment streams of k_rec_bf16
+    const void *dec_wih, *w1;                  // GEMM weights: split8 rows or fp32
+    const char* enc_buf;                       // workspace of the encoder's time-major output
+    const char *n_enc, *n_dec_scope, *n_dec_gemm, *n_dec, *n_lin1;   // profile names
+};
 
-// The split-6 chain (PV_DTYPE_F32, large calls): every matrix product of the RNN on the bf16 MFMA as six terms of three-piece
-// operands (fp32-class: the dropped terms are below 2^-24 relative), fp32 accumulation, fp32 cell updates, fp32 tail.
-//   encoder   k_rec_bf16<LSTM, enc, X6>: byte x-part (3 terms) + h-part (6 terms) per step -> fp32 rows, time-major
-//   decoder   k_gemm_bf16x6 (G = enc . W_ih^T + b, quads) + k_rec_bf16<LSTM, dec, X6> on G -> fp32 rows, batch-major (dec_out)
-//   head      linear_1 as a split-K k_gemm_bf16x6 -> k_head_tail (sum of slabs, linear_2..5, output layer, softmax in fp32)
-// The decoder's two launches form ONE profile scope "k_lstm_layer_dec" (the fp32 chain's fused decoder kernel), so per-layer
-// figures compare across the two chains; the launches inside carry names outside that prefix.
-static int p1_forward_x6(pv_ctx* ctx, const int8_t* d_images, int64_t B, float* d_probs, float* enc_out, float* dec_out, float* part,
-                         hipStream_t st, bool taps) {
+// Every matrix product of the RNN on the bf16 MFMA, fp32 accumulation, fp32 cell updates: the bf16x3 chain (PV_DTYPE_BF16_INPUT_GEMM,
+// 3-term split products) and the split-6 chain (PV_DTYPE_F32, large calls: six terms of three-piece operands, fp32-class: the
+// dropped terms are below 2^-24 relative).
+//   encoder   k_rec_bf16<LSTM, enc>: byte x-part + h-part per step -> rows, time-major
+//   decoder   one GEMM (G = enc . W_ih^T + b, quads) + k_rec_bf16<LSTM, dec> on G -> rows, batch-major (split-6: dec_out itself,
+//             fp32 [Bp][T][2H]: the head's operand and the decoder tap)
+//   head      linear_1 as a split-K GEMM into slabs [splits][Bp][512] -> k_head_tail or k_tail_bf16 (sum of slabs, linear_2..5,
+//             output layer, softmax)
+// The split-6 decoder's two launches form ONE profile scope "k_lstm_layer_dec" (the fp32 chain's fused decoder kernel), so
+// per-layer figures compare across the two chains; the launches inside carry names outside that prefix.
+static int p1_forward_mfma(pv_ctx* ctx, const pv_p1_plan& pl, const int8_t* d_images, int64_t B, float* d_probs, float* enc_out,
+                           float* dec_out, float* part, hipStream_t st, bool taps) {
     pv_rnn_p1* m = ctx->p1;
-    const int n_tiles = (int)((B + ROWS - 1) / ROWS);
-    const int64_t Bp = (int64_t)n_tiles * ROWS, M = Bp * T_STEPS;
-    float *enc_tm = nullptr, *G = nullptr;
+    const bool x6 = pl.chain == PV_CHAIN_X6;
+    const P1Chain c = x6 ? P1Chain{6, m->enc_r6, m->dec_r6, m->dec_wih_f, m->w1_f, "p1.enc_tm", "k_rec_x6_lstm_enc", "k_lstm_layer_dec",
+                                   "k_gemm_bf16x6_dec", "k_rec_x6_lstm_dec", "k_gemm_bf16x6_lin1"}
+                         : P1Chain{3, m->enc_rb, m->dec_rb, m->dec_wih_s, m->w1_s, "p1.enc_split", "k_rec_bf16_lstm_enc", nullptr,
+                                   "k_gemm_bf16x3_dec", "k_rec_bf16_lstm_dec", "k_gemm_bf16x3_lin1"};
+    const int64_t Bp = pl.Bp, M = Bp * T_STEPS;
+    const size_t out_bytes = (size_t)M * 2 * H * 4;
+    unsigned char *enc = nullptr, *dec = reinterpret_cast<unsigned char*>(dec_out);
+    float* G = nullptr;
     int rc;
-    if ((rc = pv_get(ctx, "p1.enc_tm", (size_t)M * 2 * H, &enc_tm)) || (rc = pv_get(ctx, "p1.G", (size_t)M * 2048, &G))) return rc;
+    if ((rc = pv_get(ctx, c.enc_buf, out_bytes, &enc)) || (!x6 && (rc = pv_get(ctx, "p1.dec_split", out_bytes, &dec))) ||
+        (rc = pv_get(ctx, "p1.G", (size_t)M * 2048, &G))) return rc;
     pv_rec_desc re = {};
-    re.cell = 4; re.enc = 1; re.wp = m->enc_r6; re.bias = m->enc_bias; re.x = d_images; re.x_row_bytes = PV_WINDOW_BYTES; re.x_t0 = 0;
-    re.xf = F_IN; re.x_signed = 1; re.B = B; re.Bp = Bp; re.T = T_STEPS; re.out_tm = reinterpret_cast<unsigned char*>(enc_tm);
-    re.out_f32 = taps ? enc_out : nullptr; re.mt = 1; re.x6 = 1; re.prof_name = "k_rec_x6_lstm_enc";
+    re.cell = 4; re.enc = 1; re.wp = c.enc_rec; re.bias = m->enc_bias; re.x = d_images; re.x_row_bytes = PV_WINDOW_BYTES; re.x_t0 = 0;
+    re.xf = F_IN; re.x_signed = 1; re.B = B; re.Bp = Bp; re.T = T_STEPS; re.out_tm = enc; re.out_f32 = taps ? enc_out : nullptr;
+    re.mt = pl.mt; re.x6 = x6; re.prof_name = c.n_enc;
     if ((rc = pv_rec_bf16_async(ctx, re, st))) return rc;
     {
-        pv_prof_scope ps(ctx, "k_lstm_layer_dec", st);
+        std::optional<pv_prof_scope> ps;
+        if (c.n_dec_scope) ps.emplace(ctx, c.n_dec_scope, st);
         pv_gemm_desc ga = {};
-        ga.A = reinterpret_cast<const unsigned char*>(enc_tm); ga.W = reinterpret_cast<const unsigned char*>(m->dec_wih_f);
-        ga.bias = m->dec_bias_cat; ga.C = G; ga.M = M; ga.N = 2048; ga.K = 2 * H; ga.splits = 1; ga.quads = 1; ga.terms = 6;
-        ga.prof_name = "k_gemm_bf16x6_dec";
+        ga.A = enc; ga.W = static_cast<const unsigned char*>(c.dec_wih); ga.bias = m->dec_bias_cat; ga.C = G; ga.M = M; ga.N = 2048;
+        ga.K = 2 * H; ga.splits = 1; ga.quads = 1; ga.terms = c.terms; ga.prof_name = c.n_dec_gemm;
         if ((rc = pv_gemm_bf16x3_async(ctx, ga, st))) return rc;
         pv_rec_desc rd = {};
-        rd.cell = 4; rd.enc = 0; rd.G = G; rd.wp = m->dec_r6; rd.B = B; rd.Bp = Bp; rd.T = T_STEPS;
-        rd.out_bm = reinterpret_cast<unsigned char*>(dec_out);   // fp32 [Bp][T][2H]: the head's operand and the decoder tap
-        rd.mt = 1; rd.x6 = 1; rd.prof_name = "k_rec_x6_lstm_dec";
+        rd.cell = 4; rd.enc = 0; rd.G = G; rd.wp = c.dec_rec; rd.B = B; rd.Bp = Bp; rd.T = T_STEPS; rd.out_bm = dec;
+        rd.out_f32 = taps && !x6 ? dec_out : nullptr; rd.mt = pl.mt; rd.x6 = x6; rd.prof_name = c.n_dec;
         if ((rc = pv_rec_bf16_async(ctx, rd, st))) return rc;
     }
-    // linear_1 (K = 16896) as a split-K GEMM into slabs [splits][Bp][512]: at least the 11 slabs of k_head_splitk (shorter fp32
-    // accumulation chains: with 4 slabs of 4224 the probabilities drift 1.8e-6 from the f32 kernels), more while the work
-    // items do not fill the chip
-    static const int divs[] = {11, 12, 16, 22, 24, 33};
-    const int tiles = (int)((Bp + 255) / 256) * (HEAD_N / 256);
-    int gs = 33;
-    for (int dv : divs) if (tiles * dv >= ctx->num_cu) { gs = dv; break; }
     pv_gemm_desc gl = {};
-    gl.A = reinterpret_cast<const unsigned char*>(dec_out); gl.W = reinterpret_cast<const unsigned char*>(m->w1_f); gl.bias = nullptr;
-    gl.C = part; gl.M = Bp; gl.N = HEAD_N; gl.K = HEAD_K; gl.splits = gs; gl.quads = 0; gl.terms = 6;
-    gl.prof_name = "k_gemm_bf16x6_lin1";
+    gl.A = dec; gl.W = static_cast<const unsigned char*>(c.w1); gl.bias = nullptr; gl.C = part; gl.M = Bp; gl.N = HEAD_N; gl.K = HEAD_K;
+    gl.splits = pl.splits; gl.quads = 0; gl.terms = c.terms; gl.prof_name = c.n_lin1;
     if ((rc = pv_gemm_bf16x3_async(ctx, gl, st))) return rc;
-    TailArgs tf;
-    tf.part = part; tf.b1 = m->b1; tf.splits = gs; tf.part_rows = Bp;
-    tf.wo = m->wo; tf.bo = m->bo; tf.probs = d_probs; tf.B = B; tf.epoch = m->sp_epoch; tf.err = m->sp_err;
-    launch_tail(ctx, m, tf, n_tiles, st);
-    PV_HIP(hipGetLastError());
-    return PV_OK;
+    if (pl.tail == PV_TAIL_HEAD_TAIL) {
+        launch_tail(ctx, pl, part, Bp, d_probs, B, st);
+        PV_HIP(hipGetLastError());
+        return PV_OK;
+    }
+    pv_tail_desc tb = {};
+    tb.part = part; tb.b1 = m->b1; tb.splits = pl.splits; tb.part_rows = Bp; tb.wp = m->tail_wb;
+    for (int i = 0; i < 4; i++) tb.b[i] = m->bl[i];
+    tb.wo = m->wo; tb.bo = m->bo; tb.probs = d_probs; tb.B = B; tb.epoch = m->sp_epoch; tb.err = m->sp_err;
+    return pv_tail_bf16_async(ctx, tb, st);
 }
 
+// one launch of B windows (a whole call, or one chunk of it) in the form rnn_plan.hpp names
 static int p1_forward_launch(pv_ctx* ctx, const int8_t* d_images, int64_t B, float* d_probs, float* enc_out,
                              float* dec_out, float* part, hipStream_t st, bool taps = false) {
     pv_rnn_p1* m = ctx->p1;
-    if (p1_use_x6(ctx, B)) return p1_forward_x6(ctx, d_images, B, d_probs, enc_out, dec_out, part, st, taps);
-    const int n_tiles = (int)((B + ROWS - 1) / ROWS);   // 32-row tiles: the granularity of every buffer and of the head
-    // LSTM tile form: 32-row tiles once (tile, direction) workgroups fill the chip, else 16-row tiles: twice the workgroups,
-    // half the MFMA cycles per time step (the bf16x3 mode has its own layer kernel, below)
-    int tr = (int64_t)n_tiles * 2 >= ctx->num_cu ? 32 : 16;
-    if (ctx->opt.lstm_rows) tr = ctx->opt.lstm_rows;
-    const int f = tr == 16 ? 1 : 0;
-    const int n_lt = n_tiles * (ROWS / tr);             // whole 32-row tiles are covered in either form
-    const unsigned lstm_grid = (unsigned)(((n_lt + 3) / 4) * 8);
-    if (m->dtype == PV_DTYPE_BF16_INPUT_GEMM && B >= ctx->opt.p1_bf16_min_batch) {   // (a small call is faster on the fp32 kernels below)
-        // every matrix product on the bf16 MFMA: encoder layer (x-part in the step) -> decoder input projection as ONE GEMM
-        // -> decoder layer on the projections -> linear_1 as a split-K GEMM -> fp32 tail. 64-row tiles (one weight fetch of
-        // the recurrent stream feeds twice the rows) once 32-row (tile, direction) workgroups would not fit the chip at once.
-        const int mt = (int64_t)n_tiles * 2 > ctx->num_cu ? 2 : 1;
-        const int64_t Bp = (B + 32 * mt - 1) / (32 * mt) * (32 * mt), M = Bp * T_STEPS;
-        const size_t nel = (size_t)Bp * T_STEPS * 2 * H;
-        unsigned char *enc_split = nullptr, *dec_split = nullptr;
-        float* G = nullptr;
-        int rcb;
-        if ((rcb = pv_get(ctx, "p1.enc_split", nel * 4, &enc_split)) || (rcb = pv_get(ctx, "p1.dec_split", nel * 4, &dec_split)) ||
-            (rcb = pv_get(ctx, "p1.G", (size_t)M * 2048, &G))) return rcb;
-        pv_rec_desc re = {};
-        re.cell = 4; re.enc = 1; re.wp = m->enc_rb; re.bias = m->enc_bias; re.x = d_images; re.x_row_bytes = PV_WINDOW_BYTES; re.x_t0 = 0;
-        re.xf = F_IN; re.x_signed = 1; re.B = B; re.Bp = Bp; re.T = T_STEPS; re.out_tm = enc_split; re.out_f32 = taps ? enc_out : nullptr;
-        re.mt = mt; re.prof_name = "k_rec_bf16_lstm_enc";
-        if ((rcb = pv_rec_bf16_async(ctx, re, st))) return rcb;
-        pv_gemm_desc ga = {};
-        ga.A = enc_split; ga.W = m->dec_wih_s; ga.bias = m->dec_bias_cat; ga.C = G; ga.M = M; ga.N = 2048; ga.K = 2 * H; ga.splits = 1;
-        ga.quads = 1; ga.prof_name = "k_gemm_bf16x3_dec";
-        if ((rcb = pv_gemm_bf16x3_async(ctx, ga, st))) return rcb;
-        pv_rec_desc rd = {};
-        rd.cell = 4; rd.enc = 0; rd.G = G; rd.wp = m->dec_rb; rd.B = B; rd.Bp = Bp; rd.T = T_STEPS; rd.out_bm = dec_split;
-        rd.out_f32 = taps ? dec_out : nullptr; rd.mt = mt; rd.prof_name = "k_rec_bf16_lstm_dec";
-        if ((rcb = pv_rec_bf16_async(ctx, rd, st))) return rcb;
-        // linear_1 as a split-K bf16x3 GEMM into slabs [splits][Bp][512]: the smallest split factor (a divisor of the 528
-        // K steps of 32) whose work items fill the chip
-        static const int divs[] = {1, 2, 3, 4, 6, 8, 11, 12, 16, 22, 24, 33};
-        const int tiles = (int)((Bp + 255) / 256) * (HEAD_N / 256);
-        int gs = 33;
-        for (int dv : divs) if (tiles * dv >= ctx->num_cu) { gs = dv; break; }
-        pv_gemm_desc gl = {};
-        gl.A = dec_split; gl.W = m->w1_s; gl.bias = nullptr; gl.C = part; gl.M = Bp; gl.N = HEAD_N; gl.K = HEAD_K; gl.splits = gs; gl.quads = 0;
-        gl.prof_name = "k_gemm_bf16x3_lin1";
-        if ((rcb = pv_gemm_bf16x3_async(ctx, gl, st))) return rcb;
-        // sum of the slabs + linear_2..5 + output layer + softmax. Large batches: the four 512 x 512 layers as 3-term split products
-        // too (k_tail_bf16, 64 rows per workgroup: 0.11 ms per 8192 windows against 0.27 for k_head_tail); a small batch is a few
-        // workgroups each pulling the 4 MB of weights through one CU (0.30 ms for 64-512 windows), where k_head_tail's 16-row
-        // tiles spread the same fetch over four times the CUs (0.14 ms): it keeps those
-        if ((B + 63) / 64 < ctx->num_cu / 4) {
-            TailArgs tf;
-            tf.part = part; tf.b1 = m->b1; tf.splits = gs; tf.part_rows = Bp;
-            tf.wo = m->wo; tf.bo = m->bo; tf.probs = d_probs; tf.B = B; tf.epoch = m->sp_epoch; tf.err = m->sp_err;
-            launch_tail(ctx, m, tf, n_tiles, st);
-            PV_HIP(hipGetLastError());
-            return PV_OK;
-        }
-        pv_tail_desc tb = {};
-        tb.part = part; tb.b1 = m->b1; tb.splits = gs; tb.part_rows = Bp; tb.wp = m->tail_wb;
-        for (int i = 0; i < 4; i++) tb.b[i] = m->bl[i];
-        tb.wo = m->wo; tb.bo = m->bo; tb.probs = d_probs; tb.B = B; tb.epoch = m->sp_epoch; tb.err = m->sp_err;
-        return pv_tail_bf16_async(ctx, tb, st);
-    }
-    LstmArgs e;
-    e.x_i8 = d_images; e.x_f32 = nullptr; e.wp = m->enc_wp[f]; e.bias = m->enc_bias; e.out = enc_out; e.B = B; e.n_tiles = n_lt;
-    // unit-split form: one small fp32 batch whose (16-row tile, direction, part of the hidden units) workgroups all fit on
-    // the chip at once: four parts up to 512 windows on 256 CUs, two parts up to 1024. Options lstm_split = 0, an explicit
-    // lstm_rows, or shared_device = 1 (other work on this GPU: residency is not given) keep the one-workgroup form
-    const int n_t16 = n_tiles * 2;
-    const int sp_ns = (int64_t)n_t16 * 2 * 4 <= ctx->num_cu ? 4 : 2;
-    bool split = n_t16 <= SP_MAX_TILES && (int64_t)n_t16 * 2 * sp_ns <= ctx->num_cu;
-    if (!ctx->opt.lstm_split || ctx->opt.lstm_rows || ctx->opt.shared_device) split = false;
-    LstmSplitArgs se;
-    const unsigned split_grid = (unsigned)(((n_t16 + 3) / 4) * 8 * sp_ns);
-    if (split) {
+    const pv_p1_plan pl = pv_plan_p1(m->dtype, B, ctx->num_cu, ctx->opt);
+    if (pl.chain != PV_CHAIN_F32) return p1_forward_mfma(ctx, pl, d_images, B, d_probs, enc_out, dec_out, part, st, taps);
+    const int n_tiles = (int)(pl.Bp / ROWS);   // 32-row tiles: the granularity of every buffer and of the head
+    if (pl.lstm == PV_LSTM_SPLIT4 || pl.lstm == PV_LSTM_SPLIT2) {
+        const int sp_ns = pl.lstm == PV_LSTM_SPLIT4 ? 4 : 2, n_t16 = n_tiles * 2;
+        const unsigned split_grid = (unsigned)(((n_t16 + 3) / 4) * 8 * sp_ns);
+        LstmSplitArgs se;
         se.x_i8 = d_images; se.x_f32 = nullptr; se.wp = m->enc_wps[sp_ns == 4 ? 0 : 1]; se.bias = m->enc_bias; se.out = enc_out;
         se.hx = m->sp_hx; se.flags = m->sp_flags; se.B = B; se.n_tiles = n_t16; se.epoch = m->sp_epoch; se.layer = 0;
         se.err = m->sp_err; se.spin_limit = 1 << ctx->opt.exchange_spin_log2; se.drop_part = ctx->opt.debug_drop_part;
-        pv_prof_scope ps(ctx, "k_lstm_split_enc", st);
-        if (sp_ns == 4) k_lstm_split<32, true, 4><<<split_grid, 256, lds_lstm_split<32>(), st>>>(se);
-        else k_lstm_split<32, true, 2><<<split_grid, 512, lds_lstm_split<32>(), st>>>(se);
-    } else {
-        pv_prof_scope ps(ctx, "k_lstm_layer_enc", st);
-        if (tr == 32) k_lstm_layer<32, true, 32><<<lstm_grid, 512, lds_lstm<32, 32>(), st>>>(e);
-        else k_lstm_layer<32, true, 16><<<lstm_grid, 512, lds_lstm<32, 16>(), st>>>(e);
-    }
-    LstmArgs d = e;
-    d.x_i8 = nullptr; d.x_f32 = enc_out; d.wp = m->dec_wp[f]; d.bias = m->dec_bias; d.out = dec_out;
-    if (split) {
+        {
+            pv_prof_scope ps(ctx, "k_lstm_split_enc", st);
+            if (sp_ns == 4) k_lstm_split<32, true, 4><<<split_grid, 256, lds_lstm_split<32>(), st>>>(se);
+            else k_lstm_split<32, true, 2><<<split_grid, 512, lds_lstm_split<32>(), st>>>(se);
+        }
         LstmSplitArgs sd = se;
         sd.x_i8 = nullptr; sd.x_f32 = enc_out; sd.wp = m->dec_wps[sp_ns == 4 ? 0 : 1]; sd.bias = m->dec_bias; sd.out = dec_out;
         sd.layer = 1;
@@ -1497,24 +1437,29 @@ static int p1_forward_launch(pv_ctx* ctx, const int8_t* d_images, int64_t B, flo
         if (sp_ns == 4) k_lstm_split<512, false, 4><<<split_grid, 256, lds_lstm_split<512>(), st>>>(sd);
         else k_lstm_split<512, false, 2><<<split_grid, 512, lds_lstm_split<512>(), st>>>(sd);
     } else {
+        const int tr = pl.rows, f = tr == 16 ? 1 : 0;
+        const int n_lt = n_tiles * (ROWS / tr);             // whole 32-row tiles are covered in either form
+        const unsigned lstm_grid = (unsigned)(((n_lt + 3) / 4) * 8);
+        LstmArgs e;
+        e.x_i8 = d_images; e.x_f32 = nullptr; e.wp = m->enc_wp[f]; e.bias = m->enc_bias; e.out = enc_out; e.B = B; e.n_tiles = n_lt;
+        {
+            pv_prof_scope ps(ctx, "k_lstm_layer_enc", st);
+            if (tr == 32) k_lstm_layer<32, true, 32><<<lstm_grid, 512, lds_lstm<32, 32>(), st>>>(e);
+            else k_lstm_layer<32, true, 16><<<lstm_grid, 512, lds_lstm<32, 16>(), st>>>(e);
+        }
+        LstmArgs d = e;
+        d.x_i8 = nullptr; d.x_f32 = enc_out; d.wp = m->dec_wp[f]; d.bias = m->dec_bias; d.out = dec_out;
         pv_prof_scope ps(ctx, "k_lstm_layer_dec", st);
         if (tr == 32) k_lstm_layer<512, false, 32><<<lstm_grid, 512, lds_lstm<512, 32>(), st>>>(d);
         else k_lstm_layer<512, false, 16><<<lstm_grid, 512, lds_lstm<512, 16>(), st>>>(d);
     }
     HeadArgs h;
-    // split-K factor: 11 slabs of 3 time steps; 33 single-step slabs only for batches too small to fill the chip
-    int splits = ((int64_t)n_tiles * 11 >= ctx->num_cu) ? 11 : 33;
-    if (ctx->opt.head_splits) splits = ctx->opt.head_splits;
-    h.dec = dec_out; h.w1p = m->w1p; h.part = part; h.B = B; h.n_tiles = n_tiles; h.splits = splits; h.steps_per_split = T_STEPS / splits;
-    const int head_map = ctx->opt.head_map;
-    const int total_wg = n_tiles * splits;
-    h.per_xcd = head_map ? (total_wg + 7) / 8 : 0;
-    const unsigned head_grid = head_map ? (unsigned)(h.per_xcd * 8) : (unsigned)total_wg;
+    h.dec = dec_out; h.w1p = m->w1p; h.part = part; h.B = B; h.n_tiles = n_tiles; h.splits = pl.splits; h.steps_per_split = T_STEPS / pl.splits;
+    const int total_wg = n_tiles * pl.splits;
+    h.per_xcd = pl.head_map ? (total_wg + 7) / 8 : 0;
+    const unsigned head_grid = pl.head_map ? (unsigned)(h.per_xcd * 8) : (unsigned)total_wg;
     { pv_prof_scope ps(ctx, "k_head_splitk", st); k_head_splitk<<<head_grid, 256, LDS_SPLITK, st>>>(h); }
-    TailArgs t;
-    t.part = part; t.b1 = m->b1; t.splits = splits; t.part_rows = B;
-    t.wo = m->wo; t.bo = m->bo; t.probs = d_probs; t.B = B; t.epoch = m->sp_epoch; t.err = m->sp_err;
-    launch_tail(ctx, m, t, n_tiles, st);
+    launch_tail(ctx, pl, part, B, d_probs, B, st);
     PV_HIP(hipGetLastError());
     return PV_OK;
 }
@@ -1534,10 +1479,7 @@ extern "C" int pv_rnn_forward_p1_dev(pv_ctx* ctx, const int8_t* d_images, int64_
     PV_CHECK(B >= 0 && B < (1ll << 24), PV_ERR_INVALID, "batch %lld out of range", (long long)B);
     if (B == 0) return PV_OK;
     PV_HIP(hipSetDevice(ctx->device));
-    // the bf16x3 mode materialises the decoder's input projections (33 x 8 KB per window: 4.4 GB at 16384 windows): larger
-    // batches run as chunks of P1_BF16_MAX_BATCH windows on the same stream
-    // (and so does the split-6 chain of the fp32 mode)
-    const int64_t chunk = (ctx->p1->dtype == PV_DTYPE_BF16_INPUT_GEMM || p1_use_x6(ctx, B)) ? P1_BF16_MAX_BATCH : B;
+    const int64_t chunk = pv_p1_chunk(ctx->p1->dtype, B, ctx->opt);   // the chains on the bf16 MFMA run large calls as chunks
     float *enc, *dec, *part;
     int rc = p1_workspace(ctx, std::min(B, chunk), &enc, &dec, &part);
     if (rc) return rc;
@@ -1554,10 +1496,11 @@ extern "C" int pv_rnn_forward_p1_debug(pv_ctx* ctx, const int8_t* images, int64_
     PV_CHECK(ctx->p1, PV_ERR_STATE, "pv_rnn_load_p1 has not been called on this context");
     PV_CHECK(B >= 0 && B < (1ll << 24), PV_ERR_INVALID, "batch %lld out of range", (long long)B);
     if (B == 0) return PV_OK;
-    if ((ctx->p1->dtype == PV_DTYPE_BF16_INPUT_GEMM || p1_use_x6(ctx, B)) && B > P1_BF16_MAX_BATCH) {
+    const int64_t chunk = pv_p1_chunk(ctx->p1->dtype, B, ctx->opt);
+    if (B > chunk) {
         // host-buffer form in the bf16x3 mode and the split-6 chain: chunks (the taps are per-window, so chunking does not change them)
-        for (int64_t b0 = 0; b0 < B; b0 += P1_BF16_MAX_BATCH) {
-            const int64_t nb = std::min<int64_t>(P1_BF16_MAX_BATCH, B - b0);
+        for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+            const int64_t nb = std::min(chunk, B - b0);
             const size_t tap = (size_t)b0 * T_STEPS * 2 * H;
             int rcc = pv_rnn_forward_p1_debug(ctx, images + b0 * PV_WINDOW_BYTES, nb, probs + b0 * 3, enc_out ? enc_out + tap : nullptr,
                                               dec_out ? dec_out + tap : nullptr);
@@ -1629,7 +1572,7 @@ static const unsigned* gemm_iota() {
 }
 
 static void gemm_launch(pv_ctx* ctx, GemmArgs& g, hipStream_t st, int terms = 3) {
-    g.tiles_m = (int)((g.M + 255) / 256); g.tiles_n = g.N / 256; g.items = g.tiles_m * g.tiles_n * g.splits;
+    g.tiles_m = (int)((g.M + PV_GEMM_TILE - 1) / PV_GEMM_TILE); g.tiles_n = g.N / PV_GEMM_TILE; g.items = g.tiles_m * g.tiles_n * g.splits;
     const unsigned grid = (unsigned)(std::min((g.items + 7) / 8 * 8, (ctx->num_cu + 7) / 8 * 8));
     if (terms == 6) k_gemm_bf16x6<<<grid, 512, LDS_GEMM, st>>>(g);
     else k_gemm_bf16x3<<<grid, 512, LDS_GEMM, st>>>(g);

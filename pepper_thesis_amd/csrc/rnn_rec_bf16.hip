@@ -844,7 +844,7 @@ static inline float bf_bits2f(uint16_t h) {
 // weight traffic per row), 3-term split products through the fragment ring of the recurrent layers, the activations as ONE
 // split8 tile in LDS that is updated in place (every wave holds its 64 x 64 outputs in accumulators until all waves are done
 // reading the tile). Wave w owns output columns [64 w, 64 w + 64) as two 32-column tiles ("gates" of ring_bf16).
-constexpr int TL_N = 512, TL_ROWS = 64, TL_HS = TL_N * 4 + 16, TL_KS = TL_N / 16, TL_SLOTS = TL_KS * 2, TL_D = 8;
+constexpr int TL_N = PV_HEAD_N, TL_ROWS = PV_TAIL_BF16_ROWS, TL_HS = TL_N * 4 + 16, TL_KS = TL_N / 16, TL_SLOTS = TL_KS * 2, TL_D = 8;
 struct TailBfArgs {
     const float* part; int splits; int64_t part_rows;
     const float* b1;
@@ -1311,29 +1311,17 @@ int pv_pack_p2_dense(const float* dense_w, unsigned char** d_frag, std::vector<v
     return PV_OK;
 }
 
-int pv_p2_bf16_forward(pv_ctx* ctx, const pv_p2_bf16_weights& w, const uint8_t* d_images, int64_t B, uint8_t* d_labels, float* d_acc,
-                       hipStream_t st, int seq, int nwin, const float* d_hidden_in, float* d_hidden_out, float* d_logits) {
-    // 64-row tiles (one weight fetch feeds twice the rows) once 32-row (tile, direction) workgroups would need more than two
-    // rounds of the chip; below that 32-row tiles keep more CUs busy
-    const int mt = ((B + 31) / 32) * 2 > 2 * (int64_t)ctx->num_cu ? 2 : 1;
-    // 16-row tiles (k_gru16_bf16: half the MFMA and cell-update time per step) while every (tile, direction) workgroup has a CU
-    // of its own (up to 2048 chunks on 256 CUs: 13.2 ms against 17.9 at 2048). Beyond that, two 16-row tiles per workgroup
-    // (k_gru16_bf16<.., 2>, one after the other inside the step) measured no better than the 32-row form - 6.0 / 6.3 ms against
-    // 6.0 / 6.8 per 19 windows at 2121 chunks - and cannot fold dense1 in: not used.
-    const int tr16 = ((B + 15) / 16) * 2 <= (int64_t)ctx->num_cu ? 1 : 0;
-    const int rows = tr16 ? 16 : 32 * mt;
-    const int64_t Bp = (B + rows - 1) / rows * rows, M = (int64_t)P2_WIN * Bp;
+int pv_p2_bf16_forward(pv_ctx* ctx, const pv_p2_plan& pl, const pv_p2_bf16_weights& w, const uint8_t* d_images, int64_t B, uint8_t* d_labels,
+                       float* d_acc, hipStream_t st, int seq, int nwin, const float* d_hidden_in, float* d_hidden_out, float* d_logits) {
+    const int tr16 = pl.kind == PV_P2_GRU16 ? 1 : 0, mt = pl.mt, fold_dense = pl.fold_dense;
+    const int64_t Bp = pl.Bp, M = (int64_t)P2_WIN * Bp;
     float *state = nullptr, *G = nullptr;
     unsigned char *enc_s = nullptr, *dec = nullptr;
     int rc;
     if ((rc = pv_get(ctx, "p2b.state", (size_t)Bp * 2 * P2_H, &state))) return rc;
     if ((rc = pv_get(ctx, "p2b.enc_s", (size_t)M * 2 * P2_H * 4, &enc_s))) return rc;
     if ((rc = pv_get(ctx, "p2b.G", (size_t)M * 6 * P2_H, &G))) return rc;
-    // dense1: in the 16-row form always, in the 32-row forms from 2048 chunks on, as one more MFMA tile of the decoder's steps (partial logits of 2 directions x 4 waves, 105 MB
-    // per window at 4096 chunks, summed by k_p2_combine) instead of the decoder's split8 output (420 MB) and k_p2_dense's pass
-    // over it: 24.9 -> 23.9 ms at 4096 chunks. It lengthens every decoder step by ~5 %, which is all a small batch sees (64
-    // chunks: 12.3 -> 12.6 ms), so those keep the separate pass.
-    const bool fold_dense = tr16 ? true : B >= 2048;   // (the 16-row form gains at every size: 64 chunks 6.22 -> 6.14 ms, 2048 chunks 12.1 -> 11.0)
+    // dense1 folded into the decoder: partial logits of 2 directions x 4 waves; else the decoder's split8 output for k_p2_dense
     float* dpart = nullptr;
     if (fold_dense) {
         if ((rc = pv_get(ctx, "p2b.dpart", (size_t)P2_WIN * (Bp / (tr16 ? 16 : 32)) * 8 * (tr16 ? 128 : 256), &dpart))) return rc;
