@@ -5,6 +5,11 @@ It compiles the reference's ssw.c and a small driver that includes its ssw_cpp.c
 is written into the repository but the .npz), runs the read loop of ReadAligner::align_reads_to_reference
 (simple_aligner.cpp:66-107) with Aligner(4, 6, 8, 2), the default Filter and maskLen 0 on the cases of
 tests/realign_cases.py, and stores INPUTS and EXPECTED OUTPUTS as arrays (data only).
+
+The cases at the realigner's limits (realign_cases.FIXTURE_CASES, listed under "limit_names") store OUTPUTS only, plus a
+SHA-1 of their inputs: tests/test_polish_realign_cpu.py rebuilds the inputs from the seeds and checks the digest. Where
+oracle/_ref/libref_polish.so is built (oracle/Makefile), the reference's whole ReadAligner is run on them as well and must
+give the same positions and CIGARs.
 """
 import os
 import subprocess
@@ -77,8 +82,37 @@ def all_cases():
     return out
 
 
+def limit_cases():
+    """one single-read case per realign_cases.FIXTURE_CASES entry, named as realign_cases.fixture_case names it"""
+    out = []
+    for group, region, read in realign_cases.FIXTURE_CASES:
+        name, start, win, rd = realign_cases.fixture_case(group, region, read)
+        out.append((name, start, start + len(win) - 20, win, [rd]))
+    return out
+
+
+def check_against_read_aligner(cases, blob):
+    """the same cases through the reference's ReadAligner (oracle/_ref/libref_polish.so), where it is built"""
+    from oracle import oracle
+    from pepper_thesis_amd import realign
+    from pepper_thesis_amd.batch import pack_regions
+    if not oracle.have_reference_polish():
+        print("oracle/_ref/libref_polish.so not built: ReadAligner cross-check skipped")
+        return
+    for name, s, e, w, reads in cases:
+        b = pack_regions([realign_cases.as_region(s, e, w, reads)])
+        woff, win = realign.pack_windows([w])
+        state, pos, _, coff, cig = oracle.reference_polish_realign(b, woff, win)
+        assert state.tolist() == [oracle.REF_KEPT] * len(reads), name
+        assert pos.tolist() == blob[name + "/record"][:, 6].tolist(), name
+        assert np.array_equal(coff, blob[name + "/cigar_off"]) and np.array_equal(cig, blob[name + "/cigar"]), name
+        print("%-34s ReadAligner gives the same position and cigar" % name)
+
+
 def main():
-    cases = all_cases()
+    limits = limit_cases()
+    cases = all_cases() + limits
+    limit_names = set(c[0] for c in limits)
     with tempfile.TemporaryDirectory() as tmp:
         drv = os.path.join(tmp, "driver.cpp")
         with open(drv, "w") as fh:
@@ -94,7 +128,6 @@ def main():
         res = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout.split("\n")
     blob, names, k = {}, [], 0
     for name, s, e, w, reads in cases:
-        names.append(name)
         recs, cig, cig_off = [], [], [0]
         for _ in reads:
             v = [int(t) for t in res[k].split()]
@@ -102,21 +135,27 @@ def main():
             recs.append(v[:7])
             cig.extend(v[8:8 + v[7]])
             cig_off.append(len(cig))
-        blob[name + "/start"] = np.int64(s)
-        blob[name + "/end"] = np.int64(e)
-        blob[name + "/window"] = np.frombuffer(w, np.uint8)
-        blob[name + "/read_pos"] = np.asarray([r.pos for r in reads], np.int64)
-        blob[name + "/base_off"] = np.cumsum([0] + [len(r.bases) for r in reads]).astype(np.int64)
-        blob[name + "/bases"] = np.frombuffer(b"".join(r.bases for r in reads), np.uint8)
-        blob[name + "/in_cigar_off"] = np.cumsum([0] + [len(r.cigar) for r in reads]).astype(np.int64)
-        blob[name + "/in_cigar"] = np.concatenate([r.cigar for r in reads]).astype(np.uint32)
+        if name in limit_names:
+            blob[name + "/input_sha1"] = realign_cases.input_digest(s, w, reads)
+        else:
+            names.append(name)
+            blob[name + "/start"] = np.int64(s)
+            blob[name + "/end"] = np.int64(e)
+            blob[name + "/window"] = np.frombuffer(w, np.uint8)
+            blob[name + "/read_pos"] = np.asarray([r.pos for r in reads], np.int64)
+            blob[name + "/base_off"] = np.cumsum([0] + [len(r.bases) for r in reads]).astype(np.int64)
+            blob[name + "/bases"] = np.frombuffer(b"".join(r.bases for r in reads), np.uint8)
+            blob[name + "/in_cigar_off"] = np.cumsum([0] + [len(r.cigar) for r in reads]).astype(np.int64)
+            blob[name + "/in_cigar"] = np.concatenate([r.cigar for r in reads]).astype(np.uint32)
         blob[name + "/record"] = np.asarray(recs, np.int64)   # state score ref_begin ref_end query_begin query_end new_pos
         blob[name + "/cigar_off"] = np.asarray(cig_off, np.int64)
         blob[name + "/cigar"] = np.asarray(cig, np.uint32)
         st = np.asarray(recs)[:, 0]
-        print("%-18s reads=%3d realigned=%3d dropped=%d max_score=%d" % (name, len(reads), (st == 1).sum(), (st == 2).sum(),
+        print("%-34s reads=%3d realigned=%3d dropped=%d max_score=%d" % (name, len(reads), (st == 1).sum(), (st == 2).sum(),
                                                                         np.asarray(recs)[:, 1].max()))
     blob["names"] = np.asarray(names, dtype="S")
+    blob["limit_names"] = np.asarray([c[0] for c in limits], dtype="S")
+    check_against_read_aligner(limits, blob)
     np.savez_compressed(os.path.join(ROOT, "tests", "golden", "realign_golden.npz"), **blob)
 
 

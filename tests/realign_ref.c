@@ -5,7 +5,8 @@
  * rl_align(window, wlen, query, qlen, res, cigar, cap) aligns one query against one window (already cut at the read's pos):
  *   res = {score, ref_begin, ref_end, query_begin, query_end}; returns the number of output CIGAR words (BAM packing, with
  *   '='/'X' as op 7/8 so that the caller sees the runs) or 0 when score <= 1 (nothing past res[0] is filled), -1 when cap is
- *   too small, -2 on a traceback that leaves the band (never seen; reported, not guessed). */
+ *   too small, -2 on a traceback that leaves the band (never seen; reported, not guessed).
+ * rl_last_band() is the band width at which that call's banded pass reached the score (0 when none ran). */
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -23,6 +24,9 @@ static int code(uint8_t b) {
 }
 
 static int score(int a, int b) { return (a == b && a < 4) ? MATCH : -MISMATCH; }
+
+static int last_band = 0;   /* banded()'s final band width of the latest rl_align (0: no banded pass ran) */
+int rl_last_band(void) { return last_band; }
 
 /* local affine DP over ref columns (outer) and query rows (inner).
  * forward: best = max, first column holding it, smallest row in that column.
@@ -105,6 +109,7 @@ static int banded(const int* ref, const int* read, int refLen, int readLen, int 
         if (mx >= sc) break;
         w *= 2;
     }
+    last_band = w;
     /* traceback from the last cell; ops are collected in reverse */
     int n = 0, i = readLen - 1, j = refLen - 1, e = 0, state = 2;
     char op = 'M', prev = 'M';
@@ -138,6 +143,7 @@ static int banded(const int* ref, const int* read, int refLen, int readLen, int 
 
 int rl_align(const uint8_t* win, int wlen, const uint8_t* query, int qlen, int32_t* res, uint32_t* cigar, int cap) {
     memset(res, 0, 5 * sizeof(int32_t));
+    last_band = 0;
     if (wlen <= 0 || qlen <= 0) return 0;
     int* r = (int*)malloc(sizeof(int) * (size_t)wlen);
     int* q = (int*)malloc(sizeof(int) * (size_t)qlen);

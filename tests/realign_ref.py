@@ -34,6 +34,8 @@ def _load():
         lib = C.CDLL(so)
         lib.rl_align.restype = C.c_int
         lib.rl_align.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int]
+        lib.rl_last_band.restype = C.c_int
+        lib.rl_last_band.argtypes = []
         _lib = lib
     return _lib
 
@@ -49,6 +51,11 @@ def align(window: bytes, query: bytes):
     if n < 0:
         raise RuntimeError("realign_ref: rl_align returned %d" % n)
     return tuple(int(v) for v in res) + (np.frombuffer(cig, dtype=np.uint32, count=n).copy(),)
+
+
+def last_band() -> int:
+    """banded_sw's final band width in the latest align() (0: score <= 1, no banded pass)"""
+    return int(_load().rl_last_band())
 
 
 def to_read_cigar(cig: np.ndarray) -> np.ndarray:
@@ -69,6 +76,7 @@ class Record:
     query_end: int = 0
     new_pos: int = 0
     cigar: np.ndarray = None   # read cigar (uint32, BAM packing) after realignment; the input's when unchanged
+    band: int = 0              # banded_sw's final band width (realigned reads)
 
 
 def window(contig_seq: bytes, start: int, end: int) -> bytes:
@@ -90,7 +98,7 @@ def realign_reads(start: int, win: bytes, reads: Sequence) -> List[Record]:
             continue
         sc, rb, re_, qb, qe, cig = align(win[off:], rd.bases)
         if sc > 1:
-            out.append(Record(REALIGNED, sc, rb, re_, qb, qe, pos + rb, to_read_cigar(cig)))
+            out.append(Record(REALIGNED, sc, rb, re_, qb, qe, pos + rb, to_read_cigar(cig), last_band()))
         else:
             out.append(Record(UNCHANGED, sc, new_pos=pos, cigar=np.asarray(rd.cigar, np.uint32)))
     return out

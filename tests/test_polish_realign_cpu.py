@@ -4,6 +4,7 @@ import os
 import numpy as np
 import pytest
 
+import realign_cases
 import realign_ref
 from pepper_thesis_amd.batch import Read
 
@@ -50,6 +51,45 @@ def test_checker_reproduces_the_reference(golden):
             elif exp[0] == realign_ref.UNCHANGED:
                 assert np.array_equal(r.cigar, reads[k].cigar) and r.new_pos == reads[k].pos, tag
     assert n > 200
+
+
+def limit_golden_cases(g):
+    """the fixture's cases at the realigner's limits, their inputs rebuilt from the seeds of realign_cases (the fixture holds
+    a digest of them and the reference's outputs) -> [(name, start, window, read, record [7], cigar)]"""
+    out = []
+    for (group, region, read), name in zip(realign_cases.FIXTURE_CASES, (n.decode() for n in g["limit_names"])):
+        fname, start, win, rd = realign_cases.fixture_case(group, region, read)
+        assert fname == name
+        assert np.array_equal(realign_cases.input_digest(start, win, [rd]), g[name + "/input_sha1"]), \
+            "%s: the seeded inputs are not the ones the fixture was made from" % name
+        assert g[name + "/cigar_off"].tolist() == [0, len(g[name + "/cigar"])]
+        out.append((name, start, win, rd, g[name + "/record"][0].tolist(), g[name + "/cigar"]))
+    return out
+
+
+def test_checker_reproduces_the_reference_at_the_limits(golden):
+    """the reference's striped Smith-Waterman on the largest legal score (alone, inside a 16384-base query, on a
+    homopolymer), a period-2 repeat, a band over the whole window and a dense cigar: the checker gives every field"""
+    cases = limit_golden_cases(golden)
+    assert len(cases) == 6
+    by_name = {}
+    for name, start, win, rd, exp, ecig in cases:
+        r, = realign_ref.realign_reads(start, win, [rd])
+        assert exp[0] == realign_ref.REALIGNED
+        assert (r.state, r.score, r.ref_begin, r.ref_end, r.query_begin, r.query_end, r.new_pos) == tuple(exp), name
+        assert np.array_equal(r.cigar, ecig), name
+        by_name[name.split("/", 1)[1]] = (r, rd)
+    # the reference's own figures are the ones these cases were chosen for
+    for k in ("saturation/full/0", "saturation/full/1", "saturation/homopolymer/0"):
+        assert by_name[k][0].score == 8188, k
+    r, rd = by_name["saturation/full/1"]
+    assert (r.ref_begin, r.ref_end, r.query_begin, r.query_end) == (0, 2046, 7000, 9046) and len(rd.bases) == 16384
+    r = by_name["saturation/full/0"][0]
+    assert (r.ref_begin, r.ref_end, r.query_begin, r.query_end) == (0, 2046, 0, 2046)
+    assert by_name["saturation/period2/0"][0].score == 2400
+    r = by_name["bands/bands/4"][0]
+    assert 2 * r.band + 1 >= r.ref_end - r.ref_begin + 1 == 2047
+    assert len(by_name["dense/dense/0"][0].cigar) > 1000
 
 
 def test_window_drop_keep_and_op_mapping():
