@@ -270,19 +270,24 @@ class FilledBatch:
 
 
 def fill_batch(bam: BamHandler, fasta: FastaHandler, intervals, min_mapq: int = 5, include_supplementary: bool = False,
-               downsample_rate: float = 1.0, safe_bases: int = 100) -> FilledBatch:
+               downsample_rate: float = 1.0, safe_bases: int = 100, max_reads: int = None) -> FilledBatch:
     """AlignmentSummarizer.create_summary's fetch (AlignmentSummarizer.py:180-218) for a list of (contig, start, end)
-    intervals in ONE native call that releases the GIL (reader threads run it beside the GPU launches)."""
+    intervals in ONE native call that releases the GIL (reader threads run it beside the GPU launches).
+    max_reads: the reservoir's read limit per interval (None: MAX_READS_IN_REGION, read when the call is made)."""
     n = len(intervals)
     names = (C.c_char_p * max(n, 1))(*[iv[0].encode() for iv in intervals])
     starts = (C.c_int64 * max(n, 1))(*[int(iv[1]) for iv in intervals])
     ends = (C.c_int64 * max(n, 1))(*[int(iv[2]) for iv in intervals])
     out = C.POINTER(pvio_batch)()
     rc = load().pvio_fill_batch(bam.h, fasta.h, n, names, starts, ends, int(safe_bases), int(bool(include_supplementary)),
-                                int(min_mapq), float(downsample_rate), MAX_READS_IN_REGION, RANDOM_SEED, C.byref(out))
+                                int(min_mapq), float(downsample_rate), _read_limit(max_reads), RANDOM_SEED, C.byref(out))
     if rc:
         raise IOError("fill_batch: " + _err())
     return FilledBatch(out, intervals)
+
+
+def _read_limit(max_reads) -> int:
+    return int(MAX_READS_IN_REGION if max_reads is None else max_reads)
 
 
 def _interval_args(intervals):
@@ -364,10 +369,10 @@ def fetch_reference(fasta: FastaHandler, contig: str, start: int, stop: int) -> 
 
 def fill_batch_blocks(bam: BamHandler, fasta: FastaHandler, intervals, coffset, next_coffset, isize, out_off, data,
                       min_mapq: int = 5, include_supplementary: bool = False, downsample_rate: float = 1.0,
-                      safe_bases: int = 100) -> FilledBatch:
+                      safe_bases: int = 100, max_reads: int = None) -> FilledBatch:
     """fill_batch with a table of BGZF blocks inflated elsewhere (pvio_fill_batch_blocks): block i (compressed offset
     coffset[i], ascending; the next block at next_coffset[i]) is the isize[i] bytes at data[out_off[i]:]. Blocks missing
-    from the table are read and inflated on the host (FilledBatch.blocks_host). Same arrays as fill_batch."""
+    from the table are read and inflated on the host (FilledBatch.blocks_host). Same arrays as fill_batch; max_reads as there."""
     n, names, starts, ends = _interval_args(intervals)
     co = np.ascontiguousarray(coffset, np.int64)
     nx = np.ascontiguousarray(next_coffset, np.int64)
@@ -382,7 +387,7 @@ def fill_batch_blocks(bam: BamHandler, fasta: FastaHandler, intervals, coffset, 
         d, dptr = None, int(data)
     out = C.POINTER(pvio_batch)()
     rc = load().pvio_fill_batch_blocks(bam.h, fasta.h, n, names, starts, ends, int(safe_bases), int(bool(include_supplementary)),
-                                       int(min_mapq), float(downsample_rate), MAX_READS_IN_REGION, RANDOM_SEED, len(co),
+                                       int(min_mapq), float(downsample_rate), _read_limit(max_reads), RANDOM_SEED, len(co),
                                        co.ctypes.data, nx.ctypes.data, isz.ctypes.data, oo.ctypes.data, dptr or None,
                                        C.byref(out))
     if rc:

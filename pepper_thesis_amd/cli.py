@@ -163,7 +163,15 @@ def polish_parser(ap=None):
     ap.add_argument("--realign", action="store_true", default=False,
                     help="realign every read to the draft (Smith-Waterman on the device) before the images are built; the "
                          "reference always does this (AlignmentSummarizer realignment_flag=True). Off by default for now")
+    polish_gpu_decode_flag(ap)
     return ap
+
+
+def polish_gpu_decode_flag(ap):
+    """--gpu_decode of the polisher's readers (polish, pepper polish, pepper make_images); it uses the GPU inflate internally"""
+    ap.add_argument("--gpu_decode", action="store_true", default=False,
+                    help="inflate, decode and clip the BAM records on the GPU: the reader threads only plan blocks and fetch "
+                         "draft bytes, the reads never leave the device (opt-in; same output)")
 
 
 def preset_of(args) -> str:

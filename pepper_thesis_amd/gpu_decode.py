@@ -14,6 +14,12 @@ the *_dev builders take as it is (it offers what device.DeviceBatch offers). No 
 A group whose walk needs bytes outside the plan (reads longer than the plan's 32 kb look-ahead) is read through the
 gpu_inflate route instead - its inflated bytes are copied down and bamio.fill_batch_blocks parses them - and counted in the
 timer `gpu_decode_groups_host`. A corrupt record or block fails with the host reader's own message.
+
+The polisher (`polish --gpu_decode`) uses the same kernels with its own settings (no safe bases, MAPQ 0, 1500 reads, draft
+bytes padded with N past the contig end, realign windows) and its own shape of work: about a thousand 1 kb regions per chain
+launch. region_groups cuts the work list into reader groups (short runs of regions that share BGZF blocks), plan_launches
+packs groups into scans whose workspace stays under a budget, compose_launches cuts the scanned regions into the launches the
+host path would make, and GpuDecoder.scan_groups / realize run them (decoded_launches, polish.polish_pieces).
 """
 import queue
 import threading
@@ -27,24 +33,156 @@ from . import _ffi, bamio
 from .gpu_inflate import MARGIN_BLOCKS, _align8
 
 REC_MIN_BYTES = 36   # block_size field + the 32 fixed bytes: no record is shorter, so bytes / 36 + 1 slots always suffice
+SLOT_BYTES = 60      # decode workspace per record slot (include/pepper_hip.h)
+DEFAULT_WS_BUDGET = 4 << 30   # bytes of decode workspace one scan may allocate (DESIGN.md 4.6 has the measured sizes)
+GROUP_REGIONS = 16   # regions of one polisher reader group at most: the 1 kb regions of one 16 kb BAI window
+GROUP_SHIFT = 14     # ... regions whose starts share start >> 14 fall into the same smallest BAI bin: the same chunks and blocks
+
+
+def safe_slots(out_bytes: int) -> int:
+    """record slots that always suffice for one interval of a group with out_bytes inflated bytes"""
+    return int(out_bytes) // REC_MIN_BYTES + 1
+
+
+def interval_slots(out_bytes: int, min_record_bytes: int = REC_MIN_BYTES) -> int:
+    """slots for one interval when no record is taken to be shorter than min_record_bytes (never more than safe_slots)"""
+    return min(safe_slots(out_bytes), int(out_bytes) // max(int(min_record_bytes), REC_MIN_BYTES) + 1)
+
+
+def decode_ws_bytes(n_intervals: int, slots: int) -> int:
+    """bytes GpuDecoder allocates as the workspace of one scan: pv_bam_decode_ws_bytes (12 per-slot arrays, 60 bytes per slot,
+    each rounded up to 8 bytes, and 44 bytes per interval) rounded up to whole int64 words plus one"""
+    up8 = lambda x: (int(x) + 7) & ~7
+    N, S = int(n_intervals), int(slots)
+    lib = 3 * up8(8 * S) + 9 * up8(4 * S) + 24 * N + 8 * (N + 1) + 3 * up8(4 * N) + 8
+    return 8 * max(lib // 8 + 1, 1)
+
+
+def region_groups(work, max_regions: int = GROUP_REGIONS):
+    """the polisher's reader groups: `work` (objects with contig, start, end, in run order) -> lists of consecutive entries
+    of one contig, starts ascending inside one 16 kb BAI window, max_regions at most. Such regions ask the index for the
+    same bins, so a group's blocks are read and inflated once. Every entry lands in exactly one group, in order."""
+    groups, cur = [], []
+    for w in work:
+        if cur and (len(cur) >= max_regions or w.contig != cur[0].contig or w.start < cur[-1].start
+                    or (w.start >> GROUP_SHIFT) != (cur[0].start >> GROUP_SHIFT)):
+            groups.append(cur)
+            cur = []
+        cur.append(w)
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def plan_launches(sizes, budget=None, min_record_bytes=REC_MIN_BYTES):
+    """Which groups share a scan. sizes: [(intervals, inflated bytes)] of the planned groups in order; budget: bytes of decode
+    workspace one scan may allocate (None: no limit). -> [("dev", [group indices], [slots per interval of each])
+    | ("host", [group index], None)] covering every group once, in order. A scan is cut before the group that would take
+    its workspace past the budget; a group whose safe-rule workspace alone is over the budget goes the host route (so a
+    retry with the safe rule always fits). min_record_bytes: the slot rule, one value or one per group."""
+    out, cur, per, n, slots = [], [], [], 0, 0
+
+    def cut():
+        nonlocal cur, per, n, slots
+        if cur:
+            out.append(("dev", cur, per))
+        cur, per, n, slots = [], [], 0, 0
+
+    for gi, (n_iv, out_bytes) in enumerate(sizes):
+        n_iv = int(n_iv)
+        if budget is not None and decode_ws_bytes(n_iv, n_iv * safe_slots(out_bytes)) > budget:
+            cut()
+            out.append(("host", [gi], None))
+            continue
+        p = interval_slots(out_bytes, min_record_bytes[gi] if isinstance(min_record_bytes, (list, tuple)) else min_record_bytes)
+        if budget is not None and cur and decode_ws_bytes(n + n_iv, slots + n_iv * p) > budget:
+            cut()
+        cur.append(gi)
+        per.append(p)
+        n += n_iv
+        slots += n_iv * p
+    cut()
+    return out
+
+
+def compose_launches(scans, per_launch: int, on_part=None):
+    """The chain launches of the polisher from scanned groups. scans: iterable, in work order, of objects with kind ("dev" |
+    "host" | an exception, raised here), reads (reads kept per interval; 0 drops the region), key (groups with the same key
+    were scanned together: their regions can share one fill) and n (intervals). -> lists of parts [kind, key, [(scan, k)]]:
+    per_launch regions with reads each (the last may be short), in order - what the host path's flush makes of the same
+    regions. Consecutive regions of one kind and key share a part.
+    A None among the scans says that nothing with the keys seen so far follows: the open part is complete. on_part(part) is
+    called once for every part as soon as it is complete - at such a None, when another part begins, or when its launch is
+    cut - and what it returns takes the part's place in the launch (the decoder fills a scan's regions there and lets the
+    scan's buffers go before the next scan runs)."""
+    cur, n, is_open = [], 0, False
+
+    def close():
+        nonlocal is_open
+        if is_open:
+            is_open = False
+            if on_part is not None:
+                cur[-1] = on_part(cur[-1])
+
+    for gs in scans:
+        if gs is None:
+            close()
+            continue
+        if isinstance(gs.kind, BaseException):
+            raise gs.kind
+        for k in range(gs.n):
+            if int(gs.reads[k]) <= 0:
+                continue
+            if is_open and cur[-1][0] == gs.kind and cur[-1][1] is gs.key:
+                cur[-1][2].append((gs, k))
+            else:
+                close()
+                cur.append([gs.kind, gs.key, [(gs, k)]])
+                is_open = True
+            n += 1
+            if n == per_launch:
+                close()
+                yield cur
+                cur, n = [], 0
+    close()
+    if cur:
+        yield cur
 
 
 class PlannedGroup:
     """what a reader thread prepares for one group of intervals (host work only)"""
 
-    def __init__(self, bam, fasta, ivs, safe_bases):
+    def __init__(self, bam, fasta, ivs, safe_bases, pad_ref=False, windows=False, works=None):
+        """pad_ref: the polisher's reference bytes - draft [start, end] padded with N to end - start + 1 past the contig end
+        (polish_summary.region_from_files); windows: also its realign window per interval, draft [start, min(end +
+        realign.SAFE_BASES, contig length)); works: the caller's own object per interval (polish.Work)."""
+        from .realign import SAFE_BASES
         t0, c0 = time.perf_counter(), time.thread_time()
         self.ivs = list(ivs)
+        self.works = works
         self.plan = bamio.plan_blocks(bam, ivs, safe_bases, MARGIN_BLOCKS)
         self.ivp = bamio.plan_intervals(bam, ivs, safe_bases)
         self.refs, self.ref_err = [], []
+        self.windows = [] if windows else None
         for k, iv in enumerate(self.ivs):
+            if pad_ref and int(iv[1]) < 0:
+                raise ValueError("gpu_decode: region %s:%d-%d starts before the contig" % tuple(iv))
             try:   # (the reader fetches only for intervals with reads: an error here is raised only if this one has some)
-                self.refs.append(bamio.fetch_reference(fasta, iv[0], int(self.ivp.rs[k]), int(self.ivp.re[k]) + 1))
+                r = bamio.fetch_reference(fasta, iv[0], int(self.ivp.rs[k]), int(self.ivp.re[k]) + 1)
+                if pad_ref:
+                    want = int(iv[2]) - int(iv[1]) + 1
+                    if r.size < want:   # past the contig end: columns without reads; the polisher never reads the bytes
+                        r = np.concatenate([r, np.full(want - r.size, ord("N"), np.uint8)])
+                if windows:
+                    stop = min(int(iv[2]) + SAFE_BASES, fasta.get_chromosome_sequence_length(iv[0]))
+                    self.windows.append(bamio.fetch_reference(fasta, iv[0], int(iv[1]), stop).tobytes())
+                self.refs.append(r)
                 self.ref_err.append(None)
             except IOError as e:
                 self.refs.append(np.zeros(0, np.uint8))
                 self.ref_err.append(e)
+                if windows and len(self.windows) <= k:
+                    self.windows.append(b"")
         self.t_plan, self.cpu_plan = time.perf_counter() - t0, time.thread_time() - c0   # wall and CPU seconds of this thread
 
 
@@ -57,6 +195,7 @@ class DecodedBatch:
         self.t, self.n_regions, self.intervals = t, int(n_regions), list(intervals)
         self.interval_index, self.reads_seen = interval_index, reads_seen
         self.n_reads, self.n_bases, self.n_cigar = int(n_reads), 0, 0   # (bases / words: set when the totals are back)
+        self.qmax = 0   # the longest read (set with the totals when the decoder was asked for it: the realigner's bound)
         self.n_ref_bytes, self.max_region_len = int(n_ref_bytes), int(max_region_len)
         self.read_hp = t["read_hp"]
         self.event = event
@@ -103,13 +242,44 @@ def _stage(sizes):
     return offs, max(o, 8)
 
 
+class _Scan:
+    """what one pv_bam_scan_dev call left: the groups it covered, where each begins (first block, first data byte, first
+    interval), the per-interval counts and block status on the host, and the device buffers the fills read"""
+
+    def __init__(self, groups, per):
+        self.groups, self.per = list(groups), list(per)
+
+
+class GroupScan:
+    """one planned group after its scan, as compose_launches takes it: kind "dev" | "host" | an exception; reads kept per
+    interval; key: the _Scan a "dev" group's fills read (regions of one key can share a fill), for a "host" group the group
+    itself; regions: a "host" group's polish_summary regions (None where there are no reads)"""
+
+    def __init__(self, group, kind, reads, key, gi=0, regions=None):
+        self.group, self.kind, self.reads, self.key, self.gi, self.regions = group, kind, reads, key, gi, regions
+        self.n = len(group.ivs)
+
+
 class GpuDecoder:
-    def __init__(self, ctx, bam_path, fasta_path, min_mapq, include_supplementary, downsample_rate, safe_bases, T: dict):
+    def __init__(self, ctx, bam_path, fasta_path, min_mapq, include_supplementary, downsample_rate, safe_bases, T: dict,
+                 max_reads=None, ws_budget=None, min_record_bytes=REC_MIN_BYTES, adaptive_slots=False, realign=False):
+        """max_reads: the reservoir's read limit per interval (None: bamio.MAX_READS_IN_REGION, read when it is used).
+        The rest is used by scan_groups (the polisher's form) only - ws_budget: bytes of decode workspace one scan may
+        allocate (None: DEFAULT_WS_BUDGET); min_record_bytes: slots per interval = bytes of the group's blocks /
+        min_record_bytes + 1 (36: the safe rule; more gives fewer slots, and a group that runs out is scanned again, once,
+        with the safe rule); adaptive_slots: after the first scan, size the slots from the records per inflated byte the
+        scans have seen so far (four times the densest interval); realign: host-route regions fetch their realign window."""
         import torch
         self.ctx, self.T = ctx, T
         self.bam_path, self.fasta_path = bam_path, fasta_path
         self.min_mapq, self.include_supplementary = int(min_mapq), bool(include_supplementary)
         self.downsample_rate, self.safe_bases = float(downsample_rate), int(safe_bases)
+        self.max_reads = max_reads
+        self.ws_budget = DEFAULT_WS_BUDGET if ws_budget is None else int(ws_budget)
+        self.min_record_bytes, self.adaptive_slots, self.realign = int(min_record_bytes), bool(adaptive_slots), bool(realign)
+        self.live = [0, 0]    # bytes of the live scans: workspaces, all device buffers (_account)
+        self.density = 0.0    # records walked per inflated byte of the group: the largest any interval has shown
+        self.want_qmax = self.realign   # the fills also reduce the longest read of the batch (the realigner's bound)
         self.dev = "cuda:%d" % ctx.device_id
         self.stream = torch.cuda.Stream(device=self.dev)
         for k in ("gpu_inflate_kernel_ms", "gpu_inflate_h2d_ms", "gpu_decode_scan_ms",
@@ -119,18 +289,55 @@ class GpuDecoder:
                   "gpu_decode_groups_host", "gpu_decode_h2d_bytes", "gpu_decode_d2h_bytes", "gpu_decode_records"):
             T.setdefault(k, 0)
         self.handles = None   # the service thread's own reader pair, opened when a group first needs the host route
+        self.closing = False
         self.q: "queue.Queue" = queue.Queue()
         self.thread = threading.Thread(target=self._run, daemon=True)
         self.thread.start()
+
+    def _read_limit(self):
+        return int(bamio.MAX_READS_IN_REGION if self.max_reads is None else self.max_reads)
 
     def submit(self, groups) -> Future:
         """-> a Future of the list of items of these groups, in order: ("dev", DecodedBatch), ("host", bamio.FilledBatch)
         or ("error", exception)"""
         f: Future = Future()
-        self.q.put((groups, f))
+        self.q.put((lambda: self._launch(groups), f))
         return f
 
+    def iterate(self, gen, depth=2):
+        """run a generator on the service thread, `depth` items ahead of the consumer at most -> an iterator of its items
+        (an exception of the generator is raised where the consumer takes the next item)"""
+        out: "queue.Queue" = queue.Queue(maxsize=depth)
+
+        def put(x):
+            while not self.closing:
+                try:
+                    out.put(x, timeout=0.1)
+                    return True
+                except queue.Full:
+                    pass
+            return False
+
+        def job():
+            try:
+                for x in gen:
+                    if not put(("item", x)):
+                        return
+                put(("end", None))
+            except BaseException as e:
+                put(("error", e))
+
+        self.q.put((job, Future()))
+        while True:
+            kind, x = out.get()
+            if kind == "end":
+                return
+            if kind == "error":
+                raise x
+            yield x
+
     def close(self):
+        self.closing = True
         self.q.put(None)
         self.thread.join()
 
@@ -139,19 +346,24 @@ class GpuDecoder:
             item = self.q.get()
             if item is None:
                 break
-            groups, f = item
+            fn, f = item
             try:
-                f.set_result(self._launch(groups))
+                f.set_result(fn())
             except BaseException as e:
                 f.set_exception(e)
 
     # ---- the host route of one group (reads longer than the plan's look-ahead) ------------------------------------------
-    def _host_group(self, g, data):
+    def _open_handles(self):
         if self.handles is None:
             self.handles = (bamio.BamHandler(self.bam_path), bamio.FastaHandler(self.fasta_path))
+        return self.handles
+
+    def _host_group(self, g, data):
+        bam, fasta = self._open_handles()
         p = g.plan
-        fb = bamio.fill_batch_blocks(self.handles[0], self.handles[1], g.ivs, p.coffset, p.next_coffset, p.isize, p.out_off, data,
-                                     self.min_mapq, self.include_supplementary, self.downsample_rate, self.safe_bases)
+        fb = bamio.fill_batch_blocks(bam, fasta, g.ivs, p.coffset, p.next_coffset, p.isize, p.out_off, data,
+                                     self.min_mapq, self.include_supplementary, self.downsample_rate, self.safe_bases,
+                                     max_reads=self._read_limit())
         self.T["gpu_inflate_blocks_host"] += fb.blocks_host
         return fb
 
@@ -172,9 +384,15 @@ class GpuDecoder:
             msg = "block or interval table rejected by the device (status %d)" % st
         return IOError("fill_batch: %s [interval %s:%d-%d, virtual offset %d; GPU decode]" % ((msg,) + tuple(g.ivs[k]) + (voff,)))
 
-    def _launch(self, groups):
+    def _scan(self, groups, per=None, ws_limit=None) -> _Scan:
+        """H2D, inflate and pv_bam_scan_dev of these groups in one launch; per: record slots for every interval of each
+        group (None: the safe rule); ws_limit: the scan is refused if its workspace would be larger -> the _Scan, counts
+        on the host"""
         import torch
         T, ctx = self.T, self.ctx
+        if per is None:
+            per = [safe_slots(g.plan.out_bytes) for g in groups]
+        sc = _Scan(groups, per)
         plans = [g.plan for g in groups]
         nb = sum(p.n_blocks for p in plans)
         N = sum(len(g.ivs) for g in groups)
@@ -203,7 +421,7 @@ class GpuDecoder:
         first, ref_at = [], []          # per group (first block, first data byte, first interval); per interval its ref bytes' place
         v64["iv_chunk_off"][0] = 0
         v64["iv_rec_off"][0] = 0
-        for g in groups:
+        for g, per_iv in zip(groups, per):
             p, ivp, k, n = g.plan, g.ivp, g.plan.n_blocks, len(g.ivs)
             payload[pb:pb + p.payload.size] = p.payload
             v64["in_off"][bi:bi + k] = p.in_off + pb
@@ -215,9 +433,8 @@ class GpuDecoder:
             v64["iv_chunk_off"][ii + 1:ii + n + 1] = ivp.chunk_off[1:] + ci
             v64["chunk_beg"][ci:ci + ivp.n_chunks], v64["chunk_end"][ci:ci + ivp.n_chunks] = ivp.chunk_beg, ivp.chunk_end
             dropped[ii:ii + n] = ivp.dropped
-            per = p.out_bytes // REC_MIN_BYTES + 1
-            v64["iv_rec_off"][ii + 1:ii + n + 1] = slots + per * np.arange(1, n + 1, dtype=np.int64)
-            slots += per * n
+            v64["iv_rec_off"][ii + 1:ii + n + 1] = slots + int(per_iv) * np.arange(1, n + 1, dtype=np.int64)
+            slots += int(per_iv) * n
             for r in g.refs:
                 ref[rb:rb + r.size] = r
                 ref_at.append(rb)
@@ -227,6 +444,12 @@ class GpuDecoder:
         ws_bytes = int(ctx.lib.pv_bam_decode_ws_bytes(N, slots))
         if ws_bytes < 0 or slots >= (1 << 31):
             raise _ffi.PepperHipError(_ffi.PV_ERR_LIMIT, "gpu_decode: too many record slots for one launch")
+        ws_words = max(ws_bytes // 8 + 1, 1)
+        if ws_limit is not None and 8 * ws_words > ws_limit:   # (decode_ws_bytes and the library disagree: never expected)
+            raise _ffi.PepperHipError(_ffi.PV_ERR_LIMIT, "gpu_decode: a scan of %d intervals and %d slots needs %d bytes of "
+                                      "workspace, over the budget of %d" % (N, slots, 8 * ws_words, ws_limit))
+        if ws_limit is not None:   # (the polisher's form: scan_groups made these timers)
+            self._account(sc, 8 * ws_words, 8 * ws_words + total + max(out_bytes, 8))
         counts_h = torch.empty((max(N, 1), 8), dtype=torch.int64, pin_memory=True)
         status_h = torch.empty(max(nb, 1), dtype=torch.int32, pin_memory=True)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
@@ -236,7 +459,7 @@ class GpuDecoder:
             d_out = torch.empty(max(out_bytes, 8), dtype=torch.uint8, device=self.dev)
             d_status = torch.empty(max(nb, 1), dtype=torch.int32, device=self.dev)
             d_c4 = torch.empty(4, dtype=torch.int64, device=self.dev)
-            d_ws = torch.empty(max(ws_bytes // 8 + 1, 1), dtype=torch.int64, device=self.dev)
+            d_ws = torch.empty(ws_words, dtype=torch.int64, device=self.dev)
             d_counts = torch.zeros((max(N, 1), 8), dtype=torch.int64, device=self.dev)
             ev[0].record(self.stream)
             d_up.copy_(up, non_blocking=True)
@@ -258,8 +481,6 @@ class GpuDecoder:
             counts_h.copy_(d_counts, non_blocking=True)
             status_h.copy_(d_status, non_blocking=True)
         self.stream.synchronize()
-        t_host = time.perf_counter()
-        cnt, blk_status = counts_h.numpy(), status_h.numpy()
         T["gpu_inflate_h2d_ms"] += ev[0].elapsed_time(ev[1])
         T["gpu_inflate_kernel_ms"] += ev[1].elapsed_time(ev[2])
         T["gpu_decode_scan_ms"] += ev[2].elapsed_time(ev[3])
@@ -269,35 +490,62 @@ class GpuDecoder:
         T["gpu_decode_groups"] += len(groups)
         T["gpu_decode_h2d_bytes"] += total
         T["gpu_decode_d2h_bytes"] += counts_h.numel() * 8 + status_h.numel() * 4
-        T["gpu_decode_records"] += int(cnt[:N, 7].sum())
+        sc.cnt, sc.blk_status = counts_h.numpy(), status_h.numpy()
+        T["gpu_decode_records"] += int(sc.cnt[:N, 7].sum())
+        sc.first, sc.ref_at, sc.ref_base, sc.coffset = first, ref_at, offs["ref"], v64["coffset"].copy()
+        sc.cin, sc.d_ws, sc.d_up, sc.d_out, sc.keep = cin, d_ws, d_up, d_out, (d_status, d_c4, d_counts)
+        return sc
+
+    def _account(self, sc, ws_bytes, all_bytes):
+        """the scan's workspace, and all of its device buffers (workspace, uploaded tables and payloads, inflated bytes), count
+        as live until the _Scan object goes away; the timers keep the largest single workspace and the largest live sums"""
+        import weakref
+        T, live = self.T, self.live
+        live[0] += ws_bytes
+        live[1] += all_bytes
+        T["gpu_decode_ws_peak_bytes"] = max(T["gpu_decode_ws_peak_bytes"], ws_bytes)
+        T["gpu_decode_ws_live_peak_bytes"] = max(T["gpu_decode_ws_live_peak_bytes"], live[0])
+        T["gpu_decode_buffers_live_peak_bytes"] = max(T["gpu_decode_buffers_live_peak_bytes"], live[1])
+
+        def gone():
+            live[0] -= ws_bytes
+            live[1] -= all_bytes
+        weakref.finalize(sc, gone)
+
+    def _kind(self, sc, gi):
+        """group gi of the scan: "dev" (decoded on the device), "host" (the host route) or the exception to raise"""
+        g, (b0, o0, i0) = sc.groups[gi], sc.first[gi]
+        cnt, blk_status = sc.cnt, sc.blk_status
+        for k in range(len(g.ivs)):
+            st = int(cnt[i0 + k, 3])
+            if st == _ffi.PV_BAMDEC_PAST_PLAN:
+                # the host route parses this group's inflated bytes: as in gpu_inflate mode, any failed block of its plan
+                # fails the group (the device only reports the blocks under records it walked before it stopped)
+                bad = np.flatnonzero(blk_status[b0:b0 + g.plan.n_blocks] != _ffi.PV_BGZF_OK)
+                if bad.size:
+                    i = int(bad[0])
+                    return IOError("BGZF block at offset %d: %s (corrupt file; GPU inflate)" % (
+                        int(g.plan.coffset[i]), _ffi.BGZF_STATUS_NAMES.get(int(blk_status[b0 + i]), "status %d" % int(blk_status[b0 + i]))))
+                return "host"
+            if st != _ffi.PV_BAMDEC_OK:
+                return self._error(g, k, cnt[i0 + k], blk_status, sc.coffset)
+            if cnt[i0 + k, 0] > 0 and g.ref_err[k] is not None:
+                return g.ref_err[k]
+        return "dev"
+
+    def _launch(self, groups):
+        import torch
+        T = self.T
+        sc = self._scan(groups)
+        t_host = time.perf_counter()
+        d_out = sc.d_out
         # every group: decoded on the device, or the host route, or an error - in the reader's order
-        kinds = []
-        for g, (b0, o0, i0) in zip(groups, first):
-            kind = "dev"
-            for k in range(len(g.ivs)):
-                st = int(cnt[i0 + k, 3])
-                if st == _ffi.PV_BAMDEC_PAST_PLAN:
-                    kind = "host"
-                    # the host route parses this group's inflated bytes: as in gpu_inflate mode, any failed block of its plan
-                    # fails the group (the device only reports the blocks under records it walked before it stopped)
-                    bad = np.flatnonzero(blk_status[b0:b0 + g.plan.n_blocks] != _ffi.PV_BGZF_OK)
-                    if bad.size:
-                        i = int(bad[0])
-                        kind = IOError("BGZF block at offset %d: %s (corrupt file; GPU inflate)" % (
-                            int(g.plan.coffset[i]), _ffi.BGZF_STATUS_NAMES.get(int(blk_status[b0 + i]), "status %d" % int(blk_status[b0 + i]))))
-                    break
-                if st != _ffi.PV_BAMDEC_OK:
-                    kind = self._error(g, k, cnt[i0 + k], blk_status, v64["coffset"])
-                    break
-                if cnt[i0 + k, 0] > 0 and g.ref_err[k] is not None:
-                    kind = g.ref_err[k]
-                    break
-            kinds.append(kind)
+        kinds = [self._kind(sc, gi) for gi in range(len(groups))]
         items, fills, run = [], [], []
 
         def close_run():
             if run:
-                fl = self._fill(groups, first, run, cnt, cin, d_ws, d_up, offs["ref"], ref_at)
+                fl = self._fill(sc, run)
                 if fl is not None:
                     fills.append(fl)
                     items.append(("dev", fl[0]))
@@ -310,7 +558,7 @@ class GpuDecoder:
             close_run()
             if kind == "host":
                 T["gpu_decode_groups_host"] += 1
-                b0, o0, i0 = first[gi]
+                b0, o0, i0 = sc.first[gi]
                 down = torch.empty(max(g.plan.out_bytes, 1), dtype=torch.uint8, pin_memory=True)
                 with torch.cuda.stream(self.stream):
                     down.copy_(d_out[o0:o0 + max(g.plan.out_bytes, 1)] if g.plan.out_bytes else d_out[:1], non_blocking=True)
@@ -323,36 +571,52 @@ class GpuDecoder:
             else:
                 items.append(("error", kind))
         close_run()
-        if fills:
-            self.stream.synchronize()
-            for db, totals_h, e0, e1 in fills:
-                T["gpu_decode_fill_ms"] += e0.elapsed_time(e1)
-                n_reads, n_bases, n_cigar, st = (int(x) for x in totals_h.tolist())
-                if st != _ffi.PV_OK or n_reads != db.n_reads:
-                    raise _ffi.PepperHipError(st or _ffi.PV_ERR_STATE, "gpu_decode: the fill reported status %d" % st)
-                db.n_bases, db.n_cigar = n_bases, n_cigar
-                T["gpu_decode_d2h_bytes"] += 32
+        self._finish_fills(fills)
         T["gpu_decode_host_s"] += time.perf_counter() - t_host
         return items
 
-    def _fill(self, groups, first, run, cnt, cin, d_ws, d_up, ref_base, ref_at):
-        """the fill of consecutive device-decoded groups -> (DecodedBatch, pinned totals, two timing events) or None when no region is left"""
+    def _finish_fills(self, fills):
+        """wait for the fills and take their totals (bases, CIGAR words, status; the longest read where it was asked for)"""
+        if not fills:
+            return
+        T = self.T
+        self.stream.synchronize()
+        for db, totals_h, e0, e1 in fills:
+            T["gpu_decode_fill_ms"] += e0.elapsed_time(e1)
+            n_reads, n_bases, n_cigar, st = (int(x) for x in totals_h[:4].tolist())
+            if st != _ffi.PV_OK or n_reads != db.n_reads:
+                raise _ffi.PepperHipError(st or _ffi.PV_ERR_STATE, "gpu_decode: the fill reported status %d" % st)
+            db.n_bases, db.n_cigar = n_bases, n_cigar
+            if totals_h.numel() > 4:
+                db.qmax = int(totals_h[4])
+            T["gpu_decode_d2h_bytes"] += 8 * totals_h.numel()
+
+    def _fill(self, sc, run, pick=None, detach=False):
+        """the fill of consecutive device-decoded groups of one scan (run: their indices; pick: the (group index, interval)
+        pairs to take, in order, instead of every interval of `run`) -> (DecodedBatch, pinned totals, two timing events)
+        or None when no region is left. detach: the batch takes a copy of its reference bytes and keeps no buffer of the scan
+        alive (the polisher's form: the scan goes away once its regions are filled)"""
         import torch
+        groups, first, cnt, cin, d_ws, d_up, ref_base, ref_at = (sc.groups, sc.first, sc.cnt, sc.cin, sc.d_ws, sc.d_up,
+                                                                  sc.ref_base, sc.ref_at)
         ivs_all, reg = [], []   # reg: (launch interval, index in ivs_all, reads, kept indices or None)
-        for gi in run:
+        if pick is None:
+            pick = [(gi, k) for gi in run for k in range(len(groups[gi].ivs))]
+        max_reads = self._read_limit()
+        for gi, k in pick:
             g, i0 = groups[gi], first[gi][2]
-            for k, iv in enumerate(g.ivs):
-                n = int(cnt[i0 + k, 0])
-                got = int(g.refs[k].size)
-                keep = None
-                if n > 0:
-                    limit = max(int(min(float(bamio.MAX_READS_IN_REGION), self.downsample_rate * n)), 0)
-                    if n > limit:
-                        keep = bamio.reservoir_indices(n, self.downsample_rate, bamio.MAX_READS_IN_REGION, bamio.RANDOM_SEED)
-                n_out = n if keep is None else len(keep)
-                if n_out > 0 and got > 0:
-                    reg.append((i0 + k, len(ivs_all), n, keep, n_out, iv, got, int(g.ivp.rs[k])))
-                ivs_all.append(iv)
+            iv = g.ivs[k]
+            n = int(cnt[i0 + k, 0])
+            got = int(g.refs[k].size)
+            keep = None
+            if n > 0:
+                limit = max(int(min(float(max_reads), self.downsample_rate * n)), 0)
+                if n > limit:
+                    keep = bamio.reservoir_indices(n, self.downsample_rate, max_reads, bamio.RANDOM_SEED)
+            n_out = n if keep is None else len(keep)
+            if n_out > 0 and got > 0:
+                reg.append((i0 + k, len(ivs_all), n, keep, n_out, iv, got, int(g.ivp.rs[k])))
+            ivs_all.append(iv)
         if not reg:
             return None
         G = len(reg)
@@ -379,7 +643,8 @@ class GpuDecoder:
         n_reads = int(read_off[-1])
         base_cap = int(sum(int(cnt[r[0], 1]) for r in reg))
         cigar_cap = int(sum(int(cnt[r[0], 2]) for r in reg))
-        totals_h = torch.empty(4, dtype=torch.int64, pin_memory=True)
+        n_tot = 5 if self.want_qmax else 4   # {reads, bases, CIGAR words, status} and, for the realigner, the longest read
+        totals_h = torch.zeros(n_tot, dtype=torch.int64, pin_memory=True)
         with torch.cuda.stream(self.stream):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(self.stream)
@@ -391,6 +656,8 @@ class GpuDecoder:
             pieces = [(ref_base + ref_at[r[0]], r[6]) for r in reg]
             if all(pieces[j][0] + pieces[j][1] == pieces[j + 1][0] for j in range(G - 1)):
                 t["ref"] = d_up[pieces[0][0]:pieces[-1][0] + pieces[-1][1]]
+                if detach:
+                    t["ref"] = t["ref"].clone()
             else:
                 t["ref"] = torch.cat([d_up[a:a + n] for a, n in pieces])
             t["read_pos"] = torch.empty(n_reads, dtype=torch.int64, device=self.dev)
@@ -402,7 +669,7 @@ class GpuDecoder:
             t["bases"] = torch.empty(max(base_cap, 1), dtype=torch.uint8, device=self.dev)
             t["quals"] = torch.empty(max(base_cap, 1), dtype=torch.uint8, device=self.dev)
             t["cigar"] = torch.empty(max(cigar_cap, 1), dtype=torch.int32, device=self.dev)
-            d_totals = torch.zeros(4, dtype=torch.int64, device=self.dev)
+            d_totals = torch.zeros(n_tot, dtype=torch.int64, device=self.dev)
             event = torch.cuda.Event()
             db = DecodedBatch(t, G, ivs_all, np.array([r[1] for r in reg], np.int64), np.array([r[2] for r in reg], np.int64),
                               n_reads, int(ref_off[-1]), int(got.max()), event)
@@ -411,20 +678,153 @@ class GpuDecoder:
                                   sb + offs["sel_off"], sb + offs["sel"], int(o), n_reads, base_cap, cigar_cap, db.c,
                                   t["read_hp"].data_ptr(), d_totals.data_ptr(), self.stream.cuda_stream)
             e1.record(self.stream)
+            if self.want_qmax and n_reads:   # the longest read, for the realigner: a reduction behind the fill, no kernel of ours
+                d_totals[4] = (t["base_off"][1:] - t["base_off"][:-1]).max()
             totals_h.copy_(d_totals, non_blocking=True)
             event.record(self.stream)
-        t["_small"], t["_up"] = d_small, d_up
+        t["_small"] = d_small
+        if not detach:
+            t["_up"] = d_up
         self.T["gpu_decode_h2d_bytes"] += total
         return db, totals_h, e0, e1
 
+    # ---- the polisher's form: scans under a workspace budget, launches cut as the host path cuts them -------------------
+    def _host_regions(self, g):
+        """the polisher's host route of one group: polish_summary.region_from_files per region (None: no reads)"""
+        from .polish_summary import region_from_files
+        bam, fasta = self._open_handles()
+        return [region_from_files(bam, fasta, c, s, e, realign=self.realign) for c, s, e in g.ivs]
+
+    def _host_scan(self, g):
+        self.T["gpu_decode_groups_host"] += 1
+        regions = self._host_regions(g)
+        return GroupScan(g, "host", [0 if r is None else len(r.reads) for r in regions], g, regions=regions)
+
+    def _min_record_bytes(self):
+        if self.adaptive_slots and self.density > 0.0:
+            return max(REC_MIN_BYTES, int(1.0 / (4.0 * self.density)))
+        return self.min_record_bytes
+
+    def scan_groups(self, planned):
+        """planned groups, in order -> a generator of a GroupScan for each, in order, with a None behind the groups of every
+        scan (compose_launches: their regions can be filled now). One scan runs at a time and only when the consumer asks
+        for its first group, so with a consumer that fills at every None one scan's buffers are live at a time.
+        Scans are packed by plan_launches under the workspace budget. A scan in which a group ran out of slots (fewer than
+        the safe rule were given) is dropped and its groups are scanned again, once, those groups with the safe rule; a
+        group over the budget on its own and a group that reports PV_BAMDEC_PAST_PLAN are read on the host."""
+        T = self.T
+        for k in ("gpu_decode_slot_retries", "gpu_decode_groups_over_budget", "gpu_decode_ws_peak_bytes",
+                  "gpu_decode_ws_live_peak_bytes", "gpu_decode_buffers_live_peak_bytes"):
+            T.setdefault(k, 0)
+        sizes = [(len(g.ivs), g.plan.out_bytes) for g in planned]
+
+        def short_groups(sc):
+            out = []
+            for j, g in enumerate(sc.groups):
+                i0 = sc.first[j][2]
+                if sc.per[j] < safe_slots(g.plan.out_bytes) and bool((sc.cnt[i0:i0 + len(g.ivs), 3] == _ffi.PV_BAMDEC_BAD_TABLE).any()):
+                    out.append(j)
+            return out
+
+        def run(entries, index, retry):
+            for kind, gis, per in entries:
+                if kind == "host":
+                    T["gpu_decode_groups_over_budget"] += 1
+                    yield self._host_scan(planned[index[gis[0]]])
+                    continue
+                sc = self._scan([planned[index[gi]] for gi in gis], per, self.ws_budget)
+                short = [] if retry else short_groups(sc)
+                if short:   # (PV_BAMDEC_BAD_TABLE under the safe rule is an error below: the second attempt failed)
+                    del sc
+                    T["gpu_decode_slot_retries"] += 1
+                    mine = [index[gi] for gi in gis]
+                    rule = [REC_MIN_BYTES if j in short else self._min_record_bytes() for j in range(len(mine))]
+                    yield from run(plan_launches([sizes[i] for i in mine], self.ws_budget, rule), mine, True)
+                    continue
+                for j, g in enumerate(sc.groups):
+                    i0 = sc.first[j][2]
+                    rows = sc.cnt[i0:i0 + len(g.ivs)]
+                    if g.plan.out_bytes:
+                        self.density = max(self.density, float(rows[:, 7].max(initial=0)) / g.plan.out_bytes)
+                    kind_g = self._kind(sc, j)
+                    yield self._host_scan(g) if kind_g == "host" else GroupScan(g, kind_g, rows[:, 0].copy(), sc, j)
+                del sc
+                yield None
+
+        return run(plan_launches(sizes, self.ws_budget, self._min_record_bytes()), list(range(len(planned))), False)
+
+    def realize(self, launch):
+        """parts of compose_launches -> the parts as the chain takes them: ("dev", DecodedBatch, windows, works) |
+        ("host", batch.RegionBatch, windows, works); windows None unless the groups were planned with them. A decoded batch
+        owns all it needs: the scan it was filled from can go away."""
+        from .batch import pack_regions
+        parts, fills = [], []
+        for kind, key, regs in launch:
+            works = [gs.group.works[k] if gs.group.works else gs.group.ivs[k] for gs, k in regs]
+            if kind == "host":
+                rs = [gs.regions[k] for gs, k in regs]
+                parts.append(("host", pack_regions(rs), [r.window for r in rs] if self.realign else None, works))
+                continue
+            fl = self._fill(key, None, [(gs.gi, k) for gs, k in regs], detach=True)
+            fills.append(fl)
+            win = [gs.group.windows[k] for gs, k in regs] if regs[0][0].group.windows is not None else None
+            parts.append(("dev", fl[0], win, works))
+        self._finish_fills(fills)
+        return parts
+
+
+def decoded_launches(dec, planned, per_launch, scan_regions=None):
+    """the polisher's launches from planned groups (an iterator, in work order): groups are handed to the decoder's
+    scan_groups scan_regions regions at a time (default: one launch's worth), cut into launches by compose_launches, and
+    every part is realized (filled) as soon as it is complete - before the next scan runs. dec: a GpuDecoder, or anything
+    with its scan_groups and realize (CPU tests pass a stub). A generator: GpuDecoder.iterate runs it on the service thread.
+    Adds the seconds spent in the decoder to the timer decode_s."""
+    want = int(scan_regions or per_launch)
+    T = getattr(dec, "T", {})
+
+    def clock(t0):
+        T["decode_s"] = T.get("decode_s", 0.0) + time.perf_counter() - t0
+
+    def scanned(buf):
+        it = iter(dec.scan_groups(buf))
+        while True:
+            t0 = time.perf_counter()
+            try:
+                gs = next(it)
+            except StopIteration:
+                clock(t0)
+                break
+            clock(t0)
+            yield gs
+        yield None
+
+    def scans():
+        buf, n = [], 0
+        for g in planned:
+            buf.append(g)
+            n += len(g.ivs)
+            if n >= want:
+                yield from scanned(buf)
+                buf, n = [], 0
+        if buf:
+            yield from scanned(buf)
+
+    def on_part(part):
+        t0 = time.perf_counter()
+        r = dec.realize([part])[0]
+        clock(t0)
+        return r
+
+    return compose_launches(scans(), per_launch, on_part)
+
 
 def decode_groups(ctx, bam_path, fasta_path, groups_of_intervals, min_mapq=5, include_supplementary=False, downsample_rate=1.0,
-                  safe_bases=100, T=None):
+                  safe_bases=100, T=None, max_reads=None):
     """One launch over several reader groups (lists of (contig, start, end)), for tests and tools -> the list of items
     GpuDecoder.submit gives: ("dev", DecodedBatch) | ("host", FilledBatch) | ("error", exception), and the timers in T."""
     T = T if T is not None else {}
     bam, fasta = bamio.BamHandler(bam_path), bamio.FastaHandler(fasta_path)
-    dec = GpuDecoder(ctx, bam_path, fasta_path, min_mapq, include_supplementary, downsample_rate, safe_bases, T)
+    dec = GpuDecoder(ctx, bam_path, fasta_path, min_mapq, include_supplementary, downsample_rate, safe_bases, T, max_reads=max_reads)
     try:
         planned = [PlannedGroup(bam, fasta, ivs, safe_bases) for ivs in groups_of_intervals]
         return dec.submit(planned).result()
@@ -435,12 +835,12 @@ def decode_groups(ctx, bam_path, fasta_path, groups_of_intervals, min_mapq=5, in
 
 
 def decoded_batches(ctx, bam_path, fasta_path, groups, reads_per_call, n_thr, min_mapq, include_supplementary, downsample_rate,
-                    safe_bases, T, merge):
+                    safe_bases, T, merge, max_reads=None):
     """region_batches' generator in gpu_decode mode: (DecodedBatch, intervals of its regions) pairs in the default mode's
     order; a group that took the host route comes as the default mode's host batch (a list of parts when merge is False)."""
     T.setdefault("gpu_decode_plan_cpu_s", 0.0)    # reader threads: CPU seconds (time.thread_time) planning blocks + fetching FASTA
     T.setdefault("gpu_decode_plan_wall_s", 0.0)   # ... and their wall seconds
-    dec = GpuDecoder(ctx, bam_path, fasta_path, min_mapq, include_supplementary, downsample_rate, safe_bases, T)
+    dec = GpuDecoder(ctx, bam_path, fasta_path, min_mapq, include_supplementary, downsample_rate, safe_bases, T, max_reads=max_reads)
     tls = threading.local()
 
     def plan_group(ivs):

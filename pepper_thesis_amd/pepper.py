@@ -28,6 +28,7 @@ def make_images_parser(ap=None):
     ap.add_argument("--realign", action="store_true", default=False,
                     help="realign every read to the draft (Smith-Waterman on the device) before the images are built, as "
                          "polish --realign; the reference always does this. Off by default")
+    cli.polish_gpu_decode_flag(ap)
     return ap
 
 

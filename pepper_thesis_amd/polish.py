@@ -9,7 +9,10 @@ prediction HDF5 files. Here each batch of regions goes through
 without leaving HBM; only the region offsets and the polished bases (one byte per base) come back to the host.
 
   python -m pepper_thesis_amd polish -b reads.bam -f draft.fa -m model.pkl -o out/polished [-t 5] [-r ctg:start-end] [--bf16]
-      [--realign]
+      [--realign] [--gpu_decode]
+
+--gpu_decode (opt-in) replaces the first stage: reader threads only plan blocks and fetch draft bytes, and the BAM is inflated,
+decoded and clipped on the device (gpu_decode.py; _decoded_pieces below). Same FASTA.
 
 Semantics kept from the reference:
   * regions: ImageGenerationUI.py:257-273 - for pos in range(start, end, 1000): [max(start, pos-100), min(end, pos+1100)],
@@ -179,14 +182,18 @@ class _DeviceChain:
             self.seq = torch.zeros(chunks * 1000, dtype=torch.uint8, device=self.dev)
             torch.cuda.synchronize()   # the fills ran on torch's stream; the chain runs on the context's
 
-    def _summarize(self, batch, db, host_batch=None) -> int:
+    def _summarize(self, batch, db, host_batch=None, sizes=None) -> int:
         """builder on the device; -> n_chunks. A batch beyond the device form's workspace heuristics (PV_ERR_LIMIT: e.g. a
         very long insert) runs the host form, which retries with measured bounds, and its chunks are uploaded.
-        host_batch: makes the host batch when `batch` is None (the realigned reads live on the device only)."""
+        host_batch: makes the host batch when `batch` is None (the realigned reads live on the device only).
+        sizes: (columns of all regions, regions) for the chunk estimate when neither `batch` nor db.host exists (a batch
+        decoded on the device: the sizes come from its plan)."""
         from .polish_summary import polish_summarize
-        b = batch if batch is not None else db.host
-        cols = int((b.ref_end - b.ref_start + 1).sum())
-        want = (cols + cols // 2 + 1024) // 950 + 2 * b.n_regions + 2
+        if sizes is None:
+            b = batch if batch is not None else db.host
+            sizes = int((b.ref_end - b.ref_start + 1).sum()), b.n_regions
+        cols, n_regions = sizes
+        want = (cols + cols // 2 + 1024) // 950 + 2 * n_regions + 2
         for _ in range(2):
             self._ensure(want)
             self.ctx.polish_summarize_dev(db, self.dout)
@@ -207,18 +214,21 @@ class _DeviceChain:
             getattr(self.dout, name)[:n].copy_(torch.from_numpy(getattr(out, name)))
         return n
 
-    def _realign(self, batch, db, windows):
+    def _realign(self, batch, db, windows, qmax=None, host_batch=None):
         """reads realigned to the draft on the device -> (host batch maker, device batch for the builder). The only read-back
-        is the counters (cigar total and status); the host batch is fetched only if the builder needs its host form."""
+        is the counters (cigar total and status); the host batch is fetched only if the builder needs its host form.
+        batch None (a batch decoded on the device): qmax is its longest read and host_batch makes its host copy."""
         import torch
         from .realign import DeviceRealignOut, RealignResult, device_windows, pack_windows, realigned_batch
         woff, win = pack_windows(windows)
         d_woff, d_win = device_windows(woff, win, self.dev)
-        qmax = int(np.diff(batch.base_off).max()) if batch.n_reads else 0
-        want = batch.n_cigar + 4 * batch.n_reads + batch.n_bases // 8 + 16
+        if batch is not None:
+            qmax = int(np.diff(batch.base_off).max()) if batch.n_reads else 0
+        n_reads = db.n_reads
+        want = db.n_cigar + 4 * n_reads + db.n_bases // 8 + 16
         for _ in range(2):
-            if self.rout is None or self.rout.n_reads < batch.n_reads or self.rout.capacity < want:
-                self.rout = DeviceRealignOut(max(batch.n_reads, self.rout.n_reads if self.rout else 0), want, self.dev)
+            if self.rout is None or self.rout.n_reads < n_reads or self.rout.capacity < want:
+                self.rout = DeviceRealignOut(max(n_reads, self.rout.n_reads if self.rout else 0), want, self.dev)
                 torch.cuda.synchronize()   # the fills ran on torch's stream; the chain runs on the context's
             self.ctx.polish_realign_dev(db, d_woff.data_ptr(), d_win.data_ptr(), qmax, self.rout)
             self.ctx.synchronize()
@@ -235,12 +245,12 @@ class _DeviceChain:
             setattr(c, f, getattr(db.c, f))
         c.read_pos, c.cigar_off, c.cigar = ro.read_pos.data_ptr(), ro.cigar_off.data_ptr(), ro.cigar.data_ptr()
         rdb = _RealignedDeviceBatch(c, db, total, (d_woff, d_win))
-        n = batch.n_reads
+        n = n_reads
 
         def host():
             res = RealignResult(ro.read_pos[:n].cpu().numpy(), ro.cigar_off[:n + 1].cpu().numpy(),
                                 ro.cigar[:total].cpu().numpy().view(np.uint32), None, None, None, 0, 0)
-            return realigned_batch(batch, res)
+            return realigned_batch(batch if batch is not None else host_batch(), res)
         return host, rdb
 
     def p2_labels(self, images: np.ndarray) -> np.ndarray:
@@ -258,17 +268,38 @@ class _DeviceChain:
             return db, self._summarize(None, db, host)
         return db, self._summarize(batch, db)
 
+    def build_decoded(self, dec, windows=None):
+        """build for a gpu_decode.DecodedBatch: the reads are on the device already, the decode is ordered before the chain
+        with its event, read totals and the longest read come from the decode, region sizes from its plan"""
+        dec.wait_on(self.ctx)
+        sizes = (dec.n_ref_bytes, dec.n_regions)   # (the polisher's reference bytes are one per column of the region)
+
+        def host_batch():
+            return dec.to_host()[0]
+        if windows is not None:
+            host, db = self._realign(None, dec, windows, dec.qmax, host_batch)
+            return db, self._summarize(None, db, host, sizes)
+        return dec, self._summarize(None, dec, host_batch, sizes)
+
     def run(self, batch, windows=None) -> Tuple[np.ndarray, bytes]:
         """one batch of regions -> (region_off [n_regions+1], polished bases of all its regions, concatenated).
         windows: the realignment window of every region (polish --realign), else None."""
         db, n = self.build(batch, windows)
-        region_off = np.zeros(batch.n_regions + 1, np.int64)
+        return self._labels_and_stitch(db, n, batch.n_regions)
+
+    def run_decoded(self, dec, windows=None) -> Tuple[np.ndarray, bytes]:
+        """run for a gpu_decode.DecodedBatch"""
+        db, n = self.build_decoded(dec, windows)
+        return self._labels_and_stitch(db, n, dec.n_regions)
+
+    def _labels_and_stitch(self, db, n: int, n_regions: int) -> Tuple[np.ndarray, bytes]:
+        region_off = np.zeros(n_regions + 1, np.int64)
         if n == 0:
             return region_off, b""
         import torch
-        roff = torch.empty(batch.n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
+        roff = torch.empty(n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
         self.ctx.forward_p2_dev(self.dout.images.data_ptr(), n, self.labels.data_ptr())
-        self.ctx.polish_stitch_dev(self.dout, n, self.labels.data_ptr(), db.t["ref_start"].data_ptr(), batch.n_regions,
+        self.ctx.polish_stitch_dev(self.dout, n, self.labels.data_ptr(), db.t["ref_start"].data_ptr(), n_regions,
                                    roff.data_ptr(), self.seq.data_ptr(), self.seq.numel(), self.counts.data_ptr())
         self.ctx.synchronize()   # raises if a split GRU form timed out (its labels are then poisoned)
         total, status, bad = (int(v) for v in self.counts[:3].tolist())
@@ -299,7 +330,7 @@ class _RealignedDeviceBatch:
     """a DeviceBatch whose positions and cigars are the realigner's output (same bases, quals, flags, mapq, regions)"""
 
     def __init__(self, c, db, n_cigar, keep):
-        self.c, self.host, self._keep = c, db.host, (db, keep)
+        self.c, self.host, self._keep = c, getattr(db, "host", None), (db, keep)
         self.n_reads, self.n_bases, self.n_cigar, self.n_ref_bytes = db.n_reads, db.n_bases, int(n_cigar), db.n_ref_bytes
         self.max_region_len = db.max_region_len
         self.t = db.t
@@ -317,11 +348,18 @@ def _read_ahead(ex, fn, items, depth):
 
 
 def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int = 2048, threads: int = 5, realign: bool = False,
-                  timers: Optional[dict] = None):
+                  timers: Optional[dict] = None, gpu_decode: bool = False, open_decoder=None):
     """the regions of `work` through the chain -> (contig, region start, region index, polished bases) for every region with
     reads, in `work` order. This is the whole device part of a run: the single-rank run passes every region, a rank of a
     multi-device run its share. chain.run(batch, windows) -> (region_off, bases) (_DeviceChain or a CPU test's stub).
-    timers (optional) accumulates read_s, device_s, regions, batches."""
+    timers (optional) accumulates read_s, device_s, regions, batches.
+    gpu_decode: the device read path (_decoded_pieces): the reader threads only plan, the BAM is inflated, decoded and clipped
+    on chain.ctx's device, and the chain takes the batches where they are (chain.run_decoded). open_decoder(T): the decoder,
+    by default a gpu_decode.GpuDecoder with the polisher's settings (CPU tests pass a stub with its scan_groups, realize,
+    iterate and close)."""
+    if gpu_decode:
+        yield from _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder)
+        return
     from .batch import pack_regions
     from .bamio import BamHandler, FastaHandler
     from .polish_summary import region_from_files
@@ -366,13 +404,78 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
             yield from flush(pending)
 
 
+def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder):
+    """polish_pieces' device read path. Reader threads plan reader groups (gpu_decode.region_groups: blocks, interval table,
+    draft bytes, realign windows); the decoder's service thread scans them, cuts the regions with reads into the launches
+    the host path makes (per_launch regions each) and fills them on its own stream; this thread runs the chain on every
+    part of a launch: a decoded batch as it lies on the device, a host-route group (reads longer than the plan's look-ahead,
+    or a group over the workspace budget) as the host path's packed batch. Adds the timers plan_s, decode_s, chain_runs
+    (chain runs: one per part of a launch) and the decoder's own (gpu_decode_groups_host, gpu_decode_slot_retries, gpu_decode_ws_peak_bytes, ...)."""
+    import threading
+    from . import gpu_decode as gd
+    from .bamio import BamHandler, FastaHandler
+    from .polish_summary import MAX_READS_IN_REGION
+    T = timers if timers is not None else {}
+    for k in ("read_s", "device_s", "regions", "batches", "chain_runs", "plan_s", "decode_s", "gpu_decode_groups", "gpu_decode_groups_host"):
+        T.setdefault(k, 0)
+    per_launch = max(1, int(batch_size) // 2)
+    if open_decoder is None:
+        def open_decoder(T):
+            return gd.GpuDecoder(chain.ctx, bam, fasta, 0, False, 1.0, 0, T, max_reads=MAX_READS_IN_REGION, adaptive_slots=True,
+                                 realign=realign)
+    local = threading.local()
+
+    def plan(ws):
+        if not hasattr(local, "h"):
+            local.h = (BamHandler(bam), FastaHandler(fasta))
+        return gd.PlannedGroup(local.h[0], local.h[1], [(w.contig, w.start, w.end) for w in ws], 0, pad_ref=True,
+                               windows=realign, works=ws)
+
+    groups = gd.region_groups(work)
+    dec = open_decoder(T)
+    try:
+        with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, int(threads))) as ex:
+            def planned():
+                for g in _read_ahead(ex, plan, groups, max(2 * per_launch // gd.GROUP_REGIONS, 2 * int(threads), 2)):
+                    T["plan_s"] += g.t_plan
+                    yield g
+            gen = gd.decoded_launches(dec, planned(), per_launch)
+            launches = dec.iterate(gen)
+            t0 = time.perf_counter()
+            for parts in launches:
+                T["read_s"] += time.perf_counter() - t0
+                t0 = time.perf_counter()
+                for kind, b, windows, ws in parts:
+                    roff, seq = chain.run_decoded(b, windows) if kind == "dev" else chain.run(b, windows)
+                    T["chain_runs"] += 1
+                    T["regions"] += len(ws)
+                    for g, w in enumerate(ws):
+                        yield w.contig, w.start, w.index, seq[roff[g]:roff[g + 1]]
+                T["device_s"] += time.perf_counter() - t0
+                T["batches"] += 1
+                del parts
+                t0 = time.perf_counter()
+            T["read_s"] += time.perf_counter() - t0
+    finally:
+        dec.close()
+
+
+def decode_report(T: dict) -> str:
+    """one line on what the device read path did, for the log (empty without --gpu_decode)"""
+    if "gpu_decode_groups" not in T:
+        return ""
+    return ("GPU DECODE: %d GROUPS IN %d SCANS, %d ON THE HOST ROUTE, %d SLOT RETRIES, %d CHAIN RUNS IN %d LAUNCHES"
+            % (T["gpu_decode_groups"], T.get("gpu_inflate_launches", 0), T["gpu_decode_groups_host"],
+               T.get("gpu_decode_slot_retries", 0), T.get("chain_runs", 0), T["batches"]))
+
+
 def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region: Optional[str] = None, batch_size: int = 2048,
                  threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None,
-                 realign: bool = False, chain=None) -> str:
+                 realign: bool = False, chain=None, gpu_decode: bool = False) -> str:
     """-> path of the polished FASTA. batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
     realign: realign every read to the draft on the device before the builder, as the reference always does.
     chain: a chain with the weights already loaded (open_device_chain; the caller closes it), else one is made on `ctx`
-    (default: a context on device 0) from model_path."""
+    (default: a context on device 0) from model_path. gpu_decode: polish_pieces' device read path."""
     from .bamio import BamHandler, FastaHandler
     from .runtime import Context
     t_start = time.perf_counter()
@@ -389,7 +492,7 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
         work, T["bases_in"] = polish_work(fa, bm, region)
         out_path = output_fasta_path(out_prefix)
         log("POLISHING %d REGIONS, OUTPUT: %s" % (len(work), out_path))
-        pieces = list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T))
+        pieces = list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode))
     finally:
         if own is not None:
             own.close()
@@ -432,8 +535,11 @@ def run(args, open_chain=open_device_chain) -> int:
     try:
         T = {}
         path = polish_fused(args.bam, args.fasta, args.model_path, args.output_file, args.region, args.batch_size, args.threads,
-                            timers=T, realign=bool(getattr(args, "realign", False)), chain=chain)
+                            timers=T, realign=bool(getattr(args, "realign", False)), chain=chain,
+                            gpu_decode=bool(getattr(args, "gpu_decode", False)))
     finally:
         chain.close()
+    if decode_report(T):
+        log(decode_report(T))
     log("POLISHED FASTA: %s (%d REGIONS, %d BASES IN %.2f SEC)" % (path, T["regions"], T["bases_out"], T["wall_s"]))
     return 0

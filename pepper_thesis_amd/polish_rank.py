@@ -70,6 +70,8 @@ def rank_argv(args, plan: List[RankPlan]) -> List[str]:
         argv.append("--bf16")
     if getattr(args, "realign", False):
         argv.append("--realign")
+    if getattr(args, "gpu_decode", False):
+        argv.append("--gpu_decode")
     return argv
 
 
@@ -163,7 +165,8 @@ def _polish_share(args, me: RankPlan, world: int, open_chain, T: dict):
     chain = open_chain(me.device, me.shared_device, state_dict, dtype)
     try:
         pieces = list(polish.polish_pieces(args.bam, args.fasta, mine, chain, args.batch_size, me.threads,
-                                           bool(getattr(args, "realign", False)), T))
+                                           bool(getattr(args, "realign", False)), T,
+                                           gpu_decode=bool(getattr(args, "gpu_decode", False))))
     finally:
         chain.close()
     return pieces, work, out_path
@@ -241,6 +244,8 @@ def run(args, open_chain=None, timeout_s: float = EXCHANGE_TIMEOUT_S) -> int:
                 sys.stderr.write("ERROR: polish: %s; no FASTA written.\n"
                                  % "; ".join("rank %d failed (%s)" % (r, s) for r, s in bad))
             return 1
+        if polish.decode_report(T):
+            polish.log("[RANK %d/%d] %s" % (rank, world, polish.decode_report(T)))
         polish.log("[RANK %d/%d] POLISHED %d REGIONS, %d BASES (%.2f SEC)"
                    % (rank, world, T["regions"], sum(len(p[3]) for p in pieces), time.perf_counter() - t0))
         try:

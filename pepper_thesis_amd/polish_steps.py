@@ -84,11 +84,23 @@ class _ImageChain:
 
     def run(self, batch, windows=None):
         _, n = self.chain.build(batch, windows)
+        return self._chunks(n, batch.n_regions)
+
+    def run_decoded(self, dec, windows=None):
+        """run for a gpu_decode.DecodedBatch (make_images --gpu_decode)"""
+        _, n = self.chain.build_decoded(dec, windows)
+        return self._chunks(n, dec.n_regions)
+
+    @property
+    def ctx(self):
+        return self.chain.ctx
+
+    def _chunks(self, n, n_regions):
         d = self.chain.dout
         region = d.region[:n].cpu().numpy()
         images, position = d.images[:n].cpu().numpy(), d.position[:n].cpu().numpy()
         index, chunk_id = d.index[:n].cpu().numpy(), d.chunk_id[:n].cpu().numpy()
-        region_off = np.searchsorted(region, np.arange(batch.n_regions + 1), side="left")   # the builder emits regions ascending
+        region_off = np.searchsorted(region, np.arange(n_regions + 1), side="left")   # the builder emits regions ascending
         return region_off, [(images[k], position[k], index[k], int(chunk_id[k])) for k in range(n)]
 
     def close(self):
@@ -102,8 +114,9 @@ def open_image_chain(device: int = 0) -> _ImageChain:
 
 
 def make_images(bam: str, fasta: str, region: Optional[str], output_dir: str, threads: int, realign: bool = False,
-                chain=None, batch_size: int = 2048) -> List[str]:
-    """-> the image files written. chain: an _ImageChain (CPU tests pass a stub), else one on device 0."""
+                chain=None, batch_size: int = 2048, gpu_decode: bool = False) -> List[str]:
+    """-> the image files written. chain: an _ImageChain (CPU tests pass a stub), else one on device 0.
+    gpu_decode: the device read path of polish.polish_pieces."""
     from . import polish
     from .bamio import BamHandler, FastaHandler
     from .hdf5io import PolishImageStore
@@ -118,7 +131,9 @@ def make_images(bam: str, fasta: str, region: Optional[str], output_dir: str, th
     stores, n_chunks = [], 0
     try:
         stores = [PolishImageStore(p + ".partial", "w") for p in paths]
-        for contig, _, i, chunks in polish.polish_pieces(bam, fasta, work, chain, batch_size, threads, realign):
+        T = {}
+        for contig, _, i, chunks in polish.polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T,
+                                                         gpu_decode=gpu_decode):
             w = work[i]
             for image, position, index, chunk_id in chunks:
                 stores[i % threads].write_chunk(contig, w.start, w.end, chunk_id, image, position, index)
@@ -135,6 +150,8 @@ def make_images(bam: str, fasta: str, region: Optional[str], output_dir: str, th
     finally:
         if own:
             chain.close()
+    if polish.decode_report(T):
+        log(polish.decode_report(T))
     log("FINISHED IMAGE GENERATION: %d CHUNKS" % n_chunks)
     return paths
 
@@ -148,7 +165,8 @@ def make_images_run(args, chain=None) -> int:
         sys.stderr.write("ERROR: THREADS NEEDS TO BE > 0.\n")
         return 1
     try:
-        make_images(args.bam, args.fasta, args.region, args.output_dir, args.threads, bool(args.realign), chain)
+        make_images(args.bam, args.fasta, args.region, args.output_dir, args.threads, bool(args.realign), chain,
+                    gpu_decode=bool(getattr(args, "gpu_decode", False)))
     except Exception as e:
         sys.stderr.write("ERROR: make_images: %s: %s; no image file written.\n" % (type(e).__name__, e))
         return 1

@@ -22,7 +22,10 @@
               and model load included): wall time of every command, the sizes of the image and prediction files, and whether
               the two FASTA files are byte-identical. Written to profiles/polish_steps_bench.json with --out.
 
-  python tools/bench_polish_e2e.py [--leg stitch|e2e|steps|all] [--mbp 2.0] [--reps 20] [--realign] [--d_ids 0,0] [--out f]
+  --gpu_decode: the e2e leg reads the BAM through `polish --gpu_decode` (inflate, record decode and clipping on the device).
+
+  python tools/bench_polish_e2e.py [--leg stitch|e2e|steps|all] [--mbp 2.0] [--reps 20] [--realign] [--d_ids 0,0] [--gpu_decode]
+                                   [--out f]
 For the rocprofv3 row run the stitch leg alone under `rocprofv3 --kernel-trace --stats -d <dir> -- python ... --leg stitch`.
 """
 import argparse
@@ -110,18 +113,28 @@ def stitch_leg(reps=20):
                                      "stitch_ms": round(t_host * 1e3, 1)}}
 
 
-def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info):
+def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False):
     # warm-up on a small region (code objects, allocator), then the timed run
-    polish.polish_fused(bam, fa, model, out + "_warm", region="chr20:0-50000", threads=threads, ctx=ctx, realign=realign)
+    kw = {"gpu_decode": True} if gpu_decode else {}
+    polish.polish_fused(bam, fa, model, out + "_warm", region="chr20:0-50000", threads=threads, ctx=ctx, realign=realign, **kw)
     T = {}
     t0 = time.perf_counter()
-    path = polish.polish_fused(bam, fa, model, out, threads=threads, ctx=ctx, timers=T, realign=realign)
+    path = polish.polish_fused(bam, fa, model, out, threads=threads, ctx=ctx, timers=T, realign=realign, **kw)
     wall = time.perf_counter() - t0
     size = os.path.getsize(path)
-    return {"draft_bp": T["bases_in"], "reads": info["reads"], "regions": T["regions"], "batches": T["batches"],
-            "polished_bp": T["bases_out"], "fasta_bytes": size, "wall_s": round(wall, 3),
-            "read_s": round(T["read_s"], 3), "device_s": round(T["device_s"], 3),
-            "draft_mbp_per_s": round(T["bases_in"] / wall / 1e6, 4), "reader_threads": threads}
+    res = {"draft_bp": T["bases_in"], "reads": info["reads"], "regions": T["regions"], "batches": T["batches"],
+           "polished_bp": T["bases_out"], "fasta_bytes": size, "wall_s": round(wall, 3),
+           "read_s": round(T["read_s"], 3), "device_s": round(T["device_s"], 3),
+           "draft_mbp_per_s": round(T["bases_in"] / wall / 1e6, 4), "reader_threads": threads}
+    if gpu_decode:
+        import hashlib
+        import torch
+        res["gpu_decode"] = True
+        res["torch_max_memory_allocated_bytes"] = int(torch.cuda.max_memory_allocated())   # decode and chain tensors, warm-up included
+        res["fasta_sha256"] = hashlib.sha256(open(path, "rb").read()).hexdigest()
+        res["timers"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in sorted(T.items())
+                         if k in ("plan_s", "decode_s", "chain_runs") or k.startswith("gpu_")}
+    return res
 
 
 def realign_stats(ctx, bam, fa, per_launch=1024):
@@ -179,7 +192,7 @@ def realign_stats(ctx, bam, fa, per_launch=1024):
             "band_gcups": round(band / (band_ms * 1e-3) / 1e9, 1) if band_ms else None}
 
 
-def e2e_leg(mbp=2.0, threads=16, realign=False):
+def e2e_leg(mbp=2.0, threads=16, realign=False, gpu_decode=False):
     import numpy as np
     from bench_filepath import make_files
     from pepper_thesis_amd import polish, runtime, synth
@@ -190,11 +203,11 @@ def e2e_leg(mbp=2.0, threads=16, realign=False):
         np.savez(model, **synth.make_weights_p2(4321, 3.0))
         ctx = runtime.Context(0)
         try:
-            out = _e2e_run(polish, ctx, bam, fa, model, os.path.join(d, "out"), threads, False, info)
+            out = _e2e_run(polish, ctx, bam, fa, model, os.path.join(d, "out"), threads, False, info, gpu_decode)
             if not realign:
                 return out
             res = {"without_realign": out,
-                   "with_realign": _e2e_run(polish, ctx, bam, fa, model, os.path.join(d, "out_rl"), threads, True, info)}
+                   "with_realign": _e2e_run(polish, ctx, bam, fa, model, os.path.join(d, "out_rl"), threads, True, info, gpu_decode)}
             res["realign"] = st = realign_stats(ctx, bam, fa)
             rl_s = sum(st["kernel_ms"].values()) / 1e3
             res["realign"]["kernel_s"] = round(rl_s, 3)
@@ -301,13 +314,15 @@ def main():
     ap.add_argument("--realign", action="store_true", help="e2e leg without and with polish --realign, plus realigner stats")
     ap.add_argument("--d_ids", type=str, default=None,
                     help="e2e leg: the polish command with these -d_ids against the first id alone with PV_SHARED_DEVICE=1")
+    ap.add_argument("--gpu_decode", action="store_true",
+                    help="e2e leg: the device read path (polish --gpu_decode); adds the decode timers and the FASTA's sha256")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON to this file")
     a = ap.parse_args()
     out = {}
     if a.leg in ("stitch", "all"):
         out["stitch"] = stitch_leg(a.reps)
     if a.leg in ("e2e", "all"):
-        out["e2e"] = ranks_leg(a.mbp, a.threads, a.d_ids, a.realign) if a.d_ids else e2e_leg(a.mbp, a.threads, a.realign)
+        out["e2e"] = ranks_leg(a.mbp, a.threads, a.d_ids, a.realign) if a.d_ids else e2e_leg(a.mbp, a.threads, a.realign, a.gpu_decode)
     if a.leg == "steps":
         out["steps"] = steps_leg(a.mbp, a.threads)
     print(json.dumps(out, indent=1))
