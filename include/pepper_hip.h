@@ -245,6 +245,38 @@ int pv_polish_stitch(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks,
                      const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap,
                      int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* counts);
 
+/* The polisher's per-base quality: the P2 labels and the accumulated softmax of pv_rnn_forward_p2[_dev] -> one Phred byte
+ * per chunk row. It restates what the reference's caller means to store as phred_score, -10 log10(1 - value / counts)
+ * (pepper/modules/python/models/predict_distributed_gpu.py:96-105; that code feeds the label in place of the value), as a
+ * count of thresholds, so that host and device agree bit for bit and no logarithm is called. For row r of a chunk:
+ *   cnt = 1.0f for r < seq_overlap or r >= seq_length - seq_overlap, else 2.0f (the windows that cover the row);
+ *   err = 1.0f - acc[r][labels[r]] / cnt   (one float32 divide, one float32 subtract, not fused);
+ *   q   = #{k in 1..93 : err <= T[k]},  T[k] = 10^(-k/10) rounded to float32, a literal table (pv_polish_qual_threshold).
+ * So err <= 0 gives 93 (the FASTQ ceiling '~'), a NaN acc gives 0. A label above 4 gives q = 0 and status PV_ERR_STATE.
+ * labels: uint8 [B][seq_length]; acc: float [B][seq_length][5]; qual: uint8 [B][seq_length], every row, label-0 rows included.
+ * d_counts = {rows, status, first bad chunk (-1 if none), its first bad row}. Device-resident and asynchronous on `stream`;
+ * no global atomics, no host synchronisation; capturable. */
+int pv_polish_row_qual_dev(pv_ctx* ctx, const uint8_t* labels, const float* acc, int64_t B, int seq_length, int seq_overlap,
+                           uint8_t* qual, int64_t* d_counts, void* stream);
+/* HOST buffers in and out; counts[4] as d_counts above; returns the status (qual and counts are filled on PV_ERR_STATE too). */
+int pv_polish_row_qual(pv_ctx* ctx, const uint8_t* labels, const float* acc, int64_t B, int seq_length, int seq_overlap,
+                       uint8_t* qual, int64_t* counts);
+/* T[k] of the rule above for k in 0..93 (T[0] = 1), 0 for any other k. Needs no device. */
+float pv_polish_qual_threshold(int k);
+
+/* pv_polish_stitch[_dev] with a second byte plane: row_qual uint8 [n_chunks][seq_length] (pv_polish_row_qual) in,
+ * qual uint8 [seq_capacity] out. The same columns are kept, the same chunk wins a shared column and the same label-0
+ * columns are dropped, so seq, region_off and d_counts are those of pv_polish_stitch[_dev]; qual[i] is the winning chunk's
+ * row quality of the column that gave seq[i], stored raw (no +33). */
+int pv_polish_stitch_qual_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                              const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap,
+                              int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* d_counts, void* stream,
+                              const uint8_t* row_qual, uint8_t* qual);
+int pv_polish_stitch_qual(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                          const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap,
+                          int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* counts,
+                          const uint8_t* row_qual, uint8_t* qual);
+
 /* The polisher's read realignment (AlignmentSummarizer.reads_to_reference_realignment, pepper/modules/python/
  * AlignmentSummarizer.py:159-177 -> ReadAligner::align_reads_to_reference, simple_aligner.cpp:66-107): every read of a region
  * is aligned to the draft with the reference's striped Smith-Waterman rules (match 4, mismatch 6, gap open 8, gap extend 2,

@@ -164,6 +164,9 @@ def polish_parser(ap=None):
                     help="realign every read to the draft (Smith-Waterman on the device) before the images are built; the "
                          "reference always does this (AlignmentSummarizer realignment_flag=True). Off by default for now")
     polish_gpu_decode_flag(ap)
+    ap.add_argument("--qualities", action="store_true", default=False,
+                    help="also write <output_file>/_pepper_polished.fq: the same contigs with one Phred byte per base (0..93) "
+                         "from the network's accumulated softmax (opt-in; one device; the FASTA is unchanged)")
     return ap
 
 

@@ -204,8 +204,10 @@ __global__ __launch_bounds__(ST_SCAN_THREADS) void k_stitch_scan(StitchArgs a) {
     }
 }
 
-// one block per chunk: block-local ranks of the emitted columns, then one byte each
-__global__ __launch_bounds__(ST_THREADS) void k_stitch_write(StitchArgs a) {
+// one block per chunk: block-local ranks of the emitted columns, then one byte each; QUAL: and the column's row quality
+// (pv_polish_row_qual) into a second plane at the same offset
+template <bool QUAL>
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_write(StitchArgs a, const uint8_t* row_qual, uint8_t* qual) {
     __shared__ int32_t lds[ST_THREADS / 64];
     if (a.counts[1] != PV_OK) return;
     const int64_t k = blockIdx.x;
@@ -223,13 +225,21 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_write(StitchArgs a) {
     uint8_t* dst = a.seq + a.chunk_off[k] + r0;
     for (int j = 0; j < j1 - j0; j++)
         if (lbs[j]) *dst++ = "ACGT"[lbs[j] - 1];
+    if (QUAL) {
+        uint8_t* qdst = qual + a.chunk_off[k] + r0;
+        const uint8_t* q = row_qual + v.base + j0;
+        for (int j = 0; j < j1 - j0; j++)
+            if (lbs[j]) *qdst++ = q[j];
+    }
 }
 
 }  // namespace
 
-extern "C" int pv_polish_stitch_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
-                                    const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap,
-                                    int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* d_counts, void* stream) {
+// the device form of both stitches; QUAL: with the quality plane
+template <bool QUAL>
+static int stitch_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels, const uint8_t* row_qual,
+                      const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap, int64_t* region_off,
+                      uint8_t* seq, uint8_t* qual, int64_t seq_capacity, int64_t* d_counts, void* stream) {
     PV_CHECK(ctx && chunks && region_off && d_counts, PV_ERR_INVALID, "null argument");
     PV_CHECK(n_chunks >= 0 && n_regions >= 0 && seq_capacity >= 0, PV_ERR_INVALID, "negative sizes");
     PV_CHECK(seq_length >= 1 && seq_length <= ST_THREADS * ST_MAX_CPT && seq_overlap >= 0 && seq_overlap < seq_length,
@@ -244,6 +254,7 @@ extern "C" int pv_polish_stitch_dev(pv_ctx* ctx, const pv_polish_out* chunks, in
                                region_start && n_regions > 0),
              PV_ERR_INVALID, "chunk arrays, labels or region starts missing");
     PV_CHECK(seq_capacity == 0 || seq, PV_ERR_INVALID, "seq missing");
+    if (QUAL) PV_CHECK((n_chunks == 0 || row_qual) && (seq_capacity == 0 || qual), PV_ERR_INVALID, "row_qual or qual missing");
     PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = pv_pick_stream(ctx, stream);
     StitchArgs a;
@@ -261,9 +272,27 @@ extern "C" int pv_polish_stitch_dev(pv_ctx* ctx, const pv_polish_out* chunks, in
     pv_prof_scope ps_all(ctx, "polish_stitch", st);
     if (n_chunks > 0) { pv_prof_scope ps(ctx, "k_stitch_count", st); k_stitch_count<<<(unsigned)n_chunks, ST_THREADS, 0, st>>>(a); }
     k_stitch_scan<<<1, ST_SCAN_THREADS, 0, st>>>(a);
-    if (n_chunks > 0) { pv_prof_scope ps(ctx, "k_stitch_write", st); k_stitch_write<<<(unsigned)n_chunks, ST_THREADS, 0, st>>>(a); }
+    if (n_chunks > 0) {
+        pv_prof_scope ps(ctx, QUAL ? "k_stitch_write_qual" : "k_stitch_write", st);
+        k_stitch_write<QUAL><<<(unsigned)n_chunks, ST_THREADS, 0, st>>>(a, row_qual, qual);
+    }
     PV_HIP(hipGetLastError());
     return PV_OK;
+}
+
+extern "C" int pv_polish_stitch_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                                    const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap,
+                                    int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* d_counts, void* stream) {
+    return stitch_dev<false>(ctx, chunks, n_chunks, labels, nullptr, region_start, n_regions, seq_length, seq_overlap, region_off,
+                             seq, nullptr, seq_capacity, d_counts, stream);
+}
+
+extern "C" int pv_polish_stitch_qual_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                                         const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap,
+                                         int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* d_counts, void* stream,
+                                         const uint8_t* row_qual, uint8_t* qual) {
+    return stitch_dev<true>(ctx, chunks, n_chunks, labels, row_qual, region_start, n_regions, seq_length, seq_overlap, region_off,
+                            seq, qual, seq_capacity, d_counts, stream);
 }
 
 template <typename T>
@@ -274,10 +303,13 @@ static int stage(pv_ctx* ctx, const char* name, const T* src, size_t n, T** dst,
     return PV_OK;
 }
 
-extern "C" int pv_polish_stitch(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
-                                const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap,
-                                int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* counts) {
+// the host form of both stitches; QUAL: with the quality plane
+template <bool QUAL>
+static int stitch_host(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels, const uint8_t* row_qual,
+                       const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap, int64_t* region_off,
+                       uint8_t* seq, uint8_t* qual, int64_t seq_capacity, int64_t* counts) {
     PV_CHECK(ctx && chunks && region_off && counts, PV_ERR_INVALID, "null argument");
+    if (QUAL) PV_CHECK((n_chunks == 0 || row_qual) && (seq_capacity == 0 || qual), PV_ERR_INVALID, "row_qual or qual missing");
     PV_CHECK(n_chunks >= 0 && n_regions >= 0 && seq_capacity >= 0 && seq_length >= 1, PV_ERR_INVALID, "negative sizes");
     PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -288,8 +320,13 @@ extern "C" int pv_polish_stitch(pv_ctx* ctx, const pv_polish_out* chunks, int64_
     const uint8_t* d_lab = nullptr;
     const int64_t* d_rs = nullptr;
     int64_t *d_roff = nullptr, *d_counts = nullptr;
-    uint8_t* d_seq = nullptr;
+    uint8_t *d_seq = nullptr, *d_qual = nullptr;
+    const uint8_t* d_rq = nullptr;
     int rc;
+    if (QUAL) {
+        if ((rc = stage(ctx, "st.row_qual", row_qual, nc * L, (uint8_t**)&d_rq, st))) return rc;
+        if ((rc = pv_get(ctx, "st.qual", (size_t)(seq_capacity > 0 ? seq_capacity : 1), &d_qual))) return rc;
+    }
     if ((rc = stage(ctx, "st.position", chunks->position, nc * L, &d.position, st))) return rc;
     if ((rc = stage(ctx, "st.index", chunks->index, nc * L, &d.index, st))) return rc;
     if ((rc = stage(ctx, "st.region", chunks->region, nc, &d.region, st))) return rc;
@@ -299,8 +336,8 @@ extern "C" int pv_polish_stitch(pv_ctx* ctx, const pv_polish_out* chunks, int64_
     if ((rc = pv_get(ctx, "st.region_off", (size_t)n_regions + 1, &d_roff))) return rc;
     if ((rc = pv_get(ctx, "st.seq", (size_t)(seq_capacity > 0 ? seq_capacity : 1), &d_seq))) return rc;
     if ((rc = pv_get(ctx, "st.counts", (size_t)4, &d_counts))) return rc;
-    rc = pv_polish_stitch_dev(ctx, &d, n_chunks, d_lab, d_rs, n_regions, seq_length, seq_overlap, d_roff, d_seq, seq_capacity,
-                              d_counts, st);
+    rc = stitch_dev<QUAL>(ctx, &d, n_chunks, d_lab, d_rq, d_rs, n_regions, seq_length, seq_overlap, d_roff, d_seq, d_qual,
+                          seq_capacity, d_counts, st);
     if (rc) return rc;
     PV_HIP(hipMemcpyAsync(counts, d_counts, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     PV_HIP(hipMemcpyAsync(region_off, d_roff, ((size_t)n_regions + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -317,7 +354,23 @@ extern "C" int pv_polish_stitch(pv_ctx* ctx, const pv_polish_out* chunks, int64_
     PV_CHECK(status == PV_OK, (int)status, "stitch: device status %lld", (long long)status);
     if (counts[0] > 0) {
         PV_HIP(hipMemcpyAsync(seq, d_seq, (size_t)counts[0], hipMemcpyDeviceToHost, st));
+        if (QUAL) PV_HIP(hipMemcpyAsync(qual, d_qual, (size_t)counts[0], hipMemcpyDeviceToHost, st));
         PV_HIP(hipStreamSynchronize(st));
     }
     return PV_OK;
+}
+
+extern "C" int pv_polish_stitch(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                                const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap,
+                                int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* counts) {
+    return stitch_host<false>(ctx, chunks, n_chunks, labels, nullptr, region_start, n_regions, seq_length, seq_overlap, region_off,
+                              seq, nullptr, seq_capacity, counts);
+}
+
+extern "C" int pv_polish_stitch_qual(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                                     const int64_t* region_start, int32_t n_regions, int seq_length, int seq_overlap,
+                                     int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* counts,
+                                     const uint8_t* row_qual, uint8_t* qual) {
+    return stitch_host<true>(ctx, chunks, n_chunks, labels, row_qual, region_start, n_regions, seq_length, seq_overlap, region_off,
+                             seq, qual, seq_capacity, counts);
 }

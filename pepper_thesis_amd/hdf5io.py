@@ -516,3 +516,8 @@ class PolishPredictionStore:
         r = self.f.read
         return dict(position=np.asarray(r(base + "position"), dtype=np.int64), index=np.asarray(r(base + "index"), dtype=np.int64),
                     bases=np.asarray(r(base + "bases"), dtype=np.uint8))
+
+    def read_phred(self, contig: str, region: str, chunk: str):
+        """-> a chunk's phred_score as stored (any type and shape), None when the chunk has none"""
+        path = "%s/%s/%s/%s/phred_score" % (self._prediction_path_, contig, region, chunk)
+        return np.asarray(self.f.read(path)) if path in self.f else None

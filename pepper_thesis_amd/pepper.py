@@ -49,6 +49,10 @@ def call_consensus_parser(ap=None):
     ap.add_argument("-t", "--threads", type=int, default=8, help="accepted and ignored (there is no CPU path)")
     ap.add_argument("--bf16", action="store_true", default=False,
                     help="PV_DTYPE_BF16_INPUT_GEMM: matrix products on the bf16 MFMA with 3-term split operands")
+    ap.add_argument("--qualities", action="store_true", default=False,
+                    help="write every chunk's phred_score as the per-row Phred quality of its label (0..93, from P2's "
+                         "accumulated softmax; the rule in include/pepper_hip.h) instead of the reference's label table, for "
+                         "stitch --qualities")
     return ap
 
 
@@ -59,6 +63,9 @@ def stitch_parser(ap=None):
     ap.add_argument("-o", "--output_file", type=str, required=True,
                     help="output prefix: the FASTA is <output_file>_pepper_polished.fa (parent directories are created)")
     ap.add_argument("-t", "--threads", type=int, default=5, help="accepted and ignored (the stitch runs on the device)")
+    ap.add_argument("--qualities", action="store_true", default=False,
+                    help="also write <output_file>_pepper_polished.fq with one Phred byte per base, from the phred_score that "
+                         "call_consensus --qualities wrote")
     return ap
 
 

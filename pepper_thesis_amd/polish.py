@@ -9,10 +9,16 @@ prediction HDF5 files. Here each batch of regions goes through
 without leaving HBM; only the region offsets and the polished bases (one byte per base) come back to the host.
 
   python -m pepper_thesis_amd polish -b reads.bam -f draft.fa -m model.pkl -o out/polished [-t 5] [-r ctg:start-end] [--bf16]
-      [--realign] [--gpu_decode]
+      [--realign] [--gpu_decode] [--qualities]
 
 --gpu_decode (opt-in) replaces the first stage: reader threads only plan blocks and fetch draft bytes, and the BAM is inflated,
 decoded and clipped on the device (gpu_decode.py; _decoded_pieces below). Same FASTA.
+
+--qualities (opt-in, one device) also writes `<o>/_pepper_polished.fq`: the same contigs and sequences with one Phred byte
+per base. The chain then keeps P2's accumulated softmax, turns it into row qualities (pv_polish_row_qual_dev, the rule in
+include/pepper_hip.h: what predict_distributed_gpu.py:96-105 means to store, and Stitch.py:39-91 means to string up with
+`+33` and `base != 0`, both commented out there) and stitches them beside the bases (pv_polish_stitch_qual_dev); one more
+byte per base comes back. The FASTA is byte for byte the one of a run without the flag.
 
 Semantics kept from the reference:
   * regions: ImageGenerationUI.py:257-273 - for pos in range(start, end, 1000): [max(start, pos-100), min(end, pos+1100)],
@@ -102,6 +108,34 @@ def load_polish_model(model_path: str) -> dict:
     return sd
 
 
+def output_fastq_path(fasta_path: str) -> str:
+    """the FASTQ of --qualities lies beside the FASTA: ..._pepper_polished.fa -> ..._pepper_polished.fq"""
+    assert fasta_path.endswith(".fa"), fasta_path
+    return fasta_path[:-3] + ".fq"
+
+
+def write_fastq(path: str, seqs: Dict[str, bytes], quals: Dict[str, bytes]) -> None:
+    """one four-line record `@name / seq / + / qual+33` per contig with a non-empty sequence, in write_fasta's order; quals
+    hold raw Phred bytes 0..93. Written under a temporary name and renamed."""
+    tmp = path + ".partial"
+    try:
+        with open(tmp, "wb") as fh:
+            for contig in sorted(seqs, key=natural_key):
+                if seqs[contig]:
+                    q = np.frombuffer(quals[contig], np.uint8)
+                    if len(q) != len(seqs[contig]) or (len(q) and int(q.max()) > 93):
+                        raise ValueError("contig %s: %d qualities (max %d) for %d bases" % (contig, len(q), int(q.max(initial=0)),
+                                                                                            len(seqs[contig])))
+                    fh.write(b"@" + contig.encode() + b"\n" + seqs[contig] + b"\n+\n" + (q + 33).astype(np.uint8).tobytes() + b"\n")
+        os.replace(tmp, path)
+    except BaseException:
+        try:
+            os.remove(tmp)
+        except FileNotFoundError:
+            pass
+        raise
+
+
 def write_fasta(path: str, seqs: Dict[str, bytes]) -> None:
     with open(path, "w") as fh:
         for contig in sorted(seqs, key=natural_key):
@@ -160,12 +194,14 @@ def _contig_list(fasta, bam, region: Optional[str]):
 
 
 class _DeviceChain:
-    """device buffers of the builder -> GRU -> stitch chain, grown on demand"""
+    """device buffers of the builder -> GRU -> stitch chain, grown on demand. qualities: P2's accumulated softmax is kept,
+    turned into row qualities and stitched beside the bases; run / run_decoded then return (region_off, bases, qualities)."""
 
-    def __init__(self, ctx, own_ctx: bool = False):
+    def __init__(self, ctx, own_ctx: bool = False, qualities: bool = False):
         import torch
-        self.ctx, self.dev, self.own_ctx = ctx, "cuda:%d" % ctx.device_id, own_ctx
+        self.ctx, self.dev, self.own_ctx, self.qualities = ctx, "cuda:%d" % ctx.device_id, own_ctx, bool(qualities)
         self.dout = self.labels = self.seq = None
+        self.acc = self.row_qual = self.qual = None
         self.rout = None
         self.counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
 
@@ -180,6 +216,10 @@ class _DeviceChain:
             self.dout = DevicePolishOut(chunks, device=self.dev)
             self.labels = torch.zeros((chunks, 1000), dtype=torch.uint8, device=self.dev)
             self.seq = torch.zeros(chunks * 1000, dtype=torch.uint8, device=self.dev)
+            if self.qualities:
+                self.acc = torch.zeros((chunks, 1000, 5), dtype=torch.float32, device=self.dev)
+                self.row_qual = torch.zeros((chunks, 1000), dtype=torch.uint8, device=self.dev)
+                self.qual = torch.zeros(chunks * 1000, dtype=torch.uint8, device=self.dev)
             torch.cuda.synchronize()   # the fills ran on torch's stream; the chain runs on the context's
 
     def _summarize(self, batch, db, host_batch=None, sizes=None) -> int:
@@ -258,6 +298,12 @@ class _DeviceChain:
         poisoned); the chain of `call_consensus`"""
         return self.ctx.forward_p2(images)
 
+    def p2_labels_and_qualities(self, images: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """p2_labels plus the row qualities uint8 [B,1000] of every row (pv_polish_row_qual on the labels and the accumulated
+        softmax of the same call); the chain of `call_consensus --qualities`"""
+        labels, acc = self.ctx.forward_p2(images, want_acc=True)
+        return labels, self.ctx.polish_row_qual(labels, acc, seq_overlap=50)
+
     def build(self, batch, windows=None):
         """[realignment ->] builder for one batch of regions -> (device batch, n_chunks); the chunks are in self.dout.
         windows: the realignment window of every region (polish --realign), else None."""
@@ -292,12 +338,14 @@ class _DeviceChain:
         db, n = self.build_decoded(dec, windows)
         return self._labels_and_stitch(db, n, dec.n_regions)
 
-    def _labels_and_stitch(self, db, n: int, n_regions: int) -> Tuple[np.ndarray, bytes]:
+    def _labels_and_stitch(self, db, n: int, n_regions: int):
         region_off = np.zeros(n_regions + 1, np.int64)
         if n == 0:
-            return region_off, b""
+            return (region_off, b"", b"") if self.qualities else (region_off, b"")
         import torch
         roff = torch.empty(n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
+        if self.qualities:
+            return self._labels_and_stitch_qual(db, n, n_regions, roff)
         self.ctx.forward_p2_dev(self.dout.images.data_ptr(), n, self.labels.data_ptr())
         self.ctx.polish_stitch_dev(self.dout, n, self.labels.data_ptr(), db.t["ref_start"].data_ptr(), n_regions,
                                    roff.data_ptr(), self.seq.data_ptr(), self.seq.numel(), self.counts.data_ptr())
@@ -307,20 +355,38 @@ class _DeviceChain:
             raise _ffi.PepperHipError(status, "polisher stitch: device status %d (chunk %d)" % (status, bad))
         return roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes()
 
+    def _labels_and_stitch_qual(self, db, n: int, n_regions: int, roff):
+        """_labels_and_stitch with the quality plane: P2 keeps its accumulated softmax, the row-quality kernel reads it with
+        the labels, and the stitch carries the row qualities beside the bases"""
+        self.ctx.forward_p2_dev(self.dout.images.data_ptr(), n, self.labels.data_ptr(), self.acc.data_ptr())
+        # (a label above 4 is reported by the stitch where it is on a kept column, as without qualities: the counts of the row
+        # kernel are overwritten)
+        self.ctx.polish_row_qual_dev(self.labels.data_ptr(), self.acc.data_ptr(), n, self.row_qual.data_ptr(), self.counts.data_ptr(),
+                                     self.dout.seq_length, self.dout.seq_overlap)
+        self.ctx.polish_stitch_qual_dev(self.dout, n, self.labels.data_ptr(), self.row_qual.data_ptr(), db.t["ref_start"].data_ptr(),
+                                        n_regions, roff.data_ptr(), self.seq.data_ptr(), self.qual.data_ptr(), self.seq.numel(),
+                                        self.counts.data_ptr())
+        self.ctx.synchronize()
+        total, status, bad = (int(v) for v in self.counts[:3].tolist())
+        if status != _ffi.PV_OK:
+            raise _ffi.PepperHipError(status, "polisher stitch: device status %d (chunk %d)" % (status, bad))
+        return roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes(), self.qual[:total].cpu().numpy().tobytes()
 
-def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int) -> _DeviceChain:
+
+def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int, qualities: bool = False) -> _DeviceChain:
     """a context on `device` with the polisher weights loaded, and the chain on it (closing the chain closes the context).
     shared_device: other ranks use this GPU too, so the option is set before the first device call (the split GRU forms need
     co-resident workgroups and would time out, poisoning the labels). False leaves the create-time default (PV_SHARED_DEVICE).
     This is the default `open_chain` of run and polish_rank.run; CPU tests pass a stub with the same signature, whose result
-    has run(batch, windows) -> (region_off, bases) and close()."""
+    has run(batch, windows) -> (region_off, bases) and close(). qualities (passed only when set): the chain of --qualities,
+    whose run gives (region_off, bases, qualities)."""
     from .runtime import Context
     ctx = Context(device)
     try:
         if shared_device:
             ctx.set_option("shared_device", 1)
         ctx.load_p2(state_dict, dtype)
-        return _DeviceChain(ctx, own_ctx=True)
+        return _DeviceChain(ctx, own_ctx=True, qualities=qualities)
     except BaseException:
         ctx.close()
         raise
@@ -348,7 +414,7 @@ def _read_ahead(ex, fn, items, depth):
 
 
 def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int = 2048, threads: int = 5, realign: bool = False,
-                  timers: Optional[dict] = None, gpu_decode: bool = False, open_decoder=None):
+                  timers: Optional[dict] = None, gpu_decode: bool = False, open_decoder=None, qualities: bool = False):
     """the regions of `work` through the chain -> (contig, region start, region index, polished bases) for every region with
     reads, in `work` order. This is the whole device part of a run: the single-rank run passes every region, a rank of a
     multi-device run its share. chain.run(batch, windows) -> (region_off, bases) (_DeviceChain or a CPU test's stub).
@@ -356,9 +422,11 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
     gpu_decode: the device read path (_decoded_pieces): the reader threads only plan, the BAM is inflated, decoded and clipped
     on chain.ctx's device, and the chain takes the batches where they are (chain.run_decoded). open_decoder(T): the decoder,
     by default a gpu_decode.GpuDecoder with the polisher's settings (CPU tests pass a stub with its scan_groups, realize,
-    iterate and close)."""
+    iterate and close).
+    qualities: the chain's run gives (region_off, bases, qualities), and every piece carries its raw Phred bytes as a fifth
+    entry."""
     if gpu_decode:
-        yield from _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder)
+        yield from _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder, qualities)
         return
     from .batch import pack_regions
     from .bamio import BamHandler, FastaHandler
@@ -380,8 +448,10 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
     def flush(items):
         t0 = time.perf_counter()
         regs = [r for _, r in items]
-        roff, seq = chain.run(pack_regions(regs), [r.window for r in regs] if realign else None)
-        out = [(w.contig, w.start, w.index, seq[roff[g]:roff[g + 1]]) for g, (w, _) in enumerate(items)]
+        res = chain.run(pack_regions(regs), [r.window for r in regs] if realign else None)
+        roff = res[0]
+        out = [(w.contig, w.start, w.index) + tuple(p[roff[g]:roff[g + 1]] for p in res[1:2 + bool(qualities)])
+               for g, (w, _) in enumerate(items)]
         T["device_s"] += time.perf_counter() - t0
         T["batches"] += 1
         return out
@@ -404,7 +474,7 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
             yield from flush(pending)
 
 
-def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder):
+def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder, qualities=False):
     """polish_pieces' device read path. Reader threads plan reader groups (gpu_decode.region_groups: blocks, interval table,
     draft bytes, realign windows); the decoder's service thread scans them, cuts the regions with reads into the launches
     the host path makes (per_launch regions each) and fills them on its own stream; this thread runs the chain on every
@@ -446,11 +516,12 @@ def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timer
                 T["read_s"] += time.perf_counter() - t0
                 t0 = time.perf_counter()
                 for kind, b, windows, ws in parts:
-                    roff, seq = chain.run_decoded(b, windows) if kind == "dev" else chain.run(b, windows)
+                    res = chain.run_decoded(b, windows) if kind == "dev" else chain.run(b, windows)
+                    roff = res[0]
                     T["chain_runs"] += 1
                     T["regions"] += len(ws)
                     for g, w in enumerate(ws):
-                        yield w.contig, w.start, w.index, seq[roff[g]:roff[g + 1]]
+                        yield (w.contig, w.start, w.index) + tuple(p[roff[g]:roff[g + 1]] for p in res[1:2 + bool(qualities)])
                 T["device_s"] += time.perf_counter() - t0
                 T["batches"] += 1
                 del parts
@@ -471,11 +542,12 @@ def decode_report(T: dict) -> str:
 
 def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region: Optional[str] = None, batch_size: int = 2048,
                  threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None,
-                 realign: bool = False, chain=None, gpu_decode: bool = False) -> str:
+                 realign: bool = False, chain=None, gpu_decode: bool = False, qualities: bool = False) -> str:
     """-> path of the polished FASTA. batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
     realign: realign every read to the draft on the device before the builder, as the reference always does.
     chain: a chain with the weights already loaded (open_device_chain; the caller closes it), else one is made on `ctx`
-    (default: a context on device 0) from model_path. gpu_decode: polish_pieces' device read path."""
+    (default: a context on device 0) from model_path. gpu_decode: polish_pieces' device read path.
+    qualities: also write the FASTQ beside the FASTA (output_fastq_path); a chain passed in must have been made for it."""
     from .bamio import BamHandler, FastaHandler
     from .runtime import Context
     t_start = time.perf_counter()
@@ -486,17 +558,20 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
         if ctx is None:
             ctx = own = Context(0)
         ctx.load_p2(state_dict, dtype)
-        chain = _DeviceChain(ctx)
+        chain = _DeviceChain(ctx, qualities=qualities)
     try:
         fa, bm = FastaHandler(fasta), BamHandler(bam)
         work, T["bases_in"] = polish_work(fa, bm, region)
         out_path = output_fasta_path(out_prefix)
         log("POLISHING %d REGIONS, OUTPUT: %s" % (len(work), out_path))
-        pieces = list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode))
+        pieces = list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode,
+                                    qualities=qualities))
     finally:
         if own is not None:
             own.close()
-    seqs = write_polished_fasta(out_path, pieces)
+    seqs = write_polished_fasta(out_path, [p[:4] for p in pieces] if qualities else pieces)
+    if qualities:
+        write_fastq(output_fastq_path(out_path), seqs, merge_pieces(p[:3] + (p[4],) for p in pieces))
     T["bases_out"] = sum(len(s) for s in seqs.values())
     T["wall_s"] = time.perf_counter() - t_start
     if timers is not None:
@@ -517,6 +592,11 @@ def run(args, open_chain=open_device_chain) -> int:
     except ValueError as e:
         sys.stderr.write("ERROR: %s\n" % e)
         return 2
+    qualities = bool(getattr(args, "qualities", False))
+    if qualities and len(plan) > 1:
+        sys.stderr.write("ERROR: polish --qualities runs on one device (-d_ids %s lists %d): the quality plane is not carried "
+                         "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
+        return 2
     for what, path in (("BAM", args.bam), ("FASTA", args.fasta), ("MODEL", args.model_path)):
         if not os.path.isfile(path):
             sys.stderr.write("ERROR: CAN NOT LOCATE %s FILE.\n" % what)
@@ -531,15 +611,18 @@ def run(args, open_chain=open_device_chain) -> int:
         return 2
     if len(plan) > 1:
         return polish_rank.launch(args, plan)
-    chain = open_chain(device, False, state_dict, _ffi.PV_DTYPE_BF16_INPUT_GEMM if args.bf16 else _ffi.PV_DTYPE_F32)
+    dtype = _ffi.PV_DTYPE_BF16_INPUT_GEMM if args.bf16 else _ffi.PV_DTYPE_F32
+    chain = open_chain(device, False, state_dict, dtype, qualities=True) if qualities else open_chain(device, False, state_dict, dtype)
     try:
         T = {}
         path = polish_fused(args.bam, args.fasta, args.model_path, args.output_file, args.region, args.batch_size, args.threads,
                             timers=T, realign=bool(getattr(args, "realign", False)), chain=chain,
-                            gpu_decode=bool(getattr(args, "gpu_decode", False)))
+                            gpu_decode=bool(getattr(args, "gpu_decode", False)), qualities=qualities)
     finally:
         chain.close()
     if decode_report(T):
         log(decode_report(T))
     log("POLISHED FASTA: %s (%d REGIONS, %d BASES IN %.2f SEC)" % (path, T["regions"], T["bases_out"], T["wall_s"]))
+    if qualities:
+        log("POLISHED FASTQ: " + output_fastq_path(path))
     return 0

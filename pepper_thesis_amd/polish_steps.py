@@ -11,8 +11,11 @@ machines, be kept, be re-stitched, or be handed to / taken from the reference's 
                   group, in sorted name order; file i goes to caller i % callers; a caller runs pv_rnn_forward_p2 on launches
                   of up to -bs chunks and writes the labels as `bases` and the reference's phred_score. Several -d_ids start
                   one rank per id (polish_rank's plan, launcher and supervisor); a repeated id gets `_<rank>` on later ranks.
+                  --qualities: phred_score holds the row qualities instead (pv_polish_row_qual: every row, 0..93).
   stitch:         prediction files -> <output_file>_pepper_polished.fa (perform_stitch.py:39-84, Stitch.py:37-128). Every
                   contig's regions gathered from all files, laid out as pv_polish_stitch requires and stitched by that kernel.
+                  --qualities: phred_score is stitched beside the bases (pv_polish_stitch_qual) into
+                  <output_file>_pepper_polished.fq, the FASTQ of `polish --qualities`.
 
 Every file is written under a temporary name and renamed when complete; a failing step leaves nothing under a final name.
 """
@@ -195,9 +198,10 @@ def prediction_path(out_dir: str, plan, rank: int) -> str:
     return os.path.join(out_dir, "pepper_prediction_%d%s.hdf" % (d, "_%d" % rank if repeat else ""))
 
 
-def call_share(files: List[str], out_path: str, caller, batch_size: int) -> int:
+def call_share(files: List[str], out_path: str, caller, batch_size: int, qualities: bool = False) -> int:
     """one caller: the chunks of `files` (file order, chunk groups in name order) through caller.p2_labels in launches of up to
-    batch_size -> the prediction file at out_path; -> chunks written (no file when there are none)"""
+    batch_size -> the prediction file at out_path; -> chunks written (no file when there are none).
+    qualities: caller.p2_labels_and_qualities instead, and phred_score holds the row qualities, not the reference's table"""
     from .hdf5io import PolishImageStore, PolishPredictionStore
     tmp = out_path + ".partial"
     store = PolishPredictionStore(tmp, "w")
@@ -207,10 +211,19 @@ def call_share(files: List[str], out_path: str, caller, batch_size: int) -> int:
 
         def flush():
             images = np.stack([c["image"] for _, c in pending])
-            labels = np.asarray(caller.p2_labels(images))
+            if qualities:
+                try:
+                    labels, phred = (np.asarray(a) for a in caller.p2_labels_and_qualities(images))
+                except _ffi.PepperHipError as e:
+                    if e.code != _ffi.PV_ERR_STATE:
+                        raise
+                    raise _ffi.PepperHipError(_ffi.PV_ERR_STATE, "P2 labels outside 0..4 for chunks of %s" % pending[0][0]) from None
+            else:
+                labels = np.asarray(caller.p2_labels(images))
             if labels.shape != images.shape[:2] or labels.max(initial=0) > 4:   # a poisoned P2 call is never written
                 raise _ffi.PepperHipError(_ffi.PV_ERR_STATE, "P2 labels outside 0..4 for chunks of %s" % pending[0][0])
-            phred = phred_scores(labels)
+            if not qualities:
+                phred = phred_scores(labels)
             for k, (_, c) in enumerate(pending):
                 store.write_prediction(c["contig"], c["region_start"], c["region_end"], c["chunk_id"], c["position"],
                                        c["index"], labels[k], phred[k])
@@ -261,7 +274,7 @@ def call_consensus_rank(args, plan, rank: int, open_caller=None, state_dict=None
         t0 = time.perf_counter()
         caller = open_caller(me.device, me.shared_device, state_dict, dtype)
         try:
-            n = call_share(files, out_path, caller, args.batch_size)
+            n = call_share(files, out_path, caller, args.batch_size, bool(getattr(args, "qualities", False)))
         finally:
             caller.close()
     except Exception as e:
@@ -278,6 +291,8 @@ def consensus_argv(args) -> List[str]:
         argv += ["-d_ids", args.device_ids]
     if args.bf16:
         argv.append("--bf16")
+    if getattr(args, "qualities", False):
+        argv.append("--qualities")
     return argv
 
 
@@ -355,10 +370,12 @@ class StitchLayout(NamedTuple):
     region_start: np.ndarray  # int64 [n_regions]
     regions: List[RegionRef]
     chunk_names: List[str]    # [n] the group name of every chunk, for messages
+    row_qual: Optional[np.ndarray] = None   # uint8 [n, L] the chunks' phred_score (stitch --qualities)
 
 
-def _region_chunks(s, ref: RegionRef):
-    """a region's chunks in id order 0..k -> [(name, chunk)]; a gap in the ids or a name that is no id is refused"""
+def _region_chunks(s, ref: RegionRef, qualities: bool = False):
+    """a region's chunks in id order 0..k -> [(name, chunk)]; a gap in the ids or a name that is no id is refused.
+    qualities: every chunk also holds its phred_score; one that is missing or not uint8 [SEQ_LENGTH] is refused"""
     names = s.chunk_names(ref.contig, ref.name)
     ids = []
     for nm in names:
@@ -369,12 +386,22 @@ def _region_chunks(s, ref: RegionRef):
     for want, k in enumerate(order):
         if ids[k] != want:
             raise ValueError("%s: region %s: chunk ids %s have a gap at %d" % (ref.path, ref.name, sorted(ids), want))
-    return [(names[k], s.read_chunk(ref.contig, ref.name, names[k])) for k in order]
+    out = [(names[k], s.read_chunk(ref.contig, ref.name, names[k])) for k in order]
+    if qualities:
+        for name, c in out:
+            q = s.read_phred(ref.contig, ref.name, name)
+            if q is None or q.dtype != np.uint8 or q.shape != (SEQ_LENGTH,):
+                raise ValueError("%s: chunk %s/%s/%s: %s; stitch --qualities needs the uint8 [%d] phred_score of "
+                                 "call_consensus --qualities"
+                                 % (ref.path, ref.contig, ref.name, name,
+                                    "no phred_score" if q is None else "phred_score is %s %s" % (q.dtype, list(q.shape)), SEQ_LENGTH))
+            c["phred_score"] = q
+    return out
 
 
-def stitch_layouts(regions: List[RegionRef], max_chunks: int = STITCH_CHUNKS):
+def stitch_layouts(regions: List[RegionRef], max_chunks: int = STITCH_CHUNKS, qualities: bool = False):
     """the regions of one contig (sorted) -> StitchLayout per launch of up to max_chunks chunks (more only for a region that is
-    larger on its own), split at region boundaries"""
+    larger on its own), split at region boundaries. qualities: the layouts carry row_qual"""
     from .hdf5io import PolishPredictionStore
     stores: Dict[str, PolishPredictionStore] = {}
     try:
@@ -383,21 +410,22 @@ def stitch_layouts(regions: List[RegionRef], max_chunks: int = STITCH_CHUNKS):
         for ref in regions:
             if ref.path not in stores:
                 stores[ref.path] = PolishPredictionStore(ref.path)
-            chunks = _region_chunks(stores[ref.path], ref)
+            chunks = _region_chunks(stores[ref.path], ref, qualities)
             if group and size + len(chunks) > max_chunks:
-                yield _layout(group)
+                yield _layout(group, qualities)
                 group, size = [], 0
             group.append((ref, chunks))
             size += len(chunks)
         if group:
-            yield _layout(group)
+            yield _layout(group, qualities)
     finally:
         for s in stores.values():
             s.close()
 
 
-def _layout(group) -> StitchLayout:
+def _layout(group, qualities: bool = False) -> StitchLayout:
     n = sum(len(c) for _, c in group)
+    rq = np.empty((n, SEQ_LENGTH), np.uint8) if qualities else None
     pos = np.empty((n, SEQ_LENGTH), np.int64)
     idx = np.empty((n, SEQ_LENGTH), np.int32)
     lab = np.empty((n, SEQ_LENGTH), np.uint8)
@@ -412,35 +440,44 @@ def _layout(group) -> StitchLayout:
             if c["index"].size and (c["index"].min() < INT32_MIN or c["index"].max() > INT32_MAX):
                 raise ValueError("%s: region %s, chunk %s: index beyond int32" % (ref.path, ref.name, name))
             pos[k], idx[k], lab[k] = c["position"], c["index"], c["bases"]
+            if qualities:
+                rq[k] = c["phred_score"]
             region[k], chunk_id[k] = g, cid
             names.append("%s/%s/%s" % (ref.contig, ref.name, name))
             k += 1
     return StitchLayout(pos, idx, region, chunk_id, lab, np.array([r.start for r, _ in group], np.int64), [r for r, _ in group],
-                        names)
+                        names, rq)
 
 
-def stitch_layout_bases(ctx, lay: StitchLayout) -> List[bytes]:
+def stitch_layout_bases(ctx, lay: StitchLayout, qualities: bool = False):
     """pv_polish_stitch on one layout -> the polished bases of every region. A kept label above 4 is refused by the kernel
-    (PV_ERR_STATE) and reported with the chunk it is in."""
+    (PV_ERR_STATE) and reported with the chunk it is in.
+    qualities: pv_polish_stitch_qual with the layout's row_qual -> (bases, raw Phred bytes) of every region."""
     import ctypes as C
     from .polish_summary import PolishOut
     counts = (C.c_int64 * 4)()
     out = PolishOut(None, lay.position, lay.index, lay.region, lay.chunk_id)
     try:
-        roff, seq = ctx.polish_stitch(out, lay.labels, lay.region_start, counts=counts)
+        if qualities:
+            roff, seq, qual = ctx.polish_stitch_qual(out, lay.labels, lay.row_qual, lay.region_start, counts=counts)
+        else:
+            roff, seq = ctx.polish_stitch(out, lay.labels, lay.region_start, counts=counts)
     except _ffi.PepperHipError as e:
         bad = int(counts[2])
         if e.code == _ffi.PV_ERR_STATE and 0 <= bad < len(lay.chunk_names):
             ref = lay.regions[int(lay.region[bad])]
             raise ValueError("%s: chunk %s holds a label above 4" % (ref.path, lay.chunk_names[bad])) from None
         raise
+    if qualities:
+        return [(seq[roff[g]:roff[g + 1]], qual[roff[g]:roff[g + 1]]) for g in range(len(lay.regions))]
     return [seq[roff[g]:roff[g + 1]] for g in range(len(lay.regions))]
 
 
-def stitch(input_dir: str, output_file: str, ctx=None) -> str:
+def stitch(input_dir: str, output_file: str, ctx=None, qualities: bool = False) -> str:
     """-> path of the polished FASTA. ctx: a context (made on device 0 at the first launch when None). The FASTA is written
-    only after every contig stitched."""
-    from .polish import write_fasta
+    only after every contig stitched. qualities: and the FASTQ beside it (polish.output_fastq_path), before the FASTA."""
+    from .polish import output_fastq_path, write_fasta, write_fastq
+    quals: Dict[str, bytes] = {}
     files = hdf_files(input_dir)
     by = gather_regions(files)
     own = None
@@ -449,11 +486,14 @@ def stitch(input_dir: str, output_file: str, ctx=None) -> str:
         for contig in sorted(by, key=natural_key):
             log("PROCESSING CONTIG: " + contig)
             parts: List[bytes] = []
-            for lay in stitch_layouts(by[contig]):
+            for lay in stitch_layouts(by[contig], qualities=qualities):
                 if ctx is None:
                     from .runtime import Context
                     ctx = own = Context(0)
-                parts += stitch_layout_bases(ctx, lay)
+                parts += stitch_layout_bases(ctx, lay, qualities)
+            if qualities:
+                quals[contig] = b"".join(q for _, q in parts)
+                parts = [s for s, _ in parts]
             seqs[contig] = b"".join(parts)
             log("FINISHED PROCESSING %s, POLISHED SEQUENCE LENGTH: %d." % (contig, len(seqs[contig])))
     finally:
@@ -461,6 +501,8 @@ def stitch(input_dir: str, output_file: str, ctx=None) -> str:
             own.close()
     path = output_file + "_pepper_polished.fa"
     Path(path).resolve().parent.mkdir(parents=True, exist_ok=True)
+    if qualities:
+        write_fastq(output_fastq_path(path), seqs, quals)
     write_fasta(path + ".partial", seqs)
     os.replace(path + ".partial", path)
     return path
@@ -471,7 +513,7 @@ def stitch_run(args, ctx=None) -> int:
         sys.stderr.write("ERROR: CAN NOT LOCATE INPUT DIRECTORY.\n")
         return 1
     try:
-        path = stitch(args.input_dir, args.output_file, ctx)
+        path = stitch(args.input_dir, args.output_file, ctx, bool(getattr(args, "qualities", False)))
     except (ValueError, _ffi.PepperHipError) as e:
         sys.stderr.write("ERROR: stitch: %s; no FASTA written.\n" % e)
         return 1

@@ -368,6 +368,59 @@ class Context:
                                              seq_overlap, _ffi.ptr(region_off), _ffi.ptr(seq), cap, counts))
         return region_off, seq[:int(counts[0])].tobytes()
 
+    def polish_row_qual_dev(self, d_labels: int, d_acc: int, B: int, d_qual: int, d_counts: int, seq_length: int = 1000,
+                            seq_overlap: int = 50, stream: int = 0):
+        """asynchronous, device-resident row qualities (pv_polish_row_qual_dev): labels uint8 [B,L] and acc float [B,L,5] of
+        forward_p2_dev -> qual uint8 [B,L]; {rows, status, first bad chunk, its first bad row} in d_counts."""
+        _ffi.check(self.lib.pv_polish_row_qual_dev(self.handle, d_labels, d_acc, int(B), int(seq_length), int(seq_overlap), d_qual,
+                                                   d_counts, stream or None))
+
+    def polish_row_qual(self, labels: np.ndarray, acc: np.ndarray, seq_overlap: int = 50, counts=None) -> np.ndarray:
+        """host-buffer row qualities (pv_polish_row_qual): labels uint8 [B,L], acc float32 [B,L,5] -> qual uint8 [B,L].
+        A label above 4 raises PepperHipError(PV_ERR_STATE). counts: optional ctypes int64[4], filled also when the call raises."""
+        lab = np.ascontiguousarray(labels, np.uint8)
+        a = np.ascontiguousarray(acc, np.float32)
+        assert lab.ndim == 2 and a.shape == lab.shape + (5,), (lab.shape, a.shape)
+        qual = np.zeros(lab.shape, np.uint8)
+        if counts is None:
+            counts = (C.c_int64 * 4)()
+        _ffi.check(self.lib.pv_polish_row_qual(self.handle, _ffi.ptr(lab), _ffi.ptr(a), lab.shape[0], lab.shape[1], int(seq_overlap),
+                                               _ffi.ptr(qual), counts))
+        return qual
+
+    def polish_stitch_qual_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_row_qual: int, d_region_start: int,
+                               n_regions: int, d_region_off: int, d_seq: int, d_qual: int, seq_capacity: int, d_counts: int,
+                               stream: int = 0):
+        """polish_stitch_dev with the quality plane (pv_polish_stitch_qual_dev): d_row_qual uint8 [n_chunks, L] in, d_qual
+        uint8 [seq_capacity] out, one raw Phred byte for every base of d_seq."""
+        _ffi.check(self.lib.pv_polish_stitch_qual_dev(
+            self.handle, C.byref(dout.c), int(n_chunks), d_labels, d_region_start, int(n_regions), dout.seq_length,
+            dout.seq_overlap, d_region_off, d_seq, int(seq_capacity), d_counts, stream or None, d_row_qual, d_qual))
+
+    def polish_stitch_qual(self, out, labels: np.ndarray, row_qual: np.ndarray, region_start: np.ndarray, seq_capacity: int = None,
+                           seq_length: int = 1000, seq_overlap: int = 50, counts=None):
+        """polish_stitch with the quality plane (pv_polish_stitch_qual) -> (region_off, seq bytes, qual bytes: raw Phred)."""
+        n = int(len(out.chunk_id))
+        c = _ffi.pv_polish_out()
+        keep = [np.ascontiguousarray(out.position, np.int64), np.ascontiguousarray(out.index, np.int32),
+                np.ascontiguousarray(out.region, np.int32), np.ascontiguousarray(out.chunk_id, np.int32)]
+        c.chunk_capacity = n
+        c.position, c.index, c.region, c.chunk_id = (_ffi.ptr(a) for a in keep)
+        lab = np.ascontiguousarray(labels, np.uint8)
+        rq = np.ascontiguousarray(row_qual, np.uint8)
+        rs = np.ascontiguousarray(region_start, np.int64)
+        assert lab.shape == (n, seq_length) and rq.shape == lab.shape, (lab.shape, rq.shape)
+        cap = n * seq_length if seq_capacity is None else int(seq_capacity)
+        region_off = np.zeros(len(rs) + 1, np.int64)
+        seq = np.zeros(max(cap, 1), np.uint8)
+        qual = np.zeros(max(cap, 1), np.uint8)
+        if counts is None:
+            counts = (C.c_int64 * 4)()
+        _ffi.check(self.lib.pv_polish_stitch_qual(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rs), len(rs), seq_length,
+                                                  seq_overlap, _ffi.ptr(region_off), _ffi.ptr(seq), cap, counts, _ffi.ptr(rq),
+                                                  _ffi.ptr(qual)))
+        return region_off, seq[:int(counts[0])].tobytes(), qual[:int(counts[0])].tobytes()
+
     def profile_begin(self, only: str = None):
         """bracket every kernel launch of this context with HIP events (only: just the kernels whose profile name starts
         with it - two events per launch put a few microseconds between kernels)"""

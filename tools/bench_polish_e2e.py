@@ -24,8 +24,12 @@
 
   --gpu_decode: the e2e leg reads the BAM through `polish --gpu_decode` (inflate, record decode and clipping on the device).
 
+  --qualities: the e2e leg runs in one process on the same files, without and with `polish --qualities` (the FASTQ beside
+              the FASTA) in turn, twice each, then once more each way with the stitch and the row-quality calls bracketed by HIP events: what
+              the flag adds on the device (pv_polish_row_qual_dev, the quality plane of the stitch) and on the wall.
+
   python tools/bench_polish_e2e.py [--leg stitch|e2e|steps|all] [--mbp 2.0] [--reps 20] [--realign] [--d_ids 0,0] [--gpu_decode]
-                                   [--out f]
+                                   [--qualities] [--out f]
 For the rocprofv3 row run the stitch leg alone under `rocprofv3 --kernel-trace --stats -d <dir> -- python ... --leg stitch`.
 """
 import argparse
@@ -113,9 +117,11 @@ def stitch_leg(reps=20):
                                      "stitch_ms": round(t_host * 1e3, 1)}}
 
 
-def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False):
+def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False, qualities=False):
     # warm-up on a small region (code objects, allocator), then the timed run
     kw = {"gpu_decode": True} if gpu_decode else {}
+    if qualities:
+        kw["qualities"] = True
     polish.polish_fused(bam, fa, model, out + "_warm", region="chr20:0-50000", threads=threads, ctx=ctx, realign=realign, **kw)
     T = {}
     t0 = time.perf_counter()
@@ -126,6 +132,9 @@ def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decod
            "polished_bp": T["bases_out"], "fasta_bytes": size, "wall_s": round(wall, 3),
            "read_s": round(T["read_s"], 3), "device_s": round(T["device_s"], 3),
            "draft_mbp_per_s": round(T["bases_in"] / wall / 1e6, 4), "reader_threads": threads}
+    if qualities:
+        fq = polish.output_fastq_path(path)
+        res["qualities"], res["fastq_bytes"] = True, os.path.getsize(fq)
     if gpu_decode:
         import hashlib
         import torch
@@ -190,6 +199,51 @@ def realign_stats(ctx, bam, fa, per_launch=1024):
             "band_cells_upper_bound": band,
             "score_gcups": round((fwd + rev) / (score_ms * 1e-3) / 1e9, 1) if score_ms else None,
             "band_gcups": round(band / (band_ms * 1e-3) / 1e9, 1) if band_ms else None}
+
+
+def _quality_events(polish, ctx, bam, fa, model, out, threads, qualities):
+    """one more run with the calls whose profile names start with polish_ bracketed by HIP events -> {name: [ms, launches]}"""
+    ctx.profile_begin("polish_")
+    try:
+        polish.polish_fused(bam, fa, model, out, threads=threads, ctx=ctx, qualities=qualities)
+    finally:
+        pr = ctx.profile_end()
+    return {k: [round(v[0], 4), v[1]] for k, v in sorted(pr.items()) if k in ("polish_stitch", "polish_row_qual")}
+
+
+def qualities_leg(mbp=3.0, threads=16):
+    """polish without and with --qualities on one synthetic contig, in one process on the same files"""
+    import hashlib
+    import numpy as np
+    from bench_filepath import make_files
+    from pepper_thesis_amd import polish, runtime, synth
+    d = tempfile.mkdtemp(prefix="pv_polish_qual_")
+    try:
+        bam, fa, info = make_files(d, int(mbp * 1_000_000))
+        model = os.path.join(d, "model.npz")
+        np.savez(model, **synth.make_weights_p2(4321, 3.0))
+        ctx = runtime.Context(0)
+        try:
+            # the two forms alternate, twice each: the first timed run of a process also grows the workspace to the launch size
+            runs = []
+            for k in range(2):
+                for q in (False, True):
+                    r = _e2e_run(polish, ctx, bam, fa, model, os.path.join(d, "qual" if q else "plain"), threads, False, info,
+                                 qualities=q)
+                    runs.append(dict(r, qualities=q, order=len(runs)))
+            res = {"runs": runs, "without_qualities": runs[2], "with_qualities": runs[3]}
+            sha = [hashlib.sha256(open(os.path.join(d, n, "_pepper_polished.fa"), "rb").read()).hexdigest() for n in ("plain", "qual")]
+            res["fasta_identical"] = sha[0] == sha[1]
+            res["event_ms_launches"] = {
+                "without_qualities": _quality_events(polish, ctx, bam, fa, model, os.path.join(d, "plain_ev"), threads, False),
+                "with_qualities": _quality_events(polish, ctx, bam, fa, model, os.path.join(d, "qual_ev"), threads, True)}
+            res["note"] = ("polish_stitch: count + scan + write kernels of one stitch call; polish_row_qual: the row kernel and its "
+                           "status kernel; HIP events around every call of a run, summed over the run's launches")
+            return res
+        finally:
+            ctx.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
 
 
 def e2e_leg(mbp=2.0, threads=16, realign=False, gpu_decode=False):
@@ -316,13 +370,18 @@ def main():
                     help="e2e leg: the polish command with these -d_ids against the first id alone with PV_SHARED_DEVICE=1")
     ap.add_argument("--gpu_decode", action="store_true",
                     help="e2e leg: the device read path (polish --gpu_decode); adds the decode timers and the FASTA's sha256")
+    ap.add_argument("--qualities", action="store_true",
+                    help="e2e leg without and with polish --qualities, plus HIP-event times of the stitch and row-quality calls")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON to this file")
     a = ap.parse_args()
     out = {}
     if a.leg in ("stitch", "all"):
         out["stitch"] = stitch_leg(a.reps)
     if a.leg in ("e2e", "all"):
-        out["e2e"] = ranks_leg(a.mbp, a.threads, a.d_ids, a.realign) if a.d_ids else e2e_leg(a.mbp, a.threads, a.realign, a.gpu_decode)
+        if a.qualities:
+            out["e2e"] = qualities_leg(a.mbp, a.threads)
+        else:
+            out["e2e"] = ranks_leg(a.mbp, a.threads, a.d_ids, a.realign) if a.d_ids else e2e_leg(a.mbp, a.threads, a.realign, a.gpu_decode)
     if a.leg == "steps":
         out["steps"] = steps_leg(a.mbp, a.threads)
     print(json.dumps(out, indent=1))
