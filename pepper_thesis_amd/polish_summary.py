@@ -2,7 +2,7 @@
 
 Host-side mirror of ``PEPPER.SummaryGenerator`` (pybind11, pepper/modules/src/pileup_summary/summary_generator.cpp:6-12,
 371-392) and ``AlignmentSummarizer.chunk_images`` (pepper/modules/python/AlignmentSummarizer.py:19-56). All arithmetic
-runs in the HIP kernels of csrc/summary_kernels.hip (``k_polish_*``) through ``pv_polish_summarize_regions``; nothing
+runs in the HIP kernels of csrc/summary_polish.hip (``k_polish_*``) through ``pv_polish_summarize_regions``; nothing
 here computes pixels.
 """
 import ctypes as C

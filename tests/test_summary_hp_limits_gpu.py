@@ -266,7 +266,7 @@ def test_overlay_counts_clamped_and_packed_per_group(hip_ctx, oracle_lib):
     """one candidate per region (SNP, insert, delete: t = 1, 2, 3) whose observations in one (strand x set) group are 124,
     125, 126, 255, 256 or 300, the other groups 3, 5 and 7 plus the untagged reads of the big group (they join both sets),
     and reads tagged 3 / -1 (no group). k_site_alleles clamps each group count to 125 and packs the four into one int32;
-    k_write_windows_hp unpacks them onto planes 4+t, 26+t (forward set 1 / 2) and 15+t, 37+t (reverse set 1 / 2) of the
+    k_write_windows<true> unpacks them onto planes 4+t, 26+t (forward set 1 / 2) and 15+t, 37+t (reverse set 1 / 2) of the
     middle row"""
     regs, counts = cases.hp_overlay_batch_regions()
     o = _exact(hip_ctx, oracle_lib, pack_regions(regs), P_HP, "overlay clamp")
