@@ -513,8 +513,8 @@ int pv_gather_counts(pv_ctx* ctx, pv_comm* comm, int64_t n_rows, int64_t* counts
  * *ms (optional) receives the kernel's duration. Has no counterpart in the reference. */
 int pv_debug_gemm_bf16x3(pv_ctx* ctx, const float* A, const float* W, const float* bias, int64_t M, int N, int K,
                          int splits, int quads, float* C, float* ms);
-/* The same through the 6-term GEMM of the PV_DTYPE_F32 split-6 chain (fp32 operands split into three bf16 pieces on the device),
- * same arguments and shape rules. */
+/* The same through the 6-term GEMM of the PV_DTYPE_F32 split-6 chain (A split into three bf16 pieces on the device, W on the
+ * host before the upload, as the model load does), same arguments and shape rules. */
 int pv_debug_gemm_bf16x6(pv_ctx* ctx, const float* A, const float* W, const float* bias, int64_t M, int N, int K,
                          int splits, int quads, float* C, float* ms);
 

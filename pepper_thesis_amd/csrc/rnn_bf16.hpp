@@ -11,6 +11,8 @@
 
 // C = A . W^T (+ bias) through k_gemm_bf16x3. A [M][K], W [N][K] in "split8" rows (per 8 elements: 8 bf16 hi, 8 bf16 lo);
 // C [splits][M][N] fp32 row-major, or (quads) [M/4][N][4]. M % 4 == 0, N % 256 == 0, K % (32 * splits) == 0.
+// terms = 6 (k_gemm_bf16x6): A [M][K] plain fp32 rows; W three bf16 planes [3][N][K], w = x0 + x1 + x2 (split3_planes,
+// split3_host.hpp), made once on the host.
 struct pv_gemm_desc {
     const unsigned char* A;
     const unsigned char* W;
@@ -19,7 +21,7 @@ struct pv_gemm_desc {
     int64_t M;
     int N, K, splits, quads;
     const char* prof_name;
-    int terms;   // 0 / 3: split8 operands, 3-term products; 6: plain fp32 operands, 6-term products (split in registers)
+    int terms;   // 0 / 3: split8 operands, 3-term products; 6: fp32 A (split in registers) and pre-split W planes, 6-term products
 };
 int pv_gemm_bf16x3_async(pv_ctx* ctx, const pv_gemm_desc& g, hipStream_t st);                       // rnn_kernels.hip
 int pv_gemm_bf16x3_prepare();                                                                       // function attributes (once per load)

@@ -22,6 +22,7 @@
 #include "pv_common.hpp"
 #include "mfma_tiles.hpp"
 #include "rnn_bf16.hpp"
+#include "split3_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -761,12 +762,12 @@ __global__ __launch_bounds__(256, 1) void k_head_tail(TailArgs a) {
 // the recurrent h-part, the cell update and linear_2..5 stay fp32.
 struct GemmArgs {
     const unsigned char* A;  // activations, split8 rows of K*4 bytes, [M][K] (k_gemm_bf16x6: fp32 rows)
-    const unsigned char* W;  // weights, split8 rows, [N][K] (k_gemm_bf16x6: fp32 rows)
+    const unsigned char* W;  // weights, split8 rows, [N][K] (k_gemm_bf16x6: three bf16 planes [3][N][K], split3_host.hpp)
     const float* bias;    // [N] or NULL
     float* C;             // [splits][M][N] row-major, or (c_quads) [M/4][N][4]: four consecutive rows of a column adjacent
     int64_t M;
     int N, K, splits;
-    int tiles_m, tiles_n; // 256 x 256 output tiles
+    int tiles_m, tiles_n; // 256 x 256 output tiles (k_gemm_bf16x6: 256 x 128)
     int items;            // tiles_m * tiles_n * splits work items, walked by persistent workgroups
     int c_quads;
     const unsigned* iota; // [1024] = 0 .. 1023: the source of the completion-flag transfers (below)
@@ -795,15 +796,9 @@ __device__ unsigned long long g_gemm_stamps[8];
 #else
 #define GSTAMP(i)
 #endif
-// TERMS = 6 (k_gemm_bf16x6, PV_DTYPE_F32 split-6 chain): A and W are plain fp32 rows [M][K] / [N][K]. An fp32 8-group is 32
-// bytes like a split8 group, so the transfers and the LDS image are byte for byte those of the 3-term form: the "hi" image
-// holds elements 0..3 of every 8-group, the "lo" image elements 4..7. Each wave reads its 8 + 4 fragments as fp32, splits
-// them into three bf16 pieces in registers (split3_bf16) and runs six MFMAs per output tile: a0.b0 + a0.b1 + a1.b0 + a1.b1
-// + a0.b2 + a2.b0 (the dropped a1.b2, a2.b1, a2.b2 are below 2^-24 relative). The LDS image stays 128 KB; the cost of the
-// third piece is VALU work that issues between the MFMAs.
-template <int TERMS>
+// (gemm6_body below repeats the item walk, the flag completion, the bias transfer and both epilogues for its own tile shape: a fix
+// to that machinery belongs in both)
 __device__ __forceinline__ void gemm_body(const GemmArgs& g) {
-    static_assert(TERMS == 3 || TERMS == 6, "3-term (split8 operands) or 6-term (fp32 operands)");
     constexpr int BM = PV_GEMM_TILE, BN = PV_GEMM_TILE, BK = 32;
     constexpr int ARR = BM * BK * 2;          // bytes of one bf16 operand image (16 KB); buffer = [A_hi | A_lo | W_hi | W_lo]
     extern __shared__ __attribute__((aligned(16))) unsigned char smg[];
@@ -959,29 +954,17 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g) {
             {
                 const unsigned ch16 = (unsigned)((((lane >> 4)) ^ (((lane & 15) >> 2) & 3)) * 16);
                 const unsigned fa16 = (unsigned)((128 * wr + (lane & 15)) * 64), fb16 = (unsigned)(2 * ARR + (64 * wc + (lane & 15)) * 64);
-                // TERMS = 3: {hi, lo} pieces; TERMS = 6: {x0, x1, x2} split from the fp32 image
-                constexpr int NP = TERMS == 6 ? 3 : 2;
-                bf16x8 bp[NP][4];
+                bf16x8 bp[2][4];   // {hi, lo} pieces
 #pragma unroll
                 for (int ni = 0; ni < 4; ni++) {
-                    if constexpr (TERMS == 6) {
-                        split3_bf16(*reinterpret_cast<const f32x4*>(base + fb16 + ni * 16 * 64 + ch16),
-                                    *reinterpret_cast<const f32x4*>(base + ARR + fb16 + ni * 16 * 64 + ch16), bp[0][ni], bp[1][ni], bp[2][ni]);
-                    } else {
-                        bp[0][ni] = *reinterpret_cast<const bf16x8*>(base + fb16 + ni * 16 * 64 + ch16);
-                        bp[1][ni] = *reinterpret_cast<const bf16x8*>(base + ARR + fb16 + ni * 16 * 64 + ch16);
-                    }
+                    bp[0][ni] = *reinterpret_cast<const bf16x8*>(base + fb16 + ni * 16 * 64 + ch16);
+                    bp[1][ni] = *reinterpret_cast<const bf16x8*>(base + ARR + fb16 + ni * 16 * 64 + ch16);
                 }
 #pragma unroll
                 for (int mi = 0; mi < 8; mi++) {
-                    bf16x8 ap[NP];
-                    if constexpr (TERMS == 6) {
-                        split3_bf16(*reinterpret_cast<const f32x4*>(base + fa16 + mi * 16 * 64 + ch16),
-                                    *reinterpret_cast<const f32x4*>(base + ARR + fa16 + mi * 16 * 64 + ch16), ap[0], ap[1], ap[2]);
-                    } else {
-                        ap[0] = *reinterpret_cast<const bf16x8*>(base + fa16 + mi * 16 * 64 + ch16);
-                        ap[1] = *reinterpret_cast<const bf16x8*>(base + ARR + fa16 + mi * 16 * 64 + ch16);
-                    }
+                    bf16x8 ap[2];
+                    ap[0] = *reinterpret_cast<const bf16x8*>(base + fa16 + mi * 16 * 64 + ch16);
+                    ap[1] = *reinterpret_cast<const bf16x8*>(base + ARR + fa16 + mi * 16 * 64 + ch16);
                     if (issue && mi < 4) {   // two pieces in front of each of the first four blocks
                         dma_piece(S, s_kt, buf ^ 1, 2 * mi);
                         dma_piece(S, s_kt, buf ^ 1, 2 * mi + 1);
@@ -992,11 +975,6 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g) {
                     }
 #pragma unroll
                     for (int ni = 0; ni < 4; ni++) {
-                        if constexpr (TERMS == 6) {   // the small terms first
-                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[2], bp[0][ni], acc[mi][ni], 0, 0, 0);
-                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[2][ni], acc[mi][ni], 0, 0, 0);
-                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[1], bp[1][ni], acc[mi][ni], 0, 0, 0);
-                        }
                         acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[0][ni], acc[mi][ni], 0, 0, 0);
                         acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[1][ni], acc[mi][ni], 0, 0, 0);
                         acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[1], bp[0][ni], acc[mi][ni], 0, 0, 0);
@@ -1067,9 +1045,242 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g) {
 #endif
 }
 
-// (two kernels over one body: a __launch_bounds__(512, 2) kernel template loses its host stub in this compiler)
-__global__ __launch_bounds__(512, 2) void k_gemm_bf16x3(GemmArgs g) { gemm_body<3>(g); }
-__global__ __launch_bounds__(512, 2) void k_gemm_bf16x6(GemmArgs g) { gemm_body<6>(g); }
+// ---- k_gemm_bf16x6 (PV_DTYPE_F32 split-6 chain): six-term products of three-piece operands ------------------------------
+// x = x0 + x1 + x2 (bf16 each, split3_bf16 / split3_host.hpp); x.w = a2.b0 + a0.b2 + a1.b1 + a0.b0 + a0.b1 + a1.b0 in that
+// order, the small terms first (the dropped a1.b2, a2.b1, a2.b2 are below 2^-24 relative). A is the fp32 output of the layer
+// before, rows [M][K]; W is the model's weights, which do not change between load and close: they are split ONCE, on the
+// host, into three bf16 planes [3][N][K] (split3_planes), and only A is split in the kernel - by the one wave that owns the rows.
+// A work item is 256 (M) x 128 (N); the waves go 8 x 1: wave w owns rows 32 w .. 32 w + 31 and all 128 columns (2 x 8 accumulator
+// tiles). Per K step of 32 a workgroup moves
+//     A   256 rows x 128 B of fp32 as the "hi" image (elements 0..3 of every 8-group) and the "lo" image (4..7), 2 x 16 KB: an
+//         fp32 8-group is 32 bytes like a split8 group, so these transfers are byte for byte those of the 3-term form
+//     W   three piece images of 128 rows x 64 B, 3 x 8 KB, row pitch K * 2
+// = 56 KB per stage, 112 KB double-buffered, in 16-row x 64 B LDS-DMA pieces with the XOR swizzle of the 3-term form on the
+// source address: 7 pieces per wave and stage (4 of A, one of each W plane). A wave reads its two A fragments as fp32 and
+// splits them (no other wave touches those rows), holds the six pieces, and streams the 8 x 3 W fragments over ni straight as
+// bf16x8: ~90 VALU instructions beside 96 MFMAs per step (256 x 256 items with all eight waves splitting 8 + 4 fragments:
+// ~530 beside 192, issue-bound; 256 x 256 with W piece images would need 160 KB for the operands alone). Everything else is
+// the 3-term form's machinery (above): the persistent item walk, n-tile fastest, dealt to the XCDs in groups; one K-step
+// stream across items; completion by flag transfer; bias by LDS-DMA; the next step's pieces issued between the first MFMA
+// blocks of this one; both epilogues. That machinery is repeated here from gemm_body, not shared: a fix to it belongs in both.
+constexpr int PV_GEMM6_BN = 128;   // columns of one work item of k_gemm_bf16x6 (a kernel and launcher detail: the plan counts 256 x 256 tiles)
+__device__ __forceinline__ void gemm6_body(const GemmArgs& g) {
+    constexpr int BM = PV_GEMM_TILE, BN = PV_GEMM6_BN, BK = 32;
+    constexpr int ARR = BM * BK * 2;          // bytes of one A image (16 KB)
+    constexpr int WRR = BN * BK * 2;          // bytes of one W piece image (8 KB)
+    constexpr int STAGE = 2 * ARR + 3 * WRR;  // [A_hi | A_lo | W_0 | W_1 | W_2]
+    extern __shared__ __attribute__((aligned(16))) unsigned char smg[];
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // DMA role: this wave moves rows 16 * (8p + wv) .. + 15 (p = 0, 1) of both A images and rows 16 * wv .. + 15 of every W piece
+    // image; lane -> row lane >> 2, destination chunk lane & 3, source chunk (lane & 3) ^ ((lane >> 4) & 3)
+    const int d_row = lane >> 2;
+    const unsigned d_chunk = (unsigned)((lane & 3) ^ ((lane >> 4) & 3));
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
+    const int kslice = g.K / g.splits, nk = kslice / BK;
+    const unsigned a_pitch = (unsigned)g.K * 4u, w_pitch = (unsigned)g.K * 2u;
+    const unsigned plane_bytes = (unsigned)g.N * w_pitch;
+
+    struct Item { __amdgpu_buffer_rsrc_t ra, rw; unsigned la[2], lw; int mt, nt, sp; };
+    const int step_n = (int)gridDim.x % g.tiles_n, step_r = (int)gridDim.x / g.tiles_n;
+    auto item_setup = [&](Item& I) {
+        const int64_t m0 = (int64_t)I.mt * BM;
+        const int n0 = I.nt * BN;
+        I.ra = make_rsrc(g.A + ((size_t)m0 * g.K + (size_t)I.sp * kslice) * 4);
+        I.rw = make_rsrc(g.W + ((size_t)n0 * g.K + (size_t)I.sp * kslice) * 2);
+#pragma unroll
+        for (int p = 0; p < 2; p++) {
+            int64_t r = 16 * (8 * p + wv) + d_row;
+            if (m0 + r >= g.M) r = g.M - 1 - m0;             // rows beyond M replicate the last row (never stored)
+            I.la[p] = (unsigned)r * a_pitch + d_chunk * 32u;
+        }
+        I.lw = (unsigned)(16 * wv + d_row) * w_pitch + d_chunk * 16u;   // (N is a multiple of the item's 128 columns)
+    };
+    // piece j = 0..6 of this wave for K step kt of item I into buffer buf: j < 4: (p = j >> 1) x {A_hi, A_lo}; j >= 4: W plane j - 4
+    auto dma_piece = [&](const Item& I, int kt, int buf, int j) {
+        typedef __attribute__((address_space(3))) void* lds_ptr;
+        unsigned char* base = smg + buf * STAGE + wv * 1024;
+        if (j < 4) {
+            const int p = j >> 1, arr = j & 1;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(I.ra, (lds_ptr)(base + arr * ARR + p * 8192), 16, I.la[p], (unsigned)(kt * BK * 4) + (arr ? 16u : 0u), 0, 0);
+        } else {
+            const int q = j - 4;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(I.rw, (lds_ptr)(base + 2 * ARR + q * WRR), 16, I.lw, (unsigned)(kt * BK * 2) + (unsigned)q * plane_bytes, 0, 0);
+        }
+    };
+    // the bias of an item's 128 columns by LDS-DMA (waves 0 and 1, 64 floats each) into one of two slots behind the operand buffers
+    float* sbias = reinterpret_cast<float*>(smg + 2 * STAGE);
+    auto dma_bias = [&](int nt_, int bslot) {
+        typedef __attribute__((address_space(3))) void* lds_ptr;
+        if (g.bias && wv < 2)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(make_rsrc(g.bias + nt_ * BN + wv * 64), (lds_ptr)(sbias + bslot * BN + wv * 64), 4, (unsigned)lane * 4u, 0, 0, 0);
+    };
+    // completion of a K step's transfers by flag transfer, as in the 3-term form
+    unsigned* sflag = reinterpret_cast<unsigned*>(smg + 2 * STAGE + 2048) + wv * 64;   // 256 B per wave
+    sflag[lane] = 0xFFFFFFFFu;
+    unsigned seq = 0;
+    const __amdgpu_buffer_rsrc_t riota = make_rsrc(g.iota);
+    auto dma_flag = [&]() {
+        typedef __attribute__((address_space(3))) void* lds_ptr;
+        seq = (seq + 1u) & 1023u;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(riota, (lds_ptr)sflag, 4, 0u, seq * 4u, 0, 0);
+    };
+    const unsigned flag_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned*)(sflag + lane);
+    auto dma_wait = [&]() {
+        while (true) {
+            unsigned v;
+            asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(flag_addr) : "memory");
+            if (__builtin_amdgcn_ballot_w64(v != seq) == 0) break;
+            __builtin_amdgcn_s_sleep(1);
+        }
+    };
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    int it = xcd * per_xcd + slot;
+    Item cur, nxt;
+    cur.mt = cur.nt = cur.sp = 0;
+    int r_cur = 0;                                // it / tiles_n of the current item
+    unsigned gstep = 0;                           // K steps of this workgroup so far: step s uses operand buffer s & 1, across items
+    int tile_no = 0;                              // items so far: bias slot tile_no & 1
+    if (it < g.items) {
+        cur.nt = it % g.tiles_n;
+        r_cur = it / g.tiles_n;
+        cur.sp = r_cur % g.splits;
+        cur.mt = r_cur / g.splits;
+        item_setup(cur);
+#pragma unroll
+        for (int j = 0; j < 7; j++) dma_piece(cur, 0, 0, j);
+        dma_bias(cur.nt, 0);
+        dma_flag();
+    }
+#ifdef PV_GEMM_STAMPS
+    unsigned long long gs_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, gs_last;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gs_last) :: "memory");
+#endif
+    while (it < g.items) {
+        const int it_n = it + (int)gridDim.x;
+        const bool has_next = it_n < g.items;
+        int r_n = r_cur + step_r;
+        nxt.nt = cur.nt + step_n;
+        if (nxt.nt >= g.tiles_n) { nxt.nt -= g.tiles_n; r_n++; }
+        if (g.splits == 1) { nxt.sp = 0; nxt.mt = r_n; }
+        else { nxt.sp = r_n % g.splits; nxt.mt = r_n / g.splits; }
+        if (has_next) item_setup(nxt);
+        GSTAMP(6)
+        f32x4 acc[2][8];   // 16 x 16 tiles of this wave's 32 x 128 outputs
+#pragma unroll
+        for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+            for (int ni = 0; ni < 8; ni++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) acc[mi][ni][r] = 0.0f;
+        auto k_step = [&](const Item& S, int s_kt, bool issue, bool next_bias) {
+            const int buf = (int)(gstep & 1u);
+            GSTAMP(3)
+            dma_wait();
+            GSTAMP(0)
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            GSTAMP(1)
+            const unsigned char* base = smg + buf * STAGE;
+            // lane -> row / column lane & 15, 16-byte chunk lane >> 4 of the 64-byte image row (under the XOR swizzle)
+            const unsigned ch16 = (unsigned)((((lane >> 4)) ^ (((lane & 15) >> 2) & 3)) * 16);
+            const unsigned fa16 = (unsigned)((32 * wv + (lane & 15)) * 64) + ch16, fb16 = (unsigned)(2 * ARR + (lane & 15) * 64) + ch16;
+            bf16x8 ap[2][3];   // this wave's A pieces of the step: split here, by no other wave
+#pragma unroll
+            for (int mi = 0; mi < 2; mi++)
+                split3_bf16(*reinterpret_cast<const f32x4*>(base + fa16 + mi * 16 * 64),
+                            *reinterpret_cast<const f32x4*>(base + ARR + fa16 + mi * 16 * 64), ap[mi][0], ap[mi][1], ap[mi][2]);
+#pragma unroll
+            for (int ni = 0; ni < 8; ni++) {
+                bf16x8 bp[3];
+#pragma unroll
+                for (int q = 0; q < 3; q++) bp[q] = *reinterpret_cast<const bf16x8*>(base + fb16 + q * WRR + ni * 16 * 64);
+                // the next step's seven pieces go out in front of the first four blocks (two each), the flag transfer behind them
+                if (issue && ni < 4) {
+                    dma_piece(S, s_kt, buf ^ 1, 2 * ni);
+                    if (ni < 3) dma_piece(S, s_kt, buf ^ 1, 2 * ni + 1);
+                    else {
+                        if (next_bias) dma_bias(nxt.nt, (tile_no + 1) & 1);
+                        dma_flag();
+                    }
+                }
+                // per output element the six terms in the order above; the two row tiles alternate, so that consecutive MFMAs
+                // do not depend on each other
+#pragma unroll
+                for (int mi = 0; mi < 2; mi++) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[mi][2], bp[0], acc[mi][ni], 0, 0, 0);
+#pragma unroll
+                for (int mi = 0; mi < 2; mi++) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[mi][0], bp[2], acc[mi][ni], 0, 0, 0);
+#pragma unroll
+                for (int mi = 0; mi < 2; mi++) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[mi][1], bp[1], acc[mi][ni], 0, 0, 0);
+#pragma unroll
+                for (int mi = 0; mi < 2; mi++) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[mi][0], bp[0], acc[mi][ni], 0, 0, 0);
+#pragma unroll
+                for (int mi = 0; mi < 2; mi++) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[mi][0], bp[1], acc[mi][ni], 0, 0, 0);
+#pragma unroll
+                for (int mi = 0; mi < 2; mi++) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[mi][1], bp[0], acc[mi][ni], 0, 0, 0);
+            }
+            GSTAMP(2)
+#ifdef PV_GEMM_STAMPS
+            gs_acc[4]++;
+#endif
+            gstep++;
+        };
+        for (int kt = 0; kt + 1 < nk; kt++) k_step(cur, kt + 1, true, false);
+        k_step(nxt, 0, has_next, true);          // the last step requests step 0 of the next item (and its bias)
+        // C tile as a sized buffer resource: rows beyond M fall outside it and are dropped by the bounds check
+        const int64_t m0 = (int64_t)cur.mt * BM;
+        const int n0 = cur.nt * BN;
+        const int64_t rows_left = g.M - m0 < BM ? g.M - m0 : BM;
+        float* cbase = g.C + (size_t)cur.sp * g.M * g.N;
+        float bv[8];
+#pragma unroll
+        for (int ni = 0; ni < 8; ni++) bv[ni] = g.bias ? sbias[(tile_no & 1) * BN + 16 * ni + (lane & 15)] : 0.0f;
+        GSTAMP(5)
+        if (g.c_quads) {
+            // [M/4][N][4]: one 16-byte store per accumulator tile, lane -> quad row lane >> 4, column lane & 15
+            const uint64_t cptr = (uint64_t)(cbase + ((size_t)(m0 >> 2) * g.N + n0) * 4);
+            u32x4 rcw;
+            rcw[0] = __builtin_amdgcn_readfirstlane((unsigned)cptr);
+            rcw[1] = __builtin_amdgcn_readfirstlane((unsigned)(cptr >> 32) & 0xffffu);
+            rcw[2] = __builtin_amdgcn_readfirstlane((unsigned)((((rows_left + 3) / 4 - 1) * g.N + BN) * 16));
+            rcw[3] = 0x00020000u;
+            const unsigned c_l = (unsigned)((((lane >> 4)) * g.N + (lane & 15)) * 16);
+#pragma unroll
+            for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+                for (int ni = 0; ni < 8; ni++) {
+                    f32x4 v;
+#pragma unroll
+                    for (int j = 0; j < 4; j++) v[j] = acc[mi][ni][j] + bv[ni];
+                    const unsigned so = (unsigned)(((8 * wv + 4 * mi) * g.N + 16 * ni) * 16);
+                    asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, %3 offen nt\n\ts_nop 2"
+                                 :: "v"(v), "v"(c_l), "s"(rcw), "s"(so) : "memory");
+                }
+        } else {
+            const __amdgpu_buffer_rsrc_t rc = make_rsrc_sized(cbase + (size_t)m0 * g.N + n0, (unsigned)(((rows_left - 1) * g.N + BN) * 4));
+            const unsigned c_l = (unsigned)(((4 * (lane >> 4)) * g.N + (lane & 15)) * 4);
+#pragma unroll
+            for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+                for (int ni = 0; ni < 8; ni++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+                        buf_store1_nt(acc[mi][ni][r] + bv[ni], rc, c_l, (unsigned)(((32 * wv + 16 * mi + r) * g.N + 16 * ni) * 4));
+        }
+        GSTAMP(7)
+        cur = nxt;
+        r_cur = r_n;
+        it = it_n;
+        tile_no++;
+    }
+#ifdef PV_GEMM_STAMPS
+    if (blockIdx.x == 0 && lane == 0)
+        for (int i = 0; i < 8; i++) atomicAdd(&g_gemm_stamps[i], gs_acc[i]);
+#endif
+}
+
+// (two kernels, no template: a __launch_bounds__(512, 2) kernel template loses its host stub in this compiler)
+__global__ __launch_bounds__(512, 2) void k_gemm_bf16x3(GemmArgs g) { gemm_body(g); }
+__global__ __launch_bounds__(512, 2) void k_gemm_bf16x6(GemmArgs g) { gemm6_body(g); }
 
 // ---- host-side weight packing -----------------------------------------------------------------------
 // LSTM layer, 8 waves per workgroup, wave w owns hidden units [32w, 32w+32) of the gates i,f,g,o (nt).
@@ -1150,6 +1361,7 @@ static void pack_linear(const float* W, int K, int TR, std::vector<float>& wp) {
 template <int KP> constexpr size_t lds_lstm_split() { return (size_t)(16 * (KP + 4) + 2 * 16 * (H + 4)) * sizeof(float); }
 template <int KP, int TR> constexpr size_t lds_lstm() { return (size_t)(TR * (KP + 4) + 2 * TR * (H + 4)) * sizeof(float); }
 static constexpr size_t LDS_GEMM = (size_t)2 * 4 * 256 * 32 * 2 + 2048 + 2048;   // 2 buffers x {A_hi, A_lo, W_hi, W_lo} x 256 rows x 32 bf16 = 128 KB, + two bias slots + completion flags
+static constexpr size_t LDS_GEMM6 = (size_t)2 * (2 * 256 + 3 * PV_GEMM6_BN) * 32 * 2 + 2048 + 2048;   // k_gemm_bf16x6: 2 buffers x ({A_hi, A_lo} x 256 rows + 3 W pieces x 128 rows) = 112 KB, + the same
 static constexpr size_t LDS_SPLITK = (size_t)ROWS * (2 * H + 4) * sizeof(float);
 template <int TR> constexpr size_t lds_tail() { return (size_t)2 * TR * (HEAD_N + 4) * sizeof(float); }
 
@@ -1172,24 +1384,14 @@ struct pv_rnn_p1 {
     unsigned char* w1_s = nullptr;
     unsigned char* enc_rb = nullptr; unsigned char* dec_rb = nullptr;    // bf16 fragment streams of k_rec_bf16 (encoder: W_ih | W_hh; decoder: W_hh)
     unsigned char* tail_wb = nullptr;                                    // bf16 fragment stream of k_tail_bf16 (linear_2..5)
-    // PV_DTYPE_F32, split-6 chain: three-piece fragment streams of k_rec_bf16<X6> and the fp32 operands of k_gemm_bf16x6
+    // PV_DTYPE_F32, split-6 chain: three-piece fragment streams of k_rec_bf16<X6> and the weights of k_gemm_bf16x6 as three
+    // bf16 planes [3][N][K] (split3_host.hpp), made once here
     unsigned char* enc_r6 = nullptr; unsigned char* dec_r6 = nullptr;
-    float* dec_wih_f = nullptr;   // decoder W_ih of both directions [2048][512] (biases: dec_bias_cat)
-    float* w1_f = nullptr;        // linear_1 [512][16896]
+    unsigned char* dec_wih_p3 = nullptr;   // decoder W_ih of both directions [3][2048][512] (biases: dec_bias_cat)
+    unsigned char* w1_p3 = nullptr;        // linear_1 [3][512][16896]
     std::vector<void*> owned;
 };
 
-static inline uint16_t f2bf_bits(float x) {  // round to nearest even
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-static inline float bf_bits2f(uint16_t h) {
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
 // w [N, K] row-major -> split8 rows (per 8 elements: 8 x bf16 hi, 8 x bf16 lo with w ~= hi + lo), K % 8 == 0
 static int dev_upload_split(const float* w, size_t N, size_t K, unsigned char** d_split, std::vector<void*>& owned) {
     const size_t n = N * K;
@@ -1206,6 +1408,16 @@ static int dev_upload_split(const float* w, size_t N, size_t K, unsigned char** 
     PV_HIP(hipMalloc((void**)d_split, n * 4));
     owned.push_back(*d_split);
     PV_HIP(hipMemcpy(*d_split, sw.data(), n * 4, hipMemcpyHostToDevice));
+    return PV_OK;
+}
+
+// w [N, K] row-major -> three bf16 planes [3][N][K] (w = x0 + x1 + x2), the W operand of k_gemm_bf16x6
+static int dev_upload_split3(const float* w, size_t N, size_t K, unsigned char** d_planes, std::vector<void*>& owned) {
+    std::vector<uint16_t> pl(3 * N * K);
+    split3_planes(w, N, K, pl.data());
+    PV_HIP(hipMalloc((void**)d_planes, pl.size() * 2));
+    owned.push_back(*d_planes);
+    PV_HIP(hipMemcpy(*d_planes, pl.data(), pl.size() * 2, hipMemcpyHostToDevice));
     return PV_OK;
 }
 
@@ -1299,11 +1511,11 @@ extern "C" int pv_rnn_load_p1(pv_ctx* ctx, const pv_weights_p1* w, int dtype) {
         for (int n = 0; n < 1024; n++) bcat[d * 1024 + n] = w->decoder[d].b_ih[n] + w->decoder[d].b_hh[n];
     }
     if ((rc = dev_upload(bcat, &m->dec_bias_cat, m->owned))) return rc;
-    if (dtype == PV_DTYPE_F32) {   // the split-6 chain of large calls: 3.4 + 3.4 MB of fragments, 4 + 34.6 MB of fp32 weights
+    if (dtype == PV_DTYPE_F32) {   // the split-6 chain of large calls: 3.4 + 3.4 MB of fragments, 6 + 51.9 MB of bf16 weight planes
         if ((rc = pv_pack_rec_bf16(w->encoder, 4, F_IN, &m->enc_r6, nullptr, m->owned, 3))) return rc;
         if ((rc = pv_pack_rec_bf16(w->decoder, 4, 0, &m->dec_r6, nullptr, m->owned, 3))) return rc;
-        if ((rc = dev_upload(wcat, &m->dec_wih_f, m->owned))) return rc;
-        if ((rc = dev_upload(w->linear_w[0], (size_t)HEAD_N * HEAD_K, &m->w1_f, m->owned))) return rc;
+        if ((rc = dev_upload_split3(wcat.data(), 2048, 512, &m->dec_wih_p3, m->owned))) return rc;
+        if ((rc = dev_upload_split3(w->linear_w[0], HEAD_N, HEAD_K, &m->w1_p3, m->owned))) return rc;
         if ((rc = pv_gemm_bf16x3_prepare()) || (rc = pv_rec_bf16_prepare())) return rc;
     }
     if (dtype == PV_DTYPE_BF16_INPUT_GEMM) {
@@ -1348,7 +1560,7 @@ static void launch_tail(pv_ctx* ctx, const pv_p1_plan& pl, const float* part, in
 struct P1Chain {
     int terms;                                 // of every product: 3 (split8 operands) or 6 (three-piece operands)
     const unsigned char *enc_rec, *dec_rec;    // fragment streams of k_rec_bf16
-    const void *dec_wih, *w1;                  // GEMM weights: split8 rows or fp32
+    const void *dec_wih, *w1;                  // GEMM weights: split8 rows or three bf16 planes
     const char* enc_buf;                       // workspace of the encoder's time-major output
     const char *n_enc, *n_dec_scope, *n_dec_gemm, *n_dec, *n_lin1;   // profile names
 };
@@ -1367,7 +1579,7 @@ static int p1_forward_mfma(pv_ctx* ctx, const pv_p1_plan& pl, const int8_t* d_im
                            float* dec_out, float* part, hipStream_t st, bool taps) {
     pv_rnn_p1* m = ctx->p1;
     const bool x6 = pl.chain == PV_CHAIN_X6;
-    const P1Chain c = x6 ? P1Chain{6, m->enc_r6, m->dec_r6, m->dec_wih_f, m->w1_f, "p1.enc_tm", "k_rec_x6_lstm_enc", "k_lstm_layer_dec",
+    const P1Chain c = x6 ? P1Chain{6, m->enc_r6, m->dec_r6, m->dec_wih_p3, m->w1_p3, "p1.enc_tm", "k_rec_x6_lstm_enc", "k_lstm_layer_dec",
                                    "k_gemm_bf16x6_dec", "k_rec_x6_lstm_dec", "k_gemm_bf16x6_lin1"}
                          : P1Chain{3, m->enc_rb, m->dec_rb, m->dec_wih_s, m->w1_s, "p1.enc_split", "k_rec_bf16_lstm_enc", nullptr,
                                    "k_gemm_bf16x3_dec", "k_rec_bf16_lstm_dec", "k_gemm_bf16x3_lin1"};
@@ -1572,15 +1784,16 @@ static const unsigned* gemm_iota() {
 }
 
 static void gemm_launch(pv_ctx* ctx, GemmArgs& g, hipStream_t st, int terms = 3) {
-    g.tiles_m = (int)((g.M + PV_GEMM_TILE - 1) / PV_GEMM_TILE); g.tiles_n = g.N / PV_GEMM_TILE; g.items = g.tiles_m * g.tiles_n * g.splits;
+    g.tiles_m = (int)((g.M + PV_GEMM_TILE - 1) / PV_GEMM_TILE); g.tiles_n = g.N / (terms == 6 ? PV_GEMM6_BN : PV_GEMM_TILE);
+    g.items = g.tiles_m * g.tiles_n * g.splits;
     const unsigned grid = (unsigned)(std::min((g.items + 7) / 8 * 8, (ctx->num_cu + 7) / 8 * 8));
-    if (terms == 6) k_gemm_bf16x6<<<grid, 512, LDS_GEMM, st>>>(g);
+    if (terms == 6) k_gemm_bf16x6<<<grid, 512, LDS_GEMM6, st>>>(g);
     else k_gemm_bf16x3<<<grid, 512, LDS_GEMM, st>>>(g);
 }
 
 int pv_gemm_bf16x3_prepare() {
     PV_HIP(hipFuncSetAttribute((const void*)k_gemm_bf16x3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_GEMM));
-    PV_HIP(hipFuncSetAttribute((const void*)k_gemm_bf16x6, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_GEMM));
+    PV_HIP(hipFuncSetAttribute((const void*)k_gemm_bf16x6, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_GEMM6));
     PV_CHECK(gemm_iota() != nullptr, PV_ERR_HIP, "allocation of the GEMM's flag table failed");
     return PV_OK;
 }
@@ -1616,20 +1829,21 @@ static int debug_gemm(pv_ctx* ctx, const float* A, const float* W, const float* 
     float *dB = nullptr, *dC = nullptr;
     int rc;
     auto cleanup = [&]() { for (void* p : owned) (void)hipFree(p); };
-    if (terms == 6) {   // plain fp32 operands
-        float *fA = nullptr, *fW = nullptr;
-        if ((rc = dev_upload(A, (size_t)M * K, &fA, owned)) || (rc = dev_upload(W, (size_t)N * K, &fW, owned))) { cleanup(); return rc; }
+    if (terms == 6) {   // A as plain fp32 rows, W pre-split into three bf16 planes as at load time
+        float* fA = nullptr;
+        if ((rc = dev_upload(A, (size_t)M * K, &fA, owned)) || (rc = dev_upload_split3(W, (size_t)N, (size_t)K, &dW, owned))) { cleanup(); return rc; }
         dA = reinterpret_cast<unsigned char*>(fA);
-        dW = reinterpret_cast<unsigned char*>(fW);
     } else if ((rc = dev_upload_split(A, (size_t)M, (size_t)K, &dA, owned)) || (rc = dev_upload_split(W, (size_t)N, (size_t)K, &dW, owned))) {
         cleanup();
         return rc;
     }
     if (bias && (rc = dev_upload(bias, (size_t)N, &dB, owned))) { cleanup(); return rc; }
-    const size_t nc = (size_t)splits * M * N;
-    if (hipMalloc((void**)&dC, nc * sizeof(float)) != hipSuccess) { cleanup(); pv_set_error("hipMalloc failed"); return PV_ERR_HIP; }
+    // behind C a guard of one item's rows (256 x N floats, 0xff): a row stored past M - a replicated row of a ragged last
+    // tile that its sized resource should have dropped - lands there and fails the call
+    const size_t nc = (size_t)splits * M * N, ng = (size_t)PV_GEMM_TILE * N;
+    if (hipMalloc((void**)&dC, (nc + ng) * sizeof(float)) != hipSuccess) { cleanup(); pv_set_error("hipMalloc failed"); return PV_ERR_HIP; }
     owned.push_back(dC);
-    (void)hipMemset(dC, 0xff, nc * sizeof(float));
+    (void)hipMemset(dC, 0xff, (nc + ng) * sizeof(float));
     if (pv_gemm_bf16x3_prepare() != PV_OK) { cleanup(); return PV_ERR_HIP; }
     GemmArgs g;
     g.A = dA; g.W = dW; g.bias = dB; g.C = dC; g.M = M; g.N = N; g.K = K; g.splits = splits; g.c_quads = quads;
@@ -1647,8 +1861,12 @@ static int debug_gemm(pv_ctx* ctx, const float* A, const float* W, const float* 
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (ms) *ms = t;
     if (er == hipSuccess) er = hipMemcpy(C, dC, nc * sizeof(float), hipMemcpyDeviceToHost);
+    std::vector<uint32_t> guard(ng);
+    if (er == hipSuccess) er = hipMemcpy(guard.data(), dC + nc, ng * sizeof(float), hipMemcpyDeviceToHost);
     cleanup();
     if (er != hipSuccess) { pv_set_error("GEMM failed: %s", hipGetErrorString(er)); return PV_ERR_HIP; }
+    for (size_t i = 0; i < ng; i++)
+        if (guard[i] != 0xffffffffu) { pv_set_error("GEMM stored past row M (guard word %zu behind C)", i); return PV_ERR_STATE; }
     return PV_OK;
 }
 
@@ -1656,7 +1874,8 @@ extern "C" int pv_debug_gemm_bf16x3(pv_ctx* ctx, const float* A, const float* W,
                                     int splits, int quads, float* C, float* ms) {
     return debug_gemm(ctx, A, W, bias, M, N, K, splits, quads, C, ms, 3);
 }
-// the same through the 6-term form (k_gemm_bf16x6: fp32 operands, split into three bf16 pieces in registers)
+// the same through the 6-term form (k_gemm_bf16x6: fp32 A, split into three bf16 pieces in registers; W pre-split on the host
+// into three bf16 planes by the function the model load uses)
 extern "C" int pv_debug_gemm_bf16x6(pv_ctx* ctx, const float* A, const float* W, const float* bias, int64_t M, int N, int K,
                                     int splits, int quads, float* C, float* ms) {
     return debug_gemm(ctx, A, W, bias, M, N, K, splits, quads, C, ms, 6);

@@ -16,6 +16,7 @@
 // step, so the MFMAs simply continue from them.
 #include "rnn_bf16.hpp"
 #include "mfma_tiles.hpp"
+#include "split3_host.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -825,18 +826,6 @@ template <int NG, bool ENC, int MT> constexpr size_t lds_rec() {
     return (size_t)2 * 32 * MT * C::HS + (ENC ? (size_t)2 * 32 * MT * C::XS : 0);
 }
 
-static inline uint16_t f2bf_bits(float x) {  // round to nearest even
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-static inline float bf_bits2f(uint16_t h) {
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
 
 // ---- the tail of the P1 head in this mode ---------------------------------------------------------------------------------
 // k_head_tail runs linear_2..5 (four dependent 512 x 512 layers per 32-row tile) on the fp32 MFMA, every workgroup streaming
@@ -989,13 +978,10 @@ int pv_pack_rec_bf16(const pv_rnn_dir* dirs, int cell, int kx, unsigned char** d
                         float v;
                         if (xpart) v = k < kx ? dirs[d].w_ih[(size_t)n * kx + k] : 0.0f;
                         else v = dirs[d].w_hh[(size_t)n * HID + k];
-                        // pieces: v ~= hi + lo (2), or v = x0 + x1 + x2 (3: the split3_bf16 rule)
-                        const uint16_t hi = f2bf_bits(v);
-                        const float r1 = v - bf_bits2f(hi);
-                        const uint16_t lo = f2bf_bits(r1);
-                        dst[lane * 8 + j] = hi;
-                        dst[512 + lane * 8 + j] = lo;
-                        if (pieces == 3) dst[1024 + lane * 8 + j] = f2bf_bits(r1 - bf_bits2f(lo));
+                        // pieces: v ~= hi + lo (2), or v = x0 + x1 + x2 (3): the first two or all three of split3_host.hpp's rule
+                        uint16_t p[3];
+                        split3_bits(v, p);
+                        for (int q = 0; q < pieces; q++) dst[512 * q + lane * 8 + j] = p[q];
                     }
             };
             uint16_t* base = wp.data() + (size_t)(d * NW + w) * nslot * SL;
