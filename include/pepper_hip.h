@@ -277,6 +277,54 @@ int pv_polish_stitch_qual(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_ch
                           int64_t* region_off, uint8_t* seq, int64_t seq_capacity, int64_t* counts,
                           const uint8_t* row_qual, uint8_t* qual);
 
+/* The polisher's edit list: what the labels of pv_polish_stitch[_dev]'s inputs change in the draft, one record per edited
+ * column. A column (chunk k, row j) is KEPT under the stitch's rule: position >= 0, index >= 0 and not (region_start > 0 and
+ * position <= region_start + 200). A kept column is OWNED by its chunk unless a neighbouring chunk of the same region holds
+ * the same (position, index) and has an id later in decimal string order; ownership is decided before the label is looked
+ * at, so the owned columns are exactly those whose label the stitch consults, and every kept (position, index) of the
+ * builder's layout has one owner. An owned column with label b in 0..4 is an edit in these cases:
+ *   index == 0: d = ref[ref_off[g] + position - region_start[g]], u = d with ASCII a..z upper-cased;
+ *               b == 0 is a deletion (PV_EDIT_DEL); b >= 1 with "ACGT"[b-1] != u is a substitution (PV_EDIT_SUB), so a draft
+ *               N or IUPAC byte under a base label is one, and a draft 'a' under label A is none;
+ *   index  > 0: b >= 1 is an inserted base (PV_EDIT_INS); b == 0 is nothing.
+ * Records of a region are in (position, index) order (chunk-major order of the owned columns), regions ascending.
+ * Identity with the stitch: for every position p of region g with an owned index-0 column, ascending, take the
+ * substitution's base, or nothing if p is deleted, or u if p has no index-0 record, then the bases of p's insert records in
+ * index order; the concatenation is seq[region_off[g] .. region_off[g+1]) of pv_polish_stitch on the same inputs. */
+#define PV_EDIT_SUB 1
+#define PV_EDIT_DEL 2
+#define PV_EDIT_INS 3
+typedef struct pv_polish_edit {   /* 16 bytes, little-endian */
+    int64_t position;
+    int32_t index;
+    uint8_t kind;   /* PV_EDIT_* */
+    uint8_t draft;  /* the raw draft byte for index 0, 0 for an insert */
+    uint8_t base;   /* 'A' 'C' 'G' 'T', 0 for a deletion */
+    uint8_t qual;   /* the owned column's row quality when row_qual is given, else 255 */
+} pv_polish_edit;
+
+/* chunks, labels, region_start, seq_length, seq_overlap: as for pv_polish_stitch_dev (seq_length <= 4096, 2 * seq_overlap <=
+ * seq_length); row_qual: uint8 [n_chunks][seq_length] from pv_polish_row_qual or NULL; ref_off int64 [n_regions+1] and ref:
+ * the draft bytes of the batch (pv_batch_in.ref_off, pv_batch_in.ref).
+ * Out: region_edit_off int64 [n_regions+1] exclusive offsets of every region's records (a region without chunks takes the
+ * next region's offset); edits [edit_capacity], 16-byte aligned. d_counts = {edits, status, first bad chunk (-1 if none), 0}.
+ * Status, with the stitch's precedence: PV_ERR_INVALID (chunk layout broken, or an owned column's position outside
+ * [region_start[g], region_start[g] + ref_off[g+1] - ref_off[g]): checked before the draft byte is read, which is therefore
+ * never read out of bounds), PV_ERR_STATE (an owned column's label above 4; on a losing or dropped column it is not an
+ * error), PV_ERR_CAPACITY (edit_capacity < edits: region_edit_off and d_counts[0] are valid, no record is written).
+ * ref == NULL with n_chunks > 0 is refused with PV_ERR_INVALID by the call itself. Device-resident and asynchronous on
+ * `stream`; three launches, no global atomics, no host synchronisation; capturable. */
+int pv_polish_edits_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                        const uint8_t* row_qual, const int64_t* region_start, const int64_t* ref_off, const uint8_t* ref,
+                        int32_t n_regions, int seq_length, int seq_overlap, int64_t* region_edit_off, pv_polish_edit* edits,
+                        int64_t edit_capacity, int64_t* d_counts, void* stream);
+/* HOST buffers in and out; counts[4] as d_counts above; returns the status (PV_ERR_CAPACITY with counts[0] = records needed
+ * and region_edit_off filled). */
+int pv_polish_edits(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                    const uint8_t* row_qual, const int64_t* region_start, const int64_t* ref_off, const uint8_t* ref,
+                    int32_t n_regions, int seq_length, int seq_overlap, int64_t* region_edit_off, pv_polish_edit* edits,
+                    int64_t edit_capacity, int64_t* counts);
+
 /* The polisher's read realignment (AlignmentSummarizer.reads_to_reference_realignment, pepper/modules/python/
  * AlignmentSummarizer.py:159-177 -> ReadAligner::align_reads_to_reference, simple_aligner.cpp:66-107): every read of a region
  * is aligned to the draft with the reference's striped Smith-Waterman rules (match 4, mismatch 6, gap open 8, gap extend 2,

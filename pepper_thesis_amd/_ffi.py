@@ -61,6 +61,11 @@ PV_BAMDEC_PAST_PLAN = 5
 PV_BAMDEC_SEEK = 6
 PV_BAMDEC_BAD_TABLE = 7
 
+# pv_polish_edit.kind
+PV_EDIT_SUB = 1
+PV_EDIT_DEL = 2
+PV_EDIT_INS = 3
+
 PV_PLAN_P1_LSTM = 1
 PV_PLAN_P2_GRU = 2
 PV_DTYPE_F32 = 0
@@ -154,6 +159,11 @@ class pv_polish_out(C.Structure):
     ]
 
 
+class pv_polish_edit(C.Structure):
+    _fields_ = [("position", C.c_int64), ("index", C.c_int32), ("kind", C.c_uint8), ("draft", C.c_uint8), ("base", C.c_uint8),
+                ("qual", C.c_uint8)]
+
+
 class pv_realign_out(C.Structure):
     _fields_ = [
         ("cigar_capacity", C.c_int64),
@@ -233,6 +243,12 @@ SYMBOLS = [
     ("pv_polish_stitch_qual", C.c_int,
      [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
       C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
+    ("pv_polish_edits_dev", C.c_int,
+     [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int,
+      C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("pv_polish_edits", C.c_int,
+     [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int,
+      C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("pv_polish_realign", C.c_int, [C.c_void_p, C.POINTER(pv_batch_in), C.c_void_p, C.c_void_p, C.POINTER(pv_realign_out)]),
     ("pv_polish_realign_dev", C.c_int,
      [C.c_void_p, C.POINTER(pv_batch_in), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(pv_realign_out),

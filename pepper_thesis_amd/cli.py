@@ -167,6 +167,10 @@ def polish_parser(ap=None):
     ap.add_argument("--qualities", action="store_true", default=False,
                     help="also write <output_file>/_pepper_polished.fq: the same contigs with one Phred byte per base (0..93) "
                          "from the network's accumulated softmax (opt-in; one device; the FASTA is unchanged)")
+    ap.add_argument("--edits", action="store_true", default=False,
+                    help="also write <output_file>/_pepper_polished.edits.vcf.gz (+ .tbi): every substitution, insertion and "
+                         "deletion the polisher made in the draft, with --qualities each with its quality (opt-in; one device; "
+                         "the FASTA is unchanged)")
     return ap
 
 

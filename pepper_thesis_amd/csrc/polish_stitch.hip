@@ -12,82 +12,11 @@
 //
 // Three launches, no global atomics: per-chunk counts (one block per chunk), one block scanning the chunk counts
 // into offsets (+ status, region offsets), then a block-local scan per chunk and a scattered byte write.
-#include "pv_common.hpp"
+#include "polish_stitch_common.hpp"
+
+using namespace pv_chunks;
 
 namespace {
-
-constexpr int ST_THREADS = 256;
-constexpr int ST_MAX_CPT = 16;        // columns per thread: seq_length <= 4096
-constexpr int ST_SCAN_THREADS = 1024;
-constexpr int64_t ST_BUFFER = 200;    // 2 * ImageSizeOptions.MIN_IMAGE_OVERLAP (Stitch.py:42)
-
-enum { BAD_NONE = 0, BAD_LABEL = 1, BAD_ORDER = 2 };
-
-struct StitchArgs {
-    const int64_t* pos;
-    const int32_t* idx;
-    const int32_t* region;
-    const int32_t* cid;
-    const uint8_t* lab;
-    const int64_t* rstart;
-    int64_t n_chunks;
-    int n_regions;
-    int L;
-    int step;      // seq_length - seq_overlap
-    int cpt;       // columns per thread
-    int32_t* chunk_cnt;
-    int32_t* chunk_bad;
-    int64_t* chunk_off;
-    int64_t* region_off;
-    uint8_t* seq;
-    int64_t cap;
-    int64_t* counts;
-};
-
-// str(a) > str(b) for a, b >= 0 (Python string order of the decimal forms)
-__device__ inline bool dec_str_gt(int32_t a, int32_t b) {
-    int na = 1, nb = 1;
-    for (int32_t v = a; v >= 10; v /= 10) na++;
-    for (int32_t v = b; v >= 10; v /= 10) nb++;
-    if (na == nb) return a > b;
-    if (na < nb) {
-        int32_t pb = b;
-        for (int i = na; i < nb; i++) pb /= 10;  // the first na digits of b
-        return a > pb;                            // equal: a is a proper prefix of b, so it sorts first
-    }
-    int32_t pa = a;
-    for (int i = nb; i < na; i++) pa /= 10;
-    return pa >= b;                               // equal: b is a proper prefix of a
-}
-
-// the chunk layout contract: regions ascending, a region's chunks contiguous with ids 0, 1, 2, ...
-__device__ inline bool chunk_in_order(const StitchArgs& a, int64_t k) {
-    const int32_t g = a.region[k], c = a.cid[k];
-    if (g < 0 || g >= a.n_regions || c < 0) return false;
-    if (k == 0) return c == 0;
-    const int32_t pg = a.region[k - 1];
-    return pg == g ? c == a.cid[k - 1] + 1 : (pg < g && c == 0);
-}
-
-struct ChunkView {
-    int64_t base;      // k * L
-    int64_t rs;        // region start
-    bool prev, next;   // the neighbouring chunk of the same region exists
-    int32_t c, cprev, cnext;
-};
-
-__device__ inline ChunkView chunk_view(const StitchArgs& a, int64_t k) {
-    ChunkView v;
-    v.base = k * a.L;
-    const int32_t g = a.region[k];
-    v.rs = a.rstart[g];
-    v.c = a.cid[k];
-    v.prev = k > 0 && a.region[k - 1] == g;
-    v.next = k + 1 < a.n_chunks && a.region[k + 1] == g;
-    v.cprev = v.prev ? a.cid[k - 1] : 0;
-    v.cnext = v.next ? a.cid[k + 1] : 0;
-    return v;
-}
 
 // 0: no base, 1..4: base, -1: a kept column with a label outside 0..4
 __device__ inline int column_label(const StitchArgs& a, const ChunkView& v, int j) {
@@ -111,29 +40,6 @@ __device__ inline int column_label(const StitchArgs& a, const ChunkView& v, int 
     return lb;
 }
 
-// exclusive block scan; *total gets the block's sum. NT threads, NT/64 waves.
-template <int NT, typename T>
-__device__ inline T block_excl_scan(T v, T* lds, T* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    T x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) lds[w] = x;
-    __syncthreads();
-    T off = 0, sum = 0;
-#pragma unroll
-    for (int i = 0; i < NT / 64; i++) {
-        off += i < w ? lds[i] : 0;
-        sum += lds[i];
-    }
-    __syncthreads();   // lds may be reused by the caller's next scan
-    *total = sum;
-    return off + x - v;
-}
-
 // one block per chunk: bases the chunk contributes, and whether it breaks the layout or holds a poisoned label
 __global__ __launch_bounds__(ST_THREADS) void k_stitch_count(StitchArgs a) {
     __shared__ int32_t lds[ST_THREADS / 64];
@@ -155,52 +61,6 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_count(StitchArgs a) {
     if (threadIdx.x == 0) {
         a.chunk_cnt[k] = total;
         a.chunk_bad[k] = !ordered ? BAD_ORDER : (nbad ? BAD_LABEL : BAD_NONE);
-    }
-}
-
-// one block: chunk offsets, region offsets, total, status and the first bad chunk
-__global__ __launch_bounds__(ST_SCAN_THREADS) void k_stitch_scan(StitchArgs a) {
-    __shared__ int64_t lds[ST_SCAN_THREADS / 64];
-    const int64_t n = a.n_chunks;
-    const int64_t per = (n + ST_SCAN_THREADS - 1) / ST_SCAN_THREADS;
-    const int64_t k0 = min<int64_t>(n, threadIdx.x * per), k1 = min<int64_t>(n, k0 + per);
-    int64_t s = 0, first_bad = INT64_MAX, bad_kind = BAD_NONE, n_unordered = 0;
-    for (int64_t k = k0; k < k1; k++) {
-        s += a.chunk_cnt[k];
-        n_unordered += a.chunk_bad[k] == BAD_ORDER;
-        if (a.chunk_bad[k] != BAD_NONE && first_bad == INT64_MAX) { first_bad = k; bad_kind = a.chunk_bad[k]; }
-    }
-    int64_t total, any_unordered;
-    int64_t off = block_excl_scan<ST_SCAN_THREADS, int64_t>(s, lds, &total);
-    block_excl_scan<ST_SCAN_THREADS, int64_t>(n_unordered, lds, &any_unordered);
-    // first bad chunk: the segments are in chunk order, so the first thread with one holds it
-    int64_t nbad_before, nbad;
-    nbad_before = block_excl_scan<ST_SCAN_THREADS, int64_t>(first_bad != INT64_MAX ? 1 : 0, lds, &nbad);
-    __shared__ int64_t s_bad[2];
-    if (nbad == 0 && threadIdx.x == 0) { s_bad[0] = -1; s_bad[1] = BAD_NONE; }
-    if (first_bad != INT64_MAX && nbad_before == 0) { s_bad[0] = first_bad; s_bad[1] = bad_kind; }
-    __syncthreads();
-    const int64_t bad_chunk = s_bad[0], kind = s_bad[1];
-    const int64_t status = kind == BAD_ORDER ? PV_ERR_INVALID : kind == BAD_LABEL ? PV_ERR_STATE
-                   : total > a.cap ? PV_ERR_CAPACITY : PV_OK;
-    for (int64_t k = k0; k < k1; k++) {
-        a.chunk_off[k] = off;
-        if (!any_unordered) {   // (region ids are only known to be in range then)
-            // region g's bases start at its first chunk; regions without chunks take the next one's offset
-            const int32_t g = a.region[k], pg = k > 0 ? a.region[k - 1] : -1;
-            for (int32_t r = pg + 1; r <= g; r++) a.region_off[r] = off;
-        }
-        off += a.chunk_cnt[k];
-    }
-    if (threadIdx.x == 0) {
-        if (!any_unordered) {
-            const int32_t g_last = n > 0 ? a.region[n - 1] : -1;
-            for (int32_t r = g_last + 1; r <= a.n_regions; r++) a.region_off[r] = total;
-        }
-        a.counts[0] = total;
-        a.counts[1] = status;
-        a.counts[2] = bad_chunk;
-        a.counts[3] = 0;
     }
 }
 
@@ -293,14 +153,6 @@ extern "C" int pv_polish_stitch_qual_dev(pv_ctx* ctx, const pv_polish_out* chunk
                                          const uint8_t* row_qual, uint8_t* qual) {
     return stitch_dev<true>(ctx, chunks, n_chunks, labels, row_qual, region_start, n_regions, seq_length, seq_overlap, region_off,
                             seq, qual, seq_capacity, d_counts, stream);
-}
-
-template <typename T>
-static int stage(pv_ctx* ctx, const char* name, const T* src, size_t n, T** dst, hipStream_t st) {
-    int rc = pv_get(ctx, name, n > 0 ? n : 1, dst);
-    if (rc) return rc;
-    if (n > 0) PV_HIP(hipMemcpyAsync(*dst, src, n * sizeof(T), hipMemcpyHostToDevice, st));
-    return PV_OK;
 }
 
 // the host form of both stitches; QUAL: with the quality plane

@@ -9,7 +9,7 @@ prediction HDF5 files. Here each batch of regions goes through
 without leaving HBM; only the region offsets and the polished bases (one byte per base) come back to the host.
 
   python -m pepper_thesis_amd polish -b reads.bam -f draft.fa -m model.pkl -o out/polished [-t 5] [-r ctg:start-end] [--bf16]
-      [--realign] [--gpu_decode] [--qualities]
+      [--realign] [--gpu_decode] [--qualities] [--edits]
 
 --gpu_decode (opt-in) replaces the first stage: reader threads only plan blocks and fetch draft bytes, and the BAM is inflated,
 decoded and clipped on the device (gpu_decode.py; _decoded_pieces below). Same FASTA.
@@ -19,6 +19,12 @@ per base. The chain then keeps P2's accumulated softmax, turns it into row quali
 include/pepper_hip.h: what predict_distributed_gpu.py:96-105 means to store, and Stitch.py:39-91 means to string up with
 `+33` and `base != 0`, both commented out there) and stitches them beside the bases (pv_polish_stitch_qual_dev); one more
 byte per base comes back. The FASTA is byte for byte the one of a run without the flag.
+
+--edits (opt-in, one device) also writes `<o>/_pepper_polished.edits.vcf.gz` and its tabix index: what the polisher changed
+in the draft. Behind the stitch, on the same stream, pv_polish_edits_dev compares the labels of the columns the stitch
+consults with the draft bytes of the batch and leaves one 16-byte record per substitution, deletion or inserted base (with
+--qualities: with the column's row quality); the region offsets and the records come back, and polish_edits.py joins them
+into VCF records per contig. The FASTA (and FASTQ) are byte for byte those of a run without the flag.
 
 Semantics kept from the reference:
   * regions: ImageGenerationUI.py:257-273 - for pos in range(start, end, 1000): [max(start, pos-100), min(end, pos+1100)],
@@ -195,11 +201,16 @@ def _contig_list(fasta, bam, region: Optional[str]):
 
 class _DeviceChain:
     """device buffers of the builder -> GRU -> stitch chain, grown on demand. qualities: P2's accumulated softmax is kept,
-    turned into row qualities and stitched beside the bases; run / run_decoded then return (region_off, bases, qualities)."""
+    turned into row qualities and stitched beside the bases; run / run_decoded then return (region_off, bases, qualities).
+    edits: the edit pass runs behind the stitch (with the row qualities when there are any); run / run_decoded then return
+    their usual tuple followed by the pair (region_edit_off, records as a polish_edits.EDIT_DTYPE array)."""
 
-    def __init__(self, ctx, own_ctx: bool = False, qualities: bool = False):
+    def __init__(self, ctx, own_ctx: bool = False, qualities: bool = False, edits: bool = False):
         import torch
         self.ctx, self.dev, self.own_ctx, self.qualities = ctx, "cuda:%d" % ctx.device_id, own_ctx, bool(qualities)
+        self.edits = bool(edits)
+        self.edit_buf = self.edit_off = None
+        self.edit_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.dout = self.labels = self.seq = None
         self.acc = self.row_qual = self.qual = None
         self.rout = None
@@ -220,6 +231,8 @@ class _DeviceChain:
                 self.acc = torch.zeros((chunks, 1000, 5), dtype=torch.float32, device=self.dev)
                 self.row_qual = torch.zeros((chunks, 1000), dtype=torch.uint8, device=self.dev)
                 self.qual = torch.zeros(chunks * 1000, dtype=torch.uint8, device=self.dev)
+            if self.edits:   # one record per chunk row: capacity cannot run short
+                self.edit_buf = torch.zeros((chunks * 1000, 16), dtype=torch.uint8, device=self.dev)
             torch.cuda.synchronize()   # the fills ran on torch's stream; the chain runs on the context's
 
     def _summarize(self, batch, db, host_batch=None, sizes=None) -> int:
@@ -341,7 +354,9 @@ class _DeviceChain:
     def _labels_and_stitch(self, db, n: int, n_regions: int):
         region_off = np.zeros(n_regions + 1, np.int64)
         if n == 0:
-            return (region_off, b"", b"") if self.qualities else (region_off, b"")
+            from .polish_edits import EDIT_DTYPE
+            return ((region_off, b"", b"") if self.qualities else (region_off, b"")) + (
+                ((region_off.copy(), np.zeros(0, EDIT_DTYPE)),) if self.edits else ())
         import torch
         roff = torch.empty(n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
         if self.qualities:
@@ -349,11 +364,33 @@ class _DeviceChain:
         self.ctx.forward_p2_dev(self.dout.images.data_ptr(), n, self.labels.data_ptr())
         self.ctx.polish_stitch_dev(self.dout, n, self.labels.data_ptr(), db.t["ref_start"].data_ptr(), n_regions,
                                    roff.data_ptr(), self.seq.data_ptr(), self.seq.numel(), self.counts.data_ptr())
+        eoff = self._launch_edits(db, n, n_regions, 0)
         self.ctx.synchronize()   # raises if a split GRU form timed out (its labels are then poisoned)
         total, status, bad = (int(v) for v in self.counts[:3].tolist())
         if status != _ffi.PV_OK:   # capacity cannot run short: seq holds a byte for every column
             raise _ffi.PepperHipError(status, "polisher stitch: device status %d (chunk %d)" % (status, bad))
-        return roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes()
+        return (roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes()) + self._read_edits(eoff)
+
+    def _launch_edits(self, db, n: int, n_regions: int, d_row_qual: int):
+        """the edit pass behind the stitch on the context's stream (nothing without edits) -> its region offsets on the device"""
+        if not self.edits:
+            return None
+        import torch
+        eoff = torch.empty(n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
+        self.ctx.polish_edits_dev(self.dout, n, self.labels.data_ptr(), d_row_qual, db.t["ref_start"].data_ptr(),
+                                  db.t["ref_off"].data_ptr(), db.t["ref"].data_ptr(), n_regions, eoff.data_ptr(),
+                                  self.edit_buf.data_ptr(), self.edit_buf.shape[0], self.edit_counts.data_ptr())
+        return eoff
+
+    def _read_edits(self, eoff) -> tuple:
+        """after the synchronize: () without edits, else ((region_edit_off, records),)"""
+        if eoff is None:
+            return ()
+        from .polish_edits import EDIT_DTYPE
+        total, status, bad = (int(v) for v in self.edit_counts[:3].tolist())
+        if status != _ffi.PV_OK:   # capacity cannot run short: a record for every chunk row
+            raise _ffi.PepperHipError(status, "polisher edits: device status %d (chunk %d)" % (status, bad))
+        return ((eoff.cpu().numpy(), self.edit_buf[:total].cpu().numpy().view(EDIT_DTYPE).reshape(-1)),)
 
     def _labels_and_stitch_qual(self, db, n: int, n_regions: int, roff):
         """_labels_and_stitch with the quality plane: P2 keeps its accumulated softmax, the row-quality kernel reads it with
@@ -366,27 +403,31 @@ class _DeviceChain:
         self.ctx.polish_stitch_qual_dev(self.dout, n, self.labels.data_ptr(), self.row_qual.data_ptr(), db.t["ref_start"].data_ptr(),
                                         n_regions, roff.data_ptr(), self.seq.data_ptr(), self.qual.data_ptr(), self.seq.numel(),
                                         self.counts.data_ptr())
+        eoff = self._launch_edits(db, n, n_regions, self.row_qual.data_ptr())
         self.ctx.synchronize()
         total, status, bad = (int(v) for v in self.counts[:3].tolist())
         if status != _ffi.PV_OK:
             raise _ffi.PepperHipError(status, "polisher stitch: device status %d (chunk %d)" % (status, bad))
-        return roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes(), self.qual[:total].cpu().numpy().tobytes()
+        return (roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes(),
+                self.qual[:total].cpu().numpy().tobytes()) + self._read_edits(eoff)
 
 
-def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int, qualities: bool = False) -> _DeviceChain:
+def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int, qualities: bool = False,
+                      edits: bool = False) -> _DeviceChain:
     """a context on `device` with the polisher weights loaded, and the chain on it (closing the chain closes the context).
     shared_device: other ranks use this GPU too, so the option is set before the first device call (the split GRU forms need
     co-resident workgroups and would time out, poisoning the labels). False leaves the create-time default (PV_SHARED_DEVICE).
     This is the default `open_chain` of run and polish_rank.run; CPU tests pass a stub with the same signature, whose result
     has run(batch, windows) -> (region_off, bases) and close(). qualities (passed only when set): the chain of --qualities,
-    whose run gives (region_off, bases, qualities)."""
+    whose run gives (region_off, bases, qualities). edits (passed only when set): the chain of --edits, whose run's result
+    ends with the pair (region_edit_off, records)."""
     from .runtime import Context
     ctx = Context(device)
     try:
         if shared_device:
             ctx.set_option("shared_device", 1)
         ctx.load_p2(state_dict, dtype)
-        return _DeviceChain(ctx, own_ctx=True, qualities=qualities)
+        return _DeviceChain(ctx, own_ctx=True, qualities=qualities, edits=edits)
     except BaseException:
         ctx.close()
         raise
@@ -413,8 +454,19 @@ def _read_ahead(ex, fn, items, depth):
         yield f.result()
 
 
+def _region_parts(res, g: int, qualities: bool, edits: bool) -> tuple:
+    """region g's share of a chain result: (bases[, qualities][, edit records])"""
+    roff = res[0]
+    parts = tuple(p[roff[g]:roff[g + 1]] for p in res[1:2 + bool(qualities)])
+    if edits:
+        eoff, recs = res[-1]
+        parts += (recs[eoff[g]:eoff[g + 1]],)
+    return parts
+
+
 def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int = 2048, threads: int = 5, realign: bool = False,
-                  timers: Optional[dict] = None, gpu_decode: bool = False, open_decoder=None, qualities: bool = False):
+                  timers: Optional[dict] = None, gpu_decode: bool = False, open_decoder=None, qualities: bool = False,
+                  edits: bool = False):
     """the regions of `work` through the chain -> (contig, region start, region index, polished bases) for every region with
     reads, in `work` order. This is the whole device part of a run: the single-rank run passes every region, a rank of a
     multi-device run its share. chain.run(batch, windows) -> (region_off, bases) (_DeviceChain or a CPU test's stub).
@@ -424,9 +476,10 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
     by default a gpu_decode.GpuDecoder with the polisher's settings (CPU tests pass a stub with its scan_groups, realize,
     iterate and close).
     qualities: the chain's run gives (region_off, bases, qualities), and every piece carries its raw Phred bytes as a fifth
-    entry."""
+    entry.
+    edits: the chain's result ends with (region_edit_off, records), and every piece carries its records as its last entry."""
     if gpu_decode:
-        yield from _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder, qualities)
+        yield from _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder, qualities, edits)
         return
     from .batch import pack_regions
     from .bamio import BamHandler, FastaHandler
@@ -449,9 +502,7 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
         t0 = time.perf_counter()
         regs = [r for _, r in items]
         res = chain.run(pack_regions(regs), [r.window for r in regs] if realign else None)
-        roff = res[0]
-        out = [(w.contig, w.start, w.index) + tuple(p[roff[g]:roff[g + 1]] for p in res[1:2 + bool(qualities)])
-               for g, (w, _) in enumerate(items)]
+        out = [(w.contig, w.start, w.index) + _region_parts(res, g, qualities, edits) for g, (w, _) in enumerate(items)]
         T["device_s"] += time.perf_counter() - t0
         T["batches"] += 1
         return out
@@ -474,7 +525,7 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
             yield from flush(pending)
 
 
-def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder, qualities=False):
+def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder, qualities=False, edits=False):
     """polish_pieces' device read path. Reader threads plan reader groups (gpu_decode.region_groups: blocks, interval table,
     draft bytes, realign windows); the decoder's service thread scans them, cuts the regions with reads into the launches
     the host path makes (per_launch regions each) and fills them on its own stream; this thread runs the chain on every
@@ -517,11 +568,10 @@ def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timer
                 t0 = time.perf_counter()
                 for kind, b, windows, ws in parts:
                     res = chain.run_decoded(b, windows) if kind == "dev" else chain.run(b, windows)
-                    roff = res[0]
                     T["chain_runs"] += 1
                     T["regions"] += len(ws)
                     for g, w in enumerate(ws):
-                        yield (w.contig, w.start, w.index) + tuple(p[roff[g]:roff[g + 1]] for p in res[1:2 + bool(qualities)])
+                        yield (w.contig, w.start, w.index) + _region_parts(res, g, qualities, edits)
                 T["device_s"] += time.perf_counter() - t0
                 T["batches"] += 1
                 del parts
@@ -542,12 +592,14 @@ def decode_report(T: dict) -> str:
 
 def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region: Optional[str] = None, batch_size: int = 2048,
                  threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None,
-                 realign: bool = False, chain=None, gpu_decode: bool = False, qualities: bool = False) -> str:
+                 realign: bool = False, chain=None, gpu_decode: bool = False, qualities: bool = False, edits: bool = False) -> str:
     """-> path of the polished FASTA. batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
     realign: realign every read to the draft on the device before the builder, as the reference always does.
     chain: a chain with the weights already loaded (open_device_chain; the caller closes it), else one is made on `ctx`
     (default: a context on device 0) from model_path. gpu_decode: polish_pieces' device read path.
-    qualities: also write the FASTQ beside the FASTA (output_fastq_path); a chain passed in must have been made for it."""
+    qualities: also write the FASTQ beside the FASTA (output_fastq_path); a chain passed in must have been made for it.
+    edits: also write the edits VCF and its index beside the FASTA (polish_edits.output_vcf_path); likewise. The VCF is
+    composed before any file is written, so a run it refuses (overlapping -r ranges of one contig) leaves nothing."""
     from .bamio import BamHandler, FastaHandler
     from .runtime import Context
     t_start = time.perf_counter()
@@ -558,25 +610,54 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
         if ctx is None:
             ctx = own = Context(0)
         ctx.load_p2(state_dict, dtype)
-        chain = _DeviceChain(ctx, qualities=qualities)
+        chain = _DeviceChain(ctx, qualities=qualities, edits=edits)
     try:
         fa, bm = FastaHandler(fasta), BamHandler(bam)
         work, T["bases_in"] = polish_work(fa, bm, region)
         out_path = output_fasta_path(out_prefix)
         log("POLISHING %d REGIONS, OUTPUT: %s" % (len(work), out_path))
         pieces = list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode,
-                                    qualities=qualities))
+                                    qualities=qualities, edits=edits))
+        vcf = _edits_vcf(fa, fasta, work, pieces, qualities) if edits else None
     finally:
         if own is not None:
             own.close()
-    seqs = write_polished_fasta(out_path, [p[:4] for p in pieces] if qualities else pieces)
+    seqs = write_polished_fasta(out_path, [p[:4] for p in pieces])
     if qualities:
         write_fastq(output_fastq_path(out_path), seqs, merge_pieces(p[:3] + (p[4],) for p in pieces))
+    if edits:
+        from . import polish_edits
+        polish_edits.write_edits_vcf(polish_edits.output_vcf_path(out_path), *vcf)
+        T["edit_records"], T["vcf_records"] = sum(len(p[-1]) for p in pieces), sum(len(r) for r in vcf[-1].values())
     T["bases_out"] = sum(len(s) for s in seqs.values())
     T["wall_s"] = time.perf_counter() - t_start
     if timers is not None:
         timers.update(T)
     return out_path
+
+
+def _edits_vcf(fa, fasta_path: str, work: List[Work], pieces, qualities: bool) -> tuple:
+    """the pieces' edit records -> write_edits_vcf's arguments behind the path: (source, reference, contigs of the run with
+    their lengths, read-free runs, VCF records per contig). Pieces of a contig are joined in region-start order, as
+    merge_pieces joins the bases. A region without a piece gave no chunks: the FASTA omits its kept range
+    ((start + 200, end], or [start, end] for start 0) and a pepper_no_reads header line names it."""
+    from . import polish_edits
+    names = list(dict.fromkeys(w.contig for w in work))
+    contigs = [(c, fa.get_chromosome_sequence_length(c)) for c in names]
+    done = {p[2] for p in pieces}
+    no_reads = polish_edits.no_read_runs(
+        (w.contig, w.start + 2 * MIN_IMAGE_OVERLAP + 1 if w.start > 0 else w.start, w.end)
+        for w in work if w.index not in done)
+    by: Dict[str, list] = {}
+    for p in pieces:
+        by.setdefault(p[0], []).append((p[1], p[2], p[-1]))
+    records = {}
+    for c, length in contigs:
+        if c in by:
+            recs = np.concatenate([e for _, _, e in sorted(by[c], key=lambda t: (t[0], t[1]))])
+            draft = fa.get_reference_sequence(c, 0, length).encode() if len(recs) else b""
+            records[c] = polish_edits.compose_records(c, recs, draft, qualities, warn=log)
+    return "pepper_thesis_amd polish", os.path.abspath(fasta_path), contigs, no_reads, records
 
 
 def run(args, open_chain=open_device_chain) -> int:
@@ -597,6 +678,11 @@ def run(args, open_chain=open_device_chain) -> int:
         sys.stderr.write("ERROR: polish --qualities runs on one device (-d_ids %s lists %d): the quality plane is not carried "
                          "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
         return 2
+    edits = bool(getattr(args, "edits", False))
+    if edits and len(plan) > 1:
+        sys.stderr.write("ERROR: polish --edits runs on one device (-d_ids %s lists %d): the edit records are not carried "
+                         "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
+        return 2
     for what, path in (("BAM", args.bam), ("FASTA", args.fasta), ("MODEL", args.model_path)):
         if not os.path.isfile(path):
             sys.stderr.write("ERROR: CAN NOT LOCATE %s FILE.\n" % what)
@@ -612,12 +698,20 @@ def run(args, open_chain=open_device_chain) -> int:
     if len(plan) > 1:
         return polish_rank.launch(args, plan)
     dtype = _ffi.PV_DTYPE_BF16_INPUT_GEMM if args.bf16 else _ffi.PV_DTYPE_F32
-    chain = open_chain(device, False, state_dict, dtype, qualities=True) if qualities else open_chain(device, False, state_dict, dtype)
+    kw = dict(qualities=True) if qualities else {}   # (only the keywords that are set: stub chains keep their signatures)
+    if edits:
+        kw["edits"] = True
+    chain = open_chain(device, False, state_dict, dtype, **kw)
     try:
         T = {}
         path = polish_fused(args.bam, args.fasta, args.model_path, args.output_file, args.region, args.batch_size, args.threads,
                             timers=T, realign=bool(getattr(args, "realign", False)), chain=chain,
-                            gpu_decode=bool(getattr(args, "gpu_decode", False)), qualities=qualities)
+                            gpu_decode=bool(getattr(args, "gpu_decode", False)), qualities=qualities, edits=edits)
+    except ValueError as e:
+        if not edits:
+            raise
+        sys.stderr.write("ERROR: %s\n" % e)
+        return 2
     finally:
         chain.close()
     if decode_report(T):
@@ -625,4 +719,7 @@ def run(args, open_chain=open_device_chain) -> int:
     log("POLISHED FASTA: %s (%d REGIONS, %d BASES IN %.2f SEC)" % (path, T["regions"], T["bases_out"], T["wall_s"]))
     if qualities:
         log("POLISHED FASTQ: " + output_fastq_path(path))
+    if edits:
+        from .polish_edits import output_vcf_path
+        log("EDITS VCF: %s (%d RECORDS FROM %d EDITED COLUMNS)" % (output_vcf_path(path), T["vcf_records"], T["edit_records"]))
     return 0

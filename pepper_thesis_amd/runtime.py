@@ -421,6 +421,49 @@ class Context:
                                                   _ffi.ptr(qual)))
         return region_off, seq[:int(counts[0])].tobytes(), qual[:int(counts[0])].tobytes()
 
+    def polish_edits_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_row_qual: int, d_region_start: int,
+                         d_ref_off: int, d_ref: int, n_regions: int, d_region_edit_off: int, d_edits: int, edit_capacity: int,
+                         d_counts: int, stream: int = 0):
+        """asynchronous, device-resident edit list (pv_polish_edits_dev): the labels of dout's first n_chunks chunks against the
+        draft bytes d_ref / d_ref_off of the batch -> 16-byte records (polish_edits.EDIT_DTYPE) in d_edits, region offsets in
+        d_region_edit_off [n_regions+1], {edits, status, first bad chunk, 0} in d_counts. d_row_qual 0: qual 255."""
+        _ffi.check(self.lib.pv_polish_edits_dev(
+            self.handle, C.byref(dout.c), int(n_chunks), d_labels, d_row_qual or None, d_region_start, d_ref_off, d_ref or None,
+            int(n_regions), dout.seq_length, dout.seq_overlap, d_region_edit_off, d_edits, int(edit_capacity), d_counts,
+            stream or None))
+
+    def polish_edits(self, out, labels: np.ndarray, batch, row_qual: np.ndarray = None, edit_capacity: int = None,
+                     seq_length: int = 1000, seq_overlap: int = 50, counts=None, region_edit_off: np.ndarray = None):
+        """host-buffer edit list (pv_polish_edits) of a PolishOut, its labels and the batch they were built from (ref_start,
+        ref_off, ref: a RegionBatch) -> (region_edit_off int64 [n_regions+1], records as a polish_edits.EDIT_DTYPE array).
+        edit_capacity None: one record per chunk row; a smaller one raises PepperHipError(PV_ERR_CAPACITY).
+        counts: optional ctypes int64[4] that receives {edits, status, first bad chunk, 0}, and region_edit_off an optional
+        int64 [n_regions+1] array that receives the offsets, also when the call raises."""
+        from .polish_edits import EDIT_DTYPE
+        n = int(len(out.chunk_id))
+        c = _ffi.pv_polish_out()
+        keep = [np.ascontiguousarray(out.position, np.int64), np.ascontiguousarray(out.index, np.int32),
+                np.ascontiguousarray(out.region, np.int32), np.ascontiguousarray(out.chunk_id, np.int32)]
+        c.chunk_capacity = n
+        c.position, c.index, c.region, c.chunk_id = (_ffi.ptr(a) for a in keep)
+        lab = np.ascontiguousarray(labels, np.uint8)
+        rq = None if row_qual is None else np.ascontiguousarray(row_qual, np.uint8)
+        rs = np.ascontiguousarray(batch.ref_start, np.int64)
+        ro = np.ascontiguousarray(batch.ref_off, np.int64)
+        ref = None if batch.ref is None else np.ascontiguousarray(batch.ref, np.uint8)
+        assert lab.shape == (n, seq_length) and (rq is None or rq.shape == lab.shape), lab.shape
+        assert len(ro) == len(rs) + 1 and (ref is None or len(ref) >= int(ro[-1])), (len(ro), len(rs))
+        cap = n * seq_length if edit_capacity is None else int(edit_capacity)
+        if region_edit_off is None:
+            region_edit_off = np.zeros(len(rs) + 1, np.int64)
+        edits = np.zeros(max(cap, 1), EDIT_DTYPE)
+        if counts is None:
+            counts = (C.c_int64 * 4)()
+        _ffi.check(self.lib.pv_polish_edits(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rq), _ffi.ptr(rs), _ffi.ptr(ro),
+                                            _ffi.ptr(ref), len(rs), seq_length, seq_overlap, _ffi.ptr(region_edit_off),
+                                            _ffi.ptr(edits), cap, counts))
+        return region_edit_off, edits[:int(counts[0])].copy()
+
     def profile_begin(self, only: str = None):
         """bracket every kernel launch of this context with HIP events (only: just the kernels whose profile name starts
         with it - two events per launch put a few microseconds between kernels)"""

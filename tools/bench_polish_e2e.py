@@ -28,8 +28,13 @@
               the FASTA) in turn, twice each, then once more each way with the stitch and the row-quality calls bracketed by HIP events: what
               the flag adds on the device (pv_polish_row_qual_dev, the quality plane of the stitch) and on the wall.
 
+  --edits:    the same comparison for `polish --edits` (the edits VCF beside the FASTA): wall times of both forms, twice each,
+              then the stitch and the edit calls bracketed by HIP events, the records and the bytes that come back from the
+              device, and the VCF's size. The weights are random, so most rows are edits: the record count says nothing
+              about a trained model.
+
   python tools/bench_polish_e2e.py [--leg stitch|e2e|steps|all] [--mbp 2.0] [--reps 20] [--realign] [--d_ids 0,0] [--gpu_decode]
-                                   [--qualities] [--out f]
+                                   [--qualities] [--edits] [--out f]
 For the rocprofv3 row run the stitch leg alone under `rocprofv3 --kernel-trace --stats -d <dir> -- python ... --leg stitch`.
 """
 import argparse
@@ -117,11 +122,13 @@ def stitch_leg(reps=20):
                                      "stitch_ms": round(t_host * 1e3, 1)}}
 
 
-def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False, qualities=False):
+def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False, qualities=False, edits=False):
     # warm-up on a small region (code objects, allocator), then the timed run
     kw = {"gpu_decode": True} if gpu_decode else {}
     if qualities:
         kw["qualities"] = True
+    if edits:
+        kw["edits"] = True
     polish.polish_fused(bam, fa, model, out + "_warm", region="chr20:0-50000", threads=threads, ctx=ctx, realign=realign, **kw)
     T = {}
     t0 = time.perf_counter()
@@ -135,6 +142,13 @@ def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decod
     if qualities:
         fq = polish.output_fastq_path(path)
         res["qualities"], res["fastq_bytes"] = True, os.path.getsize(fq)
+    if edits:
+        from pepper_thesis_amd import polish_edits
+        vcf = polish_edits.output_vcf_path(path)
+        res.update(edits=True, edit_records=T["edit_records"], vcf_records=T["vcf_records"], vcf_bytes=os.path.getsize(vcf),
+                   tbi_bytes=os.path.getsize(vcf + ".tbi"),
+                   # 16 bytes a record and the region offsets of every launch
+                   edits_readback_bytes=16 * T["edit_records"] + 8 * (T["regions"] + T["batches"]))
     if gpu_decode:
         import hashlib
         import torch
@@ -201,14 +215,49 @@ def realign_stats(ctx, bam, fa, per_launch=1024):
             "band_gcups": round(band / (band_ms * 1e-3) / 1e9, 1) if band_ms else None}
 
 
-def _quality_events(polish, ctx, bam, fa, model, out, threads, qualities):
+def _quality_events(polish, ctx, bam, fa, model, out, threads, qualities, edits=False):
     """one more run with the calls whose profile names start with polish_ bracketed by HIP events -> {name: [ms, launches]}"""
     ctx.profile_begin("polish_")
     try:
-        polish.polish_fused(bam, fa, model, out, threads=threads, ctx=ctx, qualities=qualities)
+        polish.polish_fused(bam, fa, model, out, threads=threads, ctx=ctx, qualities=qualities, edits=edits)
     finally:
         pr = ctx.profile_end()
-    return {k: [round(v[0], 4), v[1]] for k, v in sorted(pr.items()) if k in ("polish_stitch", "polish_row_qual")}
+    return {k: [round(v[0], 4), v[1]] for k, v in sorted(pr.items()) if k in ("polish_stitch", "polish_row_qual", "polish_edits")}
+
+
+def edits_leg(mbp=3.0, threads=16):
+    """polish without and with --edits on one synthetic contig, in one process on the same files"""
+    import hashlib
+    import numpy as np
+    from bench_filepath import make_files
+    from pepper_thesis_amd import polish, runtime, synth
+    d = tempfile.mkdtemp(prefix="pv_polish_edits_")
+    try:
+        bam, fa, info = make_files(d, int(mbp * 1_000_000))
+        model = os.path.join(d, "model.npz")
+        np.savez(model, **synth.make_weights_p2(4321, 3.0))
+        ctx = runtime.Context(0)
+        try:
+            # the two forms alternate, twice each: the first timed run of a process also grows the workspace to the launch size
+            runs = []
+            for k in range(2):
+                for e in (False, True):
+                    r = _e2e_run(polish, ctx, bam, fa, model, os.path.join(d, "edits" if e else "plain"), threads, False, info, edits=e)
+                    runs.append(dict(r, edits=e, order=len(runs)))
+            res = {"runs": runs, "without_edits": runs[2], "with_edits": runs[3]}
+            sha = [hashlib.sha256(open(os.path.join(d, n, "_pepper_polished.fa"), "rb").read()).hexdigest() for n in ("plain", "edits")]
+            res["fasta_identical"] = sha[0] == sha[1]
+            res["event_ms_launches"] = {
+                "without_edits": _quality_events(polish, ctx, bam, fa, model, os.path.join(d, "plain_ev"), threads, False),
+                "with_edits": _quality_events(polish, ctx, bam, fa, model, os.path.join(d, "edits_ev"), threads, False, True)}
+            res["note"] = ("polish_stitch / polish_edits: count + scan + write kernels of one call; HIP events around every call of a "
+                           "run, summed over the run's launches. The weights are random: most rows are edits, so the record count "
+                           "and the bytes read back are far above what a trained model gives")
+            return res
+        finally:
+            ctx.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
 
 
 def qualities_leg(mbp=3.0, threads=16):
@@ -372,13 +421,17 @@ def main():
                     help="e2e leg: the device read path (polish --gpu_decode); adds the decode timers and the FASTA's sha256")
     ap.add_argument("--qualities", action="store_true",
                     help="e2e leg without and with polish --qualities, plus HIP-event times of the stitch and row-quality calls")
+    ap.add_argument("--edits", action="store_true",
+                    help="e2e leg without and with polish --edits, plus HIP-event times of the stitch and the edit calls")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON to this file")
     a = ap.parse_args()
     out = {}
     if a.leg in ("stitch", "all"):
         out["stitch"] = stitch_leg(a.reps)
     if a.leg in ("e2e", "all"):
-        if a.qualities:
+        if a.edits:
+            out["e2e"] = edits_leg(a.mbp, a.threads)
+        elif a.qualities:
             out["e2e"] = qualities_leg(a.mbp, a.threads)
         else:
             out["e2e"] = ranks_leg(a.mbp, a.threads, a.d_ids, a.realign) if a.d_ids else e2e_leg(a.mbp, a.threads, a.realign, a.gpu_decode)
