@@ -168,14 +168,41 @@ def polish_work(fasta, bam, region: Optional[str]) -> Tuple[List[Work], int]:
     return work, bases_in
 
 
-def merge_pieces(pieces) -> Dict[str, bytes]:
-    """(contig, region start, region index, polished bases) pieces, in any order -> one sequence per contig: the regions in
-    start order (create_consensus_sequence; their kept ranges are disjoint, so this is the reference's string), equal starts
-    (a region listed twice by -r) in region-list order"""
+class ChainResult(NamedTuple):
+    """what a chain's run / run_decoded give for one batch of regions. A plane the chain was not made for is None."""
+    region_off: np.ndarray                 # int64 [n_regions+1] into bases and qual
+    bases: object                          # anything sliceable by region_off: polished bases, or make_images' chunk list
+    qual: Optional[bytes] = None           # --qualities: one raw Phred byte per base
+    edit_off: Optional[np.ndarray] = None  # --edits: int64 [n_regions+1] into edits
+    edits: Optional[np.ndarray] = None     # --edits: polish_edits.EDIT_DTYPE records
+
+    def region(self, g: int) -> tuple:
+        """region g's share: (bases, qual or None, edits or None)"""
+        a, b = self.region_off[g], self.region_off[g + 1]
+        return (self.bases[a:b], None if self.qual is None else self.qual[a:b],
+                None if self.edits is None else self.edits[self.edit_off[g]:self.edit_off[g + 1]])
+
+
+class Piece(NamedTuple):
+    """one region with reads after the chain: its Work's contig, start and index, and its share of the ChainResult"""
+    contig: str
+    start: int
+    index: int
+    bases: object
+    qual: Optional[bytes] = None
+    edits: Optional[np.ndarray] = None
+
+
+def merge_pieces(pieces, part: int = 3) -> Dict[str, bytes]:
+    """pieces (Piece, or plain (contig, region start, region index, bytes) tuples), in any order -> one string per contig
+    of their entry `part` (3: the bases, 4: the qualities): the regions in start order (create_consensus_sequence; their
+    kept ranges are disjoint, so this is the reference's string), equal starts (a region listed twice by -r) in
+    region-list order"""
     by: Dict[str, list] = {}
-    for contig, start, index, seq in pieces:
-        by.setdefault(contig, []).append((start, index, seq))
-    return {c: b"".join(s for _, _, s in sorted(p, key=lambda t: (t[0], t[1]))) for c, p in by.items()}
+    for p in pieces:
+        contig, start, index = p[:3]
+        by.setdefault(contig, []).append((start, index, p[part]))
+    return {c: b"".join(s for _, _, s in sorted(v, key=lambda t: (t[0], t[1]))) for c, v in by.items()}
 
 
 def write_polished_fasta(path: str, pieces) -> Dict[str, bytes]:
@@ -200,16 +227,16 @@ def _contig_list(fasta, bam, region: Optional[str]):
 
 
 class _DeviceChain:
-    """device buffers of the builder -> GRU -> stitch chain, grown on demand. qualities: P2's accumulated softmax is kept,
-    turned into row qualities and stitched beside the bases; run / run_decoded then return (region_off, bases, qualities).
-    edits: the edit pass runs behind the stitch (with the row qualities when there are any); run / run_decoded then return
-    their usual tuple followed by the pair (region_edit_off, records as a polish_edits.EDIT_DTYPE array)."""
+    """device buffers of the builder -> GRU -> stitch chain, grown on demand; run / run_decoded return a ChainResult.
+    qualities: P2's accumulated softmax is kept, turned into row qualities and stitched beside the bases (the result's
+    qual). edits: the edit pass runs behind the stitch, with the row qualities when there are any (the result's edit_off
+    and edits)."""
 
     def __init__(self, ctx, own_ctx: bool = False, qualities: bool = False, edits: bool = False):
         import torch
         self.ctx, self.dev, self.own_ctx, self.qualities = ctx, "cuda:%d" % ctx.device_id, own_ctx, bool(qualities)
         self.edits = bool(edits)
-        self.edit_buf = self.edit_off = None
+        self.edit_buf = None
         self.edit_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.dout = self.labels = self.seq = None
         self.acc = self.row_qual = self.qual = None
@@ -235,16 +262,11 @@ class _DeviceChain:
                 self.edit_buf = torch.zeros((chunks * 1000, 16), dtype=torch.uint8, device=self.dev)
             torch.cuda.synchronize()   # the fills ran on torch's stream; the chain runs on the context's
 
-    def _summarize(self, batch, db, host_batch=None, sizes=None) -> int:
-        """builder on the device; -> n_chunks. A batch beyond the device form's workspace heuristics (PV_ERR_LIMIT: e.g. a
-        very long insert) runs the host form, which retries with measured bounds, and its chunks are uploaded.
-        host_batch: makes the host batch when `batch` is None (the realigned reads live on the device only).
-        sizes: (columns of all regions, regions) for the chunk estimate when neither `batch` nor db.host exists (a batch
-        decoded on the device: the sizes come from its plan)."""
+    def _summarize(self, db, sizes, host_batch) -> int:
+        """builder on the device; -> n_chunks. sizes: (columns of all regions, regions), for the chunk estimate. A batch
+        beyond the device form's workspace heuristics (PV_ERR_LIMIT: e.g. a very long insert) runs the host form on
+        host_batch(), which retries with measured bounds, and its chunks are uploaded."""
         from .polish_summary import polish_summarize
-        if sizes is None:
-            b = batch if batch is not None else db.host
-            sizes = int((b.ref_end - b.ref_start + 1).sum()), b.n_regions
         cols, n_regions = sizes
         want = (cols + cols // 2 + 1024) // 950 + 2 * n_regions + 2
         for _ in range(2):
@@ -260,23 +282,21 @@ class _DeviceChain:
                 return n
             want = n
         import torch
-        out = polish_summarize(self.ctx, batch if batch is not None else host_batch())
+        out = polish_summarize(self.ctx, host_batch())
         n = len(out.chunk_id)
         self._ensure(n)
         for name in ("images", "position", "index", "region", "chunk_id"):
             getattr(self.dout, name)[:n].copy_(torch.from_numpy(getattr(out, name)))
         return n
 
-    def _realign(self, batch, db, windows, qmax=None, host_batch=None):
-        """reads realigned to the draft on the device -> (host batch maker, device batch for the builder). The only read-back
-        is the counters (cigar total and status); the host batch is fetched only if the builder needs its host form.
-        batch None (a batch decoded on the device): qmax is its longest read and host_batch makes its host copy."""
+    def _realign(self, db, host_batch, qmax: int, windows):
+        """reads of at most qmax bases realigned to the draft on the device -> (maker of the realigned host batch, device
+        batch for the builder). The only read-back is the counters (cigar total and status); the host batch is made only
+        if the builder needs its host form."""
         import torch
         from .realign import DeviceRealignOut, RealignResult, device_windows, pack_windows, realigned_batch
         woff, win = pack_windows(windows)
         d_woff, d_win = device_windows(woff, win, self.dev)
-        if batch is not None:
-            qmax = int(np.diff(batch.base_off).max()) if batch.n_reads else 0
         n_reads = db.n_reads
         want = db.n_cigar + 4 * n_reads + db.n_bases // 8 + 16
         for _ in range(2):
@@ -303,7 +323,7 @@ class _DeviceChain:
         def host():
             res = RealignResult(ro.read_pos[:n].cpu().numpy(), ro.cigar_off[:n + 1].cpu().numpy(),
                                 ro.cigar[:total].cpu().numpy().view(np.uint32), None, None, None, 0, 0)
-            return realigned_batch(batch if batch is not None else host_batch(), res)
+            return realigned_batch(host_batch(), res)
         return host, rdb
 
     def p2_labels(self, images: np.ndarray) -> np.ndarray:
@@ -317,99 +337,75 @@ class _DeviceChain:
         labels, acc = self.ctx.forward_p2(images, want_acc=True)
         return labels, self.ctx.polish_row_qual(labels, acc, seq_overlap=50)
 
-    def build(self, batch, windows=None):
-        """[realignment ->] builder for one batch of regions -> (device batch, n_chunks); the chunks are in self.dout.
-        windows: the realignment window of every region (polish --realign), else None."""
-        from .device import DeviceBatch
-        db = DeviceBatch(batch, self.dev)
+    def _build(self, db, sizes, host_batch, qmax: int, windows):
+        """[realignment ->] builder -> (device batch, n_chunks); the chunks are in self.dout. sizes, host_batch: see
+        _summarize; qmax: the longest read, for the realigner; windows: the realignment window of every region (--realign), else None."""
         if windows is not None:
-            host, db = self._realign(batch, db, windows)
-            return db, self._summarize(None, db, host)
-        return db, self._summarize(batch, db)
+            host_batch, db = self._realign(db, host_batch, qmax, windows)
+        return db, self._summarize(db, sizes, host_batch)
+
+    def build(self, batch, windows=None):
+        """_build for one host batch of regions, uploaded here"""
+        from .device import DeviceBatch
+        sizes = int((batch.ref_end - batch.ref_start + 1).sum()), batch.n_regions
+        qmax = int(np.diff(batch.base_off).max()) if windows is not None and batch.n_reads else 0   # (the realigner's alone)
+        return self._build(DeviceBatch(batch, self.dev), sizes, lambda: batch, qmax, windows)
 
     def build_decoded(self, dec, windows=None):
-        """build for a gpu_decode.DecodedBatch: the reads are on the device already, the decode is ordered before the chain
-        with its event, read totals and the longest read come from the decode, region sizes from its plan"""
+        """_build for a gpu_decode.DecodedBatch: the reads are on the device already, the decode is ordered before the
+        chain with its event, the longest read comes from the decode, the region sizes from its plan (the polisher's
+        reference bytes are one per column of the region)"""
         dec.wait_on(self.ctx)
-        sizes = (dec.n_ref_bytes, dec.n_regions)   # (the polisher's reference bytes are one per column of the region)
+        return self._build(dec, (dec.n_ref_bytes, dec.n_regions), lambda: dec.to_host()[0], dec.qmax, windows)
 
-        def host_batch():
-            return dec.to_host()[0]
-        if windows is not None:
-            host, db = self._realign(None, dec, windows, dec.qmax, host_batch)
-            return db, self._summarize(None, db, host, sizes)
-        return dec, self._summarize(None, dec, host_batch, sizes)
-
-    def run(self, batch, windows=None) -> Tuple[np.ndarray, bytes]:
-        """one batch of regions -> (region_off [n_regions+1], polished bases of all its regions, concatenated).
-        windows: the realignment window of every region (polish --realign), else None."""
+    def run(self, batch, windows=None) -> ChainResult:
+        """one batch of regions -> its ChainResult: region_off [n_regions+1], the polished bases of all its regions,
+        concatenated, and the planes this chain was made for"""
         db, n = self.build(batch, windows)
         return self._labels_and_stitch(db, n, batch.n_regions)
 
-    def run_decoded(self, dec, windows=None) -> Tuple[np.ndarray, bytes]:
+    def run_decoded(self, dec, windows=None) -> ChainResult:
         """run for a gpu_decode.DecodedBatch"""
         db, n = self.build_decoded(dec, windows)
         return self._labels_and_stitch(db, n, dec.n_regions)
 
-    def _labels_and_stitch(self, db, n: int, n_regions: int):
-        region_off = np.zeros(n_regions + 1, np.int64)
-        if n == 0:
-            from .polish_edits import EDIT_DTYPE
-            return ((region_off, b"", b"") if self.qualities else (region_off, b"")) + (
-                ((region_off.copy(), np.zeros(0, EDIT_DTYPE)),) if self.edits else ())
+    def _labels_and_stitch(self, db, n: int, n_regions: int) -> ChainResult:
+        """P2 [-> row qualities] -> stitch [-> edits] over the first n chunks of self.dout on the context's stream, one
+        synchronize, then the read-back"""
         import torch
+        from .polish_edits import EDIT_DTYPE
+        if n == 0:   # nothing to launch: every plane this chain was made for, empty
+            zero = np.zeros(n_regions + 1, np.int64)
+            res = ChainResult(zero, b"", b"" if self.qualities else None)
+            return res._replace(edit_off=zero.copy(), edits=np.zeros(0, EDIT_DTYPE)) if self.edits else res
+        d_acc, d_row_qual, d_qual = (t.data_ptr() for t in (self.acc, self.row_qual, self.qual)) if self.qualities else (0, 0, 0)
+        d_labels, d_ref_start = self.labels.data_ptr(), db.t["ref_start"].data_ptr()
         roff = torch.empty(n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
+        self.ctx.forward_p2_dev(self.dout.images.data_ptr(), n, d_labels, d_acc)
         if self.qualities:
-            return self._labels_and_stitch_qual(db, n, n_regions, roff)
-        self.ctx.forward_p2_dev(self.dout.images.data_ptr(), n, self.labels.data_ptr())
-        self.ctx.polish_stitch_dev(self.dout, n, self.labels.data_ptr(), db.t["ref_start"].data_ptr(), n_regions,
-                                   roff.data_ptr(), self.seq.data_ptr(), self.seq.numel(), self.counts.data_ptr())
-        eoff = self._launch_edits(db, n, n_regions, 0)
+            # (a label above 4 is reported by the stitch where it is on a kept column, as without qualities: the counts of
+            # the row kernel are overwritten)
+            self.ctx.polish_row_qual_dev(d_labels, d_acc, n, d_row_qual, self.counts.data_ptr(), self.dout.seq_length,
+                                         self.dout.seq_overlap)
+        self.ctx.polish_stitch_dev(self.dout, n, d_labels, d_ref_start, n_regions, roff.data_ptr(), self.seq.data_ptr(),
+                                   self.seq.numel(), self.counts.data_ptr(), d_row_qual=d_row_qual, d_qual=d_qual)
+        if self.edits:
+            eoff = torch.empty(n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
+            self.ctx.polish_edits_dev(self.dout, n, d_labels, d_row_qual, d_ref_start, db.t["ref_off"].data_ptr(),
+                                      db.t["ref"].data_ptr(), n_regions, eoff.data_ptr(), self.edit_buf.data_ptr(),
+                                      self.edit_buf.shape[0], self.edit_counts.data_ptr())
         self.ctx.synchronize()   # raises if a split GRU form timed out (its labels are then poisoned)
         total, status, bad = (int(v) for v in self.counts[:3].tolist())
         if status != _ffi.PV_OK:   # capacity cannot run short: seq holds a byte for every column
             raise _ffi.PepperHipError(status, "polisher stitch: device status %d (chunk %d)" % (status, bad))
-        return (roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes()) + self._read_edits(eoff)
-
-    def _launch_edits(self, db, n: int, n_regions: int, d_row_qual: int):
-        """the edit pass behind the stitch on the context's stream (nothing without edits) -> its region offsets on the device"""
+        res = ChainResult(roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes(),
+                          self.qual[:total].cpu().numpy().tobytes() if self.qualities else None)
         if not self.edits:
-            return None
-        import torch
-        eoff = torch.empty(n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
-        self.ctx.polish_edits_dev(self.dout, n, self.labels.data_ptr(), d_row_qual, db.t["ref_start"].data_ptr(),
-                                  db.t["ref_off"].data_ptr(), db.t["ref"].data_ptr(), n_regions, eoff.data_ptr(),
-                                  self.edit_buf.data_ptr(), self.edit_buf.shape[0], self.edit_counts.data_ptr())
-        return eoff
-
-    def _read_edits(self, eoff) -> tuple:
-        """after the synchronize: () without edits, else ((region_edit_off, records),)"""
-        if eoff is None:
-            return ()
-        from .polish_edits import EDIT_DTYPE
+            return res
         total, status, bad = (int(v) for v in self.edit_counts[:3].tolist())
         if status != _ffi.PV_OK:   # capacity cannot run short: a record for every chunk row
             raise _ffi.PepperHipError(status, "polisher edits: device status %d (chunk %d)" % (status, bad))
-        return ((eoff.cpu().numpy(), self.edit_buf[:total].cpu().numpy().view(EDIT_DTYPE).reshape(-1)),)
-
-    def _labels_and_stitch_qual(self, db, n: int, n_regions: int, roff):
-        """_labels_and_stitch with the quality plane: P2 keeps its accumulated softmax, the row-quality kernel reads it with
-        the labels, and the stitch carries the row qualities beside the bases"""
-        self.ctx.forward_p2_dev(self.dout.images.data_ptr(), n, self.labels.data_ptr(), self.acc.data_ptr())
-        # (a label above 4 is reported by the stitch where it is on a kept column, as without qualities: the counts of the row
-        # kernel are overwritten)
-        self.ctx.polish_row_qual_dev(self.labels.data_ptr(), self.acc.data_ptr(), n, self.row_qual.data_ptr(), self.counts.data_ptr(),
-                                     self.dout.seq_length, self.dout.seq_overlap)
-        self.ctx.polish_stitch_qual_dev(self.dout, n, self.labels.data_ptr(), self.row_qual.data_ptr(), db.t["ref_start"].data_ptr(),
-                                        n_regions, roff.data_ptr(), self.seq.data_ptr(), self.qual.data_ptr(), self.seq.numel(),
-                                        self.counts.data_ptr())
-        eoff = self._launch_edits(db, n, n_regions, self.row_qual.data_ptr())
-        self.ctx.synchronize()
-        total, status, bad = (int(v) for v in self.counts[:3].tolist())
-        if status != _ffi.PV_OK:
-            raise _ffi.PepperHipError(status, "polisher stitch: device status %d (chunk %d)" % (status, bad))
-        return (roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes(),
-                self.qual[:total].cpu().numpy().tobytes()) + self._read_edits(eoff)
+        return res._replace(edit_off=eoff.cpu().numpy(), edits=self.edit_buf[:total].cpu().numpy().view(EDIT_DTYPE).reshape(-1))
 
 
 def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int, qualities: bool = False,
@@ -418,9 +414,8 @@ def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype:
     shared_device: other ranks use this GPU too, so the option is set before the first device call (the split GRU forms need
     co-resident workgroups and would time out, poisoning the labels). False leaves the create-time default (PV_SHARED_DEVICE).
     This is the default `open_chain` of run and polish_rank.run; CPU tests pass a stub with the same signature, whose result
-    has run(batch, windows) -> (region_off, bases) and close(). qualities (passed only when set): the chain of --qualities,
-    whose run gives (region_off, bases, qualities). edits (passed only when set): the chain of --edits, whose run's result
-    ends with the pair (region_edit_off, records)."""
+    has run(batch, windows) -> ChainResult and close(). qualities, edits (each passed only when set): the chain of
+    --qualities / --edits, whose results carry those planes."""
     from .runtime import Context
     ctx = Context(device)
     try:
@@ -437,7 +432,7 @@ class _RealignedDeviceBatch:
     """a DeviceBatch whose positions and cigars are the realigner's output (same bases, quals, flags, mapq, regions)"""
 
     def __init__(self, c, db, n_cigar, keep):
-        self.c, self.host, self._keep = c, getattr(db, "host", None), (db, keep)
+        self.c, self._keep = c, (db, keep)
         self.n_reads, self.n_bases, self.n_cigar, self.n_ref_bytes = db.n_reads, db.n_bases, int(n_cigar), db.n_ref_bytes
         self.max_region_len = db.max_region_len
         self.t = db.t
@@ -454,47 +449,48 @@ def _read_ahead(ex, fn, items, depth):
         yield f.result()
 
 
-def _region_parts(res, g: int, qualities: bool, edits: bool) -> tuple:
-    """region g's share of a chain result: (bases[, qualities][, edit records])"""
-    roff = res[0]
-    parts = tuple(p[roff[g]:roff[g + 1]] for p in res[1:2 + bool(qualities)])
-    if edits:
-        eoff, recs = res[-1]
-        parts += (recs[eoff[g]:eoff[g + 1]],)
-    return parts
+def _timers(timers: Optional[dict], more=()) -> dict:
+    """the caller's timer dict (or a fresh one) with the keys of polish_pieces, and `more`, present"""
+    T = timers if timers is not None else {}
+    for k in ("read_s", "device_s", "regions", "batches") + tuple(more):
+        T.setdefault(k, 0)
+    return T
+
+
+def _thread_handles(bam: str, fasta: str):
+    """-> handles(): the calling thread's own (BamHandler, FastaHandler); the native handles are not shared between threads"""
+    import threading
+    from .bamio import BamHandler, FastaHandler
+    local = threading.local()
+
+    def handles():
+        if not hasattr(local, "h"):
+            local.h = (BamHandler(bam), FastaHandler(fasta))
+        return local.h
+    return handles
 
 
 def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int = 2048, threads: int = 5, realign: bool = False,
-                  timers: Optional[dict] = None, gpu_decode: bool = False, open_decoder=None, qualities: bool = False,
-                  edits: bool = False):
-    """the regions of `work` through the chain -> (contig, region start, region index, polished bases) for every region with
-    reads, in `work` order. This is the whole device part of a run: the single-rank run passes every region, a rank of a
-    multi-device run its share. chain.run(batch, windows) -> (region_off, bases) (_DeviceChain or a CPU test's stub).
+                  timers: Optional[dict] = None, gpu_decode: bool = False, open_decoder=None):
+    """the regions of `work` through the chain -> a Piece for every region with reads, in `work` order. This is the whole
+    device part of a run: the single-rank run passes every region, a rank of a multi-device run its share.
+    chain.run(batch, windows) -> ChainResult (_DeviceChain or a CPU test's stub); a piece carries the planes that result
+    carried (qual with a chain made for --qualities, edits with one made for --edits, else None).
     timers (optional) accumulates read_s, device_s, regions, batches.
     gpu_decode: the device read path (_decoded_pieces): the reader threads only plan, the BAM is inflated, decoded and clipped
     on chain.ctx's device, and the chain takes the batches where they are (chain.run_decoded). open_decoder(T): the decoder,
     by default a gpu_decode.GpuDecoder with the polisher's settings (CPU tests pass a stub with its scan_groups, realize,
-    iterate and close).
-    qualities: the chain's run gives (region_off, bases, qualities), and every piece carries its raw Phred bytes as a fifth
-    entry.
-    edits: the chain's result ends with (region_edit_off, records), and every piece carries its records as its last entry."""
+    iterate and close)."""
     if gpu_decode:
-        yield from _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder, qualities, edits)
+        yield from _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder)
         return
     from .batch import pack_regions
-    from .bamio import BamHandler, FastaHandler
     from .polish_summary import region_from_files
-    T = timers if timers is not None else {}
-    for k in ("read_s", "device_s", "regions", "batches"):
-        T.setdefault(k, 0)
-    # one reader per thread: the native BAM/FASTA handles are not shared between threads
-    import threading
-    local = threading.local()
+    T = _timers(timers)
+    handles = _thread_handles(bam, fasta)
 
     def read(w):
-        if not hasattr(local, "h"):
-            local.h = (BamHandler(bam), FastaHandler(fasta))
-        return w, region_from_files(local.h[0], local.h[1], w.contig, w.start, w.end, realign=realign)
+        return w, region_from_files(*handles(), w.contig, w.start, w.end, realign=realign)
 
     per_launch = max(1, int(batch_size) // 2)
 
@@ -502,7 +498,7 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
         t0 = time.perf_counter()
         regs = [r for _, r in items]
         res = chain.run(pack_regions(regs), [r.window for r in regs] if realign else None)
-        out = [(w.contig, w.start, w.index) + _region_parts(res, g, qualities, edits) for g, (w, _) in enumerate(items)]
+        out = [Piece(w.contig, w.start, w.index, *res.region(g)) for g, (w, _) in enumerate(items)]
         T["device_s"] += time.perf_counter() - t0
         T["batches"] += 1
         return out
@@ -525,32 +521,25 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
             yield from flush(pending)
 
 
-def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder, qualities=False, edits=False):
+def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder):
     """polish_pieces' device read path. Reader threads plan reader groups (gpu_decode.region_groups: blocks, interval table,
     draft bytes, realign windows); the decoder's service thread scans them, cuts the regions with reads into the launches
     the host path makes (per_launch regions each) and fills them on its own stream; this thread runs the chain on every
     part of a launch: a decoded batch as it lies on the device, a host-route group (reads longer than the plan's look-ahead,
     or a group over the workspace budget) as the host path's packed batch. Adds the timers plan_s, decode_s, chain_runs
     (chain runs: one per part of a launch) and the decoder's own (gpu_decode_groups_host, gpu_decode_slot_retries, gpu_decode_ws_peak_bytes, ...)."""
-    import threading
     from . import gpu_decode as gd
-    from .bamio import BamHandler, FastaHandler
     from .polish_summary import MAX_READS_IN_REGION
-    T = timers if timers is not None else {}
-    for k in ("read_s", "device_s", "regions", "batches", "chain_runs", "plan_s", "decode_s", "gpu_decode_groups", "gpu_decode_groups_host"):
-        T.setdefault(k, 0)
+    T = _timers(timers, ("chain_runs", "plan_s", "decode_s", "gpu_decode_groups", "gpu_decode_groups_host"))
     per_launch = max(1, int(batch_size) // 2)
     if open_decoder is None:
         def open_decoder(T):
             return gd.GpuDecoder(chain.ctx, bam, fasta, 0, False, 1.0, 0, T, max_reads=MAX_READS_IN_REGION, adaptive_slots=True,
                                  realign=realign)
-    local = threading.local()
+    handles = _thread_handles(bam, fasta)
 
     def plan(ws):
-        if not hasattr(local, "h"):
-            local.h = (BamHandler(bam), FastaHandler(fasta))
-        return gd.PlannedGroup(local.h[0], local.h[1], [(w.contig, w.start, w.end) for w in ws], 0, pad_ref=True,
-                               windows=realign, works=ws)
+        return gd.PlannedGroup(*handles(), [(w.contig, w.start, w.end) for w in ws], 0, pad_ref=True, windows=realign, works=ws)
 
     groups = gd.region_groups(work)
     dec = open_decoder(T)
@@ -571,7 +560,7 @@ def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timer
                     T["chain_runs"] += 1
                     T["regions"] += len(ws)
                     for g, w in enumerate(ws):
-                        yield (w.contig, w.start, w.index) + _region_parts(res, g, qualities, edits)
+                        yield Piece(w.contig, w.start, w.index, *res.region(g))
                 T["device_s"] += time.perf_counter() - t0
                 T["batches"] += 1
                 del parts
@@ -597,9 +586,11 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
     realign: realign every read to the draft on the device before the builder, as the reference always does.
     chain: a chain with the weights already loaded (open_device_chain; the caller closes it), else one is made on `ctx`
     (default: a context on device 0) from model_path. gpu_decode: polish_pieces' device read path.
-    qualities: also write the FASTQ beside the FASTA (output_fastq_path); a chain passed in must have been made for it.
-    edits: also write the edits VCF and its index beside the FASTA (polish_edits.output_vcf_path); likewise. The VCF is
-    composed before any file is written, so a run it refuses (overlapping -r ranges of one contig) leaves nothing."""
+    qualities: also write the FASTQ beside the FASTA (output_fastq_path).
+    edits: also write the edits VCF and its index beside the FASTA (polish_edits.output_vcf_path). The VCF is composed
+    before any file is written, so a run it refuses (overlapping -r ranges of one contig) leaves nothing.
+    The two flags make this function's own chain and pick the files; a chain passed in whose results lack a plane they
+    need is refused (ValueError) before any file is written."""
     from .bamio import BamHandler, FastaHandler
     from .runtime import Context
     t_start = time.perf_counter()
@@ -616,19 +607,21 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
         work, T["bases_in"] = polish_work(fa, bm, region)
         out_path = output_fasta_path(out_prefix)
         log("POLISHING %d REGIONS, OUTPUT: %s" % (len(work), out_path))
-        pieces = list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode,
-                                    qualities=qualities, edits=edits))
+        pieces = list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode))
+        for want, plane in ((qualities, "qual"), (edits, "edits")):
+            if want and pieces and getattr(pieces[0], plane) is None:
+                raise ValueError("polish_fused: the chain's results have no %s plane: it was not made for this run" % plane)
         vcf = _edits_vcf(fa, fasta, work, pieces, qualities) if edits else None
     finally:
         if own is not None:
             own.close()
-    seqs = write_polished_fasta(out_path, [p[:4] for p in pieces])
+    seqs = write_polished_fasta(out_path, pieces)
     if qualities:
-        write_fastq(output_fastq_path(out_path), seqs, merge_pieces(p[:3] + (p[4],) for p in pieces))
+        write_fastq(output_fastq_path(out_path), seqs, merge_pieces(pieces, part=4))
     if edits:
         from . import polish_edits
         polish_edits.write_edits_vcf(polish_edits.output_vcf_path(out_path), *vcf)
-        T["edit_records"], T["vcf_records"] = sum(len(p[-1]) for p in pieces), sum(len(r) for r in vcf[-1].values())
+        T["edit_records"], T["vcf_records"] = sum(len(p.edits) for p in pieces), sum(len(r) for r in vcf[-1].values())
     T["bases_out"] = sum(len(s) for s in seqs.values())
     T["wall_s"] = time.perf_counter() - t_start
     if timers is not None:
@@ -644,13 +637,13 @@ def _edits_vcf(fa, fasta_path: str, work: List[Work], pieces, qualities: bool) -
     from . import polish_edits
     names = list(dict.fromkeys(w.contig for w in work))
     contigs = [(c, fa.get_chromosome_sequence_length(c)) for c in names]
-    done = {p[2] for p in pieces}
+    done = {p.index for p in pieces}
     no_reads = polish_edits.no_read_runs(
         (w.contig, w.start + 2 * MIN_IMAGE_OVERLAP + 1 if w.start > 0 else w.start, w.end)
         for w in work if w.index not in done)
     by: Dict[str, list] = {}
     for p in pieces:
-        by.setdefault(p[0], []).append((p[1], p[2], p[-1]))
+        by.setdefault(p.contig, []).append((p.start, p.index, p.edits))
     records = {}
     for c, length in contigs:
         if c in by:

@@ -178,9 +178,9 @@ def _exchange(dist, rank: int, world: int, pieces, work, out_path) -> Optional[d
     import torch
     from . import polish
     from .dist import _gather_padded
-    table = torch.tensor([[work[i].contig_index, start, len(seq), i] for _, start, i, seq in pieces],
+    table = torch.tensor([[work[p.index].contig_index, p.start, len(p.bases), p.index] for p in pieces],
                          dtype=torch.int64).reshape(len(pieces), 4)
-    blob = np.frombuffer(b"".join(seq for _, _, _, seq in pieces), dtype=np.uint8)
+    blob = np.frombuffer(b"".join(p.bases for p in pieces), dtype=np.uint8)
     data = torch.from_numpy(blob.copy())
     counts = [torch.zeros(2, dtype=torch.int64) for _ in range(world)]
     dist.all_gather(counts, torch.tensor([len(pieces), blob.size], dtype=torch.int64))
@@ -199,7 +199,7 @@ def _exchange(dist, rank: int, world: int, pieces, work, out_path) -> Optional[d
             if w.contig_index != ci or w.start != start or i % world != r:
                 raise RuntimeError("polish exchange: rank %d sent region %d as (%d, %d); rank 0 has (%d, %d)"
                                    % (r, i, ci, start, w.contig_index, w.start))
-            merged.append((w.contig, start, i, buf[off:off + length].tobytes()))
+            merged.append(polish.Piece(w.contig, start, i, buf[off:off + length].tobytes()))
             off += length
         if off != nb:
             raise RuntimeError("polish exchange: rank %d sent %d bytes for pieces of %d" % (r, nb, off))
@@ -247,7 +247,7 @@ def run(args, open_chain=None, timeout_s: float = EXCHANGE_TIMEOUT_S) -> int:
         if polish.decode_report(T):
             polish.log("[RANK %d/%d] %s" % (rank, world, polish.decode_report(T)))
         polish.log("[RANK %d/%d] POLISHED %d REGIONS, %d BASES (%.2f SEC)"
-                   % (rank, world, T["regions"], sum(len(p[3]) for p in pieces), time.perf_counter() - t0))
+                   % (rank, world, T["regions"], sum(len(p.bases) for p in pieces), time.perf_counter() - t0))
         try:
             seqs = _exchange(dist, rank, world, pieces, work, out_path)
         except Exception as e:

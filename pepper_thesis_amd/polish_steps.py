@@ -79,8 +79,8 @@ def _remove(paths):
 # ---- make_images ------------------------------------------------------------------------------------------------------
 
 class _ImageChain:
-    """the chain contract of polish.polish_pieces (run(batch, windows) -> (region_off, per-region slices), close()) over the
-    builder of polish's device chain: region_off are chunk offsets, the slices lists of (image, position, index, chunk_id)"""
+    """the chain contract of polish.polish_pieces (run(batch, windows) -> polish.ChainResult, close()) over the builder of
+    polish's device chain: region_off are chunk offsets, and `bases` is the list of (image, position, index, chunk_id)"""
 
     def __init__(self, chain):
         self.chain = chain
@@ -99,12 +99,13 @@ class _ImageChain:
         return self.chain.ctx
 
     def _chunks(self, n, n_regions):
+        from .polish import ChainResult
         d = self.chain.dout
         region = d.region[:n].cpu().numpy()
         images, position = d.images[:n].cpu().numpy(), d.position[:n].cpu().numpy()
         index, chunk_id = d.index[:n].cpu().numpy(), d.chunk_id[:n].cpu().numpy()
         region_off = np.searchsorted(region, np.arange(n_regions + 1), side="left")   # the builder emits regions ascending
-        return region_off, [(images[k], position[k], index[k], int(chunk_id[k])) for k in range(n)]
+        return ChainResult(region_off, [(images[k], position[k], index[k], int(chunk_id[k])) for k in range(n)])
 
     def close(self):
         self.chain.close()
@@ -135,12 +136,11 @@ def make_images(bam: str, fasta: str, region: Optional[str], output_dir: str, th
     try:
         stores = [PolishImageStore(p + ".partial", "w") for p in paths]
         T = {}
-        for contig, _, i, chunks in polish.polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T,
-                                                         gpu_decode=gpu_decode):
-            w = work[i]
-            for image, position, index, chunk_id in chunks:
-                stores[i % threads].write_chunk(contig, w.start, w.end, chunk_id, image, position, index)
-            n_chunks += len(chunks)
+        for p in polish.polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode):
+            w = work[p.index]
+            for image, position, index, chunk_id in p.bases:
+                stores[p.index % threads].write_chunk(p.contig, w.start, w.end, chunk_id, image, position, index)
+            n_chunks += len(p.bases)
         for s in stores:
             s.close()
         for p in paths:
@@ -450,8 +450,8 @@ def _layout(group, qualities: bool = False) -> StitchLayout:
 
 
 def stitch_layout_bases(ctx, lay: StitchLayout, qualities: bool = False):
-    """pv_polish_stitch on one layout -> the polished bases of every region. A kept label above 4 is refused by the kernel
-    (PV_ERR_STATE) and reported with the chunk it is in.
+    """pv_polish_stitch on one layout -> (polished bases, None) of every region. A kept label above 4 is refused by the
+    kernel (PV_ERR_STATE) and reported with the chunk it is in.
     qualities: pv_polish_stitch_qual with the layout's row_qual -> (bases, raw Phred bytes) of every region."""
     import ctypes as C
     from .polish_summary import PolishOut
@@ -461,16 +461,14 @@ def stitch_layout_bases(ctx, lay: StitchLayout, qualities: bool = False):
         if qualities:
             roff, seq, qual = ctx.polish_stitch_qual(out, lay.labels, lay.row_qual, lay.region_start, counts=counts)
         else:
-            roff, seq = ctx.polish_stitch(out, lay.labels, lay.region_start, counts=counts)
+            (roff, seq), qual = ctx.polish_stitch(out, lay.labels, lay.region_start, counts=counts), None
     except _ffi.PepperHipError as e:
         bad = int(counts[2])
         if e.code == _ffi.PV_ERR_STATE and 0 <= bad < len(lay.chunk_names):
             ref = lay.regions[int(lay.region[bad])]
             raise ValueError("%s: chunk %s holds a label above 4" % (ref.path, lay.chunk_names[bad])) from None
         raise
-    if qualities:
-        return [(seq[roff[g]:roff[g + 1]], qual[roff[g]:roff[g + 1]]) for g in range(len(lay.regions))]
-    return [seq[roff[g]:roff[g + 1]] for g in range(len(lay.regions))]
+    return [(seq[a:b], None if qual is None else qual[a:b]) for a, b in zip(roff[:-1], roff[1:])]
 
 
 def stitch(input_dir: str, output_file: str, ctx=None, qualities: bool = False) -> str:
@@ -485,7 +483,7 @@ def stitch(input_dir: str, output_file: str, ctx=None, qualities: bool = False) 
     try:
         for contig in sorted(by, key=natural_key):
             log("PROCESSING CONTIG: " + contig)
-            parts: List[bytes] = []
+            parts: List[Tuple[bytes, Optional[bytes]]] = []
             for lay in stitch_layouts(by[contig], qualities=qualities):
                 if ctx is None:
                     from .runtime import Context
@@ -493,8 +491,7 @@ def stitch(input_dir: str, output_file: str, ctx=None, qualities: bool = False) 
                 parts += stitch_layout_bases(ctx, lay, qualities)
             if qualities:
                 quals[contig] = b"".join(q for _, q in parts)
-                parts = [s for s, _ in parts]
-            seqs[contig] = b"".join(parts)
+            seqs[contig] = b"".join(s for s, _ in parts)
             log("FINISHED PROCESSING %s, POLISHED SEQUENCE LENGTH: %d." % (contig, len(seqs[contig])))
     finally:
         if own is not None:

@@ -338,24 +338,33 @@ class Context:
                                             C.byref(out), d_read_hp, d_totals, stream or None))
 
     def polish_stitch_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_region_start: int, n_regions: int,
-                          d_region_off: int, d_seq: int, seq_capacity: int, d_counts: int, stream: int = 0):
+                          d_region_off: int, d_seq: int, seq_capacity: int, d_counts: int, stream: int = 0, d_row_qual: int = 0,
+                          d_qual: int = 0):
         """asynchronous, device-resident stitch (pv_polish_stitch_dev): the labels of dout's first n_chunks chunks -> polished
-        bases in d_seq, region offsets in d_region_off [n_regions+1], {bases, status, first bad chunk, 0} in d_counts."""
-        _ffi.check(self.lib.pv_polish_stitch_dev(
-            self.handle, C.byref(dout.c), int(n_chunks), d_labels, d_region_start, int(n_regions), dout.seq_length,
-            dout.seq_overlap, d_region_off, d_seq, int(seq_capacity), d_counts, stream or None))
+        bases in d_seq, region offsets in d_region_off [n_regions+1], {bases, status, first bad chunk, 0} in d_counts.
+        With d_row_qual (uint8 [n_chunks, L]) and d_qual (uint8 [seq_capacity]) the quality plane too
+        (pv_polish_stitch_qual_dev): one raw Phred byte in d_qual for every base of d_seq."""
+        args = (self.handle, C.byref(dout.c), int(n_chunks), d_labels, d_region_start, int(n_regions), dout.seq_length,
+                dout.seq_overlap, d_region_off, d_seq, int(seq_capacity), d_counts, stream or None)
+        if d_row_qual or d_qual:
+            _ffi.check(self.lib.pv_polish_stitch_qual_dev(*args, d_row_qual or None, d_qual or None))
+        else:
+            _ffi.check(self.lib.pv_polish_stitch_dev(*args))
 
-    def polish_stitch(self, out, labels: np.ndarray, region_start: np.ndarray, seq_capacity: int = None,
-                      seq_length: int = 1000, seq_overlap: int = 50, counts=None):
-        """host-buffer stitch (pv_polish_stitch) of a PolishOut and its labels -> (region_off int64 [n_regions+1], seq bytes).
-        seq_capacity None: every column's worth; a smaller one raises PepperHipError(PV_ERR_CAPACITY).
-        counts: optional ctypes int64[4] that receives {bases, status, first bad chunk, 0}, also when the call raises."""
-        n = int(len(out.chunk_id))
+    @staticmethod
+    def _host_polish_out(out):
+        """the host pv_polish_out view of a PolishOut's position, index, region and chunk_id -> (n_chunks, struct, the
+        arrays it points into: keep them until the call returns)"""
+        keep = [np.ascontiguousarray(a, t) for a, t in ((out.position, np.int64), (out.index, np.int32), (out.region, np.int32),
+                                                        (out.chunk_id, np.int32))]
         c = _ffi.pv_polish_out()
-        keep = [np.ascontiguousarray(out.position, np.int64), np.ascontiguousarray(out.index, np.int32),
-                np.ascontiguousarray(out.region, np.int32), np.ascontiguousarray(out.chunk_id, np.int32)]
-        c.chunk_capacity = n
+        c.chunk_capacity = n = int(len(out.chunk_id))
         c.position, c.index, c.region, c.chunk_id = (_ffi.ptr(a) for a in keep)
+        return n, c, keep
+
+    def _polish_stitch(self, out, labels, row_qual, region_start, seq_capacity, seq_length, seq_overlap, counts):
+        """polish_stitch (row_qual None) / polish_stitch_qual -> (region_off, seq bytes[, qual bytes])"""
+        n, c, keep = self._host_polish_out(out)
         lab = np.ascontiguousarray(labels, np.uint8)
         rs = np.ascontiguousarray(region_start, np.int64)
         assert lab.shape == (n, seq_length), lab.shape
@@ -364,9 +373,23 @@ class Context:
         seq = np.zeros(max(cap, 1), np.uint8)
         if counts is None:
             counts = (C.c_int64 * 4)()
-        _ffi.check(self.lib.pv_polish_stitch(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rs), len(rs), seq_length,
-                                             seq_overlap, _ffi.ptr(region_off), _ffi.ptr(seq), cap, counts))
-        return region_off, seq[:int(counts[0])].tobytes()
+        args = (self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rs), len(rs), seq_length, seq_overlap, _ffi.ptr(region_off),
+                _ffi.ptr(seq), cap, counts)
+        if row_qual is None:
+            _ffi.check(self.lib.pv_polish_stitch(*args))
+            return region_off, seq[:int(counts[0])].tobytes()
+        rq = np.ascontiguousarray(row_qual, np.uint8)
+        assert rq.shape == lab.shape, (lab.shape, rq.shape)
+        qual = np.zeros(max(cap, 1), np.uint8)
+        _ffi.check(self.lib.pv_polish_stitch_qual(*args, _ffi.ptr(rq), _ffi.ptr(qual)))
+        return region_off, seq[:int(counts[0])].tobytes(), qual[:int(counts[0])].tobytes()
+
+    def polish_stitch(self, out, labels: np.ndarray, region_start: np.ndarray, seq_capacity: int = None,
+                      seq_length: int = 1000, seq_overlap: int = 50, counts=None):
+        """host-buffer stitch (pv_polish_stitch) of a PolishOut and its labels -> (region_off int64 [n_regions+1], seq bytes).
+        seq_capacity None: every column's worth; a smaller one raises PepperHipError(PV_ERR_CAPACITY).
+        counts: optional ctypes int64[4] that receives {bases, status, first bad chunk, 0}, also when the call raises."""
+        return self._polish_stitch(out, labels, None, region_start, seq_capacity, seq_length, seq_overlap, counts)
 
     def polish_row_qual_dev(self, d_labels: int, d_acc: int, B: int, d_qual: int, d_counts: int, seq_length: int = 1000,
                             seq_overlap: int = 50, stream: int = 0):
@@ -391,35 +414,14 @@ class Context:
     def polish_stitch_qual_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_row_qual: int, d_region_start: int,
                                n_regions: int, d_region_off: int, d_seq: int, d_qual: int, seq_capacity: int, d_counts: int,
                                stream: int = 0):
-        """polish_stitch_dev with the quality plane (pv_polish_stitch_qual_dev): d_row_qual uint8 [n_chunks, L] in, d_qual
-        uint8 [seq_capacity] out, one raw Phred byte for every base of d_seq."""
-        _ffi.check(self.lib.pv_polish_stitch_qual_dev(
-            self.handle, C.byref(dout.c), int(n_chunks), d_labels, d_region_start, int(n_regions), dout.seq_length,
-            dout.seq_overlap, d_region_off, d_seq, int(seq_capacity), d_counts, stream or None, d_row_qual, d_qual))
+        """polish_stitch_dev with the quality plane, in the C entry point's argument order"""
+        self.polish_stitch_dev(dout, n_chunks, d_labels, d_region_start, n_regions, d_region_off, d_seq, seq_capacity, d_counts,
+                               stream, d_row_qual, d_qual)
 
     def polish_stitch_qual(self, out, labels: np.ndarray, row_qual: np.ndarray, region_start: np.ndarray, seq_capacity: int = None,
                            seq_length: int = 1000, seq_overlap: int = 50, counts=None):
         """polish_stitch with the quality plane (pv_polish_stitch_qual) -> (region_off, seq bytes, qual bytes: raw Phred)."""
-        n = int(len(out.chunk_id))
-        c = _ffi.pv_polish_out()
-        keep = [np.ascontiguousarray(out.position, np.int64), np.ascontiguousarray(out.index, np.int32),
-                np.ascontiguousarray(out.region, np.int32), np.ascontiguousarray(out.chunk_id, np.int32)]
-        c.chunk_capacity = n
-        c.position, c.index, c.region, c.chunk_id = (_ffi.ptr(a) for a in keep)
-        lab = np.ascontiguousarray(labels, np.uint8)
-        rq = np.ascontiguousarray(row_qual, np.uint8)
-        rs = np.ascontiguousarray(region_start, np.int64)
-        assert lab.shape == (n, seq_length) and rq.shape == lab.shape, (lab.shape, rq.shape)
-        cap = n * seq_length if seq_capacity is None else int(seq_capacity)
-        region_off = np.zeros(len(rs) + 1, np.int64)
-        seq = np.zeros(max(cap, 1), np.uint8)
-        qual = np.zeros(max(cap, 1), np.uint8)
-        if counts is None:
-            counts = (C.c_int64 * 4)()
-        _ffi.check(self.lib.pv_polish_stitch_qual(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rs), len(rs), seq_length,
-                                                  seq_overlap, _ffi.ptr(region_off), _ffi.ptr(seq), cap, counts, _ffi.ptr(rq),
-                                                  _ffi.ptr(qual)))
-        return region_off, seq[:int(counts[0])].tobytes(), qual[:int(counts[0])].tobytes()
+        return self._polish_stitch(out, labels, row_qual, region_start, seq_capacity, seq_length, seq_overlap, counts)
 
     def polish_edits_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_row_qual: int, d_region_start: int,
                          d_ref_off: int, d_ref: int, n_regions: int, d_region_edit_off: int, d_edits: int, edit_capacity: int,
@@ -440,12 +442,7 @@ class Context:
         counts: optional ctypes int64[4] that receives {edits, status, first bad chunk, 0}, and region_edit_off an optional
         int64 [n_regions+1] array that receives the offsets, also when the call raises."""
         from .polish_edits import EDIT_DTYPE
-        n = int(len(out.chunk_id))
-        c = _ffi.pv_polish_out()
-        keep = [np.ascontiguousarray(out.position, np.int64), np.ascontiguousarray(out.index, np.int32),
-                np.ascontiguousarray(out.region, np.int32), np.ascontiguousarray(out.chunk_id, np.int32)]
-        c.chunk_capacity = n
-        c.position, c.index, c.region, c.chunk_id = (_ffi.ptr(a) for a in keep)
+        n, c, keep = self._host_polish_out(out)
         lab = np.ascontiguousarray(labels, np.uint8)
         rq = None if row_qual is None else np.ascontiguousarray(row_qual, np.uint8)
         rs = np.ascontiguousarray(batch.ref_start, np.int64)

@@ -205,11 +205,11 @@ class _Chain:
     def run(self, batch, windows=None):
         starts = [int(s) for s in batch.ref_start]
         self.calls.append((self.T.get("batches", 0), "host", list(zip(batch.contigs, starts)), windows))
-        return np.arange(len(starts) + 1), b"".join(b"%d" % (s % 10) for s in starts)
+        return polish.ChainResult(np.arange(len(starts) + 1), b"".join(b"%d" % (s % 10) for s in starts))
 
     def run_decoded(self, dec, windows=None):
         self.calls.append((self.T.get("batches", 0), "dev", list(dec), windows))
-        return np.arange(len(dec) + 1), b"".join(b"%d" % (s % 10) for _, s in dec)
+        return polish.ChainResult(np.arange(len(dec) + 1), b"".join(b"%d" % (s % 10) for _, s in dec))
 
 
 class _Decoder:

@@ -188,8 +188,8 @@ class _EditingChain:
             out.append(s.encode())
             roff.append(roff[-1] + len(s))
             eoff.append(len(recs))
-        res = (np.asarray(roff, np.int64), b"".join(out))
-        return res + ((np.asarray(eoff, np.int64), np.array(recs, pe.EDIT_DTYPE)),) if self.edits else res
+        res = polish.ChainResult(np.asarray(roff, np.int64), b"".join(out))
+        return res._replace(edit_off=np.asarray(eoff, np.int64), edits=np.array(recs, pe.EDIT_DTYPE)) if self.edits else res
 
     def close(self):
         pass

@@ -25,7 +25,7 @@ def _free_port():
 
 
 class _StubChain:
-    """the chain's contract (run(batch, windows) -> (region_off, bases), close()) without a device; records every region"""
+    """the chain's contract (run(batch, windows) -> ChainResult, close()) without a device; records every region"""
 
     def __init__(self, log_path, device, shared, fail):
         self.log_path, self.device, self.shared, self.fail = log_path, device, shared, fail
@@ -41,7 +41,7 @@ class _StubChain:
                 out.append(draft[201:] if a > 0 else draft)
                 roff.append(roff[-1] + len(out[-1]))
                 fh.write("%s %d %d %d %d\n" % (batch.contigs[g], a, b, self.device, int(self.shared)))
-        return np.asarray(roff, np.int64), b"".join(out)
+        return polish.ChainResult(np.asarray(roff, np.int64), b"".join(out))
 
     def close(self):
         pass
