@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import rnn_budget
 from oracle import rnn_oracle
 from pepper_thesis_amd import synth
 
@@ -185,6 +186,9 @@ def test_p2_ragged_batches_vs_oracle(hip_ctx, B, rows, opts):
     lr, ar = rnn_oracle.p2_forward(w, x[sel], np.float64)
     np.testing.assert_allclose(acc[sel], ar, atol=TOL_ACC, rtol=0)
     _check_labels(labels[sel], ar, lr)
+    # and no further from float64 than 8 x what plain fp32 arithmetic loses on the same chunks (tests/rnn_budget.py)
+    _, a32 = rnn_oracle.p2_forward(w, x[sel], np.float32)
+    rnn_budget.budget(acc[sel], ar, a32, rnn_budget.FACTOR, "P2 fp32 B=%d %s-row tiles acc" % (B, rows), list(sel))
     # every position is covered by one or two windows: accumulated probabilities sum to 1 or 2
     s = acc.sum(2)
     assert np.allclose(s[:, :50], 1, atol=1e-4) and np.allclose(s[:, 50:950], 2, atol=1e-4) and np.allclose(s[:, 950:], 1, atol=1e-4)
