@@ -14,6 +14,8 @@
 // rows), hence MT = 2: 64 rows per weight fetch. The projections G arrive as quads [m / 4][column][4] whose four values are
 // the accumulator registers 4q .. 4q+3 of a lane: they are loaded straight INTO the accumulators at the end of the previous
 // step, so the MFMAs simply continue from them.
+// The split-6 form (X6, the LSTM layers of large PV_DTYPE_F32 calls) takes six terms of three-piece operands: its h rows are
+// [fp32 h | split8-style groups of the pieces x1, x2], split once by the lane that produces h (see k_rec_bf16).
 #include "rnn_bf16.hpp"
 #include "mfma_tiles.hpp"
 #include "split3_host.hpp"
@@ -34,6 +36,14 @@ __device__ __forceinline__ float tanhf_(float x) {
     const float e = __expf(2.0f * x);
     return 1.0f - 2.0f * rcpf_(e + 1.0f);
 }
+// pieces x1, x2 of split3_bf16's rule for ONE value. The residuals are taken of the rounded fp32 value: without the pragma
+// hipcc fuses `h - x0` with the product that made h (v_fma_f32 og, tanh c, -x0) and the pieces are those of another number
+__device__ __forceinline__ void split3_rest(float h, __bf16& x1, __bf16& x2) {
+#pragma clang fp contract(off)
+    const float r1 = h - (float)(__bf16)h;
+    x1 = (__bf16)r1;
+    x2 = (__bf16)(r1 - (float)x1);
+}
 __device__ __forceinline__ unsigned split8_off(unsigned k) { return (k >> 3) * 32u + (k & 7u) * 2u; }
 
 template <int NG, bool ENC, int MT = 1, bool X6 = false> struct RecCfg {
@@ -50,10 +60,14 @@ template <int NG, bool ENC, int MT = 1, bool X6 = false> struct RecCfg {
     static constexpr int NSLOT = (XRES ? 0 : KS_X * NG) + KS_H * NG;   // (gate, k-step) slots of the weight stream per step
     // ring depth (NSLOT % D == 0): 8 register sets where they fit; 4 for the 64-row LSTM forms (128 accumulator + 32 state
     // registers of 256) and the GRU encoder (its x-part fragments stay resident)
-    // (8 sets in the 64-row decoder: 14 spills, no faster). Split-6 form: 4 sets of three pieces (8 spill in the 32-row encoder)
+    // (8 sets in the 64-row decoder: 14 spills, no faster). Split-6 form: 4 sets of three pieces (8 sets in the decoder, 238
+    // registers, and 6 in the encoder, 223, are spill-free and no faster: 1.54 / 1.60 ms against 1.55 / 1.60 at 8192 windows)
     static constexpr int D = ((NG == 3 && ENC) || (NG == 4 && MT == 2) || X6) ? 4 : 8;
     static constexpr int NA = NG + ((NG == 3 && ENC) ? 1 : 0);  // accumulators per M-tile (GRU keeps the n gate's x-part apart)
-    static constexpr int HS = HID * 4 + 16;                     // LDS row stride of the split8 h tile: (HS / 4) % 64 == 4
+    // LDS row stride of the h tile, (HS / 4) % 64 == 4 (16 rows of a ds_read_b128 lane group on 16 x 4 distinct banks).
+    // split8: 4 bytes per unit. Split-6 form: 8 bytes per unit, [HID fp32 values | per 8 units: 8 bf16 x1, 8 bf16 x2]
+    static constexpr int HS = HID * (X6 ? 8 : 4) + 16;
+    static constexpr int H12 = X6 ? HID * 4 : 0;                // split-6 form: where a row's x1 | x2 groups start
     static constexpr int XS = XK * 2 + 16;                      // LDS row stride of the bf16 x tile
     static_assert(NSLOT % D == 0, "ring depth must divide the stream length");
 };
@@ -83,9 +97,11 @@ struct RecArgs {
 // At = this lane's A-fragment address of M-tile 0, k-step 0; XP: x-part (plain bf16 rows, exact operand, two terms).
 // hook(i) runs behind the MFMAs of slot i (vector / LDS / store instructions of the caller that have nothing to do with the
 // product issue there while the matrix pipe works).
-// X6 (split-6 chain of PV_DTYPE_F32): slots of three 1 KB pieces (x0 | x1 | x2); the h-part's A rows are fp32 (8 values = 32
-// bytes per lane and k-step, split into three pieces in registers) and take six terms, the exact x-part three.
-template <int NG, int MT, int NA, int D, int NTOT, int I0, int NKS, bool XP, bool X6 = false, typename Hook>
+// X6 (split-6 chain of PV_DTYPE_F32): slots of three 1 KB pieces (x0 | x1 | x2); the h-part's A rows carry 8 fp32 values (32
+// bytes per lane and k-step) and, H12 bytes further, their pieces x1 | x2 (16 bytes each) as the lane that produced them left
+// them: x0 is one conversion of the fp32 values, nothing else of the split is left in the loop. The h-part takes six terms,
+// the exact x-part three.
+template <int NG, int MT, int NA, int D, int NTOT, int I0, int NKS, bool XP, bool X6 = false, int H12 = 0, typename Hook>
 __device__ __forceinline__ void ring_bf16(f32x16 (&acc)[MT][NA], const unsigned char* __restrict__ At, int m_stride,
                                           __amdgpu_buffer_rsrc_t wr, f32x4 (&bq)[D][X6 ? 3 : 2], unsigned lane16, Hook&& hook) {
     constexpr int KSB = XP ? 32 : 64;   // bytes of one k-step inside an A row
@@ -103,8 +119,12 @@ __device__ __forceinline__ void ring_bf16(f32x16 (&acc)[MT][NA], const unsigned 
 #pragma unroll
             for (int m = 0; m < MT; m++) {
                 if constexpr (X6 && !XP) {
-                    split3_bf16(*reinterpret_cast<const f32x4*>(At + m * m_stride + ks * KSB),
-                                *reinterpret_cast<const f32x4*>(At + m * m_stride + ks * KSB + 16), ap[0][m], ap[1][m], ap[2][m]);
+                    const f32x4 lo = *reinterpret_cast<const f32x4*>(At + m * m_stride + ks * KSB);
+                    const f32x4 hi = *reinterpret_cast<const f32x4*>(At + m * m_stride + ks * KSB + 16);
+                    ap[1][m] = *reinterpret_cast<const bf16x8*>(At + m * m_stride + ks * KSB + H12);
+                    ap[2][m] = *reinterpret_cast<const bf16x8*>(At + m * m_stride + ks * KSB + H12 + 16);
+#pragma unroll
+                    for (int j = 0; j < 8; j++) ap[0][m][j] = (__bf16)(j < 4 ? lo[j] : hi[j - 4]);
                 } else {
                     ap[0][m] = *reinterpret_cast<const bf16x8*>(At + m * m_stride + ks * KSB);
                     if (!XP) ap[1][m] = *reinterpret_cast<const bf16x8*>(At + m * m_stride + ks * KSB + 16);
@@ -137,7 +157,8 @@ __device__ __forceinline__ void ring_bf16(f32x16 (&acc)[MT][NA], const unsigned 
 }
 
 #ifndef PV_REC_ABL
-#define PV_REC_ABL 0   // diagnostic ablations (timing only, results wrong): 1 = no global output stores, 2 = no LDS h writes
+#define PV_REC_ABL 0   // diagnostic ablations (timing only, results wrong): 1 = no global output stores, 2 = no LDS h writes,
+                       // 3 = LSTM cell update without its transcendentals (h = sum of the four gate sums, c untouched)
 #endif
 #ifdef PV_REC_STAMPS
 // diagnostic build: cycle sums of the phases of a step (workgroup 0, every wave adds), read by pv_debug_rec_stamps
@@ -147,9 +168,12 @@ __device__ unsigned long long g_rec_stamps[8];
 #define RSTAMP(i)
 #endif
 
-// X6: the LSTM of the split-6 chain (PV_DTYPE_F32): h_{t-1} lives in LDS as fp32 rows (the same 4 bytes per unit and the same
-// fragment addresses as split8: an fp32 8-group is 32 bytes too), the weight slots carry three pieces, the h-part takes six
-// terms and the byte x-part three (ring_bf16); the layer's outputs (the tile copies below) leave as fp32 rows.
+// X6: the LSTM of the split-6 chain (PV_DTYPE_F32): a row of the h tile in LDS is the HID fp32 values (the same fragment
+// addresses as split8: an fp32 8-group is 32 bytes too) followed by their pieces x1 | x2 in split8's group layout, written
+// by the cell update of the lane that owns the element (split3_rest), so that the eight waves no longer split the whole tile
+// at every k-step. The weight slots carry three pieces, the h-part takes six terms and the byte x-part three (ring_bf16); the
+// layer's outputs (the tile copies below) are the fp32 part of the rows. (Rows of three bf16 pieces alone would be smaller,
+// but x0 + x1 + x2 does not give back an h below 2^-110: its last bits lie under the smallest bf16 subnormal, 2^-133.)
 template <int NG, bool ENC, int MT, bool X6 = false>
 __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) {
     static_assert(!X6 || NG == 4, "split-6 form: LSTM only");
@@ -212,6 +236,7 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
 #pragma unroll
         for (int e = 0; e < 16; e++) st[m][e] = 0.0f;
     const unsigned hl = (unsigned)(4 * rg * HS) + (X6 ? (unsigned)unit * 4u : split8_off((unsigned)unit));   // lane part of an h element's LDS offset
+    const unsigned hl12 = (unsigned)(4 * rg * HS + C::H12) + split8_off((unsigned)unit);   // ... and of its pieces x1 (+ 16: x2)
     __syncthreads();
     if (NG == 3 && a.h0) {
 #pragma unroll
@@ -460,7 +485,7 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
                     }
             }
         } else {
-            ring_bf16<NG, MT, NA, D, NSLOT, NXS, C::KS_H, false, X6>(acc, a_h + cur * ROWS * HS, 32 * HS, wr, bq, lane16, copy_hook);
+            ring_bf16<NG, MT, NA, D, NSLOT, NXS, C::KS_H, false, X6, C::H12>(acc, a_h + cur * ROWS * HS, 32 * HS, wr, bq, lane16, copy_hook);
         }
         if (dense && s > 0) dense_out(t_prev, tile_prev);   // (the previous step's h tile: this step's A operand)
         if (NW == 8) { if (wv < 4) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1); }
@@ -473,13 +498,19 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
             for (int e = 0; e < 16; e++) {
                 float h;
                 if constexpr (NG == 4) {   // PyTorch LSTM gate order i, f, g, o
+#if PV_REC_ABL == 3
+                    h = ((acc[m][0][e] + acc[m][1][e]) + acc[m][2][e]) + acc[m][3][e];   // (every gate's product stays live)
+#else
                     const float ig = sigmoidf_(acc[m][0][e]);
                     const float fg = sigmoidf_(acc[m][1][e]);
                     const float gg = tanhf_(acc[m][2][e]);
                     const float og = sigmoidf_(acc[m][3][e]);
-                    const float c = fg * st[m][e] + ig * gg;
+                    // (split-6 form: the contraction hipcc picks for the other forms, spelt out, so that it cannot depend on the
+                    // code around it: the outputs of this chain are held bit for bit)
+                    const float c = X6 ? __builtin_fmaf(fg, st[m][e], ig * gg) : fg * st[m][e] + ig * gg;
                     st[m][e] = c;
                     h = og * tanhf_(c);
+#endif
                 } else {                   // PyTorch GRU: n = tanh(W_in x + b_in + r * (W_hn h + b_hn)), h' = (1 - z) n + z h
                     const float r = sigmoidf_(acc[m][0][e]);
                     const float z = sigmoidf_(acc[m][1][e]);
@@ -492,6 +523,12 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
 #if PV_REC_ABL != 2
                 if constexpr (X6) {
                     *reinterpret_cast<float*>(hn + row * HS + hl) = h;
+                    {
+                        __bf16 p1, p2;
+                        split3_rest(h, p1, p2);
+                        *reinterpret_cast<__bf16*>(hn + row * HS + hl12) = p1;
+                        *reinterpret_cast<__bf16*>(hn + row * HS + hl12 + 16) = p2;
+                    }
                 } else {
                     const __bf16 hi = (__bf16)h;
                     const __bf16 lo = (__bf16)(h - (float)hi);
@@ -821,8 +858,8 @@ __global__ __launch_bounds__(256, 1) void k_gru16_bf16(RecArgs a) {
     }
 }
 
-template <int NG, bool ENC, int MT> constexpr size_t lds_rec() {
-    typedef RecCfg<NG, ENC> C;
+template <int NG, bool ENC, int MT, bool X6 = false> constexpr size_t lds_rec() {
+    typedef RecCfg<NG, ENC, MT, X6> C;
     return (size_t)2 * 32 * MT * C::HS + (ENC ? (size_t)2 * 32 * MT * C::XS : 0);
 }
 
@@ -1088,7 +1125,7 @@ int pv_rec_bf16_prepare() {
     PV_REC_ATTR(3, true, 1); PV_REC_ATTR(3, true, 2); PV_REC_ATTR(3, false, 1); PV_REC_ATTR(3, false, 2);
 #undef PV_REC_ATTR
 #define PV_REC_ATTR6(ENC, MT) \
-    PV_HIP(hipFuncSetAttribute((const void*)k_rec_bf16<4, ENC, MT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rec<4, ENC, MT>()))
+    PV_HIP(hipFuncSetAttribute((const void*)k_rec_bf16<4, ENC, MT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rec<4, ENC, MT, true>()))
     PV_REC_ATTR6(true, 1); PV_REC_ATTR6(false, 1);
 #undef PV_REC_ATTR6
     return PV_OK;
@@ -1119,7 +1156,7 @@ int pv_rec_bf16_async(pv_ctx* ctx, const pv_rec_desc& d, hipStream_t st) {
     const unsigned grid = (unsigned)(((a.n_tiles + 3) / 4) * 8);
     pv_prof_scope ps(ctx, d.prof_name, st);
 #define PV_REC_GO(NG, ENC, MT) k_rec_bf16<NG, ENC, MT><<<grid, RecCfg<NG, ENC>::NTHR, lds_rec<NG, ENC, MT>(), st>>>(a)
-#define PV_REC_GO6(ENC, MT) k_rec_bf16<4, ENC, MT, true><<<grid, RecCfg<4, ENC>::NTHR, lds_rec<4, ENC, MT>(), st>>>(a)
+#define PV_REC_GO6(ENC, MT) k_rec_bf16<4, ENC, MT, true><<<grid, RecCfg<4, ENC>::NTHR, lds_rec<4, ENC, MT, true>(), st>>>(a)
     if (d.x6) {   // (32-row tiles only: the 64-row form spills 14 / 42 registers with three weight pieces)
         if (d.enc) PV_REC_GO6(true, 1);
         else PV_REC_GO6(false, 1);
