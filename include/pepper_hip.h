@@ -217,7 +217,17 @@ typedef struct pv_polish_out {
     int64_t* region_row_off;/* optional [n_regions+1] first flat row of every region */
     int64_t n_chunks;       /* out: chunks produced (or needed on PV_ERR_CAPACITY) */
     int64_t n_rows;         /* out: flat rows produced (or needed) */
+    uint16_t* depth;        /* optional [chunk_capacity][seq_length] read depth of every row (below); NULL: nothing is written
+                             * and nothing else changes. The last member, so the offsets above are those of earlier builds */
 } pv_polish_out;
+/* depth: for a base row (index 0) at position p, the sum of the column's ten counts before normalisation: the reads that hold
+ * a base or a deleted column (D / N / P) at p, exactly as the builder counts them for the ten planes (so reads of mapping
+ * quality 0, which the images leave out, are left out here too). It is not the normaliser `coverage` above, which carries
+ * the reference's quirk of crediting a whole deletion to its first column. An insert row takes the depth of its anchor
+ * position, a padding row 0. Values are clamped to 65535 (unreachable: a region holds at most 32767 reads). images,
+ * position, index, region, chunk_id and the counters are byte for byte those of a call with depth == NULL. The plane is
+ * gathered with the chunk rows, so it needs the chunk arrays; the flat arrays have no depth of their own. The library reads
+ * the member in every call that takes the struct: zero the struct before filling it, as for every struct of this header. */
 
 /* HOST buffers in and out. */
 int pv_polish_summarize_regions(pv_ctx* ctx, const pv_batch_in* in, int seq_length, int seq_overlap, pv_polish_out* out);
@@ -324,6 +334,39 @@ int pv_polish_edits(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, 
                     const uint8_t* row_qual, const int64_t* region_start, const int64_t* ref_off, const uint8_t* ref,
                     int32_t n_regions, int seq_length, int seq_overlap, int64_t* region_edit_off, pv_polish_edit* edits,
                     int64_t edit_capacity, int64_t* counts);
+
+/* The polisher's minimum depth: where too few reads stand behind a row, its label is rewritten to spell the draft, before
+ * the stitch, so that pv_polish_stitch[_qual] and pv_polish_edits on the rewritten labels keep the draft there (FASTA, FASTQ
+ * and edit records stay consistent, and those kernels are untouched). The reference has no counterpart.
+ * chunks: position, index, region, chunk_id and depth of n_chunks chunks (pv_polish_summarize_regions[_dev] with the depth
+ * plane); labels, row_qual (or NULL), region_start, ref_off, ref: as for pv_polish_edits_dev. For row j of chunk k, g = region[k]:
+ *   position < 0 (padding) or depth[k][j] >= min_depth: label and quality are copied unchanged - a label above 4 too, which
+ *               the stitch still reports as today;
+ *   otherwise the row is MASKED:
+ *     index == 0: d = ref[ref_off[g] + position - region_start[g]], u = d with ASCII a..z upper-cased;
+ *                 u in "ACGT": the label becomes 1 + its place in "ACGT" and the quality 0;
+ *                 any other u (N, IUPAC): no label spells it, so label and quality are copied and the row counts as UNMASKABLE;
+ *     index  > 0: the label becomes 0 (no inserted base) and the quality 0.
+ * Every row is treated, owned or not: two chunks that share a (position, index) hold the same depth and the same draft byte,
+ * so they receive the same label, and neither the stitch's string-order winner nor the ownership rule of the edits is
+ * affected. labels_out == labels and row_qual_out == row_qual (in place) are allowed; row_qual and row_qual_out are given or
+ * NULL together. min_depth == 0 is the identity.
+ * d_counts = {masked rows (label rewritten), status, first bad chunk (-1 if none), unmaskable rows}. Status PV_ERR_INVALID:
+ * the chunk layout is broken (as for the stitch), or a masked index-0 row's position lies outside [region_start[g],
+ * region_start[g] + ref_off[g+1] - ref_off[g]) - checked before the draft byte is read, which is therefore never read out
+ * of bounds; such a row is copied. chunks->depth == NULL, ref == NULL with n_chunks > 0 and min_depth outside 0..65535 are
+ * refused with PV_ERR_INVALID by the call itself, before anything is launched. Device-resident and asynchronous on `stream`;
+ * one workgroup per chunk and a one-block finish, no global atomics, no host synchronisation; capturable. */
+int pv_polish_mask_low_depth_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                                 const uint8_t* row_qual, const int64_t* region_start, const int64_t* ref_off, const uint8_t* ref,
+                                 int32_t n_regions, int seq_length, int min_depth, uint8_t* labels_out, uint8_t* row_qual_out,
+                                 int64_t* d_counts, void* stream);
+/* HOST buffers in and out; counts[4] as d_counts above; returns the status (on PV_ERR_INVALID from the device, labels_out and
+ * row_qual_out are left as they were). */
+int pv_polish_mask_low_depth(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                             const uint8_t* row_qual, const int64_t* region_start, const int64_t* ref_off, const uint8_t* ref,
+                             int32_t n_regions, int seq_length, int min_depth, uint8_t* labels_out, uint8_t* row_qual_out,
+                             int64_t* counts);
 
 /* The polisher's read realignment (AlignmentSummarizer.reads_to_reference_realignment, pepper/modules/python/
  * AlignmentSummarizer.py:159-177 -> ReadAligner::align_reads_to_reference, simple_aligner.cpp:66-107): every read of a region

@@ -156,6 +156,7 @@ class pv_polish_out(C.Structure):
         ("region_row_off", C.c_void_p),
         ("n_chunks", C.c_int64),
         ("n_rows", C.c_int64),
+        ("depth", C.c_void_p),
     ]
 
 
@@ -249,6 +250,12 @@ SYMBOLS = [
     ("pv_polish_edits", C.c_int,
      [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int,
       C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("pv_polish_mask_low_depth_dev", C.c_int,
+     [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int,
+      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pv_polish_mask_low_depth", C.c_int,
+     [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int,
+      C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     ("pv_polish_realign", C.c_int, [C.c_void_p, C.POINTER(pv_batch_in), C.c_void_p, C.c_void_p, C.POINTER(pv_realign_out)]),
     ("pv_polish_realign_dev", C.c_int,
      [C.c_void_p, C.POINTER(pv_batch_in), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(pv_realign_out),

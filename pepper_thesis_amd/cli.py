@@ -171,6 +171,10 @@ def polish_parser(ap=None):
                     help="also write <output_file>/_pepper_polished.edits.vcf.gz (+ .tbi): every substitution, insertion and "
                          "deletion the polisher made in the draft, with --qualities each with its quality (opt-in; one device; "
                          "the FASTA is unchanged)")
+    ap.add_argument("--min_depth", type=int, default=0,
+                    help="keep the draft wherever fewer than this many reads cover a column (0..65535; 0, the default, is off): "
+                         "the network's label there is replaced by the draft base before the stitch, and regions without "
+                         "reads are filled from the draft, so FASTA, FASTQ and edits agree (opt-in; one device)")
     return ap
 
 

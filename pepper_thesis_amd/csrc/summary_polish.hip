@@ -263,11 +263,20 @@ __global__ __launch_bounds__(256) void k_polish_image(SumArgs a) {
     const int32_t cov = a.pcnt[(int64_t)PC_COV * NC + col];
     const int32_t nl = a.pcnt[(int64_t)PC_LONG * NC + col];
     const int64_t pos = a.in.ref_start[g] + i;
+    // the depth plane (pv_polish_out.depth): the column's ten counts, summed; its insert rows take the same value
+    uint16_t depth = 0;
+    if (a.flat_depth) {
+        int32_t d = 0;
+#pragma unroll
+        for (int f = 0; f < 10; f++) d += a.pcnt[(int64_t)f * NC + col];
+        depth = (uint16_t)(d > 65535 ? 65535 : d);
+    }
     if (row < a.flat_cap) {
 #pragma unroll
         for (int f = 0; f < 10; f++) a.flat_img[row * 10 + f] = polish_pixel(a.pcnt[(int64_t)f * NC + col], cov);
         a.flat_pos[row] = pos;
         a.flat_idx[row] = 0;
+        if (a.flat_depth) a.flat_depth[row] = depth;
     }
     for (int32_t ii = 0; ii < nl; ii++) {
         row++;
@@ -276,6 +285,7 @@ __global__ __launch_bounds__(256) void k_polish_image(SumArgs a) {
         for (int f = 0; f < 10; f++) a.flat_img[row * 10 + f] = polish_pixel(a.ins_cnt[(ins0 + ii) * 10 + f], cov);
         a.flat_pos[row] = pos;
         a.flat_idx[row] = ii + 1;
+        if (a.flat_depth) a.flat_depth[row] = depth;
     }
 }
 
@@ -300,11 +310,13 @@ __global__ __launch_bounds__(256) void k_polish_chunks(SumArgs a) {
         for (int f = 0; f < 10; f++) dst[f] = a.flat_img[src * 10 + f];
         a.pout.position[t] = a.flat_pos[src];
         a.pout.index[t] = a.flat_idx[src];
+        if (a.pout.depth) a.pout.depth[t] = a.flat_depth[src];
     } else {
 #pragma unroll
         for (int f = 0; f < 10; f++) dst[f] = 0;
         a.pout.position[t] = -1;
         a.pout.index[t] = -1;
+        if (a.pout.depth) a.pout.depth[t] = 0;
     }
 }
 
@@ -348,6 +360,8 @@ int polish_launch(pv_ctx* ctx, const pv_batch_in* in, int64_t n_reads, int64_t n
         if ((rc = pv_get(ctx, "pol.flat_pos", (size_t)a.flat_cap, &a.flat_pos))) return rc;
         if ((rc = pv_get(ctx, "pol.flat_idx", (size_t)a.flat_cap, &a.flat_idx))) return rc;
     }
+    if (out->depth)   // the flat depth is workspace either way: pv_polish_out has no flat form of it
+        if ((rc = pv_get(ctx, "pol.flat_depth", (size_t)(a.flat_cap > 0 ? a.flat_cap : 1), &a.flat_depth))) return rc;
 
     pv_prof_scope ps_all(ctx, "polish_pipeline", st);
     front_init(a, st);

@@ -139,6 +139,7 @@ struct SumArgs {
     uint8_t* flat_img;    // [flat_cap][10]
     int64_t* flat_pos;
     int32_t* flat_idx;
+    uint16_t* flat_depth; // [flat_cap] or null: wanted only with pout.depth
     int64_t flat_cap;
     pv_polish_out pout;
 };

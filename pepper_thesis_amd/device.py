@@ -92,7 +92,9 @@ class DeviceOut:
 class DevicePolishOut:
     """Caller-owned chunk arrays of pv_polish_out in HBM (the polisher's image batches, input of forward_p2_dev)."""
 
-    def __init__(self, chunk_capacity: int, seq_length: int = 1000, seq_overlap: int = 50, device="cuda:0"):
+    def __init__(self, chunk_capacity: int, seq_length: int = 1000, seq_overlap: int = 50, device="cuda:0", depth: bool = False):
+        """depth: also carry the read-depth plane uint16 [chunk_capacity, seq_length] (pv_polish_out.depth), which the
+        builder fills and pv_polish_mask_low_depth_dev reads; without it the struct's pointer is null and nothing changes"""
         self.capacity, self.seq_length, self.seq_overlap = int(chunk_capacity), int(seq_length), int(seq_overlap)
         self.images = torch.zeros((chunk_capacity, seq_length, 10), dtype=torch.uint8, device=device)
         self.position = torch.zeros((chunk_capacity, seq_length), dtype=torch.int64, device=device)
@@ -105,6 +107,9 @@ class DevicePolishOut:
         c.images, c.position, c.index = self.images.data_ptr(), self.position.data_ptr(), self.index.data_ptr()
         c.region, c.chunk_id = self.region.data_ptr(), self.chunk_id.data_ptr()
         c.flat_images = c.flat_position = c.flat_index = c.region_row_off = None
+        # (an int16 tensor that holds the plane's uint16 bits: torch's unsigned 16-bit type has creation and copies only)
+        self.depth = torch.zeros((chunk_capacity, seq_length), dtype=torch.int16, device=device) if depth else None
+        c.depth = self.depth.data_ptr() if depth else None
         self.c = c
 
     def n_chunks(self) -> int:
@@ -112,3 +117,11 @@ class DevicePolishOut:
 
     def status(self) -> int:
         return int(self.counts[2].item())
+
+    def depth_numpy(self, n: int) -> np.ndarray:
+        """the depth plane of the first n chunks on the host, uint16 [n, seq_length]"""
+        return self.depth[:n].cpu().numpy().view(np.uint16)
+
+    def set_depth(self, depth: np.ndarray):
+        """a host depth plane uint16 [n, seq_length] into the first n chunks"""
+        self.depth[:len(depth)].copy_(torch.from_numpy(np.ascontiguousarray(depth, np.uint16).view(np.int16)))

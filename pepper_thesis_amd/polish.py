@@ -9,7 +9,7 @@ prediction HDF5 files. Here each batch of regions goes through
 without leaving HBM; only the region offsets and the polished bases (one byte per base) come back to the host.
 
   python -m pepper_thesis_amd polish -b reads.bam -f draft.fa -m model.pkl -o out/polished [-t 5] [-r ctg:start-end] [--bf16]
-      [--realign] [--gpu_decode] [--qualities] [--edits]
+      [--realign] [--gpu_decode] [--qualities] [--edits] [--min_depth N]
 
 --gpu_decode (opt-in) replaces the first stage: reader threads only plan blocks and fetch draft bytes, and the BAM is inflated,
 decoded and clipped on the device (gpu_decode.py; _decoded_pieces below). Same FASTA.
@@ -25,6 +25,15 @@ in the draft. Behind the stitch, on the same stream, pv_polish_edits_dev compare
 consults with the draft bytes of the batch and leaves one 16-byte record per substitution, deletion or inserted base (with
 --qualities: with the column's row quality); the region offsets and the records come back, and polish_edits.py joins them
 into VCF records per contig. The FASTA (and FASTQ) are byte for byte those of a run without the flag.
+
+--min_depth N (opt-in, one device; 0 = off) keeps the draft wherever fewer than N reads stand behind a column. The builder
+also hands out the read depth of every chunk row (pv_polish_out.depth), and between the network (and the row qualities) and
+the stitch pv_polish_mask_low_depth_dev rewrites, in place, the labels of the rows below N to the ones that spell the draft
+(insert rows: no base) and their qualities to 0; a draft byte other than ACGT cannot be spelled and keeps the network's
+label. Stitch, qualities and edits then agree without knowing of it. A region without reads gives no chunks, so with N >= 1
+it gets a piece of its own: the upper-cased draft of its kept range, quality 0, no edits; the FASTA then keeps the draft's
+coordinates wherever nothing was polished, and the edits VCF carries one ##pepper_min_depth=N line in place of the
+##pepper_no_reads lines. Without the flag no output changes by a byte. The reference has no counterpart.
 
 Semantics kept from the reference:
   * regions: ImageGenerationUI.py:257-273 - for pos in range(start, end, 1000): [max(start, pos-100), min(end, pos+1100)],
@@ -175,12 +184,26 @@ class ChainResult(NamedTuple):
     qual: Optional[bytes] = None           # --qualities: one raw Phred byte per base
     edit_off: Optional[np.ndarray] = None  # --edits: int64 [n_regions+1] into edits
     edits: Optional[np.ndarray] = None     # --edits: polish_edits.EDIT_DTYPE records
+    # --min_depth: (chunk rows that kept the draft, rows that could not: draft byte not ACGT). Not a tuple field, so the
+    # record keeps its five planes for everything that unpacks it; with_masked() gives a result that carries the counts
+    masked = None
 
     def region(self, g: int) -> tuple:
         """region g's share: (bases, qual or None, edits or None)"""
         a, b = self.region_off[g], self.region_off[g + 1]
         return (self.bases[a:b], None if self.qual is None else self.qual[a:b],
                 None if self.edits is None else self.edits[self.edit_off[g]:self.edit_off[g + 1]])
+
+
+class _MaskedChainResult(ChainResult):
+    """a ChainResult with an instance attribute `masked`"""
+
+
+def with_masked(res: ChainResult, masked: Tuple[int, int]) -> ChainResult:
+    """res, carrying the counts of a minimum-depth chain in its attribute `masked`"""
+    out = _MaskedChainResult(*res)
+    out.masked = (int(masked[0]), int(masked[1]))
+    return out
 
 
 class Piece(NamedTuple):
@@ -230,12 +253,15 @@ class _DeviceChain:
     """device buffers of the builder -> GRU -> stitch chain, grown on demand; run / run_decoded return a ChainResult.
     qualities: P2's accumulated softmax is kept, turned into row qualities and stitched beside the bases (the result's
     qual). edits: the edit pass runs behind the stitch, with the row qualities when there are any (the result's edit_off
-    and edits)."""
+    and edits). min_depth >= 1: the builder also fills the depth plane and, before the stitch, the labels (and row
+    qualities) of the rows below min_depth are rewritten in place to spell the draft (the result's masked)."""
 
-    def __init__(self, ctx, own_ctx: bool = False, qualities: bool = False, edits: bool = False):
+    def __init__(self, ctx, own_ctx: bool = False, qualities: bool = False, edits: bool = False, min_depth: int = 0):
         import torch
         self.ctx, self.dev, self.own_ctx, self.qualities = ctx, "cuda:%d" % ctx.device_id, own_ctx, bool(qualities)
         self.edits = bool(edits)
+        self.min_depth = int(min_depth)
+        self.mask_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.edit_buf = None
         self.edit_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.dout = self.labels = self.seq = None
@@ -251,7 +277,7 @@ class _DeviceChain:
         import torch
         from .device import DevicePolishOut
         if self.dout is None or self.dout.capacity < chunks:
-            self.dout = DevicePolishOut(chunks, device=self.dev)
+            self.dout = DevicePolishOut(chunks, device=self.dev, depth=self.min_depth > 0)
             self.labels = torch.zeros((chunks, 1000), dtype=torch.uint8, device=self.dev)
             self.seq = torch.zeros(chunks * 1000, dtype=torch.uint8, device=self.dev)
             if self.qualities:
@@ -282,11 +308,13 @@ class _DeviceChain:
                 return n
             want = n
         import torch
-        out = polish_summarize(self.ctx, host_batch())
+        out = polish_summarize(self.ctx, host_batch(), want_depth=self.min_depth > 0)
         n = len(out.chunk_id)
         self._ensure(n)
         for name in ("images", "position", "index", "region", "chunk_id"):
             getattr(self.dout, name)[:n].copy_(torch.from_numpy(getattr(out, name)))
+        if self.min_depth > 0:
+            self.dout.set_depth(out.depth)
         return n
 
     def _realign(self, db, host_batch, qmax: int, windows):
@@ -370,14 +398,15 @@ class _DeviceChain:
         return self._labels_and_stitch(db, n, dec.n_regions)
 
     def _labels_and_stitch(self, db, n: int, n_regions: int) -> ChainResult:
-        """P2 [-> row qualities] -> stitch [-> edits] over the first n chunks of self.dout on the context's stream, one
-        synchronize, then the read-back"""
+        """P2 [-> row qualities] [-> minimum-depth mask] -> stitch [-> edits] over the first n chunks of self.dout on the
+        context's stream, one synchronize, then the read-back"""
         import torch
         from .polish_edits import EDIT_DTYPE
         if n == 0:   # nothing to launch: every plane this chain was made for, empty
             zero = np.zeros(n_regions + 1, np.int64)
             res = ChainResult(zero, b"", b"" if self.qualities else None)
-            return res._replace(edit_off=zero.copy(), edits=np.zeros(0, EDIT_DTYPE)) if self.edits else res
+            res = res._replace(edit_off=zero.copy(), edits=np.zeros(0, EDIT_DTYPE)) if self.edits else res
+            return with_masked(res, (0, 0)) if self.min_depth > 0 else res
         d_acc, d_row_qual, d_qual = (t.data_ptr() for t in (self.acc, self.row_qual, self.qual)) if self.qualities else (0, 0, 0)
         d_labels, d_ref_start = self.labels.data_ptr(), db.t["ref_start"].data_ptr()
         roff = torch.empty(n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
@@ -387,6 +416,10 @@ class _DeviceChain:
             # the row kernel are overwritten)
             self.ctx.polish_row_qual_dev(d_labels, d_acc, n, d_row_qual, self.counts.data_ptr(), self.dout.seq_length,
                                          self.dout.seq_overlap)
+        if self.min_depth > 0:   # in place: what follows sees the draft's labels wherever the depth is below the minimum
+            self.ctx.polish_mask_low_depth_dev(self.dout, n, d_labels, d_row_qual, d_ref_start, db.t["ref_off"].data_ptr(),
+                                               db.t["ref"].data_ptr(), n_regions, self.min_depth, d_labels, d_row_qual,
+                                               self.mask_counts.data_ptr())
         self.ctx.polish_stitch_dev(self.dout, n, d_labels, d_ref_start, n_regions, roff.data_ptr(), self.seq.data_ptr(),
                                    self.seq.numel(), self.counts.data_ptr(), d_row_qual=d_row_qual, d_qual=d_qual)
         if self.edits:
@@ -395,34 +428,41 @@ class _DeviceChain:
                                       db.t["ref"].data_ptr(), n_regions, eoff.data_ptr(), self.edit_buf.data_ptr(),
                                       self.edit_buf.shape[0], self.edit_counts.data_ptr())
         self.ctx.synchronize()   # raises if a split GRU form timed out (its labels are then poisoned)
+        masked = None
+        if self.min_depth > 0:
+            n_masked, status, bad, n_unmaskable = (int(v) for v in self.mask_counts.tolist())
+            if status != _ffi.PV_OK:
+                raise _ffi.PepperHipError(status, "polisher minimum depth: device status %d (chunk %d)" % (status, bad))
+            masked = (n_masked, n_unmaskable)
         total, status, bad = (int(v) for v in self.counts[:3].tolist())
         if status != _ffi.PV_OK:   # capacity cannot run short: seq holds a byte for every column
             raise _ffi.PepperHipError(status, "polisher stitch: device status %d (chunk %d)" % (status, bad))
         res = ChainResult(roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes(),
                           self.qual[:total].cpu().numpy().tobytes() if self.qualities else None)
         if not self.edits:
-            return res
+            return res if masked is None else with_masked(res, masked)
         total, status, bad = (int(v) for v in self.edit_counts[:3].tolist())
         if status != _ffi.PV_OK:   # capacity cannot run short: a record for every chunk row
             raise _ffi.PepperHipError(status, "polisher edits: device status %d (chunk %d)" % (status, bad))
-        return res._replace(edit_off=eoff.cpu().numpy(), edits=self.edit_buf[:total].cpu().numpy().view(EDIT_DTYPE).reshape(-1))
+        res = res._replace(edit_off=eoff.cpu().numpy(), edits=self.edit_buf[:total].cpu().numpy().view(EDIT_DTYPE).reshape(-1))
+        return res if masked is None else with_masked(res, masked)
 
 
 def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int, qualities: bool = False,
-                      edits: bool = False) -> _DeviceChain:
+                      edits: bool = False, min_depth: int = 0) -> _DeviceChain:
     """a context on `device` with the polisher weights loaded, and the chain on it (closing the chain closes the context).
     shared_device: other ranks use this GPU too, so the option is set before the first device call (the split GRU forms need
     co-resident workgroups and would time out, poisoning the labels). False leaves the create-time default (PV_SHARED_DEVICE).
     This is the default `open_chain` of run and polish_rank.run; CPU tests pass a stub with the same signature, whose result
-    has run(batch, windows) -> ChainResult and close(). qualities, edits (each passed only when set): the chain of
-    --qualities / --edits, whose results carry those planes."""
+    has run(batch, windows) -> ChainResult and close(). qualities, edits, min_depth (each passed only when set): the chain
+    of --qualities / --edits / --min_depth, whose results carry those planes."""
     from .runtime import Context
     ctx = Context(device)
     try:
         if shared_device:
             ctx.set_option("shared_device", 1)
         ctx.load_p2(state_dict, dtype)
-        return _DeviceChain(ctx, own_ctx=True, qualities=qualities, edits=edits)
+        return _DeviceChain(ctx, own_ctx=True, qualities=qualities, edits=edits, min_depth=min_depth)
     except BaseException:
         ctx.close()
         raise
@@ -452,7 +492,7 @@ def _read_ahead(ex, fn, items, depth):
 def _timers(timers: Optional[dict], more=()) -> dict:
     """the caller's timer dict (or a fresh one) with the keys of polish_pieces, and `more`, present"""
     T = timers if timers is not None else {}
-    for k in ("read_s", "device_s", "regions", "batches") + tuple(more):
+    for k in ("read_s", "device_s", "regions", "batches", "masked_rows", "unmaskable_rows") + tuple(more):
         T.setdefault(k, 0)
     return T
 
@@ -470,13 +510,43 @@ def _thread_handles(bam: str, fasta: str):
     return handles
 
 
+def _count_masked(T: dict, res) -> None:
+    """a minimum-depth chain's row counts of one launch into the timers"""
+    if getattr(res, "masked", None) is not None:
+        T["masked_rows"] += res.masked[0]
+        T["unmaskable_rows"] += res.masked[1]
+
+
+def kept_range(w: Work) -> Tuple[int, int]:
+    """the positions of a region the stitch keeps, inclusive: (start + 200, end], or [start, end] for start 0"""
+    return (w.start + 2 * MIN_IMAGE_OVERLAP + 1 if w.start > 0 else w.start), w.end
+
+
+def draft_pieces(fa, work: List[Work], pieces, qualities: bool, edits: bool) -> List[Piece]:
+    """`--min_depth N` with N >= 1: a region of the run that gave no piece has no reads, so all of it is below N and it keeps
+    the draft: a piece of the upper-cased draft bytes of its kept range (N and IUPAC bytes as they are), quality 0 for each
+    base when the run carries qualities, no edits"""
+    from .polish_edits import EDIT_DTYPE
+    done = {p.index for p in pieces}
+    out = []
+    for w in work:
+        first, last = kept_range(w)
+        if w.index in done or last < first:
+            continue
+        bases = fa.get_reference_sequence(w.contig, first, last + 1).upper().encode()
+        out.append(Piece(w.contig, w.start, w.index, bases, bytes(len(bases)) if qualities else None,
+                         np.zeros(0, EDIT_DTYPE) if edits else None))
+    return out
+
+
 def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int = 2048, threads: int = 5, realign: bool = False,
                   timers: Optional[dict] = None, gpu_decode: bool = False, open_decoder=None):
     """the regions of `work` through the chain -> a Piece for every region with reads, in `work` order. This is the whole
     device part of a run: the single-rank run passes every region, a rank of a multi-device run its share.
     chain.run(batch, windows) -> ChainResult (_DeviceChain or a CPU test's stub); a piece carries the planes that result
     carried (qual with a chain made for --qualities, edits with one made for --edits, else None).
-    timers (optional) accumulates read_s, device_s, regions, batches.
+    timers (optional) accumulates read_s, device_s, regions, batches, and masked_rows / unmaskable_rows of the results that
+    carry the counts of a minimum-depth chain.
     gpu_decode: the device read path (_decoded_pieces): the reader threads only plan, the BAM is inflated, decoded and clipped
     on chain.ctx's device, and the chain takes the batches where they are (chain.run_decoded). open_decoder(T): the decoder,
     by default a gpu_decode.GpuDecoder with the polisher's settings (CPU tests pass a stub with its scan_groups, realize,
@@ -498,6 +568,7 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
         t0 = time.perf_counter()
         regs = [r for _, r in items]
         res = chain.run(pack_regions(regs), [r.window for r in regs] if realign else None)
+        _count_masked(T, res)
         out = [Piece(w.contig, w.start, w.index, *res.region(g)) for g, (w, _) in enumerate(items)]
         T["device_s"] += time.perf_counter() - t0
         T["batches"] += 1
@@ -557,6 +628,7 @@ def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timer
                 t0 = time.perf_counter()
                 for kind, b, windows, ws in parts:
                     res = chain.run_decoded(b, windows) if kind == "dev" else chain.run(b, windows)
+                    _count_masked(T, res)
                     T["chain_runs"] += 1
                     T["regions"] += len(ws)
                     for g, w in enumerate(ws):
@@ -581,7 +653,8 @@ def decode_report(T: dict) -> str:
 
 def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region: Optional[str] = None, batch_size: int = 2048,
                  threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None,
-                 realign: bool = False, chain=None, gpu_decode: bool = False, qualities: bool = False, edits: bool = False) -> str:
+                 realign: bool = False, chain=None, gpu_decode: bool = False, qualities: bool = False, edits: bool = False,
+                 min_depth: int = 0) -> str:
     """-> path of the polished FASTA. batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
     realign: realign every read to the draft on the device before the builder, as the reference always does.
     chain: a chain with the weights already loaded (open_device_chain; the caller closes it), else one is made on `ctx`
@@ -590,28 +663,37 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
     edits: also write the edits VCF and its index beside the FASTA (polish_edits.output_vcf_path). The VCF is composed
     before any file is written, so a run it refuses (overlapping -r ranges of one contig) leaves nothing.
     The two flags make this function's own chain and pick the files; a chain passed in whose results lack a plane they
-    need is refused (ValueError) before any file is written."""
+    need is refused (ValueError) before any file is written.
+    min_depth >= 1: this function's own chain masks the rows below it (a chain passed in must have been made for it), the
+    regions without reads are filled from the draft (draft_pieces), and the VCF names the threshold."""
     from .bamio import BamHandler, FastaHandler
     from .runtime import Context
     t_start = time.perf_counter()
-    T = dict(read_s=0.0, device_s=0.0, regions=0, batches=0, bases_in=0, bases_out=0)
+    T = dict(read_s=0.0, device_s=0.0, regions=0, batches=0, bases_in=0, bases_out=0, masked_rows=0, unmaskable_rows=0, draft_regions=0)
     own = None
     if chain is None:
         state_dict = load_polish_model(model_path)
         if ctx is None:
             ctx = own = Context(0)
         ctx.load_p2(state_dict, dtype)
-        chain = _DeviceChain(ctx, qualities=qualities, edits=edits)
+        chain = _DeviceChain(ctx, qualities=qualities, edits=edits, min_depth=min_depth)
     try:
         fa, bm = FastaHandler(fasta), BamHandler(bam)
         work, T["bases_in"] = polish_work(fa, bm, region)
         out_path = output_fasta_path(out_prefix)
         log("POLISHING %d REGIONS, OUTPUT: %s" % (len(work), out_path))
+        if min_depth >= 1 and getattr(chain, "min_depth", None) != min_depth:
+            raise ValueError("polish_fused: the chain masks below depth %r, not %d: it was not made for this run"
+                             % (getattr(chain, "min_depth", None), min_depth))
         pieces = list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode))
         for want, plane in ((qualities, "qual"), (edits, "edits")):
             if want and pieces and getattr(pieces[0], plane) is None:
                 raise ValueError("polish_fused: the chain's results have no %s plane: it was not made for this run" % plane)
-        vcf = _edits_vcf(fa, fasta, work, pieces, qualities) if edits else None
+        if min_depth >= 1:
+            filled = draft_pieces(fa, work, pieces, qualities, edits)
+            T["draft_regions"] = len(filled)
+            pieces += filled
+        vcf = _edits_vcf(fa, fasta, work, pieces, qualities, min_depth) if edits else None
     finally:
         if own is not None:
             own.close()
@@ -621,7 +703,7 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
     if edits:
         from . import polish_edits
         polish_edits.write_edits_vcf(polish_edits.output_vcf_path(out_path), *vcf)
-        T["edit_records"], T["vcf_records"] = sum(len(p.edits) for p in pieces), sum(len(r) for r in vcf[-1].values())
+        T["edit_records"], T["vcf_records"] = sum(len(p.edits) for p in pieces), sum(len(r) for r in vcf[4].values())
     T["bases_out"] = sum(len(s) for s in seqs.values())
     T["wall_s"] = time.perf_counter() - t_start
     if timers is not None:
@@ -629,18 +711,17 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
     return out_path
 
 
-def _edits_vcf(fa, fasta_path: str, work: List[Work], pieces, qualities: bool) -> tuple:
+def _edits_vcf(fa, fasta_path: str, work: List[Work], pieces, qualities: bool, min_depth: int = 0) -> tuple:
     """the pieces' edit records -> write_edits_vcf's arguments behind the path: (source, reference, contigs of the run with
-    their lengths, read-free runs, VCF records per contig). Pieces of a contig are joined in region-start order, as
-    merge_pieces joins the bases. A region without a piece gave no chunks: the FASTA omits its kept range
-    ((start + 200, end], or [start, end] for start 0) and a pepper_no_reads header line names it."""
+    their lengths, read-free runs, VCF records per contig, min_depth). Pieces of a contig are joined in region-start order,
+    as merge_pieces joins the bases. A region without a piece gave no chunks: the FASTA omits its kept range
+    (kept_range) and a pepper_no_reads header line names it. With min_depth >= 1 every region has a piece (draft_pieces)."""
     from . import polish_edits
     names = list(dict.fromkeys(w.contig for w in work))
     contigs = [(c, fa.get_chromosome_sequence_length(c)) for c in names]
     done = {p.index for p in pieces}
     no_reads = polish_edits.no_read_runs(
-        (w.contig, w.start + 2 * MIN_IMAGE_OVERLAP + 1 if w.start > 0 else w.start, w.end)
-        for w in work if w.index not in done)
+        (w.contig,) + kept_range(w) for w in work if w.index not in done)
     by: Dict[str, list] = {}
     for p in pieces:
         by.setdefault(p.contig, []).append((p.start, p.index, p.edits))
@@ -650,7 +731,7 @@ def _edits_vcf(fa, fasta_path: str, work: List[Work], pieces, qualities: bool) -
             recs = np.concatenate([e for _, _, e in sorted(by[c], key=lambda t: (t[0], t[1]))])
             draft = fa.get_reference_sequence(c, 0, length).encode() if len(recs) else b""
             records[c] = polish_edits.compose_records(c, recs, draft, qualities, warn=log)
-    return "pepper_thesis_amd polish", os.path.abspath(fasta_path), contigs, no_reads, records
+    return "pepper_thesis_amd polish", os.path.abspath(fasta_path), contigs, no_reads, records, int(min_depth)
 
 
 def run(args, open_chain=open_device_chain) -> int:
@@ -676,6 +757,14 @@ def run(args, open_chain=open_device_chain) -> int:
         sys.stderr.write("ERROR: polish --edits runs on one device (-d_ids %s lists %d): the edit records are not carried "
                          "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
         return 2
+    min_depth = int(getattr(args, "min_depth", 0) or 0)
+    if not 0 <= min_depth <= 65535:
+        sys.stderr.write("ERROR: polish --min_depth %d: the minimum depth is a number of reads from 0 (off) to 65535.\n" % min_depth)
+        return 2
+    if min_depth and len(plan) > 1:
+        sys.stderr.write("ERROR: polish --min_depth runs on one device (-d_ids %s lists %d): the depth plane is not carried "
+                         "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
+        return 2
     for what, path in (("BAM", args.bam), ("FASTA", args.fasta), ("MODEL", args.model_path)):
         if not os.path.isfile(path):
             sys.stderr.write("ERROR: CAN NOT LOCATE %s FILE.\n" % what)
@@ -694,12 +783,15 @@ def run(args, open_chain=open_device_chain) -> int:
     kw = dict(qualities=True) if qualities else {}   # (only the keywords that are set: stub chains keep their signatures)
     if edits:
         kw["edits"] = True
+    if min_depth:
+        kw["min_depth"] = min_depth
     chain = open_chain(device, False, state_dict, dtype, **kw)
     try:
         T = {}
         path = polish_fused(args.bam, args.fasta, args.model_path, args.output_file, args.region, args.batch_size, args.threads,
                             timers=T, realign=bool(getattr(args, "realign", False)), chain=chain,
-                            gpu_decode=bool(getattr(args, "gpu_decode", False)), qualities=qualities, edits=edits)
+                            gpu_decode=bool(getattr(args, "gpu_decode", False)), qualities=qualities, edits=edits,
+                            min_depth=min_depth)
     except ValueError as e:
         if not edits:
             raise
@@ -710,6 +802,9 @@ def run(args, open_chain=open_device_chain) -> int:
     if decode_report(T):
         log(decode_report(T))
     log("POLISHED FASTA: %s (%d REGIONS, %d BASES IN %.2f SEC)" % (path, T["regions"], T["bases_out"], T["wall_s"]))
+    if min_depth:
+        log("MIN DEPTH %d: %d CHUNK ROWS KEPT THE DRAFT, %d COULD NOT (DRAFT BYTE NOT ACGT), %d REGIONS WITHOUT READS FILLED FROM THE DRAFT"
+            % (min_depth, T["masked_rows"], T["unmaskable_rows"], T["draft_regions"]))
     if qualities:
         log("POLISHED FASTQ: " + output_fastq_path(path))
     if edits:

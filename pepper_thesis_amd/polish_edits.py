@@ -118,14 +118,19 @@ def no_read_runs(ranges: Iterable[Tuple[str, int, int]]) -> List[Tuple[str, int,
 
 
 def vcf_text(source: str, reference: str, contigs: Sequence[Tuple[str, int]], no_reads: Sequence[Tuple[str, int, int]],
-             records: Dict[str, Sequence[VcfRecord]]) -> str:
+             records: Dict[str, Sequence[VcfRecord]], min_depth: int = 0) -> str:
     """header (fileformat, source, reference, one contig line per contig of the run in natural order, one pepper_no_reads line
-    per read-free run, the column line) and the records, contigs in natural order; eight columns, no samples"""
+    per read-free run, the column line) and the records, contigs in natural order; eight columns, no samples.
+    min_depth >= 1 (`polish --min_depth`): one pepper_min_depth line stands in the place of the pepper_no_reads lines; the
+    run then filled its read-free regions from the draft, so there are none to name."""
     from .polish import natural_key
     names = sorted((c for c, _ in contigs), key=natural_key)
     length = dict(contigs)
     lines = ["##fileformat=VCFv4.2", "##source=" + source, "##reference=" + reference]
     lines += ["##contig=<ID=%s,length=%d>" % (c, length[c]) for c in names]
+    if min_depth >= 1:
+        assert not no_reads, no_reads
+        lines.append("##pepper_min_depth=%d" % min_depth)
     lines += ["##pepper_no_reads=%s:%d-%d" % r for r in no_reads]
     lines.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO")
     for c in names:
@@ -135,7 +140,7 @@ def vcf_text(source: str, reference: str, contigs: Sequence[Tuple[str, int]], no
 
 
 def write_edits_vcf(path: str, source: str, reference: str, contigs: Sequence[Tuple[str, int]],
-                    no_reads: Sequence[Tuple[str, int, int]], records: Dict[str, Sequence[VcfRecord]]) -> None:
+                    no_reads: Sequence[Tuple[str, int, int]], records: Dict[str, Sequence[VcfRecord]], min_depth: int = 0) -> None:
     """vcf_text through bamio.write_vcf_gz (bgzip + tabix): `path` and `path`.tbi, both written under temporary names and
     renamed when complete"""
     from . import bamio
@@ -143,7 +148,7 @@ def write_edits_vcf(path: str, source: str, reference: str, contigs: Sequence[Tu
     assert path.endswith(ext), path
     tmp = stem + ".partial" + ext
     try:
-        bamio.write_vcf_gz(tmp, vcf_text(source, reference, contigs, no_reads, records))
+        bamio.write_vcf_gz(tmp, vcf_text(source, reference, contigs, no_reads, records, min_depth))
         os.replace(tmp + ".tbi", path + ".tbi")
         os.replace(tmp, path)
     except BaseException:

@@ -31,13 +31,15 @@ class PolishOut:
     flat_position: Optional[np.ndarray] = None
     flat_index: Optional[np.ndarray] = None
     region_row_off: Optional[np.ndarray] = None  # [n_regions + 1]
+    depth: Optional[np.ndarray] = None           # [n_chunks, seq_length] uint16 read depth of every row, 0 on padding rows
 
 
 class PolishBuffers:
     """Caller-owned host buffers of one pv_polish_out."""
 
-    def __init__(self, n_regions, chunk_capacity, row_capacity, seq_length, want_flat):
+    def __init__(self, n_regions, chunk_capacity, row_capacity, seq_length, want_flat, want_depth=False):
         self.seq_length = seq_length
+        self.depth = np.zeros((chunk_capacity, seq_length), dtype=np.uint16) if want_depth else None
         self.images = np.zeros((chunk_capacity, seq_length, IMAGE_HEIGHT), dtype=np.uint8)
         self.position = np.zeros((chunk_capacity, seq_length), dtype=np.int64)
         self.index = np.zeros((chunk_capacity, seq_length), dtype=np.int32)
@@ -53,7 +55,7 @@ class PolishBuffers:
         c.chunk_capacity = chunk_capacity
         c.row_capacity = row_capacity if want_flat else 0
         for f in ("images", "position", "index", "region", "chunk_id", "flat_images", "flat_position", "flat_index",
-                  "region_row_off"):
+                  "region_row_off", "depth"):
             setattr(c, f, _ffi.ptr(getattr(self, f)))
         self.c = c
 
@@ -66,19 +68,22 @@ class PolishBuffers:
             out.flat_position = self.flat_position[:r].copy()
             out.flat_index = self.flat_index[:r].copy()
             out.region_row_off = self.region_row_off.copy()
+        if self.depth is not None:
+            out.depth = self.depth[:n].copy()
         return out
 
 
-def run_polish_summarizer(fn, batch: RegionBatch, seq_length=SEQ_LENGTH, seq_overlap=SEQ_OVERLAP, want_flat=False, ctx=None):
+def run_polish_summarizer(fn, batch: RegionBatch, seq_length=SEQ_LENGTH, seq_overlap=SEQ_OVERLAP, want_flat=False, ctx=None,
+                          want_depth=False):
     """Call any function with pv_polish_summarize_regions' signature (minus the context when ctx is None), growing the
-    caller-owned buffers on PV_ERR_CAPACITY. Returns (rc, PolishOut or None)."""
+    caller-owned buffers on PV_ERR_CAPACITY. Returns (rc, PolishOut or None). want_depth: ask for the depth plane too."""
     cin = batch.as_c()
     cols = int((batch.ref_end - batch.ref_start + 1).sum()) if batch.n_regions else 0
     rows = cols + cols // 2 + 1024
     chunks = rows // max(1, seq_length - seq_overlap) + 2 * batch.n_regions + 2
     rc = 0
     for _ in range(3):
-        pb = PolishBuffers(batch.n_regions, chunks, rows, seq_length, want_flat)
+        pb = PolishBuffers(batch.n_regions, chunks, rows, seq_length, want_flat, want_depth)
         args = (C.byref(cin), int(seq_length), int(seq_overlap), C.byref(pb.c))
         rc = fn(ctx, *args) if ctx is not None else fn(*args)
         if rc == _ffi.PV_ERR_CAPACITY:
@@ -88,9 +93,12 @@ def run_polish_summarizer(fn, batch: RegionBatch, seq_length=SEQ_LENGTH, seq_ove
     return rc, None
 
 
-def polish_summarize(ctx, batch: RegionBatch, seq_length=SEQ_LENGTH, seq_overlap=SEQ_OVERLAP, want_flat=False) -> PolishOut:
-    """generate_summary + chunk_images for every region of the batch on ctx's GPU (host buffers in and out)."""
-    rc, out = run_polish_summarizer(ctx.lib.pv_polish_summarize_regions, batch, seq_length, seq_overlap, want_flat, ctx.handle)
+def polish_summarize(ctx, batch: RegionBatch, seq_length=SEQ_LENGTH, seq_overlap=SEQ_OVERLAP, want_flat=False,
+                     want_depth=False) -> PolishOut:
+    """generate_summary + chunk_images for every region of the batch on ctx's GPU (host buffers in and out).
+    want_depth: also the read depth of every chunk row (PolishOut.depth; pv_polish_out.depth in include/pepper_hip.h)."""
+    rc, out = run_polish_summarizer(ctx.lib.pv_polish_summarize_regions, batch, seq_length, seq_overlap, want_flat, ctx.handle,
+                                    want_depth)
     _ffi.check(rc)
     return out
 

@@ -268,10 +268,11 @@ class Context:
             dbatch.n_reads, dbatch.n_bases, dbatch.n_cigar, dbatch.n_ref_bytes, C.byref(dout.c), dout.counts.data_ptr(),
             stream or None))
 
-    def polish_summarize(self, batch: RegionBatch, seq_length: int = 1000, seq_overlap: int = 50, want_flat: bool = False):
+    def polish_summarize(self, batch: RegionBatch, seq_length: int = 1000, seq_overlap: int = 50, want_flat: bool = False,
+                         want_depth: bool = False):
         """Polisher (P2) SummaryGenerator.generate_summary + chunk_images for a batch (host buffers), see polish_summary.py."""
         from .polish_summary import polish_summarize
-        return polish_summarize(self, batch, seq_length, seq_overlap, want_flat)
+        return polish_summarize(self, batch, seq_length, seq_overlap, want_flat, want_depth)
 
     def polish_summarize_dev(self, dbatch: "DeviceBatch", dout: "DevicePolishOut", stream: int = 0):
         """asynchronous, device-resident: chunks land in dout.images ([capacity, seq_length, 10] uint8 in HBM), ready
@@ -460,6 +461,45 @@ class Context:
                                             _ffi.ptr(ref), len(rs), seq_length, seq_overlap, _ffi.ptr(region_edit_off),
                                             _ffi.ptr(edits), cap, counts))
         return region_edit_off, edits[:int(counts[0])].copy()
+
+    def polish_mask_low_depth_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_row_qual: int, d_region_start: int,
+                                  d_ref_off: int, d_ref: int, n_regions: int, min_depth: int, d_labels_out: int,
+                                  d_row_qual_out: int, d_counts: int, stream: int = 0):
+        """asynchronous, device-resident minimum-depth mask (pv_polish_mask_low_depth_dev): rows of dout's first n_chunks
+        chunks whose depth (dout.depth) is below min_depth get the label that spells the draft byte under them (insert rows:
+        0) and quality 0; {masked rows, status, first bad chunk, unmaskable rows} in d_counts. d_labels_out == d_labels and
+        d_row_qual_out == d_row_qual run in place; d_row_qual 0 (with d_row_qual_out 0): no quality plane."""
+        _ffi.check(self.lib.pv_polish_mask_low_depth_dev(
+            self.handle, C.byref(dout.c), int(n_chunks), d_labels, d_row_qual or None, d_region_start, d_ref_off, d_ref or None,
+            int(n_regions), dout.seq_length, int(min_depth), d_labels_out, d_row_qual_out or None, d_counts, stream or None))
+
+    def polish_mask_low_depth(self, out, labels: np.ndarray, batch, min_depth: int, row_qual: np.ndarray = None,
+                              seq_length: int = 1000, counts=None, in_place: bool = False):
+        """host-buffer minimum-depth mask (pv_polish_mask_low_depth) of a PolishOut with its depth plane, its labels and the
+        batch they were built from (ref_start, ref_off, ref) -> (labels, row_qual or None) after the mask. in_place: the
+        arrays given (C-contiguous uint8) are rewritten and returned; else copies are.
+        counts: optional ctypes int64[4] that receives {masked rows, status, first bad chunk, unmaskable rows}, also when the
+        call raises."""
+        n, c, keep = self._host_polish_out(out)
+        depth = None if getattr(out, "depth", None) is None else np.ascontiguousarray(out.depth, np.uint16)
+        c.depth = _ffi.ptr(depth)
+        lab = labels if in_place else np.ascontiguousarray(labels, np.uint8)
+        rq = row_qual if in_place or row_qual is None else np.ascontiguousarray(row_qual, np.uint8)
+        assert lab.dtype == np.uint8 and (rq is None or rq.dtype == np.uint8)
+        rs = np.ascontiguousarray(batch.ref_start, np.int64)
+        ro = np.ascontiguousarray(batch.ref_off, np.int64)
+        ref = None if batch.ref is None else np.ascontiguousarray(batch.ref, np.uint8)
+        assert lab.shape == (n, seq_length) and (rq is None or rq.shape == lab.shape), lab.shape
+        assert depth is None or depth.shape == lab.shape, depth.shape
+        assert len(ro) == len(rs) + 1 and (ref is None or len(ref) >= int(ro[-1])), (len(ro), len(rs))
+        lab_out = lab if in_place else np.zeros_like(lab)
+        rq_out = rq if in_place or rq is None else np.zeros_like(rq)
+        if counts is None:
+            counts = (C.c_int64 * 4)()
+        _ffi.check(self.lib.pv_polish_mask_low_depth(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rq), _ffi.ptr(rs),
+                                                     _ffi.ptr(ro), _ffi.ptr(ref), len(rs), seq_length, int(min_depth),
+                                                     _ffi.ptr(lab_out), _ffi.ptr(rq_out), counts))
+        return lab_out, rq_out
 
     def profile_begin(self, only: str = None):
         """bracket every kernel launch of this context with HIP events (only: just the kernels whose profile name starts

@@ -33,8 +33,12 @@
               device, and the VCF's size. The weights are random, so most rows are edits: the record count says nothing
               about a trained model.
 
+  --min_depth N: the same comparison for `polish --min_depth N`: wall times of both forms, twice each, then one more run each way
+              with the builder, the mask and the stitch calls bracketed by HIP events, and the rows the mask rewrote. The parent
+              commit's plain figure (profiles/polish_e2e_bench.json) is recorded beside them as the yardstick.
+
   python tools/bench_polish_e2e.py [--leg stitch|e2e|steps|all] [--mbp 2.0] [--reps 20] [--realign] [--d_ids 0,0] [--gpu_decode]
-                                   [--qualities] [--edits] [--out f]
+                                   [--qualities] [--edits] [--min_depth N] [--out f]
 For the rocprofv3 row run the stitch leg alone under `rocprofv3 --kernel-trace --stats -d <dir> -- python ... --leg stitch`.
 """
 import argparse
@@ -122,9 +126,11 @@ def stitch_leg(reps=20):
                                      "stitch_ms": round(t_host * 1e3, 1)}}
 
 
-def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False, qualities=False, edits=False):
+def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False, qualities=False, edits=False, min_depth=0):
     # warm-up on a small region (code objects, allocator), then the timed run
     kw = {"gpu_decode": True} if gpu_decode else {}
+    if min_depth:
+        kw["min_depth"] = min_depth
     if qualities:
         kw["qualities"] = True
     if edits:
@@ -139,6 +145,9 @@ def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decod
            "polished_bp": T["bases_out"], "fasta_bytes": size, "wall_s": round(wall, 3),
            "read_s": round(T["read_s"], 3), "device_s": round(T["device_s"], 3),
            "draft_mbp_per_s": round(T["bases_in"] / wall / 1e6, 4), "reader_threads": threads}
+    if min_depth:
+        res.update(min_depth=min_depth, masked_rows=T["masked_rows"], unmaskable_rows=T["unmaskable_rows"],
+                   draft_regions=T["draft_regions"])
     if qualities:
         fq = polish.output_fastq_path(path)
         res["qualities"], res["fastq_bytes"] = True, os.path.getsize(fq)
@@ -215,14 +224,61 @@ def realign_stats(ctx, bam, fa, per_launch=1024):
             "band_gcups": round(band / (band_ms * 1e-3) / 1e9, 1) if band_ms else None}
 
 
-def _quality_events(polish, ctx, bam, fa, model, out, threads, qualities, edits=False):
+def _quality_events(polish, ctx, bam, fa, model, out, threads, qualities, edits=False, min_depth=0):
     """one more run with the calls whose profile names start with polish_ bracketed by HIP events -> {name: [ms, launches]}"""
     ctx.profile_begin("polish_")
     try:
-        polish.polish_fused(bam, fa, model, out, threads=threads, ctx=ctx, qualities=qualities, edits=edits)
+        polish.polish_fused(bam, fa, model, out, threads=threads, ctx=ctx, qualities=qualities, edits=edits, min_depth=min_depth)
     finally:
         pr = ctx.profile_end()
-    return {k: [round(v[0], 4), v[1]] for k, v in sorted(pr.items()) if k in ("polish_stitch", "polish_row_qual", "polish_edits")}
+    return {k: [round(v[0], 4), v[1]] for k, v in sorted(pr.items())
+            if k in ("polish_stitch", "polish_row_qual", "polish_edits", "polish_mask", "polish_pipeline")}
+
+
+def min_depth_leg(mbp=3.0, threads=16, min_depth=3):
+    """polish without and with --min_depth on one synthetic contig, in one process on the same files"""
+    import hashlib
+    import numpy as np
+    from bench_filepath import make_files
+    from pepper_thesis_amd import polish, runtime, synth
+    d = tempfile.mkdtemp(prefix="pv_polish_min_depth_")
+    try:
+        bam, fa, info = make_files(d, int(mbp * 1_000_000))
+        model = os.path.join(d, "model.npz")
+        np.savez(model, **synth.make_weights_p2(4321, 3.0))
+        ctx = runtime.Context(0)
+        try:
+            # the two forms alternate, twice each: the first timed run of a process also grows the workspace to the launch size
+            runs = []
+            for k in range(2):
+                for m in (0, min_depth):
+                    r = _e2e_run(polish, ctx, bam, fa, model, os.path.join(d, "masked" if m else "plain"), threads, False, info,
+                                 min_depth=m)
+                    runs.append(dict(r, min_depth=m, order=len(runs)))
+            res = {"runs": runs, "without_min_depth": runs[2], "with_min_depth": runs[3]}
+            sha = [hashlib.sha256(open(os.path.join(d, n, "_pepper_polished.fa"), "rb").read()).hexdigest() for n in ("plain", "masked")]
+            res["fasta_identical"] = sha[0] == sha[1]
+            res["event_ms_launches"] = {
+                "without_min_depth": _quality_events(polish, ctx, bam, fa, model, os.path.join(d, "plain_ev"), threads, False),
+                "with_min_depth": _quality_events(polish, ctx, bam, fa, model, os.path.join(d, "masked_ev"), threads, False,
+                                                  min_depth=min_depth),
+                # the mask's worst case: a threshold no depth reaches, so every row loads its position, index and draft byte
+                "with_min_depth_65535": _quality_events(polish, ctx, bam, fa, model, os.path.join(d, "all_ev"), threads, False,
+                                                        min_depth=65535)}
+            try:
+                with open(os.path.join(ROOT, "profiles", "polish_e2e_bench.json")) as fh:
+                    res["parent_plain_wall_s"] = json.load(fh)["e2e"]["wall_s"]
+            except (OSError, KeyError, ValueError):
+                res["parent_plain_wall_s"] = None
+            res["note"] = ("polish_pipeline: the image builder call (every kernel of it; with the flag it also writes the depth plane); "
+                           "polish_mask: count + finish + write kernels of one mask call; polish_stitch: count + scan + write; HIP "
+                           "events around every call of a run, summed over the run's launches. The weights are random, so the FASTA "
+                           "of the plain run is not the draft and the two FASTA files differ wherever a row was masked")
+            return res
+        finally:
+            ctx.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
 
 
 def edits_leg(mbp=3.0, threads=16):
@@ -423,13 +479,17 @@ def main():
                     help="e2e leg without and with polish --qualities, plus HIP-event times of the stitch and row-quality calls")
     ap.add_argument("--edits", action="store_true",
                     help="e2e leg without and with polish --edits, plus HIP-event times of the stitch and the edit calls")
+    ap.add_argument("--min_depth", type=int, default=0,
+                    help="e2e leg without and with polish --min_depth N, plus HIP-event times of the builder, mask and stitch calls")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON to this file")
     a = ap.parse_args()
     out = {}
     if a.leg in ("stitch", "all"):
         out["stitch"] = stitch_leg(a.reps)
     if a.leg in ("e2e", "all"):
-        if a.edits:
+        if a.min_depth:
+            out["e2e"] = min_depth_leg(a.mbp, a.threads, a.min_depth)
+        elif a.edits:
             out["e2e"] = edits_leg(a.mbp, a.threads)
         elif a.qualities:
             out["e2e"] = qualities_leg(a.mbp, a.threads)
