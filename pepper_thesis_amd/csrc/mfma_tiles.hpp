@@ -1,4 +1,4 @@
-// mfma_tiles.hpp — device helpers shared by the recurrent kernels (rnn_kernels.hip, rnn_gru.hip), gfx950 only.
+// mfma_tiles.hpp — device helpers shared by the recurrent kernels (rnn_lstm.hip, rnn_head.hip, rnn_gemm.hip, rnn_gru.hip, rnn_rec_bf16.hip), gfx950 only.
 //
 //  * raw buffer accesses: a 128-bit resource in SGPRs + one 32-bit lane offset + a scalar offset. Unlike global_load /
 //    global_store with per-lane 64-bit addresses they need no address VGPRs at all, which is what keeps kernels that hold

@@ -91,7 +91,7 @@ struct pv_prof {
     }
 };
 
-struct pv_rnn_p1;  // rnn_kernels.hip
+struct pv_rnn_p1;  // rnn_p1.hip
 struct pv_rnn_p2;
 
 struct pv_ctx {
@@ -132,6 +132,28 @@ static inline int pv_get(pv_ctx* c, const char* name, size_t n, T** out) {
     return rc;
 }
 
+// Model weights and model state: allocate, record the allocation in `owned` (freed with the model), copy `n` elements from
+// the host. The device pointer may be of another type than the elements (fragment streams are kept as bytes).
+template <typename T, typename D>
+static inline int pv_dev_upload(const T* h, size_t n, D** d, std::vector<void*>& owned) {
+    PV_HIP(hipMalloc((void**)d, n * sizeof(T)));
+    owned.push_back(*d);
+    PV_HIP(hipMemcpy(*d, h, n * sizeof(T), hipMemcpyHostToDevice));
+    return PV_OK;
+}
+template <typename T, typename D>
+static inline int pv_dev_upload(const std::vector<T>& h, D** d, std::vector<void*>& owned) {
+    return pv_dev_upload(h.data(), h.size(), d, owned);
+}
+// ... or `bytes` of zeros
+template <typename D>
+static inline int pv_dev_zeros(size_t bytes, D** d, std::vector<void*>& owned) {
+    PV_HIP(hipMalloc((void**)d, bytes));
+    owned.push_back(*d);
+    PV_HIP(hipMemset(*d, 0, bytes));
+    return PV_OK;
+}
+
 static inline hipStream_t pv_pick_stream(pv_ctx* c, void* stream) { return stream ? (hipStream_t)stream : c->stream; }
 
 // pv_api.hip: zero `bytes` (a multiple of 4) of device memory with an ordinary KERNEL on `st`. The *_dev entry points use it
@@ -140,7 +162,7 @@ static inline hipStream_t pv_pick_stream(pv_ctx* c, void* stream) { return strea
 // kernel nodes keep their order.
 int pv_zero_async(void* p, size_t bytes, hipStream_t st);
 
-// rnn_kernels.hip
+// rnn_p1.hip
 void pv_rnn_free(pv_ctx* ctx);
 // rnn_gru.hip
 void pv_rnn_free_p2(pv_ctx* ctx);

@@ -2,7 +2,7 @@
 //
 // In this mode every matrix product runs on the bf16 MFMA (v_mfma_f32_32x32x16_bf16) with fp32 accumulation and 3-term split
 // operands (x = hi + lo, w = hi + lo: x.w ~= hi.hi + hi.lo + lo.hi; byte inputs are exact in bf16, so their products need
-// two terms): the input projections as one large GEMM per layer (k_gemm_bf16x3, rnn_kernels.hip), the recurrent products
+// two terms): the input projections as one large GEMM per layer (k_gemm_bf16x3, rnn_gemm.hip), the recurrent products
 // inside k_rec_bf16 (rnn_rec_bf16.hip), linear_1 as a split-K GEMM. Cell updates, the small linear layers and the softmax
 // stay fp32.
 #pragma once
@@ -23,10 +23,12 @@ struct pv_gemm_desc {
     const char* prof_name;
     int terms;   // 0 / 3: split8 operands, 3-term products; 6: fp32 A (split in registers) and pre-split W planes, 6-term products
 };
-int pv_gemm_bf16x3_async(pv_ctx* ctx, const pv_gemm_desc& g, hipStream_t st);                       // rnn_kernels.hip
+int pv_gemm_bf16x3_async(pv_ctx* ctx, const pv_gemm_desc& g, hipStream_t st);                       // rnn_gemm.hip
 int pv_gemm_bf16x3_prepare();                                                                       // function attributes (once per load)
 // w [N][K] fp32 row-major (host) -> split8 rows on the device; the allocation is appended to `owned`
 int pv_upload_split8(const float* w, size_t N, size_t K, unsigned char** d_split, std::vector<void*>& owned);
+// ... -> three bf16 planes [3][N][K] on the device, the W operand of k_gemm_bf16x6
+int pv_upload_split3(const float* w, size_t N, size_t K, unsigned char** d_planes, std::vector<void*>& owned);
 
 // ---- k_rec_bf16: one recurrent layer on pre-packed bf16 weight fragments (rnn_rec_bf16.hip) ----------------------------
 // A workgroup is (batch tile of 32 * MT rows, direction); wave w owns hidden units [32w, 32w + 32) of every gate.
@@ -59,6 +61,7 @@ struct pv_rec_desc {
 };
 int pv_rec_bf16_async(pv_ctx* ctx, const pv_rec_desc& d, hipStream_t st);
 int pv_rec_bf16_prepare();
+// The packers: pack on the host (rnn_pack_host.hpp, where the layouts are written down), upload, append the allocation to `owned`.
 // dirs[2] (PyTorch layout) -> device fragment stream(s). kx = real input features (enc) or 0.
 // pieces = 3 (LSTM only): slots of three bf16 pieces x0 | x1 | x2 (1 KB each, split3_bf16's rule) for the split-6 form
 int pv_pack_rec_bf16(const pv_rnn_dir* dirs, int cell, int kx, unsigned char** d_wp, unsigned char** d_wx, std::vector<void*>& owned,

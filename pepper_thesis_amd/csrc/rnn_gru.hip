@@ -20,6 +20,8 @@
 #include "pv_common.hpp"
 #include "mfma_tiles.hpp"
 #include "rnn_bf16.hpp"
+#include "rnn_math.hpp"
+#include "rnn_pack_host.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -34,13 +36,6 @@ constexpr int KPE = 32;          // encoder input (10 features) padded to four k
 constexpr int KPD = 2 * HG;      // decoder input
 constexpr int LDH = HG + 4;      // LDS row strides (floats): % 64 == 4 keeps ds_read_b128 conflict-free
 constexpr int LDXD = KPD + 4;
-
-__device__ __forceinline__ float rcpf_(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float sigmoidf_(float x) { return rcpf_(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) {
-    const float e = __expf(2.0f * x);
-    return 1.0f - 2.0f * rcpf_(e + 1.0f);
-}
 
 // ---- batch-tile geometry ---------------------------------------------------------------------------------------------
 // TR = chunks (batch rows) per workgroup. 32 rows use v_mfma_f32_32x32x2_f32, 16 rows v_mfma_f32_16x16x4_f32: the same
@@ -120,7 +115,8 @@ __device__ __forceinline__ void mma3_ring(Gate<TR>& ar, Gate<TR>& az, Gate<TR>& 
 
 struct GruArgs {
     const uint8_t* images;  // [B,1000,10]
-    const float* enc_wp;    // packed [2 dirs][4 waves][(KPE+HG)/8 kb][3 gates][64 lanes][4] in the tile form of the launch
+    const float* enc_wp;    // packed [2 dirs][4 waves][(KPE+HG)/8 kb][3 gates][64 lanes][4] in the tile form of the launch (pack_gru;
+                            // k_gru_us: pack_gru_us; rnn_pack_host.hpp)
     const float* dec_wp;    // packed [2 dirs][4 waves][(KPD+HG)/8 kb][3][64][4]
     const float* enc_bias;  // [2 dirs][4][128]: b_ir+b_hr, b_iz+b_hz, b_in, b_hn
     const float* dec_bias;
@@ -593,7 +589,7 @@ __global__ __launch_bounds__(SPLIT ? 256 : 512, SPLIT ? 1 : 2) void k_gru_p2(Gru
 
 
 // ---- unit-split form: the 128 hidden units of a (tile, direction) on TWO workgroups (small batches) ----------------------
-// Same idea as k_lstm_split (rnn_kernels.hip): the launch is a chain of 3800 dependent steps, so what counts is the MFMA time
+// Same idea as k_lstm_split (rnn_lstm.hip): the launch is a chain of 3800 dependent steps, so what counts is the MFMA time
 // of ONE workgroup per step. Workgroup = (16-row tile, direction, half of the units), 4 waves, one per SIMD; a wave owns 16
 // units x {r, z, n} (three 16x16 accumulators for the x-part, three for the h-part). Every step the two halves swap their
 // 64 new h values per row: data-tagged 8-byte pairs {h, tag} written through (sc1) into the slot (step parity) of a per-(tile,
@@ -939,68 +935,7 @@ __global__ __launch_bounds__(256, 1) void k_gru_us(GruArgs a_in) {
     }
 }
 
-// unit-split form: [dir][half][wave][pair of k-blocks][gate r,z,n][lane][4], stream order [h | x] (see k_gru_us)
-void pack_gru_us(const pv_rnn_dir* dirs, int K, int KP, std::vector<float>& wp) {
-    const int np_h = HG / 16, np = (KP + HG) / 16;
-    wp.assign((size_t)2 * 2 * 4 * np * 3 * 256, 0.0f);
-    for (int d = 0; d < 2; d++) {
-        auto wval = [&](int n, int kpos) -> float {   // kpos: position in the [h | x] stream
-            if (kpos < HG) return dirs[d].w_hh[(size_t)n * HG + kpos];
-            const int k = kpos - HG;
-            return k < K ? dirs[d].w_ih[(size_t)n * K + k] : 0.0f;
-        };
-        (void)np_h;
-        for (int hf = 0; hf < 2; hf++)
-            for (int w = 0; w < 4; w++)
-                for (int pp = 0; pp < np; pp++)
-                    for (int g = 0; g < 3; g++)
-                        for (int lane = 0; lane < 64; lane++) {
-                            float* dst = &wp[(((((size_t)(d * 2 + hf) * 4 + w) * np + pp) * 3 + g) * 64 + lane) * 4];
-                            const int n = g * HG + 64 * hf + 16 * w + (lane & 15);
-                            for (int kh = 0; kh < 2; kh++)
-                                for (int j = 0; j < 2; j++) dst[2 * kh + j] = wval(n, 16 * pp + 8 * kh + 2 * (lane >> 4) + j);
-                        }
-    }
-}
 constexpr size_t LDS_US = (size_t)(2 * 16 * LDH + 2 * 16 * LDXD) * sizeof(float);
-
-// Packed weight stream of one wave: [k-block of 8][gate r,z,n][lane][4]; K = [x (padded to KP) | h].
-//  32-row form: lane -> gate column 32w + (lane&31), the four values are k = 8kb + 4*(lane>>5) + j, j = 0..3
-//  16-row form: lane -> gate columns 32w + (lane&15) (tile 0) and 32w + 16 + (lane&15) (tile 1),
-//               the four values are {tile0 j0, tile0 j1, tile1 j0, tile1 j1} with k = 8kb + 2*(lane>>4) + j
-// hx_order: the stream starts with the h-part k-blocks ([h | x], the order of the overlapped window form) instead of [x | h]
-void pack_gru(const pv_rnn_dir* dirs, int K, int KP, int TR, std::vector<float>& wp, std::vector<float>& bias, bool hx_order = false) {
-    const int nkb = (KP + HG) / 8;
-    wp.assign((size_t)2 * 4 * nkb * 3 * 256, 0.0f);
-    bias.assign((size_t)2 * 4 * HG, 0.0f);
-    for (int d = 0; d < 2; d++) {
-        for (int u = 0; u < HG; u++) {
-            bias[(size_t)d * 4 * HG + 0 * HG + u] = dirs[d].b_ih[0 * HG + u] + dirs[d].b_hh[0 * HG + u];
-            bias[(size_t)d * 4 * HG + 1 * HG + u] = dirs[d].b_ih[1 * HG + u] + dirs[d].b_hh[1 * HG + u];
-            bias[(size_t)d * 4 * HG + 2 * HG + u] = dirs[d].b_ih[2 * HG + u];
-            bias[(size_t)d * 4 * HG + 3 * HG + u] = dirs[d].b_hh[2 * HG + u];
-        }
-        auto wval = [&](int n, int k) -> float {
-            if (hx_order) k = k < HG ? KP + k : k - HG;   // stream position -> position in [x | h]
-            if (k < KP) return k < K ? dirs[d].w_ih[(size_t)n * K + k] : 0.0f;
-            return dirs[d].w_hh[(size_t)n * HG + (k - KP)];
-        };
-        for (int w = 0; w < 4; w++)
-            for (int kb = 0; kb < nkb; kb++)
-                for (int nt = 0; nt < 3; nt++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        float* dst = &wp[((((size_t)(d * 4 + w) * nkb + kb) * 3 + nt) * 64 + lane) * 4];
-                        if (TR == 32) {
-                            const int n = nt * HG + 32 * w + (lane & 31);
-                            for (int j = 0; j < 4; j++) dst[j] = wval(n, kb * 8 + 4 * (lane >> 5) + j);
-                        } else {
-                            for (int t = 0; t < 2; t++)
-                                for (int j = 0; j < 2; j++)
-                                    dst[2 * t + j] = wval(nt * HG + 32 * w + 16 * t + (lane & 15), kb * 8 + 2 * (lane >> 4) + j);
-                        }
-                    }
-    }
-}
 
 template <int TR, bool SPLIT> constexpr size_t lds_p2() { return (size_t)(SPLIT ? 1 : 2) * (2 * TR * LDH + (TR == 16 ? 2 : 1) * TR * LDXD) * sizeof(float); }
 
@@ -1018,13 +953,6 @@ struct pv_rnn_p2 {
     pv_p2_bf16_weights bf;   // PV_DTYPE_BF16_INPUT_GEMM: fragment streams / split8 rows of the layer-wise path (rnn_rec_bf16.hip)
     std::vector<void*> owned;
 };
-
-static int up2(const float* h, size_t n, float** d, std::vector<void*>& owned) {
-    PV_HIP(hipMalloc((void**)d, n * sizeof(float)));
-    owned.push_back(*d);
-    PV_HIP(hipMemcpy(*d, h, n * sizeof(float), hipMemcpyHostToDevice));
-    return PV_OK;
-}
 
 void pv_rnn_free_p2(pv_ctx* ctx) {
     if (ctx->p2) {
@@ -1073,8 +1001,8 @@ extern "C" int pv_rnn_load_p2(pv_ctx* ctx, const pv_weights_p2* w, int dtype) {
         if ((rc = pv_pack_rec_bf16(w->decoder, 3, 0, &m->bf.dec_wp, nullptr, m->owned))) return rc;
         if ((rc = pv_pack_gru16_bf16(w->encoder, FEAT, &m->bf.enc16_wp, &m->bf.enc16_wx, m->owned))) return rc;
         if ((rc = pv_pack_gru16_bf16(w->decoder, 0, &m->bf.dec16_wp, nullptr, m->owned))) return rc;
-        if ((rc = up2(eb.data(), eb.size(), &m->bf.enc_bias, m->owned)) || (rc = up2(ehn.data(), ehn.size(), &m->bf.enc_bias_hn, m->owned)) ||
-            (rc = up2(dhn.data(), dhn.size(), &m->bf.dec_bias_hn, m->owned)) || (rc = up2(bcat.data(), bcat.size(), &m->bf.dec_bias_cat, m->owned)))
+        if ((rc = pv_dev_upload(eb, &m->bf.enc_bias, m->owned)) || (rc = pv_dev_upload(ehn, &m->bf.enc_bias_hn, m->owned)) ||
+            (rc = pv_dev_upload(dhn, &m->bf.dec_bias_hn, m->owned)) || (rc = pv_dev_upload(bcat, &m->bf.dec_bias_cat, m->owned)))
             return rc;
         if ((rc = pv_upload_split8(wcat.data(), (size_t)6 * HG, KPD, &m->bf.dec_wih_s, m->owned))) return rc;
         if ((rc = pv_pack_p2_dense(w->dense_w, &m->bf.dense_frag, m->owned))) return rc;
@@ -1083,24 +1011,19 @@ extern "C" int pv_rnn_load_p2(pv_ctx* ctx, const pv_weights_p2* w, int dtype) {
     }
     for (int f = 0; f < 3; f++) {
         pack_gru(w->encoder, FEAT, KPE, f ? 16 : 32, wp, bias, f == 2);
-        if ((rc = up2(wp.data(), wp.size(), &m->enc_wp[f], m->owned))) return rc;
-        if (!f && (rc = up2(bias.data(), bias.size(), &m->enc_bias, m->owned))) return rc;
+        if ((rc = pv_dev_upload(wp, &m->enc_wp[f], m->owned))) return rc;
+        if (!f && (rc = pv_dev_upload(bias, &m->enc_bias, m->owned))) return rc;
         pack_gru(w->decoder, KPD, KPD, f ? 16 : 32, wp, bias, f == 2);
-        if ((rc = up2(wp.data(), wp.size(), &m->dec_wp[f], m->owned))) return rc;
-        if (!f && (rc = up2(bias.data(), bias.size(), &m->dec_bias, m->owned))) return rc;
+        if ((rc = pv_dev_upload(wp, &m->dec_wp[f], m->owned))) return rc;
+        if (!f && (rc = pv_dev_upload(bias, &m->dec_bias, m->owned))) return rc;
     }
     pack_gru_us(w->encoder, FEAT, KPE, wp);
-    if ((rc = up2(wp.data(), wp.size(), &m->enc_wp[3], m->owned))) return rc;
+    if ((rc = pv_dev_upload(wp, &m->enc_wp[3], m->owned))) return rc;
     pack_gru_us(w->decoder, KPD, KPD, wp);
-    if ((rc = up2(wp.data(), wp.size(), &m->dec_wp[3], m->owned))) return rc;
+    if ((rc = pv_dev_upload(wp, &m->dec_wp[3], m->owned))) return rc;
     PV_HIP(hipFuncSetAttribute((const void*)k_gru_us, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_US));
-    PV_HIP(hipMalloc((void**)&m->us_err, 64));
-    m->owned.push_back(m->us_err);
-    PV_HIP(hipMemset(m->us_err, 0, 64));
-    PV_HIP(hipMalloc((void**)&m->us_epoch, 64));
-    m->owned.push_back(m->us_epoch);
-    PV_HIP(hipMemset(m->us_epoch, 0, 64));
-    if ((rc = up2(w->dense_w, (size_t)NCLS * KPD, &m->dense_w, m->owned)) || (rc = up2(w->dense_b, NCLS, &m->dense_b, m->owned))) return rc;
+    if ((rc = pv_dev_zeros(64, &m->us_err, m->owned)) || (rc = pv_dev_zeros(64, &m->us_epoch, m->owned))) return rc;
+    if ((rc = pv_dev_upload(w->dense_w, (size_t)NCLS * KPD, &m->dense_w, m->owned)) || (rc = pv_dev_upload(w->dense_b, NCLS, &m->dense_b, m->owned))) return rc;
     m->bf.dense_w = m->dense_w; m->bf.dense_b = m->dense_b;
     PV_HIP(hipFuncSetAttribute((const void*)k_gru_p2<32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p2<32, false>()));
     PV_HIP(hipFuncSetAttribute((const void*)k_gru_p2<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p2<16, false>()));

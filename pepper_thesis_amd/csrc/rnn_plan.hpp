@@ -1,6 +1,6 @@
 // rnn_plan.hpp — which kernel form an RNN call runs: every switch point of P1 and P2, and nothing else.
 //
-// Plain C++17 with no HIP dependency: pure functions of (dtype, batch, CU count, options). The launchers (rnn_kernels.hip,
+// Plain C++17 with no HIP dependency: pure functions of (dtype, batch, CU count, options). The launchers (rnn_p1.hip,
 // rnn_gru.hip, rnn_rec_bf16.hip) plan first and then only allocate workspace, fill arguments and launch. tests/rnn_plan_shim.cpp
 // compiles this header alone; tests/test_rnn_plan_cpu.py holds it against the Python restatement tests/rnn_forms.py.
 #pragma once

@@ -10,6 +10,7 @@
 // h lives in LDS as "split8" rows (per 8 units: 8 bf16 hi, 8 bf16 lo), double-buffered, one barrier per step; a 16-byte half
 // of a group is exactly one A fragment. W_hh (and the LSTM encoder's W_ih) are pre-split on the host into B-fragment order and
 // streamed from L2 through a ring of D register sets requested D - 1 (gate, k-step) slots ahead, wrapping into the next step.
+// (The fragment streams of every kernel here: pack_rec_bf16, pack_gru16_bf16, pack_tail_bf16, pack_p2_dense{,16}, rnn_pack_host.hpp.)
 // At 4 bytes per weight the stream is what bounds a step (1 MB per LSTM step and workgroup against 12 k MFMA cycles for 32
 // rows), hence MT = 2: 64 rows per weight fetch. The projections G arrive as quads [m / 4][column][4] whose four values are
 // the accumulator registers 4q .. 4q+3 of a lane: they are loaded straight INTO the accumulators at the end of the previous
@@ -18,7 +19,8 @@
 // [fp32 h | split8-style groups of the pieces x1, x2], split once by the lane that produces h (see k_rec_bf16).
 #include "rnn_bf16.hpp"
 #include "mfma_tiles.hpp"
-#include "split3_host.hpp"
+#include "rnn_math.hpp"
+#include "rnn_pack_host.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -30,12 +32,6 @@ using namespace pvdev;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float rcpf_(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float sigmoidf_(float x) { return rcpf_(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) {
-    const float e = __expf(2.0f * x);
-    return 1.0f - 2.0f * rcpf_(e + 1.0f);
-}
 // pieces x1, x2 of split3_bf16's rule for ONE value. The residuals are taken of the rounded fp32 value: without the pragma
 // hipcc fuses `h - x0` with the product that made h (v_fma_f32 og, tanh c, -x0) and the pieces are those of another number
 __device__ __forceinline__ void split3_rest(float h, __bf16& x1, __bf16& x2) {
@@ -880,9 +876,6 @@ struct TailBfArgs {
     float* probs; int64_t B;
     unsigned* epoch; const int* err;
 };
-__device__ __forceinline__ float seluf_(float x) {
-    return 1.0507009873554805f * (x > 0.0f ? x : 1.6732632423543772f * (__expf(x) - 1.0f));
-}
 __global__ __launch_bounds__(512, 1) void k_tail_bf16(TailBfArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     unsigned char* tile = sm;   // [TL_ROWS][TL_HS] split8 rows
@@ -994,111 +987,30 @@ constexpr size_t LDS_TAIL_BF = (size_t)TL_ROWS * TL_HS;
 
 }  // namespace
 
-// Fragment stream of one (direction, wave): slots [x-part k-steps x gates | h-part k-steps x gates]; a slot is 1 KB of hi
-// fragments followed by 1 KB of lo fragments; lane -> weight row gate * HID + 32 * wave + (lane & 31), 8 consecutive K values
-// 16 * ks + 8 * (lane >> 5) + j (the B operand of v_mfma_f32_32x32x16_bf16). GRU encoder: the x-part goes to a stream of its own.
+// The exported packers: pack on the host (rnn_pack_host.hpp: the layouts are written down there), upload.
 int pv_pack_rec_bf16(const pv_rnn_dir* dirs, int cell, int kx, unsigned char** d_wp, unsigned char** d_wx, std::vector<void*>& owned,
                      int pieces) {
-    const int NG = cell, HID = cell == 4 ? 256 : 128, NW = HID / 32, KS_H = HID / 16;
-    const int KS_X = kx ? (cell == 4 ? 2 : 1) : 0;
-    const bool xres = kx && cell == 3;
-    const int nslot = (xres ? 0 : KS_X * NG) + KS_H * NG;
     PV_CHECK(pieces == 2 || (pieces == 3 && cell == 4), PV_ERR_INVALID, "three-piece fragments exist for the LSTM only");
-    const size_t SL = (size_t)pieces * 512;   // 2-byte units of one slot: a 1 KB fragment per piece
-    std::vector<uint16_t> wp((size_t)2 * NW * nslot * SL), wx(xres ? (size_t)2 * NW * NG * 1024 : 0);
-    for (int d = 0; d < 2; d++)
-        for (int w = 0; w < NW; w++) {
-            auto fill = [&](uint16_t* dst, bool xpart, int ks, int g) {
-                for (int lane = 0; lane < 64; lane++)
-                    for (int j = 0; j < 8; j++) {
-                        const int n = g * HID + 32 * w + (lane & 31), k = 16 * ks + 8 * (lane >> 5) + j;
-                        float v;
-                        if (xpart) v = k < kx ? dirs[d].w_ih[(size_t)n * kx + k] : 0.0f;
-                        else v = dirs[d].w_hh[(size_t)n * HID + k];
-                        // pieces: v ~= hi + lo (2), or v = x0 + x1 + x2 (3): the first two or all three of split3_host.hpp's rule
-                        uint16_t p[3];
-                        split3_bits(v, p);
-                        for (int q = 0; q < pieces; q++) dst[512 * q + lane * 8 + j] = p[q];
-                    }
-            };
-            uint16_t* base = wp.data() + (size_t)(d * NW + w) * nslot * SL;
-            int slot = 0;
-            if (!xres)
-                for (int ks = 0; ks < KS_X; ks++)
-                    for (int g = 0; g < NG; g++) fill(base + (size_t)(slot++) * SL, true, ks, g);
-            for (int ks = 0; ks < KS_H; ks++)
-                for (int g = 0; g < NG; g++) fill(base + (size_t)(slot++) * SL, false, ks, g);
-            if (xres)
-                for (int g = 0; g < NG; g++) fill(wx.data() + ((size_t)(d * NW + w) * NG + g) * 1024, true, 0, g);
-        }
-    PV_HIP(hipMalloc((void**)d_wp, wp.size() * 2));
-    owned.push_back(*d_wp);
-    PV_HIP(hipMemcpy(*d_wp, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
+    std::vector<uint16_t> wp, wx;
+    pack_rec_bf16(dirs, cell, kx, pieces, wp, wx);
     if (d_wx) *d_wx = nullptr;
-    if (xres) {
-        PV_HIP(hipMalloc((void**)d_wx, wx.size() * 2));
-        owned.push_back(*d_wx);
-        PV_HIP(hipMemcpy(*d_wx, wx.data(), wx.size() * 2, hipMemcpyHostToDevice));
-    }
-    return PV_OK;
+    int rc = pv_dev_upload(wp, d_wp, owned);
+    return rc || wx.empty() ? rc : pv_dev_upload(wx, d_wx, owned);
 }
 
-// GRU weights for k_gru16_bf16: per (direction, wave) 24 slots (ks * 3 + g) * 2 + nt of W_hh and, with kx > 0, 6 slots g * 2 + nt of
-// W_ih (features beyond kx zero); lane -> unit 32 w + 16 nt + (lane & 15), values k = 32 ks + 8 (lane >> 4) + j
 int pv_pack_gru16_bf16(const pv_rnn_dir* dirs, int kx, unsigned char** d_wp, unsigned char** d_wx, std::vector<void*>& owned) {
-    const int HID = 128, NW = 4;
-    std::vector<uint16_t> wp((size_t)2 * NW * 24 * 1024), wx(kx ? (size_t)2 * NW * 6 * 1024 : 0);
-    for (int d = 0; d < 2; d++)
-        for (int w = 0; w < NW; w++)
-            for (int g = 0; g < 3; g++)
-                for (int nt = 0; nt < 2; nt++) {
-                    auto fill = [&](uint16_t* dst, bool xpart, int ks) {
-                        for (int lane = 0; lane < 64; lane++)
-                            for (int j = 0; j < 8; j++) {
-                                const int n = g * HID + 32 * w + 16 * nt + (lane & 15), k = 32 * ks + 8 * (lane >> 4) + j;
-                                const float v = xpart ? (k < kx ? dirs[d].w_ih[(size_t)n * kx + k] : 0.0f) : dirs[d].w_hh[(size_t)n * HID + k];
-                                const uint16_t hi = f2bf_bits(v);
-                                dst[lane * 8 + j] = hi;
-                                dst[512 + lane * 8 + j] = f2bf_bits(v - bf_bits2f(hi));
-                            }
-                    };
-                    for (int ks = 0; ks < 4; ks++) fill(wp.data() + ((size_t)(d * NW + w) * 24 + (ks * 3 + g) * 2 + nt) * 1024, false, ks);
-                    if (kx) fill(wx.data() + ((size_t)(d * NW + w) * 6 + g * 2 + nt) * 1024, true, 0);
-                }
-    PV_HIP(hipMalloc((void**)d_wp, wp.size() * 2));
-    owned.push_back(*d_wp);
-    PV_HIP(hipMemcpy(*d_wp, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
+    std::vector<uint16_t> wp, wx;
+    pack_gru16_bf16(dirs, kx, wp, wx);
     if (d_wx) *d_wx = nullptr;
-    if (kx) {
-        PV_HIP(hipMalloc((void**)d_wx, wx.size() * 2));
-        owned.push_back(*d_wx);
-        PV_HIP(hipMemcpy(*d_wx, wx.data(), wx.size() * 2, hipMemcpyHostToDevice));
-    }
-    return PV_OK;
+    int rc = pv_dev_upload(wp, d_wp, owned);
+    return rc || wx.empty() ? rc : pv_dev_upload(wx, d_wx, owned);
 }
 
 int pv_pack_tail_bf16(const float* const* w, unsigned char** d_wp, std::vector<void*>& owned) {
-    // per wave: [layer][k-step][column tile] slots of [hi 1 KB | lo 1 KB]; lane -> column 64 wave + 32 tile + (lane & 31),
-    // values k = 16 ks + 8 (lane >> 5) + j
-    std::vector<uint16_t> wp((size_t)8 * 4 * TL_SLOTS * 1024);
-    for (int wv = 0; wv < 8; wv++)
-        for (int l = 0; l < 4; l++)
-            for (int ks = 0; ks < TL_KS; ks++)
-                for (int g = 0; g < 2; g++) {
-                    uint16_t* dst = wp.data() + ((((size_t)wv * 4 + l) * TL_KS + ks) * 2 + g) * 1024;
-                    for (int lane = 0; lane < 64; lane++)
-                        for (int j = 0; j < 8; j++) {
-                            const int n = 64 * wv + 32 * g + (lane & 31), k = 16 * ks + 8 * (lane >> 5) + j;
-                            const float v = w[l][(size_t)n * TL_N + k];
-                            const uint16_t hi = f2bf_bits(v);
-                            dst[lane * 8 + j] = hi;
-                            dst[512 + lane * 8 + j] = f2bf_bits(v - bf_bits2f(hi));
-                        }
-                }
-    PV_HIP(hipMalloc((void**)d_wp, wp.size() * 2));
-    owned.push_back(*d_wp);
-    PV_HIP(hipMemcpy(*d_wp, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
-    return PV_OK;
+    static_assert(TL_N == PV_PACK_HEAD_N, "pack_tail_bf16 packs 512 x 512 layers");
+    std::vector<uint16_t> wp;
+    pack_tail_bf16(w, wp);
+    return pv_dev_upload(wp, d_wp, owned);
 }
 
 int pv_tail_bf16_prepare() {
@@ -1290,48 +1202,15 @@ __global__ __launch_bounds__(256) void k_p2_combine(const float* __restrict__ pa
 }  // namespace
 
 int pv_pack_p2_dense16(const float* dense_w, unsigned char** d_frag, std::vector<void*>& owned) {
-    // k_gru16_bf16: wave w of direction d takes k-step w (32 units); lane -> class lane & 15 (zero beyond the five), values
-    // k = 32 w + 8 (lane >> 4) + j
-    std::vector<uint16_t> f((size_t)2 * 4 * 1024, 0);
-    for (int d = 0; d < 2; d++)
-        for (int w = 0; w < 4; w++) {
-            uint16_t* dst = f.data() + ((size_t)d * 4 + w) * 1024;
-            for (int lane = 0; lane < 64; lane++)
-                for (int j = 0; j < 8; j++) {
-                    const int n = lane & 15, k = 32 * w + 8 * (lane >> 4) + j;
-                    const float v = n < P2_NC ? dense_w[(size_t)n * 2 * P2_H + d * P2_H + k] : 0.0f;
-                    const uint16_t hi = f2bf_bits(v);
-                    dst[lane * 8 + j] = hi;
-                    dst[512 + lane * 8 + j] = f2bf_bits(v - bf_bits2f(hi));
-                }
-        }
-    PV_HIP(hipMalloc((void**)d_frag, f.size() * 2));
-    owned.push_back(*d_frag);
-    PV_HIP(hipMemcpy(*d_frag, f.data(), f.size() * 2, hipMemcpyHostToDevice));
-    return PV_OK;
+    std::vector<uint16_t> f;
+    pack_p2_dense16(dense_w, f);
+    return pv_dev_upload(f, d_frag, owned);
 }
 
 int pv_pack_p2_dense(const float* dense_w, unsigned char** d_frag, std::vector<void*>& owned) {
-    // wave w of direction d takes k-steps 2w, 2w + 1 of that direction's 128 units; lane -> class lane & 31 (zero beyond the
-    // five), values k = 16 ks + 8 (lane >> 5) + j
-    std::vector<uint16_t> f((size_t)2 * 4 * 2 * 1024, 0);
-    for (int d = 0; d < 2; d++)
-        for (int w = 0; w < 4; w++)
-            for (int kk = 0; kk < 2; kk++) {
-                uint16_t* dst = f.data() + (((size_t)d * 4 + w) * 2 + kk) * 1024;
-                for (int lane = 0; lane < 64; lane++)
-                    for (int j = 0; j < 8; j++) {
-                        const int n = lane & 31, k = 16 * (2 * w + kk) + 8 * (lane >> 5) + j;
-                        const float v = n < P2_NC ? dense_w[(size_t)n * 2 * P2_H + d * P2_H + k] : 0.0f;
-                        const uint16_t hi = f2bf_bits(v);
-                        dst[lane * 8 + j] = hi;
-                        dst[512 + lane * 8 + j] = f2bf_bits(v - bf_bits2f(hi));
-                    }
-            }
-    PV_HIP(hipMalloc((void**)d_frag, f.size() * 2));
-    owned.push_back(*d_frag);
-    PV_HIP(hipMemcpy(*d_frag, f.data(), f.size() * 2, hipMemcpyHostToDevice));
-    return PV_OK;
+    std::vector<uint16_t> f;
+    pack_p2_dense(dense_w, f);
+    return pv_dev_upload(f, d_frag, owned);
 }
 
 int pv_p2_bf16_forward(pv_ctx* ctx, const pv_p2_plan& pl, const pv_p2_bf16_weights& w, const uint8_t* d_images, int64_t B, uint8_t* d_labels,

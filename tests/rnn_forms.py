@@ -4,7 +4,7 @@ Given (model, dtype, batch size, CU count, options) the functions below say what
 rows of the recurrent kernels, the split parts, `mt`, the split-K factor of linear_1, the tail kernel, the chunks a call is
 cut into and the profile names (pv_profile_*) the launch must show. They restate, by hand and independently, the plan header the
 library's launchers consume, pepper_thesis_amd/csrc/rnn_plan.hpp: pv_p1_chunk (chunking), pv_p1_use_x6, pv_plan_p1 (P1) and
-pv_plan_p2 (P2); the profile names are those of the launchers (rnn_kernels.hip, rnn_gru.hip, rnn_rec_bf16.hip).
+pv_plan_p2 (P2); the profile names are those of the launchers (rnn_lstm.hip, rnn_head.hip, rnn_gemm.hip, rnn_gru.hip, rnn_rec_bf16.hip).
 tests/test_rnn_plan_cpu.py holds the two against each other at every batch size, without a GPU.
 `boundaries(num_cu)` walks every batch size up to the largest switch and yields the sizes on either side of each change of
 form. tests/test_rnn_forms_cpu.py pins what it yields on 256 CUs; tests/test_rnn_forms_gpu.py runs the kernels at those sizes
