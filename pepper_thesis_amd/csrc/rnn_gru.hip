@@ -21,6 +21,7 @@
 #include "mfma_tiles.hpp"
 #include "rnn_bf16.hpp"
 #include "rnn_math.hpp"
+#include "rnn_p2_head.hpp"
 #include "rnn_pack_host.hpp"
 
 #include <algorithm>
@@ -29,9 +30,8 @@
 namespace {
 
 using namespace pvdev;
+using namespace pvdev::p2;       // SEQ, WIN, JUMP, NWIN, FEAT, NCLS, HG (rnn_p2_head.hpp)
 
-constexpr int SEQ = 1000, WIN = 100, JUMP = 50, NWIN = 19, FEAT = 10, NCLS = 5;
-constexpr int HG = 128;          // GRU hidden
 constexpr int KPE = 32;          // encoder input (10 features) padded to four k-blocks of 8 (mma3_ring works in groups of 4)
 constexpr int KPD = 2 * HG;      // decoder input
 constexpr int LDH = HG + 4;      // LDS row strides (floats): % 64 == 4 keeps ds_read_b128 conflict-free
@@ -132,10 +132,10 @@ struct GruArgs {
     const float* hidden_in; // [B,2,128] or NULL (zeros)
     float* hidden_out;      // [B,2,128] or NULL
     float* logits;          // [B,100,5] raw dense1 output of the LAST window, or NULL
-    int* pair_flags;        // split form only: [n_tiles][2] hand-off counters of the two direction workgroups of a tile (zeroed per launch)
+    int* pair_flags;        // split form only: [n_tiles][2] tile_handoff counters of the two direction workgroups of a tile (zeroed per launch)
     // unit-split form only (k_gru_us):
     u32x4* hx;              // [n_tiles][2 dirs][US_HX_QUADS] data-tagged h pairs
-    int* quad_flags;        // [n_tiles][4][US_FLAG_STRIDE] layer-boundary counters of the four workgroups of a tile (zeroed per launch)
+    int* quad_flags;        // [n_tiles][4][US_FLAG_STRIDE] tile_handoff counters of the four workgroups of a tile (zeroed per launch)
     unsigned tag_base;      // tags of this launch run from tag_base + 1 (set by the kernel from *epoch)
     unsigned* epoch;        // device word: launches of the unit-split form so far (bumped by k_gru_bump behind every launch, so a
                             // replayed hipGraph advances the tags like eager launches do)
@@ -155,23 +155,88 @@ struct GruArgs {
 // workgroup's barrier, one lane publishes (release fence, drained, then the relaxed counter store) and polls the partner's
 // counter with relaxed loads, one acquire fence, barrier. Used only while both workgroups of every tile are resident at
 // once (grid <= CUs, one workgroup per CU), so a poll can never wait for a workgroup that has not been dispatched.
-__device__ __forceinline__ void pair_handoff(int* mine, const int* theirs, int value, int tid, int* err, int limit) {
+// The same hand-off joins the four workgroups of a tile in the unit-split form (k_gru_us). N workgroups, the counter of
+// workgroup `me` at flags[me * STRIDE]; `value` counts the hand-offs of the launch.
+template <int N, int STRIDE>
+__device__ __forceinline__ void tile_handoff(int* flags, int me, int value, int tid, int* err, int limit) {
+    static_assert((N & (N - 1)) == 0, "partners are counted modulo N");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's stores have left
     __syncthreads();
     if (tid == 0) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // ROCm 7.2 can drop the fence's own wait: keep this one, before the flag
-        __hip_atomic_store(mine, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int spins = 0;
-        while (__hip_atomic_load(theirs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < value) {
-            __builtin_amdgcn_s_sleep(2);
-            if (++spins > limit) { atomicAdd(err, 1); break; }   // bounded: a lost partner ends in POISONED results (k_gru_finish), never in a hung device
+        __hip_atomic_store(flags + me * STRIDE, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int k = 1; k < N; k++) {
+            const int* f = flags + ((me + k) & (N - 1)) * STRIDE;
+            int spins = 0;
+            while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < value) {
+                __builtin_amdgcn_s_sleep(2);
+                if (++spins > limit) { atomicAdd(err, 1); break; }   // bounded: a lost partner ends in POISONED results (k_gru_finish), never in a hung device
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the invalidate has completed before the barrier lets the other waves read
     }
     __syncthreads();
 }
+
+// Register staging of x_t for one direction of a tile, by the 256 threads that work on it: load(t) fetches time index t of
+// the window into registers behind a step's MFMAs, store(xb) writes them to the LDS tile xb ([TR][KP + 4]) once the step
+// that reads that tile is over. Which t, and which tile, is the window function's business.
+//   encoder: a byte per thread and 8 rows, rows tid/32 + 8u, feature tid & 31 (KPE = 32 padded features) of the uint8 image
+//   decoder: a float4 per thread and 4 rows, rows tid/64 + 4u, of the encoder output x_src [WIN][TR][KPD]
+template <int TR, int KP, bool ENC>
+struct XStage {
+    static constexpr int LDX = KP + 4;
+    static constexpr int XR = ENC ? 1 : TR / 4;
+    static constexpr int XE = TR / 8;
+    f32x4 xr[XR];
+    unsigned xe[ENC ? XE : 1];             // raw bytes: converted when they are written to LDS, so the load is not waited for
+                                           // at the top of the step (a conversion right behind the load makes hipcc drain the
+                                           // whole vmcnt queue there, weight-fragment ring included)
+    unsigned xoff[ENC ? XE : 1];           // encoder: byte offset of (row's chunk, feature k) from the tile's first chunk
+    unsigned xd_g, xd_l, xe_l;             // decoder: float offset in x_src[t] and in the tile; encoder: float offset in the tile
+    bool xe_valid;
+    const uint8_t* img0;                   // uniform: (first chunk of the tile, first column of the window)
+    __amdgpu_buffer_rsrc_t xsr;
+
+    __device__ __forceinline__ XStage(const GruArgs& a, int win_start, int tid, int64_t b0, const float* x_src, const float* wp) {
+        xd_g = (unsigned)((tid >> 6) * KPD + (tid & 63) * 4);
+        xd_l = (unsigned)((tid >> 6) * LDX + (tid & 63) * 4);
+        xe_l = (unsigned)((tid >> 5) * LDX + (tid & 31));
+        xe_valid = (tid & 31) < FEAT;
+        if constexpr (ENC) {
+#pragma unroll
+            for (int u = 0; u < XE; u++) {
+                int64_t r = (tid >> 5) + 8 * u;
+                if (b0 + r >= a.B) r = a.B - 1 - b0;   // rows past the batch re-read its last chunk: nothing of theirs leaves the tile's scratch
+                xoff[u] = (unsigned)(r * a.seq * FEAT) + (unsigned)((tid & 31) < FEAT ? (tid & 31) : FEAT - 1);   // padding lanes re-read feature 9
+            }
+        }
+        img0 = a.images + ((size_t)b0 * a.seq + win_start) * FEAT;
+        xsr = make_rsrc(ENC ? (const void*)wp : (const void*)x_src);   // (encoder: unused, any valid resource)
+    }
+    __device__ __forceinline__ void load(int t) {
+        if constexpr (ENC) {
+            const uint8_t* src = img0 + t * FEAT;
+#pragma unroll
+            for (int u = 0; u < XE; u++) xe[u] = src[xoff[u]];
+        } else {
+#pragma unroll
+            for (int u = 0; u < XR; u++) xr[u] = buf_load4(xsr, xd_g * 4u, (unsigned)((t * TR + u * 4) * KPD * 4));
+        }
+    }
+    __device__ __forceinline__ void store(float* xb) const {
+        if constexpr (ENC) {
+#pragma unroll
+            for (int u = 0; u < XE; u++) (xb + u * 8 * LDX)[xe_l] = xe_valid ? (float)xe[u] : 0.0f;
+        } else {
+#pragma unroll
+            for (int u = 0; u < XR; u++) *reinterpret_cast<f32x4*>(xb + u * 4 * LDX + xd_l) = xr[u];
+        }
+    }
+};
 
 // one GRU layer over one 100-column window for this wave's direction.
 // Addressing: every global access is a raw buffer access (wave-uniform resource + 32-bit lane offset computed once +
@@ -191,52 +256,13 @@ __device__ __forceinline__ void gru_window(const GruArgs& a, int win_start, int 
         b_r[t] = bias[0 * HG + unit + 16 * t]; b_z[t] = bias[1 * HG + unit + 16 * t];
         b_in[t] = bias[2 * HG + unit + 16 * t]; b_hn[t] = bias[3 * HG + unit + 16 * t];
     }
-    // register staging of x_t for this direction (256 threads per direction)
-    constexpr int XR = ENC ? 1 : TR / 4;   // decoder: float4 per thread, rows tid_dir/64 + 4u
-    constexpr int XE = TR / 8;             // encoder: floats per thread, rows tid_dir/32 + 8u (KPE = 32 padded features)
-    f32x4 xr[XR];
-    unsigned xe[ENC ? XE : 1];             // raw bytes: converted when they are written to LDS, so the load is not waited for
-                                           // at the top of the step (a conversion right behind the load makes hipcc drain the
-                                           // whole vmcnt queue there, weight-fragment ring included)
-    unsigned xoff[ENC ? XE : 1];           // encoder: byte offset of (row's chunk, feature k) from the tile's first chunk
-    const unsigned xd_g = (unsigned)((tid_dir >> 6) * KPD + (tid_dir & 63) * 4);   // decoder: float offset in x_src[t]
-    const unsigned xd_l = (unsigned)((tid_dir >> 6) * LDX + (tid_dir & 63) * 4);   // ... and in xbuf
-    const unsigned xe_l = (unsigned)((tid_dir >> 5) * LDX + (tid_dir & 31));
-    const bool xe_valid = (tid_dir & 31) < FEAT;
-    if constexpr (ENC) {
-#pragma unroll
-        for (int u = 0; u < XE; u++) {
-            int64_t r = (tid_dir >> 5) + 8 * u;
-            if (b0 + r >= a.B) r = a.B - 1 - b0;
-            xoff[u] = (unsigned)(r * a.seq * FEAT) + (unsigned)((tid_dir & 31) < FEAT ? (tid_dir & 31) : FEAT - 1);   // padding lanes re-read feature 9
-        }
-    }
-    const uint8_t* img0 = a.images + ((size_t)b0 * a.seq + win_start) * FEAT;  // uniform
-    const __amdgpu_buffer_rsrc_t wr = make_rsrc(wp), xsr = make_rsrc(ENC ? (const void*)wp : (const void*)x_src), osr = make_rsrc(out_dst);
-    auto x_load = [&](int t) {
-        if constexpr (ENC) {
-            const uint8_t* src = img0 + t * FEAT;
-#pragma unroll
-            for (int u = 0; u < XE; u++) xe[u] = src[xoff[u]];
-        } else {
-#pragma unroll
-            for (int u = 0; u < XR; u++) xr[u] = buf_load4(xsr, xd_g * 4u, (unsigned)((t * TR + u * 4) * KPD * 4));
-        }
-    };
+    XStage<TR, KP, ENC> xs(a, win_start, tid_dir, b0, x_src, wp);
+    const __amdgpu_buffer_rsrc_t wr = make_rsrc(wp), osr = make_rsrc(out_dst);
     // 16-row form: x_t tiles alternate between two LDS buffers (slot s & 1 holds step s): x_{s+1} is written right behind
     // step s's MFMAs, so ONE barrier per step publishes both the new h and the next x. (Two 32-row x buffers of both
     // directions do not fit the 160 KB: that form keeps one buffer and a second barrier.)
     constexpr bool XDB = TR == 16;
-    auto x_store = [&](int slot) {
-        float* xb = xbuf + (XDB ? slot : 0) * TR * LDXD;
-        if constexpr (ENC) {
-#pragma unroll
-            for (int u = 0; u < XE; u++) (xb + u * 8 * LDX)[xe_l] = xe_valid ? (float)xe[u] : 0.0f;
-        } else {
-#pragma unroll
-            for (int u = 0; u < XR; u++) *reinterpret_cast<f32x4*>(xb + u * 4 * LDX + xd_l) = xr[u];
-        }
-    };
+    auto x_store = [&](int slot) { xs.store(xbuf + (XDB ? slot : 0) * TR * LDXD); };
     f32x4 bq[4][3];  // weight-fragment ring of mma3_ring; slots 0..2 start with k-blocks 0..2
 #pragma unroll
     for (int q = 0; q < 3; q++)
@@ -244,13 +270,13 @@ __device__ __forceinline__ void gru_window(const GruArgs& a, int win_start, int 
         for (int nt = 0; nt < 3; nt++) bq[q][nt] = buf_load4(wr, (unsigned)lane * 16u, (unsigned)((q * 3 + nt) * 1024));
     const unsigned h_l = (unsigned)(lane_row<TR>(lane) * LDH + unit);   // lane part of the h tile offset
     const unsigned o_l = (unsigned)(lane_row<TR>(lane) * KPD + unit);   // lane part of the output offset
-    x_load(dir ? WIN - 1 : 0);
+    xs.load(dir ? WIN - 1 : 0);
     x_store(0);
     __syncthreads();
     for (int s = 0; s < WIN; s++) {
         const int t = dir ? (WIN - 1 - s) : s;
         const int nxt = cur ^ 1;
-        if (s + 1 < WIN) x_load(dir ? (WIN - 2 - s) : (s + 1));
+        if (s + 1 < WIN) xs.load(dir ? (WIN - 2 - s) : (s + 1));
         Gate<TR> ar, az, anx, anh;  // r and z accumulate both products; n keeps its x and h parts apart
 #pragma unroll
         for (int e = 0; e < NE; e++) {
@@ -345,48 +371,10 @@ __device__ __forceinline__ void gru_window_ovl(const GruArgs& a, int win_start, 
         b_r[t] = bias[0 * HG + unit + 16 * t]; b_z[t] = bias[1 * HG + unit + 16 * t];
         b_in[t] = bias[2 * HG + unit + 16 * t]; b_hn[t] = bias[3 * HG + unit + 16 * t];
     }
-    constexpr int XR = ENC ? 1 : TR / 4;   // decoder: float4 per thread, rows tid_dir/64 + 4u
-    constexpr int XE = TR / 8;             // encoder: floats per thread, rows tid_dir/32 + 8u
-    f32x4 xr[XR];
-    unsigned xe[ENC ? XE : 1];             // raw bytes: converted when they are written to LDS, so the load is not waited for
-                                           // at the top of the step (a conversion right behind the load makes hipcc drain the
-                                           // whole vmcnt queue there, weight-fragment ring included)
-    unsigned xoff[ENC ? XE : 1];
-    const unsigned xd_g = (unsigned)((tid_dir >> 6) * KPD + (tid_dir & 63) * 4);
-    const unsigned xd_l = (unsigned)((tid_dir >> 6) * LDX + (tid_dir & 63) * 4);
-    const unsigned xe_l = (unsigned)((tid_dir >> 5) * LDX + (tid_dir & 31));
-    const bool xe_valid = (tid_dir & 31) < FEAT;
-    if constexpr (ENC) {
-#pragma unroll
-        for (int u = 0; u < XE; u++) {
-            int64_t r = (tid_dir >> 5) + 8 * u;
-            if (b0 + r >= a.B) r = a.B - 1 - b0;
-            xoff[u] = (unsigned)(r * a.seq * FEAT) + (unsigned)((tid_dir & 31) < FEAT ? (tid_dir & 31) : FEAT - 1);   // padding lanes re-read feature 9
-        }
-    }
-    const uint8_t* img0 = a.images + ((size_t)b0 * a.seq + win_start) * FEAT;  // uniform
-    const __amdgpu_buffer_rsrc_t wr = make_rsrc(wp), xsr = make_rsrc(ENC ? (const void*)wp : (const void*)x_src), osr = make_rsrc(out_dst);
-    auto x_load = [&](int s) {   // the input of step s (time index by direction)
-        const int t = dir ? (WIN - 1 - s) : s;
-        if constexpr (ENC) {
-            const uint8_t* src = img0 + t * FEAT;
-#pragma unroll
-            for (int u = 0; u < XE; u++) xe[u] = src[xoff[u]];
-        } else {
-#pragma unroll
-            for (int u = 0; u < XR; u++) xr[u] = buf_load4(xsr, xd_g * 4u, (unsigned)((t * TR + u * 4) * KPD * 4));
-        }
-    };
-    auto x_store = [&](int slot) {
-        float* xb = xbuf + slot * TR * LDXD;
-        if constexpr (ENC) {
-#pragma unroll
-            for (int u = 0; u < XE; u++) (xb + u * 8 * LDX)[xe_l] = xe_valid ? (float)xe[u] : 0.0f;
-        } else {
-#pragma unroll
-            for (int u = 0; u < XR; u++) *reinterpret_cast<f32x4*>(xb + u * 4 * LDX + xd_l) = xr[u];
-        }
-    };
+    XStage<TR, KP, ENC> xs(a, win_start, tid_dir, b0, x_src, wp);
+    const __amdgpu_buffer_rsrc_t wr = make_rsrc(wp), osr = make_rsrc(out_dst);
+    auto x_load = [&](int s) { xs.load(dir ? (WIN - 1 - s) : s); };   // the input of step s (time index by direction)
+    auto x_store = [&](int slot) { xs.store(xbuf + slot * TR * LDXD); };
     constexpr int D = NTOT % 8 == 0 ? 8 : 4;   // decoder: 48 blocks per step, 8 register sets; encoder: 20 blocks, 4 sets
     f32x4 bq[D][3];  // the ring starts with the first x-part blocks (the prologue runs the x-part of step 0)
 #pragma unroll
@@ -478,6 +466,44 @@ __device__ __forceinline__ void gru_window_ovl(const GruArgs& a, int win_start, 
     __syncthreads();   // the window's outputs (global scratch) are read by the next phase (after the hand-off)
 }
 
+// ---- the head of a window, by the PARTS workgroups of a tile -----------------------------------------------------------------
+// dense1 + softmax + accumulate over one window (predict.py:70-89), TR * 100 (row, t) pairs, and at the end of the launch the
+// labels. Workgroup `part` of the PARTS (1, 2 or 4) that share a tile owns the columns whose position in the chunk has
+// (position & (PARTS - 1)) == part, for acc, logits and labels alike: windows overlap but positions do not move, so every
+// column of acc is added to, and finally read, by one workgroup only, and nothing is shared. (ws is even: with two parts
+// the owner of a column is the parity of t.)
+template <int TR, int NTHR, int PARTS>
+__device__ __forceinline__ void p2_dense_window(const GruArgs& a, const float* dec_out, int64_t b0, int ws, bool last, int tid, int part) {
+    for (int p = tid; p < TR * WIN; p += NTHR) {
+        const int t = p / TR, row = p - t * TR;
+        const int64_t b = b0 + row;
+        if (b >= a.B || (PARTS > 1 && ((ws + t) & (PARTS - 1)) != part)) continue;
+        const float* d = dec_out + ((size_t)t * TR + row) * KPD;
+        float lg[NCLS];
+#pragma unroll
+        for (int c = 0; c < NCLS; c++) lg[c] = a.dense_b[c];
+        for (int k = 0; k < KPD; k += 4) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(d + k);
+#pragma unroll
+            for (int c = 0; c < NCLS; c++) {
+                const f32x4 wv4 = *reinterpret_cast<const f32x4*>(a.dense_w + c * KPD + k);
+                lg[c] += v[0] * wv4[0] + v[1] * wv4[1] + v[2] * wv4[2] + v[3] * wv4[3];
+            }
+        }
+        p2_softmax_acc(lg, a.acc + ((size_t)b * a.seq + ws + t) * NCLS, last ? a.logits : nullptr, (size_t)b * WIN + t);
+    }
+}
+
+template <int TR, int NTHR, int PARTS>
+__device__ __forceinline__ void p2_argmax_rows(const GruArgs& a, int64_t b0, int tid, int part) {
+    for (int p = tid; a.labels && p < TR * a.seq; p += NTHR) {
+        const int row = p / a.seq, pos = p - row * a.seq;
+        const int64_t b = b0 + row;
+        if (b >= a.B || (PARTS > 1 && (pos & (PARTS - 1)) != part)) continue;
+        a.labels[(size_t)b * a.seq + pos] = (uint8_t)argmax5(a.acc + ((size_t)b * a.seq + pos) * NCLS);
+    }
+}
+
 template <int TR, bool SPLIT>
 __global__ __launch_bounds__(SPLIT ? 256 : 512, SPLIT ? 1 : 2) void k_gru_p2(GruArgs a) {
     extern __shared__ float smem[];
@@ -490,8 +516,6 @@ __global__ __launch_bounds__(SPLIT ? 256 : 512, SPLIT ? 1 : 2) void k_gru_p2(Gru
     float* xbuf = hbuf + 2 * TR * LDH;
     const int tile = SPLIT ? (int)(blockIdx.x >> 1) : (int)blockIdx.x;
     if (SPLIT && a.drop_part >= 0 && dir == (a.drop_part & 1)) return;   // diagnostic: a partner that never shows up
-    int* my_flag = SPLIT ? a.pair_flags + 2 * tile + dir : nullptr;
-    const int* their_flag = SPLIT ? a.pair_flags + 2 * tile + (dir ^ 1) : nullptr;
     int handoffs = 0;
     const int64_t b0 = (int64_t)tile * TR;
     float* enc_out = a.enc_out + (size_t)tile * WIN * TR * KPD;
@@ -525,45 +549,14 @@ __global__ __launch_bounds__(SPLIT ? 256 : 512, SPLIT ? 1 : 2) void k_gru_p2(Gru
         const int ws = w * JUMP;
         if constexpr (SPLIT) gru_window_ovl<KPE, true>(a, ws, dir, wq, lane, tid_dir, b0, xbuf, hbuf, cur, hst, enc_wp, enc_bias, nullptr, enc_out);
         else gru_window<TR, KPE, true>(a, ws, dir, wq, lane, tid_dir, b0, xbuf, hbuf, cur, hst, enc_wp, enc_bias, nullptr, enc_out);
-        if constexpr (SPLIT) pair_handoff(my_flag, their_flag, ++handoffs, tid, a.err, a.spin_limit << 8);   // both halves of the encoder output are there
+        // both halves of the encoder output are there
+        if constexpr (SPLIT) tile_handoff<2, 1>(a.pair_flags + 2 * tile, dir, ++handoffs, tid, a.err, a.spin_limit << 8);
         // decoder h0 = encoder final state of the same direction: hst / hbuf[cur] simply carry over
         if constexpr (SPLIT) gru_window_ovl<KPD, false>(a, ws, dir, wq, lane, tid_dir, b0, xbuf, hbuf, cur, hst, dec_wp, dec_bias, enc_out, dec_out);
         else gru_window<TR, KPD, false>(a, ws, dir, wq, lane, tid_dir, b0, xbuf, hbuf, cur, hst, dec_wp, dec_bias, enc_out, dec_out);
-        if constexpr (SPLIT) pair_handoff(my_flag, their_flag, ++handoffs, tid, a.err, a.spin_limit << 8);   // both halves of the decoder output; the partner is
-                                                                                    // done reading the encoder output as well
-        // dense1 + softmax + accumulate over the window (predict.py:70-89); TR*100 (row, t) pairs. Split form: the workgroup of
-        // direction d owns the columns of parity d (ws is even), for acc, logits and labels alike, so no column is shared.
-        for (int p = tid; p < TR * WIN; p += NTHR) {
-            const int t = p / TR, row = p - t * TR;
-            const int64_t b = b0 + row;
-            if (b >= a.B || (SPLIT && (t & 1) != dir)) continue;
-            const float* d = dec_out + ((size_t)t * TR + row) * KPD;
-            float lg[NCLS];
-#pragma unroll
-            for (int c = 0; c < NCLS; c++) lg[c] = a.dense_b[c];
-            for (int k = 0; k < KPD; k += 4) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(d + k);
-#pragma unroll
-                for (int c = 0; c < NCLS; c++) {
-                    const f32x4 wv4 = *reinterpret_cast<const f32x4*>(a.dense_w + c * KPD + k);
-                    lg[c] += v[0] * wv4[0] + v[1] * wv4[1] + v[2] * wv4[2] + v[3] * wv4[3];
-                }
-            }
-            float m = lg[0];
-#pragma unroll
-            for (int c = 1; c < NCLS; c++) m = fmaxf(m, lg[c]);
-            float e[NCLS], sum = 0.0f;
-#pragma unroll
-            for (int c = 0; c < NCLS; c++) { e[c] = expf(lg[c] - m); sum += e[c]; }
-            const float inv = 1.0f / sum;
-            float* ac = a.acc + ((size_t)b * a.seq + ws + t) * NCLS;
-#pragma unroll
-            for (int c = 0; c < NCLS; c++) ac[c] += e[c] * inv;
-            if (a.logits && w == a.nwin - 1) {
-#pragma unroll
-                for (int c = 0; c < NCLS; c++) a.logits[((size_t)b * WIN + t) * NCLS + c] = lg[c];
-            }
-        }
+        // both halves of the decoder output; the partner is done reading the encoder output as well
+        if constexpr (SPLIT) tile_handoff<2, 1>(a.pair_flags + 2 * tile, dir, ++handoffs, tid, a.err, a.spin_limit << 8);
+        p2_dense_window<TR, NTHR, SPLIT ? 2 : 1>(a, dec_out, b0, ws, w == a.nwin - 1, tid, dir);
         __syncthreads();
     }
     if (a.hidden_out) {  // final decoder state (the next window's encoder h0, simple_model.py:41)
@@ -573,18 +566,7 @@ __global__ __launch_bounds__(SPLIT ? 256 : 512, SPLIT ? 1 : 2) void k_gru_p2(Gru
             if (b < a.B) a.hidden_out[(b * 2 + dir) * HG + unit0 + elem_unit<TR>(e)] = hst[e];
         }
     }
-    // labels = argmax over the 5 classes, first maximum wins (torch.max, predict.py:91)
-    for (int p = tid; a.labels && p < TR * a.seq; p += NTHR) {
-        const int row = p / a.seq, pos = p - row * a.seq;
-        const int64_t b = b0 + row;
-        if (b >= a.B || (SPLIT && (pos & 1) != dir)) continue;
-        const float* ac = a.acc + ((size_t)b * a.seq + pos) * NCLS;
-        int best = 0;
-        float bv = ac[0];
-#pragma unroll
-        for (int c = 1; c < NCLS; c++) if (ac[c] > bv) { bv = ac[c]; best = c; }
-        a.labels[(size_t)b * a.seq + pos] = (uint8_t)best;
-    }
+    p2_argmax_rows<TR, NTHR, SPLIT ? 2 : 1>(a, b0, tid, dir);
 }
 
 
@@ -640,29 +622,6 @@ __device__ __forceinline__ void ring_us(f32x4& gr, f32x4& gz, f32x4& gn, const f
     }
 }
 
-// counters + fences among the four workgroups of a tile (layer boundaries only)
-__device__ __forceinline__ void quad_handoff(int* flags_tile, int me, int value, int tid, int* err, int limit) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(flags_tile + me * US_FLAG_STRIDE, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int k = 1; k < 4; k++) {
-            const int* f = flags_tile + ((me + k) & 3) * US_FLAG_STRIDE;
-            int spins = 0;
-            while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < value) {
-                __builtin_amdgcn_s_sleep(2);
-                if (++spins > limit) { atomicAdd(err, 1); break; }   // bounded: a lost partner ends in POISONED results, never in a hung device
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-}
-
 // one GRU layer over one 100-column window for this workgroup's (direction, half). `step` counts the steps of the launch (tags).
 template <int KP, bool ENC, int D>
 __device__ __forceinline__ void gru_window_us(const GruArgs& a, int win_start, int dir, int half, int wv, int lane, int tid,
@@ -676,46 +635,10 @@ __device__ __forceinline__ void gru_window_us(const GruArgs& a, int win_start, i
     const int unit = 64 * half + 16 * wv + (lane & 15);
     const int rowg = lane >> 4;
     const float b_r = bias[0 * HG + unit], b_z = bias[1 * HG + unit], b_in = bias[2 * HG + unit], b_hn = bias[3 * HG + unit];
-    constexpr int XR = ENC ? 1 : 4;     // decoder: float4 per thread, rows tid/64 + 4u
-    constexpr int XE = 2;               // encoder: bytes per thread, rows tid/32 + 8u
-    f32x4 xr[XR];
-    unsigned xe[ENC ? XE : 1];
-    unsigned xoff[ENC ? XE : 1];
-    const unsigned xd_g = (unsigned)((tid >> 6) * KPD + (tid & 63) * 4);
-    const unsigned xd_l = (unsigned)((tid >> 6) * LDX + (tid & 63) * 4);
-    const unsigned xe_l = (unsigned)((tid >> 5) * LDX + (tid & 31));
-    const bool xe_valid = (tid & 31) < FEAT;
-    if constexpr (ENC) {
-#pragma unroll
-        for (int u = 0; u < XE; u++) {
-            int64_t r = (tid >> 5) + 8 * u;
-            if (b0 + r >= a.B) r = a.B - 1 - b0;
-            xoff[u] = (unsigned)(r * a.seq * FEAT) + (unsigned)((tid & 31) < FEAT ? (tid & 31) : FEAT - 1);
-        }
-    }
-    const uint8_t* img0 = a.images + ((size_t)b0 * a.seq + win_start) * FEAT;
-    const __amdgpu_buffer_rsrc_t wr = make_rsrc(wp), xsr = make_rsrc(ENC ? (const void*)wp : (const void*)x_src), osr = make_rsrc(out_dst);
-    auto x_load = [&](int s) {
-        const int t = dir ? (WIN - 1 - s) : s;
-        if constexpr (ENC) {
-            const uint8_t* src = img0 + t * FEAT;
-#pragma unroll
-            for (int u = 0; u < XE; u++) xe[u] = src[xoff[u]];
-        } else {
-#pragma unroll
-            for (int u = 0; u < XR; u++) xr[u] = buf_load4(xsr, xd_g * 4u, (unsigned)((t * TR + u * 4) * KPD * 4));
-        }
-    };
-    auto x_store = [&](int slot) {
-        float* xb = xbuf + slot * TR * LDXD;
-        if constexpr (ENC) {
-#pragma unroll
-            for (int u = 0; u < XE; u++) (xb + u * 8 * LDX)[xe_l] = xe_valid ? (float)xe[u] : 0.0f;
-        } else {
-#pragma unroll
-            for (int u = 0; u < XR; u++) *reinterpret_cast<f32x4*>(xb + u * 4 * LDX + xd_l) = xr[u];
-        }
-    };
+    XStage<TR, KP, ENC> xs(a, win_start, tid, b0, x_src, wp);
+    const __amdgpu_buffer_rsrc_t wr = make_rsrc(wp), osr = make_rsrc(out_dst);
+    auto x_load = [&](int s) { xs.load(dir ? (WIN - 1 - s) : s); };   // the input of step s (time index by direction)
+    auto x_store = [&](int slot) { xs.store(xbuf + slot * TR * LDXD); };
     f32x4 bq[D][3];   // the stream order is [h | x]; the prologue runs the x-part of step 0, so the ring starts at pair NP_H
 #pragma unroll
     for (int q = 0; q < D - 1; q++)
@@ -877,42 +800,10 @@ __global__ __launch_bounds__(256, 1) void k_gru_us(GruArgs a_in) {
     for (int w = 0; w < a.nwin; w++) {
         const int ws = w * JUMP;
         gru_window_us<KPE, true, NPE>(a, ws, dir, half, wv, lane, tid, b0, xbuf, hbuf, cur, hst, step, enc_wp, enc_bias, nullptr, enc_out, hsr);
-        quad_handoff(flags_tile, sub, ++handoffs, tid, a.err, a.spin_limit << 8);   // all four quarters of the encoder output are there
+        tile_handoff<4, US_FLAG_STRIDE>(flags_tile, sub, ++handoffs, tid, a.err, a.spin_limit << 8);   // all four quarters of the encoder output are there
         gru_window_us<KPD, false, 8>(a, ws, dir, half, wv, lane, tid, b0, xbuf, hbuf, cur, hst, step, dec_wp, dec_bias, enc_out, dec_out, hsr);
-        quad_handoff(flags_tile, sub, ++handoffs, tid, a.err, a.spin_limit << 8);   // the decoder output; everybody is done reading the encoder output too
-        // dense1 + softmax + accumulate (predict.py:70-89): workgroup `sub` owns the columns with (position & 3) == sub, for
-        // acc, logits and labels alike (windows overlap, positions do not move), so no column is shared
-        for (int p = tid; p < TR * WIN; p += 256) {
-            const int t = p / TR, row = p - t * TR;
-            const int64_t b = b0 + row;
-            if (b >= a.B || ((ws + t) & 3) != sub) continue;
-            const float* d = dec_out + ((size_t)t * TR + row) * KPD;
-            float lg[NCLS];
-#pragma unroll
-            for (int c = 0; c < NCLS; c++) lg[c] = a.dense_b[c];
-            for (int k = 0; k < KPD; k += 4) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(d + k);
-#pragma unroll
-                for (int c = 0; c < NCLS; c++) {
-                    const f32x4 wv4 = *reinterpret_cast<const f32x4*>(a.dense_w + c * KPD + k);
-                    lg[c] += v[0] * wv4[0] + v[1] * wv4[1] + v[2] * wv4[2] + v[3] * wv4[3];
-                }
-            }
-            float m = lg[0];
-#pragma unroll
-            for (int c = 1; c < NCLS; c++) m = fmaxf(m, lg[c]);
-            float e[NCLS], sum = 0.0f;
-#pragma unroll
-            for (int c = 0; c < NCLS; c++) { e[c] = expf(lg[c] - m); sum += e[c]; }
-            const float inv = 1.0f / sum;
-            float* ac = a.acc + ((size_t)b * a.seq + ws + t) * NCLS;
-#pragma unroll
-            for (int c = 0; c < NCLS; c++) ac[c] += e[c] * inv;
-            if (a.logits && w == a.nwin - 1) {
-#pragma unroll
-                for (int c = 0; c < NCLS; c++) a.logits[((size_t)b * WIN + t) * NCLS + c] = lg[c];
-            }
-        }
+        tile_handoff<4, US_FLAG_STRIDE>(flags_tile, sub, ++handoffs, tid, a.err, a.spin_limit << 8);   // the decoder output; everybody is done reading the encoder output too
+        p2_dense_window<TR, 256, 4>(a, dec_out, b0, ws, w == a.nwin - 1, tid, sub);
         __syncthreads();
     }
     if (a.hidden_out) {
@@ -922,17 +813,7 @@ __global__ __launch_bounds__(256, 1) void k_gru_us(GruArgs a_in) {
             if (b < a.B) a.hidden_out[(b * 2 + dir) * HG + unit] = hst[i];
         }
     }
-    for (int p = tid; a.labels && p < TR * a.seq; p += 256) {
-        const int row = p / a.seq, pos = p - row * a.seq;
-        const int64_t b = b0 + row;
-        if (b >= a.B || (pos & 3) != sub) continue;
-        const float* ac = a.acc + ((size_t)b * a.seq + pos) * NCLS;
-        int best = 0;
-        float bv = ac[0];
-#pragma unroll
-        for (int c = 1; c < NCLS; c++) if (ac[c] > bv) { bv = ac[c]; best = c; }
-        a.labels[(size_t)b * a.seq + pos] = (uint8_t)best;
-    }
+    p2_argmax_rows<TR, 256, 4>(a, b0, tid, sub);
 }
 
 constexpr size_t LDS_US = (size_t)(2 * 16 * LDH + 2 * 16 * LDXD) * sizeof(float);

@@ -20,6 +20,7 @@
 #include "rnn_bf16.hpp"
 #include "mfma_tiles.hpp"
 #include "rnn_math.hpp"
+#include "rnn_p2_head.hpp"
 #include "rnn_pack_host.hpp"
 
 #include <algorithm>
@@ -1092,7 +1093,6 @@ int pv_rec_bf16_async(pv_ctx* ctx, const pv_rec_desc& d, hipStream_t st) {
 // between the launches in a [Bp][2][128] buffer: encoder h0 = carried state, decoder h0 = encoder final state, next window's
 // h0 = decoder final state (simple_model.py:27-42). 19 x 4 launches per call, all stream work (graph-capturable).
 namespace {
-constexpr int P2_WIN = 100, P2_JUMP = 50, P2_F = 10, P2_H = 128, P2_NC = 5;
 
 // dense1 (256 -> 5) + softmax + accumulate for one window: 8 lanes per (t, b) pair
 __global__ __launch_bounds__(256) void k_p2_dense(const unsigned char* __restrict__ dec /*split8 [100][Bp][256]*/, int64_t Bp, int64_t B,
@@ -1100,13 +1100,13 @@ __global__ __launch_bounds__(256) void k_p2_dense(const unsigned char* __restric
                                                   int seq, int ws, float* __restrict__ logits) {
     const int64_t pair = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 3;
     const int sub = threadIdx.x & 7;
-    if (pair >= (int64_t)P2_WIN * B) return;   // whole groups of 8 lanes leave together
+    if (pair >= (int64_t)p2::WIN * B) return;   // whole groups of 8 lanes leave together
     const int t = (int)(pair / B);
     const int64_t b = pair - (int64_t)t * B;
     // the decoder's output arrives as split8 rows (hi + lo = the fp32 value to 2^-17): lane `sub` takes the 8-unit groups
     // sub, sub + 8, sub + 16, sub + 24 (32 contiguous bytes each)
-    const unsigned char* d = dec + ((size_t)t * Bp + b) * (2 * P2_H * 4);
-    float lg[P2_NC] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    const unsigned char* d = dec + ((size_t)t * Bp + b) * (2 * p2::HG * 4);
+    float lg[p2::NCLS] = {0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const int grp = sub + 8 * i;
@@ -1115,32 +1115,34 @@ __global__ __launch_bounds__(256) void k_p2_dense(const unsigned char* __restric
 #pragma unroll
         for (int j = 0; j < 8; j++) v[j] = (float)hi[j] + (float)lo[j];
 #pragma unroll
-        for (int c = 0; c < P2_NC; c++) {
-            const f32x4 w0 = *reinterpret_cast<const f32x4*>(W + c * 2 * P2_H + grp * 8), w1 = *reinterpret_cast<const f32x4*>(W + c * 2 * P2_H + grp * 8 + 4);
+        for (int c = 0; c < p2::NCLS; c++) {
+            const f32x4 w0 = *reinterpret_cast<const f32x4*>(W + c * 2 * p2::HG + grp * 8), w1 = *reinterpret_cast<const f32x4*>(W + c * 2 * p2::HG + grp * 8 + 4);
             lg[c] += v[0] * w0[0] + v[1] * w0[1] + v[2] * w0[2] + v[3] * w0[3] + v[4] * w1[0] + v[5] * w1[1] + v[6] * w1[2] + v[7] * w1[3];
         }
     }
 #pragma unroll
-    for (int c = 0; c < P2_NC; c++) {
+    for (int c = 0; c < p2::NCLS; c++) {
         lg[c] += __shfl_xor(lg[c], 4, 64);
         lg[c] += __shfl_xor(lg[c], 2, 64);
         lg[c] += __shfl_xor(lg[c], 1, 64);
         lg[c] += bias[c];
     }
     if (sub != 0) return;
+    // Not p2_softmax_acc: this kernel cannot run on a 256-CU chip (rnn_plan.hpp folds dense1 into the decoder there), so nothing
+    // can test it on the hardware at hand, and with the shared tail hipcc schedules it differently. Its own copy stays.
     float m = lg[0];
 #pragma unroll
-    for (int c = 1; c < P2_NC; c++) m = fmaxf(m, lg[c]);
-    float e[P2_NC], sum = 0.0f;
+    for (int c = 1; c < p2::NCLS; c++) m = fmaxf(m, lg[c]);
+    float e[p2::NCLS], sum = 0.0f;
 #pragma unroll
-    for (int c = 0; c < P2_NC; c++) { e[c] = expf(lg[c] - m); sum += e[c]; }
+    for (int c = 0; c < p2::NCLS; c++) { e[c] = expf(lg[c] - m); sum += e[c]; }
     const float inv = 1.0f / sum;
-    float* ac = acc + ((size_t)b * seq + ws + t) * P2_NC;
+    float* ac = acc + ((size_t)b * seq + ws + t) * p2::NCLS;
 #pragma unroll
-    for (int c = 0; c < P2_NC; c++) ac[c] += e[c] * inv;
+    for (int c = 0; c < p2::NCLS; c++) ac[c] += e[c] * inv;
     if (logits) {
 #pragma unroll
-        for (int c = 0; c < P2_NC; c++) logits[((size_t)b * P2_WIN + t) * P2_NC + c] = lg[c];
+        for (int c = 0; c < p2::NCLS; c++) logits[((size_t)b * p2::WIN + t) * p2::NCLS + c] = lg[c];
     }
 }
 
@@ -1148,23 +1150,18 @@ __global__ __launch_bounds__(256) void k_p2_dense(const unsigned char* __restric
 __global__ __launch_bounds__(256) void k_p2_argmax(const float* __restrict__ acc, int64_t n, uint8_t* __restrict__ labels) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float* ac = acc + i * P2_NC;
-    int best = 0;
-    float bv = ac[0];
-#pragma unroll
-    for (int c = 1; c < P2_NC; c++) if (ac[c] > bv) { bv = ac[c]; best = c; }
-    labels[i] = (uint8_t)best;
+    labels[i] = (uint8_t)argmax5(acc + i * p2::NCLS);
 }
 
 // state [Bp][2][128] <- hidden_in [B][2][128] (rows beyond B: zeros) or zeros;   hidden_out [B][2][128] <- state
 __global__ __launch_bounds__(256) void k_p2_state_in(float* __restrict__ state, const float* __restrict__ hin, int64_t B, int64_t Bp) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= Bp * 2 * P2_H) return;
-    state[i] = (hin && i < B * 2 * P2_H) ? hin[i] : 0.0f;
+    if (i >= Bp * 2 * p2::HG) return;
+    state[i] = (hin && i < B * 2 * p2::HG) ? hin[i] : 0.0f;
 }
 __global__ __launch_bounds__(256) void k_p2_state_out(const float* __restrict__ state, float* __restrict__ hout, int64_t B) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < B * 2 * P2_H) hout[i] = state[i];
+    if (i < B * 2 * p2::HG) hout[i] = state[i];
 }
 
 // sum of the decoder kernel's partial logits (2 directions x 4 waves) + bias -> softmax -> accumulate (predict.py:70-89);
@@ -1173,31 +1170,18 @@ template <int TR>   // rows of the decoder kernel's tiles (32, or 16: k_gru16_bf
 __global__ __launch_bounds__(256) void k_p2_combine(const float* __restrict__ part, int64_t Bp, int64_t B, const float* __restrict__ bias,
                                                     float* __restrict__ acc, int seq, int ws, float* __restrict__ logits) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)P2_WIN * B) return;
+    if (i >= (int64_t)p2::WIN * B) return;
     const int t = (int)(i / B);
     const int64_t b = i - (int64_t)t * B;
     const float* p = part + (((size_t)t * (Bp / TR) + (size_t)(b / TR)) * 8) * (8 * TR) + (b % TR);
-    float lg[P2_NC];
+    float lg[p2::NCLS];
 #pragma unroll
-    for (int c = 0; c < P2_NC; c++) lg[c] = bias[c];
+    for (int c = 0; c < p2::NCLS; c++) lg[c] = bias[c];
 #pragma unroll
     for (int k = 0; k < 8; k++)   // (direction, wave)
 #pragma unroll
-        for (int c = 0; c < P2_NC; c++) lg[c] += p[k * 8 * TR + c * TR];
-    float m = lg[0];
-#pragma unroll
-    for (int c = 1; c < P2_NC; c++) m = fmaxf(m, lg[c]);
-    float e[P2_NC], sum = 0.0f;
-#pragma unroll
-    for (int c = 0; c < P2_NC; c++) { e[c] = expf(lg[c] - m); sum += e[c]; }
-    const float inv = 1.0f / sum;
-    float* ac = acc + ((size_t)b * seq + ws + t) * P2_NC;
-#pragma unroll
-    for (int c = 0; c < P2_NC; c++) ac[c] += e[c] * inv;
-    if (logits) {
-#pragma unroll
-        for (int c = 0; c < P2_NC; c++) logits[((size_t)b * P2_WIN + t) * P2_NC + c] = lg[c];
-    }
+        for (int c = 0; c < p2::NCLS; c++) lg[c] += p[k * 8 * TR + c * TR];
+    p2_softmax_acc(lg, acc + ((size_t)b * seq + ws + t) * p2::NCLS, logits, (size_t)b * p2::WIN + t);
 }
 }  // namespace
 
@@ -1216,36 +1200,36 @@ int pv_pack_p2_dense(const float* dense_w, unsigned char** d_frag, std::vector<v
 int pv_p2_bf16_forward(pv_ctx* ctx, const pv_p2_plan& pl, const pv_p2_bf16_weights& w, const uint8_t* d_images, int64_t B, uint8_t* d_labels,
                        float* d_acc, hipStream_t st, int seq, int nwin, const float* d_hidden_in, float* d_hidden_out, float* d_logits) {
     const int tr16 = pl.kind == PV_P2_GRU16 ? 1 : 0, mt = pl.mt, fold_dense = pl.fold_dense;
-    const int64_t Bp = pl.Bp, M = (int64_t)P2_WIN * Bp;
+    const int64_t Bp = pl.Bp, M = (int64_t)p2::WIN * Bp;
     float *state = nullptr, *G = nullptr;
     unsigned char *enc_s = nullptr, *dec = nullptr;
     int rc;
-    if ((rc = pv_get(ctx, "p2b.state", (size_t)Bp * 2 * P2_H, &state))) return rc;
-    if ((rc = pv_get(ctx, "p2b.enc_s", (size_t)M * 2 * P2_H * 4, &enc_s))) return rc;
-    if ((rc = pv_get(ctx, "p2b.G", (size_t)M * 6 * P2_H, &G))) return rc;
+    if ((rc = pv_get(ctx, "p2b.state", (size_t)Bp * 2 * p2::HG, &state))) return rc;
+    if ((rc = pv_get(ctx, "p2b.enc_s", (size_t)M * 2 * p2::HG * 4, &enc_s))) return rc;
+    if ((rc = pv_get(ctx, "p2b.G", (size_t)M * 6 * p2::HG, &G))) return rc;
     // dense1 folded into the decoder: partial logits of 2 directions x 4 waves; else the decoder's split8 output for k_p2_dense
     float* dpart = nullptr;
     if (fold_dense) {
-        if ((rc = pv_get(ctx, "p2b.dpart", (size_t)P2_WIN * (Bp / (tr16 ? 16 : 32)) * 8 * (tr16 ? 128 : 256), &dpart))) return rc;
-    } else if ((rc = pv_get(ctx, "p2b.dec_s", (size_t)M * 2 * P2_H * 4, &dec))) {
+        if ((rc = pv_get(ctx, "p2b.dpart", (size_t)p2::WIN * (Bp / (tr16 ? 16 : 32)) * 8 * (tr16 ? 128 : 256), &dpart))) return rc;
+    } else if ((rc = pv_get(ctx, "p2b.dec_s", (size_t)M * 2 * p2::HG * 4, &dec))) {
         return rc;
     }
-    if ((rc = pv_zero_async(d_acc, (size_t)B * seq * P2_NC * sizeof(float), st))) return rc;
-    k_p2_state_in<<<(unsigned)((Bp * 2 * P2_H + 255) / 256), 256, 0, st>>>(state, d_hidden_in, B, Bp);
+    if ((rc = pv_zero_async(d_acc, (size_t)B * seq * p2::NCLS * sizeof(float), st))) return rc;
+    k_p2_state_in<<<(unsigned)((Bp * 2 * p2::HG + 255) / 256), 256, 0, st>>>(state, d_hidden_in, B, Bp);
     for (int wi = 0; wi < nwin; wi++) {
-        const int ws = wi * P2_JUMP;
+        const int ws = wi * p2::JUMP;
         pv_rec_desc e = {};
         e.cell = 3; e.enc = 1; e.wp = w.enc_wp; e.wx = w.enc_wx; e.bias = w.enc_bias; e.bias_hn = w.enc_bias_hn;
-        e.x = d_images; e.x_row_bytes = (int64_t)seq * P2_F; e.x_t0 = ws; e.xf = P2_F; e.x_signed = 0;
-        e.B = B; e.Bp = Bp; e.T = P2_WIN; e.h0 = state; e.h_out = state; e.out_tm = enc_s; e.mt = mt; e.prof_name = "k_rec_bf16_gru_enc";
+        e.x = d_images; e.x_row_bytes = (int64_t)seq * p2::FEAT; e.x_t0 = ws; e.xf = p2::FEAT; e.x_signed = 0;
+        e.B = B; e.Bp = Bp; e.T = p2::WIN; e.h0 = state; e.h_out = state; e.out_tm = enc_s; e.mt = mt; e.prof_name = "k_rec_bf16_gru_enc";
         if (tr16) { e.tr16 = tr16; e.wp = w.enc16_wp; e.wx = w.enc16_wx; e.prof_name = "k_gru16_bf16_enc"; }
         if ((rc = pv_rec_bf16_async(ctx, e, st))) return rc;
         pv_gemm_desc g = {};
-        g.A = enc_s; g.W = w.dec_wih_s; g.bias = w.dec_bias_cat; g.C = G; g.M = M; g.N = 6 * P2_H; g.K = 2 * P2_H; g.splits = 1; g.quads = 1;
+        g.A = enc_s; g.W = w.dec_wih_s; g.bias = w.dec_bias_cat; g.C = G; g.M = M; g.N = 6 * p2::HG; g.K = 2 * p2::HG; g.splits = 1; g.quads = 1;
         g.prof_name = "k_gemm_bf16x3_gru_dec";
         if ((rc = pv_gemm_bf16x3_async(ctx, g, st))) return rc;
         pv_rec_desc d = {};
-        d.cell = 3; d.enc = 0; d.G = G; d.wp = w.dec_wp; d.bias_hn = w.dec_bias_hn; d.B = B; d.Bp = Bp; d.T = P2_WIN;
+        d.cell = 3; d.enc = 0; d.G = G; d.wp = w.dec_wp; d.bias_hn = w.dec_bias_hn; d.B = B; d.Bp = Bp; d.T = p2::WIN;
         d.h0 = state; d.h_out = state; d.mt = mt; d.prof_name = "k_rec_bf16_gru_dec";
         if (tr16) { d.tr16 = tr16; d.wp = w.dec16_wp; d.prof_name = "k_gru16_bf16_dec"; }
         float* lg_out = (d_logits && wi == nwin - 1) ? d_logits : nullptr;
@@ -1253,18 +1237,18 @@ int pv_p2_bf16_forward(pv_ctx* ctx, const pv_p2_plan& pl, const pv_p2_bf16_weigh
             d.dense_w = tr16 ? w.dense_frag16 : w.dense_frag; d.dense_part = dpart;
             if ((rc = pv_rec_bf16_async(ctx, d, st))) return rc;
             pv_prof_scope ps(ctx, "k_p2_combine", st);
-            const int64_t nthr = (int64_t)P2_WIN * B;
+            const int64_t nthr = (int64_t)p2::WIN * B;
             if (tr16) k_p2_combine<16><<<(unsigned)((nthr + 255) / 256), 256, 0, st>>>(dpart, Bp, B, w.dense_b, d_acc, seq, ws, lg_out);
             else k_p2_combine<32><<<(unsigned)((nthr + 255) / 256), 256, 0, st>>>(dpart, Bp, B, w.dense_b, d_acc, seq, ws, lg_out);
         } else {
             d.out_tm = dec;
             if ((rc = pv_rec_bf16_async(ctx, d, st))) return rc;
             pv_prof_scope ps(ctx, "k_p2_dense", st);
-            const int64_t nthr = (int64_t)P2_WIN * B * 8;
+            const int64_t nthr = (int64_t)p2::WIN * B * 8;
             k_p2_dense<<<(unsigned)((nthr + 255) / 256), 256, 0, st>>>(dec, Bp, B, w.dense_w, w.dense_b, d_acc, seq, ws, lg_out);
         }
     }
-    if (d_hidden_out) k_p2_state_out<<<(unsigned)((B * 2 * P2_H + 255) / 256), 256, 0, st>>>(state, d_hidden_out, B);
+    if (d_hidden_out) k_p2_state_out<<<(unsigned)((B * 2 * p2::HG + 255) / 256), 256, 0, st>>>(state, d_hidden_out, B);
     if (d_labels) k_p2_argmax<<<(unsigned)((B * seq + 255) / 256), 256, 0, st>>>(d_acc, B * seq, d_labels);
     PV_HIP(hipGetLastError());
     return PV_OK;

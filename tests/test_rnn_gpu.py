@@ -451,8 +451,8 @@ def test_p1_exchange_timeout_poisons_the_call(hip_ctx, opts):
 
 @pytest.mark.parametrize("form", ["unit_split", "direction_split"])
 def test_p2_exchange_timeout_poisons_the_call(hip_ctx, opts, form):
-    """the same for the GRU forms: the per-step poll (unit split), pair_handoff (direction split) and quad_handoff all count
-    their give-ups; k_gru_finish then writes labels 255 and NaN into everything the launch produced"""
+    """the same for the GRU forms: the per-step poll (unit split) and tile_handoff (two partners in the direction split, four in
+    the unit split) all count their give-ups; k_gru_finish then writes labels 255 and NaN into everything the launch produced"""
     from pepper_thesis_amd import _ffi
     hip_ctx.load_p2(synth.make_weights_p2(13, 2.0))
     y = synth.synth_p2_images(640, 20)
