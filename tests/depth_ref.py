@@ -19,21 +19,26 @@ DEPTH_MAX = 65535
 def region_depth(batch, g: int) -> np.ndarray:
     """int64 [ref_end - ref_start + 1]: reads per draft position of region g of a flat batch (RegionBatch), from its CIGARs"""
     start, end = int(batch.ref_start[g]), int(batch.ref_end[g])
-    depth = np.zeros(end - start + 1, np.int64)
-    for r in range(int(batch.read_off[g]), int(batch.read_off[g + 1])):
-        if int(batch.read_mapq[r]) == 0:
-            continue
-        ref = int(batch.read_pos[r])
-        for w in batch.cigar[int(batch.cigar_off[r]):int(batch.cigar_off[r + 1])].tolist():
-            op, ln = w & 0xF, w >> 4
-            if ref > end:
-                break
-            if op in M_OPS or op in D_OPS:
-                a, b = max(ref, start), min(ref + ln - 1, end)
-                if a <= b:
-                    depth[a - start:b - start + 1] += 1
-                ref += ln
-    return np.minimum(depth, DEPTH_MAX)
+    # all operations of the region's reads at once (a Python loop over them takes seconds on a read of 68 000 operations)
+    r0, r1 = int(batch.read_off[g]), int(batch.read_off[g + 1])
+    first = np.asarray(batch.cigar_off[r0:r1 + 1], np.int64)          # of every read: its first operation
+    words = np.asarray(batch.cigar[int(first[0]):int(first[-1])], np.int64)
+    step = np.zeros(end - start + 2, np.int64)     # +1 where an operation enters the region, -1 behind its last position in it
+    if len(words):
+        op, ln = words & 0xF, words >> 4
+        read = np.repeat(np.arange(r1 - r0), np.diff(first))         # of every operation: its read, counted from r0
+        counted = np.isin(op, M_OPS + D_OPS)
+        moves = np.where(counted, ln, 0)
+        before = np.cumsum(moves) - moves                            # positions consumed before the operation, region-wide ...
+        before -= before[np.minimum(first[:-1] - first[0], len(words) - 1)][read]     # ... and within its read
+        begin = np.asarray(batch.read_pos[r0:r1], np.int64)[read] + before
+        # an operation that begins behind the region's end ends the read (positions never decrease along a read)
+        counted &= (begin <= end) & (np.asarray(batch.read_mapq[r0:r1])[read] != 0)
+        a, b = np.maximum(begin[counted], start), np.minimum(begin[counted] + ln[counted] - 1, end)
+        inside = a <= b
+        np.add.at(step, a[inside] - start, 1)
+        np.add.at(step, b[inside] - start + 1, -1)
+    return np.minimum(np.cumsum(step)[:-1], DEPTH_MAX)
 
 
 def row_depth(batch, position, index, region) -> np.ndarray:
