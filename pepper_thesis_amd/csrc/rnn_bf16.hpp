@@ -56,7 +56,7 @@ struct pv_rec_desc {
                                // multiple of 16, mt unused)
     const unsigned char* dense_w;   // GRU decoder only: fragments of a [5][2 * hidden] dense layer (pv_pack_p2_dense) and ...
     float* dense_part;              // ... its partial logits [T][Bp / 32][2 dirs][4 waves][8][32 rows] (summed by k_p2_combine), or NULL
-    int x6;                    // LSTM only: the split-6 form (PV_DTYPE_F32 large calls): wp packed with pieces = 3, h and the outputs
+    int x6;                    // LSTM only: the split-6 form (PV_DTYPE_F32 large calls): wp from pv_pack_rec_x6, h and the outputs
                                // out_tm / out_bm as fp32 rows [.][2 * hidden] instead of split8
 };
 int pv_rec_bf16_async(pv_ctx* ctx, const pv_rec_desc& d, hipStream_t st);
@@ -66,6 +66,9 @@ int pv_rec_bf16_prepare();
 // pieces = 3 (LSTM only): slots of three bf16 pieces x0 | x1 | x2 (1 KB each, split3_bf16's rule) for the split-6 form
 int pv_pack_rec_bf16(const pv_rnn_dir* dirs, int cell, int kx, unsigned char** d_wp, unsigned char** d_wx, std::vector<void*>& owned,
                      int pieces = 2);
+// the stream of the split-6 LSTM form (d.x6) in the slot order its MFMA shape reads: pack_rec_x6_16, or pack_rec_bf16 with three
+// pieces in the -DPV_REC_X6_MFMA32 diagnostic build
+int pv_pack_rec_x6(const pv_rnn_dir* dirs, int kx, unsigned char** d_wp, std::vector<void*>& owned);
 int pv_pack_gru16_bf16(const pv_rnn_dir* dirs, int kx, unsigned char** d_wp, unsigned char** d_wx, std::vector<void*>& owned);
 
 // ---- k_tail_bf16: the tail of the P1 head (sum of linear_1 slabs + bias + SELU, linear_2..5 + SELU, output layer, softmax) with

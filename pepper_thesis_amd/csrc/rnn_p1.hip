@@ -124,8 +124,8 @@ extern "C" int pv_rnn_load_p1(pv_ctx* ctx, const pv_weights_p1* w, int dtype) {
     }
     if ((rc = pv_dev_upload(bcat, &m->dec_bias_cat, m->owned))) return rc;
     if (dtype == PV_DTYPE_F32) {   // the split-6 chain of large calls: 3.4 + 3.4 MB of fragments, 6 + 51.9 MB of bf16 weight planes
-        if ((rc = pv_pack_rec_bf16(w->encoder, 4, F_IN, &m->enc_r6, nullptr, m->owned, 3))) return rc;
-        if ((rc = pv_pack_rec_bf16(w->decoder, 4, 0, &m->dec_r6, nullptr, m->owned, 3))) return rc;
+        if ((rc = pv_pack_rec_x6(w->encoder, F_IN, &m->enc_r6, m->owned))) return rc;
+        if ((rc = pv_pack_rec_x6(w->decoder, 0, &m->dec_r6, m->owned))) return rc;
         if ((rc = pv_upload_split3(wcat.data(), 2048, 512, &m->dec_wih_p3, m->owned))) return rc;
         if ((rc = pv_upload_split3(w->linear_w[0], HEAD_N, HEAD_K, &m->w1_p3, m->owned))) return rc;
         if ((rc = pv_gemm_bf16x3_prepare()) || (rc = pv_rec_bf16_prepare())) return rc;

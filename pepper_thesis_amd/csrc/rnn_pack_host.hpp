@@ -6,7 +6,7 @@
 //
 //   fp32 fragments, f32 MFMA    pack_lstm, pack_lstm_split, pack_linear (P1: rnn_lstm.hip, rnn_head.hip)
 //                               pack_gru, pack_gru_us (P2: rnn_gru.hip)
-//   bf16 pieces, bf16 MFMA      pack_rec_bf16, pack_gru16_bf16, pack_tail_bf16, pack_p2_dense, pack_p2_dense16 (rnn_rec_bf16.hip)
+//   bf16 pieces, bf16 MFMA      pack_rec_bf16, pack_rec_x6_16, pack_gru16_bf16, pack_tail_bf16, pack_p2_dense, pack_p2_dense16 (rnn_rec_bf16.hip)
 //   GEMM operands               split8_rows (k_gemm_bf16x3); the three planes of k_gemm_bf16x6 are split3_planes (split3_host.hpp)
 #pragma once
 #include <cstddef>
@@ -194,7 +194,7 @@ static inline void pack_gru_us(const pv_rnn_dir* dirs, int K, int KP, std::vecto
 
 // ---- bf16 pieces of the bf16 MFMA (slots: pack_put_pieces) ---------------------------------------------------------------
 // k_rec_bf16. Fragment stream of one (direction, wave): slots [x-part k-steps x gates | h-part k-steps x gates]; a slot is 1 KB of
-// hi fragments followed by 1 KB of lo fragments (pieces = 3, LSTM only: x0 | x1 | x2 for the split-6 form); lane -> weight row
+// hi fragments followed by 1 KB of lo fragments (pieces = 3, LSTM only: x0 | x1 | x2, the split-6 form of the -DPV_REC_X6_MFMA32 build); lane -> weight row
 // gate * HID + 32 * wave + (lane & 31), 8 consecutive K values 16 * ks + 8 * (lane >> 5) + j (the B operand of
 // v_mfma_f32_32x32x16_bf16). cell = 4: LSTM, hidden 256, two x-part k-steps; cell = 3: GRU, hidden 128, and with kx > 0 (the
 // encoder) the x-part, one k-step, goes to a stream of its own, wx [dir][wave][gate] slots of 2 KB. kx = real input features
@@ -228,6 +228,33 @@ static inline void pack_rec_bf16(const pv_rnn_dir* dirs, int cell, int kx, int p
                 for (int g = 0; g < NG; g++) fill(base + (size_t)(slot++) * SL, false, ks, g);
             if (xres)
                 for (int g = 0; g < NG; g++) fill(wx.data() + ((size_t)(d * NW + w) * NG + g) * 1024, true, 0, g);
+        }
+}
+
+// Split-6 LSTM form of k_rec_bf16 on v_mfma_f32_16x16x32_bf16 (ring_x6_16). Fragment stream of one (direction, wave): slots
+// [x-part: gate, half | h-part: k-step of 32, gate, half], every slot three 1 KB pieces x0 | x1 | x2; lane -> weight row
+// gate * 256 + 32 * wave + 16 * half + (lane & 15), 8 consecutive K values 32 * ks + 8 * (lane >> 4) + j. kx > 0 (the encoder):
+// the x-part is ONE k-step (features beyond kx zero), 8 slots in front of the 64 of W_hh; kx = 0: no x-part. (A 16-column x 32-k
+// fragment is as many weights as a 32-column x 16-k one of pack_rec_bf16: the stream is the same 72 / 64 slots long.)
+static inline void pack_rec_x6_16(const pv_rnn_dir* dirs, int kx, std::vector<uint16_t>& wp) {
+    constexpr int HID = PV_PACK_LSTM_H, NW = HID / 32, KS_H = HID / 32, NG = 4;
+    const int nslot = (kx ? NG * 2 : 0) + KS_H * NG * 2;
+    constexpr size_t SL = 3 * 512;
+    wp.assign((size_t)2 * NW * nslot * SL, 0);
+    for (int d = 0; d < 2; d++)
+        for (int w = 0; w < NW; w++) {
+            uint16_t* dst = wp.data() + (size_t)(d * NW + w) * nslot * SL;
+            for (int ks = kx ? -1 : 0; ks < KS_H; ks++)   // -1: the x-part
+                for (int g = 0; g < NG; g++)
+                    for (int c = 0; c < 2; c++, dst += SL)
+                        for (int lane = 0; lane < 64; lane++)
+                            for (int j = 0; j < 8; j++) {
+                                const int n = g * HID + 32 * w + 16 * c + (lane & 15), k = 8 * (lane >> 4) + j;
+                                float v;
+                                if (ks < 0) v = k < kx ? dirs[d].w_ih[(size_t)n * kx + k] : 0.0f;
+                                else v = dirs[d].w_hh[(size_t)n * HID + 32 * ks + k];
+                                pack_put_pieces(dst, lane, j, v, 3);
+                            }
         }
 }
 

@@ -10,13 +10,18 @@
 // h lives in LDS as "split8" rows (per 8 units: 8 bf16 hi, 8 bf16 lo), double-buffered, one barrier per step; a 16-byte half
 // of a group is exactly one A fragment. W_hh (and the LSTM encoder's W_ih) are pre-split on the host into B-fragment order and
 // streamed from L2 through a ring of D register sets requested D - 1 (gate, k-step) slots ahead, wrapping into the next step.
-// (The fragment streams of every kernel here: pack_rec_bf16, pack_gru16_bf16, pack_tail_bf16, pack_p2_dense{,16}, rnn_pack_host.hpp.)
+// (The fragment streams of every kernel here: pack_rec_bf16, pack_rec_x6_16, pack_gru16_bf16, pack_tail_bf16, pack_p2_dense{,16}, rnn_pack_host.hpp.)
 // At 4 bytes per weight the stream is what bounds a step (1 MB per LSTM step and workgroup against 12 k MFMA cycles for 32
 // rows), hence MT = 2: 64 rows per weight fetch. The projections G arrive as quads [m / 4][column][4] whose four values are
 // the accumulator registers 4q .. 4q+3 of a lane: they are loaded straight INTO the accumulators at the end of the previous
 // step, so the MFMAs simply continue from them.
 // The split-6 form (X6, the LSTM layers of large PV_DTYPE_F32 calls) takes six terms of three-piece operands: its h rows are
-// [fp32 h | split8-style groups of the pieces x1, x2], split once by the lane that produces h (see k_rec_bf16).
+// [fp32 h | split8-style groups of the pieces x1, x2], split once by the lane that produces h (see k_rec_bf16). It alone runs
+// on v_mfma_f32_16x16x32_bf16, through a ring of its own (ring_x6_16; stream: pack_rec_x6_16): a wave still owns 32 units of
+// every gate and all 32 rows, as two 16-row tiles x two 16-unit halves per gate, slots of (k-step of 32, gate, half), twelve
+// 16-cycle MFMAs per slot instead of six of 32 cycles - the same operand traffic, registers for accumulators and state, LDS
+// layout and G quads. On this power-limited loop the chip holds a higher clock with that shape (1.82 against 1.67 GHz, DESIGN.md
+// 5b), which is the whole gain; -DPV_REC_X6_MFMA32 builds the 32x32x16 form of the same tree for the comparison.
 #include "rnn_bf16.hpp"
 #include "mfma_tiles.hpp"
 #include "rnn_math.hpp"
@@ -43,7 +48,16 @@ __device__ __forceinline__ void split3_rest(float h, __bf16& x1, __bf16& x2) {
 }
 __device__ __forceinline__ unsigned split8_off(unsigned k) { return (k >> 3) * 32u + (k & 7u) * 2u; }
 
+// The split-6 form runs on v_mfma_f32_16x16x32_bf16 (ring_x6_16, stream of pack_rec_x6_16). -DPV_REC_X6_MFMA32 is a diagnostic
+// build that keeps it on 32x32x16 (ring_bf16, pack_rec_bf16 with three pieces): the two builds differ in the MFMA shape alone.
+#ifdef PV_REC_X6_MFMA32
+constexpr bool REC_X6_16 = false;
+#else
+constexpr bool REC_X6_16 = true;
+#endif
+
 template <int NG, bool ENC, int MT = 1, bool X6 = false> struct RecCfg {
+    static constexpr bool M16 = X6 && REC_X6_16;                // 16x16x32 fragment maps (see k_rec_bf16)
     static constexpr int HID = NG == 4 ? 256 : 128;
     static constexpr int NW = HID / 32, NTHR = 64 * NW;
     static constexpr int KS_H = HID / 16;                       // k-steps (K = 16) of the recurrent product
@@ -65,7 +79,10 @@ template <int NG, bool ENC, int MT = 1, bool X6 = false> struct RecCfg {
     // split8: 4 bytes per unit. Split-6 form: 8 bytes per unit, [HID fp32 values | per 8 units: 8 bf16 x1, 8 bf16 x2]
     static constexpr int HS = HID * (X6 ? 8 : 4) + 16;
     static constexpr int H12 = X6 ? HID * 4 : 0;                // split-6 form: where a row's x1 | x2 groups start
-    static constexpr int XS = XK * 2 + 16;                      // LDS row stride of the bf16 x tile
+    // LDS row stride of the bf16 x tile. 16x16x32 map (row lane & 15, 16 bytes per lane >> 4): 96, the smallest stride whose
+    // ds_read_b128 lane groups ({0-3, 12-15, 20-27}, ...: rows 0-3 and 12-15 of one k-group, rows 4-11 of the next) fall on 64
+    // distinct banks; 80 is 2-way there
+    static constexpr int XS = M16 ? 96 : XK * 2 + 16;
     static_assert(NSLOT % D == 0, "ring depth must divide the stream length");
 };
 
@@ -153,13 +170,71 @@ __device__ __forceinline__ void ring_bf16(f32x16 (&acc)[MT][NA], const unsigned 
     }
 }
 
+// The split-6 form's own ring, on v_mfma_f32_16x16x32_bf16: slots [I0, I0 + 8 NKS) of a stream of NTOT slots, slot = (k-step of
+// 32, gate, column half c) = three 1 KB pieces x0 | x1 | x2 (pack_rec_x6_16), requested D - 1 slots ahead as in ring_bf16. A
+// fragments: lane -> row 16 mi + (lane & 15), k-group lane >> 4 (At = that lane's address in row tile 0, k-step 0); per k-step the
+// h-part lane reads 8 fp32 values and converts them once for x0, and reads x1 and x2 H12 bytes further in the row; the x-part
+// (XP: plain bf16 rows, exact operand) is one read. A slot feeds 2 row tiles x 6 terms (x-part: 3), the small terms first, in
+// ring_bf16's order per output element; the two row tiles alternate, so no MFMA waits for the one in front of it.
+template <int D, int NTOT, int I0, int NKS, bool XP, int H12, typename Hook>
+__device__ __forceinline__ void ring_x6_16(f32x4 (&acc)[2][4][2], const unsigned char* __restrict__ At, int m_stride,
+                                           __amdgpu_buffer_rsrc_t wr, f32x4 (&bq)[D][3], unsigned lane16, Hook&& hook) {
+    constexpr int KSB = XP ? 64 : 128;   // bytes of one k-step inside an A row
+    bf16x8 ap[XP ? 1 : 3][2];
+#pragma unroll
+    for (int i = 0; i < NKS * 8; i++) {
+        {
+            const int sv = (I0 + i + D - 1) % NTOT, rs = (I0 + i + D - 1) % D;
+#pragma unroll
+            for (int p = 0; p < 3; p++) bq[rs][p] = buf_load4(wr, lane16, (unsigned)(sv * 3072 + p * 1024));
+        }
+        const int ks = i / 8, g = (i / 2) % 4, c = i % 2;
+        if (i % 8 == 0) {
+#pragma unroll
+            for (int m = 0; m < 2; m++) {
+                if constexpr (!XP) {
+                    const f32x4 lo = *reinterpret_cast<const f32x4*>(At + m * m_stride + ks * KSB);
+                    const f32x4 hi = *reinterpret_cast<const f32x4*>(At + m * m_stride + ks * KSB + 16);
+                    ap[1][m] = *reinterpret_cast<const bf16x8*>(At + m * m_stride + ks * KSB + H12);
+                    ap[2][m] = *reinterpret_cast<const bf16x8*>(At + m * m_stride + ks * KSB + H12 + 16);
+#pragma unroll
+                    for (int j = 0; j < 8; j++) ap[0][m][j] = (__bf16)(j < 4 ? lo[j] : hi[j - 4]);
+                } else {
+                    ap[0][m] = *reinterpret_cast<const bf16x8*>(At + m * m_stride + ks * KSB);
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);   // keep hipcc from sinking the prefetches next to their uses
+        {
+            const int rs = (I0 + i) % D;
+            const bf16x8 b0 = __builtin_bit_cast(bf16x8, bq[rs][0]), b1 = __builtin_bit_cast(bf16x8, bq[rs][1]);
+            const bf16x8 b2 = __builtin_bit_cast(bf16x8, bq[rs][2]);
+#define PV_X6_TERM(AP, BP)          \
+    _Pragma("unroll") for (int m = 0; m < 2; m++) acc[m][g][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[AP][m], BP, acc[m][g][c], 0, 0, 0);
+            if constexpr (!XP) {
+                PV_X6_TERM(2, b0)
+                PV_X6_TERM(1, b1)
+            }
+            PV_X6_TERM(0, b2)
+            PV_X6_TERM(0, b0)
+            PV_X6_TERM(0, b1)
+            if constexpr (!XP) { PV_X6_TERM(1, b0) }
+#undef PV_X6_TERM
+        }
+        hook(i);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 #ifndef PV_REC_ABL
 #define PV_REC_ABL 0   // diagnostic ablations (timing only, results wrong): 1 = no global output stores, 2 = no LDS h writes,
                        // 3 = LSTM cell update without its transcendentals (h = sum of the four gate sums, c untouched)
 #endif
 #ifdef PV_REC_STAMPS
 // diagnostic build: cycle sums of the phases of a step (workgroup 0, every wave adds), read by pv_debug_rec_stamps
+// [5], [6]: s_memtime and s_memrealtime (100 MHz) ticks of the whole step loop, for the clock the kernel ran at (pv_debug_rec_clock)
 __device__ unsigned long long g_rec_stamps[8];
+#define RSTAMP_REAL(v) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory");
 #define RSTAMP(i) { unsigned long long now_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_) :: "memory"); st_acc[i] += now_ - st_last; st_last = now_; }
 #else
 #define RSTAMP(i)
@@ -176,6 +251,7 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
     static_assert(!X6 || NG == 4, "split-6 form: LSTM only");
     typedef RecCfg<NG, ENC, MT, X6> C;
     constexpr int NP = X6 ? 3 : 2, SB = NP * 1024;   // weight pieces, bytes of a stream slot
+    constexpr bool M16 = C::M16;
     constexpr int HID = C::HID, NW = C::NW, NTHR = C::NTHR, ROWS = 32 * MT, HS = C::HS, XS = C::XS, D = C::D, NA = C::NA;
     constexpr int NSLOT = C::NSLOT, NXS = C::XRES ? 0 : C::KS_X * NG;   // x slots at the head of the stream
     constexpr int NCOL = 2 * NG * HID;                                  // columns of a G row
@@ -189,7 +265,10 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
     const int tile = (blockIdx.x >> 3) * 4 + (xcd >> 1);
     if (tile >= a.n_tiles) return;
     const int64_t b0 = (int64_t)tile * ROWS;
-    const int unit = 32 * wv + (lane & 31), rg = lane >> 5;
+    // this lane's hidden unit and row group: 32x32x16 accumulators hold rows 8q + 4 rg + j of unit 32 wv + (lane & 31). M16:
+    // f32x4 accumulators [row tile mi][gate][column half c] hold rows 16 mi + 4 rg + j of unit 32 wv + 16 c + (lane & 15), `unit`
+    // being that of half 0. Either way the four gates of an element are in one lane and the cell update stays in registers.
+    const int unit = 32 * wv + (M16 ? (lane & 15) : (lane & 31)), rg = M16 ? lane >> 4 : lane >> 5;
     const int T = a.T;
     const __amdgpu_buffer_rsrc_t wr = make_rsrc(a.wp + (size_t)(dir * NW + wv) * NSLOT * SB);
     const unsigned lane16 = (unsigned)lane * 16u;
@@ -218,8 +297,14 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
         }
     }
     float bs[NA];   // ENC: gate biases of this lane's unit; GRU (both): index NG - 1 ... see below
+    float bs16[M16 && ENC ? 4 : 1][2];   // M16: of both column halves
     float b_hn = 0.0f;
-    if constexpr (ENC) {
+    if constexpr (M16 && ENC) {
+#pragma unroll
+        for (int g = 0; g < 4; g++)
+#pragma unroll
+            for (int c = 0; c < 2; c++) bs16[g][c] = a.bias[dir * NG * HID + g * HID + unit + 16 * c];
+    } else if constexpr (ENC) {
 #pragma unroll
         for (int g = 0; g < NG; g++) bs[g] = a.bias[dir * NG * HID + g * HID + unit];
     }
@@ -288,11 +373,25 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
     };
 
     // ---- accumulators -------------------------------------------------------------------------------------------------------
-    f32x16 acc[MT][NA];
+    f32x16 acc[M16 ? 1 : MT][M16 ? 1 : NA];
+    f32x4 acc16[M16 ? 2 : 1][4][2];   // M16: [row tile][gate][column half]
     f32x4 gn[(NG == 3 && !ENC) ? MT : 1][4];   // GRU decoder: the n gate's input projection, kept apart from W_hn h
-    const unsigned gl = (unsigned)((rg * NCOL + (lane & 31)) * 16);   // lane part of a G quad's byte offset
+    const unsigned gl = (unsigned)((rg * NCOL + (M16 ? (lane & 15) : (lane & 31))) * 16);   // lane part of a G quad's byte offset
     auto acc_init = [&](int t) {
-        if constexpr (ENC) {
+        if constexpr (M16) {
+            // ENC: the biases. Decoder: quad row (t * Bp + b0) / 4 + 4 mi + rg of the tile, column dir * 1024 + g * 256 + 32 wv + 16 c
+            // + (lane & 15) - one 16-byte load per accumulator, 16 per lane and step as in the 32x32x16 form, inside the tile's 8 quad rows
+            const __amdgpu_buffer_rsrc_t gsr = make_rsrc(ENC ? nullptr : a.G + ((size_t)t * a.Bp + b0) * NCOL);
+#pragma unroll
+            for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+                for (int g = 0; g < 4; g++)
+#pragma unroll
+                    for (int c = 0; c < 2; c++) {
+                        if constexpr (ENC) acc16[mi][g][c] = f32x4{bs16[g][c], bs16[g][c], bs16[g][c], bs16[g][c]};
+                        else acc16[mi][g][c] = buf_load4_nt(gsr, gl, (unsigned)((4 * mi * NCOL + dir * NG * HID + g * HID + 32 * wv + 16 * c) * 16));
+                    }
+        } else if constexpr (ENC) {
 #pragma unroll
             for (int m = 0; m < MT; m++) {
 #pragma unroll
@@ -334,8 +433,13 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
     acc_init(dir ? T - 1 : 0);
     __syncthreads();
 
-    const unsigned char* a_h = hbuf + (lane & 31) * HS + rg * 32;    // + cur * ROWS * HS
-    const unsigned char* a_x = xbuf + (lane & 31) * XS + rg * 16;    // + slot * ROWS * XS
+    // A fragments: row lane & 31 (M16: lane & 15 of a 16-row tile), k-group rg of a k-step. M16, h rows: HS / 4 = 516 = 4 mod 64
+    // puts 16 rows of ONE k-group on 16 x 4 distinct banks, but the lane groups of a ds_read_b128 ({0-3, 12-15, 20-27}, {4-11,
+    // 16-19, 28-31}, ...) take rows 0-3 and 12-15 from one k-group and rows 4-11 from the next, 32 bytes on: rows 4-5 and 12-13
+    // (10-11 and 2-3) then share banks, the read is 2-way (8 LDS cycles, not 4: 64 reads per wave and step, some 4 k of a
+    // 37 k-cycle step for the eight waves). No quad-preserving row map or k-group order removes it at this row stride.
+    const unsigned char* a_h = hbuf + (lane & (M16 ? 15 : 31)) * HS + rg * 32;    // + cur * ROWS * HS
+    const unsigned char* a_x = xbuf + (lane & (M16 ? 15 : 31)) * XS + rg * 16;    // + slot * ROWS * XS
     const unsigned rowb_tm = 2u * HID * 4u;                          // bytes of a time-major output row
     const unsigned rowb_bm = (unsigned)T * 2u * HID * 4u;            // bytes of a batch-major output row
     const unsigned o_f_l = (unsigned)(4 * rg) * rowb_bm + (unsigned)unit * 4u;
@@ -418,8 +522,10 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
     };
     int cur = 0;
 #ifdef PV_REC_STAMPS
-    unsigned long long st_acc[5] = {0, 0, 0, 0, 0}, st_last;
+    unsigned long long st_acc[5] = {0, 0, 0, 0, 0}, st_last, st_real0, st_real1;
+    RSTAMP_REAL(st_real0)
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last) :: "memory");
+    const unsigned long long st_first = st_last;
 #endif
     for (int s = 0; s < T; s++) {
         const int t = dir ? (T - 1 - s) : s;
@@ -457,6 +563,8 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
                     acc[m][ai] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ax[m], xw[g][0], acc[m][ai], 0, 0, 0);
                     acc[m][ai] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ax[m], xw[g][1], acc[m][ai], 0, 0, 0);
                 }
+        } else if constexpr (M16 && ENC) {
+            ring_x6_16<D, NSLOT, 0, 1, true, 0>(acc16, a_x + (s & 1) * ROWS * XS, 16 * XS, wr, bq, lane16, no_hook);
         } else if constexpr (ENC) {
             ring_bf16<NG, MT, NA, D, NSLOT, 0, C::KS_X, true, X6>(acc, a_x + (s & 1) * ROWS * XS, 32 * XS, wr, bq, lane16, no_hook);
         }
@@ -481,6 +589,8 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
                         if (m == MT - 1) copy_hook(ks * NG + g);
                     }
             }
+        } else if constexpr (M16) {
+            ring_x6_16<D, NSLOT, NXS, HID / 32, false, C::H12>(acc16, a_h + cur * ROWS * HS, 16 * HS, wr, bq, lane16, copy_hook);
         } else {
             ring_bf16<NG, MT, NA, D, NSLOT, NXS, C::KS_H, false, X6, C::H12>(acc, a_h + cur * ROWS * HS, 32 * HS, wr, bq, lane16, copy_hook);
         }
@@ -489,6 +599,12 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
         RSTAMP(1)
         // ---- cell update --------------------------------------------------------------------------------------------------------
         unsigned char* hn = hbuf + (cur ^ 1) * ROWS * HS;
+        // gate sum g of element e. M16: e = 8 mi + 4 c + j, row 16 mi + j (+ 4 rg), unit + 16 c: 64 bytes on in the fp32 part of an h
+        // row, in its x1 | x2 groups and in an output row; a wave's 4-byte LDS stores fall on 4 x 16 distinct banks
+        auto gsum = [&](int m, int g, int e) -> float {
+            if constexpr (M16) return acc16[e >> 3][g][(e >> 2) & 1][e & 3];
+            else return acc[m][g][e];
+        };
 #pragma unroll
         for (int m = 0; m < MT; m++)
 #pragma unroll
@@ -496,12 +612,12 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
                 float h;
                 if constexpr (NG == 4) {   // PyTorch LSTM gate order i, f, g, o
 #if PV_REC_ABL == 3
-                    h = ((acc[m][0][e] + acc[m][1][e]) + acc[m][2][e]) + acc[m][3][e];   // (every gate's product stays live)
+                    h = ((gsum(m, 0, e) + gsum(m, 1, e)) + gsum(m, 2, e)) + gsum(m, 3, e);   // (every gate's product stays live)
 #else
-                    const float ig = sigmoidf_(acc[m][0][e]);
-                    const float fg = sigmoidf_(acc[m][1][e]);
-                    const float gg = tanhf_(acc[m][2][e]);
-                    const float og = sigmoidf_(acc[m][3][e]);
+                    const float ig = sigmoidf_(gsum(m, 0, e));
+                    const float fg = sigmoidf_(gsum(m, 1, e));
+                    const float gg = tanhf_(gsum(m, 2, e));
+                    const float og = sigmoidf_(gsum(m, 3, e));
                     // (split-6 form: the contraction hipcc picks for the other forms, spelt out, so that it cannot depend on the
                     // code around it: the outputs of this chain are held bit for bit)
                     const float c = X6 ? __builtin_fmaf(fg, st[m][e], ig * gg) : fg * st[m][e] + ig * gg;
@@ -516,15 +632,16 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
                     h = (1.0f - z) * n + z * st[m][e];
                     st[m][e] = h;
                 }
-                const int row = 32 * m + 8 * (e >> 2) + (e & 3);   // + 4 * rg (lane part)
+                const int row = M16 ? 16 * (e >> 3) + (e & 3) : 32 * m + 8 * (e >> 2) + (e & 3);   // + 4 * rg (lane part)
+                const int cb = M16 ? 64 * ((e >> 2) & 1) : 0;                                      // M16: column half, in bytes
 #if PV_REC_ABL != 2
                 if constexpr (X6) {
-                    *reinterpret_cast<float*>(hn + row * HS + hl) = h;
+                    *reinterpret_cast<float*>(hn + row * HS + cb + hl) = h;
                     {
                         __bf16 p1, p2;
                         split3_rest(h, p1, p2);
-                        *reinterpret_cast<__bf16*>(hn + row * HS + hl12) = p1;
-                        *reinterpret_cast<__bf16*>(hn + row * HS + hl12 + 16) = p2;
+                        *reinterpret_cast<__bf16*>(hn + row * HS + cb + hl12) = p1;
+                        *reinterpret_cast<__bf16*>(hn + row * HS + cb + hl12 + 16) = p2;
                     }
                 } else {
                     const __bf16 hi = (__bf16)h;
@@ -537,7 +654,7 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
                 if (h == 123.456f)
 #endif
                 {
-                if (a.out_f32) buf_store1_nt(h, ofr, o_f_l, (unsigned)row * rowb_bm + (unsigned)((t * 2 + dir) * HID * 4));   // debug taps only
+                if (a.out_f32) buf_store1_nt(h, ofr, o_f_l, (unsigned)row * rowb_bm + (unsigned)((t * 2 + dir) * HID * 4 + cb));   // debug taps only
                 }
             }
         RSTAMP(2)
@@ -550,11 +667,17 @@ __global__ __launch_bounds__(NG == 4 ? 512 : 256, 1) void k_rec_bf16(RecArgs a) 
         lds_barrier();        // h_t (and x_{t+1}) complete; LDS only: the weight ring and the output stores stay in flight
         RSTAMP(4)
     }
+#ifdef PV_REC_STAMPS
+    RSTAMP_REAL(st_real1)   // (st_last: the s_memtime reading behind the last barrier)
+#endif
     tile_out(dir ? 0 : T - 1, hbuf + cur * ROWS * HS);
     if (dense) dense_out(dir ? 0 : T - 1, hbuf + cur * ROWS * HS);
 #ifdef PV_REC_STAMPS
-    if (blockIdx.x == 0 && lane == 0)
+    if (blockIdx.x == 0 && lane == 0) {
         for (int i = 0; i < 5; i++) atomicAdd(&g_rec_stamps[i], st_acc[i]);
+        atomicAdd(&g_rec_stamps[5], st_last - st_first);
+        atomicAdd(&g_rec_stamps[6], st_real1 - st_real0);
+    }
 #endif
     if (NG == 3 && a.h_out) {
 #pragma unroll
@@ -999,6 +1122,13 @@ int pv_pack_rec_bf16(const pv_rnn_dir* dirs, int cell, int kx, unsigned char** d
     return rc || wx.empty() ? rc : pv_dev_upload(wx, d_wx, owned);
 }
 
+int pv_pack_rec_x6(const pv_rnn_dir* dirs, int kx, unsigned char** d_wp, std::vector<void*>& owned) {
+    std::vector<uint16_t> wp, wx;
+    if (REC_X6_16) pack_rec_x6_16(dirs, kx, wp);
+    else pack_rec_bf16(dirs, 4, kx, 3, wp, wx);
+    return pv_dev_upload(wp, d_wp, owned);
+}
+
 int pv_pack_gru16_bf16(const pv_rnn_dir* dirs, int kx, unsigned char** d_wp, unsigned char** d_wx, std::vector<void*>& owned) {
     std::vector<uint16_t> wp, wx;
     pack_gru16_bf16(dirs, kx, wp, wx);
@@ -1262,6 +1392,13 @@ extern "C" int pv_debug_rec_stamps(unsigned long long* out5) {
     PV_HIP(hipDeviceSynchronize());
     PV_HIP(hipMemcpyFromSymbol(out5, HIP_SYMBOL(g_rec_stamps), 5 * sizeof(unsigned long long)));
     PV_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_rec_stamps), z, sizeof z));
+    return PV_OK;
+}
+// {s_memtime ticks, s_memrealtime ticks} of the step loops of workgroup 0 (all its waves added up) since the stamps were last
+// reset (by pv_debug_rec_stamps; read this first): their quotient x 100 MHz is the clock the kernels ran at
+extern "C" int pv_debug_rec_clock(unsigned long long* out2) {
+    PV_HIP(hipDeviceSynchronize());
+    PV_HIP(hipMemcpyFromSymbol(out2, HIP_SYMBOL(g_rec_stamps), 2 * sizeof(unsigned long long), 5 * sizeof(unsigned long long)));
     return PV_OK;
 }
 #endif

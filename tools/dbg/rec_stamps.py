@@ -1,20 +1,46 @@
-"""Diagnostic: phase cycle sums of k_rec_bf16 (needs the -DPV_REC_STAMPS variant: PEPPER_HIP_LIB=variants/libpepper_hip_recstamps.so)"""
-import sys, os, ctypes as C
+"""Diagnostic: phase cycle sums of k_rec_bf16 and the clock it ran at (needs a -DPV_REC_STAMPS variant, e.g.
+PEPPER_HIP_LIB=variants/libpepper_hip_recstamps.so; with -DPV_REC_X6_MFMA32 as well: the split-6 form on 32x32x16).
+
+  rec_stamps.py          the bf16x3 forms of P1 and P2
+  rec_stamps.py x6       the split-6 LSTM form (fp32 P1 at 8192 windows): phase sums, and the held clock = s_memtime ticks per
+                         s_memrealtime tick x 100 MHz around the step loops, after two seconds of back-to-back calls"""
+import sys, os, time, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
 from pepper_thesis_amd import runtime, synth, _ffi
 lib = _ffi.load()
 lib.pv_debug_rec_stamps.argtypes = [C.POINTER(C.c_ulonglong)]
+lib.pv_debug_rec_clock.argtypes = [C.POINTER(C.c_ulonglong)]
 def stamps():
     o = (C.c_ulonglong * 5)()
     lib.pv_debug_rec_stamps(o)
     return [int(v) for v in o]
+def clock_ghz():
+    """read BEFORE stamps(), which resets"""
+    o = (C.c_ulonglong * 2)()
+    lib.pv_debug_rec_clock(o)
+    return 0.1 * o[0] / max(int(o[1]), 1)
 names = ["x issue", "mfma", "cell", "init", "barrier"]
 def show(tag, nwaves, steps):
+    ghz = clock_ghz()
     v = stamps(); tot = sum(v)
-    print(tag, "cycles per step and wave:", {n: round(x / nwaves / steps) for n, x in zip(names, v)}, "total", round(tot / nwaves / steps), flush=True)
+    print(tag, "cycles per step and wave:", {n: round(x / nwaves / steps) for n, x in zip(names, v)}, "total", round(tot / nwaves / steps),
+          "clock %.3f GHz" % ghz, flush=True)
 dev = "cuda:0"
 ctx = runtime.Context(0)
+if sys.argv[1:] == ["x6"]:
+    B, CALLS = 8192, 20
+    ctx.load_p1(synth.make_weights_p1(5, 2.0), _ffi.PV_DTYPE_F32)
+    x = torch.from_numpy(synth.synth_windows(10, B)).to(dev); p = torch.zeros((B, 3), dtype=torch.float32, device=dev)
+    t0 = time.time()
+    while time.time() - t0 < 2.0:
+        for _ in range(16): ctx.forward_p1_dev(x.data_ptr(), B, p.data_ptr())
+        ctx.synchronize()
+    stamps()
+    for _ in range(CALLS): ctx.forward_p1_dev(x.data_ptr(), B, p.data_ptr())
+    ctx.synchronize()
+    show("P1 split-6 B=%d enc+dec (2 launches)" % B, 8, 66 * CALLS)
+    sys.exit(0)
 ctx.load_p1(synth.make_weights_p1(5, 2.0), _ffi.PV_DTYPE_BF16_INPUT_GEMM)
 for B in (2048, 8192):
     x = torch.from_numpy(synth.synth_windows(10, B)).to(dev); p = torch.zeros((B, 3), dtype=torch.float32, device=dev)
