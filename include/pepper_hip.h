@@ -368,6 +368,48 @@ int pv_polish_mask_low_depth(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n
                              int32_t n_regions, int seq_length, int min_depth, uint8_t* labels_out, uint8_t* row_qual_out,
                              int64_t* counts);
 
+/* The polisher's minimum quality: an edit whose quality is too low is taken back before the stitch, so that
+ * pv_polish_stitch[_qual] and pv_polish_edits on the rewritten labels keep the draft there (FASTA, FASTQ and edit records stay
+ * consistent, and those kernels are untouched). The reference has no counterpart. An edit is applied whole or not at all, so
+ * the unit is a RUN of adjacent edited columns, which is what the VCF composer joins into one record.
+ * chunks, labels, region_start, ref_off, ref, seq_length, seq_overlap: as for pv_polish_edits_dev; row_qual: uint8
+ * [n_chunks][seq_length] from pv_polish_row_qual, mandatory; chunks->depth is not read.
+ * Kept, owned and edit are the words of pv_polish_edits above: the owned edit columns of a region, in (position, index)
+ * order, are exactly the records pv_polish_edits_dev would emit for these labels.
+ *   RUN: a maximal stretch of a region's records in which consecutive records have equal or consecutive positions
+ *        (position[i+1] - position[i] <= 1). Runs never cross a region boundary: a VCF block that straddles two regions is
+ *        judged as two runs.
+ *   m = the minimum of row_qual over the run's columns. The run is PINNED if one of its index-0 records stands over a draft
+ *        byte whose upper-case form is not in "ACGT" (no label spells it, as for pv_polish_mask_low_depth).
+ *   m < min_qual and not pinned: the run is REVERTED: its index-0 columns get the label that spells the upper-cased draft
+ *        byte and quality 0, its insert columns label 0 and quality 0.
+ *   A pinned run is copied unchanged whatever m is, and so is every run with m >= min_qual.
+ * Every row that is not an owned edit column of a reverted run keeps its label and quality. That includes the non-owned
+ * duplicate of a reverted column in the neighbouring chunk: nothing reads it, since the stitch and the edits consult owners
+ * only and ownership does not depend on labels. Every surviving run has minimum >= min_qual, so every VCF record composed
+ * from the edits of labels_out has QUAL >= min_qual. pv_polish_edits on labels_out gives the records of labels minus those of
+ * the reverted runs; pv_polish_stitch[_qual] on labels_out gives the draft with exactly those records applied.
+ * labels_out == labels and row_qual_out == row_qual (in place) are allowed. min_qual == 0 is the identity; min_qual == 94
+ * reverts every run that is not pinned, because qualities stop at 93.
+ * d_counts = {rows reverted, status, first bad chunk (-1 if none), rows of pinned runs whose minimum was below min_qual}.
+ * Status, with the edits' precedence: PV_ERR_INVALID (chunk layout broken, or an owned column's position outside the
+ * region's draft: checked before the draft byte is read), PV_ERR_STATE (an owned column's label above 4). Under any status
+ * but PV_OK nothing but d_counts is written, in place or not. row_qual or row_qual_out == NULL, ref == NULL with n_chunks > 0,
+ * min_qual outside 0..94 and 2 * seq_overlap > seq_length are refused with PV_ERR_INVALID by the call itself, before anything
+ * is launched. Device-resident and asynchronous on `stream`; three launches (one workgroup per chunk, a one-block pass over
+ * the chunk summaries that carries a run through any number of chunks, one workgroup per chunk), no global atomics, no host
+ * synchronisation; capturable. */
+int pv_polish_filter_low_qual_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                                  const uint8_t* row_qual, const int64_t* region_start, const int64_t* ref_off, const uint8_t* ref,
+                                  int32_t n_regions, int seq_length, int seq_overlap, int min_qual, uint8_t* labels_out,
+                                  uint8_t* row_qual_out, int64_t* d_counts, void* stream);
+/* HOST buffers in and out; counts[4] as d_counts above; returns the status (on an error status from the device, labels_out and
+ * row_qual_out are left as they were). */
+int pv_polish_filter_low_qual(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                              const uint8_t* row_qual, const int64_t* region_start, const int64_t* ref_off, const uint8_t* ref,
+                              int32_t n_regions, int seq_length, int seq_overlap, int min_qual, uint8_t* labels_out,
+                              uint8_t* row_qual_out, int64_t* counts);
+
 /* The polisher's read realignment (AlignmentSummarizer.reads_to_reference_realignment, pepper/modules/python/
  * AlignmentSummarizer.py:159-177 -> ReadAligner::align_reads_to_reference, simple_aligner.cpp:66-107): every read of a region
  * is aligned to the draft with the reference's striped Smith-Waterman rules (match 4, mismatch 6, gap open 8, gap extend 2,

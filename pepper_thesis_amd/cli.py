@@ -175,6 +175,10 @@ def polish_parser(ap=None):
                     help="keep the draft wherever fewer than this many reads cover a column (0..65535; 0, the default, is off): "
                          "the network's label there is replaced by the draft base before the stitch, and regions without "
                          "reads are filled from the draft, so FASTA, FASTQ and edits agree (opt-in; one device)")
+    ap.add_argument("--min_qual", type=int, default=0,
+                    help="keep the draft wherever the network is not sure (0..94; 0, the default, is off): every run of adjacent "
+                         "edited columns whose lowest quality is below this Phred value is taken back whole before the stitch, "
+                         "so FASTA, FASTQ and edits agree and every VCF record has QUAL >= it (opt-in; one device)")
     return ap
 
 

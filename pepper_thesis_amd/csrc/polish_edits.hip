@@ -17,54 +17,6 @@ static_assert(sizeof(pv_polish_edit) == 16, "a record leaves as one 16-byte stor
 
 namespace {
 
-// what the edit kernels read beside the stitch's arguments
-struct EditRefs {
-    const int64_t* ref_off;
-    const uint8_t* ref;
-    const uint8_t* row_qual;   // may be null: qual 255
-};
-
-enum { COL_NONE = 0, COL_BAD_LABEL = -1, COL_BAD_POS = -2 };
-
-// > 0: an edit, packed as the record's last word (kind | draft << 8 | base << 16 | qual << 24); else a COL_ code.
-// span: the bytes of this region's draft. The draft byte is loaded for owned index-0 columns only, inside [0, span).
-__device__ inline int32_t column_edit(const StitchArgs& a, const EditRefs& r, const ChunkView& v, const uint8_t* draft, int64_t span,
-                                      int j) {
-    const int64_t t = v.base + j;
-    const int64_t p = a.pos[t];
-    const int32_t x = a.idx[t];
-    if (p < 0 || x < 0) return COL_NONE;
-    if (v.rs > 0 && p <= v.rs + ST_BUFFER) return COL_NONE;
-    const int ov = a.L - a.step;
-    if (v.prev && j < ov) {   // also column j + step of the previous chunk
-        const int64_t u = t - a.L + a.step;
-        if (a.pos[u] == p && a.idx[u] == x && !dec_str_gt(v.c, v.cprev)) return COL_NONE;
-    }
-    if (v.next && j >= a.step) {   // also column j - step of the next chunk
-        const int64_t u = t + a.L - a.step;
-        if (a.pos[u] == p && a.idx[u] == x && !dec_str_gt(v.c, v.cnext)) return COL_NONE;
-    }
-    const int64_t rel = p - v.rs;
-    if (rel < 0 || rel >= span) return COL_BAD_POS;
-    const uint32_t lb = a.lab[t];
-    if (lb > 4) return COL_BAD_LABEL;
-    uint32_t kind, d = 0, base = lb ? (uint32_t)"ACGT"[lb - 1] : 0;
-    if (x > 0) {
-        if (lb == 0) return COL_NONE;
-        kind = PV_EDIT_INS;
-    } else {
-        d = draft[rel];
-        const uint32_t u = d >= 'a' && d <= 'z' ? d - 32 : d;
-        if (lb == 0) kind = PV_EDIT_DEL;
-        else if (base != u) kind = PV_EDIT_SUB;
-        else return COL_NONE;
-    }
-    const uint32_t q = r.row_qual ? r.row_qual[t] : 255u;
-    return (int32_t)(kind | d << 8 | base << 16 | q << 24);   // q <= 255 and kind >= 1: bit 31 may be set, so test != codes
-}
-
-__device__ inline bool is_edit(int32_t e) { return e != COL_NONE && e != COL_BAD_LABEL && e != COL_BAD_POS; }
-
 // one block per chunk: edits the chunk contributes, and whether it breaks the layout (an owned position outside the region's
 // draft counts as that: BAD_ORDER -> PV_ERR_INVALID) or holds a poisoned label on an owned column
 __global__ __launch_bounds__(ST_THREADS) void k_edit_count(StitchArgs a, EditRefs r) {

@@ -9,7 +9,7 @@ prediction HDF5 files. Here each batch of regions goes through
 without leaving HBM; only the region offsets and the polished bases (one byte per base) come back to the host.
 
   python -m pepper_thesis_amd polish -b reads.bam -f draft.fa -m model.pkl -o out/polished [-t 5] [-r ctg:start-end] [--bf16]
-      [--realign] [--gpu_decode] [--qualities] [--edits] [--min_depth N]
+      [--realign] [--gpu_decode] [--qualities] [--edits] [--min_depth N] [--min_qual Q]
 
 --gpu_decode (opt-in) replaces the first stage: reader threads only plan blocks and fetch draft bytes, and the BAM is inflated,
 decoded and clipped on the device (gpu_decode.py; _decoded_pieces below). Same FASTA.
@@ -34,6 +34,13 @@ label. Stitch, qualities and edits then agree without knowing of it. A region wi
 it gets a piece of its own: the upper-cased draft of its kept range, quality 0, no edits; the FASTA then keeps the draft's
 coordinates wherever nothing was polished, and the edits VCF carries one ##pepper_min_depth=N line in place of the
 ##pepper_no_reads lines. Without the flag no output changes by a byte. The reference has no counterpart.
+
+--min_qual Q (opt-in, one device; 0 = off, 0..94) changes the draft only where the network is sure. The row qualities are
+computed whether or not --qualities is given, and behind the mask and before the stitch pv_polish_filter_low_qual_dev takes
+back, in place, every run of adjacent edited columns whose lowest quality is below Q: an edit is applied whole or not at all
+(the rule is in include/pepper_hip.h). A run over a draft byte other than ACGT cannot be spelled and stays. Stitch, qualities
+and edits then agree without knowing of it, every VCF record has QUAL >= Q, and the VCF carries one ##pepper_min_qual=Q line.
+Without the flag no output changes by a byte. The reference has no counterpart, and no Q is recommended.
 
 Semantics kept from the reference:
   * regions: ImageGenerationUI.py:257-273 - for pos in range(start, end, 1000): [max(start, pos-100), min(end, pos+1100)],
@@ -187,6 +194,9 @@ class ChainResult(NamedTuple):
     # --min_depth: (chunk rows that kept the draft, rows that could not: draft byte not ACGT). Not a tuple field, so the
     # record keeps its five planes for everything that unpacks it; with_masked() gives a result that carries the counts
     masked = None
+    # --min_qual: (chunk rows of edits taken back, rows of pinned runs below the threshold: draft byte not ACGT), carried the
+    # same way; with_filtered()
+    filtered = None
 
     def region(self, g: int) -> tuple:
         """region g's share: (bases, qual or None, edits or None)"""
@@ -196,13 +206,20 @@ class ChainResult(NamedTuple):
 
 
 class _MaskedChainResult(ChainResult):
-    """a ChainResult with an instance attribute `masked`"""
+    """a ChainResult with the instance attributes `masked` and `filtered`"""
 
 
 def with_masked(res: ChainResult, masked: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a minimum-depth chain in its attribute `masked`"""
     out = _MaskedChainResult(*res)
-    out.masked = (int(masked[0]), int(masked[1]))
+    out.masked, out.filtered = (int(masked[0]), int(masked[1])), res.filtered
+    return out
+
+
+def with_filtered(res: ChainResult, filtered: Tuple[int, int]) -> ChainResult:
+    """res, carrying the counts of a minimum-quality chain in its attribute `filtered`"""
+    out = _MaskedChainResult(*res)
+    out.masked, out.filtered = res.masked, (int(filtered[0]), int(filtered[1]))
     return out
 
 
@@ -254,14 +271,20 @@ class _DeviceChain:
     qualities: P2's accumulated softmax is kept, turned into row qualities and stitched beside the bases (the result's
     qual). edits: the edit pass runs behind the stitch, with the row qualities when there are any (the result's edit_off
     and edits). min_depth >= 1: the builder also fills the depth plane and, before the stitch, the labels (and row
-    qualities) of the rows below min_depth are rewritten in place to spell the draft (the result's masked)."""
+    qualities) of the rows below min_depth are rewritten in place to spell the draft (the result's masked). min_qual >= 1:
+    the row qualities are computed whether or not the chain was made for qualities and, behind the mask and before the
+    stitch, every run of adjacent edits whose lowest quality is below min_qual is taken back in place (the result's
+    filtered)."""
 
-    def __init__(self, ctx, own_ctx: bool = False, qualities: bool = False, edits: bool = False, min_depth: int = 0):
+    def __init__(self, ctx, own_ctx: bool = False, qualities: bool = False, edits: bool = False, min_depth: int = 0,
+                 min_qual: int = 0):
         import torch
         self.ctx, self.dev, self.own_ctx, self.qualities = ctx, "cuda:%d" % ctx.device_id, own_ctx, bool(qualities)
         self.edits = bool(edits)
         self.min_depth = int(min_depth)
         self.mask_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
+        self.min_qual = int(min_qual)
+        self.filter_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.edit_buf = None
         self.edit_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.dout = self.labels = self.seq = None
@@ -280,9 +303,10 @@ class _DeviceChain:
             self.dout = DevicePolishOut(chunks, device=self.dev, depth=self.min_depth > 0)
             self.labels = torch.zeros((chunks, 1000), dtype=torch.uint8, device=self.dev)
             self.seq = torch.zeros(chunks * 1000, dtype=torch.uint8, device=self.dev)
-            if self.qualities:
+            if self.qualities or self.min_qual > 0:
                 self.acc = torch.zeros((chunks, 1000, 5), dtype=torch.float32, device=self.dev)
                 self.row_qual = torch.zeros((chunks, 1000), dtype=torch.uint8, device=self.dev)
+            if self.qualities:
                 self.qual = torch.zeros(chunks * 1000, dtype=torch.uint8, device=self.dev)
             if self.edits:   # one record per chunk row: capacity cannot run short
                 self.edit_buf = torch.zeros((chunks * 1000, 16), dtype=torch.uint8, device=self.dev)
@@ -398,28 +422,36 @@ class _DeviceChain:
         return self._labels_and_stitch(db, n, dec.n_regions)
 
     def _labels_and_stitch(self, db, n: int, n_regions: int) -> ChainResult:
-        """P2 [-> row qualities] [-> minimum-depth mask] -> stitch [-> edits] over the first n chunks of self.dout on the
-        context's stream, one synchronize, then the read-back"""
+        """P2 [-> row qualities] [-> minimum-depth mask] [-> minimum-quality filter] -> stitch [-> edits] over the first n
+        chunks of self.dout on the context's stream, one synchronize, then the read-back"""
         import torch
         from .polish_edits import EDIT_DTYPE
         if n == 0:   # nothing to launch: every plane this chain was made for, empty
             zero = np.zeros(n_regions + 1, np.int64)
             res = ChainResult(zero, b"", b"" if self.qualities else None)
             res = res._replace(edit_off=zero.copy(), edits=np.zeros(0, EDIT_DTYPE)) if self.edits else res
-            return with_masked(res, (0, 0)) if self.min_depth > 0 else res
+            res = with_masked(res, (0, 0)) if self.min_depth > 0 else res
+            return with_filtered(res, (0, 0)) if self.min_qual > 0 else res
         d_acc, d_row_qual, d_qual = (t.data_ptr() for t in (self.acc, self.row_qual, self.qual)) if self.qualities else (0, 0, 0)
+        # --min_qual without --qualities: the row qualities are made for the filter alone; mask, stitch and edits run as without
+        d_filter_acc, d_filter_qual = (d_acc, d_row_qual) if self.qualities or self.min_qual <= 0 else (self.acc.data_ptr(),
+                                                                                                       self.row_qual.data_ptr())
         d_labels, d_ref_start = self.labels.data_ptr(), db.t["ref_start"].data_ptr()
         roff = torch.empty(n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
-        self.ctx.forward_p2_dev(self.dout.images.data_ptr(), n, d_labels, d_acc)
-        if self.qualities:
+        self.ctx.forward_p2_dev(self.dout.images.data_ptr(), n, d_labels, d_filter_acc)
+        if d_filter_qual:
             # (a label above 4 is reported by the stitch where it is on a kept column, as without qualities: the counts of
             # the row kernel are overwritten)
-            self.ctx.polish_row_qual_dev(d_labels, d_acc, n, d_row_qual, self.counts.data_ptr(), self.dout.seq_length,
+            self.ctx.polish_row_qual_dev(d_labels, d_filter_acc, n, d_filter_qual, self.counts.data_ptr(), self.dout.seq_length,
                                          self.dout.seq_overlap)
         if self.min_depth > 0:   # in place: what follows sees the draft's labels wherever the depth is below the minimum
             self.ctx.polish_mask_low_depth_dev(self.dout, n, d_labels, d_row_qual, d_ref_start, db.t["ref_off"].data_ptr(),
                                                db.t["ref"].data_ptr(), n_regions, self.min_depth, d_labels, d_row_qual,
                                                self.mask_counts.data_ptr())
+        if self.min_qual > 0:    # in place too: what follows sees the draft's labels over every run of edits below the minimum
+            self.ctx.polish_filter_low_qual_dev(self.dout, n, d_labels, d_filter_qual, d_ref_start, db.t["ref_off"].data_ptr(),
+                                                db.t["ref"].data_ptr(), n_regions, self.min_qual, d_labels, d_filter_qual,
+                                                self.filter_counts.data_ptr())
         self.ctx.polish_stitch_dev(self.dout, n, d_labels, d_ref_start, n_regions, roff.data_ptr(), self.seq.data_ptr(),
                                    self.seq.numel(), self.counts.data_ptr(), d_row_qual=d_row_qual, d_qual=d_qual)
         if self.edits:
@@ -434,35 +466,45 @@ class _DeviceChain:
             if status != _ffi.PV_OK:
                 raise _ffi.PepperHipError(status, "polisher minimum depth: device status %d (chunk %d)" % (status, bad))
             masked = (n_masked, n_unmaskable)
+        filtered = None
+        if self.min_qual > 0:
+            n_reverted, status, bad, n_pinned = (int(v) for v in self.filter_counts.tolist())
+            if status != _ffi.PV_OK:
+                raise _ffi.PepperHipError(status, "polisher minimum quality: device status %d (chunk %d)" % (status, bad))
+            filtered = (n_reverted, n_pinned)
+
+        def counted(res):
+            res = res if masked is None else with_masked(res, masked)
+            return res if filtered is None else with_filtered(res, filtered)
         total, status, bad = (int(v) for v in self.counts[:3].tolist())
         if status != _ffi.PV_OK:   # capacity cannot run short: seq holds a byte for every column
             raise _ffi.PepperHipError(status, "polisher stitch: device status %d (chunk %d)" % (status, bad))
         res = ChainResult(roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes(),
                           self.qual[:total].cpu().numpy().tobytes() if self.qualities else None)
         if not self.edits:
-            return res if masked is None else with_masked(res, masked)
+            return counted(res)
         total, status, bad = (int(v) for v in self.edit_counts[:3].tolist())
         if status != _ffi.PV_OK:   # capacity cannot run short: a record for every chunk row
             raise _ffi.PepperHipError(status, "polisher edits: device status %d (chunk %d)" % (status, bad))
         res = res._replace(edit_off=eoff.cpu().numpy(), edits=self.edit_buf[:total].cpu().numpy().view(EDIT_DTYPE).reshape(-1))
-        return res if masked is None else with_masked(res, masked)
+        return counted(res)
 
 
 def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int, qualities: bool = False,
-                      edits: bool = False, min_depth: int = 0) -> _DeviceChain:
+                      edits: bool = False, min_depth: int = 0, min_qual: int = 0) -> _DeviceChain:
     """a context on `device` with the polisher weights loaded, and the chain on it (closing the chain closes the context).
     shared_device: other ranks use this GPU too, so the option is set before the first device call (the split GRU forms need
     co-resident workgroups and would time out, poisoning the labels). False leaves the create-time default (PV_SHARED_DEVICE).
     This is the default `open_chain` of run and polish_rank.run; CPU tests pass a stub with the same signature, whose result
-    has run(batch, windows) -> ChainResult and close(). qualities, edits, min_depth (each passed only when set): the chain
-    of --qualities / --edits / --min_depth, whose results carry those planes."""
+    has run(batch, windows) -> ChainResult and close(). qualities, edits, min_depth, min_qual (each passed only when set):
+    the chain of --qualities / --edits / --min_depth / --min_qual, whose results carry those planes and counts."""
     from .runtime import Context
     ctx = Context(device)
     try:
         if shared_device:
             ctx.set_option("shared_device", 1)
         ctx.load_p2(state_dict, dtype)
-        return _DeviceChain(ctx, own_ctx=True, qualities=qualities, edits=edits, min_depth=min_depth)
+        return _DeviceChain(ctx, own_ctx=True, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual)
     except BaseException:
         ctx.close()
         raise
@@ -492,7 +534,7 @@ def _read_ahead(ex, fn, items, depth):
 def _timers(timers: Optional[dict], more=()) -> dict:
     """the caller's timer dict (or a fresh one) with the keys of polish_pieces, and `more`, present"""
     T = timers if timers is not None else {}
-    for k in ("read_s", "device_s", "regions", "batches", "masked_rows", "unmaskable_rows") + tuple(more):
+    for k in ("read_s", "device_s", "regions", "batches", "masked_rows", "unmaskable_rows", "reverted_rows", "pinned_rows") + tuple(more):
         T.setdefault(k, 0)
     return T
 
@@ -511,10 +553,13 @@ def _thread_handles(bam: str, fasta: str):
 
 
 def _count_masked(T: dict, res) -> None:
-    """a minimum-depth chain's row counts of one launch into the timers"""
+    """a minimum-depth chain's and a minimum-quality chain's row counts of one launch into the timers"""
     if getattr(res, "masked", None) is not None:
         T["masked_rows"] += res.masked[0]
         T["unmaskable_rows"] += res.masked[1]
+    if getattr(res, "filtered", None) is not None:
+        T["reverted_rows"] += res.filtered[0]
+        T["pinned_rows"] += res.filtered[1]
 
 
 def kept_range(w: Work) -> Tuple[int, int]:
@@ -546,7 +591,7 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
     chain.run(batch, windows) -> ChainResult (_DeviceChain or a CPU test's stub); a piece carries the planes that result
     carried (qual with a chain made for --qualities, edits with one made for --edits, else None).
     timers (optional) accumulates read_s, device_s, regions, batches, and masked_rows / unmaskable_rows of the results that
-    carry the counts of a minimum-depth chain.
+    carry the counts of a minimum-depth chain, reverted_rows / pinned_rows of those of a minimum-quality chain.
     gpu_decode: the device read path (_decoded_pieces): the reader threads only plan, the BAM is inflated, decoded and clipped
     on chain.ctx's device, and the chain takes the batches where they are (chain.run_decoded). open_decoder(T): the decoder,
     by default a gpu_decode.GpuDecoder with the polisher's settings (CPU tests pass a stub with its scan_groups, realize,
@@ -654,7 +699,7 @@ def decode_report(T: dict) -> str:
 def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region: Optional[str] = None, batch_size: int = 2048,
                  threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None,
                  realign: bool = False, chain=None, gpu_decode: bool = False, qualities: bool = False, edits: bool = False,
-                 min_depth: int = 0) -> str:
+                 min_depth: int = 0, min_qual: int = 0) -> str:
     """-> path of the polished FASTA. batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
     realign: realign every read to the draft on the device before the builder, as the reference always does.
     chain: a chain with the weights already loaded (open_device_chain; the caller closes it), else one is made on `ctx`
@@ -665,18 +710,21 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
     The two flags make this function's own chain and pick the files; a chain passed in whose results lack a plane they
     need is refused (ValueError) before any file is written.
     min_depth >= 1: this function's own chain masks the rows below it (a chain passed in must have been made for it), the
-    regions without reads are filled from the draft (draft_pieces), and the VCF names the threshold."""
+    regions without reads are filled from the draft (draft_pieces), and the VCF names the threshold.
+    min_qual >= 1: this function's own chain takes back the runs of edits below it (a chain passed in must have been made
+    for it), and the VCF names the threshold."""
     from .bamio import BamHandler, FastaHandler
     from .runtime import Context
     t_start = time.perf_counter()
-    T = dict(read_s=0.0, device_s=0.0, regions=0, batches=0, bases_in=0, bases_out=0, masked_rows=0, unmaskable_rows=0, draft_regions=0)
+    T = dict(read_s=0.0, device_s=0.0, regions=0, batches=0, bases_in=0, bases_out=0, masked_rows=0, unmaskable_rows=0, draft_regions=0,
+             reverted_rows=0, pinned_rows=0)
     own = None
     if chain is None:
         state_dict = load_polish_model(model_path)
         if ctx is None:
             ctx = own = Context(0)
         ctx.load_p2(state_dict, dtype)
-        chain = _DeviceChain(ctx, qualities=qualities, edits=edits, min_depth=min_depth)
+        chain = _DeviceChain(ctx, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual)
     try:
         fa, bm = FastaHandler(fasta), BamHandler(bam)
         work, T["bases_in"] = polish_work(fa, bm, region)
@@ -685,6 +733,9 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
         if min_depth >= 1 and getattr(chain, "min_depth", None) != min_depth:
             raise ValueError("polish_fused: the chain masks below depth %r, not %d: it was not made for this run"
                              % (getattr(chain, "min_depth", None), min_depth))
+        if min_qual >= 1 and getattr(chain, "min_qual", None) != min_qual:
+            raise ValueError("polish_fused: the chain filters below quality %r, not %d: it was not made for this run"
+                             % (getattr(chain, "min_qual", None), min_qual))
         pieces = list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode))
         for want, plane in ((qualities, "qual"), (edits, "edits")):
             if want and pieces and getattr(pieces[0], plane) is None:
@@ -693,7 +744,7 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
             filled = draft_pieces(fa, work, pieces, qualities, edits)
             T["draft_regions"] = len(filled)
             pieces += filled
-        vcf = _edits_vcf(fa, fasta, work, pieces, qualities, min_depth) if edits else None
+        vcf = _edits_vcf(fa, fasta, work, pieces, qualities, min_depth, min_qual) if edits else None
     finally:
         if own is not None:
             own.close()
@@ -711,9 +762,9 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
     return out_path
 
 
-def _edits_vcf(fa, fasta_path: str, work: List[Work], pieces, qualities: bool, min_depth: int = 0) -> tuple:
+def _edits_vcf(fa, fasta_path: str, work: List[Work], pieces, qualities: bool, min_depth: int = 0, min_qual: int = 0) -> tuple:
     """the pieces' edit records -> write_edits_vcf's arguments behind the path: (source, reference, contigs of the run with
-    their lengths, read-free runs, VCF records per contig, min_depth). Pieces of a contig are joined in region-start order,
+    their lengths, read-free runs, VCF records per contig, min_depth, min_qual). Pieces of a contig are joined in region-start order,
     as merge_pieces joins the bases. A region without a piece gave no chunks: the FASTA omits its kept range
     (kept_range) and a pepper_no_reads header line names it. With min_depth >= 1 every region has a piece (draft_pieces)."""
     from . import polish_edits
@@ -731,7 +782,7 @@ def _edits_vcf(fa, fasta_path: str, work: List[Work], pieces, qualities: bool, m
             recs = np.concatenate([e for _, _, e in sorted(by[c], key=lambda t: (t[0], t[1]))])
             draft = fa.get_reference_sequence(c, 0, length).encode() if len(recs) else b""
             records[c] = polish_edits.compose_records(c, recs, draft, qualities, warn=log)
-    return "pepper_thesis_amd polish", os.path.abspath(fasta_path), contigs, no_reads, records, int(min_depth)
+    return "pepper_thesis_amd polish", os.path.abspath(fasta_path), contigs, no_reads, records, int(min_depth), int(min_qual)
 
 
 def run(args, open_chain=open_device_chain) -> int:
@@ -765,6 +816,15 @@ def run(args, open_chain=open_device_chain) -> int:
         sys.stderr.write("ERROR: polish --min_depth runs on one device (-d_ids %s lists %d): the depth plane is not carried "
                          "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
         return 2
+    min_qual = int(getattr(args, "min_qual", 0) or 0)
+    if not 0 <= min_qual <= 94:
+        sys.stderr.write("ERROR: polish --min_qual %d: the minimum quality is a Phred value from 0 (off) to 94 (qualities stop at "
+                         "93, so 94 takes back every edit).\n" % min_qual)
+        return 2
+    if min_qual and len(plan) > 1:
+        sys.stderr.write("ERROR: polish --min_qual runs on one device (-d_ids %s lists %d): the row qualities are not carried "
+                         "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
+        return 2
     for what, path in (("BAM", args.bam), ("FASTA", args.fasta), ("MODEL", args.model_path)):
         if not os.path.isfile(path):
             sys.stderr.write("ERROR: CAN NOT LOCATE %s FILE.\n" % what)
@@ -785,13 +845,15 @@ def run(args, open_chain=open_device_chain) -> int:
         kw["edits"] = True
     if min_depth:
         kw["min_depth"] = min_depth
+    if min_qual:
+        kw["min_qual"] = min_qual
     chain = open_chain(device, False, state_dict, dtype, **kw)
     try:
         T = {}
         path = polish_fused(args.bam, args.fasta, args.model_path, args.output_file, args.region, args.batch_size, args.threads,
                             timers=T, realign=bool(getattr(args, "realign", False)), chain=chain,
                             gpu_decode=bool(getattr(args, "gpu_decode", False)), qualities=qualities, edits=edits,
-                            min_depth=min_depth)
+                            min_depth=min_depth, min_qual=min_qual)
     except ValueError as e:
         if not edits:
             raise
@@ -805,6 +867,9 @@ def run(args, open_chain=open_device_chain) -> int:
     if min_depth:
         log("MIN DEPTH %d: %d CHUNK ROWS KEPT THE DRAFT, %d COULD NOT (DRAFT BYTE NOT ACGT), %d REGIONS WITHOUT READS FILLED FROM THE DRAFT"
             % (min_depth, T["masked_rows"], T["unmaskable_rows"], T["draft_regions"]))
+    if min_qual:
+        log("MIN QUAL %d: %d CHUNK ROWS OF EDITS TAKEN BACK, %d ROWS OF LOW RUNS KEPT (DRAFT BYTE NOT ACGT)"
+            % (min_qual, T["reverted_rows"], T["pinned_rows"]))
     if qualities:
         log("POLISHED FASTQ: " + output_fastq_path(path))
     if edits:

@@ -37,8 +37,13 @@
               with the builder, the mask and the stitch calls bracketed by HIP events, and the rows the mask rewrote. The parent
               commit's plain figure (profiles/polish_e2e_bench.json) is recorded beside them as the yardstick.
 
+  --min_qual Q: the same comparison for `polish --min_qual Q`: wall times of both forms, twice each, then one more run each way
+              (with --edits, so that the edit call stands beside it) with the row-quality, filter, stitch and edit calls bracketed
+              by HIP events, and the rows the filter took back. The weights are random: nearly every column is an edit and
+              whole regions are single runs, so the reverted fraction and the host time say nothing about a trained model.
+
   python tools/bench_polish_e2e.py [--leg stitch|e2e|steps|all] [--mbp 2.0] [--reps 20] [--realign] [--d_ids 0,0] [--gpu_decode]
-                                   [--qualities] [--edits] [--min_depth N] [--out f]
+                                   [--qualities] [--edits] [--min_depth N] [--min_qual Q] [--out f]
 For the rocprofv3 row run the stitch leg alone under `rocprofv3 --kernel-trace --stats -d <dir> -- python ... --leg stitch`.
 """
 import argparse
@@ -126,11 +131,14 @@ def stitch_leg(reps=20):
                                      "stitch_ms": round(t_host * 1e3, 1)}}
 
 
-def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False, qualities=False, edits=False, min_depth=0):
+def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False, qualities=False, edits=False, min_depth=0,
+             min_qual=0):
     # warm-up on a small region (code objects, allocator), then the timed run
     kw = {"gpu_decode": True} if gpu_decode else {}
     if min_depth:
         kw["min_depth"] = min_depth
+    if min_qual:
+        kw["min_qual"] = min_qual
     if qualities:
         kw["qualities"] = True
     if edits:
@@ -148,6 +156,8 @@ def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decod
     if min_depth:
         res.update(min_depth=min_depth, masked_rows=T["masked_rows"], unmaskable_rows=T["unmaskable_rows"],
                    draft_regions=T["draft_regions"])
+    if min_qual:
+        res.update(min_qual=min_qual, reverted_rows=T["reverted_rows"], pinned_rows=T["pinned_rows"])
     if qualities:
         fq = polish.output_fastq_path(path)
         res["qualities"], res["fastq_bytes"] = True, os.path.getsize(fq)
@@ -224,15 +234,16 @@ def realign_stats(ctx, bam, fa, per_launch=1024):
             "band_gcups": round(band / (band_ms * 1e-3) / 1e9, 1) if band_ms else None}
 
 
-def _quality_events(polish, ctx, bam, fa, model, out, threads, qualities, edits=False, min_depth=0):
+def _quality_events(polish, ctx, bam, fa, model, out, threads, qualities, edits=False, min_depth=0, min_qual=0):
     """one more run with the calls whose profile names start with polish_ bracketed by HIP events -> {name: [ms, launches]}"""
     ctx.profile_begin("polish_")
     try:
-        polish.polish_fused(bam, fa, model, out, threads=threads, ctx=ctx, qualities=qualities, edits=edits, min_depth=min_depth)
+        kw = {"min_qual": min_qual} if min_qual else {}
+        polish.polish_fused(bam, fa, model, out, threads=threads, ctx=ctx, qualities=qualities, edits=edits, min_depth=min_depth, **kw)
     finally:
         pr = ctx.profile_end()
     return {k: [round(v[0], 4), v[1]] for k, v in sorted(pr.items())
-            if k in ("polish_stitch", "polish_row_qual", "polish_edits", "polish_mask", "polish_pipeline")}
+            if k in ("polish_stitch", "polish_row_qual", "polish_edits", "polish_mask", "polish_filter", "polish_pipeline")}
 
 
 def min_depth_leg(mbp=3.0, threads=16, min_depth=3):
@@ -274,6 +285,54 @@ def min_depth_leg(mbp=3.0, threads=16, min_depth=3):
                            "polish_mask: count + finish + write kernels of one mask call; polish_stitch: count + scan + write; HIP "
                            "events around every call of a run, summed over the run's launches. The weights are random, so the FASTA "
                            "of the plain run is not the draft and the two FASTA files differ wherever a row was masked")
+            return res
+        finally:
+            ctx.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def min_qual_leg(mbp=3.0, threads=16, min_qual=20):
+    """polish without and with --min_qual on one synthetic contig, in one process on the same files"""
+    import hashlib
+    import numpy as np
+    from bench_filepath import make_files
+    from pepper_thesis_amd import polish, runtime, synth
+    d = tempfile.mkdtemp(prefix="pv_polish_min_qual_")
+    try:
+        bam, fa, info = make_files(d, int(mbp * 1_000_000))
+        model = os.path.join(d, "model.npz")
+        np.savez(model, **synth.make_weights_p2(4321, 3.0))
+        ctx = runtime.Context(0)
+        try:
+            # the two forms alternate, twice each: the first timed run of a process also grows the workspace to the launch size
+            runs = []
+            for k in range(2):
+                for q in (0, min_qual):
+                    r = _e2e_run(polish, ctx, bam, fa, model, os.path.join(d, "filtered" if q else "plain"), threads, False, info,
+                                 min_qual=q)
+                    runs.append(dict(r, min_qual=q, order=len(runs)))
+            res = {"runs": runs, "without_min_qual": runs[2], "with_min_qual": runs[3]}
+            sha = [hashlib.sha256(open(os.path.join(d, n, "_pepper_polished.fa"), "rb").read()).hexdigest() for n in ("plain", "filtered")]
+            res["fasta_identical"], res["plain_fasta_sha256"] = sha[0] == sha[1], sha[0]
+            res["event_ms_launches"] = {
+                "without_min_qual": _quality_events(polish, ctx, bam, fa, model, os.path.join(d, "plain_ev"), threads, False, True),
+                "with_min_qual": _quality_events(polish, ctx, bam, fa, model, os.path.join(d, "filtered_ev"), threads, False, True,
+                                                 min_qual=min_qual),
+                # every run that is not pinned goes: the write pass stores every edit row
+                "with_min_qual_94": _quality_events(polish, ctx, bam, fa, model, os.path.join(d, "all_ev"), threads, False, True,
+                                                    min_qual=94)}
+            try:
+                with open(os.path.join(ROOT, "profiles", "polish_e2e_bench.json")) as fh:
+                    res["parent_plain_wall_s"] = json.load(fh)["e2e"]["wall_s"]
+            except (OSError, KeyError, ValueError):
+                res["parent_plain_wall_s"] = None
+            res["note"] = ("polish_filter: runs + carry + write kernels of one filter call; polish_row_qual: the row kernel and its "
+                           "status kernel (with the flag they run also without --qualities); polish_stitch / polish_edits: count + "
+                           "scan + write; HIP events around every call of a run with --edits, summed over the run's launches. The "
+                           "weights are random: nearly every column is an edit, whole regions are single runs and no quality "
+                           "reaches the threshold, so the reverted rows and the host time are not those of a trained model, and "
+                           "the two FASTA files differ wherever a run was taken back")
             return res
         finally:
             ctx.close()
@@ -481,13 +540,17 @@ def main():
                     help="e2e leg without and with polish --edits, plus HIP-event times of the stitch and the edit calls")
     ap.add_argument("--min_depth", type=int, default=0,
                     help="e2e leg without and with polish --min_depth N, plus HIP-event times of the builder, mask and stitch calls")
+    ap.add_argument("--min_qual", type=int, default=0,
+                    help="e2e leg without and with polish --min_qual Q, plus HIP-event times of the row-quality, filter, stitch and edit calls")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON to this file")
     a = ap.parse_args()
     out = {}
     if a.leg in ("stitch", "all"):
         out["stitch"] = stitch_leg(a.reps)
     if a.leg in ("e2e", "all"):
-        if a.min_depth:
+        if a.min_qual:
+            out["e2e"] = min_qual_leg(a.mbp, a.threads, a.min_qual)
+        elif a.min_depth:
             out["e2e"] = min_depth_leg(a.mbp, a.threads, a.min_depth)
         elif a.edits:
             out["e2e"] = edits_leg(a.mbp, a.threads)
