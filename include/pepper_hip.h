@@ -449,6 +449,57 @@ int pv_polish_realign(pv_ctx* ctx, const pv_batch_in* in, const int64_t* win_off
 int pv_polish_realign_dev(pv_ctx* ctx, const pv_batch_in* in, int64_t n_reads, int64_t n_bases, int64_t max_query_len,
                           const int64_t* win_off, const uint8_t* win, pv_realign_out* out, int64_t* d_counts, void* stream);
 
+/* ---- selection of a flat batch by haplotype (`polish -hp`) -----------------------------------------------------------
+ * `polish -hp` polishes once per haplotype, each pass on the reads of that haplotype. The builder and the realigner take a
+ * batch whose offset arrays are contiguous, so a read cannot be left out in place: the batch is compacted on the device.
+ * For a haplotype h >= 1 and one int per read, `read_hp` (the HP aux tag, 0 when absent; NULL = all 0):
+ *   read r is KEPT iff read_hp == NULL, read_hp[r] == 0 (untagged: counts for every haplotype, as in pv_summarize_regions_hp)
+ *   or read_hp[r] == h; any other value (the other haplotype, 3 and above, negative values) drops it.
+ * The output is the input batch with the dropped reads removed and nothing else changed: kept reads stay in input order
+ * inside their region; read_pos, read_flags, read_mapq, read_hp and each read's bytes of bases and quals and words of cigar
+ * are the input's; read_off, base_off and cigar_off are rebuilt from 0 so that the arrays are contiguous again. The region
+ * arrays (ref_start, ref_end, cand_*, ref_off, ref) are not copied: a pv_batch_in of the output points at the input's. A
+ * region may end with no reads (read_off[g+1] == read_off[g] is a legal batch). If every read is kept, every output array
+ * equals its input byte for byte (base_off[0] = cigar_off[0] = 0 given).
+ * Every array of the output is caller-owned. quals is copied only where in->quals is given. */
+typedef struct pv_select_out {
+    int64_t read_capacity;  /* in: reads the per-read arrays can hold (base_off and cigar_off: one entry more) */
+    int64_t base_capacity;  /* in: bytes bases (and quals) can hold */
+    int64_t cigar_capacity; /* in: words cigar can hold */
+    int64_t* read_off;      /* [n_regions+1] */
+    int64_t* read_pos;      /* [read_capacity] */
+    uint8_t* read_flags;    /* [read_capacity] */
+    uint8_t* read_mapq;     /* [read_capacity] */
+    int64_t* base_off;      /* [read_capacity+1] */
+    uint8_t* bases;         /* [base_capacity] */
+    uint8_t* quals;         /* [base_capacity] */
+    int64_t* cigar_off;     /* [read_capacity+1] */
+    uint32_t* cigar;        /* [cigar_capacity] */
+    int32_t* read_hp;       /* optional (may be NULL) [read_capacity]: the kept reads' tags (0 where read_hp is NULL) */
+    int64_t* src_read;      /* optional (may be NULL) [read_capacity]: the input index of every kept read */
+    int64_t n_reads;        /* out (host form): reads kept, or needed on PV_ERR_CAPACITY */
+    int64_t n_bases;        /* out (host form): bases kept, or needed */
+    int64_t n_cigar;        /* out (host form): cigar words kept, or needed */
+} pv_select_out;
+
+/* Device-resident, asynchronous form: every array is a DEVICE pointer (read_hp may be NULL); n_reads, n_bases and n_cigar are
+ * the lengths of the input's arrays. d_counts = {reads kept, bases kept, cigar words kept, status}. Status:
+ *   PV_OK;
+ *   PV_ERR_CAPACITY: a capacity is short; the three counts hold what is needed, read_off and the per-read records and offsets
+ *     of the reads that fit are written, no payload (bases, quals, cigar) is written;
+ *   PV_ERR_INVALID, found on the device before any payload byte is read: base_off or cigar_off decreasing or starting below
+ *     0, base_off[n_reads] > n_bases or cigar_off[n_reads] > n_cigar, read_off decreasing, read_off[0] != 0 or
+ *     read_off[n_regions] != n_reads; the counts are 0 and no output array is written.
+ * haplotype < 1 and null required pointers are refused by the call itself. Whatever the offsets hold, nothing is read outside
+ * the input arrays and nothing is written outside [0, kept total) of each output array (kept + 1 entries of base_off and
+ * cigar_off). Two chunked scans over the reads (4096 per workgroup), one launch for the regions and a payload gather split
+ * by 16 KB pieces of the output; no global atomics, no host synchronisation; workspace for n_reads indices. */
+int pv_batch_select_hp_dev(pv_ctx* ctx, const pv_batch_in* in, const int32_t* read_hp, int64_t n_reads, int64_t n_bases,
+                           int64_t n_cigar, int haplotype, pv_select_out* out, int64_t* d_counts, void* stream);
+/* HOST buffers in and out; the totals come from the offset arrays, which are checked on the host first. Returns the status;
+ * out->n_reads, n_bases and n_cigar hold the counts (on PV_ERR_CAPACITY what is needed; read_off is filled then too). */
+int pv_batch_select_hp(pv_ctx* ctx, const pv_batch_in* in, const int32_t* read_hp, int haplotype, pv_select_out* out);
+
 /* ---- BGZF block inflate (the BAM readers' opt-in GPU mode) ---------------------------------------------------------
  * A batch of BGZF blocks, one wavefront each: the raw-DEFLATE payloads (RFC 1951: stored, fixed and dynamic Huffman
  * blocks, any BFINAL chain) concatenated in `payload`; per block the payload offset in_off, its length clen, the gzip

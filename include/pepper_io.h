@@ -163,6 +163,11 @@ int pvio_write_bam(const char* path, int n_ref, const char* const* ref_names, co
                    const int32_t* read_tid, const int64_t* read_pos, const uint8_t* read_flags, const uint8_t* read_mapq,
                    const int64_t* base_off, const uint8_t* bases, const uint8_t* quals, const int64_t* cigar_off,
                    const uint32_t* cigar, int level);
+/* the same with one int per read (read_hp, may be NULL): a value 1 .. 255 is written as the read's HP:C aux tag */
+int pvio_write_bam_hp(const char* path, int n_ref, const char* const* ref_names, const int64_t* ref_lens, int64_t n_reads,
+                      const int32_t* read_tid, const int64_t* read_pos, const uint8_t* read_flags, const uint8_t* read_mapq,
+                      const int64_t* base_off, const uint8_t* bases, const uint8_t* quals, const int64_t* cigar_off,
+                      const uint32_t* cigar, const int32_t* read_hp, int level);
 /* bgzip `text` (a whole VCF: '#' header lines, then records sorted by contig and position) to `path` and write the tabix
  * index `path`.tbi — what pysam.VariantFile(*.vcf.gz, 'w') + pysam.tabix_index produce (VcfWriter.py:21-46) */
 int pvio_write_vcf_gz(const char* path, const char* text, int64_t n_bytes);

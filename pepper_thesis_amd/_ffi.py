@@ -181,6 +181,28 @@ class pv_realign_out(C.Structure):
     ]
 
 
+class pv_select_out(C.Structure):
+    _fields_ = [
+        ("read_capacity", C.c_int64),
+        ("base_capacity", C.c_int64),
+        ("cigar_capacity", C.c_int64),
+        ("read_off", C.c_void_p),
+        ("read_pos", C.c_void_p),
+        ("read_flags", C.c_void_p),
+        ("read_mapq", C.c_void_p),
+        ("base_off", C.c_void_p),
+        ("bases", C.c_void_p),
+        ("quals", C.c_void_p),
+        ("cigar_off", C.c_void_p),
+        ("cigar", C.c_void_p),
+        ("read_hp", C.c_void_p),
+        ("src_read", C.c_void_p),
+        ("n_reads", C.c_int64),
+        ("n_bases", C.c_int64),
+        ("n_cigar", C.c_int64),
+    ]
+
+
 class pv_rnn_dir(C.Structure):
     _fields_ = [("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p)]
 
@@ -266,6 +288,10 @@ SYMBOLS = [
     ("pv_polish_realign_dev", C.c_int,
      [C.c_void_p, C.POINTER(pv_batch_in), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(pv_realign_out),
       C.c_void_p, C.c_void_p]),
+    ("pv_batch_select_hp_dev", C.c_int,
+     [C.c_void_p, C.POINTER(pv_batch_in), C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(pv_select_out),
+      C.c_void_p, C.c_void_p]),
+    ("pv_batch_select_hp", C.c_int, [C.c_void_p, C.POINTER(pv_batch_in), C.c_void_p, C.c_int, C.POINTER(pv_select_out)]),
     ("pv_bgzf_inflate_dev", C.c_int,
      [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
       C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),

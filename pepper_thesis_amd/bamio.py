@@ -80,6 +80,9 @@ IO_SYMBOLS = [
     ("pvio_reservoir_indices", C.c_int64, [C.c_int64, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_int64)]),
     ("pvio_write_bam", C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    ("pvio_write_bam_hp", C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int]),
     ("pvio_write_vcf_gz", C.c_int, [C.c_char_p, C.c_char_p, C.c_int64]),
     ("pvio_bgzf_read_all", C.c_int64, [C.c_char_p, C.c_char_p, C.c_int64]),
     ("pvio_fasta_open", C.c_void_p, [C.c_char_p]),
@@ -403,16 +406,23 @@ def reservoir_indices(n_reads: int, downsample_rate: float = 1.0, max_reads: int
     return out[:k]
 
 
-def write_bam(path: str, refs, read_tid, batch, level: int = 1):
+def write_bam(path: str, refs, read_tid, batch, level: int = 1, read_hp=None):
     """coordinate-sorted BAM + BAI from the flat arrays of a RegionBatch-like object (read_pos, read_flags, read_mapq,
-    base_off, bases, quals, cigar_off, cigar); refs = [(name, length)]; read_tid int32 per read"""
+    base_off, bases, quals, cigar_off, cigar); refs = [(name, length)]; read_tid int32 per read; read_hp (optional) int32 per
+    read: a value 1 .. 255 becomes the read's HP aux tag"""
     names = (C.c_char_p * len(refs))(*[r[0].encode() for r in refs])
     lens = (C.c_int64 * len(refs))(*[int(r[1]) for r in refs])
     tid = np.ascontiguousarray(read_tid, dtype=np.int32)
     arrs = [np.ascontiguousarray(getattr(batch, f)) for f in ("read_pos", "read_flags", "read_mapq", "base_off", "bases", "quals",
                                                                 "cigar_off", "cigar")]
-    rc = load().pvio_write_bam(path.encode(), len(refs), names, lens, int(tid.shape[0]), tid.ctypes.data,
-                               *[a.ctypes.data for a in arrs], int(level))
+    if read_hp is None:
+        rc = load().pvio_write_bam(path.encode(), len(refs), names, lens, int(tid.shape[0]), tid.ctypes.data,
+                                   *[a.ctypes.data for a in arrs], int(level))
+    else:
+        hp = np.ascontiguousarray(read_hp, dtype=np.int32)
+        assert hp.shape == tid.shape
+        rc = load().pvio_write_bam_hp(path.encode(), len(refs), names, lens, int(tid.shape[0]), tid.ctypes.data,
+                                      *[a.ctypes.data for a in arrs], hp.ctypes.data, int(level))
     if rc:
         raise IOError("write_bam: " + _err())
 

@@ -179,6 +179,11 @@ def polish_parser(ap=None):
                     help="keep the draft wherever the network is not sure (0..94; 0, the default, is off): every run of adjacent "
                          "edited columns whose lowest quality is below this Phred value is taken back whole before the stitch, "
                          "so FASTA, FASTQ and edits agree and every VCF record has QUAL >= it (opt-in; one device)")
+    ap.add_argument("-hp", "--use_hp_info", action="store_true", default=False,
+                    help="one polished sequence per haplotype from the reads' HP tags: writes <output_file>/_pepper_polished_hp1.fa "
+                         "and _hp2.fa (and the _hp1 / _hp2 forms of the FASTQ and the edits VCF) in place of the un-suffixed "
+                         "files; haplotype h is polished with the untagged reads and those tagged HP:h, selected on the device "
+                         "from one read of the BAM (opt-in; one device)")
     return ap
 
 

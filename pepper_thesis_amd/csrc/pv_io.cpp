@@ -1461,10 +1461,11 @@ extern "C" int pvio_plan_intervals(pv_bam* b, int n_intervals, const char* const
 // ---- writers ---------------------------------------------------------------------------------------------------------
 // A coordinate-sorted BAM + BAI from flat arrays (synthetic inputs of the file-path benchmark and tests). Reads must be
 // sorted by (tid, pos); flags: bit0 = reverse strand.
-extern "C" int pvio_write_bam(const char* path, int n_ref, const char* const* ref_names, const int64_t* ref_lens, int64_t n_reads,
-                              const int32_t* read_tid, const int64_t* read_pos, const uint8_t* read_flags, const uint8_t* read_mapq,
-                              const int64_t* base_off, const uint8_t* bases, const uint8_t* quals, const int64_t* cigar_off,
-                              const uint32_t* cigar, int level) {
+// read_hp (may be null): a read with a value 1 .. 255 carries it as its HP:C aux tag.
+extern "C" int pvio_write_bam_hp(const char* path, int n_ref, const char* const* ref_names, const int64_t* ref_lens, int64_t n_reads,
+                                 const int32_t* read_tid, const int64_t* read_pos, const uint8_t* read_flags, const uint8_t* read_mapq,
+                                 const int64_t* base_off, const uint8_t* bases, const uint8_t* quals, const int64_t* cigar_off,
+                                 const uint32_t* cigar, const int32_t* read_hp, int level) {
     if (!path || n_ref <= 0 || !ref_names || !ref_lens) { io_err("null argument"); return -1; }
     BgzfWriter w;
     w.level = level;
@@ -1517,6 +1518,10 @@ extern "C" int pvio_write_bam(const char* path, int n_ref, const char* const* re
         rec.resize(at + (size_t)((l_seq + 1) / 2), 0);
         for (int64_t i = 0; i < l_seq; i++) rec[at + (size_t)(i >> 1)] |= (uint8_t)(code[bases[b0 + i]] << ((~i & 1) << 2));
         rec.insert(rec.end(), quals + b0, quals + b1);
+        if (read_hp && read_hp[r] >= 1 && read_hp[r] <= 255) {
+            const uint8_t aux[4] = {'H', 'P', 'C', (uint8_t)read_hp[r]};
+            rec.insert(rec.end(), aux, aux + 4);
+        }
         const uint32_t bs = (uint32_t)(rec.size() - 4);
         for (int i = 0; i < 4; i++) rec[i] = (bs >> (8 * i)) & 0xFF;
         if (w.cur.size() + rec.size() > BgzfWriter::BLOCK && !w.flush_block()) { fclose(w.f); return -1; }
@@ -1534,6 +1539,14 @@ extern "C" int pvio_write_bam(const char* path, int n_ref, const char* const* re
     if (!f || fwrite(bai.data(), 1, bai.size(), f) != bai.size()) { io_err("cannot write %s", bp.c_str()); if (f) fclose(f); return -1; }
     fclose(f);
     return 0;
+}
+
+extern "C" int pvio_write_bam(const char* path, int n_ref, const char* const* ref_names, const int64_t* ref_lens, int64_t n_reads,
+                              const int32_t* read_tid, const int64_t* read_pos, const uint8_t* read_flags, const uint8_t* read_mapq,
+                              const int64_t* base_off, const uint8_t* bases, const uint8_t* quals, const int64_t* cigar_off,
+                              const uint32_t* cigar, int level) {
+    return pvio_write_bam_hp(path, n_ref, ref_names, ref_lens, n_reads, read_tid, read_pos, read_flags, read_mapq, base_off, bases,
+                             quals, cigar_off, cigar, nullptr, level);
 }
 
 // bgzip a VCF text and write its tabix index (<path>.tbi), the two things pysam.VariantFile('w' on *.vcf.gz) +

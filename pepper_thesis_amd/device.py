@@ -125,3 +125,55 @@ class DevicePolishOut:
     def set_depth(self, depth: np.ndarray):
         """a host depth plane uint16 [n, seq_length] into the first n chunks"""
         self.depth[:len(depth)].copy_(torch.from_numpy(np.ascontiguousarray(depth, np.uint16).view(np.int16)))
+
+
+class DeviceSelectOut:
+    """Caller-owned output arrays of pv_select_out in HBM (the reads of one haplotype, `polish -hp`). `fill` (a byte value)
+    presets every array, for tests that look at what a call left alone."""
+
+    def __init__(self, n_regions: int, read_capacity: int, base_capacity: int, cigar_capacity: int, device="cuda:0",
+                 want_hp: bool = True, want_src: bool = True, fill: int = None):
+        self.n_regions = int(n_regions)
+        self.read_capacity, self.base_capacity, self.cigar_capacity = int(read_capacity), int(base_capacity), int(cigar_capacity)
+        nr, nb, nc = self.read_capacity, self.base_capacity, self.cigar_capacity
+
+        def buf(n, dtype):
+            t = torch.empty(max(int(n), 1), dtype=dtype, device=device)
+            if fill is not None:
+                t.view(torch.uint8).fill_(int(fill))
+            return t
+        self.t = dict(read_off=buf(self.n_regions + 1, torch.int64), read_pos=buf(nr, torch.int64),
+                      read_flags=buf(nr, torch.uint8), read_mapq=buf(nr, torch.uint8), base_off=buf(nr + 1, torch.int64),
+                      bases=buf(nb, torch.uint8), quals=buf(nb, torch.uint8), cigar_off=buf(nr + 1, torch.int64),
+                      cigar=buf(nc, torch.int32))
+        self.read_hp = buf(nr, torch.int32) if want_hp else None
+        self.src_read = buf(nr, torch.int64) if want_src else None
+        self.counts = torch.zeros(4, dtype=torch.int64, device=device)
+        c = _ffi.pv_select_out()
+        c.read_capacity, c.base_capacity, c.cigar_capacity = nr, nb, nc
+        for f, t in self.t.items():
+            setattr(c, f, t.data_ptr())
+        c.read_hp = self.read_hp.data_ptr() if want_hp else None
+        c.src_read = self.src_read.data_ptr() if want_src else None
+        self.c = c
+
+    def fits(self, n_regions: int, n_reads: int, n_bases: int, n_cigar: int) -> bool:
+        return (self.n_regions >= n_regions and self.read_capacity >= n_reads and self.base_capacity >= n_bases
+                and self.cigar_capacity >= n_cigar)
+
+
+class SelectedDeviceBatch:
+    """a device batch whose read arrays are a DeviceSelectOut's (the reads of one haplotype) and whose region arrays are the
+    input's: what the realigner and the builders take in place of the DeviceBatch it was selected from"""
+
+    def __init__(self, db, sel: DeviceSelectOut, n_reads: int, n_bases: int, n_cigar: int):
+        c = _ffi.pv_batch_in()
+        for f, _ in _ffi.pv_batch_in._fields_:
+            setattr(c, f, getattr(db.c, f))
+        for f, t in sel.t.items():
+            setattr(c, f, t.data_ptr())
+        self.c, self._keep = c, (db, sel)
+        self.read_hp = sel.read_hp
+        self.n_reads, self.n_bases, self.n_cigar = int(n_reads), int(n_bases), int(n_cigar)
+        self.n_ref_bytes, self.max_region_len = db.n_ref_bytes, db.max_region_len
+        self.t = db.t

@@ -9,7 +9,7 @@ prediction HDF5 files. Here each batch of regions goes through
 without leaving HBM; only the region offsets and the polished bases (one byte per base) come back to the host.
 
   python -m pepper_thesis_amd polish -b reads.bam -f draft.fa -m model.pkl -o out/polished [-t 5] [-r ctg:start-end] [--bf16]
-      [--realign] [--gpu_decode] [--qualities] [--edits] [--min_depth N] [--min_qual Q]
+      [--realign] [--gpu_decode] [--qualities] [--edits] [--min_depth N] [--min_qual Q] [-hp]
 
 --gpu_decode (opt-in) replaces the first stage: reader threads only plan blocks and fetch draft bytes, and the BAM is inflated,
 decoded and clipped on the device (gpu_decode.py; _decoded_pieces below). Same FASTA.
@@ -41,6 +41,15 @@ back, in place, every run of adjacent edited columns whose lowest quality is bel
 (the rule is in include/pepper_hip.h). A run over a draft byte other than ACGT cannot be spelled and stays. Stitch, qualities
 and edits then agree without knowing of it, every VCF record has QUAL >= Q, and the VCF carries one ##pepper_min_qual=Q line.
 Without the flag no output changes by a byte. The reference has no counterpart, and no Q is recommended.
+
+-hp / --use_hp_info (opt-in, one device) writes one polished sequence per haplotype, `<o>/_pepper_polished_hp1.fa` and
+`_hp2.fa` (with --qualities / --edits their `_hp1` / `_hp2` forms; the un-suffixed files are not written). A launch is read,
+decoded and uploaded once; then for h in (1, 2) pv_batch_select_hp_dev compacts the batch on the device to the reads whose HP
+tag is 0 or h (the rule is in include/pepper_hip.h) and the chain above runs on that batch, from the realigner on, with its
+kernels unchanged and its buffers reused. The selection's counters and read_off come back: a region left without reads for h
+gives no piece for h (with --min_depth it is filled from the draft), as a region without reads gives none. A launch in which
+no read is tagged runs the chain once for both. Each haplotype's files are those of a plain run on a BAM holding only the
+untagged reads and those of the haplotype. The edits VCF carries one ##pepper_haplotype=h line.
 
 Semantics kept from the reference:
   * regions: ImageGenerationUI.py:257-273 - for pos in range(start, end, 1000): [max(start, pos-100), min(end, pos+1100)],
@@ -205,6 +214,23 @@ class ChainResult(NamedTuple):
                 None if self.edits is None else self.edits[self.edit_off[g]:self.edit_off[g + 1]])
 
 
+class HapChainResult(NamedTuple):
+    """what a chain made with use_hp gives for one batch of regions: a ChainResult per haplotype, 1 then 2"""
+    results: tuple     # (ChainResult of haplotype 1, of haplotype 2)
+    has_reads: tuple   # per haplotype: bool [n_regions], False where the selection left the region without reads
+    tags: tuple        # (reads, untagged, HP1, HP2, other values) of the batch: batch_select.tag_counts
+    payload: int = 0   # bytes of bases, qualities and cigar words the two selections read and wrote (0: nothing was selected)
+
+
+HP_TIMERS = ("hp_reads", "hp_untagged", "hp_1", "hp_2", "hp_other")   # and hp_payload_bytes
+
+
+def hp_path(path: str, haplotype: int) -> str:
+    """..._pepper_polished.fa -> ..._pepper_polished_hp<h>.fa"""
+    assert path.endswith(".fa"), path
+    return "%s_hp%d.fa" % (path[:-3], haplotype)
+
+
 class _MaskedChainResult(ChainResult):
     """a ChainResult with the instance attributes `masked` and `filtered`"""
 
@@ -274,11 +300,14 @@ class _DeviceChain:
     qualities) of the rows below min_depth are rewritten in place to spell the draft (the result's masked). min_qual >= 1:
     the row qualities are computed whether or not the chain was made for qualities and, behind the mask and before the
     stitch, every run of adjacent edits whose lowest quality is below min_qual is taken back in place (the result's
-    filtered)."""
+    filtered). use_hp: run / run_decoded return a HapChainResult: the batch is selected on the device by haplotype
+    (pv_batch_select_hp_dev) and everything from the realigner on runs once per haplotype on the selected reads."""
 
     def __init__(self, ctx, own_ctx: bool = False, qualities: bool = False, edits: bool = False, min_depth: int = 0,
-                 min_qual: int = 0):
+                 min_qual: int = 0, use_hp: bool = False):
         import torch
+        self.use_hp = bool(use_hp)
+        self.sel = None
         self.ctx, self.dev, self.own_ctx, self.qualities = ctx, "cuda:%d" % ctx.device_id, own_ctx, bool(qualities)
         self.edits = bool(edits)
         self.min_depth = int(min_depth)
@@ -396,30 +425,93 @@ class _DeviceChain:
             host_batch, db = self._realign(db, host_batch, qmax, windows)
         return db, self._summarize(db, sizes, host_batch)
 
-    def build(self, batch, windows=None):
-        """_build for one host batch of regions, uploaded here"""
+    def _host_inputs(self, batch, windows):
+        """_build's first four arguments for one host batch of regions, uploaded here"""
         from .device import DeviceBatch
         sizes = int((batch.ref_end - batch.ref_start + 1).sum()), batch.n_regions
         qmax = int(np.diff(batch.base_off).max()) if windows is not None and batch.n_reads else 0   # (the realigner's alone)
-        return self._build(DeviceBatch(batch, self.dev), sizes, lambda: batch, qmax, windows)
+        return DeviceBatch(batch, self.dev), sizes, lambda: batch, qmax
+
+    def _decoded_inputs(self, dec):
+        """_build's first four arguments for a gpu_decode.DecodedBatch: the reads are on the device already, the decode is
+        ordered before the chain with its event, the longest read comes from the decode, the region sizes from its plan
+        (the polisher's reference bytes are one per column of the region)"""
+        dec.wait_on(self.ctx)
+        if not self.use_hp:
+            return dec, (dec.n_ref_bytes, dec.n_regions), lambda: dec.to_host()[0], dec.qmax
+
+        def host():   # the host copy with its tags, for the host form of the selection
+            b, hp = dec.to_host()
+            b.read_hp = np.ascontiguousarray(hp, np.int32)
+            return b
+        return dec, (dec.n_ref_bytes, dec.n_regions), host, dec.qmax
+
+    def build(self, batch, windows=None):
+        """_build for one host batch of regions"""
+        return self._build(*self._host_inputs(batch, windows), windows)
 
     def build_decoded(self, dec, windows=None):
-        """_build for a gpu_decode.DecodedBatch: the reads are on the device already, the decode is ordered before the
-        chain with its event, the longest read comes from the decode, the region sizes from its plan (the polisher's
-        reference bytes are one per column of the region)"""
-        dec.wait_on(self.ctx)
-        return self._build(dec, (dec.n_ref_bytes, dec.n_regions), lambda: dec.to_host()[0], dec.qmax, windows)
+        """_build for a gpu_decode.DecodedBatch"""
+        return self._build(*self._decoded_inputs(dec), windows)
 
     def run(self, batch, windows=None) -> ChainResult:
         """one batch of regions -> its ChainResult: region_off [n_regions+1], the polished bases of all its regions,
-        concatenated, and the planes this chain was made for"""
+        concatenated, and the planes this chain was made for (a chain made with use_hp: a HapChainResult)"""
+        if self.use_hp:
+            return self._run_hp(*self._host_inputs(batch, windows), windows, batch.n_regions)
         db, n = self.build(batch, windows)
         return self._labels_and_stitch(db, n, batch.n_regions)
 
     def run_decoded(self, dec, windows=None) -> ChainResult:
         """run for a gpu_decode.DecodedBatch"""
+        if self.use_hp:
+            return self._run_hp(*self._decoded_inputs(dec), windows, dec.n_regions)
         db, n = self.build_decoded(dec, windows)
         return self._labels_and_stitch(db, n, dec.n_regions)
+
+    def _select(self, db, haplotype: int, n_regions: int):
+        """the reads of one haplotype of a device batch, compacted into the chain's selection buffers -> (device batch of
+        the kept reads, its read_off on the host). The counters and read_off are read back: the builder takes the totals as
+        arguments, and the regions left without reads give no piece."""
+        import torch
+        from .device import DeviceSelectOut, SelectedDeviceBatch
+        if self.sel is None or not self.sel.fits(n_regions, db.n_reads, db.n_bases, db.n_cigar):
+            old = self.sel
+            self.sel = DeviceSelectOut(*(max(a, b) for a, b in zip(
+                (n_regions, db.n_reads, db.n_bases, db.n_cigar),
+                (old.n_regions, old.read_capacity, old.base_capacity, old.cigar_capacity) if old else (0, 0, 0, 0))),
+                device=self.dev, want_src=False)
+            torch.cuda.synchronize()
+        self.ctx.batch_select_hp_dev(db, haplotype, self.sel)
+        self.ctx.synchronize()
+        kept, n_bases, n_cigar, status = (int(v) for v in self.sel.counts.tolist())
+        if status != _ffi.PV_OK:   # capacity cannot run short: the buffers hold the whole batch
+            raise _ffi.PepperHipError(status, "polisher haplotype selection: device status %d" % status)
+        read_off = self.sel.t["read_off"][:n_regions + 1].cpu().numpy()
+        return SelectedDeviceBatch(db, self.sel, kept, n_bases, n_cigar), read_off
+
+    def _run_hp(self, db, sizes, host_batch, qmax: int, windows, n_regions: int) -> HapChainResult:
+        """one uploaded (or decoded) batch -> a ChainResult per haplotype: select, [realign], builder, then the rest of the
+        chain, for h = 1, 2 in turn on the chain's buffers. A host batch without tags (read_hp None) keeps every read for
+        both, so the chain runs once."""
+        from .batch_select import tag_counts
+        tags = tag_counts(db.read_hp, db.n_reads)
+        if db.read_hp is None:
+            has = np.diff(host_batch().read_off) > 0
+            b, n = self._build(db, sizes, host_batch, qmax, windows)
+            res = self._labels_and_stitch(b, n, n_regions)
+            return HapChainResult((res, res), (has, has), tags)
+        results, has_reads, payload = [], [], 0
+        for h in (1, 2):
+            sdb, read_off = self._select(db, h, n_regions)
+            has_reads.append(np.diff(read_off) > 0)
+            payload += 2 * (2 * sdb.n_bases + 4 * sdb.n_cigar)
+            if sdb.n_reads == 0:   # nothing to build from
+                results.append(self._labels_and_stitch(sdb, 0, n_regions))
+                continue
+            b, n = self._build(sdb, sizes, lambda h=h: self.ctx.batch_select_hp(host_batch(), h)[0], qmax, windows)
+            results.append(self._labels_and_stitch(b, n, n_regions))
+        return HapChainResult(tuple(results), tuple(has_reads), tags, payload)
 
     def _labels_and_stitch(self, db, n: int, n_regions: int) -> ChainResult:
         """P2 [-> row qualities] [-> minimum-depth mask] [-> minimum-quality filter] -> stitch [-> edits] over the first n
@@ -491,20 +583,22 @@ class _DeviceChain:
 
 
 def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int, qualities: bool = False,
-                      edits: bool = False, min_depth: int = 0, min_qual: int = 0) -> _DeviceChain:
+                      edits: bool = False, min_depth: int = 0, min_qual: int = 0, use_hp: bool = False) -> _DeviceChain:
     """a context on `device` with the polisher weights loaded, and the chain on it (closing the chain closes the context).
     shared_device: other ranks use this GPU too, so the option is set before the first device call (the split GRU forms need
     co-resident workgroups and would time out, poisoning the labels). False leaves the create-time default (PV_SHARED_DEVICE).
     This is the default `open_chain` of run and polish_rank.run; CPU tests pass a stub with the same signature, whose result
     has run(batch, windows) -> ChainResult and close(). qualities, edits, min_depth, min_qual (each passed only when set):
-    the chain of --qualities / --edits / --min_depth / --min_qual, whose results carry those planes and counts."""
+    the chain of --qualities / --edits / --min_depth / --min_qual, whose results carry those planes and counts. use_hp
+    (passed only when set): the chain of -hp, whose run gives a HapChainResult."""
     from .runtime import Context
     ctx = Context(device)
     try:
         if shared_device:
             ctx.set_option("shared_device", 1)
         ctx.load_p2(state_dict, dtype)
-        return _DeviceChain(ctx, own_ctx=True, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual)
+        return _DeviceChain(ctx, own_ctx=True, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual,
+                            use_hp=use_hp)
     except BaseException:
         ctx.close()
         raise
@@ -584,8 +678,20 @@ def draft_pieces(fa, work: List[Work], pieces, qualities: bool, edits: bool) -> 
     return out
 
 
+def _hap_pieces(T: dict, hres: HapChainResult, works) -> list:
+    """a launch's HapChainResult -> [(haplotype, Piece)]: haplotype 1's regions, then haplotype 2's, each without the regions
+    its selection left without reads; the tag counts and the row counts go into the timers"""
+    for k, v in zip(HP_TIMERS + ("hp_payload_bytes",), tuple(hres.tags) + (hres.payload,)):
+        T[k] = T.get(k, 0) + int(v)
+    out = []
+    for h, (res, has) in enumerate(zip(hres.results, hres.has_reads), 1):
+        _count_masked(T, res)
+        out += [(h, Piece(w.contig, w.start, w.index, *res.region(g))) for g, w in enumerate(works) if has[g]]
+    return out
+
+
 def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int = 2048, threads: int = 5, realign: bool = False,
-                  timers: Optional[dict] = None, gpu_decode: bool = False, open_decoder=None):
+                  timers: Optional[dict] = None, gpu_decode: bool = False, open_decoder=None, use_hp: bool = False):
     """the regions of `work` through the chain -> a Piece for every region with reads, in `work` order. This is the whole
     device part of a run: the single-rank run passes every region, a rank of a multi-device run its share.
     chain.run(batch, windows) -> ChainResult (_DeviceChain or a CPU test's stub); a piece carries the planes that result
@@ -595,9 +701,11 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
     gpu_decode: the device read path (_decoded_pieces): the reader threads only plan, the BAM is inflated, decoded and clipped
     on chain.ctx's device, and the chain takes the batches where they are (chain.run_decoded). open_decoder(T): the decoder,
     by default a gpu_decode.GpuDecoder with the polisher's settings (CPU tests pass a stub with its scan_groups, realize,
-    iterate and close)."""
+    iterate and close).
+    use_hp: the chain was made with use_hp and gives a HapChainResult per launch; (haplotype, Piece) pairs are yielded, per
+    launch haplotype 1's then haplotype 2's, and the timers also count the tags (HP_TIMERS)."""
     if gpu_decode:
-        yield from _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder)
+        yield from _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder, use_hp)
         return
     from .batch import pack_regions
     from .polish_summary import region_from_files
@@ -613,8 +721,11 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
         t0 = time.perf_counter()
         regs = [r for _, r in items]
         res = chain.run(pack_regions(regs), [r.window for r in regs] if realign else None)
-        _count_masked(T, res)
-        out = [Piece(w.contig, w.start, w.index, *res.region(g)) for g, (w, _) in enumerate(items)]
+        if use_hp:
+            out = _hap_pieces(T, res, [w for w, _ in items])
+        else:
+            _count_masked(T, res)
+            out = [Piece(w.contig, w.start, w.index, *res.region(g)) for g, (w, _) in enumerate(items)]
         T["device_s"] += time.perf_counter() - t0
         T["batches"] += 1
         return out
@@ -637,7 +748,7 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
             yield from flush(pending)
 
 
-def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder):
+def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timers, open_decoder, use_hp=False):
     """polish_pieces' device read path. Reader threads plan reader groups (gpu_decode.region_groups: blocks, interval table,
     draft bytes, realign windows); the decoder's service thread scans them, cuts the regions with reads into the launches
     the host path makes (per_launch regions each) and fills them on its own stream; this thread runs the chain on every
@@ -673,9 +784,12 @@ def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timer
                 t0 = time.perf_counter()
                 for kind, b, windows, ws in parts:
                     res = chain.run_decoded(b, windows) if kind == "dev" else chain.run(b, windows)
-                    _count_masked(T, res)
                     T["chain_runs"] += 1
                     T["regions"] += len(ws)
+                    if use_hp:
+                        yield from _hap_pieces(T, res, ws)
+                        continue
+                    _count_masked(T, res)
                     for g, w in enumerate(ws):
                         yield Piece(w.contig, w.start, w.index, *res.region(g))
                 T["device_s"] += time.perf_counter() - t0
@@ -699,8 +813,8 @@ def decode_report(T: dict) -> str:
 def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region: Optional[str] = None, batch_size: int = 2048,
                  threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None,
                  realign: bool = False, chain=None, gpu_decode: bool = False, qualities: bool = False, edits: bool = False,
-                 min_depth: int = 0, min_qual: int = 0) -> str:
-    """-> path of the polished FASTA. batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
+                 min_depth: int = 0, min_qual: int = 0, use_hp: bool = False) -> str:
+    """-> path of the polished FASTA (use_hp: of haplotype 1's). batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
     realign: realign every read to the draft on the device before the builder, as the reference always does.
     chain: a chain with the weights already loaded (open_device_chain; the caller closes it), else one is made on `ctx`
     (default: a context on device 0) from model_path. gpu_decode: polish_pieces' device read path.
@@ -712,7 +826,9 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
     min_depth >= 1: this function's own chain masks the rows below it (a chain passed in must have been made for it), the
     regions without reads are filled from the draft (draft_pieces), and the VCF names the threshold.
     min_qual >= 1: this function's own chain takes back the runs of edits below it (a chain passed in must have been made
-    for it), and the VCF names the threshold."""
+    for it), and the VCF names the threshold.
+    use_hp: one set of files per haplotype (hp_path) in place of the un-suffixed ones; this function's own chain selects the
+    reads by haplotype (a chain passed in must have been made with use_hp)."""
     from .bamio import BamHandler, FastaHandler
     from .runtime import Context
     t_start = time.perf_counter()
@@ -724,7 +840,7 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
         if ctx is None:
             ctx = own = Context(0)
         ctx.load_p2(state_dict, dtype)
-        chain = _DeviceChain(ctx, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual)
+        chain = _DeviceChain(ctx, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual, use_hp=use_hp)
     try:
         fa, bm = FastaHandler(fasta), BamHandler(bam)
         work, T["bases_in"] = polish_work(fa, bm, region)
@@ -736,30 +852,40 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
         if min_qual >= 1 and getattr(chain, "min_qual", None) != min_qual:
             raise ValueError("polish_fused: the chain filters below quality %r, not %d: it was not made for this run"
                              % (getattr(chain, "min_qual", None), min_qual))
-        pieces = list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode))
-        for want, plane in ((qualities, "qual"), (edits, "edits")):
-            if want and pieces and getattr(pieces[0], plane) is None:
-                raise ValueError("polish_fused: the chain's results have no %s plane: it was not made for this run" % plane)
-        if min_depth >= 1:
-            filled = draft_pieces(fa, work, pieces, qualities, edits)
-            T["draft_regions"] = len(filled)
-            pieces += filled
-        vcf = _edits_vcf(fa, fasta, work, pieces, qualities, min_depth, min_qual) if edits else None
+        if use_hp and not getattr(chain, "use_hp", False):
+            raise ValueError("polish_fused: the chain does not select reads by haplotype: it was not made for this run")
+        if use_hp:
+            pairs = list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode, use_hp=True))
+            outputs = [(h, hp_path(out_path, h), [p for k, p in pairs if k == h]) for h in (1, 2)]
+        else:
+            outputs = [(0, out_path, list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode)))]
+        vcfs = []
+        for _, _, pieces in outputs:
+            for want, plane in ((qualities, "qual"), (edits, "edits")):
+                if want and pieces and getattr(pieces[0], plane) is None:
+                    raise ValueError("polish_fused: the chain's results have no %s plane: it was not made for this run" % plane)
+            if min_depth >= 1:
+                filled = draft_pieces(fa, work, pieces, qualities, edits)
+                T["draft_regions"] += len(filled)
+                pieces += filled
+            vcfs.append(_edits_vcf(fa, fasta, work, pieces, qualities, min_depth, min_qual) if edits else None)
     finally:
         if own is not None:
             own.close()
-    seqs = write_polished_fasta(out_path, pieces)
-    if qualities:
-        write_fastq(output_fastq_path(out_path), seqs, merge_pieces(pieces, part=4))
-    if edits:
-        from . import polish_edits
-        polish_edits.write_edits_vcf(polish_edits.output_vcf_path(out_path), *vcf)
-        T["edit_records"], T["vcf_records"] = sum(len(p.edits) for p in pieces), sum(len(r) for r in vcf[4].values())
-    T["bases_out"] = sum(len(s) for s in seqs.values())
+    for (h, path, pieces), vcf in zip(outputs, vcfs):
+        seqs = write_polished_fasta(path, pieces)
+        if qualities:
+            write_fastq(output_fastq_path(path), seqs, merge_pieces(pieces, part=4))
+        if edits:
+            from . import polish_edits
+            polish_edits.write_edits_vcf(polish_edits.output_vcf_path(path), *vcf, **({"haplotype": h} if h else {}))
+            T["edit_records"] = T.get("edit_records", 0) + sum(len(p.edits) for p in pieces)
+            T["vcf_records"] = T.get("vcf_records", 0) + sum(len(r) for r in vcf[4].values())
+        T["bases_out"] += sum(len(s) for s in seqs.values())
     T["wall_s"] = time.perf_counter() - t_start
     if timers is not None:
         timers.update(T)
-    return out_path
+    return outputs[0][1]
 
 
 def _edits_vcf(fa, fasta_path: str, work: List[Work], pieces, qualities: bool, min_depth: int = 0, min_qual: int = 0) -> tuple:
@@ -825,6 +951,11 @@ def run(args, open_chain=open_device_chain) -> int:
         sys.stderr.write("ERROR: polish --min_qual runs on one device (-d_ids %s lists %d): the row qualities are not carried "
                          "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
         return 2
+    use_hp = bool(getattr(args, "use_hp_info", False))
+    if use_hp and len(plan) > 1:
+        sys.stderr.write("ERROR: polish -hp runs on one device (-d_ids %s lists %d): the haplotypes are not carried through the "
+                         "rank exchange yet.\n" % (args.device_ids, len(plan)))
+        return 2
     for what, path in (("BAM", args.bam), ("FASTA", args.fasta), ("MODEL", args.model_path)):
         if not os.path.isfile(path):
             sys.stderr.write("ERROR: CAN NOT LOCATE %s FILE.\n" % what)
@@ -847,13 +978,15 @@ def run(args, open_chain=open_device_chain) -> int:
         kw["min_depth"] = min_depth
     if min_qual:
         kw["min_qual"] = min_qual
+    if use_hp:
+        kw["use_hp"] = True
     chain = open_chain(device, False, state_dict, dtype, **kw)
     try:
         T = {}
         path = polish_fused(args.bam, args.fasta, args.model_path, args.output_file, args.region, args.batch_size, args.threads,
                             timers=T, realign=bool(getattr(args, "realign", False)), chain=chain,
                             gpu_decode=bool(getattr(args, "gpu_decode", False)), qualities=qualities, edits=edits,
-                            min_depth=min_depth, min_qual=min_qual)
+                            min_depth=min_depth, min_qual=min_qual, **({"use_hp": True} if use_hp else {}))
     except ValueError as e:
         if not edits:
             raise
@@ -864,6 +997,14 @@ def run(args, open_chain=open_device_chain) -> int:
     if decode_report(T):
         log(decode_report(T))
     log("POLISHED FASTA: %s (%d REGIONS, %d BASES IN %.2f SEC)" % (path, T["regions"], T["bases_out"], T["wall_s"]))
+    paths = [path]
+    if use_hp:
+        paths.append(hp_path(path[:-len("_hp1.fa")] + ".fa", 2))
+        log("POLISHED FASTA: " + paths[1])
+        log("HAPLOTYPES: %d READS SEEN, %d UNTAGGED, %d HP1, %d HP2, %d WITH OTHER TAG VALUES (IN NEITHER HAPLOTYPE)"
+            % tuple(T.get(k, 0) for k in HP_TIMERS))
+        if T.get("hp_reads", 0) == T.get("hp_untagged", 0):
+            sys.stderr.write("WARNING: polish -hp: no read carries an HP tag; both haplotypes are the plain polish of all reads.\n")
     if min_depth:
         log("MIN DEPTH %d: %d CHUNK ROWS KEPT THE DRAFT, %d COULD NOT (DRAFT BYTE NOT ACGT), %d REGIONS WITHOUT READS FILLED FROM THE DRAFT"
             % (min_depth, T["masked_rows"], T["unmaskable_rows"], T["draft_regions"]))
@@ -871,8 +1012,9 @@ def run(args, open_chain=open_device_chain) -> int:
         log("MIN QUAL %d: %d CHUNK ROWS OF EDITS TAKEN BACK, %d ROWS OF LOW RUNS KEPT (DRAFT BYTE NOT ACGT)"
             % (min_qual, T["reverted_rows"], T["pinned_rows"]))
     if qualities:
-        log("POLISHED FASTQ: " + output_fastq_path(path))
+        log("POLISHED FASTQ: " + ", ".join(output_fastq_path(p) for p in paths))
     if edits:
         from .polish_edits import output_vcf_path
-        log("EDITS VCF: %s (%d RECORDS FROM %d EDITED COLUMNS)" % (output_vcf_path(path), T["vcf_records"], T["edit_records"]))
+        log("EDITS VCF: %s (%d RECORDS FROM %d EDITED COLUMNS)" % (", ".join(output_vcf_path(p) for p in paths), T["vcf_records"],
+                                                                   T["edit_records"]))
     return 0

@@ -293,6 +293,21 @@ class Context:
             self.handle, C.byref(dbatch.c), dbatch.n_reads, dbatch.n_bases, int(max_query_len), d_win_off, d_win,
             C.byref(dout.c), dout.counts.data_ptr(), stream or None))
 
+    def batch_select_hp(self, batch: RegionBatch, haplotype: int, capacities=None):
+        """the reads of one haplotype of a host batch (pv_batch_select_hp, host buffers) -> (RegionBatch of the kept reads,
+        src_read int64 [kept]: their input indices); see batch_select.py"""
+        from .batch_select import select_hp
+        return select_hp(self, batch, haplotype, capacities)
+
+    def batch_select_hp_dev(self, dbatch, haplotype: int, dout: "DeviceSelectOut", stream: int = 0):
+        """asynchronous, device-resident selection of dbatch's reads by haplotype (pv_batch_select_hp_dev) into a
+        device.DeviceSelectOut; counters {reads, bases, cigar words kept, status} in dout.counts. dbatch.read_hp None = no
+        read is tagged (every read is kept)."""
+        hp = getattr(dbatch, "read_hp", None)
+        _ffi.check(self.lib.pv_batch_select_hp_dev(
+            self.handle, C.byref(dbatch.c), None if hp is None else hp.data_ptr(), dbatch.n_reads, dbatch.n_bases, dbatch.n_cigar,
+            int(haplotype), C.byref(dout.c), dout.counts.data_ptr(), stream or None))
+
     def bgzf_inflate(self, payload: np.ndarray, in_off, clen, isize, crc, out_off, out: np.ndarray = None):
         """host-buffer BGZF inflate (pv_bgzf_inflate) of a block table -> (out uint8, status int32 [n], counts (bytes,
         status, first bad block, its status)). A failed block does not raise: its status says why (the PV_BGZF_* codes).

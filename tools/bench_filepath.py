@@ -27,8 +27,9 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def make_files(dirname, contig_len, depth=60, read_len=10_000, site_every=198, seed=77):
-    """synthetic contig + reads -> ref.fa(.fai), reads.bam(.bai)"""
+def make_files(dirname, contig_len, depth=60, read_len=10_000, site_every=198, seed=77, hp_seed=None):
+    """synthetic contig + reads -> ref.fa(.fai), reads.bam(.bai). hp_seed: the reads carry HP tags dealt by that seed, about a
+    third each untagged, HP:1 and HP:2 (info["hp_counts"])"""
     from pepper_thesis_amd import bamio, synth
     from pepper_thesis_amd.batch import pack_regions
     t0 = time.perf_counter()
@@ -51,8 +52,10 @@ def make_files(dirname, contig_len, depth=60, read_len=10_000, site_every=198, s
     with open(fa + ".fai", "w") as f:
         f.write("chr20\t%d\t%d\t%d\t%d\n" % (len(ref), off, width, width + 1))
     bam = os.path.join(dirname, "reads.bam")
-    bamio.write_bam(bam, [("chr20", contig_len)], np.zeros(b.n_reads, np.int32), b, level=1)
-    return bam, fa, dict(reads=b.n_reads, bases=b.n_bases, synth_and_write_s=time.perf_counter() - t0,
+    hp = None if hp_seed is None else np.random.default_rng(hp_seed).integers(0, 3, b.n_reads).astype(np.int32)
+    bamio.write_bam(bam, [("chr20", contig_len)], np.zeros(b.n_reads, np.int32), b, level=1, read_hp=hp)
+    more = {} if hp is None else dict(hp_counts=np.bincount(hp, minlength=3).tolist())
+    return bam, fa, dict(more, reads=b.n_reads, bases=b.n_bases, synth_and_write_s=time.perf_counter() - t0,
                          bam_bytes=os.path.getsize(bam), inflate_backend=bamio.inflate_backend())
 
 

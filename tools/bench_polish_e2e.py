@@ -42,8 +42,13 @@
               by HIP events, and the rows the filter took back. The weights are random: nearly every column is an edit and
               whole regions are single runs, so the reverted fraction and the host time say nothing about a trained model.
 
+  -hp:        the same comparison for `polish -hp` on a BAM whose reads carry HP tags (about a third each untagged, 1 and 2, a
+              fixed seed): wall times of the plain form and the -hp form on that file, twice each, then one more -hp run with
+              --realign with the selection, the realigner and the builder calls bracketed by HIP events, and the selection's
+              achieved bytes per second (payload read + payload written over its time).
+
   python tools/bench_polish_e2e.py [--leg stitch|e2e|steps|all] [--mbp 2.0] [--reps 20] [--realign] [--d_ids 0,0] [--gpu_decode]
-                                   [--qualities] [--edits] [--min_depth N] [--min_qual Q] [--out f]
+                                   [--qualities] [--edits] [--min_depth N] [--min_qual Q] [-hp] [--out f]
 For the rocprofv3 row run the stitch leg alone under `rocprofv3 --kernel-trace --stats -d <dir> -- python ... --leg stitch`.
 """
 import argparse
@@ -132,9 +137,11 @@ def stitch_leg(reps=20):
 
 
 def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False, qualities=False, edits=False, min_depth=0,
-             min_qual=0):
+             min_qual=0, use_hp=False):
     # warm-up on a small region (code objects, allocator), then the timed run
     kw = {"gpu_decode": True} if gpu_decode else {}
+    if use_hp:
+        kw["use_hp"] = True
     if min_depth:
         kw["min_depth"] = min_depth
     if min_qual:
@@ -153,6 +160,9 @@ def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decod
            "polished_bp": T["bases_out"], "fasta_bytes": size, "wall_s": round(wall, 3),
            "read_s": round(T["read_s"], 3), "device_s": round(T["device_s"], 3),
            "draft_mbp_per_s": round(T["bases_in"] / wall / 1e6, 4), "reader_threads": threads}
+    if use_hp:
+        res.update(use_hp=True, fasta_bytes_hp2=os.path.getsize(polish.hp_path(path[:-len("_hp1.fa")] + ".fa", 2)),
+                   tags={k: T[k] for k in polish.HP_TIMERS})
     if min_depth:
         res.update(min_depth=min_depth, masked_rows=T["masked_rows"], unmaskable_rows=T["unmaskable_rows"],
                    draft_regions=T["draft_regions"])
@@ -285,6 +295,87 @@ def min_depth_leg(mbp=3.0, threads=16, min_depth=3):
                            "polish_mask: count + finish + write kernels of one mask call; polish_stitch: count + scan + write; HIP "
                            "events around every call of a run, summed over the run's launches. The weights are random, so the FASTA "
                            "of the plain run is not the draft and the two FASTA files differ wherever a row was masked")
+            return res
+        finally:
+            ctx.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def select_kernels(ctx, reads=67_000, regions=1000, reps=20):
+    """pv_batch_select_hp_dev alone on a synthetic batch of the shape of one launch of the 3 Mbp run (clipped reads of 600 to
+    1700 bases, tags a third each): microseconds per call of every kernel and of the whole call (HIP events, two profiled
+    rounds: the kernels, then the call), and bytes per second of the bases / qualities gather and of the call"""
+    import numpy as np
+    import torch
+    import select_ref as sel
+    from pepper_thesis_amd.device import DeviceBatch, DeviceSelectOut
+    rng = np.random.default_rng(1)
+    b = sel.make_batch(rng.integers(600, 1700, reads), rng.integers(20, 60, reads), np.full(regions, reads // regions),
+                       rng.integers(0, 3, reads), 2)
+    db = DeviceBatch(b)
+    so = DeviceSelectOut(regions, b.n_reads, b.n_bases, b.n_cigar, want_src=False)
+    torch.cuda.synchronize()
+    for _ in range(3):
+        ctx.batch_select_hp_dev(db, 1, so)
+    ctx.synchronize()
+    out = {"reads": reads, "bases": b.n_bases, "cigar_words": b.n_cigar, "reps": reps, "us_per_call": {}}
+    for only in ("k_sel", "polish_select"):
+        ctx.profile_begin(only)
+        for _ in range(reps):
+            ctx.batch_select_hp_dev(db, 1, so)
+        out["us_per_call"].update({k: round(v[0] / reps * 1e3, 2) for k, v in ctx.profile_end().items()})
+    kept, kb, kc, status = so.counts.cpu().numpy().tolist()
+    assert status == 0, status
+    out["kept_reads_bases_words"] = [kept, kb, kc]
+    out["payload_bytes_read_plus_written"] = 2 * (2 * kb + 4 * kc)
+    out["gather_bases_gb_per_s"] = round(4 * kb / (out["us_per_call"]["k_sel_gather_bases"] * 1e-6) / 1e9, 1)
+    out["call_gb_per_s"] = round(out["payload_bytes_read_plus_written"] / (out["us_per_call"]["polish_select"] * 1e-6) / 1e9, 1)
+    return out
+
+
+def hp_leg(mbp=3.0, threads=16):
+    """polish without and with -hp on one synthetic contig whose reads carry HP tags, in one process on the same files"""
+    import numpy as np
+    from bench_filepath import make_files
+    from pepper_thesis_amd import polish, runtime, synth
+    d = tempfile.mkdtemp(prefix="pv_polish_hp_")
+    try:
+        bam, fa, info = make_files(d, int(mbp * 1_000_000), hp_seed=2024)
+        model = os.path.join(d, "model.npz")
+        np.savez(model, **synth.make_weights_p2(4321, 3.0))
+        ctx = runtime.Context(0)
+        try:
+            # the two forms alternate, twice each: the first timed run of a process also grows the workspace to the launch size
+            runs = []
+            for k in range(2):
+                for hp in (False, True):
+                    r = _e2e_run(polish, ctx, bam, fa, model, os.path.join(d, "hp" if hp else "plain"), threads, False, info, use_hp=hp)
+                    runs.append(dict(r, use_hp=hp, order=len(runs)))
+            res = {"runs": runs, "without_hp": runs[2], "with_hp": runs[3], "hp_counts_of_the_file": info["hp_counts"]}
+            res["hp_over_plain_wall"] = round(runs[3]["wall_s"] / runs[2]["wall_s"], 3)
+            # one more -hp run, with --realign, the selection, realigner and builder calls between HIP events
+            ctx.profile_begin("polish_")
+            try:
+                T = {}
+                polish.polish_fused(bam, fa, model, os.path.join(d, "hp_ev"), threads=threads, ctx=ctx, realign=True, use_hp=True, timers=T)
+            finally:
+                pr = ctx.profile_end()
+            keep = ("polish_select", "polish_realign", "polish_pipeline", "polish_stitch")
+            res["event_ms_launches"] = {k: [round(v[0], 4), v[1]] for k, v in sorted(pr.items()) if k in keep}
+            # the selection's payload as the chain counted it: bases, qualities and cigar words of the kept reads, read once and
+            # written once, both passes of every launch
+            sel_ms, payload = pr.get("polish_select", [0.0, 0])[0], int(T.get("hp_payload_bytes", 0))
+            res["selection"] = {"reads_seen": T.get("hp_reads", 0), "calls": pr.get("polish_select", [0.0, 0])[1], "ms": round(sel_ms, 3),
+                                "payload_bytes_read_plus_written": payload,
+                                "achieved_gb_per_s": round(payload / (sel_ms * 1e-3) / 1e9, 1) if sel_ms else None,
+                                "hbm_copy_rate_gb_per_s_for_comparison": 6290}
+            res["selection_kernels"] = select_kernels(ctx)
+            try:
+                with open(os.path.join(ROOT, "profiles", "polish_e2e_bench.json")) as fh:
+                    res["parent_plain_wall_s"] = json.load(fh)["e2e"]["wall_s"]
+            except (OSError, KeyError, ValueError):
+                res["parent_plain_wall_s"] = None
             return res
         finally:
             ctx.close()
@@ -542,13 +633,17 @@ def main():
                     help="e2e leg without and with polish --min_depth N, plus HIP-event times of the builder, mask and stitch calls")
     ap.add_argument("--min_qual", type=int, default=0,
                     help="e2e leg without and with polish --min_qual Q, plus HIP-event times of the row-quality, filter, stitch and edit calls")
+    ap.add_argument("-hp", "--use_hp_info", action="store_true",
+                    help="e2e leg without and with polish -hp on a BAM with HP tags, plus HIP-event times of the selection, realigner and builder calls")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON to this file")
     a = ap.parse_args()
     out = {}
     if a.leg in ("stitch", "all"):
         out["stitch"] = stitch_leg(a.reps)
     if a.leg in ("e2e", "all"):
-        if a.min_qual:
+        if a.use_hp_info:
+            out["e2e"] = hp_leg(a.mbp, a.threads)
+        elif a.min_qual:
             out["e2e"] = min_qual_leg(a.mbp, a.threads, a.min_qual)
         elif a.min_depth:
             out["e2e"] = min_depth_leg(a.mbp, a.threads, a.min_depth)
