@@ -141,7 +141,7 @@ def no_read_ranges(header: Sequence[str], contig: str) -> List[Tuple[int, int]]:
 
 def apply(records: Sequence[tuple], draft: bytes, cut: Sequence[Tuple[int, int]] = ()) -> str:
     """(POS, REF, ALT, ...) records on the upper-cased draft, then the 0-based inclusive ranges of `cut` taken out. A record's
-    first base, where REF and ALT share it and differ in length, is the anchor and stays with its own position."""
+    first base, where REF and ALT share it and differ in length, is the anchor and stays with its own position; so does the last base of a record at POS 1 that is anchored behind."""
     own = [upper(c) for c in draft]           # what stands for every draft position ...
     tail = [""] * len(draft)                  # ... and what is inserted behind it
     last = 0
@@ -156,6 +156,8 @@ def apply(records: Sequence[tuple], draft: bytes, cut: Sequence[Tuple[int, int]]
                 tail[p] = alt
                 continue
             p += 1
+        elif len(ref) != len(alt) and pos == 1 and len(ref) > 1 and ref[-1:] == alt[-1:]:
+            ref, alt = ref[:-1], alt[:-1]         # a block at the contig's start is anchored behind: that base stays too
         own[p] = alt
         for k in range(p + 1, p + len(ref)):
             own[k] = ""
