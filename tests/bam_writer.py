@@ -10,10 +10,14 @@ NT16 = "=ACMGRSVTWYHKDBN"
 NT16_CODE = {c: i for i, c in enumerate(NT16)}
 
 
-def _bgzf_block(data: bytes) -> bytes:
-    co = zlib.compressobj(6, zlib.DEFLATED, -15)
-    comp = co.compress(data) + co.flush()
+def _bgzf_block(data: bytes, deflate=None) -> bytes:
+    if deflate is None:
+        co = zlib.compressobj(6, zlib.DEFLATED, -15)
+        comp = co.compress(data) + co.flush()
+    else:
+        comp = deflate(data)
     bsize = len(comp) + 25
+    assert bsize < 65536, "the compressed block does not fit a BGZF member"
     return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", bsize) + comp +
             struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))
 
@@ -40,22 +44,22 @@ def ref_len(cigar):
     return sum(l for op, l in cigar if op in (0, 2, 3, 7, 8))
 
 
-def write_bam(path, refs, records, block_records=40):
+def write_bam(path, refs, records, block_records=40, deflate=None):
     """refs: [(name, length)]; records: dicts(tid,pos,mapq,flag,cigar[(op,len)],seq(str),qual(list),name,hp)
-    sorted by (tid,pos). Writes path and path+'.bai'."""
+    sorted by (tid,pos). Writes path and path+'.bai'. deflate: bytes -> raw DEFLATE stream of one block, instead of zlib's."""
     text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % r for r in refs)
     hdr = b"BAM\x01" + struct.pack("<I", len(text)) + text.encode() + struct.pack("<I", len(refs))
     for name, ln in refs:
         hdr += struct.pack("<I", len(name) + 1) + name.encode() + b"\x00" + struct.pack("<I", ln)
     out = bytearray()
-    out += _bgzf_block(hdr)
+    out += _bgzf_block(hdr, deflate)
     index = [dict(bins={}, linear={}) for _ in refs]
     cur = bytearray()
 
     def flush():
         nonlocal cur
         if cur:
-            out.extend(_bgzf_block(bytes(cur)))
+            out.extend(_bgzf_block(bytes(cur), deflate))
             cur = bytearray()
 
     n_in_block = 0
@@ -90,7 +94,7 @@ def write_bam(path, refs, records, block_records=40):
         cur += data
         while len(cur) > 0xFF00:                   # a record longer than a block spans blocks
             head, rest = bytes(cur[:0xFF00]), cur[0xFF00:]
-            out.extend(_bgzf_block(head))
+            out.extend(_bgzf_block(head, deflate))
             cur = bytearray(rest)
         n_in_block += 1
         vend = (len(out) << 16) | len(cur)

@@ -7,6 +7,7 @@ import zlib
 import numpy as np
 import pytest
 
+from deflate_writer import DBASE, DEXT, LBASE, LEXT, Bits  # noqa: F401
 from pepper_thesis_amd import _ffi
 
 pytestmark = pytest.mark.gpu
@@ -25,58 +26,6 @@ def flushed(data: bytes) -> bytes:
     k = len(data) // 3
     return (co.compress(data[:k]) + co.flush(zlib.Z_SYNC_FLUSH) + co.compress(data[k:2 * k]) + co.flush(zlib.Z_FULL_FLUSH) +
             co.flush(zlib.Z_SYNC_FLUSH) + co.compress(data[2 * k:]) + co.flush())
-
-
-class Bits:
-    """LSB-first bit writer (RFC 1951 3.1.1); Huffman codes go MSB-first"""
-
-    def __init__(self):
-        self.v, self.n = 0, 0
-
-    def put(self, val, nbits):
-        self.v |= (val & ((1 << nbits) - 1)) << self.n
-        self.n += nbits
-        return self
-
-    def code(self, c, nbits):
-        for i in range(nbits - 1, -1, -1):
-            self.put((c >> i) & 1, 1)
-        return self
-
-    def lit_fixed(self, sym):
-        if sym < 144:
-            return self.code(0x30 + sym, 8)
-        if sym < 256:
-            return self.code(0x190 + sym - 144, 9)
-        if sym < 280:
-            return self.code(sym - 256, 7)
-        return self.code(0xC0 + sym - 280, 8)
-
-    def bytes(self):
-        return self.v.to_bytes((self.n + 7) // 8 + 1, "little")
-
-    def stored(self, data: bytes, final=0):
-        """a stored block (RFC 1951 3.2.4): header, pad to a byte, LEN, NLEN, the bytes"""
-        self.put(final, 1).put(0, 2)
-        self.n = (self.n + 7) // 8 * 8
-        self.put(len(data), 16).put(~len(data), 16)
-        self.v |= int.from_bytes(data, "little") << self.n
-        self.n += 8 * len(data)
-        return self
-
-    def match_fixed(self, length, dist):
-        """a length/distance pair with the fixed codes, extra bits included"""
-        li = 28 if length == 258 else max(i for i in range(28) if LBASE[i] <= length)
-        self.lit_fixed(257 + li).put(length - LBASE[li], LEXT[li])
-        di = max(i for i in range(30) if DBASE[i] <= dist)
-        return self.code(di, 5).put(dist - DBASE[di], DEXT[di])
-
-
-LBASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
-LEXT = [0] * 8 + [1] * 4 + [2] * 4 + [3] * 4 + [4] * 4 + [5] * 4 + [0]
-DBASE = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145,
-         8193, 12289, 16385, 24577]
-DEXT = [0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13]
 
 
 def far_matches(rng):
@@ -320,7 +269,7 @@ def test_device_form_on_a_second_stream_agrees(hip_ctx):
 
 # ---- the reader mode end to end ----------------------------------------------------------------------------------------
 
-def _reads_bam(tmp_path, seed=17, length=40_000, n_reads=500):
+def _reads_bam(tmp_path, seed=17, length=40_000, n_reads=500, **bam_kw):
     import bam_writer as bw
     from pepper_thesis_amd import build
     build.build_io()
@@ -342,7 +291,7 @@ def _reads_bam(tmp_path, seed=17, length=40_000, n_reads=500):
                 rp += ln
         r["seq"], r["mapq"] = "".join(seq), 60
         r["flag"] &= 0x10
-    bw.write_bam(str(tmp_path / "reads.bam"), [("chr20", len(ref))], recs)
+    bw.write_bam(str(tmp_path / "reads.bam"), [("chr20", len(ref))], recs, **bam_kw)
     return str(tmp_path / "reads.bam"), str(tmp_path / "ref.fa")
 
 
