@@ -72,7 +72,9 @@ int pv_pack_rec_x6(const pv_rnn_dir* dirs, int kx, unsigned char** d_wp, std::ve
 int pv_pack_gru16_bf16(const pv_rnn_dir* dirs, int kx, unsigned char** d_wp, unsigned char** d_wx, std::vector<void*>& owned);
 
 // ---- k_tail_bf16: the tail of the P1 head (sum of linear_1 slabs + bias + SELU, linear_2..5 + SELU, output layer, softmax) with
-// the four 512 x 512 layers as 3-term split products (rnn_rec_bf16.hip). 64 rows per workgroup.
+// the four 512 x 512 layers as 3-term split products (rnn_rec_bf16.hip). 64 rows per workgroup. x6: the six-term form of the
+// split-6 chain on 32-row tiles (three-piece weights, fp32 rows with their pieces x1 | x2), under the profile scope "k_head_tail",
+// whose 32-row launch it replaces there: only the four products differ from that kernel's arithmetic.
 struct pv_tail_desc {
     const float* part;         // linear_1 slabs [splits][part_rows][512]
     int splits;
@@ -86,11 +88,13 @@ struct pv_tail_desc {
     int64_t B;
     unsigned* epoch;           // bumped once (the forward-call counter of the unit-split LSTM form) or NULL
     const int* err;            // non-zero: the probabilities leave as NaN (see k_head_tail) or NULL
+    int x6;                    // the six-term form: wp from pv_pack_tail_bf16 with three pieces
 };
 int pv_tail_bf16_async(pv_ctx* ctx, const pv_tail_desc& d, hipStream_t st);
 int pv_tail_bf16_prepare();
-// w[4]: linear_2..5, [512][512] fp32 row-major (host) -> the fragment stream of k_tail_bf16
-int pv_pack_tail_bf16(const float* const* w, unsigned char** d_wp, std::vector<void*>& owned);
+// w[4]: linear_2..5, [512][512] fp32 row-major (host) -> the fragment stream of k_tail_bf16; pieces = 3: of its six-term form
+// (pack_tail_x6, 6.3 MB)
+int pv_pack_tail_bf16(const float* const* w, unsigned char** d_wp, std::vector<void*>& owned, int pieces = 2);
 
 // ---- P2 (bi-GRU polisher model) in this mode: device weights and the layer-wise forward (rnn_rec_bf16.hip) --------------
 struct pv_p2_bf16_weights {

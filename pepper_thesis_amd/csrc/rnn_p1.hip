@@ -8,7 +8,8 @@
 //   fp32          k_lstm_layer / k_lstm_split (rnn_lstm.hip) -> k_head_splitk -> k_head_tail (rnn_head.hip): rnn_f32.hpp
 //   bf16x3        PV_DTYPE_BF16_INPUT_GEMM: k_rec_bf16 (rnn_rec_bf16.hip) and k_gemm_bf16x3 (rnn_gemm.hip) -> k_tail_bf16 or
 //                 k_head_tail: rnn_bf16.hpp
-//   split-6       large PV_DTYPE_F32 calls: the same on three-piece operands, k_gemm_bf16x6
+//   split-6       large PV_DTYPE_F32 calls: the same on three-piece operands, k_gemm_bf16x6; a 32-row k_head_tail plan runs
+//                 the six-term form of k_tail_bf16
 // Weights are packed on the host (rnn_pack_host.hpp) and uploaded once, at load.
 #include "pv_common.hpp"
 #include "rnn_bf16.hpp"
@@ -54,6 +55,7 @@ struct pv_rnn_p1 {
     unsigned char* enc_r6 = nullptr; unsigned char* dec_r6 = nullptr;
     unsigned char* dec_wih_p3 = nullptr;   // decoder W_ih of both directions [3][2048][512] (biases: dec_bias_cat)
     unsigned char* w1_p3 = nullptr;        // linear_1 [3][512][16896]
+    unsigned char* tail_w6 = nullptr;      // three-piece fragment stream of k_tail_bf16<X6> (linear_2..5, pack_tail_x6)
     std::vector<void*> owned;
 };
 
@@ -123,19 +125,20 @@ extern "C" int pv_rnn_load_p1(pv_ctx* ctx, const pv_weights_p1* w, int dtype) {
         for (int n = 0; n < 1024; n++) bcat[d * 1024 + n] = w->decoder[d].b_ih[n] + w->decoder[d].b_hh[n];
     }
     if ((rc = pv_dev_upload(bcat, &m->dec_bias_cat, m->owned))) return rc;
-    if (dtype == PV_DTYPE_F32) {   // the split-6 chain of large calls: 3.4 + 3.4 MB of fragments, 6 + 51.9 MB of bf16 weight planes
+    const float* tail_w[4] = {w->linear_w[1], w->linear_w[2], w->linear_w[3], w->linear_w[4]};
+    if (dtype == PV_DTYPE_F32) {   // the split-6 chain of large calls: 3.4 + 3.4 + 6.3 MB of fragments, 6 + 51.9 MB of bf16 weight planes
         if ((rc = pv_pack_rec_x6(w->encoder, F_IN, &m->enc_r6, m->owned))) return rc;
         if ((rc = pv_pack_rec_x6(w->decoder, 0, &m->dec_r6, m->owned))) return rc;
         if ((rc = pv_upload_split3(wcat.data(), 2048, 512, &m->dec_wih_p3, m->owned))) return rc;
         if ((rc = pv_upload_split3(w->linear_w[0], HEAD_N, HEAD_K, &m->w1_p3, m->owned))) return rc;
-        if ((rc = pv_gemm_bf16x3_prepare()) || (rc = pv_rec_bf16_prepare())) return rc;
+        if ((rc = pv_pack_tail_bf16(tail_w, &m->tail_w6, m->owned, 3))) return rc;
+        if ((rc = pv_gemm_bf16x3_prepare()) || (rc = pv_rec_bf16_prepare()) || (rc = pv_tail_bf16_prepare())) return rc;
     }
     if (dtype == PV_DTYPE_BF16_INPUT_GEMM) {
         if ((rc = pv_upload_split8(wcat.data(), 2048, 512, &m->dec_wih_s, m->owned))) return rc;
         if ((rc = pv_upload_split8(w->linear_w[0], HEAD_N, HEAD_K, &m->w1_s, m->owned))) return rc;
         if ((rc = pv_pack_rec_bf16(w->encoder, 4, F_IN, &m->enc_rb, nullptr, m->owned))) return rc;
         if ((rc = pv_pack_rec_bf16(w->decoder, 4, 0, &m->dec_rb, nullptr, m->owned))) return rc;
-        const float* tail_w[4] = {w->linear_w[1], w->linear_w[2], w->linear_w[3], w->linear_w[4]};
         if ((rc = pv_pack_tail_bf16(tail_w, &m->tail_wb, m->owned))) return rc;
         if ((rc = pv_gemm_bf16x3_prepare()) || (rc = pv_rec_bf16_prepare()) || (rc = pv_tail_bf16_prepare())) return rc;
     }
@@ -212,9 +215,12 @@ static int p1_forward_mfma(pv_ctx* ctx, const pv_p1_plan& pl, const int8_t* d_im
     gl.A = dec; gl.W = static_cast<const unsigned char*>(c.w1); gl.bias = nullptr; gl.C = part; gl.M = Bp; gl.N = HEAD_N; gl.K = HEAD_K;
     gl.splits = pl.splits; gl.quads = 0; gl.terms = c.terms; gl.prof_name = c.n_lin1;
     if ((rc = pv_gemm_bf16x3_async(ctx, gl, st))) return rc;
-    if (pl.tail == PV_TAIL_HEAD_TAIL) return launch_tail(ctx, pl, part, Bp, d_probs, B, st);
+    // a 32-row k_head_tail plan on the split-6 chain is the six-term form of the tail; its 16-row plans (fewer than one 32-row
+    // tile per CU) and the bf16x3 chain's small calls keep k_head_tail on the f32 MFMA
+    const bool tail6 = x6 && pl.tail == PV_TAIL_HEAD_TAIL && pl.tail_rows == 32;
+    if (pl.tail == PV_TAIL_HEAD_TAIL && !tail6) return launch_tail(ctx, pl, part, Bp, d_probs, B, st);
     pv_tail_desc tb = {};
-    tb.part = part; tb.b1 = m->b1; tb.splits = pl.splits; tb.part_rows = Bp; tb.wp = m->tail_wb;
+    tb.part = part; tb.b1 = m->b1; tb.splits = pl.splits; tb.part_rows = Bp; tb.wp = tail6 ? m->tail_w6 : m->tail_wb; tb.x6 = tail6;
     for (int i = 0; i < 4; i++) tb.b[i] = m->bl[i];
     tb.wo = m->wo; tb.bo = m->bo; tb.probs = d_probs; tb.B = B; tb.epoch = m->sp_epoch; tb.err = m->sp_err;
     return pv_tail_bf16_async(ctx, tb, st);

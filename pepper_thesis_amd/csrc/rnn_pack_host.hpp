@@ -6,7 +6,7 @@
 //
 //   fp32 fragments, f32 MFMA    pack_lstm, pack_lstm_split, pack_linear (P1: rnn_lstm.hip, rnn_head.hip)
 //                               pack_gru, pack_gru_us (P2: rnn_gru.hip)
-//   bf16 pieces, bf16 MFMA      pack_rec_bf16, pack_rec_x6_16, pack_gru16_bf16, pack_tail_bf16, pack_p2_dense, pack_p2_dense16 (rnn_rec_bf16.hip)
+//   bf16 pieces, bf16 MFMA      pack_rec_bf16, pack_rec_x6_16, pack_gru16_bf16, pack_tail_bf16, pack_tail_x6, pack_p2_dense, pack_p2_dense16 (rnn_rec_bf16.hip)
 //   GEMM operands               split8_rows (k_gemm_bf16x3); the three planes of k_gemm_bf16x6 are split3_planes (split3_host.hpp)
 #pragma once
 #include <cstddef>
@@ -295,6 +295,25 @@ static inline void pack_tail_bf16(const float* const* w, std::vector<uint16_t>& 
                         for (int j = 0; j < 8; j++) {
                             const int n = 64 * wv + 32 * g + (lane & 31), k = 16 * ks + 8 * (lane >> 5) + j;
                             pack_put_pieces(dst, lane, j, w[l][(size_t)n * N + k]);
+                        }
+                }
+}
+
+// k_tail_x6 (the split-6 chain's 32-row tail), w[4] = linear_2..5 [512][512]: pack_tail_bf16's slot order and lane map with
+// slots of three pieces [x0 1 KB | x1 1 KB | x2 1 KB]: 8 waves x 4 layers x 32 k-steps x 2 column tiles x 3 KB = 6.3 MB
+static inline void pack_tail_x6(const float* const* w, std::vector<uint16_t>& wp) {
+    constexpr int N = PV_PACK_HEAD_N, KS = N / 16;
+    constexpr size_t SL = 3 * 512;
+    wp.assign((size_t)8 * 4 * KS * 2 * SL, 0);
+    for (int wv = 0; wv < 8; wv++)
+        for (int l = 0; l < 4; l++)
+            for (int ks = 0; ks < KS; ks++)
+                for (int g = 0; g < 2; g++) {
+                    uint16_t* dst = wp.data() + ((((size_t)wv * 4 + l) * KS + ks) * 2 + g) * SL;
+                    for (int lane = 0; lane < 64; lane++)
+                        for (int j = 0; j < 8; j++) {
+                            const int n = 64 * wv + 32 * g + (lane & 31), k = 16 * ks + 8 * (lane >> 5) + j;
+                            pack_put_pieces(dst, lane, j, w[l][(size_t)n * N + k], 3);
                         }
                 }
 }

@@ -68,7 +68,9 @@ inline pv_p1_plan pv_plan_p1(int dtype, int64_t B, int num_cu, const pv_opts& o)
     pv_p1_plan p = {};
     const int n_tiles = (int)((B + PV_P1_ROWS - 1) / PV_P1_ROWS);
     p.head_map = o.head_map;
-    // k_head_tail (PV_TAIL_HEAD_TAIL = 0): 16-row tiles unless 32-row tiles already fill the chip
+    // k_head_tail (PV_TAIL_HEAD_TAIL = 0): 16-row tiles unless 32-row tiles already fill the chip. On the X6 chain a 32-row
+    // k_head_tail plan means the six-term form of the tail (k_tail_bf16<X6>, rnn_rec_bf16.hip: linear_2..5 on the bf16 MFMA,
+    // the rest k_head_tail's arithmetic, the same profile scope); its 16-row plans run k_head_tail<16> itself
     p.tail_rows = o.tail_rows ? o.tail_rows : n_tiles >= num_cu ? 32 : 16;
     if (pv_p1_use_x6(dtype, B, o)) {   // 32-row tiles only: the 64-row form spills with three weight pieces
         p.chain = PV_CHAIN_X6; p.rows = 32; p.mt = 1; p.Bp = (int64_t)n_tiles * PV_P1_ROWS;

@@ -10,7 +10,7 @@
 // h lives in LDS as "split8" rows (per 8 units: 8 bf16 hi, 8 bf16 lo), double-buffered, one barrier per step; a 16-byte half
 // of a group is exactly one A fragment. W_hh (and the LSTM encoder's W_ih) are pre-split on the host into B-fragment order and
 // streamed from L2 through a ring of D register sets requested D - 1 (gate, k-step) slots ahead, wrapping into the next step.
-// (The fragment streams of every kernel here: pack_rec_bf16, pack_rec_x6_16, pack_gru16_bf16, pack_tail_bf16, pack_p2_dense{,16}, rnn_pack_host.hpp.)
+// (The fragment streams of every kernel here: pack_rec_bf16, pack_rec_x6_16, pack_gru16_bf16, pack_tail_bf16, pack_tail_x6, pack_p2_dense{,16}, rnn_pack_host.hpp.)
 // At 4 bytes per weight the stream is what bounds a step (1 MB per LSTM step and workgroup against 12 k MFMA cycles for 32
 // rows), hence MT = 2: 64 rows per weight fetch. The projections G arrive as quads [m / 4][column][4] whose four values are
 // the accumulator registers 4q .. 4q+3 of a lane: they are loaded straight INTO the accumulators at the end of the previous
@@ -226,6 +226,56 @@ __device__ __forceinline__ void ring_x6_16(f32x4 (&acc)[2][4][2], const unsigned
     }
 }
 
+// The ring of the six-term tail (k_tail_bf16<X6>): k-steps [K0, K0 + NKS) of a stream of NKTOT k-steps, a k-step = the two
+// 32-column tiles' slots of three 1 KB pieces (pack_tail_x6), requested DK - 1 k-steps ahead, wrapping as in ring_bf16. One M-tile
+// of 32 rows is one accumulator per column tile, so a slot's six terms are ONE dependent MFMA chain and a k-step offers only 12
+// MFMAs to hide its A fragments' LDS latency behind: the two tiles' chains alternate (per output element the order of ring_bf16<X6>,
+// the small terms first), and the A fragments of k-step ks + 1 are requested under the MFMAs of ks - x1 and x2 as they are,
+// the fp32 values raw, converted to x0 at the head of their own k-step.
+template <int DK, int NKTOT, int K0, int NKS, int H12>
+__device__ __forceinline__ void ring_tail_x6(f32x16 (&acc)[1][2], const unsigned char* __restrict__ At, __amdgpu_buffer_rsrc_t wr,
+                                             f32x4 (&bq)[DK][2][3], unsigned lane16) {
+    f32x4 raw[2];
+    bf16x8 ap[3], nx[2];
+    auto a_load = [&](int ks) {
+        raw[0] = *reinterpret_cast<const f32x4*>(At + ks * 64);
+        raw[1] = *reinterpret_cast<const f32x4*>(At + ks * 64 + 16);
+        nx[0] = *reinterpret_cast<const bf16x8*>(At + ks * 64 + H12);
+        nx[1] = *reinterpret_cast<const bf16x8*>(At + ks * 64 + H12 + 16);
+    };
+    a_load(0);
+#pragma unroll
+    for (int ks = 0; ks < NKS; ks++) {
+        {   // request k-step ks + DK - 1
+            const int kv = (K0 + ks + DK - 1) % NKTOT, rs = (K0 + ks + DK - 1) % DK;
+#pragma unroll
+            for (int g = 0; g < 2; g++)
+#pragma unroll
+                for (int p = 0; p < 3; p++) bq[rs][g][p] = buf_load4(wr, lane16, (unsigned)((kv * 2 + g) * 3072 + p * 1024));
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) ap[0][j] = (__bf16)(j < 4 ? raw[0][j] : raw[1][j - 4]);
+        ap[1] = nx[0];
+        ap[2] = nx[1];
+        if (ks + 1 < NKS) a_load(ks + 1);
+        __builtin_amdgcn_sched_barrier(0);   // keep hipcc from sinking the prefetches next to their uses
+        {
+            const int rs = (K0 + ks) % DK;
+#define PV_T6_TERM(AP, BP)          \
+    _Pragma("unroll") for (int g = 0; g < 2; g++)             \
+        acc[0][g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[AP], __builtin_bit_cast(bf16x8, bq[rs][g][BP]), acc[0][g], 0, 0, 0);
+            PV_T6_TERM(2, 0)
+            PV_T6_TERM(1, 1)
+            PV_T6_TERM(0, 2)
+            PV_T6_TERM(0, 0)
+            PV_T6_TERM(0, 1)
+            PV_T6_TERM(1, 0)
+#undef PV_T6_TERM
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 #ifndef PV_REC_ABL
 #define PV_REC_ABL 0   // diagnostic ablations (timing only, results wrong): 1 = no global output stores, 2 = no LDS h writes,
                        // 3 = LSTM cell update without its transcendentals (h = sum of the four gate sums, c untouched)
@@ -234,6 +284,7 @@ __device__ __forceinline__ void ring_x6_16(f32x4 (&acc)[2][4][2], const unsigned
 // diagnostic build: cycle sums of the phases of a step (workgroup 0, every wave adds), read by pv_debug_rec_stamps
 // [5], [6]: s_memtime and s_memrealtime (100 MHz) ticks of the whole step loop, for the clock the kernel ran at (pv_debug_rec_clock)
 __device__ unsigned long long g_rec_stamps[8];
+__device__ unsigned long long g_tail_stamps[5];   // k_tail_bf16's phases (pv_debug_tail_stamps)
 #define RSTAMP_REAL(v) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory");
 #define RSTAMP(i) { unsigned long long now_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_) :: "memory"); st_acc[i] += now_ - st_last; st_last = now_; }
 #else
@@ -990,7 +1041,23 @@ template <int NG, bool ENC, int MT, bool X6 = false> constexpr size_t lds_rec() 
 // weight traffic per row), 3-term split products through the fragment ring of the recurrent layers, the activations as ONE
 // split8 tile in LDS that is updated in place (every wave holds its 64 x 64 outputs in accumulators until all waves are done
 // reading the tile). Wave w owns output columns [64 w, 64 w + 64) as two 32-column tiles ("gates" of ring_bf16).
-constexpr int TL_N = PV_HEAD_N, TL_ROWS = PV_TAIL_BF16_ROWS, TL_HS = TL_N * 4 + 16, TL_KS = TL_N / 16, TL_SLOTS = TL_KS * 2, TL_D = 8;
+// X6: the same tail for the split-6 chain (PV_DTYPE_F32, launches whose plan names 32-row k_head_tail tiles), the four products
+// as six terms of three-piece operands, the small terms first (ring_tail_x6; stream: pack_tail_x6). 32 rows per workgroup -
+// 256 workgroups at 8192 windows, one per CU - in the split-6 recurrent kernels' row layout: 512 fp32 values, then their
+// pieces x1 | x2 in split8's group order, 8 bytes per unit (stride 4112 B, 4112 / 4 = 4 mod 64 as RecCfg::HS; 131 584 B of LDS).
+// The lane that produces an activation writes the value and split3_rest of it; the K loop converts x0 only. Everything around
+// the four products is k_head_tail's arithmetic: the sequential slab sum, seluf_, the bias as the accumulators' start, the output
+// layer on the fp32 part of the rows with its 8 lanes per (row, class), k order and shuffles, the softmax.
+// TL_DK: k-steps of ring_tail_x6's register sets. 5 (240 VGPRs, no scratch) against 4 (32 fewer): the ring phases of a launch take
+// 125 k against 129 k cycles per wave at 8192 windows - the 6.3 MB stream does not stay in an XCD's 4 MB L2 as the recurrent
+// kernels' does, its requests travel further; a sixth set (24 more registers) does not fit the 256
+constexpr int TL_N = PV_HEAD_N, TL_KS = TL_N / 16, TL_SLOTS = TL_KS * 2, TL_D = 8, TL_DK = 5;
+template <bool X6> struct TailCfg {
+    static constexpr int ROWS = X6 ? PV_P1_ROWS : PV_TAIL_BF16_ROWS, MT = ROWS / 32;
+    static constexpr int HS = TL_N * (X6 ? 8 : 4) + 16, H12 = X6 ? TL_N * 4 : 0;
+    static constexpr int NP = X6 ? 3 : 2, SB = NP * 1024;   // weight pieces, bytes of a stream slot
+    static constexpr size_t LDS = (size_t)ROWS * HS;
+};
 struct TailBfArgs {
     const float* part; int splits; int64_t part_rows;
     const float* b1;
@@ -1000,74 +1067,129 @@ struct TailBfArgs {
     float* probs; int64_t B;
     unsigned* epoch; const int* err;
 };
+template <bool X6>
 __global__ __launch_bounds__(512, 1) void k_tail_bf16(TailBfArgs a) {
+    typedef TailCfg<X6> C;
+    constexpr int TL_ROWS = C::ROWS, TL_HS = C::HS, MT = C::MT, NP = C::NP, SB = C::SB;
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
-    unsigned char* tile = sm;   // [TL_ROWS][TL_HS] split8 rows
+    unsigned char* tile = sm;   // [TL_ROWS][TL_HS] split8 rows (X6: fp32 | x1, x2 groups)
     __shared__ float logits[TL_ROWS][4];
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), rg = lane >> 5;
     const int64_t b0 = (int64_t)blockIdx.x * TL_ROWS;
     if (a.epoch && blockIdx.x == 0 && tid == 0) atomicAdd(a.epoch, 1u);   // both LSTM kernels of this call are done (stream order)
-    const __amdgpu_buffer_rsrc_t wr = make_rsrc(a.wp + (size_t)wv * 4 * TL_SLOTS * 2048);
+    const __amdgpu_buffer_rsrc_t wr = make_rsrc(a.wp + (size_t)wv * 4 * TL_SLOTS * SB);
     const unsigned lane16 = (unsigned)lane * 16u;
-    f32x4 bq[TL_D][2];
+    f32x4 bq[X6 ? 1 : TL_D][NP];       // ring_bf16's register sets, by slot ...
+    f32x4 bk[X6 ? TL_DK : 1][2][3];    // ... X6: ring_tail_x6's, by k-step (the same 24 fragments)
+    if constexpr (X6) {
 #pragma unroll
-    for (int k = 0; k < TL_D - 1; k++) {
-        bq[k][0] = buf_load4(wr, lane16, (unsigned)(k * 2048));
-        bq[k][1] = buf_load4(wr, lane16, (unsigned)(k * 2048 + 1024));
+        for (int k = 0; k < TL_DK - 1; k++)
+#pragma unroll
+            for (int g = 0; g < 2; g++)
+#pragma unroll
+                for (int p = 0; p < 3; p++) bk[k][g][p] = buf_load4(wr, lane16, (unsigned)((k * 2 + g) * SB + p * 1024));
+    } else {
+#pragma unroll
+        for (int k = 0; k < TL_D - 1; k++)
+#pragma unroll
+            for (int p = 0; p < NP; p++) bq[k][p] = buf_load4(wr, lane16, (unsigned)(k * SB + p * 1024));
     }
+#ifdef PV_REC_STAMPS
+    // phases of workgroup 0 (every wave adds; pv_debug_tail_stamps): slab sum, the four rings, the wait for the last wave's ring,
+    // the activations' write-back, output layer + softmax
+    unsigned long long st_acc[5] = {0, 0, 0, 0, 0}, st_last;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last) :: "memory");
+#endif
     // y = selu(sum of slabs + b1) (simple_model.py:57-59) -> split8 rows; four consecutive columns per thread and pass
     for (int i = tid; i < TL_ROWS * (TL_N / 4); i += 512) {
         const int row = i / (TL_N / 4), n4 = (i % (TL_N / 4)) * 4;
         int64_t b = b0 + row;
         if (b >= a.B) b = a.B - 1;
         f32x4 v = *reinterpret_cast<const f32x4*>(a.b1 + n4);
-        for (int s = 0; s < a.splits; s++) {
-            const f32x4 p = *reinterpret_cast<const f32x4*>(a.part + ((size_t)s * a.part_rows + b) * TL_N + n4);
+        if constexpr (X6) {
+#pragma unroll 11
+            for (int s = 0; s < a.splits; s++) {
+                const f32x4 p = *reinterpret_cast<const f32x4*>(a.part + ((size_t)s * a.part_rows + b) * TL_N + n4);
 #pragma unroll
-            for (int j = 0; j < 4; j++) v[j] += p[j];
-        }
-        bf16x4 hi, lo;
+                for (int j = 0; j < 4; j++) v[j] += p[j];
+            }
+            f32x4 y;
+            bf16x4 x1, x2;
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const float y = seluf_(v[j]);
-            hi[j] = (__bf16)y;
-            lo[j] = (__bf16)(y - (float)hi[j]);
+            for (int j = 0; j < 4; j++) {
+                y[j] = seluf_(v[j]);
+                __bf16 p1, p2;
+                split3_rest(y[j], p1, p2);
+                x1[j] = p1; x2[j] = p2;
+            }
+            *reinterpret_cast<f32x4*>(tile + row * TL_HS + n4 * 4) = y;
+            unsigned char* p = tile + row * TL_HS + C::H12 + split8_off((unsigned)n4);
+            *reinterpret_cast<bf16x4*>(p) = x1;
+            *reinterpret_cast<bf16x4*>(p + 16) = x2;
+        } else {
+            for (int s = 0; s < a.splits; s++) {
+                const f32x4 p = *reinterpret_cast<const f32x4*>(a.part + ((size_t)s * a.part_rows + b) * TL_N + n4);
+#pragma unroll
+                for (int j = 0; j < 4; j++) v[j] += p[j];
+            }
+            bf16x4 hi, lo;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const float y = seluf_(v[j]);
+                hi[j] = (__bf16)y;
+                lo[j] = (__bf16)(y - (float)hi[j]);
+            }
+            unsigned char* p = tile + row * TL_HS + split8_off((unsigned)n4);
+            *reinterpret_cast<bf16x4*>(p) = hi;
+            *reinterpret_cast<bf16x4*>(p + 16) = lo;
         }
-        unsigned char* p = tile + row * TL_HS + split8_off((unsigned)n4);
-        *reinterpret_cast<bf16x4*>(p) = hi;
-        *reinterpret_cast<bf16x4*>(p + 16) = lo;
     }
     __syncthreads();
+    RSTAMP(0)
     const unsigned char* a_h = tile + (lane & 31) * TL_HS + rg * 32;
     auto no_hook = [](int) {};
     auto layer = [&](auto L) {   // linear_(2 + L) + SELU (:61-76), in place
         constexpr int LI = decltype(L)::value;
-        f32x16 acc[2][2];
+        f32x16 acc[MT][2];
 #pragma unroll
         for (int g = 0; g < 2; g++) {
             const float bv = a.b[LI][64 * wv + 32 * g + (lane & 31)];
 #pragma unroll
-            for (int m = 0; m < 2; m++)
+            for (int m = 0; m < MT; m++)
 #pragma unroll
                 for (int e = 0; e < 16; e++) acc[m][g][e] = bv;
         }
-        ring_bf16<2, 2, 2, TL_D, 4 * TL_SLOTS, LI * TL_SLOTS, TL_KS, false>(acc, a_h, 32 * TL_HS, wr, bq, lane16, no_hook);
+        if constexpr (X6) ring_tail_x6<TL_DK, 4 * TL_KS, LI * TL_KS, TL_KS, C::H12>(acc, a_h, wr, bk, lane16);
+        else ring_bf16<2, MT, 2, TL_D, 4 * TL_SLOTS, LI * TL_SLOTS, TL_KS, false>(acc, a_h, 32 * TL_HS, wr, bq, lane16, no_hook);
+        RSTAMP(1)
         __syncthreads();   // every wave has read the whole tile
+        RSTAMP(2)
 #pragma unroll
-        for (int m = 0; m < 2; m++)
+        for (int m = 0; m < MT; m++)
 #pragma unroll
             for (int g = 0; g < 2; g++)
 #pragma unroll
                 for (int e = 0; e < 16; e++) {
                     const int row = 32 * m + 8 * (e >> 2) + (e & 3) + 4 * rg;
+                    const unsigned col = (unsigned)(64 * wv + 32 * g + (lane & 31));
                     const float y = seluf_(acc[m][g][e]);
-                    const __bf16 hi = (__bf16)y;
-                    const __bf16 lo = (__bf16)(y - (float)hi);
-                    unsigned char* p = tile + row * TL_HS + split8_off((unsigned)(64 * wv + 32 * g + (lane & 31)));
-                    *reinterpret_cast<__bf16*>(p) = hi;
-                    *reinterpret_cast<__bf16*>(p + 16) = lo;
+                    if constexpr (X6) {
+                        *reinterpret_cast<float*>(tile + row * TL_HS + col * 4u) = y;
+                        __bf16 p1, p2;
+                        split3_rest(y, p1, p2);
+                        unsigned char* p = tile + row * TL_HS + C::H12 + split8_off(col);
+                        *reinterpret_cast<__bf16*>(p) = p1;
+                        *reinterpret_cast<__bf16*>(p + 16) = p2;
+                    } else {
+                        const __bf16 hi = (__bf16)y;
+                        const __bf16 lo = (__bf16)(y - (float)hi);
+                        unsigned char* p = tile + row * TL_HS + split8_off(col);
+                        *reinterpret_cast<__bf16*>(p) = hi;
+                        *reinterpret_cast<__bf16*>(p + 16) = lo;
+                    }
                 }
         __syncthreads();
+        RSTAMP(3)
     };
     layer(std::integral_constant<int, 0>());
     layer(std::integral_constant<int, 1>());
@@ -1079,11 +1201,22 @@ __global__ __launch_bounds__(512, 1) void k_tail_bf16(TailBfArgs a) {
         for (int p = pair; p < TL_ROWS * 3; p += 64) {
             const int row = p / 3, cls = p - row * 3;
             float s = 0.0f;
-            for (int k8 = sub; k8 < TL_N / 8; k8 += 8) {   // one group of 8 columns: 8 hi then 8 lo
-                const bf16x8 hi = *reinterpret_cast<const bf16x8*>(tile + row * TL_HS + k8 * 32);
-                const bf16x8 lo = *reinterpret_cast<const bf16x8*>(tile + row * TL_HS + k8 * 32 + 16);
+            if constexpr (X6) {   // k_head_tail's sum: k = sub, sub + 8, ... over the fp32 part of the row
+                // (unrolled: the 64 weight loads of a pair leave together; as a loop every one of them was a round trip to the
+                // cache in front of its FMA: 143 -> 134 us per launch at 8192 windows)
+                const float* src = reinterpret_cast<const float*>(tile + row * TL_HS);
+                float wk[TL_N / 8];
 #pragma unroll
-                for (int j = 0; j < 8; j++) s += ((float)hi[j] + (float)lo[j]) * a.wo[cls * TL_N + k8 * 8 + j];
+                for (int i = 0; i < TL_N / 8; i++) wk[i] = a.wo[cls * TL_N + sub + 8 * i];
+#pragma unroll
+                for (int i = 0; i < TL_N / 8; i++) s = __builtin_fmaf(src[sub + 8 * i], wk[i], s);
+            } else {
+                for (int k8 = sub; k8 < TL_N / 8; k8 += 8) {   // one group of 8 columns: 8 hi then 8 lo
+                    const bf16x8 hi = *reinterpret_cast<const bf16x8*>(tile + row * TL_HS + k8 * 32);
+                    const bf16x8 lo = *reinterpret_cast<const bf16x8*>(tile + row * TL_HS + k8 * 32 + 16);
+#pragma unroll
+                    for (int j = 0; j < 8; j++) s += ((float)hi[j] + (float)lo[j]) * a.wo[cls * TL_N + k8 * 8 + j];
+                }
             }
             s += __shfl_xor(s, 4, 64);
             s += __shfl_xor(s, 2, 64);
@@ -1106,8 +1239,12 @@ __global__ __launch_bounds__(512, 1) void k_tail_bf16(TailBfArgs a) {
             a.probs[b * 3 + 2] = bad ? nanv : e2 * inv;
         }
     }
+#ifdef PV_REC_STAMPS
+    RSTAMP(4)
+    if (blockIdx.x == 0 && lane == 0)
+        for (int i = 0; i < 5; i++) atomicAdd(&g_tail_stamps[i], st_acc[i]);
+#endif
 }
-constexpr size_t LDS_TAIL_BF = (size_t)TL_ROWS * TL_HS;
 
 }  // namespace
 
@@ -1137,15 +1274,18 @@ int pv_pack_gru16_bf16(const pv_rnn_dir* dirs, int kx, unsigned char** d_wp, uns
     return rc || wx.empty() ? rc : pv_dev_upload(wx, d_wx, owned);
 }
 
-int pv_pack_tail_bf16(const float* const* w, unsigned char** d_wp, std::vector<void*>& owned) {
+int pv_pack_tail_bf16(const float* const* w, unsigned char** d_wp, std::vector<void*>& owned, int pieces) {
     static_assert(TL_N == PV_PACK_HEAD_N, "pack_tail_bf16 packs 512 x 512 layers");
+    PV_CHECK(pieces == 2 || pieces == 3, PV_ERR_INVALID, "two or three pieces");
     std::vector<uint16_t> wp;
-    pack_tail_bf16(w, wp);
+    if (pieces == 3) pack_tail_x6(w, wp);
+    else pack_tail_bf16(w, wp);
     return pv_dev_upload(wp, d_wp, owned);
 }
 
 int pv_tail_bf16_prepare() {
-    PV_HIP(hipFuncSetAttribute((const void*)k_tail_bf16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_TAIL_BF));
+    PV_HIP(hipFuncSetAttribute((const void*)k_tail_bf16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TailCfg<false>::LDS));
+    PV_HIP(hipFuncSetAttribute((const void*)k_tail_bf16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TailCfg<true>::LDS));
     return PV_OK;
 }
 
@@ -1155,8 +1295,10 @@ int pv_tail_bf16_async(pv_ctx* ctx, const pv_tail_desc& d, hipStream_t st) {
     a.part = d.part; a.splits = d.splits; a.part_rows = d.part_rows; a.b1 = d.b1; a.wp = d.wp;
     for (int i = 0; i < 4; i++) a.b[i] = d.b[i];
     a.wo = d.wo; a.bo = d.bo; a.probs = d.probs; a.B = d.B; a.epoch = d.epoch; a.err = d.err;
-    pv_prof_scope ps(ctx, "k_tail_bf16", st);
-    k_tail_bf16<<<(unsigned)((d.B + TL_ROWS - 1) / TL_ROWS), 512, LDS_TAIL_BF, st>>>(a);
+    // the six-term form stands in for a 32-row k_head_tail of the split-6 chain and keeps its profile scope
+    pv_prof_scope ps(ctx, d.x6 ? "k_head_tail" : "k_tail_bf16", st);
+    if (d.x6) k_tail_bf16<true><<<(unsigned)((d.B + TailCfg<true>::ROWS - 1) / TailCfg<true>::ROWS), 512, TailCfg<true>::LDS, st>>>(a);
+    else k_tail_bf16<false><<<(unsigned)((d.B + TailCfg<false>::ROWS - 1) / TailCfg<false>::ROWS), 512, TailCfg<false>::LDS, st>>>(a);
     PV_HIP(hipGetLastError());
     return PV_OK;
 }
@@ -1392,6 +1534,14 @@ extern "C" int pv_debug_rec_stamps(unsigned long long* out5) {
     PV_HIP(hipDeviceSynchronize());
     PV_HIP(hipMemcpyFromSymbol(out5, HIP_SYMBOL(g_rec_stamps), 5 * sizeof(unsigned long long)));
     PV_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_rec_stamps), z, sizeof z));
+    return PV_OK;
+}
+// k_tail_bf16: cycle sums of workgroup 0's phases (all its waves added up) since the last call
+extern "C" int pv_debug_tail_stamps(unsigned long long* out5) {
+    unsigned long long z[5] = {0, 0, 0, 0, 0};
+    PV_HIP(hipDeviceSynchronize());
+    PV_HIP(hipMemcpyFromSymbol(out5, HIP_SYMBOL(g_tail_stamps), sizeof z));
+    PV_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_tail_stamps), z, sizeof z));
     return PV_OK;
 }
 // {s_memtime ticks, s_memrealtime ticks} of the step loops of workgroup 0 (all its waves added up) since the stamps were last
