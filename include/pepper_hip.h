@@ -218,7 +218,9 @@ typedef struct pv_polish_out {
     int64_t n_chunks;       /* out: chunks produced (or needed on PV_ERR_CAPACITY) */
     int64_t n_rows;         /* out: flat rows produced (or needed) */
     uint16_t* depth;        /* optional [chunk_capacity][seq_length] read depth of every row (below); NULL: nothing is written
-                             * and nothing else changes. The last member, so the offsets above are those of earlier builds */
+                             * and nothing else changes. Behind the members of earlier builds, so their offsets stay */
+    uint16_t* counts;       /* optional [chunk_capacity][seq_length][10] raw counts of every row (below), 4-byte aligned; NULL:
+                             * nothing is written and nothing else changes. The last member, so the offsets above stay */
 } pv_polish_out;
 /* depth: for a base row (index 0) at position p, the sum of the column's ten counts before normalisation: the reads that hold
  * a base or a deleted column (D / N / P) at p, exactly as the builder counts them for the ten planes (so reads of mapping
@@ -227,7 +229,16 @@ typedef struct pv_polish_out {
  * position, a padding row 0. Values are clamped to 65535 (unreachable: a region holds at most 32767 reads). images,
  * position, index, region, chunk_id and the counters are byte for byte those of a call with depth == NULL. The plane is
  * gathered with the chunk rows, so it needs the chunk arrays; the flat arrays have no depth of their own. The library reads
- * the member in every call that takes the struct: zero the struct before filling it, as for every struct of this header. */
+ * the member in every call that takes the struct: zero the struct before filling it, as for every struct of this header.
+ * counts: for a base row (index 0), the column's ten counts before normalisation, in the order of the image's ten features:
+ * 0-3 A,C,G,T on reverse-strand reads, 4-7 A,C,G,T on forward-strand reads, 8 / 9 other or deleted on reverse / forward
+ * reads (a read byte that is not ACGT after upper-casing, an N for instance, and every deleted column D / N / P). For an
+ * insert row, that row's own ten counts: the reads that hold a base in this insert row, by base and strand (8 / 9: an
+ * inserted byte that is not ACGT). A padding row is all zero. Reads of mapping quality 0 are left out, as in the images.
+ * Each value is clamped to 65535 (unreachable, as for depth). Invariant: on a base row the ten counts sum to the row's
+ * depth (wherever no clamp is met, which is everywhere in a region of at most 32767 reads). Every other output of the call (images, position, index, region, chunk_id, the counters, and depth where it was
+ * asked for) is byte for byte that of a call with counts == NULL. Like depth, the plane is gathered with the chunk rows and
+ * the flat arrays have none; the host form and the device form both fill it. */
 
 /* HOST buffers in and out. */
 int pv_polish_summarize_regions(pv_ctx* ctx, const pv_batch_in* in, int seq_length, int seq_overlap, pv_polish_out* out);
@@ -334,6 +345,39 @@ int pv_polish_edits(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, 
                     const uint8_t* row_qual, const int64_t* region_start, const int64_t* ref_off, const uint8_t* ref,
                     int32_t n_regions, int seq_length, int seq_overlap, int64_t* region_edit_off, pv_polish_edit* edits,
                     int64_t edit_capacity, int64_t* counts);
+
+/* The read evidence of every edit: pv_polish_edits[_dev] with one 8-byte record beside every edit record, taken from the
+ * depth and the raw counts of the edit's own chunk row (pv_polish_out.depth and .counts, which the builder fills on request).
+ * Write c[f] for the ten counts of that row, u for the upper-cased draft byte, k(x) = 0..3 for x in A, C, G, T:
+ *   substitution to base b: alt_rev = c[k(b)], alt_fwd = c[4 + k(b)], ref = c[k(u)] + c[4 + k(u)] if u is in ACGT, else 0;
+ *   deletion:               alt_rev = c[8],    alt_fwd = c[9],        ref as for a substitution. Planes 8 and 9 also count
+ *                           read bytes that are not ACGT (an N in a read), so a deletion's support includes those reads;
+ *   inserted base b:        alt_rev = c[k(b)], alt_fwd = c[4 + k(b)] of the insert row's own counts,
+ *                           ref = max(0, depth - sum of c[0..9]): the reads over the anchor that hold nothing in this
+ *                           insert row.
+ * depth is chunks->depth of the edited column (an insert column carries its anchor's); ref is clamped to 65535. */
+typedef struct pv_polish_evidence {   /* 8 bytes, little-endian; evidence[i] belongs to edits[i] */
+    uint16_t depth;
+    uint16_t ref;      /* reads that spell the draft there */
+    uint16_t alt_fwd;  /* forward-strand reads that spell the edit */
+    uint16_t alt_rev;  /* reverse-strand reads that spell the edit */
+} pv_polish_evidence;
+/* Arguments, edits, region_edit_off, d_counts, statuses and their precedence: those of pv_polish_edits_dev, byte for byte,
+ * with and without row_qual. evidence [edit_capacity], 8-byte aligned. chunks->depth == NULL or chunks->counts == NULL with
+ * n_chunks > 0, and a misaligned evidence, are refused with PV_ERR_INVALID by the call itself. Under any status but PV_OK no
+ * evidence record is written. The counts row and the depth are loaded for edit columns only, after the classification; a
+ * record leaves as one 8-byte store. Three launches (the count pass and the scan are those of pv_polish_edits_dev), no
+ * global atomics, no host synchronisation; capturable. */
+int pv_polish_edits_evidence_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                                 const uint8_t* row_qual, const int64_t* region_start, const int64_t* ref_off,
+                                 const uint8_t* ref, int32_t n_regions, int seq_length, int seq_overlap,
+                                 int64_t* region_edit_off, pv_polish_edit* edits, pv_polish_evidence* evidence,
+                                 int64_t edit_capacity, int64_t* d_counts, void* stream);
+/* HOST buffers in and out (chunks->depth and chunks->counts too); otherwise as pv_polish_edits. */
+int pv_polish_edits_evidence(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                             const uint8_t* row_qual, const int64_t* region_start, const int64_t* ref_off, const uint8_t* ref,
+                             int32_t n_regions, int seq_length, int seq_overlap, int64_t* region_edit_off, pv_polish_edit* edits,
+                             pv_polish_evidence* evidence, int64_t edit_capacity, int64_t* counts);
 
 /* The polisher's minimum depth: where too few reads stand behind a row, its label is rewritten to spell the draft, before
  * the stitch, so that pv_polish_stitch[_qual] and pv_polish_edits on the rewritten labels keep the draft there (FASTA, FASTQ

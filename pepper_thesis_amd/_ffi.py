@@ -157,12 +157,17 @@ class pv_polish_out(C.Structure):
         ("n_chunks", C.c_int64),
         ("n_rows", C.c_int64),
         ("depth", C.c_void_p),
+        ("counts", C.c_void_p),
     ]
 
 
 class pv_polish_edit(C.Structure):
     _fields_ = [("position", C.c_int64), ("index", C.c_int32), ("kind", C.c_uint8), ("draft", C.c_uint8), ("base", C.c_uint8),
                 ("qual", C.c_uint8)]
+
+
+class pv_polish_evidence(C.Structure):
+    _fields_ = [("depth", C.c_uint16), ("ref", C.c_uint16), ("alt_fwd", C.c_uint16), ("alt_rev", C.c_uint16)]
 
 
 class pv_realign_out(C.Structure):
@@ -272,6 +277,12 @@ SYMBOLS = [
     ("pv_polish_edits", C.c_int,
      [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int,
       C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("pv_polish_edits_evidence_dev", C.c_int,
+     [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int,
+      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("pv_polish_edits_evidence", C.c_int,
+     [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int,
+      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("pv_polish_mask_low_depth_dev", C.c_int,
      [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int,
       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

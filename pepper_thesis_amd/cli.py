@@ -171,6 +171,10 @@ def polish_parser(ap=None):
                     help="also write <output_file>/_pepper_polished.edits.vcf.gz (+ .tbi): every substitution, insertion and "
                          "deletion the polisher made in the draft, with --qualities each with its quality (opt-in; one device; "
                          "the FASTA is unchanged)")
+    ap.add_argument("--evidence", action="store_true", default=False,
+                    help="with --edits: every VCF record also carries DP (reads over it), AD (reads that spell the draft, reads "
+                         "that spell the edit), SAF and SAR (the edit's reads by strand) of its weakest column, from the image "
+                         "builder's raw counts (opt-in; one device; needs --edits; FASTA and the other VCF columns are unchanged)")
     ap.add_argument("--min_depth", type=int, default=0,
                     help="keep the draft wherever fewer than this many reads cover a column (0..65535; 0, the default, is off): "
                          "the network's label there is replaced by the draft base before the stitch, and regions without "

@@ -281,6 +281,8 @@ extern "C" int pv_polish_summarize_regions(pv_ctx* ctx, const pv_batch_in* in, i
     if ((rc = pv_get(ctx, "pout.chunk_id", (size_t)ccap + 1, &dout.chunk_id))) return rc;
     if (out->depth)
         if ((rc = pv_get(ctx, "pout.depth", (ccap + 1) * L, &dout.depth))) return rc;
+    if (out->counts)
+        if ((rc = pv_get(ctx, "pout.counts", (ccap + 1) * L * 10, &dout.counts))) return rc;
     dout.flat_images = nullptr; dout.flat_position = nullptr; dout.flat_index = nullptr; dout.region_row_off = nullptr;
     if (out->flat_images) {
         PV_CHECK(out->flat_position && out->flat_index, PV_ERR_INVALID, "flat_position / flat_index missing");
@@ -319,6 +321,7 @@ extern "C" int pv_polish_summarize_regions(pv_ctx* ctx, const pv_batch_in* in, i
         PV_HIP(hipMemcpyAsync(out->region, dout.region, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         PV_HIP(hipMemcpyAsync(out->chunk_id, dout.chunk_id, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         if (out->depth) PV_HIP(hipMemcpyAsync(out->depth, dout.depth, n * L * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+        if (out->counts) PV_HIP(hipMemcpyAsync(out->counts, dout.counts, n * L * 10 * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
     }
     if (out->flat_images && out->n_rows > 0) {
         const size_t nr = (size_t)out->n_rows;

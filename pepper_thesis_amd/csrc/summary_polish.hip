@@ -248,7 +248,17 @@ __device__ __forceinline__ uint8_t polish_pixel(int32_t cnt, int32_t cov) {  // 
     return (uint8_t)(uint32_t)(int32_t)v;
 }
 
-// thread per column: its base row and its insert rows
+// ten counts -> the 20 bytes of a counts row (pv_polish_out.counts), clamped to uint16, as five dwords: the row is 4-byte aligned
+__device__ __forceinline__ uint32_t cnt16(int32_t v) { return (uint32_t)(v > 65535 ? 65535 : v); }
+__device__ __forceinline__ void store_counts_row(uint16_t* row, const int32_t* c) {
+    uint32_t* d = reinterpret_cast<uint32_t*>(row);
+#pragma unroll
+    for (int w = 0; w < 5; w++) d[w] = cnt16(c[2 * w]) | cnt16(c[2 * w + 1]) << 16;
+}
+
+// thread per column: its base row and its insert rows. COUNTS: also the raw counts of every row (a.flat_counts); the
+// instantiation without them is the kernel as it was
+template <bool COUNTS>
 __global__ __launch_bounds__(256) void k_polish_image(SumArgs a) {
     const int64_t col = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (col >= a.n_cols || a.diag[D_STATUS] != 0) return;
@@ -277,6 +287,12 @@ __global__ __launch_bounds__(256) void k_polish_image(SumArgs a) {
         a.flat_pos[row] = pos;
         a.flat_idx[row] = 0;
         if (a.flat_depth) a.flat_depth[row] = depth;
+        if (COUNTS) {
+            int32_t c[10];
+#pragma unroll
+            for (int f = 0; f < 10; f++) c[f] = a.pcnt[(int64_t)f * NC + col];
+            store_counts_row(a.flat_counts + row * 10, c);
+        }
     }
     for (int32_t ii = 0; ii < nl; ii++) {
         row++;
@@ -286,10 +302,12 @@ __global__ __launch_bounds__(256) void k_polish_image(SumArgs a) {
         a.flat_pos[row] = pos;
         a.flat_idx[row] = ii + 1;
         if (a.flat_depth) a.flat_depth[row] = depth;
+        if (COUNTS) store_counts_row(a.flat_counts + row * 10, a.ins_cnt + (ins0 + ii) * 10);
     }
 }
 
-// thread per (chunk, row): gather from the flat rows, or pad
+// thread per (chunk, row): gather from the flat rows, or pad. COUNTS: the counts row too, five dwords
+template <bool COUNTS>
 __global__ __launch_bounds__(256) void k_polish_chunks(SumArgs a) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (a.diag[D_STATUS] != 0) return;
@@ -311,12 +329,23 @@ __global__ __launch_bounds__(256) void k_polish_chunks(SumArgs a) {
         a.pout.position[t] = a.flat_pos[src];
         a.pout.index[t] = a.flat_idx[src];
         if (a.pout.depth) a.pout.depth[t] = a.flat_depth[src];
+        if (COUNTS) {
+            const uint32_t* cs = reinterpret_cast<const uint32_t*>(a.flat_counts + src * 10);
+            uint32_t* cd = reinterpret_cast<uint32_t*>(a.pout.counts + t * 10);
+#pragma unroll
+            for (int w = 0; w < 5; w++) cd[w] = cs[w];
+        }
     } else {
 #pragma unroll
         for (int f = 0; f < 10; f++) dst[f] = 0;
         a.pout.position[t] = -1;
         a.pout.index[t] = -1;
         if (a.pout.depth) a.pout.depth[t] = 0;
+        if (COUNTS) {
+            uint32_t* cd = reinterpret_cast<uint32_t*>(a.pout.counts + t * 10);
+#pragma unroll
+            for (int w = 0; w < 5; w++) cd[w] = 0;
+        }
     }
 }
 
@@ -362,6 +391,10 @@ int polish_launch(pv_ctx* ctx, const pv_batch_in* in, int64_t n_reads, int64_t n
     }
     if (out->depth)   // the flat depth is workspace either way: pv_polish_out has no flat form of it
         if ((rc = pv_get(ctx, "pol.flat_depth", (size_t)(a.flat_cap > 0 ? a.flat_cap : 1), &a.flat_depth))) return rc;
+    if (out->counts) {   // and so is the flat counts plane
+        PV_CHECK(((uintptr_t)out->counts & 3) == 0, PV_ERR_INVALID, "counts is not aligned to 4 bytes");
+        if ((rc = pv_get(ctx, "pol.flat_counts", (size_t)(a.flat_cap > 0 ? a.flat_cap : 1) * 10, &a.flat_counts))) return rc;
+    }
 
     pv_prof_scope ps_all(ctx, "polish_pipeline", st);
     front_init(a, st);
@@ -373,11 +406,16 @@ int polish_launch(pv_ctx* ctx, const pv_batch_in* in, int64_t n_reads, int64_t n
     k_polish_insoff<<<(unsigned)n_blk, 1024, 0, st>>>(a);
     k_polish_regions<<<1, 1, 0, st>>>(a);
     if (n_cigar > 0) { pv_prof_scope ps(ctx, "k_polish_insert", st); k_polish_insert<<<grid_for(n_cigar, 256), 256, 0, st>>>(a); }
-    { pv_prof_scope ps(ctx, "k_polish_image", st); k_polish_image<<<grid_for(n_cols, 256), 256, 0, st>>>(a); }
+    {
+        pv_prof_scope ps(ctx, "k_polish_image", st);
+        if (a.flat_counts) k_polish_image<true><<<grid_for(n_cols, 256), 256, 0, st>>>(a);
+        else k_polish_image<false><<<grid_for(n_cols, 256), 256, 0, st>>>(a);
+    }
     if (out->chunk_capacity > 0 && out->images) {
         PV_CHECK(out->position && out->index && out->region && out->chunk_id, PV_ERR_INVALID, "chunk output arrays missing");
         pv_prof_scope ps(ctx, "k_polish_chunks", st);
-        k_polish_chunks<<<grid_for(out->chunk_capacity * seq_length, 256), 256, 0, st>>>(a);
+        if (a.flat_counts) k_polish_chunks<true><<<grid_for(out->chunk_capacity * seq_length, 256), 256, 0, st>>>(a);
+        else k_polish_chunks<false><<<grid_for(out->chunk_capacity * seq_length, 256), 256, 0, st>>>(a);
     }
     if (out->region_row_off)
         PV_HIP(hipMemcpyAsync(out->region_row_off, a.reg_rows, (size_t)(G + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));

@@ -140,6 +140,7 @@ struct SumArgs {
     int64_t* flat_pos;
     int32_t* flat_idx;
     uint16_t* flat_depth; // [flat_cap] or null: wanted only with pout.depth
+    uint16_t* flat_counts; // [flat_cap][10] or null: wanted only with pout.counts
     int64_t flat_cap;
     pv_polish_out pout;
 };

@@ -92,8 +92,11 @@ class DeviceOut:
 class DevicePolishOut:
     """Caller-owned chunk arrays of pv_polish_out in HBM (the polisher's image batches, input of forward_p2_dev)."""
 
-    def __init__(self, chunk_capacity: int, seq_length: int = 1000, seq_overlap: int = 50, device="cuda:0", depth: bool = False):
-        """depth: also carry the read-depth plane uint16 [chunk_capacity, seq_length] (pv_polish_out.depth), which the
+    def __init__(self, chunk_capacity: int, seq_length: int = 1000, seq_overlap: int = 50, device="cuda:0", depth: bool = False,
+                 counts: bool = False):
+        """counts: also carry the raw counts plane uint16 [chunk_capacity, seq_length, 10] (pv_polish_out.counts), which the
+        builder fills and pv_polish_edits_evidence_dev reads (as int16 bits, like depth).
+        depth: also carry the read-depth plane uint16 [chunk_capacity, seq_length] (pv_polish_out.depth), which the
         builder fills and pv_polish_mask_low_depth_dev reads; without it the struct's pointer is null and nothing changes"""
         self.capacity, self.seq_length, self.seq_overlap = int(chunk_capacity), int(seq_length), int(seq_overlap)
         self.images = torch.zeros((chunk_capacity, seq_length, 10), dtype=torch.uint8, device=device)
@@ -110,6 +113,8 @@ class DevicePolishOut:
         # (an int16 tensor that holds the plane's uint16 bits: torch's unsigned 16-bit type has creation and copies only)
         self.depth = torch.zeros((chunk_capacity, seq_length), dtype=torch.int16, device=device) if depth else None
         c.depth = self.depth.data_ptr() if depth else None
+        self.row_counts = torch.zeros((chunk_capacity, seq_length, 10), dtype=torch.int16, device=device) if counts else None
+        c.counts = self.row_counts.data_ptr() if counts else None
         self.c = c
 
     def n_chunks(self) -> int:
@@ -121,6 +126,14 @@ class DevicePolishOut:
     def depth_numpy(self, n: int) -> np.ndarray:
         """the depth plane of the first n chunks on the host, uint16 [n, seq_length]"""
         return self.depth[:n].cpu().numpy().view(np.uint16)
+
+    def row_counts_numpy(self, n: int) -> np.ndarray:
+        """the counts plane of the first n chunks on the host, uint16 [n, seq_length, 10]"""
+        return self.row_counts[:n].cpu().numpy().view(np.uint16)
+
+    def set_row_counts(self, counts: np.ndarray):
+        """a host counts plane uint16 [n, seq_length, 10] into the first n chunks"""
+        self.row_counts[:len(counts)].copy_(torch.from_numpy(np.ascontiguousarray(counts, np.uint16).view(np.int16)))
 
     def set_depth(self, depth: np.ndarray):
         """a host depth plane uint16 [n, seq_length] into the first n chunks"""

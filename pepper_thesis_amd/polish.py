@@ -9,7 +9,7 @@ prediction HDF5 files. Here each batch of regions goes through
 without leaving HBM; only the region offsets and the polished bases (one byte per base) come back to the host.
 
   python -m pepper_thesis_amd polish -b reads.bam -f draft.fa -m model.pkl -o out/polished [-t 5] [-r ctg:start-end] [--bf16]
-      [--realign] [--gpu_decode] [--qualities] [--edits] [--min_depth N] [--min_qual Q] [-hp]
+      [--realign] [--gpu_decode] [--qualities] [--edits [--evidence]] [--min_depth N] [--min_qual Q] [-hp]
 
 --gpu_decode (opt-in) replaces the first stage: reader threads only plan blocks and fetch draft bytes, and the BAM is inflated,
 decoded and clipped on the device (gpu_decode.py; _decoded_pieces below). Same FASTA.
@@ -25,6 +25,13 @@ in the draft. Behind the stitch, on the same stream, pv_polish_edits_dev compare
 consults with the draft bytes of the batch and leaves one 16-byte record per substitution, deletion or inserted base (with
 --qualities: with the column's row quality); the region offsets and the records come back, and polish_edits.py joins them
 into VCF records per contig. The FASTA (and FASTQ) are byte for byte those of a run without the flag.
+
+--evidence (opt-in, one device, needs --edits) gives every VCF record its read support. The builder also hands out the depth and
+the ten raw counts of every chunk row (pv_polish_out.depth, .counts), pv_polish_edits_evidence_dev runs in place of the edits
+call and leaves one 8-byte record beside every edit record (depth, reads that spell the draft, reads that spell the edit on
+either strand; the rule is in include/pepper_hip.h), 8 more bytes per edit come back, and polish_edits.py writes the numbers
+of each record's weakest column as INFO (DP, AD, SAF, SAR). FASTA, FASTQ and the other VCF columns are byte for byte those of
+a run without the flag.
 
 --min_depth N (opt-in, one device; 0 = off) keeps the draft wherever fewer than N reads stand behind a column. The builder
 also hands out the read depth of every chunk row (pv_polish_out.depth), and between the network (and the row qualities) and
@@ -206,12 +213,16 @@ class ChainResult(NamedTuple):
     # --min_qual: (chunk rows of edits taken back, rows of pinned runs below the threshold: draft byte not ACGT), carried the
     # same way; with_filtered()
     filtered = None
+    # --evidence: polish_edits.EVIDENCE_DTYPE records, evidence[i] beside edits[i], carried the same way; with_evidence()
+    evidence = None
 
     def region(self, g: int) -> tuple:
-        """region g's share: (bases, qual or None, edits or None)"""
+        """region g's share: (bases, qual or None, edits or None), and behind them its evidence records where the result
+        carries any"""
         a, b = self.region_off[g], self.region_off[g + 1]
-        return (self.bases[a:b], None if self.qual is None else self.qual[a:b],
-                None if self.edits is None else self.edits[self.edit_off[g]:self.edit_off[g + 1]])
+        share = (self.bases[a:b], None if self.qual is None else self.qual[a:b],
+                 None if self.edits is None else self.edits[self.edit_off[g]:self.edit_off[g + 1]])
+        return share if self.evidence is None else share + (self.evidence[self.edit_off[g]:self.edit_off[g + 1]],)
 
 
 class HapChainResult(NamedTuple):
@@ -232,20 +243,28 @@ def hp_path(path: str, haplotype: int) -> str:
 
 
 class _MaskedChainResult(ChainResult):
-    """a ChainResult with the instance attributes `masked` and `filtered`"""
+    """a ChainResult with the instance attributes `masked`, `filtered` and `evidence`"""
 
 
 def with_masked(res: ChainResult, masked: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a minimum-depth chain in its attribute `masked`"""
     out = _MaskedChainResult(*res)
-    out.masked, out.filtered = (int(masked[0]), int(masked[1])), res.filtered
+    out.masked, out.filtered, out.evidence = (int(masked[0]), int(masked[1])), res.filtered, res.evidence
     return out
 
 
 def with_filtered(res: ChainResult, filtered: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a minimum-quality chain in its attribute `filtered`"""
     out = _MaskedChainResult(*res)
-    out.masked, out.filtered = res.masked, (int(filtered[0]), int(filtered[1]))
+    out.masked, out.filtered, out.evidence = res.masked, (int(filtered[0]), int(filtered[1])), res.evidence
+    return out
+
+
+def with_evidence(res: ChainResult, evidence: np.ndarray) -> ChainResult:
+    """res, carrying the evidence records of an evidence chain (one per edit record) in its attribute `evidence`"""
+    assert res.edits is not None and len(evidence) == len(res.edits), (len(evidence), res.edits is None)
+    out = _MaskedChainResult(*res)
+    out.masked, out.filtered, out.evidence = res.masked, res.filtered, evidence
     return out
 
 
@@ -257,6 +276,22 @@ class Piece(NamedTuple):
     bases: object
     qual: Optional[bytes] = None
     edits: Optional[np.ndarray] = None
+    # --evidence: one polish_edits.EVIDENCE_DTYPE record beside every edit record. Not a tuple field, as ChainResult's
+    # counts are none: the piece keeps its six for everything that builds or unpacks it; piece_of() attaches it
+    evidence = None
+
+
+class _EvidencePiece(Piece):
+    """a Piece with the instance attribute `evidence`"""
+
+
+def piece_of(w, share: tuple) -> Piece:
+    """the Piece of Work w from its share of a ChainResult (ChainResult.region): (bases, qual, edits[, evidence])"""
+    if len(share) == 3:
+        return Piece(w.contig, w.start, w.index, *share)
+    out = _EvidencePiece(w.contig, w.start, w.index, *share[:3])
+    out.evidence = share[3]
+    return out
 
 
 def merge_pieces(pieces, part: int = 3) -> Dict[str, bytes]:
@@ -301,11 +336,17 @@ class _DeviceChain:
     the row qualities are computed whether or not the chain was made for qualities and, behind the mask and before the
     stitch, every run of adjacent edits whose lowest quality is below min_qual is taken back in place (the result's
     filtered). use_hp: run / run_decoded return a HapChainResult: the batch is selected on the device by haplotype
-    (pv_batch_select_hp_dev) and everything from the realigner on runs once per haplotype on the selected reads."""
+    (pv_batch_select_hp_dev) and everything from the realigner on runs once per haplotype on the selected reads.
+    evidence (needs edits): the builder also fills the depth and the counts plane, and pv_polish_edits_evidence_dev runs in
+    place of the edits call, so every edit record gets its read support (the result's evidence)."""
 
     def __init__(self, ctx, own_ctx: bool = False, qualities: bool = False, edits: bool = False, min_depth: int = 0,
-                 min_qual: int = 0, use_hp: bool = False):
+                 min_qual: int = 0, use_hp: bool = False, evidence: bool = False):
         import torch
+        if evidence and not edits:
+            raise ValueError("a chain with evidence needs edits: the evidence records stand beside the edit records")
+        self.evidence = bool(evidence)
+        self.ev_buf = None
         self.use_hp = bool(use_hp)
         self.sel = None
         self.ctx, self.dev, self.own_ctx, self.qualities = ctx, "cuda:%d" % ctx.device_id, own_ctx, bool(qualities)
@@ -329,7 +370,7 @@ class _DeviceChain:
         import torch
         from .device import DevicePolishOut
         if self.dout is None or self.dout.capacity < chunks:
-            self.dout = DevicePolishOut(chunks, device=self.dev, depth=self.min_depth > 0)
+            self.dout = DevicePolishOut(chunks, device=self.dev, depth=self.min_depth > 0 or self.evidence, counts=self.evidence)
             self.labels = torch.zeros((chunks, 1000), dtype=torch.uint8, device=self.dev)
             self.seq = torch.zeros(chunks * 1000, dtype=torch.uint8, device=self.dev)
             if self.qualities or self.min_qual > 0:
@@ -339,6 +380,8 @@ class _DeviceChain:
                 self.qual = torch.zeros(chunks * 1000, dtype=torch.uint8, device=self.dev)
             if self.edits:   # one record per chunk row: capacity cannot run short
                 self.edit_buf = torch.zeros((chunks * 1000, 16), dtype=torch.uint8, device=self.dev)
+            if self.evidence:
+                self.ev_buf = torch.zeros((chunks * 1000, 8), dtype=torch.uint8, device=self.dev)
             torch.cuda.synchronize()   # the fills ran on torch's stream; the chain runs on the context's
 
     def _summarize(self, db, sizes, host_batch) -> int:
@@ -361,13 +404,16 @@ class _DeviceChain:
                 return n
             want = n
         import torch
-        out = polish_summarize(self.ctx, host_batch(), want_depth=self.min_depth > 0)
+        want_depth = self.min_depth > 0 or self.evidence
+        out = polish_summarize(self.ctx, host_batch(), want_depth=want_depth, **({"want_counts": True} if self.evidence else {}))
         n = len(out.chunk_id)
         self._ensure(n)
         for name in ("images", "position", "index", "region", "chunk_id"):
             getattr(self.dout, name)[:n].copy_(torch.from_numpy(getattr(out, name)))
-        if self.min_depth > 0:
+        if want_depth:
             self.dout.set_depth(out.depth)
+        if self.evidence:
+            self.dout.set_row_counts(out.counts)
         return n
 
     def _realign(self, db, host_batch, qmax: int, windows):
@@ -517,11 +563,12 @@ class _DeviceChain:
         """P2 [-> row qualities] [-> minimum-depth mask] [-> minimum-quality filter] -> stitch [-> edits] over the first n
         chunks of self.dout on the context's stream, one synchronize, then the read-back"""
         import torch
-        from .polish_edits import EDIT_DTYPE
+        from .polish_edits import EDIT_DTYPE, EVIDENCE_DTYPE
         if n == 0:   # nothing to launch: every plane this chain was made for, empty
             zero = np.zeros(n_regions + 1, np.int64)
             res = ChainResult(zero, b"", b"" if self.qualities else None)
             res = res._replace(edit_off=zero.copy(), edits=np.zeros(0, EDIT_DTYPE)) if self.edits else res
+            res = with_evidence(res, np.zeros(0, EVIDENCE_DTYPE)) if self.evidence else res
             res = with_masked(res, (0, 0)) if self.min_depth > 0 else res
             return with_filtered(res, (0, 0)) if self.min_qual > 0 else res
         d_acc, d_row_qual, d_qual = (t.data_ptr() for t in (self.acc, self.row_qual, self.qual)) if self.qualities else (0, 0, 0)
@@ -548,9 +595,14 @@ class _DeviceChain:
                                    self.seq.numel(), self.counts.data_ptr(), d_row_qual=d_row_qual, d_qual=d_qual)
         if self.edits:
             eoff = torch.empty(n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
-            self.ctx.polish_edits_dev(self.dout, n, d_labels, d_row_qual, d_ref_start, db.t["ref_off"].data_ptr(),
-                                      db.t["ref"].data_ptr(), n_regions, eoff.data_ptr(), self.edit_buf.data_ptr(),
-                                      self.edit_buf.shape[0], self.edit_counts.data_ptr())
+            if self.evidence:   # the edits call's twin: the same records, and each one's read support beside it
+                self.ctx.polish_edits_evidence_dev(self.dout, n, d_labels, d_row_qual, d_ref_start, db.t["ref_off"].data_ptr(),
+                                                   db.t["ref"].data_ptr(), n_regions, eoff.data_ptr(), self.edit_buf.data_ptr(),
+                                                   self.ev_buf.data_ptr(), self.edit_buf.shape[0], self.edit_counts.data_ptr())
+            else:
+                self.ctx.polish_edits_dev(self.dout, n, d_labels, d_row_qual, d_ref_start, db.t["ref_off"].data_ptr(),
+                                          db.t["ref"].data_ptr(), n_regions, eoff.data_ptr(), self.edit_buf.data_ptr(),
+                                          self.edit_buf.shape[0], self.edit_counts.data_ptr())
         self.ctx.synchronize()   # raises if a split GRU form timed out (its labels are then poisoned)
         masked = None
         if self.min_depth > 0:
@@ -579,18 +631,22 @@ class _DeviceChain:
         if status != _ffi.PV_OK:   # capacity cannot run short: a record for every chunk row
             raise _ffi.PepperHipError(status, "polisher edits: device status %d (chunk %d)" % (status, bad))
         res = res._replace(edit_off=eoff.cpu().numpy(), edits=self.edit_buf[:total].cpu().numpy().view(EDIT_DTYPE).reshape(-1))
+        if self.evidence:
+            res = with_evidence(res, self.ev_buf[:total].cpu().numpy().view(EVIDENCE_DTYPE).reshape(-1))
         return counted(res)
 
 
 def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int, qualities: bool = False,
-                      edits: bool = False, min_depth: int = 0, min_qual: int = 0, use_hp: bool = False) -> _DeviceChain:
+                      edits: bool = False, min_depth: int = 0, min_qual: int = 0, use_hp: bool = False,
+                      evidence: bool = False) -> _DeviceChain:
     """a context on `device` with the polisher weights loaded, and the chain on it (closing the chain closes the context).
     shared_device: other ranks use this GPU too, so the option is set before the first device call (the split GRU forms need
     co-resident workgroups and would time out, poisoning the labels). False leaves the create-time default (PV_SHARED_DEVICE).
     This is the default `open_chain` of run and polish_rank.run; CPU tests pass a stub with the same signature, whose result
     has run(batch, windows) -> ChainResult and close(). qualities, edits, min_depth, min_qual (each passed only when set):
     the chain of --qualities / --edits / --min_depth / --min_qual, whose results carry those planes and counts. use_hp
-    (passed only when set): the chain of -hp, whose run gives a HapChainResult."""
+    (passed only when set): the chain of -hp, whose run gives a HapChainResult. evidence (passed only when set): the chain of
+    --evidence, whose results carry an evidence record per edit record."""
     from .runtime import Context
     ctx = Context(device)
     try:
@@ -598,7 +654,7 @@ def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype:
             ctx.set_option("shared_device", 1)
         ctx.load_p2(state_dict, dtype)
         return _DeviceChain(ctx, own_ctx=True, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual,
-                            use_hp=use_hp)
+                            use_hp=use_hp, **({"evidence": True} if evidence else {}))
     except BaseException:
         ctx.close()
         raise
@@ -661,11 +717,11 @@ def kept_range(w: Work) -> Tuple[int, int]:
     return (w.start + 2 * MIN_IMAGE_OVERLAP + 1 if w.start > 0 else w.start), w.end
 
 
-def draft_pieces(fa, work: List[Work], pieces, qualities: bool, edits: bool) -> List[Piece]:
+def draft_pieces(fa, work: List[Work], pieces, qualities: bool, edits: bool, evidence: bool = False) -> List[Piece]:
     """`--min_depth N` with N >= 1: a region of the run that gave no piece has no reads, so all of it is below N and it keeps
     the draft: a piece of the upper-cased draft bytes of its kept range (N and IUPAC bytes as they are), quality 0 for each
-    base when the run carries qualities, no edits"""
-    from .polish_edits import EDIT_DTYPE
+    base when the run carries qualities, no edits and therefore (evidence: an empty plane of) no evidence"""
+    from .polish_edits import EDIT_DTYPE, EVIDENCE_DTYPE
     done = {p.index for p in pieces}
     out = []
     for w in work:
@@ -673,8 +729,8 @@ def draft_pieces(fa, work: List[Work], pieces, qualities: bool, edits: bool) -> 
         if w.index in done or last < first:
             continue
         bases = fa.get_reference_sequence(w.contig, first, last + 1).upper().encode()
-        out.append(Piece(w.contig, w.start, w.index, bases, bytes(len(bases)) if qualities else None,
-                         np.zeros(0, EDIT_DTYPE) if edits else None))
+        out.append(piece_of(w, (bases, bytes(len(bases)) if qualities else None, np.zeros(0, EDIT_DTYPE) if edits else None)
+                            + ((np.zeros(0, EVIDENCE_DTYPE),) if evidence else ())))
     return out
 
 
@@ -686,7 +742,7 @@ def _hap_pieces(T: dict, hres: HapChainResult, works) -> list:
     out = []
     for h, (res, has) in enumerate(zip(hres.results, hres.has_reads), 1):
         _count_masked(T, res)
-        out += [(h, Piece(w.contig, w.start, w.index, *res.region(g))) for g, w in enumerate(works) if has[g]]
+        out += [(h, piece_of(w, res.region(g))) for g, w in enumerate(works) if has[g]]
     return out
 
 
@@ -725,7 +781,7 @@ def polish_pieces(bam: str, fasta: str, work: List[Work], chain, batch_size: int
             out = _hap_pieces(T, res, [w for w, _ in items])
         else:
             _count_masked(T, res)
-            out = [Piece(w.contig, w.start, w.index, *res.region(g)) for g, (w, _) in enumerate(items)]
+            out = [piece_of(w, res.region(g)) for g, (w, _) in enumerate(items)]
         T["device_s"] += time.perf_counter() - t0
         T["batches"] += 1
         return out
@@ -791,7 +847,7 @@ def _decoded_pieces(bam, fasta, work, chain, batch_size, threads, realign, timer
                         continue
                     _count_masked(T, res)
                     for g, w in enumerate(ws):
-                        yield Piece(w.contig, w.start, w.index, *res.region(g))
+                        yield piece_of(w, res.region(g))
                 T["device_s"] += time.perf_counter() - t0
                 T["batches"] += 1
                 del parts
@@ -813,7 +869,7 @@ def decode_report(T: dict) -> str:
 def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region: Optional[str] = None, batch_size: int = 2048,
                  threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None,
                  realign: bool = False, chain=None, gpu_decode: bool = False, qualities: bool = False, edits: bool = False,
-                 min_depth: int = 0, min_qual: int = 0, use_hp: bool = False) -> str:
+                 min_depth: int = 0, min_qual: int = 0, use_hp: bool = False, evidence: bool = False) -> str:
     """-> path of the polished FASTA (use_hp: of haplotype 1's). batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
     realign: realign every read to the draft on the device before the builder, as the reference always does.
     chain: a chain with the weights already loaded (open_device_chain; the caller closes it), else one is made on `ctx`
@@ -828,7 +884,9 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
     min_qual >= 1: this function's own chain takes back the runs of edits below it (a chain passed in must have been made
     for it), and the VCF names the threshold.
     use_hp: one set of files per haplotype (hp_path) in place of the un-suffixed ones; this function's own chain selects the
-    reads by haplotype (a chain passed in must have been made with use_hp)."""
+    reads by haplotype (a chain passed in must have been made with use_hp).
+    evidence (with edits): every VCF record carries DP, AD, SAF and SAR of its weakest column (polish_edits.compose_records);
+    this function's own chain attaches the evidence (a chain passed in must have been made for it)."""
     from .bamio import BamHandler, FastaHandler
     from .runtime import Context
     t_start = time.perf_counter()
@@ -840,7 +898,10 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
         if ctx is None:
             ctx = own = Context(0)
         ctx.load_p2(state_dict, dtype)
-        chain = _DeviceChain(ctx, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual, use_hp=use_hp)
+        chain = _DeviceChain(ctx, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual, use_hp=use_hp,
+                             **({"evidence": True} if evidence else {}))
+    if evidence and not edits:
+        raise ValueError("polish_fused: evidence needs edits: the numbers go into the edits VCF")
     try:
         fa, bm = FastaHandler(fasta), BamHandler(bam)
         work, T["bases_in"] = polish_work(fa, bm, region)
@@ -861,14 +922,15 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
             outputs = [(0, out_path, list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode)))]
         vcfs = []
         for _, _, pieces in outputs:
-            for want, plane in ((qualities, "qual"), (edits, "edits")):
+            for want, plane in ((qualities, "qual"), (edits, "edits"), (evidence, "evidence")):
                 if want and pieces and getattr(pieces[0], plane) is None:
                     raise ValueError("polish_fused: the chain's results have no %s plane: it was not made for this run" % plane)
             if min_depth >= 1:
-                filled = draft_pieces(fa, work, pieces, qualities, edits)
+                filled = draft_pieces(fa, work, pieces, qualities, edits, *((True,) if evidence else ()))
                 T["draft_regions"] += len(filled)
                 pieces += filled
-            vcfs.append(_edits_vcf(fa, fasta, work, pieces, qualities, min_depth, min_qual) if edits else None)
+            vcfs.append(_edits_vcf(fa, fasta, work, pieces, qualities, min_depth, min_qual, *((True,) if evidence else ()))
+                        if edits else None)
     finally:
         if own is not None:
             own.close()
@@ -878,7 +940,11 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
             write_fastq(output_fastq_path(path), seqs, merge_pieces(pieces, part=4))
         if edits:
             from . import polish_edits
-            polish_edits.write_edits_vcf(polish_edits.output_vcf_path(path), *vcf, **({"haplotype": h} if h else {}))
+            polish_edits.write_edits_vcf(polish_edits.output_vcf_path(path), *vcf, **({"haplotype": h} if h else {}),
+                                         **({"evidence": True} if evidence else {}))
+            if evidence:   # records whose alt support (of their weakest column) stands on one strand only
+                T["one_strand_records"] = T.get("one_strand_records", 0) + sum(
+                    (r.evidence[2] == 0) != (r.evidence[3] == 0) for recs in vcf[4].values() for r in recs)
             T["edit_records"] = T.get("edit_records", 0) + sum(len(p.edits) for p in pieces)
             T["vcf_records"] = T.get("vcf_records", 0) + sum(len(r) for r in vcf[4].values())
         T["bases_out"] += sum(len(s) for s in seqs.values())
@@ -888,11 +954,13 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
     return outputs[0][1]
 
 
-def _edits_vcf(fa, fasta_path: str, work: List[Work], pieces, qualities: bool, min_depth: int = 0, min_qual: int = 0) -> tuple:
+def _edits_vcf(fa, fasta_path: str, work: List[Work], pieces, qualities: bool, min_depth: int = 0, min_qual: int = 0,
+               evidence: bool = False) -> tuple:
     """the pieces' edit records -> write_edits_vcf's arguments behind the path: (source, reference, contigs of the run with
     their lengths, read-free runs, VCF records per contig, min_depth, min_qual). Pieces of a contig are joined in region-start order,
     as merge_pieces joins the bases. A region without a piece gave no chunks: the FASTA omits its kept range
-    (kept_range) and a pepper_no_reads header line names it. With min_depth >= 1 every region has a piece (draft_pieces)."""
+    (kept_range) and a pepper_no_reads header line names it. With min_depth >= 1 every region has a piece (draft_pieces).
+    evidence: the pieces' evidence records are joined alike and the VCF records carry their weakest column's."""
     from . import polish_edits
     names = list(dict.fromkeys(w.contig for w in work))
     contigs = [(c, fa.get_chromosome_sequence_length(c)) for c in names]
@@ -901,13 +969,15 @@ def _edits_vcf(fa, fasta_path: str, work: List[Work], pieces, qualities: bool, m
         (w.contig,) + kept_range(w) for w in work if w.index not in done)
     by: Dict[str, list] = {}
     for p in pieces:
-        by.setdefault(p.contig, []).append((p.start, p.index, p.edits))
+        by.setdefault(p.contig, []).append((p.start, p.index, p.edits, p.evidence if evidence else None))
     records = {}
     for c, length in contigs:
         if c in by:
-            recs = np.concatenate([e for _, _, e in sorted(by[c], key=lambda t: (t[0], t[1]))])
+            parts = sorted(by[c], key=lambda t: (t[0], t[1]))
+            recs = np.concatenate([e for _, _, e, _ in parts])
             draft = fa.get_reference_sequence(c, 0, length).encode() if len(recs) else b""
-            records[c] = polish_edits.compose_records(c, recs, draft, qualities, warn=log)
+            ev = {"evidence": np.concatenate([v for _, _, _, v in parts])} if evidence else {}
+            records[c] = polish_edits.compose_records(c, recs, draft, qualities, warn=log, **ev)
     return "pepper_thesis_amd polish", os.path.abspath(fasta_path), contigs, no_reads, records, int(min_depth), int(min_qual)
 
 
@@ -933,6 +1003,10 @@ def run(args, open_chain=open_device_chain) -> int:
     if edits and len(plan) > 1:
         sys.stderr.write("ERROR: polish --edits runs on one device (-d_ids %s lists %d): the edit records are not carried "
                          "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
+        return 2
+    evidence = bool(getattr(args, "evidence", False))
+    if evidence and not edits:
+        sys.stderr.write("ERROR: polish --evidence needs --edits: the read support goes into the INFO column of the edits VCF.\n")
         return 2
     min_depth = int(getattr(args, "min_depth", 0) or 0)
     if not 0 <= min_depth <= 65535:
@@ -980,13 +1054,16 @@ def run(args, open_chain=open_device_chain) -> int:
         kw["min_qual"] = min_qual
     if use_hp:
         kw["use_hp"] = True
+    if evidence:
+        kw["evidence"] = True
     chain = open_chain(device, False, state_dict, dtype, **kw)
     try:
         T = {}
         path = polish_fused(args.bam, args.fasta, args.model_path, args.output_file, args.region, args.batch_size, args.threads,
                             timers=T, realign=bool(getattr(args, "realign", False)), chain=chain,
                             gpu_decode=bool(getattr(args, "gpu_decode", False)), qualities=qualities, edits=edits,
-                            min_depth=min_depth, min_qual=min_qual, **({"use_hp": True} if use_hp else {}))
+                            min_depth=min_depth, min_qual=min_qual, **({"use_hp": True} if use_hp else {}),
+                            **({"evidence": True} if evidence else {}))
     except ValueError as e:
         if not edits:
             raise
@@ -1017,4 +1094,6 @@ def run(args, open_chain=open_device_chain) -> int:
         from .polish_edits import output_vcf_path
         log("EDITS VCF: %s (%d RECORDS FROM %d EDITED COLUMNS)" % (", ".join(output_vcf_path(p) for p in paths), T["vcf_records"],
                                                                    T["edit_records"]))
+    if evidence:
+        log("EVIDENCE: %d OF %d RECORDS HAVE THEIR ALT SUPPORT ON ONE STRAND ONLY" % (T.get("one_strand_records", 0), T["vcf_records"]))
     return 0

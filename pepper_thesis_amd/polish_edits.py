@@ -22,6 +22,15 @@ from . import _ffi
 EDIT_DTYPE = np.dtype([("position", "<i8"), ("index", "<i4"), ("kind", "u1"), ("draft", "u1"), ("base", "u1"), ("qual", "u1")])
 assert EDIT_DTYPE.itemsize == 16
 KIND_SUB, KIND_DEL, KIND_INS = _ffi.PV_EDIT_SUB, _ffi.PV_EDIT_DEL, _ffi.PV_EDIT_INS
+# `polish --evidence`: one record beside every edit record (pv_polish_evidence, the rule in include/pepper_hip.h)
+EVIDENCE_DTYPE = np.dtype([("depth", "<u2"), ("ref", "<u2"), ("alt_fwd", "<u2"), ("alt_rev", "<u2")])
+assert EVIDENCE_DTYPE.itemsize == 8
+EVIDENCE_INFO_LINES = (
+    '##INFO=<ID=DP,Number=1,Type=Integer,Description="Reads over the weakest edited column of the record">',
+    '##INFO=<ID=AD,Number=R,Type=Integer,Description="Reads that spell the draft, reads that spell the edit, at that column">',
+    '##INFO=<ID=SAF,Number=A,Type=Integer,Description="Forward-strand reads that spell the edit at that column">',
+    '##INFO=<ID=SAR,Number=A,Type=Integer,Description="Reverse-strand reads that spell the edit at that column">',
+)
 
 
 class VcfRecord(NamedTuple):
@@ -32,18 +41,39 @@ class VcfRecord(NamedTuple):
     qual: Optional[int]
 
 
+class EvidenceVcfRecord(NamedTuple):
+    """a VcfRecord of a run with --evidence: evidence is (depth, ref, alt_fwd, alt_rev) of the record's weakest column"""
+    pos: int
+    ref: str
+    alt: str
+    qual: Optional[int]
+    evidence: Tuple[int, int, int, int]
+
+
+def info_text(evidence: Tuple[int, int, int, int]) -> str:
+    """the INFO column of a record with evidence"""
+    depth, ref, fwd, rev = (int(v) for v in evidence)
+    return "DP=%d;AD=%d,%d;SAF=%d;SAR=%d" % (depth, ref, fwd + rev, fwd, rev)
+
+
 def output_vcf_path(fasta_path: str) -> str:
     """the VCF of --edits lies beside the FASTA: ..._pepper_polished.fa -> ..._pepper_polished.edits.vcf.gz"""
     assert fasta_path.endswith(".fa"), fasta_path
     return fasta_path[:-3] + ".edits.vcf.gz"
 
 
-def compose_records(contig: str, edits: np.ndarray, draft: bytes, qualities: bool, warn=None) -> List[VcfRecord]:
+def compose_records(contig: str, edits: np.ndarray, draft: bytes, qualities: bool, warn=None,
+                    evidence: Optional[np.ndarray] = None) -> List[VcfRecord]:
     """the records of one contig (EDIT_DTYPE, the pieces in region-start order) + the contig's draft -> its VCF records, POS
     strictly increasing. ValueError (naming the contig) when the records are not strictly increasing in (position, index),
     as happens when -r lists overlapping ranges of one contig, or reach past the draft. qualities: QUAL is the minimum qual
-    of the block's records, else None. warn(msg): told about a block that deletes the whole contig (no record is written)."""
+    of the block's records, else None. warn(msg): told about a block that deletes the whole contig (no record is written).
+    evidence (EVIDENCE_DTYPE, one per edit record): the records are EvidenceVcfRecords that carry the evidence of their
+    block's weakest column, the one with the lowest alt_fwd + alt_rev (the first such on a tie); all four numbers are that
+    column's."""
     n = len(edits)
+    if evidence is not None and len(evidence) != n:
+        raise ValueError("contig %s: %d evidence records for %d edit records" % (contig, len(evidence), n))
     if n == 0:
         return []
     pos, idx = edits["position"].astype(np.int64), edits["index"].astype(np.int64)
@@ -83,8 +113,15 @@ def compose_records(contig: str, edits: np.ndarray, draft: bytes, qualities: boo
     ref_all = up.tobytes().decode("latin-1")
     a_all, b_all = pos[first].tolist(), pos[np.append(first[1:], n) - 1].tolist()
     q_all = np.minimum.reduceat(qual, first).tolist() if qualities else [None] * len(first)
+    ev_all = [None] * len(first)
+    if evidence is not None:
+        alt = evidence["alt_fwd"].astype(np.int64) + evidence["alt_rev"].astype(np.int64)
+        lowest = np.minimum.reduceat(alt, first)[block]
+        # the first column of every block whose support is the block's lowest
+        weakest = np.minimum.reduceat(np.where(alt == lowest, np.arange(n), n), first)
+        ev_all = [tuple(int(v) for v in evidence[k]) for k in weakest.tolist()]
     out, o0 = [], 0
-    for a, b, o1, q in zip(a_all, b_all, alt_end, q_all):
+    for a, b, o1, q, ev in zip(a_all, b_all, alt_end, q_all, ev_all):
         ref, alt = ref_all[a:b + 1], alt_all[o0:o1]
         o0 = o1
         if len(alt) == len(ref) or (alt and alt[0] == ref[0]):
@@ -99,7 +136,7 @@ def compose_records(contig: str, edits: np.ndarray, draft: bytes, qualities: boo
             if warn is not None:
                 warn("contig %s: the edits delete the whole contig; no VCF record is written for it" % contig)
             continue
-        out.append(VcfRecord(vpos, ref, alt, q))
+        out.append(VcfRecord(vpos, ref, alt, q) if ev is None else EvidenceVcfRecord(vpos, ref, alt, q, ev))
     return out
 
 
@@ -118,18 +155,23 @@ def no_read_runs(ranges: Iterable[Tuple[str, int, int]]) -> List[Tuple[str, int,
 
 
 def vcf_text(source: str, reference: str, contigs: Sequence[Tuple[str, int]], no_reads: Sequence[Tuple[str, int, int]],
-             records: Dict[str, Sequence[VcfRecord]], min_depth: int = 0, min_qual: int = 0, haplotype: int = 0) -> str:
+             records: Dict[str, Sequence[VcfRecord]], min_depth: int = 0, min_qual: int = 0, haplotype: int = 0,
+             evidence: bool = False) -> str:
     """header (fileformat, source, reference, one contig line per contig of the run in natural order, one pepper_no_reads line
     per read-free run, the column line) and the records, contigs in natural order; eight columns, no samples.
     min_depth >= 1 (`polish --min_depth`): one pepper_min_depth line stands in the place of the pepper_no_reads lines; the
     run then filled its read-free regions from the draft, so there are none to name.
     min_qual >= 1 (`polish --min_qual`): one pepper_min_qual line behind them, before the column line.
-    haplotype >= 1 (`polish -hp`): one pepper_haplotype line, the last before the column line."""
+    haplotype >= 1 (`polish -hp`): one pepper_haplotype line, the last before the column line.
+    evidence (`polish --evidence`): four ##INFO lines (DP, AD, SAF, SAR) in front of the pepper_* lines, and the INFO column of
+    every EvidenceVcfRecord holds its numbers (info_text); any other record keeps `.`."""
     from .polish import natural_key
     names = sorted((c for c, _ in contigs), key=natural_key)
     length = dict(contigs)
     lines = ["##fileformat=VCFv4.2", "##source=" + source, "##reference=" + reference]
     lines += ["##contig=<ID=%s,length=%d>" % (c, length[c]) for c in names]
+    if evidence:
+        lines += list(EVIDENCE_INFO_LINES)
     if min_depth >= 1:
         assert not no_reads, no_reads
         lines.append("##pepper_min_depth=%d" % min_depth)
@@ -141,13 +183,14 @@ def vcf_text(source: str, reference: str, contigs: Sequence[Tuple[str, int]], no
     lines.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO")
     for c in names:
         for r in records.get(c, ()):
-            lines.append("%s\t%d\t.\t%s\t%s\t%s\tPASS\t." % (c, r.pos, r.ref, r.alt, "." if r.qual is None else str(r.qual)))
+            info = info_text(r.evidence) if evidence and len(r) > 4 else "."
+            lines.append("%s\t%d\t.\t%s\t%s\t%s\tPASS\t%s" % (c, r.pos, r.ref, r.alt, "." if r.qual is None else str(r.qual), info))
     return "\n".join(lines) + "\n"
 
 
 def write_edits_vcf(path: str, source: str, reference: str, contigs: Sequence[Tuple[str, int]],
                     no_reads: Sequence[Tuple[str, int, int]], records: Dict[str, Sequence[VcfRecord]], min_depth: int = 0,
-                    min_qual: int = 0, haplotype: int = 0) -> None:
+                    min_qual: int = 0, haplotype: int = 0, evidence: bool = False) -> None:
     """vcf_text through bamio.write_vcf_gz (bgzip + tabix): `path` and `path`.tbi, both written under temporary names and
     renamed when complete"""
     from . import bamio
@@ -155,7 +198,7 @@ def write_edits_vcf(path: str, source: str, reference: str, contigs: Sequence[Tu
     assert path.endswith(ext), path
     tmp = stem + ".partial" + ext
     try:
-        bamio.write_vcf_gz(tmp, vcf_text(source, reference, contigs, no_reads, records, min_depth, min_qual, haplotype))
+        bamio.write_vcf_gz(tmp, vcf_text(source, reference, contigs, no_reads, records, min_depth, min_qual, haplotype, evidence))
         os.replace(tmp + ".tbi", path + ".tbi")
         os.replace(tmp, path)
     except BaseException:

@@ -32,13 +32,15 @@ class PolishOut:
     flat_index: Optional[np.ndarray] = None
     region_row_off: Optional[np.ndarray] = None  # [n_regions + 1]
     depth: Optional[np.ndarray] = None           # [n_chunks, seq_length] uint16 read depth of every row, 0 on padding rows
+    counts: Optional[np.ndarray] = None          # [n_chunks, seq_length, 10] uint16 raw counts of every row, 0 on padding rows
 
 
 class PolishBuffers:
     """Caller-owned host buffers of one pv_polish_out."""
 
-    def __init__(self, n_regions, chunk_capacity, row_capacity, seq_length, want_flat, want_depth=False):
+    def __init__(self, n_regions, chunk_capacity, row_capacity, seq_length, want_flat, want_depth=False, want_counts=False):
         self.seq_length = seq_length
+        self.counts = np.zeros((chunk_capacity, seq_length, IMAGE_HEIGHT), dtype=np.uint16) if want_counts else None
         self.depth = np.zeros((chunk_capacity, seq_length), dtype=np.uint16) if want_depth else None
         self.images = np.zeros((chunk_capacity, seq_length, IMAGE_HEIGHT), dtype=np.uint8)
         self.position = np.zeros((chunk_capacity, seq_length), dtype=np.int64)
@@ -55,7 +57,7 @@ class PolishBuffers:
         c.chunk_capacity = chunk_capacity
         c.row_capacity = row_capacity if want_flat else 0
         for f in ("images", "position", "index", "region", "chunk_id", "flat_images", "flat_position", "flat_index",
-                  "region_row_off", "depth"):
+                  "region_row_off", "depth", "counts"):
             setattr(c, f, _ffi.ptr(getattr(self, f)))
         self.c = c
 
@@ -70,20 +72,23 @@ class PolishBuffers:
             out.region_row_off = self.region_row_off.copy()
         if self.depth is not None:
             out.depth = self.depth[:n].copy()
+        if self.counts is not None:
+            out.counts = self.counts[:n].copy()
         return out
 
 
 def run_polish_summarizer(fn, batch: RegionBatch, seq_length=SEQ_LENGTH, seq_overlap=SEQ_OVERLAP, want_flat=False, ctx=None,
-                          want_depth=False):
+                          want_depth=False, want_counts=False):
     """Call any function with pv_polish_summarize_regions' signature (minus the context when ctx is None), growing the
-    caller-owned buffers on PV_ERR_CAPACITY. Returns (rc, PolishOut or None). want_depth: ask for the depth plane too."""
+    caller-owned buffers on PV_ERR_CAPACITY. Returns (rc, PolishOut or None). want_depth: ask for the depth plane too;
+    want_counts: and for the counts plane."""
     cin = batch.as_c()
     cols = int((batch.ref_end - batch.ref_start + 1).sum()) if batch.n_regions else 0
     rows = cols + cols // 2 + 1024
     chunks = rows // max(1, seq_length - seq_overlap) + 2 * batch.n_regions + 2
     rc = 0
     for _ in range(3):
-        pb = PolishBuffers(batch.n_regions, chunks, rows, seq_length, want_flat, want_depth)
+        pb = PolishBuffers(batch.n_regions, chunks, rows, seq_length, want_flat, want_depth, want_counts)
         args = (C.byref(cin), int(seq_length), int(seq_overlap), C.byref(pb.c))
         rc = fn(ctx, *args) if ctx is not None else fn(*args)
         if rc == _ffi.PV_ERR_CAPACITY:
@@ -94,11 +99,12 @@ def run_polish_summarizer(fn, batch: RegionBatch, seq_length=SEQ_LENGTH, seq_ove
 
 
 def polish_summarize(ctx, batch: RegionBatch, seq_length=SEQ_LENGTH, seq_overlap=SEQ_OVERLAP, want_flat=False,
-                     want_depth=False) -> PolishOut:
+                     want_depth=False, want_counts=False) -> PolishOut:
     """generate_summary + chunk_images for every region of the batch on ctx's GPU (host buffers in and out).
-    want_depth: also the read depth of every chunk row (PolishOut.depth; pv_polish_out.depth in include/pepper_hip.h)."""
+    want_depth: also the read depth of every chunk row (PolishOut.depth; pv_polish_out.depth in include/pepper_hip.h).
+    want_counts: also the ten raw counts of every chunk row (PolishOut.counts; pv_polish_out.counts)."""
     rc, out = run_polish_summarizer(ctx.lib.pv_polish_summarize_regions, batch, seq_length, seq_overlap, want_flat, ctx.handle,
-                                    want_depth)
+                                    want_depth, want_counts)
     _ffi.check(rc)
     return out
 

@@ -269,10 +269,10 @@ class Context:
             stream or None))
 
     def polish_summarize(self, batch: RegionBatch, seq_length: int = 1000, seq_overlap: int = 50, want_flat: bool = False,
-                         want_depth: bool = False):
+                         want_depth: bool = False, want_counts: bool = False):
         """Polisher (P2) SummaryGenerator.generate_summary + chunk_images for a batch (host buffers), see polish_summary.py."""
         from .polish_summary import polish_summarize
-        return polish_summarize(self, batch, seq_length, seq_overlap, want_flat, want_depth)
+        return polish_summarize(self, batch, seq_length, seq_overlap, want_flat, want_depth, want_counts)
 
     def polish_summarize_dev(self, dbatch: "DeviceBatch", dout: "DevicePolishOut", stream: int = 0):
         """asynchronous, device-resident: chunks land in dout.images ([capacity, seq_length, 10] uint8 in HBM), ready
@@ -476,6 +476,51 @@ class Context:
                                             _ffi.ptr(ref), len(rs), seq_length, seq_overlap, _ffi.ptr(region_edit_off),
                                             _ffi.ptr(edits), cap, counts))
         return region_edit_off, edits[:int(counts[0])].copy()
+
+    def polish_edits_evidence_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_row_qual: int, d_region_start: int,
+                                  d_ref_off: int, d_ref: int, n_regions: int, d_region_edit_off: int, d_edits: int, d_evidence: int,
+                                  edit_capacity: int, d_counts: int, stream: int = 0):
+        """polish_edits_dev with one 8-byte evidence record (polish_edits.EVIDENCE_DTYPE) per edit record in d_evidence
+        (pv_polish_edits_evidence_dev); dout must carry the depth and the counts plane"""
+        _ffi.check(self.lib.pv_polish_edits_evidence_dev(
+            self.handle, C.byref(dout.c), int(n_chunks), d_labels, d_row_qual or None, d_region_start, d_ref_off, d_ref or None,
+            int(n_regions), dout.seq_length, dout.seq_overlap, d_region_edit_off, d_edits, d_evidence or None, int(edit_capacity),
+            d_counts, stream or None))
+
+    def polish_edits_evidence(self, out, labels: np.ndarray, batch, row_qual: np.ndarray = None, edit_capacity: int = None,
+                              seq_length: int = 1000, seq_overlap: int = 50, counts=None, region_edit_off: np.ndarray = None,
+                              evidence: np.ndarray = None):
+        """host-buffer form (pv_polish_edits_evidence) of a PolishOut with its depth and counts planes -> (region_edit_off,
+        edit records, evidence records as a polish_edits.EVIDENCE_DTYPE array). The other arguments are polish_edits';
+        evidence: an optional EVIDENCE_DTYPE array of at least the capacity that receives the records (tests look at what
+        the call left alone)."""
+        from .polish_edits import EDIT_DTYPE, EVIDENCE_DTYPE
+        n, c, keep = self._host_polish_out(out)
+        depth = None if getattr(out, "depth", None) is None else np.ascontiguousarray(out.depth, np.uint16)
+        rowc = None if getattr(out, "counts", None) is None else np.ascontiguousarray(out.counts, np.uint16)
+        c.depth, c.counts = _ffi.ptr(depth), _ffi.ptr(rowc)
+        lab = np.ascontiguousarray(labels, np.uint8)
+        rq = None if row_qual is None else np.ascontiguousarray(row_qual, np.uint8)
+        rs = np.ascontiguousarray(batch.ref_start, np.int64)
+        ro = np.ascontiguousarray(batch.ref_off, np.int64)
+        ref = None if batch.ref is None else np.ascontiguousarray(batch.ref, np.uint8)
+        assert lab.shape == (n, seq_length) and (rq is None or rq.shape == lab.shape), lab.shape
+        assert depth is None or depth.shape == lab.shape, depth.shape
+        assert rowc is None or rowc.shape == lab.shape + (10,), rowc.shape
+        assert len(ro) == len(rs) + 1 and (ref is None or len(ref) >= int(ro[-1])), (len(ro), len(rs))
+        cap = n * seq_length if edit_capacity is None else int(edit_capacity)
+        if region_edit_off is None:
+            region_edit_off = np.zeros(len(rs) + 1, np.int64)
+        edits = np.zeros(max(cap, 1), EDIT_DTYPE)
+        if evidence is None:
+            evidence = np.zeros(max(cap, 1), EVIDENCE_DTYPE)
+        assert evidence.dtype == EVIDENCE_DTYPE and len(evidence) >= cap and evidence.flags.c_contiguous
+        if counts is None:
+            counts = (C.c_int64 * 4)()
+        _ffi.check(self.lib.pv_polish_edits_evidence(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rq), _ffi.ptr(rs),
+                                                     _ffi.ptr(ro), _ffi.ptr(ref), len(rs), seq_length, seq_overlap,
+                                                     _ffi.ptr(region_edit_off), _ffi.ptr(edits), _ffi.ptr(evidence), cap, counts))
+        return region_edit_off, edits[:int(counts[0])].copy(), evidence[:int(counts[0])].copy()
 
     def polish_mask_low_depth_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_row_qual: int, d_region_start: int,
                                   d_ref_off: int, d_ref: int, n_regions: int, min_depth: int, d_labels_out: int,

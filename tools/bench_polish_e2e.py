@@ -33,6 +33,8 @@
               device, and the VCF's size. The weights are random, so most rows are edits: the record count says nothing
               about a trained model.
 
+  --edits --evidence: `polish --edits` without and with --evidence: wall times of both forms, twice each, then HIP events around
+              the builder call without a plane, with the depth plane and with both, and around the edits / evidence call.
   --min_depth N: the same comparison for `polish --min_depth N`: wall times of both forms, twice each, then one more run each way
               with the builder, the mask and the stitch calls bracketed by HIP events, and the rows the mask rewrote. The parent
               commit's plain figure (profiles/polish_e2e_bench.json) is recorded beside them as the yardstick.
@@ -48,7 +50,7 @@
               achieved bytes per second (payload read + payload written over its time).
 
   python tools/bench_polish_e2e.py [--leg stitch|e2e|steps|all] [--mbp 2.0] [--reps 20] [--realign] [--d_ids 0,0] [--gpu_decode]
-                                   [--qualities] [--edits] [--min_depth N] [--min_qual Q] [-hp] [--out f]
+                                   [--qualities] [--edits [--evidence]] [--min_depth N] [--min_qual Q] [-hp] [--out f]
 For the rocprofv3 row run the stitch leg alone under `rocprofv3 --kernel-trace --stats -d <dir> -- python ... --leg stitch`.
 """
 import argparse
@@ -137,7 +139,7 @@ def stitch_leg(reps=20):
 
 
 def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False, qualities=False, edits=False, min_depth=0,
-             min_qual=0, use_hp=False):
+             min_qual=0, use_hp=False, evidence=False):
     # warm-up on a small region (code objects, allocator), then the timed run
     kw = {"gpu_decode": True} if gpu_decode else {}
     if use_hp:
@@ -150,6 +152,8 @@ def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decod
         kw["qualities"] = True
     if edits:
         kw["edits"] = True
+    if evidence:
+        kw["evidence"] = True
     polish.polish_fused(bam, fa, model, out + "_warm", region="chr20:0-50000", threads=threads, ctx=ctx, realign=realign, **kw)
     T = {}
     t0 = time.perf_counter()
@@ -178,6 +182,8 @@ def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decod
                    tbi_bytes=os.path.getsize(vcf + ".tbi"),
                    # 16 bytes a record and the region offsets of every launch
                    edits_readback_bytes=16 * T["edit_records"] + 8 * (T["regions"] + T["batches"]))
+    if evidence:
+        res.update(evidence=True, evidence_readback_bytes=8 * T["edit_records"], one_strand_records=T.get("one_strand_records", 0))
     if gpu_decode:
         import hashlib
         import torch
@@ -244,16 +250,19 @@ def realign_stats(ctx, bam, fa, per_launch=1024):
             "band_gcups": round(band / (band_ms * 1e-3) / 1e9, 1) if band_ms else None}
 
 
-def _quality_events(polish, ctx, bam, fa, model, out, threads, qualities, edits=False, min_depth=0, min_qual=0):
+def _quality_events(polish, ctx, bam, fa, model, out, threads, qualities, edits=False, min_depth=0, min_qual=0, evidence=False):
     """one more run with the calls whose profile names start with polish_ bracketed by HIP events -> {name: [ms, launches]}"""
     ctx.profile_begin("polish_")
     try:
         kw = {"min_qual": min_qual} if min_qual else {}
+        if evidence:
+            kw["evidence"] = True
         polish.polish_fused(bam, fa, model, out, threads=threads, ctx=ctx, qualities=qualities, edits=edits, min_depth=min_depth, **kw)
     finally:
         pr = ctx.profile_end()
     return {k: [round(v[0], 4), v[1]] for k, v in sorted(pr.items())
-            if k in ("polish_stitch", "polish_row_qual", "polish_edits", "polish_mask", "polish_filter", "polish_pipeline")}
+            if k in ("polish_stitch", "polish_row_qual", "polish_edits", "polish_edits_evidence", "polish_mask", "polish_filter",
+                     "polish_pipeline")}
 
 
 def min_depth_leg(mbp=3.0, threads=16, min_depth=3):
@@ -466,6 +475,49 @@ def edits_leg(mbp=3.0, threads=16):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def evidence_leg(mbp=3.0, threads=16):
+    """polish --edits without and with --evidence on one synthetic contig, in one process on the same files"""
+    import hashlib
+    import numpy as np
+    from bench_filepath import make_files
+    from pepper_thesis_amd import bamio, polish, polish_edits, runtime, synth
+    d = tempfile.mkdtemp(prefix="pv_polish_evidence_")
+    try:
+        bam, fa, info = make_files(d, int(mbp * 1_000_000))
+        model = os.path.join(d, "model.npz")
+        np.savez(model, **synth.make_weights_p2(4321, 3.0))
+        ctx = runtime.Context(0)
+        try:
+            runs = []
+            for k in range(2):
+                for e in (False, True):
+                    r = _e2e_run(polish, ctx, bam, fa, model, os.path.join(d, "evidence" if e else "edits"), threads, False, info,
+                                 edits=True, evidence=e)
+                    runs.append(dict(r, evidence=e, order=len(runs)))
+            res = {"runs": runs, "without_evidence": runs[2], "with_evidence": runs[3]}
+            sha = [hashlib.sha256(open(os.path.join(d, n, "_pepper_polished.fa"), "rb").read()).hexdigest() for n in ("edits", "evidence")]
+            res["fasta_identical"], res["fasta_sha256"] = sha[0] == sha[1], sha[0]
+            vcf = [bamio.bgzf_read_all(polish_edits.output_vcf_path(os.path.join(d, n, "_pepper_polished.fa"))).decode().split("\n")
+                   for n in ("edits", "evidence")]
+            blank = [l if l.startswith("#") or not l else "\t".join(l.split("\t")[:7] + ["."]) for l in vcf[1] if not l.startswith("##INFO=")]
+            res["vcf_identical_but_info"] = blank == vcf[0]
+            ev = lambda name, **kw: _quality_events(polish, ctx, bam, fa, model, os.path.join(d, name), threads, False, **kw)
+            res["event_ms_launches"] = {
+                "plain": ev("plain_ev"),                                             # the builder without a plane
+                "edits": ev("edits_ev", edits=True),                                 # ... and the edits call
+                "edits_min_depth_1": ev("depth_ev", edits=True, min_depth=1),        # the builder with the depth plane
+                "edits_evidence": ev("evidence_ev", edits=True, evidence=True)}      # both planes, the evidence call
+            res["note"] = ("polish_pipeline: the builder call; polish_edits / polish_edits_evidence: count + scan + write kernels of "
+                           "one call; HIP events around every call of a run, summed over the run's launches. The weights are random: "
+                           "nearly every column is an edit, the worst case for the evidence call, and neither the record count nor "
+                           "the host time represents a trained model")
+            return res
+        finally:
+            ctx.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 def qualities_leg(mbp=3.0, threads=16):
     """polish without and with --qualities on one synthetic contig, in one process on the same files"""
     import hashlib
@@ -629,6 +681,9 @@ def main():
                     help="e2e leg without and with polish --qualities, plus HIP-event times of the stitch and row-quality calls")
     ap.add_argument("--edits", action="store_true",
                     help="e2e leg without and with polish --edits, plus HIP-event times of the stitch and the edit calls")
+    ap.add_argument("--evidence", action="store_true",
+                    help="with --edits: e2e leg of polish --edits without and with --evidence, plus HIP-event times of the builder "
+                         "without a plane, with the depth plane and with both, and of the edits call against the evidence call")
     ap.add_argument("--min_depth", type=int, default=0,
                     help="e2e leg without and with polish --min_depth N, plus HIP-event times of the builder, mask and stitch calls")
     ap.add_argument("--min_qual", type=int, default=0,
@@ -648,7 +703,7 @@ def main():
         elif a.min_depth:
             out["e2e"] = min_depth_leg(a.mbp, a.threads, a.min_depth)
         elif a.edits:
-            out["e2e"] = edits_leg(a.mbp, a.threads)
+            out["e2e"] = evidence_leg(a.mbp, a.threads) if a.evidence else edits_leg(a.mbp, a.threads)
         elif a.qualities:
             out["e2e"] = qualities_leg(a.mbp, a.threads)
         else:
