@@ -745,6 +745,11 @@ int pv_debug_gemm_bf16x3(pv_ctx* ctx, const float* A, const float* W, const floa
  * host before the upload, as the model load does), same arguments and shape rules. */
 int pv_debug_gemm_bf16x6(pv_ctx* ctx, const float* A, const float* W, const float* bias, int64_t M, int N, int K,
                          int splits, int quads, float* C, float* ms);
+/* The same product through k_gemm_x6_stream, the decoder projection's launch in the split-6 chain (48-row A tiles resident in
+ * LDS, W streamed in the order made at load time): K = 512, N a multiple of 512 up to 2048, no split-K. C is bit-identical to
+ * pv_debug_gemm_bf16x6's. */
+int pv_debug_gemm_x6_stream(pv_ctx* ctx, const float* A, const float* W, const float* bias, int64_t M, int N, int K,
+                            int quads, float* C, float* ms);
 
 /* Per-kernel timing for the benchmark's roofline leg: between pv_profile_begin and pv_profile_end every
  * kernel the context launches is bracketed by HIP events on its launch stream. pv_profile_end
@@ -779,6 +784,8 @@ int pv_rnn_exchange_timeouts(pv_ctx* ctx);
  *   p1_f32x6_min_batch [PV_P1_F32X6_MIN_BATCH]  P1 in the PV_DTYPE_F32 mode: calls of at least this many windows (1..16777216,
  *                                   default 2048) and no explicit lstm_rows run the split-6 chain; smaller calls the f32 MFMA
  *                                   kernels, bit for bit as before. 16777216 (above any batch) turns the chain off
+ *   p1_gemm6_stream                 1 (default) / 0: the split-6 chain's decoder input projection as k_gemm_x6_stream / as
+ *                                   k_gemm_bf16x6; the results are the same bit for bit
  *   shared_device [PV_SHARED_DEVICE] 0 / 1: other streams or processes keep this GPU busy (e.g. several un-fused callers per
  *                                   GPU, RunInferenceArguments.py:67-74): never choose a form that needs co-resident workgroups
  *   exchange_spin_log2              2..22 (default 18): bounded polls give up after 2^n tries

@@ -331,6 +331,8 @@ SYMBOLS = [
                                         C.c_void_p, C.POINTER(C.c_float)]),
     ("pv_debug_gemm_bf16x6", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.POINTER(C.c_float)]),
+    ("pv_debug_gemm_x6_stream", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p, C.POINTER(C.c_float)]),
     ("pv_profile_begin", C.c_int, [C.c_void_p]),
     ("pv_profile_begin_only", C.c_int, [C.c_void_p, C.c_char_p]),
     ("pv_profile_end", C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int]),

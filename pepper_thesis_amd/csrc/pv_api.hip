@@ -55,6 +55,7 @@ const opt_desc OPTS[] = {
     {"debug_drop_part", nullptr, &pv_opts::debug_drop_part, -1, 3},
     {"p1_bf16_min_batch", nullptr, &pv_opts::p1_bf16_min_batch, 0, 1 << 20},
     {"p1_f32x6_min_batch", "PV_P1_F32X6_MIN_BATCH", &pv_opts::p1_f32x6_min_batch, 1, 1 << 24},
+    {"p1_gemm6_stream", nullptr, &pv_opts::p1_gemm6_stream, 0, 1},
     {"realign_scratch_kb", nullptr, &pv_opts::realign_scratch_kb, 1, 1 << 22},
 };
 bool opt_value_ok(const opt_desc& d, int v) {

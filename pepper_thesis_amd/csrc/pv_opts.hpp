@@ -21,5 +21,7 @@ struct pv_opts {
     int p1_f32x6_min_batch = 2048; // PV_DTYPE_F32, P1: calls of at least this many windows (and no explicit lstm_rows) run the split-6
                                    // chain (fp32 products as six bf16 MFMA terms); smaller calls the fp32 kernels, bit for bit
                                    // (measured: 1.86 against 1.63 ms at 1024 windows, 2.07 against 2.64 at 1536)
+    int p1_gemm6_stream = 1;     // split-6 chain: the decoder input projection as k_gemm_x6_stream (A tile resident in LDS, W streamed);
+                                 // 0: as k_gemm_bf16x6 like every other six-term product. The results are the same bit for bit.
     int realign_scratch_kb = 512 << 10; // bounded pool of the realigner's direction bytes (pv_polish_realign*), in KB
 };

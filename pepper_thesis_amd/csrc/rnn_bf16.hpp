@@ -22,6 +22,10 @@ struct pv_gemm_desc {
     int N, K, splits, quads;
     const char* prof_name;
     int terms;   // 0 / 3: split8 operands, 3-term products; 6: fp32 A (split in registers) and pre-split W planes, 6-term products
+    const unsigned char* W_stream;   // terms = 6, optional: the same W as the fragment stream of pack_gemm6_stream (pv_upload_gemm6_stream).
+                                     // With it a product of K = 512, N % 512 == 0, N <= 2048, splits = 1 runs as k_gemm_x6_stream (A tiles
+                                     // of 48 rows resident in LDS, W streamed from L2), C bit for bit the same; option p1_gemm6_stream = 0
+                                     // keeps k_gemm_bf16x6. W stays required: every other shape reads the planes.
 };
 int pv_gemm_bf16x3_async(pv_ctx* ctx, const pv_gemm_desc& g, hipStream_t st);                       // rnn_gemm.hip
 int pv_gemm_bf16x3_prepare();                                                                       // function attributes (once per load)
@@ -29,6 +33,8 @@ int pv_gemm_bf16x3_prepare();                                                   
 int pv_upload_split8(const float* w, size_t N, size_t K, unsigned char** d_split, std::vector<void*>& owned);
 // ... -> three bf16 planes [3][N][K] on the device, the W operand of k_gemm_bf16x6
 int pv_upload_split3(const float* w, size_t N, size_t K, unsigned char** d_planes, std::vector<void*>& owned);
+// ... -> the fragment stream of k_gemm_x6_stream (pack_gemm6_stream, rnn_pack_host.hpp; as many bytes as the planes); N % 512 == 0, K % 32 == 0
+int pv_upload_gemm6_stream(const float* w, size_t N, size_t K, unsigned char** d_stream, std::vector<void*>& owned);
 
 // ---- k_rec_bf16: one recurrent layer on pre-packed bf16 weight fragments (rnn_rec_bf16.hip) ----------------------------
 // A workgroup is (batch tile of 32 * MT rows, direction); wave w owns hidden units [32w, 32w + 32) of every gate.

@@ -3,6 +3,8 @@
 //   k_gemm_bf16x3          3-term split products of "split8" operands: the decoder input projections and linear_1 of
 //        PV_DTYPE_BF16_INPUT_GEMM (P1: rnn_p1.hip; P2: rnn_rec_bf16.hip)
 //   k_gemm_bf16x6          6-term products of three-piece operands: the same two products of the split-6 chain of PV_DTYPE_F32
+//   k_gemm_x6_stream       the same 6-term product, bit for bit, at K = 512 (the split-6 decoder projection): 48-row A tiles resident
+//        in LDS as bf16 pieces, W streamed from L2 in the order of pack_gemm6_stream, no barrier inside an item
 // The recurrent layers between them are k_rec_bf16 (rnn_rec_bf16.hip). Operand formats: split8_rows (rnn_pack_host.hpp) and
 // split3_planes (split3_host.hpp); both are made on the host, once, and uploaded here (pv_upload_split8, pv_upload_split3).
 #include "pv_common.hpp"
@@ -546,6 +548,195 @@ __device__ __forceinline__ void gemm6_body(const GemmArgs& g) {
 __global__ __launch_bounds__(512, 2) void k_gemm_bf16x3(GemmArgs g) { gemm_body(g); }
 __global__ __launch_bounds__(512, 2) void k_gemm_bf16x6(GemmArgs g) { gemm6_body(g); }
 
+// ---- k_gemm_x6_stream: the six-term product at K = 512 with A resident in LDS and W streamed from L2 --------------------------
+// The decoder input projection has K = 512 only: the whole K extent of a 48-row tile fits in LDS as its three bf16 pieces, so the
+// product takes the recurrent kernels' structure (ring_x6_16, rnn_rec_bf16.hip) instead of a staged GEMM's. A work item is 48 rows
+// x all N columns; persistent workgroups (one per CU, 8 waves) walk the items, and every workgroup reads W in the same order.
+//   item prologue   the item's fp32 rows (rows past M read as zeros and are never stored), split ONCE with split3_bf16 by the lane
+//                   that loaded them, into three piece planes [48 rows][K] of bf16 in LDS, row pitch 1040 B (260 dwords = 4 mod
+//                   64: the bank rule of RecCfg::HS); one barrier in front (every wave is done with the old tile), one behind
+//   main loop       no workgroup barrier. Wave w owns columns [w N / 8, (w + 1) N / 8) and walks them in blocks of 64 (four column
+//                   tiles), the 16 k-steps inside a block: 3 x 4 accumulator tiles. A fragments: nine ds_read_b128 per k-step,
+//                   requested one k-step ahead into a second register set. W fragments: the stream of pack_gemm6_stream through a
+//                   ring of GS_D slots (three pieces, 12 registers each) on raw buffer loads GS_D - 1 slots ahead, fenced with
+//                   sched_barrier as in ring_x6_16; the ring runs on across blocks and wraps into the next item.
+//   MFMA order      v_mfma_f32_16x16x32_bf16, lane group g = k 8g .. 8g + 7 of the step; per accumulator tile the k-steps ascend and
+//                   the six terms go a2.b0, a0.b2, a1.b1, a0.b0, a0.b1, a1.b0, the three row tiles alternating: per output element
+//                   the sequence of gemm6_body, so C is bit-identical to k_gemm_bf16x6's
+//   epilogue        acc + bias (from LDS, loaded once per launch), every wave's block ends in its own nt stores through a sized
+//                   resource that drops rows past M; both layouts
+// No flags, no atomics, nothing between workgroups.
+constexpr int GS_ROWS = 48, GS_K = 512, GS_PITCH = GS_K * 2 + 16, GS_PLANE = GS_ROWS * GS_PITCH, GS_D = 8;
+constexpr int GS_MAXN = 2048;   // columns of the bias image in LDS
+constexpr size_t LDS_GEMM_STREAM = (size_t)3 * GS_PLANE + GS_MAXN * 4;   // 149 760 B of pieces + 8 KB of bias
+struct GemmStreamArgs {
+    const float* A;           // [M][512] fp32 rows
+    const unsigned char* Ws;  // pack_gemm6_stream
+    const float* bias;        // [N] or NULL
+    float* C;                 // [M][N], or (c_quads) [M/4][N][4]
+    int64_t M;
+    int N, c_quads, items;    // items of 48 rows
+};
+#ifdef PV_GEMM_STAMPS
+#define SSTAMP(i) { unsigned long long now_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_) :: "memory"); gs_acc[i] += now_ - gs_last; gs_last = now_; }
+#else
+#define SSTAMP(i)
+#endif
+__global__ __launch_bounds__(512) void k_gemm_x6_stream(GemmStreamArgs g) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smg[];
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ncol_w = g.N >> 3, nblk = ncol_w >> 6;          // columns of a wave, blocks of 64 of them
+    const __amdgpu_buffer_rsrc_t wr = make_rsrc(g.Ws + (size_t)wv * (size_t)nblk * (64 * 3072));
+    const unsigned lane16 = (unsigned)lane * 16u;
+    float* sbias = reinterpret_cast<float*>(smg + 3 * GS_PLANE);
+    for (int n = tid; n < g.N; n += 512) sbias[n] = g.bias ? g.bias[n] : 0.0f;   // (published by the first item's barriers)
+    // the ring: slots 0 .. GS_D - 2 of the wave's stream are on their way when an item starts
+    f32x4 bq[GS_D][3];
+#pragma unroll
+    for (int q = 0; q < GS_D - 1; q++)
+#pragma unroll
+        for (int p = 0; p < 3; p++) bq[q][p] = buf_load4(wr, lane16, (unsigned)(q * 3072 + p * 1024));
+    // A fragments: lane -> row 16 mi + (lane & 15), k-group lane >> 4 of the k-step
+    const unsigned char* a_l = smg + (lane & 15) * GS_PITCH + (lane >> 4) * 16;
+#ifdef PV_GEMM_STAMPS
+    unsigned long long gs_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, gs_last, gs_t0, gs_r0;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gs_last) :: "memory");
+    gs_t0 = gs_last;
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gs_r0) :: "memory");
+#endif
+    for (int it = blockIdx.x; it < g.items; it += (int)gridDim.x) {
+        const int64_t m0 = (int64_t)it * GS_ROWS;
+        const int rows_left = (int)(g.M - m0 < GS_ROWS ? g.M - m0 : GS_ROWS);
+        // (lane numbers the optimiser cannot see through: what the prologue and the epilogues derive from them is worked out where
+        // it is used, a few VALU instructions, and holds no register across the MFMA loop, which has none to spare)
+        int lane_p;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_p));
+        {   // item prologue: wave w loads rows w, w + 8, .. w + 40 of the tile, lane -> 8-group lane of the row (32 B of fp32 -> 16 B a piece)
+            const unsigned pl_g = (unsigned)wv * (GS_K * 4) + (unsigned)lane_p * 32u;
+            unsigned char* pl_s = smg + wv * GS_PITCH + lane_p * 16;
+            const __amdgpu_buffer_rsrc_t ra = make_rsrc_sized(g.A + (size_t)m0 * GS_K, (unsigned)rows_left * (GS_K * 4));
+            f32x4 raw[6][2];
+#pragma unroll
+            for (int j = 0; j < 6; j++) {
+                raw[j][0] = buf_load4_nt(ra, pl_g, (unsigned)(j * 8 * GS_K * 4));
+                raw[j][1] = buf_load4_nt(ra, pl_g, (unsigned)(j * 8 * GS_K * 4 + 16));
+            }
+            lds_barrier();   // every wave has read the last of the tile before
+#pragma unroll
+            for (int j = 0; j < 6; j++) {
+                bf16x8 x0, x1, x2;
+                split3_bf16(raw[j][0], raw[j][1], x0, x1, x2);
+                *reinterpret_cast<bf16x8*>(pl_s + j * 8 * GS_PITCH) = x0;
+                *reinterpret_cast<bf16x8*>(pl_s + j * 8 * GS_PITCH + GS_PLANE) = x1;
+                *reinterpret_cast<bf16x8*>(pl_s + j * 8 * GS_PITCH + 2 * GS_PLANE) = x2;
+            }
+            lds_barrier();
+        }
+        SSTAMP(0)
+        // C of the item as a sized resource: rows past M fall outside it and are dropped by the bounds check
+        const __amdgpu_buffer_rsrc_t rc = g.c_quads
+            ? make_rsrc_sized(g.C + (size_t)(m0 >> 2) * g.N * 4, (unsigned)(rows_left >> 2) * (unsigned)g.N * 16u)
+            : make_rsrc_sized(g.C + (size_t)m0 * g.N, (unsigned)rows_left * (unsigned)g.N * 4u);
+#pragma nounroll
+        for (int b = 0; b < nblk; b++) {
+            const unsigned sb_cur = (unsigned)b * (64 * 3072), sb_nxt = b + 1 < nblk ? sb_cur + 64 * 3072 : 0u;
+            f32x4 acc[3][4];
+#pragma unroll
+            for (int mi = 0; mi < 3; mi++)
+#pragma unroll
+                for (int ct = 0; ct < 4; ct++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) acc[mi][ct][r] = 0.0f;
+            bf16x8 ap[2][3][3];   // [set][piece][row tile]
+#define GS_A(set, ks)                                                                                   \
+    _Pragma("unroll") for (int q = 0; q < 3; q++)                                                        \
+        _Pragma("unroll") for (int mi = 0; mi < 3; mi++)                                                 \
+            ap[set][q][mi] = *reinterpret_cast<const bf16x8*>(a_l + q * GS_PLANE + mi * 16 * GS_PITCH + (ks) * 64);
+            GS_A(0, 0)
+#pragma unroll
+            for (int i = 0; i < 64; i++) {
+                const int ks = i >> 2, ct = i & 3, as = ks & 1;
+                {   // request slot i + GS_D - 1 (beyond the block: of the next block, beyond the item: of the next item)
+                    const int t = i + GS_D - 1, rs = t % GS_D;
+                    const unsigned so = t < 64 ? sb_cur + (unsigned)(t * 3072) : sb_nxt + (unsigned)((t - 64) * 3072);
+#pragma unroll
+                    for (int p = 0; p < 3; p++) bq[rs][p] = buf_load4(wr, lane16, so + (unsigned)(p * 1024));
+                }
+                if (ct == 0 && ks + 1 < 16) { GS_A(as ^ 1, ks + 1) }
+                __builtin_amdgcn_sched_barrier(0);   // keep hipcc from sinking the prefetches next to their uses
+                {
+                    const int rs = i % GS_D;
+                    const bf16x8 b0 = __builtin_bit_cast(bf16x8, bq[rs][0]), b1 = __builtin_bit_cast(bf16x8, bq[rs][1]);
+                    const bf16x8 b2 = __builtin_bit_cast(bf16x8, bq[rs][2]);
+#define GS_TERM(AP, BP)             \
+    _Pragma("unroll") for (int mi = 0; mi < 3; mi++) acc[mi][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[as][AP][mi], BP, acc[mi][ct], 0, 0, 0);
+                    GS_TERM(2, b0)
+                    GS_TERM(0, b2)
+                    GS_TERM(1, b1)
+                    GS_TERM(0, b0)
+                    GS_TERM(0, b1)
+                    GS_TERM(1, b0)
+#undef GS_TERM
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#undef GS_A
+            SSTAMP(1)
+            int lane_e;
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+            const int col_l = wv * ncol_w + 64 * b + (lane_e & 15);   // + 16 ct: this lane's column
+            float bv[4];
+#pragma unroll
+            for (int ct = 0; ct < 4; ct++) bv[ct] = sbias[col_l + 16 * ct];
+            // lane part of a C offset, both layouts: rows 4 (lane >> 4) .. + 3 are N * 16 bytes per lane group, a column 16 or 4 bytes
+            const unsigned c_l = (unsigned)((lane_e >> 4) * g.N * 16 + col_l * (g.c_quads ? 16 : 4));
+            if (g.c_quads) {
+                // [M/4][N][4]: the four registers of an accumulator tile are four consecutive rows of one column: one 16-byte store,
+                // lane -> quad row lane >> 4, column lane & 15
+#pragma unroll
+                for (int mi = 0; mi < 3; mi++)
+#pragma unroll
+                    for (int ct = 0; ct < 4; ct++) {
+                        f32x4 v;
+#pragma unroll
+                        for (int r = 0; r < 4; r++) v[r] = acc[mi][ct][r] + bv[ct];
+                        // gfx950 reads the data of a 16-byte store late: the wait states that gemm6_body's stores carry inside their
+                        // inline asm, here around the builtin (the ring's loads are in flight, and hipcc counts vmcnt only for
+                        // accesses it issued itself), fenced so that nothing is scheduled in between
+                        __builtin_amdgcn_sched_barrier(0);
+                        asm volatile("s_nop 4" ::: "memory");
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rc, c_l, (unsigned)((4 * mi * g.N + 16 * ct) * 16), 2);
+                        asm volatile("s_nop 2" ::: "memory");
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+            } else {
+#pragma unroll
+                for (int mi = 0; mi < 3; mi++)
+#pragma unroll
+                    for (int ct = 0; ct < 4; ct++)
+#pragma unroll
+                        for (int r = 0; r < 4; r++)
+                            buf_store1_nt(acc[mi][ct][r] + bv[ct], rc, c_l, (unsigned)(((16 * mi + r) * g.N + 16 * ct) * 4));
+            }
+            SSTAMP(2)
+        }
+#ifdef PV_GEMM_STAMPS
+        gs_acc[3]++;
+#endif
+    }
+#ifdef PV_GEMM_STAMPS
+    {   // [5], [6]: s_memtime and s_memrealtime (100 MHz) ticks of the whole item walk, for the clock the kernel ran at
+        unsigned long long t1, r1;
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1) :: "memory");
+        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r1) :: "memory");
+        gs_acc[5] = t1 - gs_t0;
+        gs_acc[6] = r1 - gs_r0;
+    }
+    if (blockIdx.x == 0 && lane == 0)
+        for (int i = 0; i < 8; i++) atomicAdd(&g_gemm_stamps[i], gs_acc[i]);
+#endif
+}
+
 constexpr size_t LDS_GEMM = (size_t)2 * 4 * 256 * 32 * 2 + 2048 + 2048;   // 2 buffers x {A_hi, A_lo, W_hi, W_lo} x 256 rows x 32 bf16 = 128 KB, + two bias slots + completion flags
 constexpr size_t LDS_GEMM6 = (size_t)2 * (2 * 256 + 3 * PV_GEMM6_BN) * 32 * 2 + 2048 + 2048;   // k_gemm_bf16x6: 2 buffers x ({A_hi, A_lo} x 256 rows + 3 W pieces x 128 rows) = 112 KB, + the same
 
@@ -576,9 +767,21 @@ static void gemm_launch(pv_ctx* ctx, GemmArgs& g, hipStream_t st, int terms = 3)
     else k_gemm_bf16x3<<<grid, 512, LDS_GEMM, st>>>(g);
 }
 
+// the shapes k_gemm_x6_stream takes (K is the kernel's constant; N: whole blocks of 64 columns per wave, the bias image in LDS)
+static bool gemm_stream_shape(int N, int K, int splits) { return splits == 1 && K == GS_K && N % 512 == 0 && N <= GS_MAXN; }
+
+static void gemm_stream_launch(pv_ctx* ctx, const float* A, const unsigned char* Ws, const float* bias, float* C, int64_t M, int N, int quads,
+                               hipStream_t st) {
+    GemmStreamArgs g;
+    g.A = A; g.Ws = Ws; g.bias = bias; g.C = C; g.M = M; g.N = N; g.c_quads = quads;
+    g.items = (int)((M + GS_ROWS - 1) / GS_ROWS);
+    k_gemm_x6_stream<<<(unsigned)std::min(g.items, ctx->num_cu), 512, LDS_GEMM_STREAM, st>>>(g);
+}
+
 int pv_gemm_bf16x3_prepare() {
     PV_HIP(hipFuncSetAttribute((const void*)k_gemm_bf16x3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_GEMM));
     PV_HIP(hipFuncSetAttribute((const void*)k_gemm_bf16x6, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_GEMM6));
+    PV_HIP(hipFuncSetAttribute((const void*)k_gemm_x6_stream, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_GEMM_STREAM));
     PV_CHECK(gemm_iota() != nullptr, PV_ERR_HIP, "allocation of the GEMM's flag table failed");
     return PV_OK;
 }
@@ -595,15 +798,28 @@ int pv_upload_split3(const float* w, size_t N, size_t K, unsigned char** d_plane
     return pv_dev_upload(pl, d_planes, owned);
 }
 
+int pv_upload_gemm6_stream(const float* w, size_t N, size_t K, unsigned char** d_stream, std::vector<void*>& owned) {
+    std::vector<uint16_t> sw;
+    pack_gemm6_stream(w, N, K, sw);
+    return pv_dev_upload(sw, d_stream, owned);
+}
+
 int pv_gemm_bf16x3_async(pv_ctx* ctx, const pv_gemm_desc& d, hipStream_t st) {
     PV_CHECK(d.A && d.W && d.C && d.M > 0 && d.M % 4 == 0 && d.N % 256 == 0 && d.splits >= 1 && d.K % (32 * d.splits) == 0 &&
                  (!d.quads || d.splits == 1) && (d.terms == 0 || d.terms == 3 || d.terms == 6), PV_ERR_INVALID, "bad GEMM shape");
+    pv_prof_scope ps(ctx, d.prof_name ? d.prof_name : (d.terms == 6 ? "k_gemm_bf16x6" : "k_gemm_bf16x3"), st);
+    // the six-term product at K = 512 with the stream-ordered weights at hand: A resident in LDS, W streamed (k_gemm_x6_stream);
+    // same C, bit for bit. Every other shape, and option p1_gemm6_stream = 0, keeps k_gemm_bf16x6.
+    if (d.terms == 6 && d.W_stream && ctx->opt.p1_gemm6_stream && gemm_stream_shape(d.N, d.K, d.splits)) {
+        gemm_stream_launch(ctx, reinterpret_cast<const float*>(d.A), d.W_stream, d.bias, d.C, d.M, d.N, d.quads, st);
+        PV_HIP(hipGetLastError());
+        return PV_OK;
+    }
     GemmArgs g;
     g.A = d.A; g.W = d.W; g.bias = d.bias; g.C = d.C; g.M = d.M; g.N = d.N; g.K = d.K; g.splits = d.splits;
     g.c_quads = d.quads;
     g.iota = gemm_iota();
     PV_CHECK(g.iota, PV_ERR_HIP, "GEMM flag table missing");
-    pv_prof_scope ps(ctx, d.prof_name ? d.prof_name : (d.terms == 6 ? "k_gemm_bf16x6" : "k_gemm_bf16x3"), st);
     gemm_launch(ctx, g, st, d.terms == 6 ? 6 : 3);
     PV_HIP(hipGetLastError());
     return PV_OK;
@@ -612,6 +828,7 @@ int pv_gemm_bf16x3_async(pv_ctx* ctx, const pv_gemm_desc& d, hipStream_t st) {
 // Diagnostic entry (tests, tuning): C = A . W^T + bias through k_gemm_bf16x3 alone. HOST pointers, fp32 row-major A [M,K],
 // W [N,K], bias [N] or NULL, C [splits][M][N] row-major (quads = 0) or [M/4][N][4] (quads = 1, splits must be 1).
 // M % 4 == 0, N % 256 == 0, K % (32 * splits) == 0. Returns the kernel time in ms through *ms when non-NULL.
+constexpr int TERMS_STREAM = -6;   // debug_gemm: the six-term product through k_gemm_x6_stream
 static int debug_gemm(pv_ctx* ctx, const float* A, const float* W, const float* bias, int64_t M, int N, int K, int splits, int quads,
                       float* C, float* ms, int terms) {
     PV_CHECK(ctx && A && W && C, PV_ERR_INVALID, "null argument");
@@ -622,7 +839,12 @@ static int debug_gemm(pv_ctx* ctx, const float* A, const float* W, const float* 
     float *dB = nullptr, *dC = nullptr;
     int rc;
     auto cleanup = [&]() { for (void* p : owned) (void)hipFree(p); };
-    if (terms == 6) {   // A as plain fp32 rows, W pre-split into three bf16 planes as at load time
+    if (terms == TERMS_STREAM) {   // A as plain fp32 rows, W as the fragment stream made at load time
+        PV_CHECK(gemm_stream_shape(N, K, splits), PV_ERR_INVALID, "k_gemm_x6_stream: K = 512, N a multiple of 512 up to 2048, no split-K");
+        float* fA = nullptr;
+        if ((rc = pv_dev_upload(A, (size_t)M * K, &fA, owned)) || (rc = pv_upload_gemm6_stream(W, (size_t)N, (size_t)K, &dW, owned))) { cleanup(); return rc; }
+        dA = reinterpret_cast<unsigned char*>(fA);
+    } else if (terms == 6) {   // A as plain fp32 rows, W pre-split into three bf16 planes as at load time
         float* fA = nullptr;
         if ((rc = pv_dev_upload(A, (size_t)M * K, &fA, owned)) || (rc = pv_upload_split3(W, (size_t)N, (size_t)K, &dW, owned))) { cleanup(); return rc; }
         dA = reinterpret_cast<unsigned char*>(fA);
@@ -644,9 +866,13 @@ static int debug_gemm(pv_ctx* ctx, const float* A, const float* W, const float* 
     if (!g.iota) { cleanup(); pv_set_error("GEMM flag table missing"); return PV_ERR_HIP; }
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    gemm_launch(ctx, g, ctx->stream, terms);   // warm
+    auto launch = [&]() {
+        if (terms == TERMS_STREAM) gemm_stream_launch(ctx, reinterpret_cast<const float*>(dA), dW, dB, dC, M, N, quads, ctx->stream);
+        else gemm_launch(ctx, g, ctx->stream, terms);
+    };
+    launch();   // warm
     (void)hipEventRecord(e0, ctx->stream);
-    gemm_launch(ctx, g, ctx->stream, terms);
+    launch();
     (void)hipEventRecord(e1, ctx->stream);
     hipError_t er = hipStreamSynchronize(ctx->stream);
     float t = 0.f;
@@ -672,6 +898,13 @@ extern "C" int pv_debug_gemm_bf16x3(pv_ctx* ctx, const float* A, const float* W,
 extern "C" int pv_debug_gemm_bf16x6(pv_ctx* ctx, const float* A, const float* W, const float* bias, int64_t M, int N, int K,
                                     int splits, int quads, float* C, float* ms) {
     return debug_gemm(ctx, A, W, bias, M, N, K, splits, quads, C, ms, 6);
+}
+
+// the same product through k_gemm_x6_stream (W as the fragment stream of pack_gemm6_stream, made by the function the model load
+// uses): K = 512, N a multiple of 512 up to 2048; C bit-identical to pv_debug_gemm_bf16x6's
+extern "C" int pv_debug_gemm_x6_stream(pv_ctx* ctx, const float* A, const float* W, const float* bias, int64_t M, int N, int K,
+                                       int quads, float* C, float* ms) {
+    return debug_gemm(ctx, A, W, bias, M, N, K, 1, quads, C, ms, TERMS_STREAM);
 }
 
 #ifdef PV_GEMM_STAMPS

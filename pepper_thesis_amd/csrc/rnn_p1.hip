@@ -54,6 +54,7 @@ struct pv_rnn_p1 {
     // bf16 planes [3][N][K] (split3_host.hpp), made once here
     unsigned char* enc_r6 = nullptr; unsigned char* dec_r6 = nullptr;
     unsigned char* dec_wih_p3 = nullptr;   // decoder W_ih of both directions [3][2048][512] (biases: dec_bias_cat)
+    unsigned char* dec_wih_s6 = nullptr;   // ... and as the fragment stream of k_gemm_x6_stream (pack_gemm6_stream), 6.3 MB more
     unsigned char* w1_p3 = nullptr;        // linear_1 [3][512][16896]
     unsigned char* tail_w6 = nullptr;      // three-piece fragment stream of k_tail_bf16<X6> (linear_2..5, pack_tail_x6)
     std::vector<void*> owned;
@@ -126,10 +127,12 @@ extern "C" int pv_rnn_load_p1(pv_ctx* ctx, const pv_weights_p1* w, int dtype) {
     }
     if ((rc = pv_dev_upload(bcat, &m->dec_bias_cat, m->owned))) return rc;
     const float* tail_w[4] = {w->linear_w[1], w->linear_w[2], w->linear_w[3], w->linear_w[4]};
-    if (dtype == PV_DTYPE_F32) {   // the split-6 chain of large calls: 3.4 + 3.4 + 6.3 MB of fragments, 6 + 51.9 MB of bf16 weight planes
+    if (dtype == PV_DTYPE_F32) {   // the split-6 chain of large calls: 3.4 + 3.4 + 6.3 MB of fragments, 6 + 51.9 MB of bf16 weight planes, 6.3 MB of
+                                   // the decoder W_ih again in k_gemm_x6_stream's order
         if ((rc = pv_pack_rec_x6(w->encoder, F_IN, &m->enc_r6, m->owned))) return rc;
         if ((rc = pv_pack_rec_x6(w->decoder, 0, &m->dec_r6, m->owned))) return rc;
         if ((rc = pv_upload_split3(wcat.data(), 2048, 512, &m->dec_wih_p3, m->owned))) return rc;
+        if ((rc = pv_upload_gemm6_stream(wcat.data(), 2048, 512, &m->dec_wih_s6, m->owned))) return rc;
         if ((rc = pv_upload_split3(w->linear_w[0], HEAD_N, HEAD_K, &m->w1_p3, m->owned))) return rc;
         if ((rc = pv_pack_tail_bf16(tail_w, &m->tail_w6, m->owned, 3))) return rc;
         if ((rc = pv_gemm_bf16x3_prepare()) || (rc = pv_rec_bf16_prepare()) || (rc = pv_tail_bf16_prepare())) return rc;
@@ -205,6 +208,7 @@ static int p1_forward_mfma(pv_ctx* ctx, const pv_p1_plan& pl, const int8_t* d_im
         pv_gemm_desc ga = {};
         ga.A = enc; ga.W = static_cast<const unsigned char*>(c.dec_wih); ga.bias = m->dec_bias_cat; ga.C = G; ga.M = M; ga.N = 2048;
         ga.K = 2 * H; ga.splits = 1; ga.quads = 1; ga.terms = c.terms; ga.prof_name = c.n_dec_gemm;
+        ga.W_stream = x6 ? m->dec_wih_s6 : nullptr;
         if ((rc = pv_gemm_bf16x3_async(ctx, ga, st))) return rc;
         pv_rec_desc rd = {};
         rd.cell = 4; rd.enc = 0; rd.G = G; rd.wp = c.dec_rec; rd.B = B; rd.Bp = Bp; rd.T = T_STEPS; rd.out_bm = dec;

@@ -7,7 +7,8 @@
 //   fp32 fragments, f32 MFMA    pack_lstm, pack_lstm_split, pack_linear (P1: rnn_lstm.hip, rnn_head.hip)
 //                               pack_gru, pack_gru_us (P2: rnn_gru.hip)
 //   bf16 pieces, bf16 MFMA      pack_rec_bf16, pack_rec_x6_16, pack_gru16_bf16, pack_tail_bf16, pack_tail_x6, pack_p2_dense, pack_p2_dense16 (rnn_rec_bf16.hip)
-//   GEMM operands               split8_rows (k_gemm_bf16x3); the three planes of k_gemm_bf16x6 are split3_planes (split3_host.hpp)
+//   GEMM operands               split8_rows (k_gemm_bf16x3); the three planes of k_gemm_bf16x6 are split3_planes (split3_host.hpp);
+//                               pack_gemm6_stream (k_gemm_x6_stream)
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -256,6 +257,27 @@ static inline void pack_rec_x6_16(const pv_rnn_dir* dirs, int kx, std::vector<ui
                                 pack_put_pieces(dst, lane, j, v, 3);
                             }
         }
+}
+
+// k_gemm_x6_stream (rnn_gemm.hip): W [N][K] fp32 row-major, N % 512 == 0, K % 32 == 0, as the fragment stream its eight waves read
+// front to back. Wave w owns columns [w N / 8, (w + 1) N / 8) and walks them in blocks of 64; its stream is the slots
+// [block][k-step of 32][column tile of 16], every slot three 1 KB pieces x0 | x1 | x2 (pack_put_pieces): [8 waves][N / 512 blocks]
+// [K / 32][4][3][64 lanes][8]. lane -> weight row w N / 8 + 64 block + 16 tile + (lane & 15), 8 consecutive K values
+// 32 ks + 8 (lane >> 4) + j: the B operand of v_mfma_f32_16x16x32_bf16, as in pack_rec_x6_16.
+static inline void pack_gemm6_stream(const float* w, size_t N, size_t K, std::vector<uint16_t>& wp) {
+    constexpr size_t SL = 3 * 512;
+    const size_t NB = N / 512, KS = K / 32;
+    wp.assign(8 * NB * KS * 4 * SL, 0);
+    uint16_t* dst = wp.data();
+    for (size_t wv = 0; wv < 8; wv++)
+        for (size_t b = 0; b < NB; b++)
+            for (size_t ks = 0; ks < KS; ks++)
+                for (size_t ct = 0; ct < 4; ct++, dst += SL)
+                    for (int lane = 0; lane < 64; lane++)
+                        for (int j = 0; j < 8; j++) {
+                            const size_t n = wv * (N / 8) + 64 * b + 16 * ct + (size_t)(lane & 15), k = 32 * ks + 8 * (size_t)(lane >> 4) + j;
+                            pack_put_pieces(dst, lane, j, w[n * K + k], 3);
+                        }
 }
 
 // GRU weights for k_gru16_bf16: per (direction, wave) 24 slots (ks * 3 + g) * 2 + nt of W_hh and, with kx > 0, 6 slots g * 2 + nt of
