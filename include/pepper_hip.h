@@ -454,6 +454,57 @@ int pv_polish_filter_low_qual(pv_ctx* ctx, const pv_polish_out* chunks, int64_t 
                               int32_t n_regions, int seq_length, int seq_overlap, int min_qual, uint8_t* labels_out,
                               uint8_t* row_qual_out, int64_t* counts);
 
+/* The polisher's minimum support: an edit that too few reads spell is taken back before the stitch, for the reasons and with
+ * the consequences of pv_polish_filter_low_qual above: the network sees normalised frequencies and carries state along the
+ * sequence, so it can emit a base, a deletion or an inserted base where no read, or a single read, holds it. The reference
+ * has no counterpart. KEPT, OWNED, edit, RUN and PINNED are the words of pv_polish_edits and pv_polish_filter_low_qual: the
+ * owned edit columns of a region in (position, index) order are the records pv_polish_edits_dev would emit, a run is a
+ * maximal stretch of them with position[i+1] - position[i] <= 1, runs never cross a region boundary, and a run is pinned if
+ * one of its index-0 records stands over a draft byte whose upper-case form is not in "ACGT".
+ * chunks, labels, region_start, ref_off, ref, seq_length, seq_overlap: as for pv_polish_edits_evidence_dev: chunks->counts
+ * (4-byte aligned) and chunks->depth must be there; the counts row is loaded for edit columns only, after the
+ * classification, as five dwords; the support does not depend on the depth, which is not loaded. row_qual, row_qual_out:
+ * uint8 [n_chunks][seq_length], given or NULL together; they are not judged, only copied and zeroed.
+ *   The SUPPORT of an edit column is alt_fwd + alt_rev of the pv_polish_evidence record pv_polish_edits_evidence writes for it,
+ *        with c[f] the ten counts of its own row and k(x) = 0..3 for x in A, C, G, T:
+ *          substitution to base b: c[k(b)] + c[4 + k(b)];
+ *          deletion:               c[8] + c[9] (which also count read bytes that are not ACGT);
+ *          inserted base b:        c[k(b)] + c[4 + k(b)] of the insert row's own counts.
+ *        Each addend is a uint16; the sum (up to 131070) is compared as an int and is not clamped again. Reads of mapping
+ *        quality 0 are in no count.
+ *   s = the minimum support over the run's columns: the weakest column the evidence reports for the run's VCF record.
+ *   s < min_support and not pinned: the run is REVERTED whole: its index-0 columns get the label that spells the upper-cased
+ *        draft byte, its insert columns label 0, and every such row quality 0 where a quality plane is given.
+ *   A pinned run is copied unchanged whatever s is, and so is every run with s >= min_support.
+ * Every row that is not an owned edit column of a reverted run keeps its label and quality, the non-owned duplicate of a
+ * reverted column included. min_support == 0 is the identity; the range is 0..65535; min_support == 1 is "no edit without a
+ * read behind it". labels_out == labels and row_qual_out == row_qual (in place) are allowed.
+ * Consequences: pv_polish_edits on labels_out gives the records of labels minus those of the reverted runs;
+ * pv_polish_stitch[_qual] on labels_out gives the draft with exactly the surviving records applied; every VCF record composed
+ * afterwards from pv_polish_edits_evidence has alt_fwd + alt_rev >= min_support in its weakest column (a VCF block that
+ * straddles two regions is two runs, each >= min_support). The filter commutes with pv_polish_filter_low_qual: both revert
+ * whole runs, and reverting one run neither splits nor joins another (the reverted columns stop being records, the others
+ * keep their positions and the gaps between them only grow where a run is gone whole), so either order gives the union of
+ * the reverted runs. It does not commute with pv_polish_mask_low_depth, which works per row and can split a run: the mask
+ * goes first.
+ * d_counts = {rows reverted, status, first bad chunk (-1 if none), rows of pinned runs whose support was below min_support}.
+ * Statuses and their precedence: those of pv_polish_filter_low_qual; under any status but PV_OK nothing but d_counts is
+ * written. chunks->counts == NULL or chunks->depth == NULL with n_chunks > 0, ref == NULL with n_chunks > 0, min_support
+ * outside 0..65535, 2 * seq_overlap > seq_length and exactly one of row_qual and row_qual_out given are refused with
+ * PV_ERR_INVALID by the call itself, before anything is launched. Device-resident and asynchronous on `stream`; the three
+ * launches of pv_polish_filter_low_qual_dev (its run machinery and its one-block pass; the per-chunk kernels take the value
+ * of a record from the counts row instead of the quality byte), no global atomics, no host synchronisation; capturable. */
+int pv_polish_filter_low_support_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                                     const uint8_t* row_qual, const int64_t* region_start, const int64_t* ref_off,
+                                     const uint8_t* ref, int32_t n_regions, int seq_length, int seq_overlap, int min_support,
+                                     uint8_t* labels_out, uint8_t* row_qual_out, int64_t* d_counts, void* stream);
+/* HOST buffers in and out (chunks->depth and chunks->counts too); counts[4] as d_counts above; returns the status (on an error
+ * status from the device, labels_out and row_qual_out are left as they were). */
+int pv_polish_filter_low_support(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const uint8_t* labels,
+                                 const uint8_t* row_qual, const int64_t* region_start, const int64_t* ref_off, const uint8_t* ref,
+                                 int32_t n_regions, int seq_length, int seq_overlap, int min_support, uint8_t* labels_out,
+                                 uint8_t* row_qual_out, int64_t* counts);
+
 /* The polisher's read realignment (AlignmentSummarizer.reads_to_reference_realignment, pepper/modules/python/
  * AlignmentSummarizer.py:159-177 -> ReadAligner::align_reads_to_reference, simple_aligner.cpp:66-107): every read of a region
  * is aligned to the draft with the reference's striped Smith-Waterman rules (match 4, mismatch 6, gap open 8, gap extend 2,

@@ -183,6 +183,11 @@ def polish_parser(ap=None):
                     help="keep the draft wherever the network is not sure (0..94; 0, the default, is off): every run of adjacent "
                          "edited columns whose lowest quality is below this Phred value is taken back whole before the stitch, "
                          "so FASTA, FASTQ and edits agree and every VCF record has QUAL >= it (opt-in; one device)")
+    ap.add_argument("--min_support", type=int, default=0,
+                    help="keep the draft wherever the reads do not show the edit (0..65535; 0, the default, is off): every run of "
+                         "adjacent edited columns whose weakest column fewer than this many reads spell is taken back whole "
+                         "before the stitch, so FASTA, FASTQ and edits agree and every --evidence record has AD's second number "
+                         ">= it; 1 means no edit without a read behind it (opt-in; one device)")
     ap.add_argument("-hp", "--use_hp_info", action="store_true", default=False,
                     help="one polished sequence per haplotype from the reads' HP tags: writes <output_file>/_pepper_polished_hp1.fa "
                          "and _hp2.fa (and the _hp1 / _hp2 forms of the FASTQ and the edits VCF) in place of the un-suffixed "

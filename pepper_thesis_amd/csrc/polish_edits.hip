@@ -57,26 +57,17 @@ struct EvRefs {
     pv_polish_evidence* ev;
 };
 
-// count f (0..9) of a counts row held as five dwords; selects, so the row stays in registers
-struct CountsRow { uint32_t w0, w1, w2, w3, w4; };
-__device__ __forceinline__ uint32_t row_count(const CountsRow& w, uint32_t f) {
-    const uint32_t h = f >> 1;
-    const uint32_t x = h == 0 ? w.w0 : h == 1 ? w.w1 : h == 2 ? w.w2 : h == 3 ? w.w3 : w.w4;
-    return (f & 1 ? x >> 16 : x) & 0xFFFFu;
-}
 __device__ __forceinline__ uint32_t halves(uint32_t x) { return (x & 0xFFFFu) + (x >> 16); }
-// 0..3 for A C G T (upper case), else 4
-__device__ __forceinline__ uint32_t acgt_index(uint32_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
 
-// the evidence record of the edit `e` (column_edit's word) at chunk row t, as its two dwords (the rule is in pepper_hip.h)
+// the evidence record of the edit `e` (column_edit's word) at chunk row t, as its two dwords (the rule is in pepper_hip.h;
+// the reads behind the edit are edit_alt_counts, which the minimum-support filter shares)
 __device__ __forceinline__ uint2 edit_evidence(const EvRefs& x, int64_t t, int32_t e) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(x.counts + t * 10);   // 20 bytes a row: dword aligned
-    const CountsRow w = {src[0], src[1], src[2], src[3], src[4]};
+    const CountsRow w = counts_row(x.counts, t);
     const uint32_t depth = x.depth[t];
-    const uint32_t kind = (uint32_t)e & 0xFF, d = ((uint32_t)e >> 8) & 0xFF, base = ((uint32_t)e >> 16) & 0xFF;
-    uint32_t ref, fwd, rev;
-    if (kind == PV_EDIT_DEL) { rev = row_count(w, 8); fwd = row_count(w, 9); }
-    else { const uint32_t k = acgt_index(base); rev = row_count(w, k); fwd = row_count(w, 4 + k); }
+    const uint32_t kind = (uint32_t)e & 0xFF, d = ((uint32_t)e >> 8) & 0xFF;
+    const uint2 alt = edit_alt_counts(w, e);
+    const uint32_t fwd = alt.x, rev = alt.y;
+    uint32_t ref;
     if (kind == PV_EDIT_INS) {
         const uint32_t sum = halves(w.w0) + halves(w.w1) + halves(w.w2) + halves(w.w3) + halves(w.w4);
         ref = depth > sum ? depth - sum : 0;

@@ -128,6 +128,33 @@ __device__ inline int32_t column_edit(const StitchArgs& a, const EditRefs& r, co
 
 __device__ inline bool is_edit(int32_t e) { return e != COL_NONE && e != COL_BAD_LABEL && e != COL_BAD_POS; }
 
+// one row of the builder's counts plane (pv_polish_out.counts, [row][10] uint16) held as five dwords, and count f (0..9) of
+// it. 20 bytes a row: dword aligned when the plane is. row_count takes the row by value and picks the dword with masks, so
+// that no address of a member is ever selected: a `?:` or an `if` over the members becomes an indexed load of the struct,
+// which then lives in scratch or, promoted, in 20 bytes of LDS per lane. Like this the row stays in registers (the kernels'
+// LDS is their scans' alone).
+struct CountsRow { uint32_t w0, w1, w2, w3, w4; };
+__device__ __forceinline__ CountsRow counts_row(const uint16_t* counts, int64_t t) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(counts + t * 10);
+    return CountsRow{src[0], src[1], src[2], src[3], src[4]};
+}
+__device__ __forceinline__ uint32_t row_count(CountsRow w, uint32_t f) {
+    const uint32_t h = f >> 1;
+    const uint32_t x = (w.w0 & (0u - (h == 0))) | (w.w1 & (0u - (h == 1))) | (w.w2 & (0u - (h == 2))) | (w.w3 & (0u - (h == 3))) |
+                       (w.w4 & (0u - (h == 4)));
+    return (f & 1 ? x >> 16 : x) & 0xFFFFu;
+}
+// 0..3 for A C G T (upper case), else 4
+__device__ __forceinline__ uint32_t acgt_index(uint32_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
+
+// the reads that spell the edit `e` (column_edit's word) in its own counts row: x = alt_fwd, y = alt_rev of the edit's
+// pv_polish_evidence record (the rule is in pepper_hip.h). x + y is the edit's SUPPORT (pv_polish_filter_low_support).
+__device__ __forceinline__ uint2 edit_alt_counts(const CountsRow& w, int32_t e) {
+    const uint32_t kind = (uint32_t)e & 0xFF, base = ((uint32_t)e >> 16) & 0xFF;
+    const uint32_t k = acgt_index(base), f_rev = kind == PV_EDIT_DEL ? 8u : k, f_fwd = kind == PV_EDIT_DEL ? 9u : 4u + k;
+    return make_uint2(row_count(w, f_fwd), row_count(w, f_rev));
+}
+
 // exclusive block scan; *total gets the block's sum. NT threads, NT/64 waves.
 template <int NT, typename T>
 __device__ inline T block_excl_scan(T v, T* lds, T* total) {

@@ -9,7 +9,7 @@ prediction HDF5 files. Here each batch of regions goes through
 without leaving HBM; only the region offsets and the polished bases (one byte per base) come back to the host.
 
   python -m pepper_thesis_amd polish -b reads.bam -f draft.fa -m model.pkl -o out/polished [-t 5] [-r ctg:start-end] [--bf16]
-      [--realign] [--gpu_decode] [--qualities] [--edits [--evidence]] [--min_depth N] [--min_qual Q] [-hp]
+      [--realign] [--gpu_decode] [--qualities] [--edits [--evidence]] [--min_depth N] [--min_qual Q] [--min_support K] [-hp]
 
 --gpu_decode (opt-in) replaces the first stage: reader threads only plan blocks and fetch draft bytes, and the BAM is inflated,
 decoded and clipped on the device (gpu_decode.py; _decoded_pieces below). Same FASTA.
@@ -48,6 +48,15 @@ back, in place, every run of adjacent edited columns whose lowest quality is bel
 (the rule is in include/pepper_hip.h). A run over a draft byte other than ACGT cannot be spelled and stays. Stitch, qualities
 and edits then agree without knowing of it, every VCF record has QUAL >= Q, and the VCF carries one ##pepper_min_qual=Q line.
 Without the flag no output changes by a byte. The reference has no counterpart, and no Q is recommended.
+
+--min_support K (opt-in, one device; 0 = off, 0..65535) never changes the draft to something fewer than K reads show. The
+builder also hands out the depth and the ten raw counts of every chunk row (as for --evidence), and behind the quality filter
+and before the stitch pv_polish_filter_low_support_dev takes back, in place, every run of adjacent edited columns whose
+weakest column is spelled by fewer than K reads (alt_fwd + alt_rev of the evidence rule; include/pepper_hip.h). A run over a
+draft byte other than ACGT cannot be spelled and stays. Stitch, qualities and edits then agree without knowing of it, every
+VCF record written with --evidence has AD's second number >= K, and the VCF carries one ##pepper_min_support=K line. It needs
+none of --edits, --qualities and --evidence. --min_support 1 means "no edit without a read behind it"; no larger K is
+recommended. Without the flag no output changes by a byte. The reference has no counterpart.
 
 -hp / --use_hp_info (opt-in, one device) writes one polished sequence per haplotype, `<o>/_pepper_polished_hp1.fa` and
 `_hp2.fa` (with --qualities / --edits their `_hp1` / `_hp2` forms; the un-suffixed files are not written). A launch is read,
@@ -213,6 +222,9 @@ class ChainResult(NamedTuple):
     # --min_qual: (chunk rows of edits taken back, rows of pinned runs below the threshold: draft byte not ACGT), carried the
     # same way; with_filtered()
     filtered = None
+    # --min_support: (chunk rows of edits taken back, rows of pinned runs below the minimum), carried the same way;
+    # with_supported()
+    supported = None
     # --evidence: polish_edits.EVIDENCE_DTYPE records, evidence[i] beside edits[i], carried the same way; with_evidence()
     evidence = None
 
@@ -243,13 +255,14 @@ def hp_path(path: str, haplotype: int) -> str:
 
 
 class _MaskedChainResult(ChainResult):
-    """a ChainResult with the instance attributes `masked`, `filtered` and `evidence`"""
+    """a ChainResult with the instance attributes `masked`, `filtered`, `supported` and `evidence`"""
 
 
 def with_masked(res: ChainResult, masked: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a minimum-depth chain in its attribute `masked`"""
     out = _MaskedChainResult(*res)
     out.masked, out.filtered, out.evidence = (int(masked[0]), int(masked[1])), res.filtered, res.evidence
+    out.supported = res.supported
     return out
 
 
@@ -257,6 +270,15 @@ def with_filtered(res: ChainResult, filtered: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a minimum-quality chain in its attribute `filtered`"""
     out = _MaskedChainResult(*res)
     out.masked, out.filtered, out.evidence = res.masked, (int(filtered[0]), int(filtered[1])), res.evidence
+    out.supported = res.supported
+    return out
+
+
+def with_supported(res: ChainResult, supported: Tuple[int, int]) -> ChainResult:
+    """res, carrying the counts of a minimum-support chain in its attribute `supported`"""
+    out = _MaskedChainResult(*res)
+    out.masked, out.filtered, out.evidence = res.masked, res.filtered, res.evidence
+    out.supported = (int(supported[0]), int(supported[1]))
     return out
 
 
@@ -265,6 +287,7 @@ def with_evidence(res: ChainResult, evidence: np.ndarray) -> ChainResult:
     assert res.edits is not None and len(evidence) == len(res.edits), (len(evidence), res.edits is None)
     out = _MaskedChainResult(*res)
     out.masked, out.filtered, out.evidence = res.masked, res.filtered, evidence
+    out.supported = res.supported
     return out
 
 
@@ -338,10 +361,13 @@ class _DeviceChain:
     filtered). use_hp: run / run_decoded return a HapChainResult: the batch is selected on the device by haplotype
     (pv_batch_select_hp_dev) and everything from the realigner on runs once per haplotype on the selected reads.
     evidence (needs edits): the builder also fills the depth and the counts plane, and pv_polish_edits_evidence_dev runs in
-    place of the edits call, so every edit record gets its read support (the result's evidence)."""
+    place of the edits call, so every edit record gets its read support (the result's evidence). min_support >= 1: the
+    builder also fills the depth and the counts plane and, behind the quality filter and before the stitch, every run of
+    adjacent edits whose weakest column fewer than min_support reads spell is taken back in place (the result's supported);
+    it needs neither edits nor qualities nor evidence."""
 
     def __init__(self, ctx, own_ctx: bool = False, qualities: bool = False, edits: bool = False, min_depth: int = 0,
-                 min_qual: int = 0, use_hp: bool = False, evidence: bool = False):
+                 min_qual: int = 0, use_hp: bool = False, evidence: bool = False, min_support: int = 0):
         import torch
         if evidence and not edits:
             raise ValueError("a chain with evidence needs edits: the evidence records stand beside the edit records")
@@ -355,6 +381,8 @@ class _DeviceChain:
         self.mask_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.min_qual = int(min_qual)
         self.filter_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
+        self.min_support = int(min_support)
+        self.support_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.edit_buf = None
         self.edit_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.dout = self.labels = self.seq = None
@@ -370,7 +398,8 @@ class _DeviceChain:
         import torch
         from .device import DevicePolishOut
         if self.dout is None or self.dout.capacity < chunks:
-            self.dout = DevicePolishOut(chunks, device=self.dev, depth=self.min_depth > 0 or self.evidence, counts=self.evidence)
+            want_counts = self.evidence or self.min_support > 0
+            self.dout = DevicePolishOut(chunks, device=self.dev, depth=self.min_depth > 0 or want_counts, counts=want_counts)
             self.labels = torch.zeros((chunks, 1000), dtype=torch.uint8, device=self.dev)
             self.seq = torch.zeros(chunks * 1000, dtype=torch.uint8, device=self.dev)
             if self.qualities or self.min_qual > 0:
@@ -404,15 +433,16 @@ class _DeviceChain:
                 return n
             want = n
         import torch
-        want_depth = self.min_depth > 0 or self.evidence
-        out = polish_summarize(self.ctx, host_batch(), want_depth=want_depth, **({"want_counts": True} if self.evidence else {}))
+        want_counts = self.evidence or self.min_support > 0
+        want_depth = self.min_depth > 0 or want_counts
+        out = polish_summarize(self.ctx, host_batch(), want_depth=want_depth, **({"want_counts": True} if want_counts else {}))
         n = len(out.chunk_id)
         self._ensure(n)
         for name in ("images", "position", "index", "region", "chunk_id"):
             getattr(self.dout, name)[:n].copy_(torch.from_numpy(getattr(out, name)))
         if want_depth:
             self.dout.set_depth(out.depth)
-        if self.evidence:
+        if want_counts:
             self.dout.set_row_counts(out.counts)
         return n
 
@@ -560,7 +590,8 @@ class _DeviceChain:
         return HapChainResult(tuple(results), tuple(has_reads), tags, payload)
 
     def _labels_and_stitch(self, db, n: int, n_regions: int) -> ChainResult:
-        """P2 [-> row qualities] [-> minimum-depth mask] [-> minimum-quality filter] -> stitch [-> edits] over the first n
+        """P2 [-> row qualities] [-> minimum-depth mask] [-> minimum-quality filter] [-> minimum-support filter] -> stitch
+        [-> edits] over the first n
         chunks of self.dout on the context's stream, one synchronize, then the read-back"""
         import torch
         from .polish_edits import EDIT_DTYPE, EVIDENCE_DTYPE
@@ -570,7 +601,8 @@ class _DeviceChain:
             res = res._replace(edit_off=zero.copy(), edits=np.zeros(0, EDIT_DTYPE)) if self.edits else res
             res = with_evidence(res, np.zeros(0, EVIDENCE_DTYPE)) if self.evidence else res
             res = with_masked(res, (0, 0)) if self.min_depth > 0 else res
-            return with_filtered(res, (0, 0)) if self.min_qual > 0 else res
+            res = with_filtered(res, (0, 0)) if self.min_qual > 0 else res
+            return with_supported(res, (0, 0)) if self.min_support > 0 else res
         d_acc, d_row_qual, d_qual = (t.data_ptr() for t in (self.acc, self.row_qual, self.qual)) if self.qualities else (0, 0, 0)
         # --min_qual without --qualities: the row qualities are made for the filter alone; mask, stitch and edits run as without
         d_filter_acc, d_filter_qual = (d_acc, d_row_qual) if self.qualities or self.min_qual <= 0 else (self.acc.data_ptr(),
@@ -591,6 +623,11 @@ class _DeviceChain:
             self.ctx.polish_filter_low_qual_dev(self.dout, n, d_labels, d_filter_qual, d_ref_start, db.t["ref_off"].data_ptr(),
                                                 db.t["ref"].data_ptr(), n_regions, self.min_qual, d_labels, d_filter_qual,
                                                 self.filter_counts.data_ptr())
+        if self.min_support > 0:   # and the runs that too few reads spell, by the counts of this batch's own reads; the row
+            # qualities it zeroes are those the stitch and the edits read (none without --qualities)
+            self.ctx.polish_filter_low_support_dev(self.dout, n, d_labels, d_row_qual, d_ref_start, db.t["ref_off"].data_ptr(),
+                                                   db.t["ref"].data_ptr(), n_regions, self.min_support, d_labels, d_row_qual,
+                                                   self.support_counts.data_ptr())
         self.ctx.polish_stitch_dev(self.dout, n, d_labels, d_ref_start, n_regions, roff.data_ptr(), self.seq.data_ptr(),
                                    self.seq.numel(), self.counts.data_ptr(), d_row_qual=d_row_qual, d_qual=d_qual)
         if self.edits:
@@ -616,10 +653,17 @@ class _DeviceChain:
             if status != _ffi.PV_OK:
                 raise _ffi.PepperHipError(status, "polisher minimum quality: device status %d (chunk %d)" % (status, bad))
             filtered = (n_reverted, n_pinned)
+        supported = None
+        if self.min_support > 0:
+            n_reverted, status, bad, n_pinned = (int(v) for v in self.support_counts.tolist())
+            if status != _ffi.PV_OK:
+                raise _ffi.PepperHipError(status, "polisher minimum support: device status %d (chunk %d)" % (status, bad))
+            supported = (n_reverted, n_pinned)
 
         def counted(res):
             res = res if masked is None else with_masked(res, masked)
-            return res if filtered is None else with_filtered(res, filtered)
+            res = res if filtered is None else with_filtered(res, filtered)
+            return res if supported is None else with_supported(res, supported)
         total, status, bad = (int(v) for v in self.counts[:3].tolist())
         if status != _ffi.PV_OK:   # capacity cannot run short: seq holds a byte for every column
             raise _ffi.PepperHipError(status, "polisher stitch: device status %d (chunk %d)" % (status, bad))
@@ -638,7 +682,7 @@ class _DeviceChain:
 
 def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int, qualities: bool = False,
                       edits: bool = False, min_depth: int = 0, min_qual: int = 0, use_hp: bool = False,
-                      evidence: bool = False) -> _DeviceChain:
+                      evidence: bool = False, min_support: int = 0) -> _DeviceChain:
     """a context on `device` with the polisher weights loaded, and the chain on it (closing the chain closes the context).
     shared_device: other ranks use this GPU too, so the option is set before the first device call (the split GRU forms need
     co-resident workgroups and would time out, poisoning the labels). False leaves the create-time default (PV_SHARED_DEVICE).
@@ -646,7 +690,8 @@ def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype:
     has run(batch, windows) -> ChainResult and close(). qualities, edits, min_depth, min_qual (each passed only when set):
     the chain of --qualities / --edits / --min_depth / --min_qual, whose results carry those planes and counts. use_hp
     (passed only when set): the chain of -hp, whose run gives a HapChainResult. evidence (passed only when set): the chain of
-    --evidence, whose results carry an evidence record per edit record."""
+    --evidence, whose results carry an evidence record per edit record. min_support (passed only when set): the chain of
+    --min_support, whose results carry its counts."""
     from .runtime import Context
     ctx = Context(device)
     try:
@@ -654,7 +699,8 @@ def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype:
             ctx.set_option("shared_device", 1)
         ctx.load_p2(state_dict, dtype)
         return _DeviceChain(ctx, own_ctx=True, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual,
-                            use_hp=use_hp, **({"evidence": True} if evidence else {}))
+                            use_hp=use_hp, **({"evidence": True} if evidence else {}),
+                            **({"min_support": min_support} if min_support else {}))
     except BaseException:
         ctx.close()
         raise
@@ -684,7 +730,8 @@ def _read_ahead(ex, fn, items, depth):
 def _timers(timers: Optional[dict], more=()) -> dict:
     """the caller's timer dict (or a fresh one) with the keys of polish_pieces, and `more`, present"""
     T = timers if timers is not None else {}
-    for k in ("read_s", "device_s", "regions", "batches", "masked_rows", "unmaskable_rows", "reverted_rows", "pinned_rows") + tuple(more):
+    for k in ("read_s", "device_s", "regions", "batches", "masked_rows", "unmaskable_rows", "reverted_rows", "pinned_rows",
+              "unsupported_rows", "pinned_unsupported_rows") + tuple(more):
         T.setdefault(k, 0)
     return T
 
@@ -703,13 +750,16 @@ def _thread_handles(bam: str, fasta: str):
 
 
 def _count_masked(T: dict, res) -> None:
-    """a minimum-depth chain's and a minimum-quality chain's row counts of one launch into the timers"""
+    """a minimum-depth, a minimum-quality and a minimum-support chain's row counts of one launch into the timers"""
     if getattr(res, "masked", None) is not None:
         T["masked_rows"] += res.masked[0]
         T["unmaskable_rows"] += res.masked[1]
     if getattr(res, "filtered", None) is not None:
         T["reverted_rows"] += res.filtered[0]
         T["pinned_rows"] += res.filtered[1]
+    if getattr(res, "supported", None) is not None:
+        T["unsupported_rows"] += res.supported[0]
+        T["pinned_unsupported_rows"] += res.supported[1]
 
 
 def kept_range(w: Work) -> Tuple[int, int]:
@@ -869,7 +919,8 @@ def decode_report(T: dict) -> str:
 def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region: Optional[str] = None, batch_size: int = 2048,
                  threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None,
                  realign: bool = False, chain=None, gpu_decode: bool = False, qualities: bool = False, edits: bool = False,
-                 min_depth: int = 0, min_qual: int = 0, use_hp: bool = False, evidence: bool = False) -> str:
+                 min_depth: int = 0, min_qual: int = 0, use_hp: bool = False, evidence: bool = False,
+                 min_support: int = 0) -> str:
     """-> path of the polished FASTA (use_hp: of haplotype 1's). batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
     realign: realign every read to the draft on the device before the builder, as the reference always does.
     chain: a chain with the weights already loaded (open_device_chain; the caller closes it), else one is made on `ctx`
@@ -883,6 +934,8 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
     regions without reads are filled from the draft (draft_pieces), and the VCF names the threshold.
     min_qual >= 1: this function's own chain takes back the runs of edits below it (a chain passed in must have been made
     for it), and the VCF names the threshold.
+    min_support >= 1: this function's own chain takes back the runs of edits that fewer reads spell (a chain passed in must
+    have been made for it), and the VCF names the threshold.
     use_hp: one set of files per haplotype (hp_path) in place of the un-suffixed ones; this function's own chain selects the
     reads by haplotype (a chain passed in must have been made with use_hp).
     evidence (with edits): every VCF record carries DP, AD, SAF and SAR of its weakest column (polish_edits.compose_records);
@@ -891,7 +944,7 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
     from .runtime import Context
     t_start = time.perf_counter()
     T = dict(read_s=0.0, device_s=0.0, regions=0, batches=0, bases_in=0, bases_out=0, masked_rows=0, unmaskable_rows=0, draft_regions=0,
-             reverted_rows=0, pinned_rows=0)
+             reverted_rows=0, pinned_rows=0, unsupported_rows=0, pinned_unsupported_rows=0)
     own = None
     if chain is None:
         state_dict = load_polish_model(model_path)
@@ -899,7 +952,7 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
             ctx = own = Context(0)
         ctx.load_p2(state_dict, dtype)
         chain = _DeviceChain(ctx, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual, use_hp=use_hp,
-                             **({"evidence": True} if evidence else {}))
+                             **({"evidence": True} if evidence else {}), **({"min_support": min_support} if min_support else {}))
     if evidence and not edits:
         raise ValueError("polish_fused: evidence needs edits: the numbers go into the edits VCF")
     try:
@@ -913,6 +966,9 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
         if min_qual >= 1 and getattr(chain, "min_qual", None) != min_qual:
             raise ValueError("polish_fused: the chain filters below quality %r, not %d: it was not made for this run"
                              % (getattr(chain, "min_qual", None), min_qual))
+        if min_support >= 1 and getattr(chain, "min_support", None) != min_support:
+            raise ValueError("polish_fused: the chain filters below support %r, not %d: it was not made for this run"
+                             % (getattr(chain, "min_support", None), min_support))
         if use_hp and not getattr(chain, "use_hp", False):
             raise ValueError("polish_fused: the chain does not select reads by haplotype: it was not made for this run")
         if use_hp:
@@ -941,7 +997,8 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
         if edits:
             from . import polish_edits
             polish_edits.write_edits_vcf(polish_edits.output_vcf_path(path), *vcf, **({"haplotype": h} if h else {}),
-                                         **({"evidence": True} if evidence else {}))
+                                         **({"evidence": True} if evidence else {}),
+                                         **({"min_support": min_support} if min_support else {}))
             if evidence:   # records whose alt support (of their weakest column) stands on one strand only
                 T["one_strand_records"] = T.get("one_strand_records", 0) + sum(
                     (r.evidence[2] == 0) != (r.evidence[3] == 0) for recs in vcf[4].values() for r in recs)
@@ -1025,6 +1082,15 @@ def run(args, open_chain=open_device_chain) -> int:
         sys.stderr.write("ERROR: polish --min_qual runs on one device (-d_ids %s lists %d): the row qualities are not carried "
                          "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
         return 2
+    min_support = int(getattr(args, "min_support", 0) or 0)
+    if not 0 <= min_support <= 65535:
+        sys.stderr.write("ERROR: polish --min_support %d: the minimum support is a number of reads from 0 (off) to 65535.\n"
+                         % min_support)
+        return 2
+    if min_support and len(plan) > 1:
+        sys.stderr.write("ERROR: polish --min_support runs on one device (-d_ids %s lists %d): the counts plane is not carried "
+                         "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
+        return 2
     use_hp = bool(getattr(args, "use_hp_info", False))
     if use_hp and len(plan) > 1:
         sys.stderr.write("ERROR: polish -hp runs on one device (-d_ids %s lists %d): the haplotypes are not carried through the "
@@ -1056,6 +1122,8 @@ def run(args, open_chain=open_device_chain) -> int:
         kw["use_hp"] = True
     if evidence:
         kw["evidence"] = True
+    if min_support:
+        kw["min_support"] = min_support
     chain = open_chain(device, False, state_dict, dtype, **kw)
     try:
         T = {}
@@ -1063,7 +1131,8 @@ def run(args, open_chain=open_device_chain) -> int:
                             timers=T, realign=bool(getattr(args, "realign", False)), chain=chain,
                             gpu_decode=bool(getattr(args, "gpu_decode", False)), qualities=qualities, edits=edits,
                             min_depth=min_depth, min_qual=min_qual, **({"use_hp": True} if use_hp else {}),
-                            **({"evidence": True} if evidence else {}))
+                            **({"evidence": True} if evidence else {}),
+                            **({"min_support": min_support} if min_support else {}))
     except ValueError as e:
         if not edits:
             raise
@@ -1088,6 +1157,9 @@ def run(args, open_chain=open_device_chain) -> int:
     if min_qual:
         log("MIN QUAL %d: %d CHUNK ROWS OF EDITS TAKEN BACK, %d ROWS OF LOW RUNS KEPT (DRAFT BYTE NOT ACGT)"
             % (min_qual, T["reverted_rows"], T["pinned_rows"]))
+    if min_support:
+        log("MIN SUPPORT %d: %d CHUNK ROWS OF EDITS TAKEN BACK, %d ROWS OF WEAK RUNS KEPT (DRAFT BYTE NOT ACGT)"
+            % (min_support, T["unsupported_rows"], T["pinned_unsupported_rows"]))
     if qualities:
         log("POLISHED FASTQ: " + ", ".join(output_fastq_path(p) for p in paths))
     if edits:

@@ -156,12 +156,13 @@ def no_read_runs(ranges: Iterable[Tuple[str, int, int]]) -> List[Tuple[str, int,
 
 def vcf_text(source: str, reference: str, contigs: Sequence[Tuple[str, int]], no_reads: Sequence[Tuple[str, int, int]],
              records: Dict[str, Sequence[VcfRecord]], min_depth: int = 0, min_qual: int = 0, haplotype: int = 0,
-             evidence: bool = False) -> str:
+             evidence: bool = False, min_support: int = 0) -> str:
     """header (fileformat, source, reference, one contig line per contig of the run in natural order, one pepper_no_reads line
     per read-free run, the column line) and the records, contigs in natural order; eight columns, no samples.
     min_depth >= 1 (`polish --min_depth`): one pepper_min_depth line stands in the place of the pepper_no_reads lines; the
     run then filled its read-free regions from the draft, so there are none to name.
     min_qual >= 1 (`polish --min_qual`): one pepper_min_qual line behind them, before the column line.
+    min_support >= 1 (`polish --min_support`): one pepper_min_support line behind the pepper_min_qual line.
     haplotype >= 1 (`polish -hp`): one pepper_haplotype line, the last before the column line.
     evidence (`polish --evidence`): four ##INFO lines (DP, AD, SAF, SAR) in front of the pepper_* lines, and the INFO column of
     every EvidenceVcfRecord holds its numbers (info_text); any other record keeps `.`."""
@@ -178,6 +179,8 @@ def vcf_text(source: str, reference: str, contigs: Sequence[Tuple[str, int]], no
     lines += ["##pepper_no_reads=%s:%d-%d" % r for r in no_reads]
     if min_qual >= 1:
         lines.append("##pepper_min_qual=%d" % min_qual)
+    if min_support >= 1:
+        lines.append("##pepper_min_support=%d" % min_support)
     if haplotype >= 1:
         lines.append("##pepper_haplotype=%d" % haplotype)
     lines.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO")
@@ -190,7 +193,7 @@ def vcf_text(source: str, reference: str, contigs: Sequence[Tuple[str, int]], no
 
 def write_edits_vcf(path: str, source: str, reference: str, contigs: Sequence[Tuple[str, int]],
                     no_reads: Sequence[Tuple[str, int, int]], records: Dict[str, Sequence[VcfRecord]], min_depth: int = 0,
-                    min_qual: int = 0, haplotype: int = 0, evidence: bool = False) -> None:
+                    min_qual: int = 0, haplotype: int = 0, evidence: bool = False, min_support: int = 0) -> None:
     """vcf_text through bamio.write_vcf_gz (bgzip + tabix): `path` and `path`.tbi, both written under temporary names and
     renamed when complete"""
     from . import bamio
@@ -198,7 +201,8 @@ def write_edits_vcf(path: str, source: str, reference: str, contigs: Sequence[Tu
     assert path.endswith(ext), path
     tmp = stem + ".partial" + ext
     try:
-        bamio.write_vcf_gz(tmp, vcf_text(source, reference, contigs, no_reads, records, min_depth, min_qual, haplotype, evidence))
+        bamio.write_vcf_gz(tmp, vcf_text(source, reference, contigs, no_reads, records, min_depth, min_qual, haplotype, evidence,
+                                              **({"min_support": min_support} if min_support else {})))
         os.replace(tmp + ".tbi", path + ".tbi")
         os.replace(tmp, path)
     except BaseException:

@@ -599,6 +599,51 @@ class Context:
                                                       int(min_qual), _ffi.ptr(lab_out), _ffi.ptr(rq_out), counts))
         return lab_out, rq_out
 
+    def polish_filter_low_support_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_row_qual: int,
+                                      d_region_start: int, d_ref_off: int, d_ref: int, n_regions: int, min_support: int,
+                                      d_labels_out: int, d_row_qual_out: int, d_counts: int, stream: int = 0):
+        """asynchronous, device-resident minimum-support filter (pv_polish_filter_low_support_dev): every run of adjacent owned
+        edit columns of dout's first n_chunks chunks whose weakest column is spelled by fewer than min_support reads (dout's
+        counts plane; dout must carry depth and counts) is taken back: its rows get the labels that spell the draft (insert
+        rows: 0) and quality 0; {rows reverted, status, first bad chunk, rows of pinned runs below min_support} in d_counts.
+        d_labels_out == d_labels and d_row_qual_out == d_row_qual run in place; d_row_qual 0 (with d_row_qual_out 0): no
+        quality plane."""
+        _ffi.check(self.lib.pv_polish_filter_low_support_dev(
+            self.handle, C.byref(dout.c), int(n_chunks), d_labels, d_row_qual or None, d_region_start, d_ref_off, d_ref or None,
+            int(n_regions), dout.seq_length, dout.seq_overlap, int(min_support), d_labels_out, d_row_qual_out or None, d_counts,
+            stream or None))
+
+    def polish_filter_low_support(self, out, labels: np.ndarray, batch, min_support: int, row_qual: np.ndarray = None,
+                                  seq_length: int = 1000, seq_overlap: int = 50, counts=None, in_place: bool = False):
+        """host-buffer minimum-support filter (pv_polish_filter_low_support) of a PolishOut with its depth and counts planes,
+        its labels, their row qualities (or None) and the batch they were built from (ref_start, ref_off, ref) -> (labels,
+        row_qual or None) after the filter. in_place: the arrays given (C-contiguous uint8) are rewritten and returned; else
+        copies are.
+        counts: optional ctypes int64[4] that receives {rows reverted, status, first bad chunk, rows of pinned runs below
+        min_support}, also when the call raises."""
+        n, c, keep = self._host_polish_out(out)
+        depth = None if getattr(out, "depth", None) is None else np.ascontiguousarray(out.depth, np.uint16)
+        rowc = None if getattr(out, "counts", None) is None else np.ascontiguousarray(out.counts, np.uint16)
+        c.depth, c.counts = _ffi.ptr(depth), _ffi.ptr(rowc)
+        lab = labels if in_place else np.ascontiguousarray(labels, np.uint8)
+        rq = row_qual if in_place or row_qual is None else np.ascontiguousarray(row_qual, np.uint8)
+        assert lab.dtype == np.uint8 and (rq is None or rq.dtype == np.uint8)
+        rs = np.ascontiguousarray(batch.ref_start, np.int64)
+        ro = np.ascontiguousarray(batch.ref_off, np.int64)
+        ref = None if batch.ref is None else np.ascontiguousarray(batch.ref, np.uint8)
+        assert lab.shape == (n, seq_length) and (rq is None or rq.shape == lab.shape), lab.shape
+        assert depth is None or depth.shape == lab.shape, depth.shape
+        assert rowc is None or rowc.shape == lab.shape + (10,), rowc.shape
+        assert len(ro) == len(rs) + 1 and (ref is None or len(ref) >= int(ro[-1])), (len(ro), len(rs))
+        lab_out = lab if in_place else np.zeros_like(lab)
+        rq_out = rq if in_place or rq is None else np.zeros_like(rq)
+        if counts is None:
+            counts = (C.c_int64 * 4)()
+        _ffi.check(self.lib.pv_polish_filter_low_support(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rq), _ffi.ptr(rs),
+                                                         _ffi.ptr(ro), _ffi.ptr(ref), len(rs), seq_length, int(seq_overlap),
+                                                         int(min_support), _ffi.ptr(lab_out), _ffi.ptr(rq_out), counts))
+        return lab_out, rq_out
+
     def profile_begin(self, only: str = None):
         """bracket every kernel launch of this context with HIP events (only: just the kernels whose profile name starts
         with it - two events per launch put a few microseconds between kernels)"""

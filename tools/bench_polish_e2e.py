@@ -50,7 +50,7 @@
               achieved bytes per second (payload read + payload written over its time).
 
   python tools/bench_polish_e2e.py [--leg stitch|e2e|steps|all] [--mbp 2.0] [--reps 20] [--realign] [--d_ids 0,0] [--gpu_decode]
-                                   [--qualities] [--edits [--evidence]] [--min_depth N] [--min_qual Q] [-hp] [--out f]
+                                   [--qualities] [--edits [--evidence]] [--min_depth N] [--min_qual Q] [--min_support K] [-hp] [--out f]
 For the rocprofv3 row run the stitch leg alone under `rocprofv3 --kernel-trace --stats -d <dir> -- python ... --leg stitch`.
 """
 import argparse
@@ -139,7 +139,7 @@ def stitch_leg(reps=20):
 
 
 def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False, qualities=False, edits=False, min_depth=0,
-             min_qual=0, use_hp=False, evidence=False):
+             min_qual=0, use_hp=False, evidence=False, min_support=0):
     # warm-up on a small region (code objects, allocator), then the timed run
     kw = {"gpu_decode": True} if gpu_decode else {}
     if use_hp:
@@ -148,6 +148,8 @@ def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decod
         kw["min_depth"] = min_depth
     if min_qual:
         kw["min_qual"] = min_qual
+    if min_support:
+        kw["min_support"] = min_support
     if qualities:
         kw["qualities"] = True
     if edits:
@@ -172,6 +174,8 @@ def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decod
                    draft_regions=T["draft_regions"])
     if min_qual:
         res.update(min_qual=min_qual, reverted_rows=T["reverted_rows"], pinned_rows=T["pinned_rows"])
+    if min_support:
+        res.update(min_support=min_support, unsupported_rows=T["unsupported_rows"], pinned_unsupported_rows=T["pinned_unsupported_rows"])
     if qualities:
         fq = polish.output_fastq_path(path)
         res["qualities"], res["fastq_bytes"] = True, os.path.getsize(fq)
@@ -250,19 +254,22 @@ def realign_stats(ctx, bam, fa, per_launch=1024):
             "band_gcups": round(band / (band_ms * 1e-3) / 1e9, 1) if band_ms else None}
 
 
-def _quality_events(polish, ctx, bam, fa, model, out, threads, qualities, edits=False, min_depth=0, min_qual=0, evidence=False):
+def _quality_events(polish, ctx, bam, fa, model, out, threads, qualities, edits=False, min_depth=0, min_qual=0, evidence=False,
+                    min_support=0):
     """one more run with the calls whose profile names start with polish_ bracketed by HIP events -> {name: [ms, launches]}"""
     ctx.profile_begin("polish_")
     try:
         kw = {"min_qual": min_qual} if min_qual else {}
         if evidence:
             kw["evidence"] = True
+        if min_support:
+            kw["min_support"] = min_support
         polish.polish_fused(bam, fa, model, out, threads=threads, ctx=ctx, qualities=qualities, edits=edits, min_depth=min_depth, **kw)
     finally:
         pr = ctx.profile_end()
     return {k: [round(v[0], 4), v[1]] for k, v in sorted(pr.items())
             if k in ("polish_stitch", "polish_row_qual", "polish_edits", "polish_edits_evidence", "polish_mask", "polish_filter",
-                     "polish_pipeline")}
+                     "polish_filter_support", "polish_pipeline")}
 
 
 def min_depth_leg(mbp=3.0, threads=16, min_depth=3):
@@ -304,6 +311,50 @@ def min_depth_leg(mbp=3.0, threads=16, min_depth=3):
                            "polish_mask: count + finish + write kernels of one mask call; polish_stitch: count + scan + write; HIP "
                            "events around every call of a run, summed over the run's launches. The weights are random, so the FASTA "
                            "of the plain run is not the draft and the two FASTA files differ wherever a row was masked")
+            return res
+        finally:
+            ctx.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def min_support_leg(mbp=3.0, threads=16, min_support=1):
+    """polish without and with --min_support on one synthetic contig, in one process on the same files; the quality filter
+    (--min_qual 20) is timed in the same process for comparison"""
+    import numpy as np
+    from bench_filepath import make_files
+    from pepper_thesis_amd import polish, runtime, synth
+    d = tempfile.mkdtemp(prefix="pv_polish_min_support_")
+    try:
+        bam, fa, info = make_files(d, int(mbp * 1_000_000))
+        model = os.path.join(d, "model.npz")
+        np.savez(model, **synth.make_weights_p2(4321, 3.0))
+        ctx = runtime.Context(0)
+        try:
+            # the two forms alternate, twice each: the first timed run of a process also grows the workspace to the launch size
+            runs = []
+            for k in range(2):
+                for m in (0, min_support):
+                    r = _e2e_run(polish, ctx, bam, fa, model, os.path.join(d, "supported" if m else "plain"), threads, False, info,
+                                 min_support=m)
+                    runs.append(dict(r, min_support=m, order=len(runs)))
+            res = {"runs": runs, "without_min_support": runs[2], "with_min_support": runs[3]}
+            ev = lambda name, **kw: _quality_events(polish, ctx, bam, fa, model, os.path.join(d, name), threads, False, True, **kw)
+            res["event_ms_launches"] = {
+                "without": ev("plain_ev"),
+                "with_min_support": ev("sup_ev", min_support=min_support),
+                # every run that is not pinned goes: no count reaches 65535
+                "with_min_support_65535": ev("all_ev", min_support=65535),
+                "with_min_qual_20": ev("qual_ev", min_qual=20)}
+            try:
+                with open(os.path.join(ROOT, "profiles", "polish_e2e_bench.json")) as fh:
+                    res["parent_plain_wall_s"] = json.load(fh)["e2e"]["wall_s"]
+            except (OSError, KeyError, ValueError):
+                res["parent_plain_wall_s"] = None
+            res["note"] = ("polish_pipeline: the image builder call (with the flag it also writes the depth and the counts plane); "
+                           "polish_filter_support / polish_filter: runs + carry + write kernels of one filter call; HIP events around "
+                           "every call of a run with --edits, summed over the run's launches. The weights are random, so nearly "
+                           "every column is an edit and whole regions are single runs")
             return res
         finally:
             ctx.close()
@@ -688,6 +739,9 @@ def main():
                     help="e2e leg without and with polish --min_depth N, plus HIP-event times of the builder, mask and stitch calls")
     ap.add_argument("--min_qual", type=int, default=0,
                     help="e2e leg without and with polish --min_qual Q, plus HIP-event times of the row-quality, filter, stitch and edit calls")
+    ap.add_argument("--min_support", type=int, default=0,
+                    help="e2e leg without and with polish --min_support K, plus HIP-event times of the builder, the support filter, "
+                         "the quality filter (at 20, in a run of its own), stitch and edit calls")
     ap.add_argument("-hp", "--use_hp_info", action="store_true",
                     help="e2e leg without and with polish -hp on a BAM with HP tags, plus HIP-event times of the selection, realigner and builder calls")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON to this file")
@@ -698,6 +752,8 @@ def main():
     if a.leg in ("e2e", "all"):
         if a.use_hp_info:
             out["e2e"] = hp_leg(a.mbp, a.threads)
+        elif a.min_support:
+            out["e2e"] = min_support_leg(a.mbp, a.threads, a.min_support)
         elif a.min_qual:
             out["e2e"] = min_qual_leg(a.mbp, a.threads, a.min_qual)
         elif a.min_depth:
