@@ -505,6 +505,50 @@ int pv_polish_filter_low_support(pv_ctx* ctx, const pv_polish_out* chunks, int64
                                  int32_t n_regions, int seq_length, int seq_overlap, int min_support, uint8_t* labels_out,
                                  uint8_t* row_qual_out, int64_t* counts);
 
+/* The polisher without a model: a majority vote of the reads of every chunk row, from the builder's raw counts, that writes
+ * the two planes pv_rnn_forward_p2[_dev] writes, labels and acc, so that everything behind the network (pv_polish_row_qual,
+ * the mask, the filters, the stitch, the edits and their evidence) runs on it unchanged. It is the floor a trained network
+ * is compared with, not a replacement: a pileup majority cannot mend systematic read errors (homopolymer lengths). The
+ * reference has no counterpart.
+ * chunks: position, index, region, chunk_id, depth and counts (4-byte aligned) of n_chunks chunks (pv_polish_summarize_regions
+ * [_dev] with both planes); region_start, ref_off, ref, seq_length, seq_overlap: as for pv_polish_edits_evidence_dev.
+ * Out: labels uint8 [n_chunks][seq_length]; acc float [n_chunks][seq_length][5] or NULL, which is then not written.
+ * For row j of chunk k write c[0..9] for counts[k][j], d for depth[k][j], g = region[k]:
+ *   position < 0 or index < 0 (padding): label 0, acc all 0.
+ *   index == 0 (a base row): n[b] = c[b-1] + c[4+b-1] for b = 1..4 (A, C, G, T on both strands); n[0] = c[8] + c[9] (deleted
+ *               columns and read bytes that are not ACGT, as in the evidence rule); total = n[0] + ... + n[4], from the counts
+ *               (d is not used); u = ref[ref_off[g] + position - region_start[g]] with ASCII a..z upper-cased, dl = 1 + its
+ *               place in "ACGT", or none. The winner is the b with the largest n[b]: among equal bases dl if it is one of
+ *               them, else the smallest of 1..4; label 0 (a deletion) wins only strictly ahead of every base. With total == 0
+ *               the winner is dl, and label 0 where dl is none: a column without reads over a draft byte no label spells
+ *               cannot be spelled and leaves the sequence.
+ *   index  > 0 (an insert row): n[1..4] as above from the row's own counts; n[0] = max(0, d - (c[0] + ... + c[9])) + c[8] + c[9]:
+ *               the reads over the anchor that hold nothing in this insert row, and those whose inserted byte is not ACGT;
+ *               total = n[0] + ... + n[4]. The winner is the largest; on a tie label 0 (nothing, which is the draft) wins,
+ *               then the smallest of 1..4.
+ *   acc[k][j][b] = w(j) * ((float)n[b] / (float)max(total, 1)), w(j) = 1.0f for j < seq_overlap or j >= seq_length -
+ *               seq_overlap, else 2.0f (the cnt of pv_polish_row_qual): one correctly rounded float32 divide and one multiply
+ *               by a power of two, so pv_polish_row_qual sees n / total exactly, and its Phred byte is that of the fraction of
+ *               reads that disagree with the winner (0 for a row without reads, 93 where all reads agree).
+ * Every row is treated, owned or not: two chunks that share a (position, index) hold the same counts, depth and draft byte,
+ * so they receive the same label.
+ * d_counts = {rows that are not padding whose winner is not what the draft holds (a base row with label != dl - always so
+ * where dl is none - or an insert row with label >= 1), status, first bad chunk (-1 if none), base rows with total == 0}.
+ * Status PV_ERR_INVALID: the chunk layout is broken (as for the stitch), or a base row's position lies outside
+ * [region_start[g], region_start[g] + ref_off[g+1] - ref_off[g]) - checked before the draft byte is read, which is therefore
+ * never read out of bounds; then nothing but d_counts is written. chunks->depth == NULL, chunks->counts == NULL or ref == NULL
+ * with n_chunks > 0, and 2 * seq_overlap > seq_length, are refused with PV_ERR_INVALID by the call itself, before anything
+ * is launched. Device-resident and asynchronous on `stream`; three launches (one workgroup per chunk, a one-block finish, one
+ * workgroup per chunk), no global atomics, no host synchronisation; capturable. */
+int pv_polish_vote_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const int64_t* region_start,
+                       const int64_t* ref_off, const uint8_t* ref, int32_t n_regions, int seq_length, int seq_overlap,
+                       uint8_t* labels, float* acc, int64_t* d_counts, void* stream);
+/* HOST buffers in and out (chunks->depth and chunks->counts too); counts[4] as d_counts above; returns the status (on
+ * PV_ERR_INVALID from the device, labels and acc are left as they were). */
+int pv_polish_vote(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const int64_t* region_start,
+                   const int64_t* ref_off, const uint8_t* ref, int32_t n_regions, int seq_length, int seq_overlap,
+                   uint8_t* labels, float* acc, int64_t* counts);
+
 /* The polisher's read realignment (AlignmentSummarizer.reads_to_reference_realignment, pepper/modules/python/
  * AlignmentSummarizer.py:159-177 -> ReadAligner::align_reads_to_reference, simple_aligner.cpp:66-107): every read of a region
  * is aligned to the draft with the reference's striped Smith-Waterman rules (match 4, mismatch 6, gap open 8, gap extend 2,

@@ -147,7 +147,13 @@ def polish_parser(ap=None):
     ap = ap or argparse.ArgumentParser(prog="polish")
     ap.add_argument("-b", "--bam", type=str, required=True)
     ap.add_argument("-f", "--fasta", type=str, required=True)
-    ap.add_argument("-m", "--model_path", type=str, required=True)
+    ap.add_argument("-m", "--model_path", type=str, default=None, help="the polisher model; required unless --vote is given")
+    ap.add_argument("--vote", action="store_true", default=False,
+                    help="polish without a model: every column takes what most of its reads spell, from the image builder's raw "
+                         "counts (ties keep the draft, a deletion must be strictly ahead, a column without reads keeps the "
+                         "draft), and qualities come from the fraction of reads that disagree. In place of -m and --bf16; the "
+                         "floor a trained model is compared with, not a replacement (opt-in; one device)")
+    _model_or_vote(ap)
     ap.add_argument("-o", "--output_file", type=str, required=True,
                     help="output prefix; made a directory as in the reference: the FASTA is <output_file>/_pepper_polished.fa")
     ap.add_argument("-t", "--threads", type=int, default=5, help="reader threads (with several -d_ids: the total over the ranks)")
@@ -194,6 +200,19 @@ def polish_parser(ap=None):
                          "files; haplotype h is polished with the untagged reads and those tagged HP:h, selected on the device "
                          "from one read of the BAM (opt-in; one device)")
     return ap
+
+
+def _model_or_vote(ap):
+    """-m is required unless --vote is given: the parser (a sub-command's too: its parent parses through the same method)
+    ends a command line with neither as argparse ends one that lacks a required argument, before anything is opened"""
+    parse = ap.parse_known_args
+
+    def parse_known_args(args=None, namespace=None):
+        ns, rest = parse(args, namespace)
+        if getattr(ns, "model_path", None) is None and not getattr(ns, "vote", False):
+            ap.error("the following arguments are required: -m/--model_path")
+        return ns, rest
+    ap.parse_known_args = parse_known_args
 
 
 def polish_gpu_decode_flag(ap):

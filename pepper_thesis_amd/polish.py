@@ -10,6 +10,7 @@ without leaving HBM; only the region offsets and the polished bases (one byte pe
 
   python -m pepper_thesis_amd polish -b reads.bam -f draft.fa -m model.pkl -o out/polished [-t 5] [-r ctg:start-end] [--bf16]
       [--realign] [--gpu_decode] [--qualities] [--edits [--evidence]] [--min_depth N] [--min_qual Q] [--min_support K] [-hp]
+  python -m pepper_thesis_amd polish -b reads.bam -f draft.fa --vote -o out/polished [the same flags but -m and --bf16]
 
 --gpu_decode (opt-in) replaces the first stage: reader threads only plan blocks and fetch draft bytes, and the BAM is inflated,
 decoded and clipped on the device (gpu_decode.py; _decoded_pieces below). Same FASTA.
@@ -66,6 +67,17 @@ kernels unchanged and its buffers reused. The selection's counters and read_off 
 gives no piece for h (with --min_depth it is filled from the draft), as a region without reads gives none. A launch in which
 no read is tagged runs the chain once for both. Each haplotype's files are those of a plain run on a BAM holding only the
 untagged reads and those of the haplotype. The edits VCF carries one ##pepper_haplotype=h line.
+
+--vote (opt-in, one device; in place of -m and --bf16) polishes without a model. The builder also hands out the depth and the
+ten raw counts of every chunk row (as for --evidence), and where pv_rnn_forward_p2_dev stands pv_polish_vote_dev writes the
+same two planes from them: the label most reads of the row spell (ties go to the draft; a deletion must be strictly ahead;
+the rule is in include/pepper_hip.h) and, where qualities are wanted, the fraction of the reads behind each label, so that
+a row's quality is the Phred value of the fraction of reads that disagree with the winner. Everything behind it runs
+unchanged, so every other flag works with it, and under -hp each haplotype votes with its own reads. A column without reads
+keeps the draft; over a draft byte other than ACGT it leaves the sequence, since no label spells it. The log counts the rows
+changed and the rows without reads, and the edits VCF carries one ##pepper_consensus=vote line. It is the floor a trained
+model is compared with, not a replacement: a majority cannot mend systematic read errors such as homopolymer lengths.
+Without the flag no output changes by a byte. The reference has no counterpart.
 
 Semantics kept from the reference:
   * regions: ImageGenerationUI.py:257-273 - for pos in range(start, end, 1000): [max(start, pos-100), min(end, pos+1100)],
@@ -227,6 +239,8 @@ class ChainResult(NamedTuple):
     supported = None
     # --evidence: polish_edits.EVIDENCE_DTYPE records, evidence[i] beside edits[i], carried the same way; with_evidence()
     evidence = None
+    # --vote: (chunk rows whose winner is not what the draft holds, base rows without reads), carried the same way; with_voted()
+    voted = None
 
     def region(self, g: int) -> tuple:
         """region g's share: (bases, qual or None, edits or None), and behind them its evidence records where the result
@@ -255,14 +269,14 @@ def hp_path(path: str, haplotype: int) -> str:
 
 
 class _MaskedChainResult(ChainResult):
-    """a ChainResult with the instance attributes `masked`, `filtered`, `supported` and `evidence`"""
+    """a ChainResult with the instance attributes `masked`, `filtered`, `supported`, `evidence` and `voted`"""
 
 
 def with_masked(res: ChainResult, masked: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a minimum-depth chain in its attribute `masked`"""
     out = _MaskedChainResult(*res)
     out.masked, out.filtered, out.evidence = (int(masked[0]), int(masked[1])), res.filtered, res.evidence
-    out.supported = res.supported
+    out.supported, out.voted = res.supported, res.voted
     return out
 
 
@@ -270,7 +284,7 @@ def with_filtered(res: ChainResult, filtered: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a minimum-quality chain in its attribute `filtered`"""
     out = _MaskedChainResult(*res)
     out.masked, out.filtered, out.evidence = res.masked, (int(filtered[0]), int(filtered[1])), res.evidence
-    out.supported = res.supported
+    out.supported, out.voted = res.supported, res.voted
     return out
 
 
@@ -278,7 +292,15 @@ def with_supported(res: ChainResult, supported: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a minimum-support chain in its attribute `supported`"""
     out = _MaskedChainResult(*res)
     out.masked, out.filtered, out.evidence = res.masked, res.filtered, res.evidence
-    out.supported = (int(supported[0]), int(supported[1]))
+    out.supported, out.voted = (int(supported[0]), int(supported[1])), res.voted
+    return out
+
+
+def with_voted(res: ChainResult, voted: Tuple[int, int]) -> ChainResult:
+    """res, carrying the counts of a vote chain in its attribute `voted`"""
+    out = _MaskedChainResult(*res)
+    out.masked, out.filtered, out.evidence, out.supported = res.masked, res.filtered, res.evidence, res.supported
+    out.voted = (int(voted[0]), int(voted[1]))
     return out
 
 
@@ -287,7 +309,7 @@ def with_evidence(res: ChainResult, evidence: np.ndarray) -> ChainResult:
     assert res.edits is not None and len(evidence) == len(res.edits), (len(evidence), res.edits is None)
     out = _MaskedChainResult(*res)
     out.masked, out.filtered, out.evidence = res.masked, res.filtered, evidence
-    out.supported = res.supported
+    out.supported, out.voted = res.supported, res.voted
     return out
 
 
@@ -364,11 +386,15 @@ class _DeviceChain:
     place of the edits call, so every edit record gets its read support (the result's evidence). min_support >= 1: the
     builder also fills the depth and the counts plane and, behind the quality filter and before the stitch, every run of
     adjacent edits whose weakest column fewer than min_support reads spell is taken back in place (the result's supported);
-    it needs neither edits nor qualities nor evidence."""
+    it needs neither edits nor qualities nor evidence. vote: the builder also fills the depth and the counts plane and
+    pv_polish_vote_dev stands where the network stands: the labels (and, where row qualities are needed, the read fractions
+    in the place of the softmax sums) come from the majority of the reads of every row, and the context needs no weights (the
+    result's voted)."""
 
     def __init__(self, ctx, own_ctx: bool = False, qualities: bool = False, edits: bool = False, min_depth: int = 0,
-                 min_qual: int = 0, use_hp: bool = False, evidence: bool = False, min_support: int = 0):
+                 min_qual: int = 0, use_hp: bool = False, evidence: bool = False, min_support: int = 0, vote: bool = False):
         import torch
+        self.vote = bool(vote)
         if evidence and not edits:
             raise ValueError("a chain with evidence needs edits: the evidence records stand beside the edit records")
         self.evidence = bool(evidence)
@@ -383,6 +409,7 @@ class _DeviceChain:
         self.filter_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.min_support = int(min_support)
         self.support_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
+        self.vote_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.edit_buf = None
         self.edit_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.dout = self.labels = self.seq = None
@@ -398,7 +425,7 @@ class _DeviceChain:
         import torch
         from .device import DevicePolishOut
         if self.dout is None or self.dout.capacity < chunks:
-            want_counts = self.evidence or self.min_support > 0
+            want_counts = self.evidence or self.min_support > 0 or self.vote
             self.dout = DevicePolishOut(chunks, device=self.dev, depth=self.min_depth > 0 or want_counts, counts=want_counts)
             self.labels = torch.zeros((chunks, 1000), dtype=torch.uint8, device=self.dev)
             self.seq = torch.zeros(chunks * 1000, dtype=torch.uint8, device=self.dev)
@@ -433,7 +460,7 @@ class _DeviceChain:
                 return n
             want = n
         import torch
-        want_counts = self.evidence or self.min_support > 0
+        want_counts = self.evidence or self.min_support > 0 or self.vote
         want_depth = self.min_depth > 0 or want_counts
         out = polish_summarize(self.ctx, host_batch(), want_depth=want_depth, **({"want_counts": True} if want_counts else {}))
         n = len(out.chunk_id)
@@ -590,7 +617,7 @@ class _DeviceChain:
         return HapChainResult(tuple(results), tuple(has_reads), tags, payload)
 
     def _labels_and_stitch(self, db, n: int, n_regions: int) -> ChainResult:
-        """P2 [-> row qualities] [-> minimum-depth mask] [-> minimum-quality filter] [-> minimum-support filter] -> stitch
+        """P2 (a vote chain: the majority vote) [-> row qualities] [-> minimum-depth mask] [-> minimum-quality filter] [-> minimum-support filter] -> stitch
         [-> edits] over the first n
         chunks of self.dout on the context's stream, one synchronize, then the read-back"""
         import torch
@@ -602,6 +629,7 @@ class _DeviceChain:
             res = with_evidence(res, np.zeros(0, EVIDENCE_DTYPE)) if self.evidence else res
             res = with_masked(res, (0, 0)) if self.min_depth > 0 else res
             res = with_filtered(res, (0, 0)) if self.min_qual > 0 else res
+            res = with_voted(res, (0, 0)) if self.vote else res
             return with_supported(res, (0, 0)) if self.min_support > 0 else res
         d_acc, d_row_qual, d_qual = (t.data_ptr() for t in (self.acc, self.row_qual, self.qual)) if self.qualities else (0, 0, 0)
         # --min_qual without --qualities: the row qualities are made for the filter alone; mask, stitch and edits run as without
@@ -609,7 +637,11 @@ class _DeviceChain:
                                                                                                        self.row_qual.data_ptr())
         d_labels, d_ref_start = self.labels.data_ptr(), db.t["ref_start"].data_ptr()
         roff = torch.empty(n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
-        self.ctx.forward_p2_dev(self.dout.images.data_ptr(), n, d_labels, d_filter_acc)
+        if self.vote:   # the reads' majority in the network's place: the same two planes, from the counts of this batch
+            self.ctx.polish_vote_dev(self.dout, n, d_ref_start, db.t["ref_off"].data_ptr(), db.t["ref"].data_ptr(), n_regions,
+                                     d_labels, d_filter_acc, self.vote_counts.data_ptr())
+        else:
+            self.ctx.forward_p2_dev(self.dout.images.data_ptr(), n, d_labels, d_filter_acc)
         if d_filter_qual:
             # (a label above 4 is reported by the stitch where it is on a kept column, as without qualities: the counts of
             # the row kernel are overwritten)
@@ -660,7 +692,15 @@ class _DeviceChain:
                 raise _ffi.PepperHipError(status, "polisher minimum support: device status %d (chunk %d)" % (status, bad))
             supported = (n_reverted, n_pinned)
 
+        voted = None
+        if self.vote:
+            n_changed, status, bad, n_no_reads = (int(v) for v in self.vote_counts.tolist())
+            if status != _ffi.PV_OK:
+                raise _ffi.PepperHipError(status, "polisher vote: device status %d (chunk %d)" % (status, bad))
+            voted = (n_changed, n_no_reads)
+
         def counted(res):
+            res = res if voted is None else with_voted(res, voted)
             res = res if masked is None else with_masked(res, masked)
             res = res if filtered is None else with_filtered(res, filtered)
             return res if supported is None else with_supported(res, supported)
@@ -682,7 +722,7 @@ class _DeviceChain:
 
 def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int, qualities: bool = False,
                       edits: bool = False, min_depth: int = 0, min_qual: int = 0, use_hp: bool = False,
-                      evidence: bool = False, min_support: int = 0) -> _DeviceChain:
+                      evidence: bool = False, min_support: int = 0, vote: bool = False) -> _DeviceChain:
     """a context on `device` with the polisher weights loaded, and the chain on it (closing the chain closes the context).
     shared_device: other ranks use this GPU too, so the option is set before the first device call (the split GRU forms need
     co-resident workgroups and would time out, poisoning the labels). False leaves the create-time default (PV_SHARED_DEVICE).
@@ -691,16 +731,18 @@ def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype:
     the chain of --qualities / --edits / --min_depth / --min_qual, whose results carry those planes and counts. use_hp
     (passed only when set): the chain of -hp, whose run gives a HapChainResult. evidence (passed only when set): the chain of
     --evidence, whose results carry an evidence record per edit record. min_support (passed only when set): the chain of
-    --min_support, whose results carry its counts."""
+    --min_support, whose results carry its counts. vote (passed only when set): the chain of --vote, whose results carry its
+    counts; no weights are loaded and state_dict may be None."""
     from .runtime import Context
     ctx = Context(device)
     try:
         if shared_device:
             ctx.set_option("shared_device", 1)
-        ctx.load_p2(state_dict, dtype)
+        if not vote:
+            ctx.load_p2(state_dict, dtype)
         return _DeviceChain(ctx, own_ctx=True, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual,
                             use_hp=use_hp, **({"evidence": True} if evidence else {}),
-                            **({"min_support": min_support} if min_support else {}))
+                            **({"min_support": min_support} if min_support else {}), **({"vote": True} if vote else {}))
     except BaseException:
         ctx.close()
         raise
@@ -731,7 +773,7 @@ def _timers(timers: Optional[dict], more=()) -> dict:
     """the caller's timer dict (or a fresh one) with the keys of polish_pieces, and `more`, present"""
     T = timers if timers is not None else {}
     for k in ("read_s", "device_s", "regions", "batches", "masked_rows", "unmaskable_rows", "reverted_rows", "pinned_rows",
-              "unsupported_rows", "pinned_unsupported_rows") + tuple(more):
+              "unsupported_rows", "pinned_unsupported_rows", "voted_rows", "no_read_rows") + tuple(more):
         T.setdefault(k, 0)
     return T
 
@@ -750,7 +792,7 @@ def _thread_handles(bam: str, fasta: str):
 
 
 def _count_masked(T: dict, res) -> None:
-    """a minimum-depth, a minimum-quality and a minimum-support chain's row counts of one launch into the timers"""
+    """a minimum-depth, a minimum-quality, a minimum-support and a vote chain's row counts of one launch into the timers"""
     if getattr(res, "masked", None) is not None:
         T["masked_rows"] += res.masked[0]
         T["unmaskable_rows"] += res.masked[1]
@@ -760,6 +802,9 @@ def _count_masked(T: dict, res) -> None:
     if getattr(res, "supported", None) is not None:
         T["unsupported_rows"] += res.supported[0]
         T["pinned_unsupported_rows"] += res.supported[1]
+    if getattr(res, "voted", None) is not None:
+        T["voted_rows"] += res.voted[0]
+        T["no_read_rows"] += res.voted[1]
 
 
 def kept_range(w: Work) -> Tuple[int, int]:
@@ -920,7 +965,7 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
                  threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None,
                  realign: bool = False, chain=None, gpu_decode: bool = False, qualities: bool = False, edits: bool = False,
                  min_depth: int = 0, min_qual: int = 0, use_hp: bool = False, evidence: bool = False,
-                 min_support: int = 0) -> str:
+                 min_support: int = 0, vote: bool = False) -> str:
     """-> path of the polished FASTA (use_hp: of haplotype 1's). batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
     realign: realign every read to the draft on the device before the builder, as the reference always does.
     chain: a chain with the weights already loaded (open_device_chain; the caller closes it), else one is made on `ctx`
@@ -939,20 +984,24 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
     use_hp: one set of files per haplotype (hp_path) in place of the un-suffixed ones; this function's own chain selects the
     reads by haplotype (a chain passed in must have been made with use_hp).
     evidence (with edits): every VCF record carries DP, AD, SAF and SAR of its weakest column (polish_edits.compose_records);
-    this function's own chain attaches the evidence (a chain passed in must have been made for it)."""
+    this function's own chain attaches the evidence (a chain passed in must have been made for it).
+    vote: the labels come from the reads' majority: model_path is not read (it may be None), this function's own chain votes
+    (a chain passed in must have been made for it), and the VCF names the consensus."""
     from .bamio import BamHandler, FastaHandler
     from .runtime import Context
     t_start = time.perf_counter()
     T = dict(read_s=0.0, device_s=0.0, regions=0, batches=0, bases_in=0, bases_out=0, masked_rows=0, unmaskable_rows=0, draft_regions=0,
-             reverted_rows=0, pinned_rows=0, unsupported_rows=0, pinned_unsupported_rows=0)
+             reverted_rows=0, pinned_rows=0, unsupported_rows=0, pinned_unsupported_rows=0, voted_rows=0, no_read_rows=0)
     own = None
     if chain is None:
-        state_dict = load_polish_model(model_path)
+        state_dict = None if vote else load_polish_model(model_path)
         if ctx is None:
             ctx = own = Context(0)
-        ctx.load_p2(state_dict, dtype)
+        if not vote:
+            ctx.load_p2(state_dict, dtype)
         chain = _DeviceChain(ctx, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual, use_hp=use_hp,
-                             **({"evidence": True} if evidence else {}), **({"min_support": min_support} if min_support else {}))
+                             **({"evidence": True} if evidence else {}), **({"min_support": min_support} if min_support else {}),
+                             **({"vote": True} if vote else {}))
     if evidence and not edits:
         raise ValueError("polish_fused: evidence needs edits: the numbers go into the edits VCF")
     try:
@@ -969,6 +1018,9 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
         if min_support >= 1 and getattr(chain, "min_support", None) != min_support:
             raise ValueError("polish_fused: the chain filters below support %r, not %d: it was not made for this run"
                              % (getattr(chain, "min_support", None), min_support))
+        if bool(vote) != bool(getattr(chain, "vote", False)):
+            raise ValueError("polish_fused: the chain %s: it was not made for this run"
+                             % ("does not vote" if vote else "votes in the network's place"))
         if use_hp and not getattr(chain, "use_hp", False):
             raise ValueError("polish_fused: the chain does not select reads by haplotype: it was not made for this run")
         if use_hp:
@@ -998,7 +1050,8 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
             from . import polish_edits
             polish_edits.write_edits_vcf(polish_edits.output_vcf_path(path), *vcf, **({"haplotype": h} if h else {}),
                                          **({"evidence": True} if evidence else {}),
-                                         **({"min_support": min_support} if min_support else {}))
+                                         **({"min_support": min_support} if min_support else {}),
+                                         **({"consensus": "vote"} if vote else {}))
             if evidence:   # records whose alt support (of their weakest column) stands on one strand only
                 T["one_strand_records"] = T.get("one_strand_records", 0) + sum(
                     (r.evidence[2] == 0) != (r.evidence[3] == 0) for recs in vcf[4].values() for r in recs)
@@ -1042,6 +1095,14 @@ def run(args, open_chain=open_device_chain) -> int:
     """the `polish` command. With several -d_ids: check the inputs here (no GPU API is touched), then start one rank per id
     and wait for them (polish_rank.launch). open_chain: see open_device_chain (CPU tests pass a stub)."""
     from . import cli, polish_rank
+    vote = bool(getattr(args, "vote", False))
+    if not vote and getattr(args, "model_path", None) is None:   # (a namespace not made by cli.polish_parser, which refuses this itself)
+        sys.stderr.write("ERROR: polish: the following arguments are required: -m/--model_path (or --vote, which needs no model)\n")
+        return 2
+    if vote and (getattr(args, "model_path", None) is not None or getattr(args, "bf16", False)):
+        sys.stderr.write("ERROR: polish --vote takes no %s: the vote stands in the network's place, so no model is read and none "
+                         "may be named.\n" % ("-m" if getattr(args, "model_path", None) is not None else "--bf16"))
+        return 2
     _, world, device = cli.rank_world_device(args)
     if world > 1:
         sys.stderr.write("ERROR: polish runs on one process (WORLD_SIZE=%d): multi-rank polishing is not part of this build.\n" % world)
@@ -1091,12 +1152,16 @@ def run(args, open_chain=open_device_chain) -> int:
         sys.stderr.write("ERROR: polish --min_support runs on one device (-d_ids %s lists %d): the counts plane is not carried "
                          "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
         return 2
+    if vote and len(plan) > 1:
+        sys.stderr.write("ERROR: polish --vote runs on one device (-d_ids %s lists %d): the counts plane is not carried "
+                         "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
+        return 2
     use_hp = bool(getattr(args, "use_hp_info", False))
     if use_hp and len(plan) > 1:
         sys.stderr.write("ERROR: polish -hp runs on one device (-d_ids %s lists %d): the haplotypes are not carried through the "
                          "rank exchange yet.\n" % (args.device_ids, len(plan)))
         return 2
-    for what, path in (("BAM", args.bam), ("FASTA", args.fasta), ("MODEL", args.model_path)):
+    for what, path in (("BAM", args.bam), ("FASTA", args.fasta)) + (() if vote else (("MODEL", args.model_path),)):
         if not os.path.isfile(path):
             sys.stderr.write("ERROR: CAN NOT LOCATE %s FILE.\n" % what)
             return 1
@@ -1104,7 +1169,7 @@ def run(args, open_chain=open_device_chain) -> int:
         sys.stderr.write("ERROR: THREADS AND batch_size NEED TO BE > 0.\n")
         return 1
     try:
-        state_dict = load_polish_model(args.model_path)
+        state_dict = None if vote else load_polish_model(args.model_path)
     except ValueError as e:
         sys.stderr.write("ERROR: %s\n" % e)
         return 2
@@ -1124,6 +1189,8 @@ def run(args, open_chain=open_device_chain) -> int:
         kw["evidence"] = True
     if min_support:
         kw["min_support"] = min_support
+    if vote:
+        kw["vote"] = True
     chain = open_chain(device, False, state_dict, dtype, **kw)
     try:
         T = {}
@@ -1132,7 +1199,7 @@ def run(args, open_chain=open_device_chain) -> int:
                             gpu_decode=bool(getattr(args, "gpu_decode", False)), qualities=qualities, edits=edits,
                             min_depth=min_depth, min_qual=min_qual, **({"use_hp": True} if use_hp else {}),
                             **({"evidence": True} if evidence else {}),
-                            **({"min_support": min_support} if min_support else {}))
+                            **({"min_support": min_support} if min_support else {}), **({"vote": True} if vote else {}))
     except ValueError as e:
         if not edits:
             raise
@@ -1151,6 +1218,9 @@ def run(args, open_chain=open_device_chain) -> int:
             % tuple(T.get(k, 0) for k in HP_TIMERS))
         if T.get("hp_reads", 0) == T.get("hp_untagged", 0):
             sys.stderr.write("WARNING: polish -hp: no read carries an HP tag; both haplotypes are the plain polish of all reads.\n")
+    if vote:
+        log("VOTE: %d CHUNK ROWS WHERE THE READS' MAJORITY IS NOT THE DRAFT, %d BASE ROWS WITHOUT READS (THE DRAFT IS KEPT, OR "
+            "DROPPED WHERE ITS BYTE IS NOT ACGT)" % (T["voted_rows"], T["no_read_rows"]))
     if min_depth:
         log("MIN DEPTH %d: %d CHUNK ROWS KEPT THE DRAFT, %d COULD NOT (DRAFT BYTE NOT ACGT), %d REGIONS WITHOUT READS FILLED FROM THE DRAFT"
             % (min_depth, T["masked_rows"], T["unmaskable_rows"], T["draft_regions"]))

@@ -644,6 +644,45 @@ class Context:
                                                          int(min_support), _ffi.ptr(lab_out), _ffi.ptr(rq_out), counts))
         return lab_out, rq_out
 
+    def polish_vote_dev(self, dout: "DevicePolishOut", n_chunks: int, d_region_start: int, d_ref_off: int, d_ref: int,
+                        n_regions: int, d_labels: int, d_acc: int, d_counts: int, stream: int = 0):
+        """asynchronous, device-resident majority vote (pv_polish_vote_dev), in the place of forward_p2_dev: the counts and
+        depth planes of dout's first n_chunks chunks (dout must carry both) and the draft bytes -> labels uint8 [n,L] in
+        d_labels and, unless d_acc is 0, the five read fractions of every row times the windows that cover it in d_acc, float
+        [n,L,5]; {rows whose winner is not the draft's, status, first bad chunk, base rows without reads} in d_counts."""
+        _ffi.check(self.lib.pv_polish_vote_dev(
+            self.handle, C.byref(dout.c), int(n_chunks), d_region_start, d_ref_off, d_ref or None, int(n_regions), dout.seq_length,
+            dout.seq_overlap, d_labels, d_acc or None, d_counts, stream or None))
+
+    def polish_vote(self, out, batch, seq_length: int = 1000, seq_overlap: int = 50, want_acc: bool = False, counts=None,
+                    labels: np.ndarray = None, acc: np.ndarray = None):
+        """host-buffer majority vote (pv_polish_vote) of a PolishOut with its depth and counts planes and the batch it was
+        built from (ref_start, ref_off, ref) -> labels uint8 [n,L], or (labels, acc float32 [n,L,5]) with want_acc.
+        counts: optional ctypes int64[4] that receives {rows whose winner is not the draft's, status, first bad chunk, base
+        rows without reads}, also when the call raises. labels, acc: optional C-contiguous arrays that receive the planes
+        (tests look at what the call left alone); acc implies want_acc."""
+        n, c, keep = self._host_polish_out(out)
+        depth = None if getattr(out, "depth", None) is None else np.ascontiguousarray(out.depth, np.uint16)
+        rowc = None if getattr(out, "counts", None) is None else np.ascontiguousarray(out.counts, np.uint16)
+        c.depth, c.counts = _ffi.ptr(depth), _ffi.ptr(rowc)
+        rs = np.ascontiguousarray(batch.ref_start, np.int64)
+        ro = np.ascontiguousarray(batch.ref_off, np.int64)
+        ref = None if batch.ref is None else np.ascontiguousarray(batch.ref, np.uint8)
+        assert depth is None or depth.shape == (n, seq_length), depth.shape
+        assert rowc is None or rowc.shape == (n, seq_length, 10), rowc.shape
+        assert len(ro) == len(rs) + 1 and (ref is None or len(ref) >= int(ro[-1])), (len(ro), len(rs))
+        if labels is None:
+            labels = np.zeros((n, seq_length), np.uint8)
+        if acc is None and want_acc:
+            acc = np.zeros((n, seq_length, 5), np.float32)
+        assert labels.dtype == np.uint8 and labels.shape == (n, seq_length), labels.shape
+        assert acc is None or (acc.dtype == np.float32 and acc.shape == (n, seq_length, 5)), acc.shape
+        if counts is None:
+            counts = (C.c_int64 * 4)()
+        _ffi.check(self.lib.pv_polish_vote(self.handle, C.byref(c), n, _ffi.ptr(rs), _ffi.ptr(ro), _ffi.ptr(ref), len(rs), seq_length,
+                                           int(seq_overlap), _ffi.ptr(labels), _ffi.ptr(acc), counts))
+        return labels if acc is None else (labels, acc)
+
     def profile_begin(self, only: str = None):
         """bracket every kernel launch of this context with HIP events (only: just the kernels whose profile name starts
         with it - two events per launch put a few microseconds between kernels)"""

@@ -49,8 +49,12 @@
               --realign with the selection, the realigner and the builder calls bracketed by HIP events, and the selection's
               achieved bytes per second (payload read + payload written over its time).
 
+  --vote:     `polish` with the seeded model against `polish --vote` without one: wall times of both forms, twice each, then one
+              more --vote run with --qualities whose vote kernels are bracketed by HIP events, the chunks they saw, and the
+              bytes per second the two kernels move by the per-row byte count kept in vote_leg.
+
   python tools/bench_polish_e2e.py [--leg stitch|e2e|steps|all] [--mbp 2.0] [--reps 20] [--realign] [--d_ids 0,0] [--gpu_decode]
-                                   [--qualities] [--edits [--evidence]] [--min_depth N] [--min_qual Q] [--min_support K] [-hp] [--out f]
+                                   [--qualities] [--edits [--evidence]] [--min_depth N] [--min_qual Q] [--min_support K] [-hp] [--vote] [--out f]
 For the rocprofv3 row run the stitch leg alone under `rocprofv3 --kernel-trace --stats -d <dir> -- python ... --leg stitch`.
 """
 import argparse
@@ -139,7 +143,7 @@ def stitch_leg(reps=20):
 
 
 def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False, qualities=False, edits=False, min_depth=0,
-             min_qual=0, use_hp=False, evidence=False, min_support=0):
+             min_qual=0, use_hp=False, evidence=False, min_support=0, vote=False):
     # warm-up on a small region (code objects, allocator), then the timed run
     kw = {"gpu_decode": True} if gpu_decode else {}
     if use_hp:
@@ -156,6 +160,8 @@ def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decod
         kw["edits"] = True
     if evidence:
         kw["evidence"] = True
+    if vote:
+        kw["vote"] = True
     polish.polish_fused(bam, fa, model, out + "_warm", region="chr20:0-50000", threads=threads, ctx=ctx, realign=realign, **kw)
     T = {}
     t0 = time.perf_counter()
@@ -176,6 +182,8 @@ def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decod
         res.update(min_qual=min_qual, reverted_rows=T["reverted_rows"], pinned_rows=T["pinned_rows"])
     if min_support:
         res.update(min_support=min_support, unsupported_rows=T["unsupported_rows"], pinned_unsupported_rows=T["pinned_unsupported_rows"])
+    if vote:
+        res.update(vote=True, voted_rows=T["voted_rows"], no_read_rows=T["no_read_rows"])
     if qualities:
         fq = polish.output_fastq_path(path)
         res["qualities"], res["fastq_bytes"] = True, os.path.getsize(fq)
@@ -604,6 +612,61 @@ def qualities_leg(mbp=3.0, threads=16):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def vote_leg(mbp=2.0, threads=16):
+    """polish with the seeded model and polish --vote (no model) on one synthetic contig, in one process on the same files,
+    each twice in alternation; then one more --vote run, with qualities, whose vote kernels are bracketed by HIP events
+    (k_vote_count, k_vote_write; the one-block finish between them is not bracketed) and whose chunks are counted, so that
+    the bytes the two kernels move per second can be set against the HBM peak"""
+    import numpy as np
+    from bench_filepath import make_files
+    from pepper_thesis_amd import polish, runtime, synth
+    d = tempfile.mkdtemp(prefix="pv_polish_vote_")
+    try:
+        bam, fa, info = make_files(d, int(mbp * 1_000_000))
+        model = os.path.join(d, "model.npz")
+        np.savez(model, **synth.make_weights_p2(4321, 3.0))
+        ctx = runtime.Context(0)
+        try:
+            runs = []
+            for rep in range(2):
+                for v in (False, True):
+                    r = _e2e_run(polish, ctx, bam, fa, None if v else model, os.path.join(d, "vote" if v else "model"), threads, False,
+                                 info, vote=v)
+                    runs.append(dict(r, vote=v, order=len(runs)))
+            res = {"runs": runs, "without_vote": runs[2], "with_vote": runs[3]}
+            seen = {"chunks": 0, "calls": 0}
+            real = ctx.polish_vote_dev
+
+            def counting(dout, n_chunks, *a, **k):
+                seen["chunks"] += int(n_chunks)
+                seen["calls"] += 1
+                return real(dout, n_chunks, *a, **k)
+            ctx.polish_vote_dev = counting
+            ctx.profile_begin("k_vote")
+            try:
+                polish.polish_fused(bam, fa, None, os.path.join(d, "vote_ev"), threads=threads, ctx=ctx, qualities=True, vote=True)
+            finally:
+                pr = ctx.profile_end()
+                del ctx.polish_vote_dev
+            rows = seen["chunks"] * 1000
+            ms = {k: [round(v[0], 4), v[1]] for k, v in sorted(pr.items())}
+            # per row: position 8, index 4, counts 20, depth 2 and the draft byte read by both kernels; label 1 and acc 20 written
+            count_b, write_b = rows * (8 + 4 + 20 + 2 + 1), rows * (8 + 4 + 20 + 2 + 1 + 1 + 20)
+            res["vote_kernels"] = {"chunks": seen["chunks"], "calls": seen["calls"], "kernel_ms": ms, "with_acc": True,
+                                   "bytes": {"k_vote_count": count_b, "k_vote_write": write_b}}
+            for k, b in (("k_vote_count", count_b), ("k_vote_write", write_b)):
+                if k in pr and pr[k][0] > 0:
+                    res["vote_kernels"][k + "_gb_per_s"] = round(b / (pr[k][0] * 1e-3) / 1e9, 1)
+            res["note"] = ("without_vote runs the seeded random model: its sequence is noise and only its time is of interest; "
+                           "the vote kernels' bytes count every plane a row reads once per kernel (the insert rows' depth and the "
+                           "base rows' draft byte both counted for every row)")
+            return res
+        finally:
+            ctx.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 def e2e_leg(mbp=2.0, threads=16, realign=False, gpu_decode=False):
     import numpy as np
     from bench_filepath import make_files
@@ -744,6 +807,9 @@ def main():
                          "the quality filter (at 20, in a run of its own), stitch and edit calls")
     ap.add_argument("-hp", "--use_hp_info", action="store_true",
                     help="e2e leg without and with polish -hp on a BAM with HP tags, plus HIP-event times of the selection, realigner and builder calls")
+    ap.add_argument("--vote", action="store_true",
+                    help="e2e leg with the seeded model and with polish --vote (no model), plus HIP-event times of the vote kernels "
+                         "and the bytes they move per second")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON to this file")
     a = ap.parse_args()
     out = {}
@@ -752,6 +818,8 @@ def main():
     if a.leg in ("e2e", "all"):
         if a.use_hp_info:
             out["e2e"] = hp_leg(a.mbp, a.threads)
+        elif a.vote:
+            out["e2e"] = vote_leg(a.mbp, a.threads)
         elif a.min_support:
             out["e2e"] = min_support_leg(a.mbp, a.threads, a.min_support)
         elif a.min_qual:
