@@ -907,6 +907,73 @@ int pv_graph_end(pv_ctx* ctx, pv_graph** graph);
 int pv_graph_launch(pv_graph* graph, void* stream);
 void pv_graph_destroy(pv_graph* graph);
 
+/* ---- assess: score an assembly against a truth sequence (`pepper assess`) ----------------------------------------------
+ * Identity, QV and the error breakdown of a polished (or draft) assembly against a known true sequence, contig by contig.
+ * Contigs are paired by the caller, in the same orientation, and taken to be colinear: no reverse complement and no
+ * rearrangement is looked for. The reference has no counterpart (it leaves assessment to outside tools).
+ * Constants: K = PV_ASSESS_K = 32 (anchor length), W = PV_ASSESS_W = 128 (band cells), L = `segment`. For one pair, A is the
+ * assembly (n_A bytes) and B the truth (n_B bytes), both with a..z upper-cased by the caller; bytes are compared as they
+ * stand, N included.
+ * Anchors. For k = 1 .. floor(n_A / L) the candidates are a = k*L + 32*t, t = 0..7, while a + K <= n_A. A candidate is tried
+ *   only if A[a, a+K) is ACGT-only; it is searched byte for byte in B at the start positions j in [max(0, c - max_shift),
+ *   min(n_B - K, c + max_shift)], c = floor(a * n_B / n_A) in int64. The first t whose 32-mer occurs at exactly one such j
+ *   gives anchor (a, j); if no t does, k has no anchor.
+ * Chain. Left to right from (a_prev, b_prev) = (-K, -K): an anchor is kept iff a >= a_prev + K and b >= b_prev + K.
+ * Segments. Between consecutive kept anchors: rows A[a_prev+K, a) against columns B[b_prev+K, b); the first starts at (0, 0),
+ *   the last ends at (n_A, n_B). Every kept anchor contributes K matches (the `anchor` field of the segment it ends). All
+ *   segments are global, both ends fixed; contig ends are not free. A pair has at most floor(n_A / L) + 1 segments.
+ * Band. A segment of n rows and m columns, d = m - n. |d| > PV_ASSESS_MAX_DIFF = 96: status PV_ASSESS_SEG_UNALIGNED, counts
+ *   zero, its lengths go to the unaligned totals; it is never guessed at. Else dlo = min(0, d) - floor((W - 1 - |d|) / 2);
+ *   cell c of row i is column j = i + dlo + c, valid iff 0 <= j <= m. H[0][j] = j. For i >= 1: diag = H[i-1][j-1] +
+ *   (A[i-1] != B[j-1]) for j >= 1; up = H[i-1][j] + 1; T = diag if diag <= up else up; H[i][j] = min(T, H[i][j-1] + 1), the
+ *   direction being left iff that is strictly smaller than T, else T's own. Cells outside the band or the matrix are infinite.
+ * Traceback from (n, m) by the stored directions; on row 0 every step is left. diag: a match or a substitution; up: an
+ *   insertion (an assembly base the truth lacks); left: a deletion (a truth base the assembly lacks). edge = 1 iff the path
+ *   visits band cell 0 or W-1. An inserted base x between truth bytes t[j-1] and t[j] (contig coordinates, each used where it
+ *   exists) is hp_ins iff x equals either; a deleted truth byte t[j] is hp_del iff it equals t[j-1] or t[j+1].
+ * The result is an alignment: sub + ins + del is an upper bound of the edit distance, and equals it when the optimal path
+ * stays inside the band and runs through the anchors (sparse errors). `edge` and `unaligned` say when to distrust a line.
+ *
+ * pv_assess_dev: DEVICE pointers. A, B: the pairs' bytes, pair p at [a_off[p], a_off[p+1]) and [b_off[p], b_off[p+1]);
+ * segment: a multiple of 32 in [256, 65536]; max_shift in [32, 1048576]; contigs shorter than 2^31 bytes.
+ * Out: segs[seg_capacity], pair p's records at [pair_seg_off[p], pair_seg_off[p+1]) in order; pair_seg_off[n_pairs+1];
+ * totals int64 [n_pairs][PV_ASSESS_TOTALS] = {segments, aligned, unaligned, with edge = 1, matches (anchors included),
+ * substitutions, insertions, deletions, hp_ins, hp_del, unaligned assembly bases, unaligned truth bases, anchors kept, anchors
+ * found, 0, 0}; d_counts = {records written, status, records needed, scratch bytes needed}.
+ * scratch: scratch_bytes of device memory, 256-byte aligned, at least pv_assess_scratch_bytes(): the anchor and segment
+ * tables and the direction bits (two per cell, 32 bytes per row, a lane's four bits of eight rows in one dword).
+ * Status: null pointers, negative sizes, a segment or max_shift out of range are refused with PV_ERR_INVALID by the call
+ * itself; offsets that decrease or a contig of 2^31 bytes or more are status PV_ERR_INVALID; seg_capacity below the sum of
+ * floor(n_A / L) + 1, or scratch_bytes below the need, are PV_ERR_LIMIT. Under any status but PV_OK every output but d_counts
+ * is poisoned: all seg_capacity records, pair_seg_off and totals hold -1 in every field. Asynchronous on `stream`, seven
+ * launches, no global atomics, no host read-back. */
+#define PV_ASSESS_K 32
+#define PV_ASSESS_W 128
+#define PV_ASSESS_MAX_DIFF 96
+#define PV_ASSESS_TOTALS 16
+#define PV_ASSESS_SEG_ALIGNED 0
+#define PV_ASSESS_SEG_UNALIGNED 1
+#define PV_ASSESS_SEG_BROKEN 2   /* the traceback left the band or the matrix: never expected; the counts are void */
+typedef struct pv_assess_seg {   /* 64 bytes, little-endian */
+    int64_t a_start, b_start;    /* the segment's first row / column, in contig coordinates */
+    int32_t n_rows, n_cols;
+    int32_t status;              /* PV_ASSESS_SEG_* */
+    int32_t edge;
+    int32_t match, sub, ins, del, hp_ins, hp_del;   /* of the segment's own cells (zero when unaligned) */
+    int32_t anchor;              /* K if a kept anchor ends the segment, 0 for a pair's last */
+    int32_t pair;
+} pv_assess_seg;
+int pv_assess_dev(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, const uint8_t* B, const int64_t* b_off, int64_t n_pairs,
+                  int segment, int max_shift, int64_t seg_capacity, pv_assess_seg* segs, int64_t* pair_seg_off, int64_t* totals,
+                  void* scratch, int64_t scratch_bytes, int64_t* d_counts, void* stream);
+/* HOST buffers in and out (a_off[0] = b_off[0] = 0); the scratch is the context's own. counts[4] as d_counts above; returns the
+ * status. On PV_ERR_LIMIT (seg_capacity too small; counts[2] holds the need) the outputs are poisoned as above. */
+int pv_assess(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, const uint8_t* B, const int64_t* b_off, int64_t n_pairs,
+              int segment, int max_shift, int64_t seg_capacity, pv_assess_seg* segs, int64_t* pair_seg_off, int64_t* totals,
+              int64_t* counts);
+/* bytes of scratch a batch needs, from the HOST offsets of its assemblies (negative: PV_ERR_INVALID) */
+int64_t pv_assess_scratch_bytes(int64_t n_pairs, const int64_t* a_off, int segment);
+
 /* bytes of device workspace the context currently holds (diagnostics) */
 int64_t pv_workspace_bytes(pv_ctx* ctx);
 /* library/ABI version: major*10000 + minor*100 + patch */

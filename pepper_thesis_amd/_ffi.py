@@ -66,6 +66,15 @@ PV_EDIT_SUB = 1
 PV_EDIT_DEL = 2
 PV_EDIT_INS = 3
 
+# pv_assess
+PV_ASSESS_K = 32
+PV_ASSESS_W = 128
+PV_ASSESS_MAX_DIFF = 96
+PV_ASSESS_TOTALS = 16
+PV_ASSESS_SEG_ALIGNED = 0
+PV_ASSESS_SEG_UNALIGNED = 1
+PV_ASSESS_SEG_BROKEN = 2
+
 PV_PLAN_P1_LSTM = 1
 PV_PLAN_P2_GRU = 2
 PV_DTYPE_F32 = 0
@@ -184,6 +193,12 @@ class pv_realign_out(C.Structure):
         ("n_realigned", C.c_int64),
         ("n_dropped", C.c_int64),
     ]
+
+
+class pv_assess_seg(C.Structure):
+    _fields_ = [("a_start", C.c_int64), ("b_start", C.c_int64), ("n_rows", C.c_int32), ("n_cols", C.c_int32),
+                ("status", C.c_int32), ("edge", C.c_int32), ("match", C.c_int32), ("sub", C.c_int32), ("ins", C.c_int32),
+                ("del", C.c_int32), ("hp_ins", C.c_int32), ("hp_del", C.c_int32), ("anchor", C.c_int32), ("pair", C.c_int32)]
 
 
 class pv_select_out(C.Structure):
@@ -355,6 +370,13 @@ SYMBOLS = [
     ("pv_graph_end", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     ("pv_graph_launch", C.c_int, [C.c_void_p, C.c_void_p]),
     ("pv_graph_destroy", None, [C.c_void_p]),
+    ("pv_assess_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("pv_assess", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+      C.c_void_p, C.POINTER(C.c_int64)]),
+    ("pv_assess_scratch_bytes", C.c_int64, [C.c_int64, C.c_void_p, C.c_int]),
     ("pv_workspace_bytes", C.c_int64, [C.c_void_p]),
     ("pv_version", C.c_int, []),
 ]

@@ -5,6 +5,7 @@
   make_images     BAM + draft -> image HDF5 files              (polish_steps.make_images_run)
   call_consensus  image files -> prediction HDF5 files         (polish_steps.call_consensus_run)
   stitch          prediction files -> polished FASTA           (polish_steps.stitch_run)
+  assess          polished FASTA + truth FASTA -> identity, QV and error tables, on the device (assess.run)
 
 A program of its own, as in the reference: its `make_images` is the polisher's, not the variant caller's sub-command of the
 same name (`python -m pepper_thesis_amd make_images`). download_models and torch_stat are not part of this build.
@@ -69,6 +70,27 @@ def stitch_parser(ap=None):
     return ap
 
 
+def assess_parser(ap=None):
+    """`assess`: the reference has no counterpart (it leaves assessment to outside tools)"""
+    ap = ap or argparse.ArgumentParser(prog="assess")
+    ap.add_argument("-a", "--assembly", type=str, required=True, help="FASTA of the assembly to score (the polished one)")
+    ap.add_argument("-t", "--truth", type=str, required=True,
+                    help="FASTA of the true sequence. Contigs are paired by name, in the same orientation, and taken to be "
+                         "colinear: no reverse complement and no rearrangement is looked for")
+    ap.add_argument("-o", "--output", type=str, required=True,
+                    help="output prefix: <output>_assess.tsv (one line per contig and TOTAL) and <output>_assess.segments.tsv "
+                         "(one line per segment); parent directories are created")
+    ap.add_argument("-d", "--draft", type=str, default=None,
+                    help="FASTA of the draft: scored the same way into <output>_assess_draft.tsv; the log gives errors and QV "
+                         "before -> after")
+    ap.add_argument("--segment", type=int, default=1024,
+                    help="bases between anchors, a multiple of 32 in [256, 65536]; the windowed error track has this resolution")
+    ap.add_argument("--max_shift", type=int, default=8192,
+                    help="how far from its proportional place an anchor is searched in the truth, in [32, 1048576]")
+    ap.add_argument("-d_id", "--device_id", type=int, default=0, help="the device")
+    return ap
+
+
 def parser():
     ap = argparse.ArgumentParser(prog="pepper", description="PEPPER polisher on the MI355X-native hot path: polish, or its three "
                                                             "steps make_images -> call_consensus -> stitch through files")
@@ -78,6 +100,7 @@ def parser():
     make_images_parser(sub.add_parser("make_images", help="image HDF5 files of the reads aligned to the draft"))
     call_consensus_parser(sub.add_parser("call_consensus", help="prediction HDF5 files from the image files and a model"))
     stitch_parser(sub.add_parser("stitch", help="the polished FASTA from the prediction files"))
+    assess_parser(sub.add_parser("assess", help="identity, QV and error breakdown of an assembly against a truth FASTA"))
     return ap
 
 
@@ -90,6 +113,9 @@ def main(argv=None) -> int:
     if args.sub_command == "polish":
         from . import polish
         return polish.run(args)
+    if args.sub_command == "assess":
+        from . import assess
+        return assess.run(args)
     from . import polish_steps
     if args.sub_command == "make_images":
         return polish_steps.make_images_run(args)

@@ -683,6 +683,50 @@ class Context:
                                            int(seq_overlap), _ffi.ptr(labels), _ffi.ptr(acc), counts))
         return labels if acc is None else (labels, acc)
 
+    # ---- assess ----------------------------------------------------------------------------------
+    def assess_scratch_bytes(self, a_off: np.ndarray, segment: int) -> int:
+        """bytes of scratch pv_assess_dev needs for assemblies with these (host) offsets"""
+        ao = np.ascontiguousarray(a_off, np.int64)
+        n = int(self.lib.pv_assess_scratch_bytes(len(ao) - 1, _ffi.ptr(ao), int(segment)))
+        if n < 0:
+            raise _ffi.PepperHipError(n, "assess: bad offsets or segment")
+        return n
+
+    def assess_dev(self, d_a: int, d_a_off: int, d_b: int, d_b_off: int, n_pairs: int, segment: int, max_shift: int,
+                   seg_capacity: int, d_segs: int, d_pair_seg_off: int, d_totals: int, d_scratch: int, scratch_bytes: int,
+                   d_counts: int, stream: int = 0):
+        """asynchronous, device-resident pv_assess_dev: every array is a device pointer; {records, status, records needed,
+        scratch needed} in d_counts. Under a status other than PV_OK the outputs hold -1 in every field."""
+        _ffi.check(self.lib.pv_assess_dev(self.handle, d_a or None, d_a_off, d_b or None, d_b_off, int(n_pairs), int(segment),
+                                          int(max_shift), int(seg_capacity), d_segs or None, d_pair_seg_off, d_totals or None,
+                                          d_scratch or None, int(scratch_bytes), d_counts, stream or None))
+
+    def assess(self, pairs, segment: int = 1024, max_shift: int = 8192, seg_capacity: int = None, counts=None, out=None):
+        """host-buffer pv_assess of [(assembly bytes, truth bytes)], already upper-cased -> (segs, pair_seg_off, totals):
+        segs a numpy record array of pv_assess_seg [n_segments], pair_seg_off int64 [n_pairs+1], totals int64 [n_pairs, 16].
+        seg_capacity: records to provide (default: what the pairs need). counts: optional ctypes int64[4]; out: optional
+        (segs [seg_capacity], pair_seg_off, totals) arrays that receive the outputs, also when the call raises."""
+        n = len(pairs)
+        a_off = np.zeros(n + 1, np.int64)
+        b_off = np.zeros(n + 1, np.int64)
+        a_off[1:] = np.cumsum([len(a) for a, _ in pairs])
+        b_off[1:] = np.cumsum([len(b) for _, b in pairs])
+        A = np.frombuffer(b"".join(bytes(a) for a, _ in pairs) or b"\0", np.uint8)   # (never a null pointer: one unread byte)
+        B = np.frombuffer(b"".join(bytes(b) for _, b in pairs) or b"\0", np.uint8)
+        if seg_capacity is None:
+            seg_capacity = int(sum(len(a) // int(segment) + 1 for a, _ in pairs))
+        if out is None:
+            out = (np.zeros(seg_capacity, np.dtype(_ffi.pv_assess_seg)), np.zeros(n + 1, np.int64),
+                   np.zeros((n, _ffi.PV_ASSESS_TOTALS), np.int64))
+        segs, seg_off, totals = out
+        assert segs.dtype.itemsize == 64 and len(segs) >= seg_capacity and len(seg_off) == n + 1 and totals.shape == (n, 16)
+        if counts is None:
+            counts = (C.c_int64 * 4)()
+        _ffi.check(self.lib.pv_assess(self.handle, _ffi.ptr(A), _ffi.ptr(a_off), _ffi.ptr(B), _ffi.ptr(b_off), n, int(segment), int(max_shift), int(seg_capacity),
+                                      _ffi.ptr(segs) if len(segs) else None, _ffi.ptr(seg_off), _ffi.ptr(totals) if n else None,
+                                      counts))
+        return segs[:int(counts[0])], seg_off, totals
+
     def profile_begin(self, only: str = None):
         """bracket every kernel launch of this context with HIP events (only: just the kernels whose profile name starts
         with it - two events per launch put a few microseconds between kernels)"""
