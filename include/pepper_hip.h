@@ -974,6 +974,62 @@ int pv_assess(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, const uint8_t
 /* bytes of scratch a batch needs, from the HOST offsets of its assemblies (negative: PV_ERR_INVALID) */
 int64_t pv_assess_scratch_bytes(int64_t n_pairs, const int64_t* a_off, int segment);
 
+/* ---- assess, the errors themselves and the calibration of a FASTQ's qualities (`pepper assess --errors / -q`) ------------
+ * Anchors, chain, segments, band, tie-breaks and traceback are those of pv_assess, unchanged; segs, pair_seg_off and totals
+ * are byte for byte what pv_assess_dev gives on the same inputs. What is added:
+ * Error record. One per substitution, insertion and deletion that the traceback of a segment of status
+ *   PV_ASSESS_SEG_ALIGNED meets; unaligned and broken segments give none. With i, j as in the traceback (the step leaves cell
+ *   (i, j)), a0 = a_start, b0 = b_start, in contig coordinates:
+ *     diag with unequal bytes (sub): a_pos = a0+i-1, b_pos = b0+j-1, both bases set
+ *     up (ins):    a_pos = a0+i-1, b_pos = b0+j, the truth position the base stands before (may be n_B); b_base = 0
+ *     left (del):  a_pos = a0+i, the assembly position the missing base would stand before (may be n_A), b_pos = b0+j-1;
+ *                  a_base = 0
+ *   hp is the hp_ins / hp_del test of pv_assess for that step, 0 for a substitution. A segment's records are in path order
+ *   from (0, 0) to (n, m), segments in order, pairs in order: pair p's at [pair_err_off[p], pair_err_off[p+1]).
+ * Qualities. Q, optional: uint8 parallel to A (the same a_off), raw Phred 0..93 without the +33. A substitution or insertion
+ *   has qual = Q[a_pos]; a deletion the smaller of Q[a_pos-1] and Q[a_pos], each where it lies inside the contig (a FASTQ has
+ *   no slot for a missing base: the weaker neighbour is charged), and 0 when the assembly contig is empty. Without Q, qual =
+ *   255. The device form counts a byte above 93 as 93; the host form refuses it (PV_ERR_INVALID) before any launch.
+ * Calibration table. qhist int64 [n_pairs][PV_ASSESS_QBINS][4] = {bases, sub, ins, del}: bases[q] counts the assembly bases
+ *   of quality q inside aligned segments or kept anchors (the `anchor` bytes behind a segment, whatever its status); sub, ins
+ *   and del count the error records by their qual. Over q, bases sums to the totals' match + sub + ins, and sub, ins, del to
+ *   the totals' fields. Written only with Q; Q without qhist or the reverse is PV_ERR_INVALID by the call itself.
+ *
+ * pv_assess_errors_dev: DEVICE pointers; errs[err_capacity] aligned to 8 bytes (else PV_ERR_INVALID), pair_err_off
+ * [n_pairs+1]; d_counts int64[8] = {segment records, status, slots needed, scratch needed, error records written, error
+ * records needed, 0, 0}; scratch at least pv_assess_errors_scratch_bytes() (pv_assess's, plus a count and an offset per slot
+ * and a partial table of 94 x 4 uint32 per slot).
+ * Status, in this precedence: PV_ERR_INVALID and PV_ERR_LIMIT exactly as in pv_assess_dev; every output, the new ones
+ * included, is then poisoned (-1 in every field, all err_capacity records bytes 0xFF; d_counts[4] = 0, d_counts[5] = -1).
+ * Else PV_ERR_CAPACITY when err_capacity is below the records needed: every output but errs is valid, d_counts[4] = 0,
+ * d_counts[5] holds the need and no error record is written (the buffer stays as it was). Asynchronous on `stream`: the seven
+ * launches of pv_assess_dev and up to six more, no global atomics, no host read-back. */
+#define PV_ASSESS_QBINS 94
+#define PV_ASSESS_ERR_SUB 1
+#define PV_ASSESS_ERR_INS 2
+#define PV_ASSESS_ERR_DEL 3
+typedef struct pv_assess_error {   /* 32 bytes, little-endian */
+    int64_t a_pos, b_pos;          /* contig coordinates, 0-based */
+    int32_t pair, segment;         /* segment = index within the pair */
+    uint8_t kind;                  /* PV_ASSESS_ERR_* */
+    uint8_t a_base, b_base;        /* 0 where the side has no base */
+    uint8_t hp;
+    uint8_t qual;                  /* 255 when Q is NULL */
+    uint8_t pad[3];                /* 0 */
+} pv_assess_error;
+int pv_assess_errors_dev(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, const uint8_t* B, const int64_t* b_off,
+                         int64_t n_pairs, int segment, int max_shift, int64_t seg_capacity, pv_assess_seg* segs,
+                         int64_t* pair_seg_off, int64_t* totals, const uint8_t* Q, int64_t err_capacity, pv_assess_error* errs,
+                         int64_t* pair_err_off, int64_t* qhist, void* scratch, int64_t scratch_bytes, int64_t* d_counts,
+                         void* stream);
+/* HOST buffers in and out, the scratch the context's own; counts[8] as d_counts. Returns the status. On PV_ERR_CAPACITY the
+ * need is in counts[5], errs is untouched and every other output is filled; on PV_ERR_LIMIT all outputs are poisoned. */
+int pv_assess_errors(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, const uint8_t* B, const int64_t* b_off, int64_t n_pairs,
+                     int segment, int max_shift, int64_t seg_capacity, pv_assess_seg* segs, int64_t* pair_seg_off,
+                     int64_t* totals, const uint8_t* Q, int64_t err_capacity, pv_assess_error* errs, int64_t* pair_err_off,
+                     int64_t* qhist, int64_t* counts);
+int64_t pv_assess_errors_scratch_bytes(int64_t n_pairs, const int64_t* a_off, int segment);
+
 /* bytes of device workspace the context currently holds (diagnostics) */
 int64_t pv_workspace_bytes(pv_ctx* ctx);
 /* library/ABI version: major*10000 + minor*100 + patch */

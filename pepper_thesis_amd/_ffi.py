@@ -74,6 +74,10 @@ PV_ASSESS_TOTALS = 16
 PV_ASSESS_SEG_ALIGNED = 0
 PV_ASSESS_SEG_UNALIGNED = 1
 PV_ASSESS_SEG_BROKEN = 2
+PV_ASSESS_QBINS = 94
+PV_ASSESS_ERR_SUB = 1
+PV_ASSESS_ERR_INS = 2
+PV_ASSESS_ERR_DEL = 3
 
 PV_PLAN_P1_LSTM = 1
 PV_PLAN_P2_GRU = 2
@@ -199,6 +203,11 @@ class pv_assess_seg(C.Structure):
     _fields_ = [("a_start", C.c_int64), ("b_start", C.c_int64), ("n_rows", C.c_int32), ("n_cols", C.c_int32),
                 ("status", C.c_int32), ("edge", C.c_int32), ("match", C.c_int32), ("sub", C.c_int32), ("ins", C.c_int32),
                 ("del", C.c_int32), ("hp_ins", C.c_int32), ("hp_del", C.c_int32), ("anchor", C.c_int32), ("pair", C.c_int32)]
+
+
+class pv_assess_error(C.Structure):
+    _fields_ = [("a_pos", C.c_int64), ("b_pos", C.c_int64), ("pair", C.c_int32), ("segment", C.c_int32), ("kind", C.c_uint8),
+                ("a_base", C.c_uint8), ("b_base", C.c_uint8), ("hp", C.c_uint8), ("qual", C.c_uint8), ("pad", C.c_uint8 * 3)]
 
 
 class pv_select_out(C.Structure):
@@ -377,6 +386,13 @@ SYMBOLS = [
      [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
       C.c_void_p, C.POINTER(C.c_int64)]),
     ("pv_assess_scratch_bytes", C.c_int64, [C.c_int64, C.c_void_p, C.c_int]),
+    ("pv_assess_errors_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("pv_assess_errors", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    ("pv_assess_errors_scratch_bytes", C.c_int64, [C.c_int64, C.c_void_p, C.c_int]),
     ("pv_workspace_bytes", C.c_int64, [C.c_void_p]),
     ("pv_version", C.c_int, []),
 ]

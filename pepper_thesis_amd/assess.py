@@ -6,6 +6,11 @@ stretches between them globally in a band of 128 cells (the rule: include/pepper
 alignment: substitutions + insertions + deletions is an upper bound of the edit distance and equals it where the errors are
 sparse. Segments whose lengths differ by more than 96 are `unaligned` and never guessed at; `unaligned` and `edge` (the path
 touched the band's rim) are the warning signs of a line. The reference has no counterpart.
+
+--errors keeps the traceback's path: every substitution, insertion and deletion in assembly and truth coordinates
+(<o>_assess.errors.tsv). -q FILE reads the qualities `polish --qualities` wrote for the assembly and tabulates, per contig and
+quality value, how many bases carry it and how many errors were charged to it (<o>_assess.calibration.tsv): predicted quality
+against observed error rate (the rule: include/pepper_hip.h, pv_assess_errors). The tool reports; it recommends no threshold.
 """
 import math
 import os
@@ -24,6 +29,10 @@ CONTIG_HEADER = ("#name\tstatus\tassembly_length\ttruth_length\taligned_columns\
                  "unaligned_truth_bases\tidentity\tQV\n")
 SEGMENT_HEADER = ("#name\tsegment\tassembly_start\tassembly_end\ttruth_start\ttruth_end\tstatus\tedge\tanchor_matches\tmatches\t"
                   "substitutions\tinsertions\tdeletions\thp_ins\thp_del\n")
+ERRORS_HEADER = "#name\tkind\tassembly_pos\ttruth_pos\tassembly_base\ttruth_base\thp\tqual\tsegment\n"
+CALIBRATION_HEADER = "#name\tqual\tbases\tsubstitutions\tinsertions\tdeletions\terrors\tcolumns\tobserved_QV\n"
+QBINS = 94
+KIND_NAME = {1: "sub", 2: "ins", 3: "del"}
 
 
 def log(msg):
@@ -59,6 +68,39 @@ def read_fasta(path: str) -> List[Tuple[str, bytes]]:
     return out
 
 
+def read_fastq(path: str, asm) -> Dict[str, np.ndarray]:
+    """the qualities of the assembly asm = [(name, sequence)]: four-line records as `polish --qualities` writes them (@name
+    first word, sequence, +, quality) -> {name: raw Phred uint8 array, 0..93}. Refused, naming the contig: a record that is
+    not four lines, a quality string of another length than its sequence, a byte outside '!'..'~', a name that occurs twice, a
+    sequence that differs from the assembly's (letter case aside), a non-empty contig of the assembly that is missing"""
+    with open(path, "rb") as fh:
+        lines = fh.read().split(b"\n")
+    if lines and lines[-1] == b"":   # what follows the last newline; an empty contig ends in an empty quality line
+        lines.pop()
+    want = {n: upper(s) for n, s in asm}
+    out = {}
+    for k in range(0, len(lines), 4):
+        rec = [ln.rstrip(b"\r") for ln in lines[k:k + 4]]
+        words = rec[0][1:].split()
+        name = words[0].decode() if rec[0].startswith(b"@") and words else "record %d" % (k // 4 + 1)
+        if len(rec) < 4 or not rec[0].startswith(b"@") or not rec[2].startswith(b"+"):
+            raise AssessError("%s: %s is not a four-line record" % (path, name))
+        if len(rec[3]) != len(rec[1]):
+            raise AssessError("%s: contig %s has %d qualities for %d bases" % (path, name, len(rec[3]), len(rec[1])))
+        q = np.frombuffer(rec[3], np.uint8)
+        if len(q) and (int(q.min()) < 33 or int(q.max()) > 126):
+            raise AssessError("%s: contig %s has a quality byte outside '!'..'~'" % (path, name))
+        if name in out:
+            raise AssessError("%s: contig %s occurs twice" % (path, name))
+        if name in want and upper(rec[1]) != want[name]:
+            raise AssessError("%s: the sequence of contig %s differs from the assembly's" % (path, name))
+        out[name] = (q - 33).astype(np.uint8)
+    for n, s in asm:
+        if len(s) and n not in out:
+            raise AssessError("%s: contig %s of the assembly is missing" % (path, n))
+    return out
+
+
 def upper(seq: bytes) -> bytes:
     """bytes a..z upper-cased; everything else stays"""
     a = np.frombuffer(seq, np.uint8).copy()
@@ -79,12 +121,18 @@ def direction_bytes(n_a: int, segment: int) -> int:
     return 32 * n_a + 256 * (n_a // segment + 1)
 
 
-def pack_launches(lengths: Sequence[int], segment: int, budget: int = DEFAULT_WORKSPACE) -> List[List[int]]:
+def error_bytes(n_a: int, segment: int) -> int:
+    """what --errors / -q add to one pair's scratch: per segment slot an error count, an error offset and a partial quality
+    table of 94 x 4 uint32"""
+    return (8 + 8 + 4 * 4 * QBINS) * (n_a // segment + 1)
+
+
+def pack_launches(lengths: Sequence[int], segment: int, budget: int = DEFAULT_WORKSPACE, errors: bool = False) -> List[List[int]]:
     """assembly lengths of the pairs, in order -> the pairs of each launch: consecutive pairs while their direction scratch
-    stays within the budget; a pair that alone needs more gets a launch of its own"""
+    (with errors: and the error pass's tables) stays within the budget; a pair that alone needs more gets a launch of its own"""
     out, cur, used = [], [], 0
     for i, n in enumerate(lengths):
-        need = direction_bytes(n, segment)
+        need = direction_bytes(n, segment) + (error_bytes(n, segment) if errors else 0)
         if cur and used + need > budget:
             out.append(cur)
             cur, used = [], 0
@@ -105,6 +153,54 @@ def assess_pairs(ctx, pairs: Sequence[Tuple[bytes, bytes]], segment: int, max_sh
         for k, i in enumerate(launch):
             res[i] = (segs[int(off[k]):int(off[k + 1])].copy(), dict(zip(TOTAL_FIELDS, (int(v) for v in totals[k]))))
     return res
+
+
+def assess_pairs_errors(ctx, pairs, quals, segment: int, max_shift: int, budget: int = DEFAULT_WORKSPACE):
+    """as assess_pairs, through pv_assess_errors; quals: one raw Phred array per pair, or None -> per pair (segment records,
+    totals dict, error records, qhist [94][4] or None)"""
+    res = [None] * len(pairs)
+    for launch in pack_launches([len(a) for a, _ in pairs], segment, budget, errors=True):
+        segs, off, totals, errs, eoff, qhist = ctx.assess_errors([pairs[i] for i in launch],
+                                                                 None if quals is None else [quals[i] for i in launch],
+                                                                 segment, max_shift)
+        if len(segs) and int(segs["status"].max()) > 1:
+            raise RuntimeError("assess: a traceback left its band (segment status %d)" % int(segs["status"].max()))
+        for k, i in enumerate(launch):
+            res[i] = (segs[int(off[k]):int(off[k + 1])].copy(), dict(zip(TOTAL_FIELDS, (int(v) for v in totals[k]))),
+                      errs[int(eoff[k]):int(eoff[k + 1])].copy(), None if qhist is None else qhist[k].copy())
+    return res
+
+
+def error_line(name: str, r) -> str:
+    def base(x):
+        return chr(x) if x else "."
+    return "\t".join([name, KIND_NAME[int(r["kind"])], str(int(r["a_pos"])), str(int(r["b_pos"])), base(int(r["a_base"])),
+                      base(int(r["b_base"])), str(int(r["hp"])), "." if int(r["qual"]) == 255 else str(int(r["qual"])),
+                      str(int(r["segment"]))]) + "\n"
+
+
+def calibration_lines(name: str, hist) -> str:
+    """one line per quality value that has a base or an error: columns = bases + deletions, errors = S + I + D"""
+    out = []
+    for q in range(QBINS):
+        b, s, i, d = (int(v) for v in hist[q])
+        if b + s + i + d:
+            err, cols = s + i + d, b + d
+            qv = "inf" if err == 0 else "%.2f" % (-10.0 * math.log10(err / cols) + 0.0)   # (+ 0.0: no "-0.00")
+            out.append("\t".join([name] + [str(v) for v in (q, b, s, i, d, err, cols)] + [qv]) + "\n")
+    return "".join(out)
+
+
+def calibrated_from(hist):
+    """the lowest quality value q of the table such that the bases of quality q or more have an observed QV of at least q;
+    None if no value of the table does"""
+    for q in range(QBINS):
+        if not hist[q].sum():
+            continue
+        err, cols = int(hist[q:, 1:].sum()), int(hist[q:, 0].sum() + hist[q:, 3].sum())
+        if err == 0 or -10.0 * math.log10(err / cols) >= q:
+            return q
+    return None
 
 
 def identity_qv(M: int, S: int, I: int, D: int) -> Tuple[str, str]:
@@ -132,6 +228,16 @@ def pair_names(asm, truth):
 
 def tables(ctx, asm, truth, segment: int, max_shift: int, budget: int = DEFAULT_WORKSPACE):
     """-> (text of the contig table, text of the segment table, TOTAL's dict)"""
+    return _tables(ctx, asm, truth, segment, max_shift, budget)[:3]
+
+
+def error_tables(ctx, asm, truth, segment: int, max_shift: int, quals=None, budget: int = DEFAULT_WORKSPACE):
+    """quals: {name: raw Phred array} of the assembly, or None -> (text of the contig table, of the segment table, TOTAL's
+    dict, text of the error list, text of the calibration table or None, TOTAL's quality table or None)"""
+    return _tables(ctx, asm, truth, segment, max_shift, budget, True, quals)
+
+
+def _tables(ctx, asm, truth, segment: int, max_shift: int, budget: int, errors: bool = False, quals=None):
     paired, lone = pair_names(asm, truth)
     if not paired:
         raise AssessError("no contig name occurs in both files")
@@ -140,7 +246,12 @@ def tables(ctx, asm, truth, segment: int, max_shift: int, budget: int = DEFAULT_
         if len(am[n]) >= MAX_CONTIG or len(tr[n]) >= MAX_CONTIG:
             raise AssessError("contig %s holds 2^31 bytes or more" % n)
     pairs = [(upper(am[n]), upper(tr[n])) for n in paired]
-    res = dict(zip(paired, assess_pairs(ctx, pairs, segment, max_shift, budget)))
+    if errors:
+        q = None if quals is None else [quals.get(n, np.zeros(0, np.uint8)) for n in paired]
+        res = dict(zip(paired, assess_pairs_errors(ctx, pairs, q, segment, max_shift, budget)))
+    else:
+        res = dict(zip(paired, assess_pairs(ctx, pairs, segment, max_shift, budget)))
+    err_txt, cal_txt, cal_total = [ERRORS_HEADER], [CALIBRATION_HEADER], np.zeros((QBINS, 4), np.int64)
     zero = {f: 0 for f in TOTAL_FIELDS}
     total, la_sum, lb_sum = dict(zero), 0, 0
     contig, seg_txt = [CONTIG_HEADER], [SEGMENT_HEADER]
@@ -149,7 +260,12 @@ def tables(ctx, asm, truth, segment: int, max_shift: int, budget: int = DEFAULT_
         if name in lone_asm:
             contig.append(contig_line(name, "unpaired", len(a), 0, zero))
             continue
-        segs, t = res[name]
+        segs, t = res[name][:2]
+        if errors:
+            err_txt += [error_line(name, r) for r in res[name][2]]
+            if quals is not None:
+                cal_txt.append(calibration_lines(name, res[name][3]))
+                cal_total += res[name][3]
         contig.append(contig_line(name, "paired", len(a), len(tr[name]), t))
         la_sum += len(a)
         lb_sum += len(tr[name])
@@ -165,7 +281,12 @@ def tables(ctx, asm, truth, segment: int, max_shift: int, budget: int = DEFAULT_
         if not in_asm:
             contig.append(contig_line(name, "unpaired", 0, ln, zero))
     contig.append(contig_line("TOTAL", "total", la_sum, lb_sum, total))
-    return "".join(contig), "".join(seg_txt), total
+    if not errors:
+        return "".join(contig), "".join(seg_txt), total
+    if quals is None:
+        return "".join(contig), "".join(seg_txt), total, "".join(err_txt), None, None
+    cal_txt.append(calibration_lines("TOTAL", cal_total))
+    return "".join(contig), "".join(seg_txt), total, "".join(err_txt), "".join(cal_txt), cal_total
 
 
 def write_text(path: str, text: str) -> None:
@@ -190,20 +311,31 @@ def _errors_qv(t):
 def run(args) -> int:
     try:
         check_options(int(args.segment), int(args.max_shift))
+        want_errors, fastq = bool(getattr(args, "errors", False)), getattr(args, "fastq", None)
         for what, p in (("assembly", args.assembly), ("truth", args.truth), ("draft", args.draft)):
             if p is not None and not os.path.isfile(p):
                 raise AssessError("cannot find the %s FASTA %s" % (what, p))
+        if fastq is not None and not os.path.isfile(fastq):
+            raise AssessError("cannot find the FASTQ %s" % fastq)
         asm, truth = read_fasta(args.assembly), read_fasta(args.truth)
         draft = read_fasta(args.draft) if args.draft else None
+        quals = read_fastq(fastq, asm) if fastq is not None else None
         for label, seqs in (("assembly", asm), ("draft", draft)):
             for n, in_asm, _ in (pair_names(seqs, truth)[1] if seqs is not None else ()):
                 log("assess: contig %s is only in the %s FASTA: unpaired" % (n, label if in_asm else "truth"))
         from . import runtime
         ctx = runtime.Context(int(args.device_id))
         try:
-            contig_txt, seg_txt, total = tables(ctx, asm, truth, int(args.segment), int(args.max_shift))
+            err_txt = cal_txt = cal_total = draft_err_txt = None
+            if want_errors or quals is not None:
+                contig_txt, seg_txt, total, err_txt, cal_txt, cal_total = error_tables(ctx, asm, truth, int(args.segment),
+                                                                                       int(args.max_shift), quals)
+            else:
+                contig_txt, seg_txt, total = tables(ctx, asm, truth, int(args.segment), int(args.max_shift))
             draft_txt = draft_total = None
-            if draft is not None:
+            if draft is not None and want_errors:
+                draft_txt, _, draft_total, draft_err_txt = error_tables(ctx, draft, truth, int(args.segment), int(args.max_shift))[:4]
+            elif draft is not None:
                 draft_txt, _, draft_total = tables(ctx, draft, truth, int(args.segment), int(args.max_shift))
         finally:
             ctx.close()
@@ -215,6 +347,17 @@ def run(args) -> int:
         os.makedirs(d, exist_ok=True)
     write_text(args.output + "_assess.tsv", contig_txt)
     write_text(args.output + "_assess.segments.tsv", seg_txt)
+    if want_errors:
+        write_text(args.output + "_assess.errors.tsv", err_txt)
+        if draft_err_txt is not None:
+            write_text(args.output + "_assess_draft.errors.tsv", draft_err_txt)
+    if cal_txt is not None:
+        write_text(args.output + "_assess.calibration.tsv", cal_txt)
+        q = calibrated_from(cal_total)
+        if q is None:
+            log("assess: calibration: at no quality value q do the bases of quality q or more reach an observed QV of q")
+        else:
+            log("assess: calibration: from quality %d up the observed QV of the bases is at least the quality" % q)
     err, qv = _errors_qv(total)
     if draft_txt is not None:
         write_text(args.output + "_assess_draft.tsv", draft_txt)

@@ -14,6 +14,16 @@
 //   k_as_trace    one lane per segment: walks the direction words back from (n, m) and writes the segment's record
 //   k_as_reduce   one workgroup per pair: the records -> the contig's totals
 // A status other than PV_OK makes every later kernel poison its outputs instead (bytes 0xFF: every field -1).
+//
+// pv_assess_errors_dev keeps the traceback's path (the rule: pv_assess_errors in the header). The same seven launches, then:
+//   k_as_errcnt   one lane per slot: the aligned segment's sub + ins + del, from its record
+//   k_as_erroff   one block: the scan over all slots -> each segment's first error record, pair_err_off, the need, the status
+//   k_as_hist     one workgroup per slot: the qualities of the segment's rows and anchor bytes into an LDS table -> the slot's
+//                 partial table in the scratch (only with Q)
+//   k_as_errors   one lane per slot: the walk of k_as_trace again (as_walk, one template for both), each record stored from the
+//                 end of the segment's range; with Q the lane adds its errors to its own slot's partial table
+//   k_as_qreduce  one workgroup per pair: the partial tables of its segments, summed in a fixed order -> qhist (only with Q)
+//   k_as_epoison  under PV_ERR_INVALID / PV_ERR_LIMIT: 0xFF over errs, pair_err_off and qhist
 #include <algorithm>
 
 #include "pv_common.hpp"
@@ -29,16 +39,21 @@ struct SegSlot { int64_t a0, b0, n, m; };   // a pair's segments, in its slots o
 struct Anchor { int64_t a, b; };            // a < 0: slot without an anchor
 
 // the scratch area: offsets in bytes, all multiples of 256
-struct Layout { int64_t slot_off, pair_cnt, anchors, segs, dirs, total; };
+struct Layout { int64_t slot_off, pair_cnt, anchors, segs, dirs, err_cnt, err_off, qpart, total; };
+constexpr int AS_QTAB = PV_ASSESS_QBINS * 4;   // a slot's partial table: uint32 {bases, sub, ins, del} per quality
 __host__ __device__ inline int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-__host__ __device__ inline Layout as_layout(int64_t n_pairs, int64_t slots, int64_t total_a) {
+// with_err: the per-slot error counts and offsets and the partial quality tables of pv_assess_errors_dev, behind the rest
+__host__ __device__ inline Layout as_layout(int64_t n_pairs, int64_t slots, int64_t total_a, int with_err) {
     Layout y;
     y.slot_off = 0;
     y.pair_cnt = up256((n_pairs + 1) * 8);
     y.anchors = y.pair_cnt + up256(n_pairs * 16);
     y.segs = y.anchors + up256(slots * 16);
     y.dirs = y.segs + up256(slots * 32);
-    y.total = y.dirs + up256(32 * total_a + 256 * slots);
+    y.err_cnt = y.dirs + up256(32 * total_a + 256 * slots);
+    y.err_off = y.err_cnt + (with_err ? up256(slots * 8) : 0);
+    y.qpart = y.err_off + (with_err ? up256((slots + 1) * 8) : 0);
+    y.total = y.qpart + (with_err ? up256(slots * AS_QTAB * 4) : 0);
     return y;
 }
 
@@ -52,12 +67,21 @@ struct Args {
     int64_t* pair_seg_off;
     int64_t* totals;
     uint8_t* scratch; int64_t scratch_bytes;
-    int64_t* counts;   // {segments, status, slots needed, scratch bytes needed}
+    int64_t* counts;   // {segments, status, slots needed, scratch bytes needed}; with_err: int64[8], see ErrArgs
+    int with_err;
+};
+// what pv_assess_errors_dev adds; counts[4..7] = {error records written, needed, 0, 0}
+struct ErrArgs {
+    const uint8_t* Q;
+    int64_t err_capacity;
+    pv_assess_error* errs;
+    int64_t* pair_err_off;
+    int64_t* qhist;
 };
 
 __device__ inline int64_t* slot_off_of(const Args& g) { return (int64_t*)g.scratch; }
 __device__ inline Layout layout_of(const Args& g) {
-    return as_layout(g.n_pairs, slot_off_of(g)[g.n_pairs], g.a_off[g.n_pairs] - g.a_off[0]);
+    return as_layout(g.n_pairs, slot_off_of(g)[g.n_pairs], g.a_off[g.n_pairs] - g.a_off[0], g.with_err);
 }
 // the pair that owns slot s: the last p with slot_off[p] <= s
 __device__ inline int64_t pair_of_slot(const int64_t* slot_off, int64_t n_pairs, int64_t s) {
@@ -120,11 +144,12 @@ __global__ __launch_bounds__(AS_THREADS) void k_as_setup(Args g) {
         return bad ? (int64_t)1 : na / L + 1;
     });
     if (threadIdx.x == 0) {
-        const Layout y = as_layout(g.n_pairs, slots, bad ? 0 : g.a_off[g.n_pairs] - g.a_off[0]);
+        const Layout y = as_layout(g.n_pairs, slots, bad ? 0 : g.a_off[g.n_pairs] - g.a_off[0], g.with_err);
         g.counts[0] = 0;
         g.counts[1] = bad ? PV_ERR_INVALID : (slots > g.seg_capacity || y.total > g.scratch_bytes) ? PV_ERR_LIMIT : PV_OK;
         g.counts[2] = slots;
         g.counts[3] = y.total;
+        if (g.with_err) { g.counts[4] = 0; g.counts[5] = -1; g.counts[6] = 0; g.counts[7] = 0; }
     }
 }
 
@@ -337,6 +362,56 @@ __device__ inline void poison_seg(pv_assess_seg* s) {
     for (int i = 0; i < 8; i++) w[i] = -1;
 }
 
+// the walk back from (n, m) by the stored directions, for the counting pass and the writing pass alike: the visitor sees every
+// step with the i, j it leaves from. false: the walk left the band or the matrix (never expected; nothing is read outside).
+//   v.diag(i, j, a, b)   A[a0+i-1] against B[b0+j-1]: a match or a substitution
+//   v.up(i, j, x, hp)    an insertion of x = A[a0+i-1] before truth position b0+j
+//   v.left(i, j, x, hp)  a deletion of x = B[b0+j-1] before assembly position a0+i
+template <typename V>
+__device__ inline bool as_walk(const SegRef& r, const uint8_t* Ac, const uint8_t* Bc, int64_t nb, int dlo, int32_t* edge_out,
+                               V& v) {
+    int64_t i = r.s.n, j = r.s.m, have = -1;
+    uint32_t word = 0;
+    int32_t edge = 0;
+    bool broken = false;
+    for (;;) {
+        const int c = (int)(j - i - dlo);
+        if (c < 0 || c >= AS_W || j < 0) { broken = true; break; }
+        if (c == 0 || c == AS_W - 1) edge = 1;
+        if (i == 0 && j == 0) break;
+        int step = DIR_LEFT;
+        if (i > 0) {
+            const int64_t at = ((i - 1) >> 3) * 64 + (c >> 1);
+            if (at != have) { word = r.dirs[at]; have = at; }
+            step = (word >> (4 * ((i - 1) & 7) + 2 * (c & 1))) & 3;
+        }
+        if (j == 0 && step != DIR_UP) { broken = true; break; }
+        if (step == DIR_DIAG) {
+            v.diag(i, j, Ac[r.s.a0 + i - 1], Bc[r.s.b0 + j - 1]);
+            i--; j--;
+        } else if (step == DIR_UP) {
+            const uint8_t x = Ac[r.s.a0 + i - 1];
+            const int64_t q = r.s.b0 + j;
+            v.up(i, j, x, (q - 1 >= 0 && Bc[q - 1] == x) || (q < nb && Bc[q] == x));
+            i--;
+        } else {
+            const int64_t q = r.s.b0 + j - 1;
+            const uint8_t x = Bc[q];
+            v.left(i, j, x, (q - 1 >= 0 && Bc[q - 1] == x) || (q + 1 < nb && Bc[q + 1] == x));
+            j--;
+        }
+    }
+    *edge_out = edge;
+    return !broken;
+}
+
+struct CountSteps {
+    int32_t nm = 0, nsub = 0, nins = 0, ndel = 0, hpi = 0, hpd = 0;
+    __device__ void diag(int64_t, int64_t, uint8_t a, uint8_t b) { if (a == b) nm++; else nsub++; }
+    __device__ void up(int64_t, int64_t, uint8_t, bool hp) { nins++; hpi += hp; }
+    __device__ void left(int64_t, int64_t, uint8_t, bool hp) { ndel++; hpd += hp; }
+};
+
 // one lane per slot: the walk back from (n, m), and the segment's record
 __global__ __launch_bounds__(AS_THREADS) void k_as_trace(Args g) {
     const int64_t slot = (int64_t)blockIdx.x * AS_THREADS + threadIdx.x;
@@ -364,41 +439,11 @@ __global__ __launch_bounds__(AS_THREADS) void k_as_trace(Args g) {
     const uint8_t* Ac = g.A + g.a_off[r.pair];   // contig coordinates
     const uint8_t* Bc = g.B + g.b_off[r.pair];
     const int dlo = as_dlo(d);
-    int64_t i = n, j = m, have = -1;
-    uint32_t word = 0;
-    int32_t nm = 0, nsub = 0, nins = 0, ndel = 0, hpi = 0, hpd = 0, edge = 0;
-    bool broken = false;
-    for (;;) {
-        const int c = (int)(j - i - dlo);
-        if (c < 0 || c >= AS_W || j < 0) { broken = true; break; }   // never expected: nothing is read outside the band
-        if (c == 0 || c == AS_W - 1) edge = 1;
-        if (i == 0 && j == 0) break;
-        int step = DIR_LEFT;
-        if (i > 0) {
-            const int64_t at = ((i - 1) >> 3) * 64 + (c >> 1);
-            if (at != have) { word = r.dirs[at]; have = at; }
-            step = (word >> (4 * ((i - 1) & 7) + 2 * (c & 1))) & 3;
-        }
-        if (j == 0 && step != DIR_UP) { broken = true; break; }
-        if (step == DIR_DIAG) {
-            if (Ac[r.s.a0 + i - 1] == Bc[r.s.b0 + j - 1]) nm++; else nsub++;
-            i--; j--;
-        } else if (step == DIR_UP) {
-            const uint8_t x = Ac[r.s.a0 + i - 1];
-            const int64_t q = r.s.b0 + j;
-            nins++;
-            if ((q - 1 >= 0 && Bc[q - 1] == x) || (q < nb && Bc[q] == x)) hpi++;
-            i--;
-        } else {
-            const int64_t q = r.s.b0 + j - 1;
-            const uint8_t x = Bc[q];
-            ndel++;
-            if ((q - 1 >= 0 && Bc[q - 1] == x) || (q + 1 < nb && Bc[q + 1] == x)) hpd++;
-            j--;
-        }
-    }
+    CountSteps v;
+    int32_t edge = 0;
+    const bool broken = !as_walk(r, Ac, Bc, nb, dlo, &edge, v);
     o.status = broken ? PV_ASSESS_SEG_BROKEN : PV_ASSESS_SEG_ALIGNED;
-    o.edge = edge; o.match = nm; o.sub = nsub; o.ins = nins; o.del = ndel; o.hp_ins = hpi; o.hp_del = hpd;
+    o.edge = edge; o.match = v.nm; o.sub = v.nsub; o.ins = v.nins; o.del = v.ndel; o.hp_ins = v.hpi; o.hp_del = v.hpd;
     g.segs[r.out] = o;
 }
 
@@ -447,7 +492,176 @@ __global__ __launch_bounds__(AS_THREADS) void k_as_poison(Args g, int64_t need_s
     if (t < g.seg_capacity) poison_seg(g.segs + t);
     if (t <= g.n_pairs) g.pair_seg_off[t] = -1;
     if (t < g.n_pairs * PV_ASSESS_TOTALS) g.totals[t] = -1;
-    if (t == 0) { g.counts[0] = 0; g.counts[1] = PV_ERR_LIMIT; g.counts[2] = -1; g.counts[3] = need_scratch; }
+    if (t == 0) {
+        g.counts[0] = 0; g.counts[1] = PV_ERR_LIMIT; g.counts[2] = -1; g.counts[3] = need_scratch;
+        if (g.with_err) { g.counts[4] = 0; g.counts[5] = -1; g.counts[6] = 0; g.counts[7] = 0; }
+    }
+}
+
+// ---- pv_assess_errors_dev: the error records and the calibration table ---------------------------------------------------
+// PV_ERR_CAPACITY is the one status under which the outputs (but errs) are still valid
+__device__ inline bool as_failed(const Args& g) { return g.counts[1] != PV_OK && g.counts[1] != PV_ERR_CAPACITY; }
+
+// one lane per slot: how many error records its segment gives
+__global__ __launch_bounds__(AS_THREADS) void k_as_errcnt(Args g) {
+    if (as_failed(g)) return;
+    const int64_t slot = (int64_t)blockIdx.x * AS_THREADS + threadIdx.x;
+    if (slot >= slot_off_of(g)[g.n_pairs]) return;
+    const Layout y = layout_of(g);
+    SegRef r;
+    int64_t cnt = 0;
+    if (seg_of_slot(g, y, slot, &r)) {
+        const pv_assess_seg x = g.segs[r.out];
+        if (x.status == PV_ASSESS_SEG_ALIGNED) cnt = (int64_t)x.sub + x.ins + x.del;
+    }
+    ((int64_t*)(g.scratch + y.err_cnt))[slot] = cnt;
+}
+
+// one block: the scan over all slots, pair_err_off, the need and the status
+__global__ __launch_bounds__(AS_THREADS) void k_as_erroff(Args g, ErrArgs e) {
+    __shared__ int64_t lds[AS_THREADS / 64];
+    if (as_failed(g)) return;
+    const Layout y = layout_of(g);
+    const int64_t* slot_off = slot_off_of(g);
+    const int64_t* err_cnt = (const int64_t*)(g.scratch + y.err_cnt);
+    int64_t* err_off = (int64_t*)(g.scratch + y.err_off);
+    const int64_t need = block_scan_to(slot_off[g.n_pairs], err_off, lds, [&](int64_t s) { return err_cnt[s]; });
+    __syncthreads();   // err_off is complete
+    for (int64_t p = threadIdx.x; p <= g.n_pairs; p += AS_THREADS) e.pair_err_off[p] = err_off[slot_off[p]];
+    if (threadIdx.x == 0) {
+        const bool fits = need <= e.err_capacity;
+        g.counts[4] = fits ? need : 0;
+        g.counts[5] = need;
+        if (!fits) g.counts[1] = PV_ERR_CAPACITY;
+    }
+}
+
+__device__ inline uint32_t as_q(uint8_t q) { return q > PV_ASSESS_QBINS - 1 ? PV_ASSESS_QBINS - 1 : q; }
+
+// one workgroup per slot: the qualities of the segment's rows (if it is aligned) and of the anchor behind it -> the slot's
+// partial table, its error columns zero (k_as_errors fills them)
+__global__ __launch_bounds__(AS_THREADS) void k_as_hist(Args g, ErrArgs e) {
+    __shared__ uint32_t s_tab[AS_QTAB];
+    if (as_failed(g)) return;
+    const Layout y = layout_of(g);
+    const int64_t slot = blockIdx.x;
+    SegRef r;
+    if (!seg_of_slot(g, y, slot, &r)) return;   // (the same in every thread)
+    for (int t = threadIdx.x; t < AS_QTAB; t += AS_THREADS) s_tab[t] = 0;
+    __syncthreads();
+    const pv_assess_seg x = g.segs[r.out];
+    const uint8_t* Q = e.Q + g.a_off[r.pair];
+    // the anchor lies directly behind the segment's rows: one contiguous range
+    const int64_t lo = x.status == PV_ASSESS_SEG_ALIGNED ? r.s.a0 : r.s.a0 + r.s.n, hi = r.s.a0 + r.s.n + x.anchor;
+    uint32_t cur = 0, run = 0;   // equal qualities in a row cost one LDS atomic
+    for (int64_t k = lo + threadIdx.x; k < hi; k += AS_THREADS) {
+        const uint32_t q = as_q(Q[k]);
+        if (q != cur && run) { atomicAdd(&s_tab[4 * cur], run); run = 0; }
+        cur = q;
+        run++;
+    }
+    if (run) atomicAdd(&s_tab[4 * cur], run);
+    __syncthreads();
+    uint32_t* part = (uint32_t*)(g.scratch + y.qpart) + slot * AS_QTAB;
+    for (int t = threadIdx.x; t < AS_QTAB; t += AS_THREADS) part[t] = s_tab[t];
+}
+
+// the writing pass: records from the end of the segment's range, since the walk runs backwards
+struct WriteSteps {
+    pv_assess_error* out;    // one past the next record to write; null: none is written
+    const uint8_t* Q;        // the contig's qualities, or null
+    uint32_t* part;          // the slot's partial table, or null
+    int64_t a0, b0, na;
+    int32_t pair, segment;
+    __device__ void put(uint8_t kind, int64_t a_pos, int64_t b_pos, uint8_t a_base, uint8_t b_base, bool hp) {
+        uint32_t q = 255;
+        if (Q) {
+            if (kind != PV_ASSESS_ERR_DEL) q = as_q(Q[a_pos]);
+            else if (na == 0) q = 0;
+            else {
+                q = PV_ASSESS_QBINS - 1;
+                if (a_pos - 1 >= 0) q = min(q, as_q(Q[a_pos - 1]));
+                if (a_pos < na) q = min(q, as_q(Q[a_pos]));
+            }
+            part[4 * q + kind]++;   // this lane's own slot: nobody else writes it
+        }
+        if (!out) return;
+        pv_assess_error x;
+        x.a_pos = a_pos; x.b_pos = b_pos; x.pair = pair; x.segment = segment;
+        x.kind = kind; x.a_base = a_base; x.b_base = b_base; x.hp = hp; x.qual = (uint8_t)q;
+        x.pad[0] = x.pad[1] = x.pad[2] = 0;
+        *--out = x;
+    }
+    __device__ void diag(int64_t i, int64_t j, uint8_t a, uint8_t b) {
+        if (a != b) put(PV_ASSESS_ERR_SUB, a0 + i - 1, b0 + j - 1, a, b, false);
+    }
+    __device__ void up(int64_t i, int64_t j, uint8_t x, bool hp) { put(PV_ASSESS_ERR_INS, a0 + i - 1, b0 + j, x, 0, hp); }
+    __device__ void left(int64_t i, int64_t j, uint8_t x, bool hp) { put(PV_ASSESS_ERR_DEL, a0 + i, b0 + j - 1, 0, x, hp); }
+};
+
+// one lane per slot: the walk again. Under PV_ERR_CAPACITY nothing is written, but the table still gets its errors.
+__global__ __launch_bounds__(AS_THREADS) void k_as_errors(Args g, ErrArgs e) {
+    if (as_failed(g)) return;
+    const bool write = g.counts[1] == PV_OK;
+    if (!write && !e.Q) return;
+    const int64_t slot = (int64_t)blockIdx.x * AS_THREADS + threadIdx.x;
+    const Layout y = layout_of(g);
+    SegRef r;
+    if (!seg_of_slot(g, y, slot, &r)) return;
+    const int64_t* err_off = (const int64_t*)(g.scratch + y.err_off);
+    const int64_t first = err_off[slot], last = err_off[slot + 1];
+    if (first == last) return;   // no record: unaligned, broken or without an error
+    WriteSteps v;
+    v.out = write ? e.errs + last : nullptr;
+    v.Q = e.Q ? e.Q + g.a_off[r.pair] : nullptr;
+    v.part = e.Q ? (uint32_t*)(g.scratch + y.qpart) + slot * AS_QTAB : nullptr;
+    v.a0 = r.s.a0; v.b0 = r.s.b0; v.na = g.a_off[r.pair + 1] - g.a_off[r.pair];
+    v.pair = (int32_t)r.pair; v.segment = (int32_t)r.idx;
+    int32_t edge;
+    as_walk(r, g.A + g.a_off[r.pair], g.B + g.b_off[r.pair], g.b_off[r.pair + 1] - g.b_off[r.pair], as_dlo(r.s.m - r.s.n), &edge, v);
+}
+
+// one workgroup per pair: wave w sums the partial tables of the pair's segments w, w + 8, ..., a lane six entries of each; the
+// eight sums are then added in the order of w
+constexpr int QR_WAVES = 8, QR_PER = (AS_QTAB + 63) / 64;
+__global__ __launch_bounds__(QR_WAVES * 64) void k_as_qreduce(Args g, ErrArgs e) {
+    __shared__ int64_t s_sum[QR_WAVES][AS_QTAB];
+    if (as_failed(g)) return;
+    const Layout y = layout_of(g);
+    const int64_t p = blockIdx.x;
+    const int64_t ns = ((const int64_t*)(g.scratch + y.pair_cnt))[2 * p];
+    const uint32_t* part = (const uint32_t*)(g.scratch + y.qpart) + slot_off_of(g)[p] * AS_QTAB;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int64_t acc[QR_PER];
+#pragma unroll
+    for (int k = 0; k < QR_PER; k++) acc[k] = 0;
+    for (int64_t s = w; s < ns; s += QR_WAVES) {   // (asking for this loop to be unrolled by four made the kernel four times slower)
+#pragma unroll
+        for (int k = 0; k < QR_PER; k++) {
+            const int t = lane + 64 * k;
+            if (t < AS_QTAB) acc[k] += part[s * AS_QTAB + t];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < QR_PER; k++)
+        if (lane + 64 * k < AS_QTAB) s_sum[w][lane + 64 * k] = acc[k];
+    __syncthreads();
+    for (int t = threadIdx.x; t < AS_QTAB; t += QR_WAVES * 64) {
+        int64_t v = 0;
+        for (int i = 0; i < QR_WAVES; i++) v += s_sum[i][t];
+        e.qhist[p * AS_QTAB + t] = v;
+    }
+}
+
+// PV_ERR_INVALID or PV_ERR_LIMIT: 0xFF over every new output
+__global__ __launch_bounds__(AS_THREADS) void k_as_epoison(Args g, ErrArgs e) {
+    if (!as_failed(g)) return;
+    const int64_t t0 = (int64_t)blockIdx.x * AS_THREADS + threadIdx.x, step = (int64_t)gridDim.x * AS_THREADS;
+    int64_t* w = (int64_t*)e.errs;
+    for (int64_t t = t0; t < e.err_capacity * 4; t += step) w[t] = -1;
+    for (int64_t t = t0; t <= g.n_pairs; t += step) e.pair_err_off[t] = -1;
+    if (e.qhist)
+        for (int64_t t = t0; t < g.n_pairs * AS_QTAB; t += step) e.qhist[t] = -1;
 }
 
 int assess_check(int64_t n_pairs, int segment, int max_shift, int64_t seg_capacity) {
@@ -459,43 +673,18 @@ int assess_check(int64_t n_pairs, int segment, int max_shift, int64_t seg_capaci
     return PV_OK;
 }
 
-}  // namespace
-
-extern "C" int64_t pv_assess_scratch_bytes(int64_t n_pairs, const int64_t* a_off, int segment) {
-    if (n_pairs < 0 || (n_pairs > 0 && !a_off) || segment < 1) return PV_ERR_INVALID;
-    int64_t slots = 0;
-    for (int64_t p = 0; p < n_pairs; p++) {
-        const int64_t na = a_off[p + 1] - a_off[p];
-        if (na < 0) return PV_ERR_INVALID;
-        slots += na / segment + 1;
-    }
-    return as_layout(n_pairs, slots, n_pairs ? a_off[n_pairs] - a_off[0] : 0).total;
-}
-
-extern "C" int pv_assess_dev(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, const uint8_t* B, const int64_t* b_off,
-                             int64_t n_pairs, int segment, int max_shift, int64_t seg_capacity, pv_assess_seg* segs,
-                             int64_t* pair_seg_off, int64_t* totals, void* scratch, int64_t scratch_bytes, int64_t* d_counts,
-                             void* stream) {
-    PV_CHECK(ctx && a_off && b_off && pair_seg_off && d_counts, PV_ERR_INVALID, "assess: null argument");
-    PV_CHECK(scratch_bytes >= 0, PV_ERR_INVALID, "assess: negative sizes");
-    int rc;
-    if ((rc = assess_check(n_pairs, segment, max_shift, seg_capacity))) return rc;
-    PV_CHECK(n_pairs == 0 || (A && B && totals), PV_ERR_INVALID, "assess: sequences or totals missing");
-    PV_CHECK(seg_capacity == 0 || segs, PV_ERR_INVALID, "assess: segment records missing");
-    PV_CHECK(scratch_bytes == 0 || scratch, PV_ERR_INVALID, "assess: scratch missing");
-    PV_CHECK(((uintptr_t)scratch & 255) == 0 && ((uintptr_t)segs & 7) == 0, PV_ERR_INVALID,
-             "assess: scratch must be aligned to 256 bytes and the records to 8");
-    PV_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = pv_pick_stream(ctx, stream);
-    Args g = {A, a_off, B, b_off, n_pairs, segment, max_shift, seg_capacity, segs, pair_seg_off, totals, (uint8_t*)scratch,
-              scratch_bytes, d_counts};
+// the launches of pv_assess_dev and, with e, those of pv_assess_errors_dev behind them
+int assess_launch(pv_ctx* ctx, const Args& g, const ErrArgs* e, hipStream_t st) {
+    const int64_t n_pairs = g.n_pairs, seg_capacity = g.seg_capacity;
     pv_prof_scope ps_all(ctx, "assess", st);
     const int64_t most = std::max(std::max(seg_capacity, n_pairs * PV_ASSESS_TOTALS), n_pairs + 1);
-    const int64_t head = as_layout(n_pairs, n_pairs, 0).total;   // the least any batch of n_pairs needs
-    if (scratch_bytes < head) {
+    const int64_t head = as_layout(n_pairs, n_pairs, 0, g.with_err).total;   // the least any batch of n_pairs needs
+    const unsigned per_slot = (unsigned)((seg_capacity + AS_THREADS - 1) / AS_THREADS);
+    if (g.scratch_bytes < head) {
         k_as_poison<<<(unsigned)((most + AS_THREADS - 1) / AS_THREADS), AS_THREADS, 0, st>>>(g, head);
+        if (e) k_as_epoison<<<1024, AS_THREADS, 0, st>>>(g, *e);
         PV_HIP(hipGetLastError());
-        pv_set_error("assess: the scratch of %lld bytes cannot hold %lld pairs", (long long)scratch_bytes, (long long)n_pairs);
+        pv_set_error("assess: the scratch of %lld bytes cannot hold %lld pairs", (long long)g.scratch_bytes, (long long)n_pairs);
         return PV_ERR_LIMIT;
     }
     k_as_setup<<<1, AS_THREADS, 0, st>>>(g);
@@ -508,11 +697,97 @@ extern "C" int pv_assess_dev(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off
             k_as_sweep<<<(unsigned)((seg_capacity + AS_THREADS / 64 - 1) / (AS_THREADS / 64)), AS_THREADS, 0, st>>>(g);
         }
         pv_prof_scope ps(ctx, "k_as_trace", st);
-        k_as_trace<<<(unsigned)((seg_capacity + AS_THREADS - 1) / AS_THREADS), AS_THREADS, 0, st>>>(g);
+        k_as_trace<<<per_slot, AS_THREADS, 0, st>>>(g);
     }
     if (n_pairs > 0) k_as_reduce<<<(unsigned)n_pairs, AS_THREADS, 0, st>>>(g);
+    if (e) {
+        if (seg_capacity > 0) { pv_prof_scope ps(ctx, "k_as_errcnt", st); k_as_errcnt<<<per_slot, AS_THREADS, 0, st>>>(g); }
+        { pv_prof_scope ps(ctx, "k_as_erroff", st); k_as_erroff<<<1, AS_THREADS, 0, st>>>(g, *e); }
+        if (seg_capacity > 0) {
+            if (e->Q) { pv_prof_scope ps(ctx, "k_as_hist", st); k_as_hist<<<(unsigned)seg_capacity, AS_THREADS, 0, st>>>(g, *e); }
+            pv_prof_scope ps(ctx, "k_as_errors", st);
+            k_as_errors<<<per_slot, AS_THREADS, 0, st>>>(g, *e);
+        }
+        if (e->Q && n_pairs > 0) {
+            pv_prof_scope ps(ctx, "k_as_qreduce", st);
+            k_as_qreduce<<<(unsigned)n_pairs, QR_WAVES * 64, 0, st>>>(g, *e);
+        }
+        k_as_epoison<<<1024, AS_THREADS, 0, st>>>(g, *e);
+    }
     PV_HIP(hipGetLastError());
     return PV_OK;
+}
+
+int64_t scratch_bytes_of(int64_t n_pairs, const int64_t* a_off, int segment, int with_err) {
+    if (n_pairs < 0 || (n_pairs > 0 && !a_off) || segment < 1) return PV_ERR_INVALID;
+    int64_t slots = 0;
+    for (int64_t p = 0; p < n_pairs; p++) {
+        const int64_t na = a_off[p + 1] - a_off[p];
+        if (na < 0) return PV_ERR_INVALID;
+        slots += na / segment + 1;
+    }
+    return as_layout(n_pairs, slots, n_pairs ? a_off[n_pairs] - a_off[0] : 0, with_err).total;
+}
+
+// the refusals that pv_assess_dev and pv_assess_errors_dev share
+int assess_dev_check(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, const uint8_t* B, const int64_t* b_off, int64_t n_pairs,
+                     int segment, int max_shift, int64_t seg_capacity, pv_assess_seg* segs, int64_t* pair_seg_off, int64_t* totals,
+                     void* scratch, int64_t scratch_bytes, int64_t* d_counts) {
+    PV_CHECK(ctx && a_off && b_off && pair_seg_off && d_counts, PV_ERR_INVALID, "assess: null argument");
+    PV_CHECK(scratch_bytes >= 0, PV_ERR_INVALID, "assess: negative sizes");
+    int rc;
+    if ((rc = assess_check(n_pairs, segment, max_shift, seg_capacity))) return rc;
+    PV_CHECK(n_pairs == 0 || (A && B && totals), PV_ERR_INVALID, "assess: sequences or totals missing");
+    PV_CHECK(seg_capacity == 0 || segs, PV_ERR_INVALID, "assess: segment records missing");
+    PV_CHECK(scratch_bytes == 0 || scratch, PV_ERR_INVALID, "assess: scratch missing");
+    PV_CHECK(((uintptr_t)scratch & 255) == 0 && ((uintptr_t)segs & 7) == 0, PV_ERR_INVALID,
+             "assess: scratch must be aligned to 256 bytes and the records to 8");
+    return PV_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t pv_assess_scratch_bytes(int64_t n_pairs, const int64_t* a_off, int segment) {
+    return scratch_bytes_of(n_pairs, a_off, segment, 0);
+}
+
+extern "C" int64_t pv_assess_errors_scratch_bytes(int64_t n_pairs, const int64_t* a_off, int segment) {
+    return scratch_bytes_of(n_pairs, a_off, segment, 1);
+}
+
+extern "C" int pv_assess_dev(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, const uint8_t* B, const int64_t* b_off,
+                             int64_t n_pairs, int segment, int max_shift, int64_t seg_capacity, pv_assess_seg* segs,
+                             int64_t* pair_seg_off, int64_t* totals, void* scratch, int64_t scratch_bytes, int64_t* d_counts,
+                             void* stream) {
+    int rc;
+    if ((rc = assess_dev_check(ctx, A, a_off, B, b_off, n_pairs, segment, max_shift, seg_capacity, segs, pair_seg_off, totals,
+                               scratch, scratch_bytes, d_counts)))
+        return rc;
+    PV_HIP(hipSetDevice(ctx->device));
+    Args g = {A, a_off, B, b_off, n_pairs, segment, max_shift, seg_capacity, segs, pair_seg_off, totals, (uint8_t*)scratch,
+              scratch_bytes, d_counts, 0};
+    return assess_launch(ctx, g, nullptr, pv_pick_stream(ctx, stream));
+}
+
+extern "C" int pv_assess_errors_dev(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, const uint8_t* B, const int64_t* b_off,
+                                    int64_t n_pairs, int segment, int max_shift, int64_t seg_capacity, pv_assess_seg* segs,
+                                    int64_t* pair_seg_off, int64_t* totals, const uint8_t* Q, int64_t err_capacity,
+                                    pv_assess_error* errs, int64_t* pair_err_off, int64_t* qhist, void* scratch,
+                                    int64_t scratch_bytes, int64_t* d_counts, void* stream) {
+    int rc;
+    if ((rc = assess_dev_check(ctx, A, a_off, B, b_off, n_pairs, segment, max_shift, seg_capacity, segs, pair_seg_off, totals,
+                               scratch, scratch_bytes, d_counts)))
+        return rc;
+    PV_CHECK(pair_err_off && err_capacity >= 0, PV_ERR_INVALID, "assess: error offsets missing or a negative capacity");
+    PV_CHECK(err_capacity == 0 || errs, PV_ERR_INVALID, "assess: error records missing");
+    PV_CHECK(((uintptr_t)errs & 7) == 0, PV_ERR_INVALID, "assess: the error records must be aligned to 8 bytes");
+    PV_CHECK((Q != nullptr) == (qhist != nullptr), PV_ERR_INVALID,
+             "assess: qualities and their table come together or not at all");
+    PV_HIP(hipSetDevice(ctx->device));
+    Args g = {A, a_off, B, b_off, n_pairs, segment, max_shift, seg_capacity, segs, pair_seg_off, totals, (uint8_t*)scratch,
+              scratch_bytes, d_counts, 1};
+    ErrArgs e = {Q, err_capacity, errs, pair_err_off, qhist};
+    return assess_launch(ctx, g, &e, pv_pick_stream(ctx, stream));
 }
 
 extern "C" int pv_assess(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, const uint8_t* B, const int64_t* b_off,
@@ -567,6 +842,82 @@ extern "C" int pv_assess(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, co
     }
     PV_CHECK(status != PV_ERR_LIMIT, PV_ERR_LIMIT, "assess: %lld segment records needed, %lld given", (long long)counts[2],
              (long long)seg_capacity);
+    PV_CHECK(status == PV_OK, (int)status, "assess: device status %lld", (long long)status);
+    return PV_OK;
+}
+
+extern "C" int pv_assess_errors(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, const uint8_t* B, const int64_t* b_off,
+                                int64_t n_pairs, int segment, int max_shift, int64_t seg_capacity, pv_assess_seg* segs,
+                                int64_t* pair_seg_off, int64_t* totals, const uint8_t* Q, int64_t err_capacity,
+                                pv_assess_error* errs, int64_t* pair_err_off, int64_t* qhist, int64_t* counts) {
+    PV_CHECK(ctx && a_off && b_off && pair_seg_off && pair_err_off && counts, PV_ERR_INVALID, "assess: null argument");
+    int rc;
+    if ((rc = assess_check(n_pairs, segment, max_shift, seg_capacity))) return rc;
+    PV_CHECK(n_pairs == 0 || (A && B && totals), PV_ERR_INVALID, "assess: sequences or totals missing");
+    PV_CHECK(seg_capacity == 0 || segs, PV_ERR_INVALID, "assess: segment records missing");
+    PV_CHECK(err_capacity >= 0 && (err_capacity == 0 || errs), PV_ERR_INVALID, "assess: error records missing");
+    PV_CHECK(((uintptr_t)errs & 7) == 0, PV_ERR_INVALID, "assess: the error records must be aligned to 8 bytes");
+    PV_CHECK((Q != nullptr) == (qhist != nullptr), PV_ERR_INVALID, "assess: qualities and their table come together or not at all");
+    for (int64_t p = 0; p < n_pairs; p++) {
+        const int64_t na = a_off[p + 1] - a_off[p], nb = b_off[p + 1] - b_off[p];
+        PV_CHECK(na >= 0 && nb >= 0, PV_ERR_INVALID, "assess: the offsets of pair %lld decrease", (long long)p);
+        PV_CHECK(na < (1ll << 31) && nb < (1ll << 31), PV_ERR_INVALID, "assess: pair %lld holds a contig of 2^31 bytes or more",
+                 (long long)p);
+    }
+    PV_CHECK(a_off[0] == 0 && b_off[0] == 0, PV_ERR_INVALID, "assess: offsets must start at 0");
+    const size_t np = (size_t)n_pairs, cap = (size_t)seg_capacity, ecap = (size_t)err_capacity;
+    const size_t n_a = (size_t)a_off[n_pairs], n_b = (size_t)b_off[n_pairs];
+    if (Q)
+        for (size_t k = 0; k < n_a; k++)
+            PV_CHECK(Q[k] < PV_ASSESS_QBINS, PV_ERR_INVALID, "assess: quality %d at byte %lld is above %d", (int)Q[k], (long long)k,
+                     PV_ASSESS_QBINS - 1);
+    PV_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t need = pv_assess_errors_scratch_bytes(n_pairs, a_off, segment);
+    uint8_t *d_a = nullptr, *d_b = nullptr, *d_q = nullptr, *d_scratch = nullptr;
+    int64_t *d_ao = nullptr, *d_bo = nullptr, *d_so = nullptr, *d_tot = nullptr, *d_eo = nullptr, *d_qh = nullptr, *d_counts = nullptr;
+    pv_assess_seg* d_segs = nullptr;
+    pv_assess_error* d_errs = nullptr;
+    if ((rc = pv_get(ctx, "as.a", n_a > 0 ? n_a : 1, &d_a))) return rc;
+    if ((rc = pv_get(ctx, "as.b", n_b > 0 ? n_b : 1, &d_b))) return rc;
+    if ((rc = pv_get(ctx, "as.q", n_a > 0 ? n_a : 1, &d_q))) return rc;
+    if ((rc = pv_get(ctx, "as.a_off", np + 1, &d_ao))) return rc;
+    if ((rc = pv_get(ctx, "as.b_off", np + 1, &d_bo))) return rc;
+    if ((rc = pv_get(ctx, "as.seg_off", np + 1, &d_so))) return rc;
+    if ((rc = pv_get(ctx, "as.err_off", np + 1, &d_eo))) return rc;
+    if ((rc = pv_get(ctx, "as.totals", np > 0 ? np * PV_ASSESS_TOTALS : 1, &d_tot))) return rc;
+    if ((rc = pv_get(ctx, "as.qhist", np > 0 ? np * AS_QTAB : 1, &d_qh))) return rc;
+    if ((rc = pv_get(ctx, "as.segs", cap > 0 ? cap : 1, &d_segs))) return rc;
+    if ((rc = pv_get(ctx, "as.errs", ecap > 0 ? ecap : 1, &d_errs))) return rc;
+    if ((rc = pv_get(ctx, "as.scratch", (size_t)need, &d_scratch))) return rc;
+    if ((rc = pv_get(ctx, "as.counts", (size_t)8, &d_counts))) return rc;
+    if (n_a) PV_HIP(hipMemcpyAsync(d_a, A, n_a, hipMemcpyHostToDevice, st));
+    if (n_b) PV_HIP(hipMemcpyAsync(d_b, B, n_b, hipMemcpyHostToDevice, st));
+    if (n_a && Q) PV_HIP(hipMemcpyAsync(d_q, Q, n_a, hipMemcpyHostToDevice, st));
+    PV_HIP(hipMemcpyAsync(d_ao, a_off, (np + 1) * 8, hipMemcpyHostToDevice, st));
+    PV_HIP(hipMemcpyAsync(d_bo, b_off, (np + 1) * 8, hipMemcpyHostToDevice, st));
+    rc = pv_assess_errors_dev(ctx, d_a, d_ao, d_b, d_bo, n_pairs, segment, max_shift, seg_capacity, d_segs, d_so, d_tot,
+                              Q ? d_q : nullptr, err_capacity, d_errs, d_eo, Q ? d_qh : nullptr, d_scratch, need, d_counts, st);
+    if (rc) return rc;
+    PV_HIP(hipMemcpyAsync(counts, d_counts, 8 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    PV_HIP(hipMemcpyAsync(pair_seg_off, d_so, (np + 1) * 8, hipMemcpyDeviceToHost, st));
+    PV_HIP(hipMemcpyAsync(pair_err_off, d_eo, (np + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (np) PV_HIP(hipMemcpyAsync(totals, d_tot, np * PV_ASSESS_TOTALS * 8, hipMemcpyDeviceToHost, st));
+    if (np && Q) PV_HIP(hipMemcpyAsync(qhist, d_qh, np * AS_QTAB * 8, hipMemcpyDeviceToHost, st));
+    PV_HIP(hipStreamSynchronize(st));
+    const int64_t status = counts[1];
+    const bool valid = status == PV_OK || status == PV_ERR_CAPACITY;
+    // the records: all of them where the call failed (they are poisoned), else those written; under PV_ERR_CAPACITY no error
+    // record was written and the caller's stay as they were
+    const size_t n_rec = valid ? (size_t)counts[0] : cap;
+    const size_t n_err = status == PV_OK ? (size_t)counts[4] : valid ? 0 : ecap;
+    if (n_rec) PV_HIP(hipMemcpyAsync(segs, d_segs, n_rec * sizeof(pv_assess_seg), hipMemcpyDeviceToHost, st));
+    if (n_err) PV_HIP(hipMemcpyAsync(errs, d_errs, n_err * sizeof(pv_assess_error), hipMemcpyDeviceToHost, st));
+    if (n_rec || n_err) PV_HIP(hipStreamSynchronize(st));
+    PV_CHECK(status != PV_ERR_LIMIT, PV_ERR_LIMIT, "assess: %lld segment records needed, %lld given", (long long)counts[2],
+             (long long)seg_capacity);
+    PV_CHECK(status != PV_ERR_CAPACITY, PV_ERR_CAPACITY, "assess: %lld error records needed, %lld given", (long long)counts[5],
+             (long long)err_capacity);
     PV_CHECK(status == PV_OK, (int)status, "assess: device status %lld", (long long)status);
     return PV_OK;
 }

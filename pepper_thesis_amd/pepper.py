@@ -83,6 +83,14 @@ def assess_parser(ap=None):
     ap.add_argument("-d", "--draft", type=str, default=None,
                     help="FASTA of the draft: scored the same way into <output>_assess_draft.tsv; the log gives errors and QV "
                          "before -> after")
+    ap.add_argument("--errors", action="store_true", default=False,
+                    help="also write <output>_assess.errors.tsv: every substitution, insertion and deletion of the alignment, in "
+                         "assembly and truth coordinates (0-based); with -d the draft's list goes to "
+                         "<output>_assess_draft.errors.tsv")
+    ap.add_argument("-q", "--fastq", type=str, default=None,
+                    help="the FASTQ `polish --qualities` wrote for the -a assembly: every error is charged to the quality of its "
+                         "base, and <output>_assess.calibration.tsv gives, per contig and quality value, bases, errors and the "
+                         "observed QV")
     ap.add_argument("--segment", type=int, default=1024,
                     help="bases between anchors, a multiple of 32 in [256, 65536]; the windowed error track has this resolution")
     ap.add_argument("--max_shift", type=int, default=8192,

@@ -727,6 +727,74 @@ class Context:
                                       counts))
         return segs[:int(counts[0])], seg_off, totals
 
+    def assess_errors_scratch_bytes(self, a_off: np.ndarray, segment: int) -> int:
+        """bytes of scratch pv_assess_errors_dev needs for assemblies with these (host) offsets"""
+        ao = np.ascontiguousarray(a_off, np.int64)
+        n = int(self.lib.pv_assess_errors_scratch_bytes(len(ao) - 1, _ffi.ptr(ao), int(segment)))
+        if n < 0:
+            raise _ffi.PepperHipError(n, "assess: bad offsets or segment")
+        return n
+
+    def assess_errors_dev(self, d_a: int, d_a_off: int, d_b: int, d_b_off: int, n_pairs: int, segment: int, max_shift: int,
+                          seg_capacity: int, d_segs: int, d_pair_seg_off: int, d_totals: int, d_q: int, err_capacity: int,
+                          d_errs: int, d_pair_err_off: int, d_qhist: int, d_scratch: int, scratch_bytes: int, d_counts: int,
+                          stream: int = 0):
+        """asynchronous, device-resident pv_assess_errors_dev: every array is a device pointer (d_q and d_qhist both 0 without
+        qualities); d_counts int64[8] = {segment records, status, slots needed, scratch needed, error records written, error
+        records needed, 0, 0}. The status PV_ERR_CAPACITY (err_capacity too small) leaves every output but d_errs valid."""
+        _ffi.check(self.lib.pv_assess_errors_dev(self.handle, d_a or None, d_a_off, d_b or None, d_b_off, int(n_pairs), int(segment),
+                                                 int(max_shift), int(seg_capacity), d_segs or None, d_pair_seg_off,
+                                                 d_totals or None, d_q or None, int(err_capacity), d_errs or None, d_pair_err_off,
+                                                 d_qhist or None, d_scratch or None, int(scratch_bytes), d_counts, stream or None))
+
+    def assess_errors(self, pairs, quals=None, segment: int = 1024, max_shift: int = 8192, err_capacity: int = None,
+                      seg_capacity: int = None, counts=None, out=None):
+        """host-buffer pv_assess_errors of [(assembly bytes, truth bytes)], already upper-cased, and optionally one array of raw
+        Phred bytes (0..93) per assembly -> (segs, pair_seg_off, totals, errs, pair_err_off, qhist or None): errs a numpy record
+        array of pv_assess_error, pair_err_off int64 [n_pairs+1], qhist int64 [n_pairs, 94, 4] = {bases, sub, ins, del}.
+        err_capacity None: starts from (len A + len B) // 16 + 1024 records and, if the device reports PV_ERR_CAPACITY, calls
+        once more with the need it reported. A given err_capacity is used as it is. counts: optional ctypes int64[8]; out:
+        optional (segs, pair_seg_off, totals, errs [err_capacity], pair_err_off, qhist or None) arrays that receive the outputs,
+        also when the call raises."""
+        n = len(pairs)
+        a_off = np.zeros(n + 1, np.int64)
+        b_off = np.zeros(n + 1, np.int64)
+        a_off[1:] = np.cumsum([len(a) for a, _ in pairs])
+        b_off[1:] = np.cumsum([len(b) for _, b in pairs])
+        A = np.frombuffer(b"".join(bytes(a) for a, _ in pairs) or b"\0", np.uint8)
+        B = np.frombuffer(b"".join(bytes(b) for _, b in pairs) or b"\0", np.uint8)
+        Q = None
+        if quals is not None:
+            assert len(quals) == n and all(len(q) == len(a) for q, (a, _) in zip(quals, pairs)), "one quality per assembly base"
+            Q = np.ascontiguousarray(np.concatenate([np.frombuffer(bytes(q), np.uint8) for q in quals] + [np.zeros(1, np.uint8)]))
+        if seg_capacity is None:
+            seg_capacity = int(sum(len(a) // int(segment) + 1 for a, _ in pairs))
+        sized = err_capacity is not None
+        if not sized:
+            err_capacity = (int(a_off[n]) + int(b_off[n])) // 16 + 1024
+        if counts is None:
+            counts = (C.c_int64 * 8)()
+        for attempt in (0, 1):
+            if out is None or attempt:
+                out = (np.zeros(seg_capacity, np.dtype(_ffi.pv_assess_seg)), np.zeros(n + 1, np.int64),
+                       np.zeros((n, _ffi.PV_ASSESS_TOTALS), np.int64), np.zeros(err_capacity, np.dtype(_ffi.pv_assess_error)),
+                       np.zeros(n + 1, np.int64), None if Q is None else np.zeros((n, _ffi.PV_ASSESS_QBINS, 4), np.int64))
+            segs, seg_off, totals, errs, err_off, qhist = out
+            assert segs.dtype.itemsize == 64 and len(segs) >= seg_capacity and len(seg_off) == n + 1 and totals.shape == (n, 16)
+            assert errs.dtype.itemsize == 32 and len(errs) >= err_capacity and len(err_off) == n + 1
+            assert (qhist is None) == (Q is None) and (qhist is None or qhist.shape == (n, _ffi.PV_ASSESS_QBINS, 4))
+            rc = self.lib.pv_assess_errors(self.handle, _ffi.ptr(A), _ffi.ptr(a_off), _ffi.ptr(B), _ffi.ptr(b_off), n, int(segment),
+                                           int(max_shift), int(seg_capacity), _ffi.ptr(segs) if len(segs) else None,
+                                           _ffi.ptr(seg_off), _ffi.ptr(totals) if n else None, _ffi.ptr(Q), int(err_capacity),
+                                           _ffi.ptr(errs) if len(errs) else None, _ffi.ptr(err_off),
+                                           _ffi.ptr(qhist) if Q is not None else None, counts)
+            if rc == _ffi.PV_ERR_CAPACITY and not sized and attempt == 0:
+                err_capacity = int(counts[5])   # the one sized second call
+                continue
+            _ffi.check(rc)
+            break
+        return segs[:int(counts[0])], seg_off, totals, errs[:int(counts[4])], err_off, qhist
+
     def profile_begin(self, only: str = None):
         """bracket every kernel launch of this context with HIP events (only: just the kernels whose profile name starts
         with it - two events per launch put a few microseconds between kernels)"""
