@@ -508,7 +508,8 @@ int pv_polish_filter_low_support(pv_ctx* ctx, const pv_polish_out* chunks, int64
 /* The polisher without a model: a majority vote of the reads of every chunk row, from the builder's raw counts, that writes
  * the two planes pv_rnn_forward_p2[_dev] writes, labels and acc, so that everything behind the network (pv_polish_row_qual,
  * the mask, the filters, the stitch, the edits and their evidence) runs on it unchanged. It is the floor a trained network
- * is compared with, not a replacement: a pileup majority cannot mend systematic read errors (homopolymer lengths). The
+ * is compared with, not a replacement: a pileup majority cannot mend systematic read errors (homopolymer lengths; the part
+ * of them that comes from voting per column and not per read is what pv_polish_vote_runs below takes on). The
  * reference has no counterpart.
  * chunks: position, index, region, chunk_id, depth and counts (4-byte aligned) of n_chunks chunks (pv_polish_summarize_regions
  * [_dev] with both planes); region_start, ref_off, ref, seq_length, seq_overlap: as for pv_polish_edits_evidence_dev.
@@ -548,6 +549,61 @@ int pv_polish_vote_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunk
 int pv_polish_vote(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const int64_t* region_start,
                    const int64_t* ref_off, const uint8_t* ref, int32_t n_regions, int seq_length, int seq_overlap,
                    uint8_t* labels, float* acc, int64_t* counts);
+
+/* The run vote (`polish --vote --runs`): behind pv_polish_vote[_dev], on the same labels / acc planes and in place, the
+ * length of every homopolymer run of the draft is voted READ BY READ. The column vote sees the ten counts of a row, not which
+ * read spelled what: deletions that the aligner left-aligns pile up in a run's first column though no length but the
+ * draft's has a majority, and an inserted base that sits at several anchors never gathers one in any insert row. Here every
+ * read measures the run once. What stays out of reach: a miscall most reads share, runs above 48 bytes, adjacent runs. The
+ * reference has no counterpart.
+ * chunks: position, index, region, chunk_id of n_chunks chunks (chunk_capacity >= n_chunks; depth and counts are not read);
+ * in: the read batch the builder was given, DEVICE pointers (read_off, read_pos, read_mapq, base_off, bases, cigar_off, cigar
+ * are read; in->n_regions must equal n_regions) with its totals n_reads, n_bases, n_cigar and n_ref_bytes = ref_off[n_regions],
+ * as pv_polish_summarize_regions_dev takes them; region_start, ref_off, ref, n_regions, seq_length, seq_overlap: as for
+ * pv_polish_vote_dev; min_run in 2..48, anything else is refused with PV_ERR_INVALID by the call itself.
+ * STRETCHES AND CANDIDATES. In the draft bytes of region g, ref[ref_off[g] .. ref_off[g+1]), a stretch is a maximal sequence
+ *   [s, e] of one letter b of A, C, G, T (ASCII a..z upper-cased first; any other byte ends a stretch), n = e - s + 1. It is a
+ *   CANDIDATE when min_run <= n <= 48 and both flanks s-1 and e+1 lie inside the region's draft bytes. A candidate one of whose
+ *   flanks lies in another candidate (the stretch that ends at s-1 or starts at e+1 is a candidate by the sentence before;
+ *   the test is not repeated on what it leaves) is SKIPPED: the two would share the insert rows between them, so both stay
+ *   with the column vote. The others are the runs voted on. Positions below are draft positions, region_start[g] + offset.
+ * VOTERS. Walk a read's CIGAR from read_pos: M, = and X align a read base to every draft position they cover; I and S advance
+ *   the read only; D, N and P the draft only (the builder's deleted columns); anything else nothing. A read of region g
+ *   (read_off) with mapping quality above 0 (the builder's rule, so the voters are reads the images hold) SPANS a run when it
+ *   has an aligned base at s-1 and at e+1, at read offsets q0 < q1; S is the number of spanning reads (mapping quality 0 is
+ *   in neither S nor V). A spanning read is a VOTER when len = q1 - q0 - 1 <= 63, its bytes at q0 and q1, upper-cased,
+ *   differ from b, and every byte strictly between them, upper-cased, equals b. len = 0 is valid: the read deleted the run.
+ *   V is the number of voters, h[len] their number per length; both strands count together.
+ * DECISION. A run is decided iff V >= 1 and 2 * V > S; an undecided run keeps the column vote's rows (an insertion of another
+ *   base next to the run makes most reads impure, and that insertion must survive). The winner L is the length with the
+ *   largest h; among equal ones n, else the closest to n, else the smaller.
+ * ROWS. A decided run's span is every chunk row with position in [s, e] and the insert rows (index > 0) at position s-1, in
+ *   every chunk that holds one, owned or not, in (position, index) order:
+ *   L <= n: the first n - L base rows get label 0 (left-aligned, as VCF normalisation places a deletion), the other base rows
+ *           b's label (1 + its place in "ACGT"), every insert row of the span 0.
+ *   L >  n: every base row gets b's label, the first L - n insert rows of the span b's label, the others 0. Some voter holds
+ *           L - n inserted bytes inside the span, so that many insert rows exist; where the chunks hold fewer the status is
+ *           PV_ERR_STATE (never expected).
+ *   acc (where not NULL) of a rewritten row j: w(j) * ((float)h[L] / (float)V) in the label's slot, w(j) as in the vote rule,
+ *           and 0.0f in the other four. pv_polish_row_qual reads the label's slot only, so the row's Phred byte is that of the
+ *           fraction of the run's voters whose length is not L, the same for every row of the span.
+ *   The flat row of chunk c's row j inside its region is c * (seq_length - seq_overlap) + j (the builder's layout); the rank
+ *   of an insert row inside its span follows from it and from the flat row of the left flank's base row.
+ * d_counts[6] = {runs decided, status, first bad chunk (-1 if none), decided runs with L != n, candidates, candidates
+ * skipped}. Status PV_ERR_INVALID: the chunk layout is broken exactly as for pv_polish_vote_dev; PV_ERR_STATE as above
+ * (d_counts[2] = -1). Under either nothing but d_counts is written, and d_counts[0] and [3] are 0. With n_chunks == 0 or no
+ * draft bytes nothing is looked at: d_counts = {0, PV_OK, -1, 0, 0, 0}. Device-resident and asynchronous on `stream`; six
+ * launches, no global atomics (the histograms are LDS counters of the tile of 256 draft bytes a run starts in), no host
+ * synchronisation; capturable; the result does not depend on the launch geometry. */
+int pv_polish_vote_runs_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const pv_batch_in* in, int64_t n_reads,
+                            int64_t n_bases, int64_t n_cigar, int64_t n_ref_bytes, const int64_t* region_start,
+                            const int64_t* ref_off, const uint8_t* ref, int32_t n_regions, int seq_length, int seq_overlap,
+                            int min_run, uint8_t* labels, float* acc, int64_t* d_counts, void* stream);
+/* HOST buffers in and out: `in` is the host batch (its ref_start, ref_off and ref are the regions' and the draft's; it is staged
+ * with pv_upload_batch, so it must pass the builder's checks); labels and acc (or NULL) hold the column vote's planes and are
+ * rewritten in place; counts[6] as d_counts above; returns the status (on an error status labels and acc are left as they were). */
+int pv_polish_vote_runs(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, const pv_batch_in* in, int seq_length,
+                        int seq_overlap, int min_run, uint8_t* labels, float* acc, int64_t* counts);
 
 /* The polisher's read realignment (AlignmentSummarizer.reads_to_reference_realignment, pepper/modules/python/
  * AlignmentSummarizer.py:159-177 -> ReadAligner::align_reads_to_reference, simple_aligner.cpp:66-107): every read of a region

@@ -331,6 +331,12 @@ SYMBOLS = [
     ("pv_polish_vote", C.c_int,
      [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int, C.c_void_p,
       C.c_void_p, C.POINTER(C.c_int64)]),
+    ("pv_polish_vote_runs_dev", C.c_int,
+     [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.POINTER(pv_batch_in), C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pv_polish_vote_runs", C.c_int,
+     [C.c_void_p, C.POINTER(pv_polish_out), C.c_int64, C.POINTER(pv_batch_in), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+      C.POINTER(C.c_int64)]),
     ("pv_polish_realign", C.c_int, [C.c_void_p, C.POINTER(pv_batch_in), C.c_void_p, C.c_void_p, C.POINTER(pv_realign_out)]),
     ("pv_polish_realign_dev", C.c_int,
      [C.c_void_p, C.POINTER(pv_batch_in), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(pv_realign_out),

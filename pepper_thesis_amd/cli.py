@@ -154,6 +154,15 @@ def polish_parser(ap=None):
                          "draft), and qualities come from the fraction of reads that disagree. In place of -m and --bf16; the "
                          "floor a trained model is compared with, not a replacement (opt-in; one device)")
     _model_or_vote(ap)
+    ap.add_argument("--runs", action="store_true", default=False,
+                    help="with --vote: vote the length of every homopolymer run of the draft read by read. A read that spans a run "
+                         "and holds nothing but the run's letter between the flanks votes its length; where more than half of "
+                         "the spanning reads vote, the most frequent length is written (ties keep the draft's). Mends what a "
+                         "column vote cannot: left-aligned deletions piling up in a correct run, an inserted base spread over "
+                         "several anchors. Not with --min_support or several -d_ids (opt-in)")
+    ap.add_argument("--min_run", type=int, default=None,
+                    help="with --runs: the shortest draft run voted on, 2..48 (default 3); runs above 48 bases and runs that "
+                         "touch another run are left to the column vote")
     ap.add_argument("-o", "--output_file", type=str, required=True,
                     help="output prefix; made a directory as in the reference: the FASTA is <output_file>/_pepper_polished.fa")
     ap.add_argument("-t", "--threads", type=int, default=5, help="reader threads (with several -d_ids: the total over the ranks)")

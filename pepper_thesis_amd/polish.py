@@ -10,7 +10,7 @@ without leaving HBM; only the region offsets and the polished bases (one byte pe
 
   python -m pepper_thesis_amd polish -b reads.bam -f draft.fa -m model.pkl -o out/polished [-t 5] [-r ctg:start-end] [--bf16]
       [--realign] [--gpu_decode] [--qualities] [--edits [--evidence]] [--min_depth N] [--min_qual Q] [--min_support K] [-hp]
-  python -m pepper_thesis_amd polish -b reads.bam -f draft.fa --vote -o out/polished [the same flags but -m and --bf16]
+  python -m pepper_thesis_amd polish -b reads.bam -f draft.fa --vote [--runs [--min_run N]] -o out/polished [the same flags but -m and --bf16]
 
 --gpu_decode (opt-in) replaces the first stage: reader threads only plan blocks and fetch draft bytes, and the BAM is inflated,
 decoded and clipped on the device (gpu_decode.py; _decoded_pieces below). Same FASTA.
@@ -78,6 +78,17 @@ keeps the draft; over a draft byte other than ACGT it leaves the sequence, since
 changed and the rows without reads, and the edits VCF carries one ##pepper_consensus=vote line. It is the floor a trained
 model is compared with, not a replacement: a majority cannot mend systematic read errors such as homopolymer lengths.
 Without the flag no output changes by a byte. The reference has no counterpart.
+
+--vote --runs [--min_run N] (opt-in, one device, behind --vote only; N in 2..48, default 3; not with --min_support, whose
+promise is per column) also votes the length of every homopolymer run of the draft read by read: directly behind the column
+vote pv_polish_vote_runs_dev takes the batch the builder was given (realigned under --realign, one haplotype's under -hp),
+lets every read that spans a run and holds nothing but its letter between the flanks vote its length, and where more than
+half of the spanning reads vote rewrites the run's rows to the most frequent length (ties keep the draft's; the rule is in
+include/pepper_hip.h). It mends what a column vote cannot: left-aligned deletions piling up in a correct run's first column,
+an inserted base spread over several anchors. A miscall most reads share stays wrong; runs above 48 bases and adjacent runs
+are left alone. The --evidence numbers stay the column's own counts. The log counts the runs seen, decided, changed and
+skipped, and the edits VCF carries ##pepper_consensus=vote+runs and ##pepper_min_run=N. Without the flag no output changes by
+a byte.
 
 Semantics kept from the reference:
   * regions: ImageGenerationUI.py:257-273 - for pos in range(start, end, 1000): [max(start, pos-100), min(end, pos+1100)],
@@ -241,6 +252,9 @@ class ChainResult(NamedTuple):
     evidence = None
     # --vote: (chunk rows whose winner is not what the draft holds, base rows without reads), carried the same way; with_voted()
     voted = None
+    # --vote --runs: (candidate runs seen, runs decided, decided runs whose length changes, candidates skipped as adjacent),
+    # carried the same way; with_runs()
+    runs = None
 
     def region(self, g: int) -> tuple:
         """region g's share: (bases, qual or None, edits or None), and behind them its evidence records where the result
@@ -269,14 +283,14 @@ def hp_path(path: str, haplotype: int) -> str:
 
 
 class _MaskedChainResult(ChainResult):
-    """a ChainResult with the instance attributes `masked`, `filtered`, `supported`, `evidence` and `voted`"""
+    """a ChainResult with the instance attributes `masked`, `filtered`, `supported`, `evidence`, `voted` and `runs`"""
 
 
 def with_masked(res: ChainResult, masked: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a minimum-depth chain in its attribute `masked`"""
     out = _MaskedChainResult(*res)
     out.masked, out.filtered, out.evidence = (int(masked[0]), int(masked[1])), res.filtered, res.evidence
-    out.supported, out.voted = res.supported, res.voted
+    out.supported, out.voted, out.runs = res.supported, res.voted, res.runs
     return out
 
 
@@ -284,7 +298,7 @@ def with_filtered(res: ChainResult, filtered: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a minimum-quality chain in its attribute `filtered`"""
     out = _MaskedChainResult(*res)
     out.masked, out.filtered, out.evidence = res.masked, (int(filtered[0]), int(filtered[1])), res.evidence
-    out.supported, out.voted = res.supported, res.voted
+    out.supported, out.voted, out.runs = res.supported, res.voted, res.runs
     return out
 
 
@@ -292,7 +306,7 @@ def with_supported(res: ChainResult, supported: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a minimum-support chain in its attribute `supported`"""
     out = _MaskedChainResult(*res)
     out.masked, out.filtered, out.evidence = res.masked, res.filtered, res.evidence
-    out.supported, out.voted = (int(supported[0]), int(supported[1])), res.voted
+    out.supported, out.voted, out.runs = (int(supported[0]), int(supported[1])), res.voted, res.runs
     return out
 
 
@@ -300,7 +314,15 @@ def with_voted(res: ChainResult, voted: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a vote chain in its attribute `voted`"""
     out = _MaskedChainResult(*res)
     out.masked, out.filtered, out.evidence, out.supported = res.masked, res.filtered, res.evidence, res.supported
-    out.voted = (int(voted[0]), int(voted[1]))
+    out.voted, out.runs = (int(voted[0]), int(voted[1])), res.runs
+    return out
+
+
+def with_runs(res: ChainResult, runs: Tuple[int, int, int, int]) -> ChainResult:
+    """res, carrying the counts of a run-vote chain in its attribute `runs`"""
+    out = _MaskedChainResult(*res)
+    out.masked, out.filtered, out.evidence, out.supported = res.masked, res.filtered, res.evidence, res.supported
+    out.voted, out.runs = res.voted, tuple(int(v) for v in runs)
     return out
 
 
@@ -309,7 +331,7 @@ def with_evidence(res: ChainResult, evidence: np.ndarray) -> ChainResult:
     assert res.edits is not None and len(evidence) == len(res.edits), (len(evidence), res.edits is None)
     out = _MaskedChainResult(*res)
     out.masked, out.filtered, out.evidence = res.masked, res.filtered, evidence
-    out.supported, out.voted = res.supported, res.voted
+    out.supported, out.voted, out.runs = res.supported, res.voted, res.runs
     return out
 
 
@@ -389,12 +411,20 @@ class _DeviceChain:
     it needs neither edits nor qualities nor evidence. vote: the builder also fills the depth and the counts plane and
     pv_polish_vote_dev stands where the network stands: the labels (and, where row qualities are needed, the read fractions
     in the place of the softmax sums) come from the majority of the reads of every row, and the context needs no weights (the
-    result's voted)."""
+    result's voted). vote_runs = min_run >= 2 (needs vote): pv_polish_vote_runs_dev runs directly behind the vote with the
+    batch the builder was given (realigned under --realign, one haplotype's under -hp) and rewrites the rows of every
+    homopolymer run whose length the reads decide (the result's runs)."""
 
     def __init__(self, ctx, own_ctx: bool = False, qualities: bool = False, edits: bool = False, min_depth: int = 0,
-                 min_qual: int = 0, use_hp: bool = False, evidence: bool = False, min_support: int = 0, vote: bool = False):
+                 min_qual: int = 0, use_hp: bool = False, evidence: bool = False, min_support: int = 0, vote: bool = False,
+                 vote_runs: int = 0):
         import torch
         self.vote = bool(vote)
+        self.vote_runs = int(vote_runs)
+        if self.vote_runs and not self.vote:
+            raise ValueError("a chain with vote_runs needs vote: the run vote rewrites the rows the column vote left")
+        if self.vote_runs and min_support:
+            raise ValueError("a chain with vote_runs takes no min_support: that filter's promise is per column")
         if evidence and not edits:
             raise ValueError("a chain with evidence needs edits: the evidence records stand beside the edit records")
         self.evidence = bool(evidence)
@@ -410,6 +440,7 @@ class _DeviceChain:
         self.min_support = int(min_support)
         self.support_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.vote_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
+        self.runs_counts = torch.zeros(6, dtype=torch.int64, device=self.dev)
         self.edit_buf = None
         self.edit_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.dout = self.labels = self.seq = None
@@ -630,6 +661,7 @@ class _DeviceChain:
             res = with_masked(res, (0, 0)) if self.min_depth > 0 else res
             res = with_filtered(res, (0, 0)) if self.min_qual > 0 else res
             res = with_voted(res, (0, 0)) if self.vote else res
+            res = with_runs(res, (0, 0, 0, 0)) if self.vote_runs else res
             return with_supported(res, (0, 0)) if self.min_support > 0 else res
         d_acc, d_row_qual, d_qual = (t.data_ptr() for t in (self.acc, self.row_qual, self.qual)) if self.qualities else (0, 0, 0)
         # --min_qual without --qualities: the row qualities are made for the filter alone; mask, stitch and edits run as without
@@ -640,6 +672,9 @@ class _DeviceChain:
         if self.vote:   # the reads' majority in the network's place: the same two planes, from the counts of this batch
             self.ctx.polish_vote_dev(self.dout, n, d_ref_start, db.t["ref_off"].data_ptr(), db.t["ref"].data_ptr(), n_regions,
                                      d_labels, d_filter_acc, self.vote_counts.data_ptr())
+            if self.vote_runs:   # and every homopolymer run's length read by read, in place, from the reads the builder had
+                self.ctx.polish_vote_runs_dev(self.dout, n, db, d_ref_start, db.t["ref_off"].data_ptr(), db.t["ref"].data_ptr(),
+                                              n_regions, self.vote_runs, d_labels, d_filter_acc, self.runs_counts.data_ptr())
         else:
             self.ctx.forward_p2_dev(self.dout.images.data_ptr(), n, d_labels, d_filter_acc)
         if d_filter_qual:
@@ -698,9 +733,16 @@ class _DeviceChain:
             if status != _ffi.PV_OK:
                 raise _ffi.PepperHipError(status, "polisher vote: device status %d (chunk %d)" % (status, bad))
             voted = (n_changed, n_no_reads)
+        runs = None
+        if self.vote_runs:
+            n_decided, status, bad, n_run_changed, n_seen, n_skipped = (int(v) for v in self.runs_counts.tolist())
+            if status != _ffi.PV_OK:
+                raise _ffi.PepperHipError(status, "polisher run vote: device status %d (chunk %d)" % (status, bad))
+            runs = (n_seen, n_decided, n_run_changed, n_skipped)
 
         def counted(res):
             res = res if voted is None else with_voted(res, voted)
+            res = res if runs is None else with_runs(res, runs)
             res = res if masked is None else with_masked(res, masked)
             res = res if filtered is None else with_filtered(res, filtered)
             return res if supported is None else with_supported(res, supported)
@@ -722,7 +764,7 @@ class _DeviceChain:
 
 def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int, qualities: bool = False,
                       edits: bool = False, min_depth: int = 0, min_qual: int = 0, use_hp: bool = False,
-                      evidence: bool = False, min_support: int = 0, vote: bool = False) -> _DeviceChain:
+                      evidence: bool = False, min_support: int = 0, vote: bool = False, vote_runs: int = 0) -> _DeviceChain:
     """a context on `device` with the polisher weights loaded, and the chain on it (closing the chain closes the context).
     shared_device: other ranks use this GPU too, so the option is set before the first device call (the split GRU forms need
     co-resident workgroups and would time out, poisoning the labels). False leaves the create-time default (PV_SHARED_DEVICE).
@@ -732,7 +774,8 @@ def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype:
     (passed only when set): the chain of -hp, whose run gives a HapChainResult. evidence (passed only when set): the chain of
     --evidence, whose results carry an evidence record per edit record. min_support (passed only when set): the chain of
     --min_support, whose results carry its counts. vote (passed only when set): the chain of --vote, whose results carry its
-    counts; no weights are loaded and state_dict may be None."""
+    counts; no weights are loaded and state_dict may be None. vote_runs (passed only when set): the chain of --vote --runs
+    with that min_run, whose results carry the run counts."""
     from .runtime import Context
     ctx = Context(device)
     try:
@@ -742,7 +785,8 @@ def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype:
             ctx.load_p2(state_dict, dtype)
         return _DeviceChain(ctx, own_ctx=True, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual,
                             use_hp=use_hp, **({"evidence": True} if evidence else {}),
-                            **({"min_support": min_support} if min_support else {}), **({"vote": True} if vote else {}))
+                            **({"min_support": min_support} if min_support else {}), **({"vote": True} if vote else {}),
+                            **({"vote_runs": vote_runs} if vote_runs else {}))
     except BaseException:
         ctx.close()
         raise
@@ -773,7 +817,8 @@ def _timers(timers: Optional[dict], more=()) -> dict:
     """the caller's timer dict (or a fresh one) with the keys of polish_pieces, and `more`, present"""
     T = timers if timers is not None else {}
     for k in ("read_s", "device_s", "regions", "batches", "masked_rows", "unmaskable_rows", "reverted_rows", "pinned_rows",
-              "unsupported_rows", "pinned_unsupported_rows", "voted_rows", "no_read_rows") + tuple(more):
+              "unsupported_rows", "pinned_unsupported_rows", "voted_rows", "no_read_rows", "runs_seen", "runs_decided",
+              "runs_changed", "runs_skipped") + tuple(more):
         T.setdefault(k, 0)
     return T
 
@@ -805,6 +850,9 @@ def _count_masked(T: dict, res) -> None:
     if getattr(res, "voted", None) is not None:
         T["voted_rows"] += res.voted[0]
         T["no_read_rows"] += res.voted[1]
+    if getattr(res, "runs", None) is not None:
+        for k, v in zip(("runs_seen", "runs_decided", "runs_changed", "runs_skipped"), res.runs):
+            T[k] += v
 
 
 def kept_range(w: Work) -> Tuple[int, int]:
@@ -965,7 +1013,7 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
                  threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None,
                  realign: bool = False, chain=None, gpu_decode: bool = False, qualities: bool = False, edits: bool = False,
                  min_depth: int = 0, min_qual: int = 0, use_hp: bool = False, evidence: bool = False,
-                 min_support: int = 0, vote: bool = False) -> str:
+                 min_support: int = 0, vote: bool = False, vote_runs: int = 0) -> str:
     """-> path of the polished FASTA (use_hp: of haplotype 1's). batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
     realign: realign every read to the draft on the device before the builder, as the reference always does.
     chain: a chain with the weights already loaded (open_device_chain; the caller closes it), else one is made on `ctx`
@@ -986,12 +1034,15 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
     evidence (with edits): every VCF record carries DP, AD, SAF and SAR of its weakest column (polish_edits.compose_records);
     this function's own chain attaches the evidence (a chain passed in must have been made for it).
     vote: the labels come from the reads' majority: model_path is not read (it may be None), this function's own chain votes
-    (a chain passed in must have been made for it), and the VCF names the consensus."""
+    (a chain passed in must have been made for it), and the VCF names the consensus.
+    vote_runs = min_run >= 2 (with vote): this function's own chain also votes every homopolymer run's length read by read
+    (a chain passed in must have been made with the same min_run), and the VCF names the consensus vote+runs and min_run."""
     from .bamio import BamHandler, FastaHandler
     from .runtime import Context
     t_start = time.perf_counter()
     T = dict(read_s=0.0, device_s=0.0, regions=0, batches=0, bases_in=0, bases_out=0, masked_rows=0, unmaskable_rows=0, draft_regions=0,
-             reverted_rows=0, pinned_rows=0, unsupported_rows=0, pinned_unsupported_rows=0, voted_rows=0, no_read_rows=0)
+             reverted_rows=0, pinned_rows=0, unsupported_rows=0, pinned_unsupported_rows=0, voted_rows=0, no_read_rows=0,
+             runs_seen=0, runs_decided=0, runs_changed=0, runs_skipped=0)
     own = None
     if chain is None:
         state_dict = None if vote else load_polish_model(model_path)
@@ -1001,7 +1052,7 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
             ctx.load_p2(state_dict, dtype)
         chain = _DeviceChain(ctx, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual, use_hp=use_hp,
                              **({"evidence": True} if evidence else {}), **({"min_support": min_support} if min_support else {}),
-                             **({"vote": True} if vote else {}))
+                             **({"vote": True} if vote else {}), **({"vote_runs": vote_runs} if vote_runs else {}))
     if evidence and not edits:
         raise ValueError("polish_fused: evidence needs edits: the numbers go into the edits VCF")
     try:
@@ -1021,6 +1072,9 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
         if bool(vote) != bool(getattr(chain, "vote", False)):
             raise ValueError("polish_fused: the chain %s: it was not made for this run"
                              % ("does not vote" if vote else "votes in the network's place"))
+        if int(vote_runs) != int(getattr(chain, "vote_runs", 0) or 0):
+            raise ValueError("polish_fused: the chain votes runs from length %r, not %d: it was not made for this run"
+                             % (getattr(chain, "vote_runs", 0), vote_runs))
         if use_hp and not getattr(chain, "use_hp", False):
             raise ValueError("polish_fused: the chain does not select reads by haplotype: it was not made for this run")
         if use_hp:
@@ -1051,7 +1105,8 @@ def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region:
             polish_edits.write_edits_vcf(polish_edits.output_vcf_path(path), *vcf, **({"haplotype": h} if h else {}),
                                          **({"evidence": True} if evidence else {}),
                                          **({"min_support": min_support} if min_support else {}),
-                                         **({"consensus": "vote"} if vote else {}))
+                                         **({"consensus": "vote+runs" if vote_runs else "vote"} if vote else {}),
+                                         **({"min_run": vote_runs} if vote_runs else {}))
             if evidence:   # records whose alt support (of their weakest column) stands on one strand only
                 T["one_strand_records"] = T.get("one_strand_records", 0) + sum(
                     (r.evidence[2] == 0) != (r.evidence[3] == 0) for recs in vcf[4].values() for r in recs)
@@ -1152,6 +1207,26 @@ def run(args, open_chain=open_device_chain) -> int:
         sys.stderr.write("ERROR: polish --min_support runs on one device (-d_ids %s lists %d): the counts plane is not carried "
                          "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
         return 2
+    runs = bool(getattr(args, "runs", False))
+    min_run = int(getattr(args, "min_run", None) or 3) if runs else 0
+    if getattr(args, "min_run", None) is not None and not runs:
+        sys.stderr.write("ERROR: polish --min_run needs --runs: it is the shortest homopolymer run the run vote looks at.\n")
+        return 2
+    if runs and not vote:
+        sys.stderr.write("ERROR: polish --runs needs --vote: the run vote rewrites the rows the reads' column vote left; behind a "
+                         "model it has no meaning.\n")
+        return 2
+    if runs and not 2 <= min_run <= 48:
+        sys.stderr.write("ERROR: polish --min_run %d: the shortest run voted on is a length from 2 to 48.\n" % min_run)
+        return 2
+    if runs and len(plan) > 1:
+        sys.stderr.write("ERROR: polish --runs runs on one device (-d_ids %s lists %d): the reads are not carried through the "
+                         "rank exchange.\n" % (args.device_ids, len(plan)))
+        return 2
+    if runs and min_support:
+        sys.stderr.write("ERROR: polish --runs takes no --min_support: that filter promises that at least K reads spell an edit in "
+                         "its own column, and a run-voted column can be one that few reads delete there.\n")
+        return 2
     if vote and len(plan) > 1:
         sys.stderr.write("ERROR: polish --vote runs on one device (-d_ids %s lists %d): the counts plane is not carried "
                          "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
@@ -1191,6 +1266,8 @@ def run(args, open_chain=open_device_chain) -> int:
         kw["min_support"] = min_support
     if vote:
         kw["vote"] = True
+    if runs:
+        kw["vote_runs"] = min_run
     chain = open_chain(device, False, state_dict, dtype, **kw)
     try:
         T = {}
@@ -1199,7 +1276,8 @@ def run(args, open_chain=open_device_chain) -> int:
                             gpu_decode=bool(getattr(args, "gpu_decode", False)), qualities=qualities, edits=edits,
                             min_depth=min_depth, min_qual=min_qual, **({"use_hp": True} if use_hp else {}),
                             **({"evidence": True} if evidence else {}),
-                            **({"min_support": min_support} if min_support else {}), **({"vote": True} if vote else {}))
+                            **({"min_support": min_support} if min_support else {}), **({"vote": True} if vote else {}),
+                            **({"vote_runs": min_run} if runs else {}))
     except ValueError as e:
         if not edits:
             raise
@@ -1221,6 +1299,9 @@ def run(args, open_chain=open_device_chain) -> int:
     if vote:
         log("VOTE: %d CHUNK ROWS WHERE THE READS' MAJORITY IS NOT THE DRAFT, %d BASE ROWS WITHOUT READS (THE DRAFT IS KEPT, OR "
             "DROPPED WHERE ITS BYTE IS NOT ACGT)" % (T["voted_rows"], T["no_read_rows"]))
+    if runs:
+        log("RUNS (MIN RUN %d): %d CANDIDATE RUNS SEEN, %d DECIDED BY THEIR READS, %d OF THEM WITH A LENGTH THAT IS NOT THE DRAFT'S, "
+            "%d SKIPPED AS ADJACENT" % (min_run, T["runs_seen"], T["runs_decided"], T["runs_changed"], T["runs_skipped"]))
     if min_depth:
         log("MIN DEPTH %d: %d CHUNK ROWS KEPT THE DRAFT, %d COULD NOT (DRAFT BYTE NOT ACGT), %d REGIONS WITHOUT READS FILLED FROM THE DRAFT"
             % (min_depth, T["masked_rows"], T["unmaskable_rows"], T["draft_regions"]))

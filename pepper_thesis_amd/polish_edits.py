@@ -156,7 +156,7 @@ def no_read_runs(ranges: Iterable[Tuple[str, int, int]]) -> List[Tuple[str, int,
 
 def vcf_text(source: str, reference: str, contigs: Sequence[Tuple[str, int]], no_reads: Sequence[Tuple[str, int, int]],
              records: Dict[str, Sequence[VcfRecord]], min_depth: int = 0, min_qual: int = 0, haplotype: int = 0,
-             evidence: bool = False, min_support: int = 0, consensus: str = "") -> str:
+             evidence: bool = False, min_support: int = 0, consensus: str = "", min_run: int = 0) -> str:
     """header (fileformat, source, reference, one contig line per contig of the run in natural order, one pepper_no_reads line
     per read-free run, the column line) and the records, contigs in natural order; eight columns, no samples.
     min_depth >= 1 (`polish --min_depth`): one pepper_min_depth line stands in the place of the pepper_no_reads lines; the
@@ -166,6 +166,7 @@ def vcf_text(source: str, reference: str, contigs: Sequence[Tuple[str, int]], no
     haplotype >= 1 (`polish -hp`): one pepper_haplotype line, the last before the column line.
     consensus (`polish --vote`: "vote"): one pepper_consensus line, the first of the pepper_* lines: the labels came from the
     reads' majority, not from a model.
+    min_run >= 2 (`polish --vote --runs`, consensus "vote+runs"): one pepper_min_run line directly behind the pepper_consensus line.
     evidence (`polish --evidence`): four ##INFO lines (DP, AD, SAF, SAR) in front of the pepper_* lines, and the INFO column of
     every EvidenceVcfRecord holds its numbers (info_text); any other record keeps `.`."""
     from .polish import natural_key
@@ -177,6 +178,8 @@ def vcf_text(source: str, reference: str, contigs: Sequence[Tuple[str, int]], no
         lines += list(EVIDENCE_INFO_LINES)
     if consensus:
         lines.append("##pepper_consensus=" + consensus)
+    if min_run >= 2:
+        lines.append("##pepper_min_run=%d" % min_run)
     if min_depth >= 1:
         assert not no_reads, no_reads
         lines.append("##pepper_min_depth=%d" % min_depth)
@@ -198,7 +201,7 @@ def vcf_text(source: str, reference: str, contigs: Sequence[Tuple[str, int]], no
 def write_edits_vcf(path: str, source: str, reference: str, contigs: Sequence[Tuple[str, int]],
                     no_reads: Sequence[Tuple[str, int, int]], records: Dict[str, Sequence[VcfRecord]], min_depth: int = 0,
                     min_qual: int = 0, haplotype: int = 0, evidence: bool = False, min_support: int = 0,
-                    consensus: str = "") -> None:
+                    consensus: str = "", min_run: int = 0) -> None:
     """vcf_text through bamio.write_vcf_gz (bgzip + tabix): `path` and `path`.tbi, both written under temporary names and
     renamed when complete"""
     from . import bamio
@@ -208,7 +211,8 @@ def write_edits_vcf(path: str, source: str, reference: str, contigs: Sequence[Tu
     try:
         bamio.write_vcf_gz(tmp, vcf_text(source, reference, contigs, no_reads, records, min_depth, min_qual, haplotype, evidence,
                                               **({"min_support": min_support} if min_support else {}),
-                                              **({"consensus": consensus} if consensus else {})))
+                                              **({"consensus": consensus} if consensus else {}),
+                                              **({"min_run": min_run} if min_run else {})))
         os.replace(tmp + ".tbi", path + ".tbi")
         os.replace(tmp, path)
     except BaseException:

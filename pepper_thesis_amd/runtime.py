@@ -683,6 +683,32 @@ class Context:
                                            int(seq_overlap), _ffi.ptr(labels), _ffi.ptr(acc), counts))
         return labels if acc is None else (labels, acc)
 
+    def polish_vote_runs_dev(self, dout: "DevicePolishOut", n_chunks: int, dbatch, d_region_start: int, d_ref_off: int,
+                             d_ref: int, n_regions: int, min_run: int, d_labels: int, d_acc: int, d_counts: int, stream: int = 0):
+        """asynchronous, device-resident run vote (pv_polish_vote_runs_dev) behind polish_vote_dev, in place on the same
+        d_labels / d_acc (0: no acc): the reads of dbatch, the batch the builder was given, vote the length of every
+        homopolymer run of the draft; {runs decided, status, first bad chunk, decided runs whose length changes, candidates,
+        candidates skipped as adjacent} in the six int64 of d_counts."""
+        _ffi.check(self.lib.pv_polish_vote_runs_dev(
+            self.handle, C.byref(dout.c), int(n_chunks), C.byref(dbatch.c), dbatch.n_reads, dbatch.n_bases, dbatch.n_cigar,
+            dbatch.n_ref_bytes, d_region_start, d_ref_off, d_ref or None, int(n_regions), dout.seq_length, dout.seq_overlap,
+            int(min_run), d_labels, d_acc or None, d_counts, stream or None))
+
+    def polish_vote_runs(self, out, batch, labels: np.ndarray, acc: np.ndarray = None, min_run: int = 3, seq_length: int = 1000,
+                         seq_overlap: int = 50, counts=None):
+        """host-buffer run vote (pv_polish_vote_runs) of a PolishOut and the host batch it was built from, in place on
+        labels uint8 [n,L] and acc float32 [n,L,5] (or None), the planes polish_vote left -> labels, or (labels, acc).
+        counts: optional ctypes int64[6] that receives the six counters, also when the call raises."""
+        n, c, keep = self._host_polish_out(out)
+        assert labels.dtype == np.uint8 and labels.shape == (n, seq_length) and labels.flags.c_contiguous, labels.shape
+        assert acc is None or (acc.dtype == np.float32 and acc.shape == (n, seq_length, 5) and acc.flags.c_contiguous), acc.shape
+        cin = batch.as_c()
+        if counts is None:
+            counts = (C.c_int64 * 6)()
+        _ffi.check(self.lib.pv_polish_vote_runs(self.handle, C.byref(c), n, C.byref(cin), seq_length, int(seq_overlap), int(min_run),
+                                                _ffi.ptr(labels), _ffi.ptr(acc), counts))
+        return labels if acc is None else (labels, acc)
+
     # ---- assess ----------------------------------------------------------------------------------
     def assess_scratch_bytes(self, a_off: np.ndarray, segment: int) -> int:
         """bytes of scratch pv_assess_dev needs for assemblies with these (host) offsets"""

@@ -53,8 +53,11 @@
               more --vote run with --qualities whose vote kernels are bracketed by HIP events, the chunks they saw, and the
               bytes per second the two kernels move by the per-row byte count kept in vote_leg.
 
+  --runs N:   `polish --vote` against `polish --vote --runs --min_run N`: wall times of both forms, twice each, then two more
+              --runs runs under HIP events: the whole calls (image builder, column vote, run vote), and the run vote's kernels.
+
   python tools/bench_polish_e2e.py [--leg stitch|e2e|steps|all] [--mbp 2.0] [--reps 20] [--realign] [--d_ids 0,0] [--gpu_decode]
-                                   [--qualities] [--edits [--evidence]] [--min_depth N] [--min_qual Q] [--min_support K] [-hp] [--vote] [--out f]
+                                   [--qualities] [--edits [--evidence]] [--min_depth N] [--min_qual Q] [--min_support K] [-hp] [--vote] [--runs N] [--out f]
 For the rocprofv3 row run the stitch leg alone under `rocprofv3 --kernel-trace --stats -d <dir> -- python ... --leg stitch`.
 """
 import argparse
@@ -143,7 +146,7 @@ def stitch_leg(reps=20):
 
 
 def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False, qualities=False, edits=False, min_depth=0,
-             min_qual=0, use_hp=False, evidence=False, min_support=0, vote=False):
+             min_qual=0, use_hp=False, evidence=False, min_support=0, vote=False, vote_runs=0):
     # warm-up on a small region (code objects, allocator), then the timed run
     kw = {"gpu_decode": True} if gpu_decode else {}
     if use_hp:
@@ -162,6 +165,8 @@ def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decod
         kw["evidence"] = True
     if vote:
         kw["vote"] = True
+    if vote_runs:
+        kw["vote_runs"] = vote_runs
     polish.polish_fused(bam, fa, model, out + "_warm", region="chr20:0-50000", threads=threads, ctx=ctx, realign=realign, **kw)
     T = {}
     t0 = time.perf_counter()
@@ -184,6 +189,8 @@ def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decod
         res.update(min_support=min_support, unsupported_rows=T["unsupported_rows"], pinned_unsupported_rows=T["pinned_unsupported_rows"])
     if vote:
         res.update(vote=True, voted_rows=T["voted_rows"], no_read_rows=T["no_read_rows"])
+    if vote_runs:
+        res.update(min_run=vote_runs, **{k: T[k] for k in ("runs_seen", "runs_decided", "runs_changed", "runs_skipped")})
     if qualities:
         fq = polish.output_fastq_path(path)
         res["qualities"], res["fastq_bytes"] = True, os.path.getsize(fq)
@@ -667,6 +674,42 @@ def vote_leg(mbp=2.0, threads=16):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def runs_leg(mbp=2.0, threads=16, min_run=3):
+    """polish --vote without and with --runs on one synthetic contig, in one process on the same files, each twice in
+    alternation; then two more --vote --runs runs with qualities under HIP events: one brackets the whole calls (the image
+    builder, the column vote, the run vote), the other the run vote's kernels (the one-block finish is not bracketed)"""
+    from bench_filepath import make_files
+    from pepper_thesis_amd import polish, runtime
+    d = tempfile.mkdtemp(prefix="pv_polish_runs_")
+    try:
+        bam, fa, info = make_files(d, int(mbp * 1_000_000))
+        ctx = runtime.Context(0)
+        try:
+            runs = []
+            for rep in range(2):
+                for v in (0, min_run):
+                    r = _e2e_run(polish, ctx, bam, fa, None, os.path.join(d, "runs" if v else "vote"), threads, False, info,
+                                 vote=True, vote_runs=v)
+                    runs.append(dict(r, runs=bool(v), order=len(runs)))
+            res = {"runs": runs, "without_runs": runs[2], "with_runs": runs[3]}
+            for key, only in (("calls_ms", "polish_"), ("run_vote_kernels_ms", "k_runs")):
+                ctx.profile_begin(only)
+                try:
+                    polish.polish_fused(bam, fa, None, os.path.join(d, "ev_" + key), threads=threads, ctx=ctx, qualities=True,
+                                        vote=True, vote_runs=min_run)
+                finally:
+                    pr = ctx.profile_end()
+                res[key] = {k: [round(v[0], 4), v[1]] for k, v in sorted(pr.items())}
+            b, r = res["calls_ms"].get("polish_pipeline"), res["calls_ms"].get("polish_vote_runs")
+            if b and r and b[0] > 0:
+                res["run_vote_over_builder"] = round(r[0] / b[0], 3)
+            return res
+        finally:
+            ctx.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 def e2e_leg(mbp=2.0, threads=16, realign=False, gpu_decode=False):
     import numpy as np
     from bench_filepath import make_files
@@ -810,6 +853,9 @@ def main():
     ap.add_argument("--vote", action="store_true",
                     help="e2e leg with the seeded model and with polish --vote (no model), plus HIP-event times of the vote kernels "
                          "and the bytes they move per second")
+    ap.add_argument("--runs", type=int, default=0, metavar="MIN_RUN",
+                    help="e2e leg of polish --vote without and with --runs --min_run MIN_RUN, plus HIP-event times of the image "
+                         "builder, the column vote and the run vote, and of the run vote's kernels")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON to this file")
     a = ap.parse_args()
     out = {}
@@ -818,6 +864,8 @@ def main():
     if a.leg in ("e2e", "all"):
         if a.use_hp_info:
             out["e2e"] = hp_leg(a.mbp, a.threads)
+        elif a.runs:
+            out["e2e"] = runs_leg(a.mbp, a.threads, a.runs)
         elif a.vote:
             out["e2e"] = vote_leg(a.mbp, a.threads)
         elif a.min_support:
