@@ -143,13 +143,8 @@ static int edits_launch(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chun
     }
     PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = pv_pick_stream(ctx, stream);
-    StitchArgs a;
-    memset(&a, 0, sizeof(a));
-    a.pos = chunks->position; a.idx = chunks->index; a.region = chunks->region; a.cid = chunks->chunk_id;
-    a.lab = labels; a.rstart = region_start;
-    a.n_chunks = n_chunks; a.n_regions = n_regions;
-    a.L = seq_length; a.step = seq_length - seq_overlap; a.cpt = (seq_length + ST_THREADS - 1) / ST_THREADS;
-    a.region_off = region_edit_off; a.cap = edit_capacity; a.counts = d_counts;
+    StitchArgs a = chunk_args(chunks, labels, region_start, n_chunks, n_regions, seq_length, seq_overlap, d_counts);
+    a.region_off = region_edit_off; a.cap = edit_capacity;
     EditRefs r = {ref_off, ref, row_qual};
     const size_t nk = (size_t)(n_chunks > 0 ? n_chunks : 1);
     int rc;
@@ -206,32 +201,20 @@ static int edits_host(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks
     PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const size_t nc = (size_t)n_chunks, L = (size_t)seq_length;
-    const size_t n_ref = ref_off && ref ? (size_t)ref_off[n_regions] : 0;
     pv_polish_out d;
-    memset(&d, 0, sizeof(d));
-    d.chunk_capacity = n_chunks;
     uint8_t *d_lab = nullptr, *d_rq = nullptr, *d_ref = nullptr;
     int64_t *d_rs = nullptr, *d_ro = nullptr, *d_eoff = nullptr, *d_counts = nullptr;
     pv_polish_edit* d_edits = nullptr;
     int rc;
     if (row_qual && (rc = stage(ctx, "ed.row_qual", row_qual, nc * L, &d_rq, st))) return rc;
-    if ((rc = stage(ctx, "ed.position", (const int64_t*)chunks->position, nc * L, &d.position, st))) return rc;
-    if ((rc = stage(ctx, "ed.index", (const int32_t*)chunks->index, nc * L, &d.index, st))) return rc;
-    if ((rc = stage(ctx, "ed.region", (const int32_t*)chunks->region, nc, &d.region, st))) return rc;
-    if ((rc = stage(ctx, "ed.chunk_id", (const int32_t*)chunks->chunk_id, nc, &d.chunk_id, st))) return rc;
+    if ((rc = stage_chunks(ctx, "ed", chunks, nc, L, want_ev, want_ev, &d, st))) return rc;
     if ((rc = stage(ctx, "ed.labels", labels, nc * L, &d_lab, st))) return rc;
-    if ((rc = stage(ctx, "ed.region_start", region_start, (size_t)n_regions, &d_rs, st))) return rc;
-    if ((rc = stage(ctx, "ed.ref_off", ref_off, ref_off ? (size_t)n_regions + 1 : 0, &d_ro, st))) return rc;
-    if ((rc = stage(ctx, "ed.ref", ref, n_ref, &d_ref, st))) return rc;
+    if ((rc = stage_draft(ctx, "ed", region_start, ref_off, ref, n_regions, &d_rs, &d_ro, &d_ref, st))) return rc;
     if ((rc = pv_get(ctx, "ed.region_edit_off", (size_t)n_regions + 1, &d_eoff))) return rc;
     if ((rc = pv_get(ctx, "ed.edits", (size_t)(edit_capacity > 0 ? edit_capacity : 1), &d_edits))) return rc;
     if ((rc = pv_get(ctx, "ed.counts", (size_t)4, &d_counts))) return rc;
     pv_polish_evidence* d_ev = nullptr;
-    if (want_ev) {
-        if ((rc = stage(ctx, "ed.depth", (const uint16_t*)chunks->depth, nc * L, &d.depth, st))) return rc;
-        if ((rc = stage(ctx, "ed.rowcounts", (const uint16_t*)chunks->counts, nc * L * 10, &d.counts, st))) return rc;
-        if ((rc = pv_get(ctx, "ed.evidence", (size_t)(edit_capacity > 0 ? edit_capacity : 1), &d_ev))) return rc;
-    }
+    if (want_ev && (rc = pv_get(ctx, "ed.evidence", (size_t)(edit_capacity > 0 ? edit_capacity : 1), &d_ev))) return rc;
     rc = edits_launch(ctx, &d, n_chunks, d_lab, row_qual ? d_rq : nullptr, d_rs, d_ro, d_ref, n_regions, seq_length, seq_overlap,
                       d_eoff, d_edits, edit_capacity, d_counts, st, want_ev, d_ev);
     if (rc) return rc;

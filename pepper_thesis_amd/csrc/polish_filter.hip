@@ -330,13 +330,7 @@ int filter_launch(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, co
              PV_ERR_INVALID, "chunk arrays, labels, region starts or draft offsets missing");
     PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = pv_pick_stream(ctx, stream);
-    StitchArgs a;
-    memset(&a, 0, sizeof(a));
-    a.pos = chunks->position; a.idx = chunks->index; a.region = chunks->region; a.cid = chunks->chunk_id;
-    a.lab = labels; a.rstart = region_start;
-    a.n_chunks = n_chunks; a.n_regions = n_regions;
-    a.L = seq_length; a.step = seq_length - seq_overlap; a.cpt = (seq_length + ST_THREADS - 1) / ST_THREADS;
-    a.counts = d_counts;
+    StitchArgs a = chunk_args(chunks, labels, region_start, n_chunks, n_regions, seq_length, seq_overlap, d_counts);
     // the support filter classifies without the quality byte: it judges by the counts row and only copies and zeroes qualities
     EditRefs r = {ref_off, ref, sup ? nullptr : row_qual};
     FilterArgs f = {labels_out, row_qual, row_qual_out, min_value, sup ? chunks->counts : nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -379,25 +373,13 @@ int filter_host(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks, cons
     PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const size_t nc = (size_t)n_chunks, L = (size_t)seq_length;
-    const size_t n_ref = ref_off && ref ? (size_t)ref_off[n_regions] : 0;
     pv_polish_out d;
-    memset(&d, 0, sizeof(d));
-    d.chunk_capacity = n_chunks;
     uint8_t *d_lab = nullptr, *d_rq = nullptr, *d_ref = nullptr, *d_lab_out = nullptr, *d_rq_out = nullptr;
     int64_t *d_rs = nullptr, *d_ro = nullptr, *d_counts = nullptr;
     if (row_qual && (rc = stage(ctx, "fl.row_qual", row_qual, nc * L, &d_rq, st))) return rc;
-    if ((rc = stage(ctx, "fl.position", (const int64_t*)chunks->position, nc * L, &d.position, st))) return rc;
-    if ((rc = stage(ctx, "fl.index", (const int32_t*)chunks->index, nc * L, &d.index, st))) return rc;
-    if ((rc = stage(ctx, "fl.region", (const int32_t*)chunks->region, nc, &d.region, st))) return rc;
-    if ((rc = stage(ctx, "fl.chunk_id", (const int32_t*)chunks->chunk_id, nc, &d.chunk_id, st))) return rc;
+    if ((rc = stage_chunks(ctx, "fl", chunks, nc, L, sup && nc > 0, sup && nc > 0, &d, st))) return rc;   // (no chunks: no planes)
     if ((rc = stage(ctx, "fl.labels", labels, nc * L, &d_lab, st))) return rc;
-    if ((rc = stage(ctx, "fl.region_start", region_start, (size_t)n_regions, &d_rs, st))) return rc;
-    if ((rc = stage(ctx, "fl.ref_off", ref_off, ref_off ? (size_t)n_regions + 1 : 0, &d_ro, st))) return rc;
-    if ((rc = stage(ctx, "fl.ref", ref, n_ref, &d_ref, st))) return rc;
-    if (sup && nc > 0) {
-        if ((rc = stage(ctx, "fl.depth", (const uint16_t*)chunks->depth, nc * L, &d.depth, st))) return rc;
-        if ((rc = stage(ctx, "fl.rowcounts", (const uint16_t*)chunks->counts, nc * L * 10, &d.counts, st))) return rc;
-    }
+    if ((rc = stage_draft(ctx, "fl", region_start, ref_off, ref, n_regions, &d_rs, &d_ro, &d_ref, st))) return rc;
     // in place on the host is in place on the device
     d_lab_out = d_lab;
     if (labels_out != labels && (rc = pv_get(ctx, "fl.labels_out", nc * L > 0 ? nc * L : 1, &d_lab_out))) return rc;

@@ -16,8 +16,6 @@ using namespace pv_chunks;
 
 namespace {
 
-constexpr int MK_FINISH_THREADS = 1024;
-
 // what the mask kernels read and write beside the stitch's arguments (a.lab: labels in)
 struct MaskArgs {
     const uint16_t* depth;
@@ -77,37 +75,6 @@ __global__ __launch_bounds__(ST_THREADS) void k_mask_count(StitchArgs a, MaskArg
     }
 }
 
-// one block: the sums, the status and the first bad chunk -> d_counts
-__global__ __launch_bounds__(MK_FINISH_THREADS) void k_mask_finish(StitchArgs a, MaskArgs m) {
-    __shared__ int64_t lds[MK_FINISH_THREADS / 64];
-    int64_t n = 0, unm = 0, bad = INT64_MAX;
-    for (int64_t k = threadIdx.x; k < a.n_chunks; k += MK_FINISH_THREADS) {
-        n += a.chunk_cnt[k];
-        unm += m.chunk_unm[k];
-        if (a.chunk_bad[k] != BAD_NONE && k < bad) bad = k;
-    }
-    int64_t total, nunm, nbad;
-    block_excl_scan<MK_FINISH_THREADS, int64_t>(n, lds, &total);
-    block_excl_scan<MK_FINISH_THREADS, int64_t>(unm, lds, &nunm);
-    block_excl_scan<MK_FINISH_THREADS, int64_t>(bad != INT64_MAX ? 1 : 0, lds, &nbad);
-    __shared__ int64_t s_bad[MK_FINISH_THREADS / 64];
-    // block minimum of the first bad chunk: wave minimum, then the waves' minima by one thread
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const int64_t y = __shfl_xor(bad, d, 64);
-        bad = y < bad ? y : bad;
-    }
-    if ((threadIdx.x & 63) == 0) s_bad[threadIdx.x >> 6] = bad;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < MK_FINISH_THREADS / 64; i++) bad = s_bad[i] < bad ? s_bad[i] : bad;
-        a.counts[0] = nbad ? 0 : total;
-        a.counts[1] = nbad ? PV_ERR_INVALID : PV_OK;
-        a.counts[2] = nbad ? bad : -1;
-        a.counts[3] = nbad ? 0 : nunm;
-    }
-}
-
 // one block per chunk, under status PV_OK only: the rewrite. In place, rows that keep their label are not stored.
 __global__ __launch_bounds__(ST_THREADS) void k_mask_write(StitchArgs a, MaskArgs m) {
     if (a.counts[1] != PV_OK) return;
@@ -149,13 +116,7 @@ extern "C" int pv_polish_mask_low_depth_dev(pv_ctx* ctx, const pv_polish_out* ch
     PV_CHECK((row_qual != nullptr) == (row_qual_out != nullptr), PV_ERR_INVALID, "mask: row_qual and row_qual_out go together");
     PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = pv_pick_stream(ctx, stream);
-    StitchArgs a;
-    memset(&a, 0, sizeof(a));
-    a.pos = chunks->position; a.idx = chunks->index; a.region = chunks->region; a.cid = chunks->chunk_id;
-    a.lab = labels; a.rstart = region_start;
-    a.n_chunks = n_chunks; a.n_regions = n_regions;
-    a.L = seq_length;
-    a.counts = d_counts;
+    StitchArgs a = chunk_args(chunks, labels, region_start, n_chunks, n_regions, seq_length, 0, d_counts);
     MaskArgs m = {chunks->depth, row_qual, ref_off, ref, labels_out, row_qual_out, min_depth, nullptr};
     const size_t nk = (size_t)(n_chunks > 0 ? n_chunks : 1);
     int rc;
@@ -164,7 +125,7 @@ extern "C" int pv_polish_mask_low_depth_dev(pv_ctx* ctx, const pv_polish_out* ch
     if ((rc = pv_get(ctx, "mask.unm", nk, &m.chunk_unm))) return rc;
     pv_prof_scope ps_all(ctx, "polish_mask", st);
     if (n_chunks > 0) { pv_prof_scope ps(ctx, "k_mask_count", st); k_mask_count<<<(unsigned)n_chunks, ST_THREADS, 0, st>>>(a, m); }
-    k_mask_finish<<<1, MK_FINISH_THREADS, 0, st>>>(a, m);
+    k_chunk_finish<<<1, ST_FINISH_THREADS, 0, st>>>(a, m.chunk_unm);
     if (n_chunks > 0) { pv_prof_scope ps(ctx, "k_mask_write", st); k_mask_write<<<(unsigned)n_chunks, ST_THREADS, 0, st>>>(a, m); }
     PV_HIP(hipGetLastError());
     return PV_OK;
@@ -185,23 +146,14 @@ extern "C" int pv_polish_mask_low_depth(pv_ctx* ctx, const pv_polish_out* chunks
     PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const size_t nc = (size_t)n_chunks, L = (size_t)seq_length;
-    const size_t n_ref = ref_off && ref ? (size_t)ref_off[n_regions] : 0;
     pv_polish_out d;
-    memset(&d, 0, sizeof(d));
-    d.chunk_capacity = n_chunks;
     uint8_t *d_lab = nullptr, *d_rq = nullptr, *d_ref = nullptr, *d_lab_out = nullptr, *d_rq_out = nullptr;
     int64_t *d_rs = nullptr, *d_ro = nullptr, *d_counts = nullptr;
     int rc;
     if (row_qual && (rc = stage(ctx, "mk.row_qual", row_qual, nc * L, &d_rq, st))) return rc;
-    if ((rc = stage(ctx, "mk.position", (const int64_t*)chunks->position, nc * L, &d.position, st))) return rc;
-    if ((rc = stage(ctx, "mk.index", (const int32_t*)chunks->index, nc * L, &d.index, st))) return rc;
-    if ((rc = stage(ctx, "mk.depth", (const uint16_t*)chunks->depth, nc * L, &d.depth, st))) return rc;
-    if ((rc = stage(ctx, "mk.region", (const int32_t*)chunks->region, nc, &d.region, st))) return rc;
-    if ((rc = stage(ctx, "mk.chunk_id", (const int32_t*)chunks->chunk_id, nc, &d.chunk_id, st))) return rc;
+    if ((rc = stage_chunks(ctx, "mk", chunks, nc, L, true, false, &d, st))) return rc;
     if ((rc = stage(ctx, "mk.labels", labels, nc * L, &d_lab, st))) return rc;
-    if ((rc = stage(ctx, "mk.region_start", region_start, (size_t)n_regions, &d_rs, st))) return rc;
-    if ((rc = stage(ctx, "mk.ref_off", ref_off, ref_off ? (size_t)n_regions + 1 : 0, &d_ro, st))) return rc;
-    if ((rc = stage(ctx, "mk.ref", ref, n_ref, &d_ref, st))) return rc;
+    if ((rc = stage_draft(ctx, "mk", region_start, ref_off, ref, n_regions, &d_rs, &d_ro, &d_ref, st))) return rc;
     // in place on the host is in place on the device
     d_lab_out = d_lab;
     if (labels_out != labels && (rc = pv_get(ctx, "mk.labels_out", nc * L > 0 ? nc * L : 1, &d_lab_out))) return rc;

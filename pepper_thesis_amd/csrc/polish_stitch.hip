@@ -117,13 +117,8 @@ static int stitch_dev(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunks
     if (QUAL) PV_CHECK((n_chunks == 0 || row_qual) && (seq_capacity == 0 || qual), PV_ERR_INVALID, "row_qual or qual missing");
     PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = pv_pick_stream(ctx, stream);
-    StitchArgs a;
-    memset(&a, 0, sizeof(a));
-    a.pos = chunks->position; a.idx = chunks->index; a.region = chunks->region; a.cid = chunks->chunk_id;
-    a.lab = labels; a.rstart = region_start;
-    a.n_chunks = n_chunks; a.n_regions = n_regions;
-    a.L = seq_length; a.step = seq_length - seq_overlap; a.cpt = (seq_length + ST_THREADS - 1) / ST_THREADS;
-    a.region_off = region_off; a.seq = seq; a.cap = seq_capacity; a.counts = d_counts;
+    StitchArgs a = chunk_args(chunks, labels, region_start, n_chunks, n_regions, seq_length, seq_overlap, d_counts);
+    a.region_off = region_off; a.seq = seq; a.cap = seq_capacity;
     const size_t nk = (size_t)(n_chunks > 0 ? n_chunks : 1);
     int rc;
     if ((rc = pv_get(ctx, "stitch.cnt", nk, &a.chunk_cnt))) return rc;
@@ -167,8 +162,6 @@ static int stitch_host(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunk
     hipStream_t st = ctx->stream;
     const size_t nc = (size_t)n_chunks, L = (size_t)seq_length;
     pv_polish_out d;
-    memset(&d, 0, sizeof(d));
-    d.chunk_capacity = n_chunks;
     const uint8_t* d_lab = nullptr;
     const int64_t* d_rs = nullptr;
     int64_t *d_roff = nullptr, *d_counts = nullptr;
@@ -179,10 +172,7 @@ static int stitch_host(pv_ctx* ctx, const pv_polish_out* chunks, int64_t n_chunk
         if ((rc = stage(ctx, "st.row_qual", row_qual, nc * L, (uint8_t**)&d_rq, st))) return rc;
         if ((rc = pv_get(ctx, "st.qual", (size_t)(seq_capacity > 0 ? seq_capacity : 1), &d_qual))) return rc;
     }
-    if ((rc = stage(ctx, "st.position", chunks->position, nc * L, &d.position, st))) return rc;
-    if ((rc = stage(ctx, "st.index", chunks->index, nc * L, &d.index, st))) return rc;
-    if ((rc = stage(ctx, "st.region", chunks->region, nc, &d.region, st))) return rc;
-    if ((rc = stage(ctx, "st.chunk_id", chunks->chunk_id, nc, &d.chunk_id, st))) return rc;
+    if ((rc = stage_chunks(ctx, "st", chunks, nc, L, false, false, &d, st))) return rc;
     if ((rc = stage(ctx, "st.labels", labels, nc * L, (uint8_t**)&d_lab, st))) return rc;
     if ((rc = stage(ctx, "st.region_start", region_start, (size_t)n_regions, (int64_t**)&d_rs, st))) return rc;
     if ((rc = pv_get(ctx, "st.region_off", (size_t)n_regions + 1, &d_roff))) return rc;

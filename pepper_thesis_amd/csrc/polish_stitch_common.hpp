@@ -224,6 +224,62 @@ static __global__ __launch_bounds__(ST_SCAN_THREADS) void k_stitch_scan(StitchAr
     }
 }
 
+// what every pass's launcher fills of the kernel arguments: the chunk arrays, the labels (null where the pass reads none), the
+// region starts, the sizes and the counters. The per-chunk arrays and a pass's own outputs are the launcher's to add.
+inline StitchArgs chunk_args(const pv_polish_out* chunks, const uint8_t* labels, const int64_t* region_start, int64_t n_chunks,
+                             int32_t n_regions, int seq_length, int seq_overlap, int64_t* d_counts) {
+    StitchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pos = chunks->position; a.idx = chunks->index; a.region = chunks->region; a.cid = chunks->chunk_id;
+    a.lab = labels; a.rstart = region_start;
+    a.n_chunks = n_chunks; a.n_regions = n_regions;
+    a.L = seq_length; a.step = seq_length - seq_overlap; a.cpt = (seq_length + ST_THREADS - 1) / ST_THREADS;
+    a.counts = d_counts;
+    return a;
+}
+
+// the block's smallest `bad` (INT64_MAX: no thread has one), in thread 0 only: the wave minimum, then the waves' minima by one
+// thread. NT threads; lds holds NT/64 entries of its own.
+template <int NT>
+__device__ inline int64_t block_first_bad(int64_t bad, int64_t* lds) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int64_t y = __shfl_xor(bad, d, 64);
+        bad = y < bad ? y : bad;
+    }
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = bad;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int i = 1; i < NT / 64; i++) bad = lds[i] < bad ? lds[i] : bad;
+    return bad;
+}
+
+constexpr int ST_FINISH_THREADS = 1024;
+
+// one block, for a pass that counts two things per chunk (the mask, the vote): the sums of a.chunk_cnt and chunk_cnt2, the
+// status and the first bad chunk -> d_counts. A bad chunk zeroes both sums.
+static __global__ __launch_bounds__(ST_FINISH_THREADS) void k_chunk_finish(StitchArgs a, const int32_t* chunk_cnt2) {
+    __shared__ int64_t lds[ST_FINISH_THREADS / 64];
+    __shared__ int64_t s_bad[ST_FINISH_THREADS / 64];
+    int64_t n = 0, n2 = 0, bad = INT64_MAX;
+    for (int64_t k = threadIdx.x; k < a.n_chunks; k += ST_FINISH_THREADS) {
+        n += a.chunk_cnt[k];
+        n2 += chunk_cnt2[k];
+        if (a.chunk_bad[k] != BAD_NONE && k < bad) bad = k;
+    }
+    int64_t total, total2, nbad;
+    block_excl_scan<ST_FINISH_THREADS, int64_t>(n, lds, &total);
+    block_excl_scan<ST_FINISH_THREADS, int64_t>(n2, lds, &total2);
+    block_excl_scan<ST_FINISH_THREADS, int64_t>(bad != INT64_MAX ? 1 : 0, lds, &nbad);
+    bad = block_first_bad<ST_FINISH_THREADS>(bad, s_bad);
+    if (threadIdx.x == 0) {
+        a.counts[0] = nbad ? 0 : total;
+        a.counts[1] = nbad ? PV_ERR_INVALID : PV_OK;
+        a.counts[2] = nbad ? bad : -1;
+        a.counts[3] = nbad ? 0 : total2;
+    }
+}
+
 // the host forms' upload of one input array into a named workspace slot
 template <typename T>
 static int stage(pv_ctx* ctx, const char* name, const T* src, size_t n, T** dst, hipStream_t st) {
@@ -231,6 +287,36 @@ static int stage(pv_ctx* ctx, const char* name, const T* src, size_t n, T** dst,
     if (rc) return rc;
     if (n > 0) PV_HIP(hipMemcpyAsync(*dst, src, n * sizeof(T), hipMemcpyHostToDevice, st));
     return PV_OK;
+}
+
+// the host forms' upload of the chunk arrays of nc chunks of L rows into the slots <prefix>.position, .index, .region and
+// .chunk_id and, where the pass reads them, .depth and .rowcounts -> *d, the device's pv_polish_out
+static int stage_chunks(pv_ctx* ctx, const char* prefix, const pv_polish_out* chunks, size_t nc, size_t L, bool want_depth,
+                        bool want_counts, pv_polish_out* d, hipStream_t st) {
+    const std::string p(prefix);
+    memset(d, 0, sizeof(*d));
+    d->chunk_capacity = (int64_t)nc;
+    int rc;
+    if ((rc = stage(ctx, (p + ".position").c_str(), (const int64_t*)chunks->position, nc * L, &d->position, st))) return rc;
+    if ((rc = stage(ctx, (p + ".index").c_str(), (const int32_t*)chunks->index, nc * L, &d->index, st))) return rc;
+    if ((rc = stage(ctx, (p + ".region").c_str(), (const int32_t*)chunks->region, nc, &d->region, st))) return rc;
+    if ((rc = stage(ctx, (p + ".chunk_id").c_str(), (const int32_t*)chunks->chunk_id, nc, &d->chunk_id, st))) return rc;
+    if (want_depth && (rc = stage(ctx, (p + ".depth").c_str(), (const uint16_t*)chunks->depth, nc * L, &d->depth, st))) return rc;
+    if (want_counts && (rc = stage(ctx, (p + ".rowcounts").c_str(), (const uint16_t*)chunks->counts, nc * L * 10, &d->counts, st)))
+        return rc;
+    return PV_OK;
+}
+
+// the host forms' upload of the draft triple into the slots <prefix>.region_start, .ref_off and .ref. ref_off or ref may be
+// null (the device form refuses that where it has chunks): nothing is copied for it.
+static int stage_draft(pv_ctx* ctx, const char* prefix, const int64_t* region_start, const int64_t* ref_off, const uint8_t* ref,
+                       int32_t n_regions, int64_t** d_rs, int64_t** d_ro, uint8_t** d_ref, hipStream_t st) {
+    const std::string p(prefix);
+    const size_t n_ref = ref_off && ref ? (size_t)ref_off[n_regions] : 0;
+    int rc;
+    if ((rc = stage(ctx, (p + ".region_start").c_str(), region_start, (size_t)n_regions, d_rs, st))) return rc;
+    if ((rc = stage(ctx, (p + ".ref_off").c_str(), ref_off, ref_off ? (size_t)n_regions + 1 : 0, d_ro, st))) return rc;
+    return stage(ctx, (p + ".ref").c_str(), ref, n_ref, d_ref, st);
 }
 
 }  // namespace pv_chunks

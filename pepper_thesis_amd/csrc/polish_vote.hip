@@ -17,8 +17,6 @@ using namespace pv_chunks;
 
 namespace {
 
-constexpr int VT_FINISH_THREADS = 1024;
-
 // what the vote kernels read and write beside the stitch's arguments (a.lab is not read: there are no labels yet)
 struct VoteArgs {
     const uint16_t* depth;
@@ -115,37 +113,6 @@ __global__ __launch_bounds__(ST_THREADS) void k_vote_count(StitchArgs a, VoteArg
     }
 }
 
-// one block: the sums, the status and the first bad chunk -> d_counts
-__global__ __launch_bounds__(VT_FINISH_THREADS) void k_vote_finish(StitchArgs a, VoteArgs m) {
-    __shared__ int64_t lds[VT_FINISH_THREADS / 64];
-    __shared__ int64_t s_bad[VT_FINISH_THREADS / 64];
-    int64_t n = 0, nr = 0, bad = INT64_MAX;
-    for (int64_t k = threadIdx.x; k < a.n_chunks; k += VT_FINISH_THREADS) {
-        n += a.chunk_cnt[k];
-        nr += m.chunk_nr[k];
-        if (a.chunk_bad[k] != BAD_NONE && k < bad) bad = k;
-    }
-    int64_t total, n_nr, nbad;
-    block_excl_scan<VT_FINISH_THREADS, int64_t>(n, lds, &total);
-    block_excl_scan<VT_FINISH_THREADS, int64_t>(nr, lds, &n_nr);
-    block_excl_scan<VT_FINISH_THREADS, int64_t>(bad != INT64_MAX ? 1 : 0, lds, &nbad);
-    // block minimum of the first bad chunk: wave minimum, then the waves' minima by one thread
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const int64_t y = __shfl_xor(bad, d, 64);
-        bad = y < bad ? y : bad;
-    }
-    if ((threadIdx.x & 63) == 0) s_bad[threadIdx.x >> 6] = bad;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < VT_FINISH_THREADS / 64; i++) bad = s_bad[i] < bad ? s_bad[i] : bad;
-        a.counts[0] = nbad ? 0 : total;
-        a.counts[1] = nbad ? PV_ERR_INVALID : PV_OK;
-        a.counts[2] = nbad ? bad : -1;
-        a.counts[3] = nbad ? 0 : n_nr;
-    }
-}
-
 // one block per chunk, under status PV_OK only: every row's label, and its five fractions where acc is given
 __global__ __launch_bounds__(ST_THREADS) void k_vote_write(StitchArgs a, VoteArgs m) {
 #pragma clang fp contract(off)
@@ -212,13 +179,7 @@ extern "C" int pv_polish_vote_dev(pv_ctx* ctx, const pv_polish_out* chunks, int6
              PV_ERR_INVALID, "chunk arrays, labels, region starts or draft offsets missing");
     PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = pv_pick_stream(ctx, stream);
-    StitchArgs a;
-    memset(&a, 0, sizeof(a));
-    a.pos = chunks->position; a.idx = chunks->index; a.region = chunks->region; a.cid = chunks->chunk_id;
-    a.rstart = region_start;
-    a.n_chunks = n_chunks; a.n_regions = n_regions;
-    a.L = seq_length;
-    a.counts = d_counts;
+    StitchArgs a = chunk_args(chunks, nullptr, region_start, n_chunks, n_regions, seq_length, seq_overlap, d_counts);
     VoteArgs m = {chunks->depth, chunks->counts, ref_off, ref, labels, acc, seq_overlap, nullptr};
     const size_t nk = (size_t)(n_chunks > 0 ? n_chunks : 1);
     if ((rc = pv_get(ctx, "vote.cnt", nk, &a.chunk_cnt))) return rc;
@@ -226,7 +187,7 @@ extern "C" int pv_polish_vote_dev(pv_ctx* ctx, const pv_polish_out* chunks, int6
     if ((rc = pv_get(ctx, "vote.nr", nk, &m.chunk_nr))) return rc;
     pv_prof_scope ps_all(ctx, "polish_vote", st);
     if (n_chunks > 0) { pv_prof_scope ps(ctx, "k_vote_count", st); k_vote_count<<<(unsigned)n_chunks, ST_THREADS, 0, st>>>(a, m); }
-    k_vote_finish<<<1, VT_FINISH_THREADS, 0, st>>>(a, m);
+    k_chunk_finish<<<1, ST_FINISH_THREADS, 0, st>>>(a, m.chunk_nr);
     if (n_chunks > 0) { pv_prof_scope ps(ctx, "k_vote_write", st); k_vote_write<<<(unsigned)n_chunks, ST_THREADS, 0, st>>>(a, m); }
     PV_HIP(hipGetLastError());
     return PV_OK;
@@ -245,22 +206,12 @@ extern "C" int pv_polish_vote(pv_ctx* ctx, const pv_polish_out* chunks, int64_t 
     PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const size_t nc = (size_t)n_chunks, L = (size_t)seq_length;
-    const size_t n_ref = ref_off && ref ? (size_t)ref_off[n_regions] : 0;
     pv_polish_out d;
-    memset(&d, 0, sizeof(d));
-    d.chunk_capacity = n_chunks;
     uint8_t *d_lab = nullptr, *d_ref = nullptr;
     float* d_acc = nullptr;
     int64_t *d_rs = nullptr, *d_ro = nullptr, *d_counts = nullptr;
-    if ((rc = stage(ctx, "vt.position", (const int64_t*)chunks->position, nc * L, &d.position, st))) return rc;
-    if ((rc = stage(ctx, "vt.index", (const int32_t*)chunks->index, nc * L, &d.index, st))) return rc;
-    if ((rc = stage(ctx, "vt.depth", (const uint16_t*)chunks->depth, nc * L, &d.depth, st))) return rc;
-    if ((rc = stage(ctx, "vt.rowcounts", (const uint16_t*)chunks->counts, nc * L * 10, &d.counts, st))) return rc;
-    if ((rc = stage(ctx, "vt.region", (const int32_t*)chunks->region, nc, &d.region, st))) return rc;
-    if ((rc = stage(ctx, "vt.chunk_id", (const int32_t*)chunks->chunk_id, nc, &d.chunk_id, st))) return rc;
-    if ((rc = stage(ctx, "vt.region_start", region_start, (size_t)n_regions, &d_rs, st))) return rc;
-    if ((rc = stage(ctx, "vt.ref_off", ref_off, ref_off ? (size_t)n_regions + 1 : 0, &d_ro, st))) return rc;
-    if ((rc = stage(ctx, "vt.ref", ref, n_ref, &d_ref, st))) return rc;
+    if ((rc = stage_chunks(ctx, "vt", chunks, nc, L, true, true, &d, st))) return rc;
+    if ((rc = stage_draft(ctx, "vt", region_start, ref_off, ref, n_regions, &d_rs, &d_ro, &d_ref, st))) return rc;
     if ((rc = pv_get(ctx, "vt.labels", nc * L > 0 ? nc * L : 1, &d_lab))) return rc;
     if (acc && (rc = pv_get(ctx, "vt.acc", nc * L > 0 ? nc * L * 5 : 1, &d_acc))) return rc;
     if ((rc = pv_get(ctx, "vt.counts", (size_t)4, &d_counts))) return rc;

@@ -29,7 +29,7 @@ constexpr int VR_MAX_LEN = 63;
 constexpr int VR_SLOTS = 88;             // runs that can start in a tile: each takes its bytes and a byte that is not a candidate's, >= 3
 constexpr int VR_H = VR_MAX_LEN + 3;     // h[0..63], S, V
 constexpr int VR_UNDECIDED = 255;
-constexpr int VR_FINISH_THREADS = 1024;
+constexpr int VR_FINISH_THREADS = 512;   // (its six scans keep their waves' sums in registers: at 1024 threads they spill to scratch)
 
 struct RunArgs {
     pv_batch_in in;            // device pointers
@@ -296,15 +296,8 @@ __global__ __launch_bounds__(VR_FINISH_THREADS) void k_runs_finish(StitchArgs sa
     block_excl_scan<VR_FINISH_THREADS, int64_t>(chg, lds, &n_chg);
     block_excl_scan<VR_FINISH_THREADS, int64_t>(state, lds, &n_state);
     block_excl_scan<VR_FINISH_THREADS, int64_t>(bad != INT64_MAX ? 1 : 0, lds, &nbad);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const int64_t y = __shfl_xor(bad, d, 64);
-        bad = y < bad ? y : bad;
-    }
-    if ((threadIdx.x & 63) == 0) s_bad[threadIdx.x >> 6] = bad;
-    __syncthreads();
+    bad = block_first_bad<VR_FINISH_THREADS>(bad, s_bad);
     if (threadIdx.x == 0) {
-        for (int i = 1; i < VR_FINISH_THREADS / 64; i++) bad = s_bad[i] < bad ? s_bad[i] : bad;
         const int64_t status = nbad ? PV_ERR_INVALID : n_state ? PV_ERR_STATE : PV_OK;
         sa.counts[0] = status == PV_OK ? n_dec : 0;
         sa.counts[1] = status;
@@ -393,14 +386,7 @@ extern "C" int pv_polish_vote_runs_dev(pv_ctx* ctx, const pv_polish_out* chunks,
              PV_ERR_INVALID, "run vote: read arrays missing");
     PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = pv_pick_stream(ctx, stream);
-    StitchArgs a;
-    memset(&a, 0, sizeof(a));
-    a.pos = chunks->position; a.idx = chunks->index; a.region = chunks->region; a.cid = chunks->chunk_id;
-    a.rstart = region_start;
-    a.n_chunks = work ? n_chunks : 0; a.n_regions = n_regions;
-    a.L = seq_length;
-    a.step = seq_length - seq_overlap;
-    a.counts = d_counts;
+    StitchArgs a = chunk_args(chunks, nullptr, region_start, work ? n_chunks : 0, n_regions, seq_length, seq_overlap, d_counts);
     RunArgs m;
     memset(&m, 0, sizeof(m));
     m.in = *in;
@@ -457,15 +443,10 @@ extern "C" int pv_polish_vote_runs(pv_ctx* ctx, const pv_polish_out* chunks, int
     if ((rc = pv_upload_batch(ctx, in, &dev, totals, st))) return rc;
     const size_t nc = (size_t)n_chunks, L = (size_t)seq_length;
     pv_polish_out d;
-    memset(&d, 0, sizeof(d));
-    d.chunk_capacity = n_chunks;
     uint8_t* d_lab = nullptr;
     float* d_acc = nullptr;
     int64_t* d_counts = nullptr;
-    if ((rc = stage(ctx, "vr.position", (const int64_t*)chunks->position, nc * L, &d.position, st))) return rc;
-    if ((rc = stage(ctx, "vr.index", (const int32_t*)chunks->index, nc * L, &d.index, st))) return rc;
-    if ((rc = stage(ctx, "vr.region", (const int32_t*)chunks->region, nc, &d.region, st))) return rc;
-    if ((rc = stage(ctx, "vr.chunk_id", (const int32_t*)chunks->chunk_id, nc, &d.chunk_id, st))) return rc;
+    if ((rc = stage_chunks(ctx, "vr", chunks, nc, L, false, false, &d, st))) return rc;
     if ((rc = stage(ctx, "vr.labels", (const uint8_t*)labels, nc * L, &d_lab, st))) return rc;
     if (acc && (rc = stage(ctx, "vr.acc", (const float*)acc, nc * L * 5, &d_acc, st))) return rc;
     if ((rc = pv_get(ctx, "vr.counts", (size_t)6, &d_counts))) return rc;

@@ -108,6 +108,7 @@ launch of `polish` (torchrun without this parent) is refused.
 """
 import collections
 import concurrent.futures
+import dataclasses
 import itertools
 import os
 import re
@@ -232,29 +233,125 @@ def polish_work(fasta, bam, region: Optional[str]) -> Tuple[List[Work], int]:
     return work, bases_in
 
 
+@dataclasses.dataclass(frozen=True)
+class ChainOptions:
+    """the opt-in stages a chain is made for: the one place that lists them (False / 0: off; the module docstring has each
+    flag's rule). A set no chain is made for is refused here."""
+    qualities: bool = False   # --qualities: the result's qual
+    edits: bool = False       # --edits: the result's edit_off and edits
+    evidence: bool = False    # --evidence (needs edits): the result's evidence
+    min_depth: int = 0        # --min_depth N: the result's masked
+    min_qual: int = 0         # --min_qual Q: the result's filtered
+    min_support: int = 0      # --min_support K: the result's supported
+    use_hp: bool = False      # -hp: run / run_decoded give a HapChainResult
+    vote: bool = False        # --vote: the result's voted; the context needs no weights
+    vote_runs: int = 0        # --vote --runs: min_run >= 2 (needs vote, takes no min_support); the result's runs
+    checked: dataclasses.InitVar[bool] = True   # False: from_args, whose caller refuses a bad set in the command's words first
+
+    def __post_init__(self, checked):
+        for f in dataclasses.fields(self):
+            object.__setattr__(self, f.name, type(f.default)(getattr(self, f.name)))
+        if checked:
+            self.check()
+
+    def check(self) -> None:
+        if self.vote_runs and not self.vote:
+            raise ValueError("a chain with vote_runs needs vote: the run vote rewrites the rows the column vote left")
+        if self.vote_runs and self.min_support:
+            raise ValueError("a chain with vote_runs takes no min_support: that filter's promise is per column")
+        if self.evidence and not self.edits:
+            raise ValueError("a chain with evidence needs edits: the evidence records stand beside the edit records")
+
+    @classmethod
+    def from_args(cls, args) -> "ChainOptions":
+        """the set a `polish` namespace asks for (one not made by cli.polish_parser may lack any flag), not yet checked"""
+        def flag(name, default=False):
+            return getattr(args, name, default) or default
+        return cls(flag("qualities"), flag("edits"), flag("evidence"), flag("min_depth", 0), flag("min_qual", 0),
+                   flag("min_support", 0), flag("use_hp_info"), flag("vote"), flag("min_run", 3) if flag("runs") else 0, checked=False)
+
+    def keywords(self) -> dict:
+        """only the options that are set: what open_chain, a chain's constructor and polish_fused are called with, so that a
+        stub chain keeps its narrow signature"""
+        return {k: v for k, v in dataclasses.asdict(self).items() if v}
+
+    @property
+    def want_counts(self) -> bool:
+        """the builder also hands out the ten raw counts of every chunk row (and then their depth)"""
+        return self.evidence or self.min_support > 0 or self.vote
+
+    @property
+    def want_depth(self) -> bool:
+        return self.min_depth > 0 or self.want_counts
+
+    @property
+    def want_row_qual(self) -> bool:
+        """the row qualities are computed: for the outputs, or (min_qual alone) for the quality filter only"""
+        return self.qualities or self.min_qual > 0
+
+
+class Pass(NamedTuple):
+    """one pass of the chain that leaves counters on the device and counts in the result"""
+    attr: str                   # the ChainResult attribute that carries its counts; with_<attr>() sets it
+    option: str                 # the ChainOptions field that switches it on (> 0)
+    timers: Tuple[str, ...]     # the timer key of every entry of the counts
+    counters: str               # the chain's int64 device tensor: {., status, first bad chunk, ...}
+    n_counters: int
+    pick: Tuple[int, ...]       # where every entry of the counts stands in the counters
+    noun: str                   # "polisher <noun>: device status ..."
+    in_place: Optional[str]     # the context's call, for a pass that rewrites the labels in place before the stitch
+    report: str                 # the command's log line, filled from the options and the timers
+
+    @property
+    def empty(self) -> tuple:
+        """the counts of a launch without chunks"""
+        return (0,) * len(self.timers)
+
+
+# The count-carrying passes, in the order their status is read back (the first bad one is reported); the in-place ones are
+# launched in this order too, behind the votes, which stand in the network's place. Timers, the no-chunk result, the status
+# read-back, the log lines and ChainResult's extra planes all follow from here: a new pass is one row.
+PASSES = (
+    # (rows that kept the draft, rows that could not: draft byte not ACGT)
+    Pass("masked", "min_depth", ("masked_rows", "unmaskable_rows"), "mask_counts", 4, (0, 3), "minimum depth",
+         "polish_mask_low_depth_dev",
+         "MIN DEPTH %(min_depth)d: %(masked_rows)d CHUNK ROWS KEPT THE DRAFT, %(unmaskable_rows)d COULD NOT (DRAFT BYTE NOT ACGT), "
+         "%(draft_regions)d REGIONS WITHOUT READS FILLED FROM THE DRAFT"),
+    # (rows of edits taken back, rows of pinned runs below the threshold: draft byte not ACGT)
+    Pass("filtered", "min_qual", ("reverted_rows", "pinned_rows"), "filter_counts", 4, (0, 3), "minimum quality",
+         "polish_filter_low_qual_dev",
+         "MIN QUAL %(min_qual)d: %(reverted_rows)d CHUNK ROWS OF EDITS TAKEN BACK, %(pinned_rows)d ROWS OF LOW RUNS KEPT (DRAFT BYTE "
+         "NOT ACGT)"),
+    # (rows of edits taken back, rows of pinned runs below the minimum)
+    Pass("supported", "min_support", ("unsupported_rows", "pinned_unsupported_rows"), "support_counts", 4, (0, 3),
+         "minimum support", "polish_filter_low_support_dev",
+         "MIN SUPPORT %(min_support)d: %(unsupported_rows)d CHUNK ROWS OF EDITS TAKEN BACK, %(pinned_unsupported_rows)d ROWS OF WEAK "
+         "RUNS KEPT (DRAFT BYTE NOT ACGT)"),
+    # (rows whose winner is not what the draft holds, base rows without reads)
+    Pass("voted", "vote", ("voted_rows", "no_read_rows"), "vote_counts", 4, (0, 3), "vote", None,
+         "VOTE: %(voted_rows)d CHUNK ROWS WHERE THE READS' MAJORITY IS NOT THE DRAFT, %(no_read_rows)d BASE ROWS WITHOUT READS (THE "
+         "DRAFT IS KEPT, OR DROPPED WHERE ITS BYTE IS NOT ACGT)"),
+    # (candidate runs seen, runs decided, decided runs whose length changes, candidates skipped as adjacent)
+    Pass("runs", "vote_runs", ("runs_seen", "runs_decided", "runs_changed", "runs_skipped"), "runs_counts", 6, (4, 0, 3, 5),
+         "run vote", None,
+         "RUNS (MIN RUN %(vote_runs)d): %(runs_seen)d CANDIDATE RUNS SEEN, %(runs_decided)d DECIDED BY THEIR READS, %(runs_changed)d "
+         "OF THEM WITH A LENGTH THAT IS NOT THE DRAFT'S, %(runs_skipped)d SKIPPED AS ADJACENT"),
+)
+PASS_TIMERS = tuple(k for p in PASSES for k in p.timers)
+# what a ChainResult may carry beside its five planes: every pass's counts, and --evidence's polish_edits.EVIDENCE_DTYPE
+# records, evidence[i] beside edits[i]
+RESULT_EXTRAS = tuple(p.attr for p in PASSES) + ("evidence",)
+
+
 class ChainResult(NamedTuple):
-    """what a chain's run / run_decoded give for one batch of regions. A plane the chain was not made for is None."""
+    """what a chain's run / run_decoded give for one batch of regions. A plane the chain was not made for is None. The
+    RESULT_EXTRAS are attributes (None here), not tuple fields, so the record keeps its five planes for everything that
+    unpacks it; with_masked() and its kin give a result that carries one."""
     region_off: np.ndarray                 # int64 [n_regions+1] into bases and qual
     bases: object                          # anything sliceable by region_off: polished bases, or make_images' chunk list
     qual: Optional[bytes] = None           # --qualities: one raw Phred byte per base
     edit_off: Optional[np.ndarray] = None  # --edits: int64 [n_regions+1] into edits
     edits: Optional[np.ndarray] = None     # --edits: polish_edits.EDIT_DTYPE records
-    # --min_depth: (chunk rows that kept the draft, rows that could not: draft byte not ACGT). Not a tuple field, so the
-    # record keeps its five planes for everything that unpacks it; with_masked() gives a result that carries the counts
-    masked = None
-    # --min_qual: (chunk rows of edits taken back, rows of pinned runs below the threshold: draft byte not ACGT), carried the
-    # same way; with_filtered()
-    filtered = None
-    # --min_support: (chunk rows of edits taken back, rows of pinned runs below the minimum), carried the same way;
-    # with_supported()
-    supported = None
-    # --evidence: polish_edits.EVIDENCE_DTYPE records, evidence[i] beside edits[i], carried the same way; with_evidence()
-    evidence = None
-    # --vote: (chunk rows whose winner is not what the draft holds, base rows without reads), carried the same way; with_voted()
-    voted = None
-    # --vote --runs: (candidate runs seen, runs decided, decided runs whose length changes, candidates skipped as adjacent),
-    # carried the same way; with_runs()
-    runs = None
 
     def region(self, g: int) -> tuple:
         """region g's share: (bases, qual or None, edits or None), and behind them its evidence records where the result
@@ -263,6 +360,10 @@ class ChainResult(NamedTuple):
         share = (self.bases[a:b], None if self.qual is None else self.qual[a:b],
                  None if self.edits is None else self.edits[self.edit_off[g]:self.edit_off[g + 1]])
         return share if self.evidence is None else share + (self.evidence[self.edit_off[g]:self.edit_off[g + 1]],)
+
+
+for _name in RESULT_EXTRAS:
+    setattr(ChainResult, _name, None)
 
 
 class HapChainResult(NamedTuple):
@@ -283,56 +384,46 @@ def hp_path(path: str, haplotype: int) -> str:
 
 
 class _MaskedChainResult(ChainResult):
-    """a ChainResult with the instance attributes `masked`, `filtered`, `supported`, `evidence`, `voted` and `runs`"""
+    """a ChainResult with the RESULT_EXTRAS as instance attributes"""
+
+
+def _with(res: ChainResult, name: str, value) -> ChainResult:
+    """res, carrying `value` in its attribute `name` and every other extra it carried"""
+    out = _MaskedChainResult(*res)
+    for k in RESULT_EXTRAS:
+        setattr(out, k, value if k == name else getattr(res, k))
+    return out
 
 
 def with_masked(res: ChainResult, masked: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a minimum-depth chain in its attribute `masked`"""
-    out = _MaskedChainResult(*res)
-    out.masked, out.filtered, out.evidence = (int(masked[0]), int(masked[1])), res.filtered, res.evidence
-    out.supported, out.voted, out.runs = res.supported, res.voted, res.runs
-    return out
+    return _with(res, "masked", (int(masked[0]), int(masked[1])))
 
 
 def with_filtered(res: ChainResult, filtered: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a minimum-quality chain in its attribute `filtered`"""
-    out = _MaskedChainResult(*res)
-    out.masked, out.filtered, out.evidence = res.masked, (int(filtered[0]), int(filtered[1])), res.evidence
-    out.supported, out.voted, out.runs = res.supported, res.voted, res.runs
-    return out
+    return _with(res, "filtered", (int(filtered[0]), int(filtered[1])))
 
 
 def with_supported(res: ChainResult, supported: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a minimum-support chain in its attribute `supported`"""
-    out = _MaskedChainResult(*res)
-    out.masked, out.filtered, out.evidence = res.masked, res.filtered, res.evidence
-    out.supported, out.voted, out.runs = (int(supported[0]), int(supported[1])), res.voted, res.runs
-    return out
+    return _with(res, "supported", (int(supported[0]), int(supported[1])))
 
 
 def with_voted(res: ChainResult, voted: Tuple[int, int]) -> ChainResult:
     """res, carrying the counts of a vote chain in its attribute `voted`"""
-    out = _MaskedChainResult(*res)
-    out.masked, out.filtered, out.evidence, out.supported = res.masked, res.filtered, res.evidence, res.supported
-    out.voted, out.runs = (int(voted[0]), int(voted[1])), res.runs
-    return out
+    return _with(res, "voted", (int(voted[0]), int(voted[1])))
 
 
 def with_runs(res: ChainResult, runs: Tuple[int, int, int, int]) -> ChainResult:
     """res, carrying the counts of a run-vote chain in its attribute `runs`"""
-    out = _MaskedChainResult(*res)
-    out.masked, out.filtered, out.evidence, out.supported = res.masked, res.filtered, res.evidence, res.supported
-    out.voted, out.runs = res.voted, tuple(int(v) for v in runs)
-    return out
+    return _with(res, "runs", tuple(int(v) for v in runs))
 
 
 def with_evidence(res: ChainResult, evidence: np.ndarray) -> ChainResult:
     """res, carrying the evidence records of an evidence chain (one per edit record) in its attribute `evidence`"""
     assert res.edits is not None and len(evidence) == len(res.edits), (len(evidence), res.edits is None)
-    out = _MaskedChainResult(*res)
-    out.masked, out.filtered, out.evidence = res.masked, res.filtered, evidence
-    out.supported, out.voted, out.runs = res.supported, res.voted, res.runs
-    return out
+    return _with(res, "evidence", evidence)
 
 
 class Piece(NamedTuple):
@@ -415,33 +506,15 @@ class _DeviceChain:
     batch the builder was given (realigned under --realign, one haplotype's under -hp) and rewrites the rows of every
     homopolymer run whose length the reads decide (the result's runs)."""
 
-    def __init__(self, ctx, own_ctx: bool = False, qualities: bool = False, edits: bool = False, min_depth: int = 0,
-                 min_qual: int = 0, use_hp: bool = False, evidence: bool = False, min_support: int = 0, vote: bool = False,
-                 vote_runs: int = 0):
+    def __init__(self, ctx, own_ctx: bool = False, **options):
+        self.options = ChainOptions(**options)   # (refuses a bad set before the context is touched)
+        for k, v in dataclasses.asdict(self.options).items():   # the chain's public attributes: qualities, edits, ...
+            setattr(self, k, v)
         import torch
-        self.vote = bool(vote)
-        self.vote_runs = int(vote_runs)
-        if self.vote_runs and not self.vote:
-            raise ValueError("a chain with vote_runs needs vote: the run vote rewrites the rows the column vote left")
-        if self.vote_runs and min_support:
-            raise ValueError("a chain with vote_runs takes no min_support: that filter's promise is per column")
-        if evidence and not edits:
-            raise ValueError("a chain with evidence needs edits: the evidence records stand beside the edit records")
-        self.evidence = bool(evidence)
-        self.ev_buf = None
-        self.use_hp = bool(use_hp)
-        self.sel = None
-        self.ctx, self.dev, self.own_ctx, self.qualities = ctx, "cuda:%d" % ctx.device_id, own_ctx, bool(qualities)
-        self.edits = bool(edits)
-        self.min_depth = int(min_depth)
-        self.mask_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
-        self.min_qual = int(min_qual)
-        self.filter_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
-        self.min_support = int(min_support)
-        self.support_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
-        self.vote_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
-        self.runs_counts = torch.zeros(6, dtype=torch.int64, device=self.dev)
-        self.edit_buf = None
+        self.ctx, self.dev, self.own_ctx = ctx, "cuda:%d" % ctx.device_id, own_ctx
+        for p in PASSES:
+            setattr(self, p.counters, torch.zeros(p.n_counters, dtype=torch.int64, device=self.dev))
+        self.edit_buf = self.ev_buf = self.sel = None
         self.edit_counts = torch.zeros(4, dtype=torch.int64, device=self.dev)
         self.dout = self.labels = self.seq = None
         self.acc = self.row_qual = self.qual = None
@@ -456,11 +529,10 @@ class _DeviceChain:
         import torch
         from .device import DevicePolishOut
         if self.dout is None or self.dout.capacity < chunks:
-            want_counts = self.evidence or self.min_support > 0 or self.vote
-            self.dout = DevicePolishOut(chunks, device=self.dev, depth=self.min_depth > 0 or want_counts, counts=want_counts)
+            self.dout = DevicePolishOut(chunks, device=self.dev, depth=self.options.want_depth, counts=self.options.want_counts)
             self.labels = torch.zeros((chunks, 1000), dtype=torch.uint8, device=self.dev)
             self.seq = torch.zeros(chunks * 1000, dtype=torch.uint8, device=self.dev)
-            if self.qualities or self.min_qual > 0:
+            if self.options.want_row_qual:
                 self.acc = torch.zeros((chunks, 1000, 5), dtype=torch.float32, device=self.dev)
                 self.row_qual = torch.zeros((chunks, 1000), dtype=torch.uint8, device=self.dev)
             if self.qualities:
@@ -491,9 +563,9 @@ class _DeviceChain:
                 return n
             want = n
         import torch
-        want_counts = self.evidence or self.min_support > 0 or self.vote
-        want_depth = self.min_depth > 0 or want_counts
-        out = polish_summarize(self.ctx, host_batch(), want_depth=want_depth, **({"want_counts": True} if want_counts else {}))
+        want_depth, want_counts = self.options.want_depth, self.options.want_counts
+        planes = dict(want_depth=want_depth, want_counts=True) if want_counts else dict(want_depth=want_depth)
+        out = polish_summarize(self.ctx, host_batch(), **planes)
         n = len(out.chunk_id)
         self._ensure(n)
         for name in ("images", "position", "index", "region", "chunk_id"):
@@ -648,33 +720,33 @@ class _DeviceChain:
         return HapChainResult(tuple(results), tuple(has_reads), tags, payload)
 
     def _labels_and_stitch(self, db, n: int, n_regions: int) -> ChainResult:
-        """P2 (a vote chain: the majority vote) [-> row qualities] [-> minimum-depth mask] [-> minimum-quality filter] [-> minimum-support filter] -> stitch
-        [-> edits] over the first n
-        chunks of self.dout on the context's stream, one synchronize, then the read-back"""
-        import torch
+        """P2 (a vote chain: the majority vote [-> the run vote]) [-> row qualities] [-> minimum-depth mask] [-> minimum-quality
+        filter] [-> minimum-support filter] -> stitch [-> edits] over the first n chunks of self.dout on the context's stream,
+        one synchronize, then the read-back"""
         from .polish_edits import EDIT_DTYPE, EVIDENCE_DTYPE
+        o = self.options
+        on = [p for p in PASSES if getattr(o, p.option) > 0]
         if n == 0:   # nothing to launch: every plane this chain was made for, empty
             zero = np.zeros(n_regions + 1, np.int64)
-            res = ChainResult(zero, b"", b"" if self.qualities else None)
-            res = res._replace(edit_off=zero.copy(), edits=np.zeros(0, EDIT_DTYPE)) if self.edits else res
-            res = with_evidence(res, np.zeros(0, EVIDENCE_DTYPE)) if self.evidence else res
-            res = with_masked(res, (0, 0)) if self.min_depth > 0 else res
-            res = with_filtered(res, (0, 0)) if self.min_qual > 0 else res
-            res = with_voted(res, (0, 0)) if self.vote else res
-            res = with_runs(res, (0, 0, 0, 0)) if self.vote_runs else res
-            return with_supported(res, (0, 0)) if self.min_support > 0 else res
-        d_acc, d_row_qual, d_qual = (t.data_ptr() for t in (self.acc, self.row_qual, self.qual)) if self.qualities else (0, 0, 0)
-        # --min_qual without --qualities: the row qualities are made for the filter alone; mask, stitch and edits run as without
-        d_filter_acc, d_filter_qual = (d_acc, d_row_qual) if self.qualities or self.min_qual <= 0 else (self.acc.data_ptr(),
-                                                                                                       self.row_qual.data_ptr())
-        d_labels, d_ref_start = self.labels.data_ptr(), db.t["ref_start"].data_ptr()
+            res = ChainResult(zero, b"", b"" if o.qualities else None)
+            res = res._replace(edit_off=zero.copy(), edits=np.zeros(0, EDIT_DTYPE)) if o.edits else res
+            res = with_evidence(res, np.zeros(0, EVIDENCE_DTYPE)) if o.evidence else res
+            for p in on:
+                res = _with(res, p.attr, p.empty)
+            return res
+        import torch
+        # --min_qual without --qualities computes the row qualities for the filter alone: the mask, the support filter, the
+        # stitch and the edits get 0 and run as in a chain without qualities
+        d_filter_acc, d_filter_qual = (self.acc.data_ptr(), self.row_qual.data_ptr()) if o.want_row_qual else (0, 0)
+        d_row_qual, d_qual = (d_filter_qual, self.qual.data_ptr()) if o.qualities else (0, 0)
+        d_labels = self.labels.data_ptr()
+        draft = (db.t["ref_start"].data_ptr(), db.t["ref_off"].data_ptr(), db.t["ref"].data_ptr(), n_regions)
         roff = torch.empty(n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
-        if self.vote:   # the reads' majority in the network's place: the same two planes, from the counts of this batch
-            self.ctx.polish_vote_dev(self.dout, n, d_ref_start, db.t["ref_off"].data_ptr(), db.t["ref"].data_ptr(), n_regions,
-                                     d_labels, d_filter_acc, self.vote_counts.data_ptr())
-            if self.vote_runs:   # and every homopolymer run's length read by read, in place, from the reads the builder had
-                self.ctx.polish_vote_runs_dev(self.dout, n, db, d_ref_start, db.t["ref_off"].data_ptr(), db.t["ref"].data_ptr(),
-                                              n_regions, self.vote_runs, d_labels, d_filter_acc, self.runs_counts.data_ptr())
+        if o.vote:   # the reads' majority in the network's place: the same two planes, from the counts of this batch
+            self.ctx.polish_vote_dev(self.dout, n, *draft, d_labels, d_filter_acc, self.vote_counts.data_ptr())
+            if o.vote_runs:   # and every homopolymer run's length read by read, in place, from the reads the builder had
+                self.ctx.polish_vote_runs_dev(self.dout, n, db, *draft, o.vote_runs, d_labels, d_filter_acc,
+                                              self.runs_counts.data_ptr())
         else:
             self.ctx.forward_p2_dev(self.dout.images.data_ptr(), n, d_labels, d_filter_acc)
         if d_filter_qual:
@@ -682,114 +754,70 @@ class _DeviceChain:
             # the row kernel are overwritten)
             self.ctx.polish_row_qual_dev(d_labels, d_filter_acc, n, d_filter_qual, self.counts.data_ptr(), self.dout.seq_length,
                                          self.dout.seq_overlap)
-        if self.min_depth > 0:   # in place: what follows sees the draft's labels wherever the depth is below the minimum
-            self.ctx.polish_mask_low_depth_dev(self.dout, n, d_labels, d_row_qual, d_ref_start, db.t["ref_off"].data_ptr(),
-                                               db.t["ref"].data_ptr(), n_regions, self.min_depth, d_labels, d_row_qual,
-                                               self.mask_counts.data_ptr())
-        if self.min_qual > 0:    # in place too: what follows sees the draft's labels over every run of edits below the minimum
-            self.ctx.polish_filter_low_qual_dev(self.dout, n, d_labels, d_filter_qual, d_ref_start, db.t["ref_off"].data_ptr(),
-                                                db.t["ref"].data_ptr(), n_regions, self.min_qual, d_labels, d_filter_qual,
-                                                self.filter_counts.data_ptr())
-        if self.min_support > 0:   # and the runs that too few reads spell, by the counts of this batch's own reads; the row
-            # qualities it zeroes are those the stitch and the edits read (none without --qualities)
-            self.ctx.polish_filter_low_support_dev(self.dout, n, d_labels, d_row_qual, d_ref_start, db.t["ref_off"].data_ptr(),
-                                                   db.t["ref"].data_ptr(), n_regions, self.min_support, d_labels, d_row_qual,
-                                                   self.support_counts.data_ptr())
-        self.ctx.polish_stitch_dev(self.dout, n, d_labels, d_ref_start, n_regions, roff.data_ptr(), self.seq.data_ptr(),
+        for p in on:
+            if p.in_place:   # what follows sees the draft's labels wherever the pass took the network's back; the row qualities
+                # it zeroes are those the stitch and the edits read (the quality filter: its own, see above)
+                d_q = d_filter_qual if p.option == "min_qual" else d_row_qual
+                getattr(self.ctx, p.in_place)(self.dout, n, d_labels, d_q, *draft, getattr(o, p.option), d_labels, d_q,
+                                              getattr(self, p.counters).data_ptr())
+        self.ctx.polish_stitch_dev(self.dout, n, d_labels, draft[0], n_regions, roff.data_ptr(), self.seq.data_ptr(),
                                    self.seq.numel(), self.counts.data_ptr(), d_row_qual=d_row_qual, d_qual=d_qual)
-        if self.edits:
+        if o.edits:
             eoff = torch.empty(n_regions + 1, dtype=torch.int64, device=self.dev)   # every entry is written
-            if self.evidence:   # the edits call's twin: the same records, and each one's read support beside it
-                self.ctx.polish_edits_evidence_dev(self.dout, n, d_labels, d_row_qual, d_ref_start, db.t["ref_off"].data_ptr(),
-                                                   db.t["ref"].data_ptr(), n_regions, eoff.data_ptr(), self.edit_buf.data_ptr(),
-                                                   self.ev_buf.data_ptr(), self.edit_buf.shape[0], self.edit_counts.data_ptr())
+            if o.evidence:   # the edits call's twin: the same records, and each one's read support beside it
+                self.ctx.polish_edits_evidence_dev(self.dout, n, d_labels, d_row_qual, *draft, eoff.data_ptr(),
+                                                   self.edit_buf.data_ptr(), self.ev_buf.data_ptr(), self.edit_buf.shape[0],
+                                                   self.edit_counts.data_ptr())
             else:
-                self.ctx.polish_edits_dev(self.dout, n, d_labels, d_row_qual, d_ref_start, db.t["ref_off"].data_ptr(),
-                                          db.t["ref"].data_ptr(), n_regions, eoff.data_ptr(), self.edit_buf.data_ptr(),
+                self.ctx.polish_edits_dev(self.dout, n, d_labels, d_row_qual, *draft, eoff.data_ptr(), self.edit_buf.data_ptr(),
                                           self.edit_buf.shape[0], self.edit_counts.data_ptr())
         self.ctx.synchronize()   # raises if a split GRU form timed out (its labels are then poisoned)
-        masked = None
-        if self.min_depth > 0:
-            n_masked, status, bad, n_unmaskable = (int(v) for v in self.mask_counts.tolist())
-            if status != _ffi.PV_OK:
-                raise _ffi.PepperHipError(status, "polisher minimum depth: device status %d (chunk %d)" % (status, bad))
-            masked = (n_masked, n_unmaskable)
-        filtered = None
-        if self.min_qual > 0:
-            n_reverted, status, bad, n_pinned = (int(v) for v in self.filter_counts.tolist())
-            if status != _ffi.PV_OK:
-                raise _ffi.PepperHipError(status, "polisher minimum quality: device status %d (chunk %d)" % (status, bad))
-            filtered = (n_reverted, n_pinned)
-        supported = None
-        if self.min_support > 0:
-            n_reverted, status, bad, n_pinned = (int(v) for v in self.support_counts.tolist())
-            if status != _ffi.PV_OK:
-                raise _ffi.PepperHipError(status, "polisher minimum support: device status %d (chunk %d)" % (status, bad))
-            supported = (n_reverted, n_pinned)
-
-        voted = None
-        if self.vote:
-            n_changed, status, bad, n_no_reads = (int(v) for v in self.vote_counts.tolist())
-            if status != _ffi.PV_OK:
-                raise _ffi.PepperHipError(status, "polisher vote: device status %d (chunk %d)" % (status, bad))
-            voted = (n_changed, n_no_reads)
-        runs = None
-        if self.vote_runs:
-            n_decided, status, bad, n_run_changed, n_seen, n_skipped = (int(v) for v in self.runs_counts.tolist())
-            if status != _ffi.PV_OK:
-                raise _ffi.PepperHipError(status, "polisher run vote: device status %d (chunk %d)" % (status, bad))
-            runs = (n_seen, n_decided, n_run_changed, n_skipped)
-
-        def counted(res):
-            res = res if voted is None else with_voted(res, voted)
-            res = res if runs is None else with_runs(res, runs)
-            res = res if masked is None else with_masked(res, masked)
-            res = res if filtered is None else with_filtered(res, filtered)
-            return res if supported is None else with_supported(res, supported)
+        extras = {}
+        for p in on:
+            c = [int(v) for v in getattr(self, p.counters).tolist()]
+            if c[1] != _ffi.PV_OK:
+                raise _ffi.PepperHipError(c[1], "polisher %s: device status %d (chunk %d)" % (p.noun, c[1], c[2]))
+            extras[p.attr] = tuple(c[i] for i in p.pick)
         total, status, bad = (int(v) for v in self.counts[:3].tolist())
         if status != _ffi.PV_OK:   # capacity cannot run short: seq holds a byte for every column
             raise _ffi.PepperHipError(status, "polisher stitch: device status %d (chunk %d)" % (status, bad))
         res = ChainResult(roff.cpu().numpy(), self.seq[:total].cpu().numpy().tobytes(),
-                          self.qual[:total].cpu().numpy().tobytes() if self.qualities else None)
-        if not self.edits:
-            return counted(res)
-        total, status, bad = (int(v) for v in self.edit_counts[:3].tolist())
-        if status != _ffi.PV_OK:   # capacity cannot run short: a record for every chunk row
-            raise _ffi.PepperHipError(status, "polisher edits: device status %d (chunk %d)" % (status, bad))
-        res = res._replace(edit_off=eoff.cpu().numpy(), edits=self.edit_buf[:total].cpu().numpy().view(EDIT_DTYPE).reshape(-1))
-        if self.evidence:
-            res = with_evidence(res, self.ev_buf[:total].cpu().numpy().view(EVIDENCE_DTYPE).reshape(-1))
-        return counted(res)
+                          self.qual[:total].cpu().numpy().tobytes() if o.qualities else None)
+        if o.edits:
+            total, status, bad = (int(v) for v in self.edit_counts[:3].tolist())
+            if status != _ffi.PV_OK:   # capacity cannot run short: a record for every chunk row
+                raise _ffi.PepperHipError(status, "polisher edits: device status %d (chunk %d)" % (status, bad))
+            res = res._replace(edit_off=eoff.cpu().numpy(), edits=self.edit_buf[:total].cpu().numpy().view(EDIT_DTYPE).reshape(-1))
+            if o.evidence:
+                res = with_evidence(res, self.ev_buf[:total].cpu().numpy().view(EVIDENCE_DTYPE).reshape(-1))
+        for attr, counts in extras.items():
+            res = _with(res, attr, counts)
+        return res
 
 
-def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int, qualities: bool = False,
-                      edits: bool = False, min_depth: int = 0, min_qual: int = 0, use_hp: bool = False,
-                      evidence: bool = False, min_support: int = 0, vote: bool = False, vote_runs: int = 0) -> _DeviceChain:
+
+
+def open_device_chain(device: int, shared_device: bool, state_dict: dict, dtype: int, **options) -> _DeviceChain:
     """a context on `device` with the polisher weights loaded, and the chain on it (closing the chain closes the context).
     shared_device: other ranks use this GPU too, so the option is set before the first device call (the split GRU forms need
     co-resident workgroups and would time out, poisoning the labels). False leaves the create-time default (PV_SHARED_DEVICE).
     This is the default `open_chain` of run and polish_rank.run; CPU tests pass a stub with the same signature, whose result
-    has run(batch, windows) -> ChainResult and close(). qualities, edits, min_depth, min_qual (each passed only when set):
-    the chain of --qualities / --edits / --min_depth / --min_qual, whose results carry those planes and counts. use_hp
-    (passed only when set): the chain of -hp, whose run gives a HapChainResult. evidence (passed only when set): the chain of
-    --evidence, whose results carry an evidence record per edit record. min_support (passed only when set): the chain of
-    --min_support, whose results carry its counts. vote (passed only when set): the chain of --vote, whose results carry its
-    counts; no weights are loaded and state_dict may be None. vote_runs (passed only when set): the chain of --vote --runs
-    with that min_run, whose results carry the run counts."""
+    has run(batch, windows) -> ChainResult and close(). options: the ChainOptions the chain is made for, each passed only
+    when set (ChainOptions.keywords); its results carry the planes and counts of those. With vote no weights are loaded and
+    state_dict may be None."""
     from .runtime import Context
     ctx = Context(device)
     try:
         if shared_device:
             ctx.set_option("shared_device", 1)
-        if not vote:
+        if not options.get("vote"):
             ctx.load_p2(state_dict, dtype)
-        return _DeviceChain(ctx, own_ctx=True, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual,
-                            use_hp=use_hp, **({"evidence": True} if evidence else {}),
-                            **({"min_support": min_support} if min_support else {}), **({"vote": True} if vote else {}),
-                            **({"vote_runs": vote_runs} if vote_runs else {}))
+        return _DeviceChain(ctx, own_ctx=True, **options)
     except BaseException:
         ctx.close()
         raise
+
+
 
 
 class _RealignedDeviceBatch:
@@ -816,11 +844,11 @@ def _read_ahead(ex, fn, items, depth):
 def _timers(timers: Optional[dict], more=()) -> dict:
     """the caller's timer dict (or a fresh one) with the keys of polish_pieces, and `more`, present"""
     T = timers if timers is not None else {}
-    for k in ("read_s", "device_s", "regions", "batches", "masked_rows", "unmaskable_rows", "reverted_rows", "pinned_rows",
-              "unsupported_rows", "pinned_unsupported_rows", "voted_rows", "no_read_rows", "runs_seen", "runs_decided",
-              "runs_changed", "runs_skipped") + tuple(more):
+    for k in ("read_s", "device_s", "regions", "batches") + PASS_TIMERS + tuple(more):
         T.setdefault(k, 0)
     return T
+
+
 
 
 def _thread_handles(bam: str, fasta: str):
@@ -837,22 +865,12 @@ def _thread_handles(bam: str, fasta: str):
 
 
 def _count_masked(T: dict, res) -> None:
-    """a minimum-depth, a minimum-quality, a minimum-support and a vote chain's row counts of one launch into the timers"""
-    if getattr(res, "masked", None) is not None:
-        T["masked_rows"] += res.masked[0]
-        T["unmaskable_rows"] += res.masked[1]
-    if getattr(res, "filtered", None) is not None:
-        T["reverted_rows"] += res.filtered[0]
-        T["pinned_rows"] += res.filtered[1]
-    if getattr(res, "supported", None) is not None:
-        T["unsupported_rows"] += res.supported[0]
-        T["pinned_unsupported_rows"] += res.supported[1]
-    if getattr(res, "voted", None) is not None:
-        T["voted_rows"] += res.voted[0]
-        T["no_read_rows"] += res.voted[1]
-    if getattr(res, "runs", None) is not None:
-        for k, v in zip(("runs_seen", "runs_decided", "runs_changed", "runs_skipped"), res.runs):
+    """the counts a result carries of every pass of PASSES (one launch's) into the timers"""
+    for p in PASSES:
+        for k, v in zip(p.timers, getattr(res, p.attr, None) or ()):
             T[k] += v
+
+
 
 
 def kept_range(w: Work) -> Tuple[int, int]:
@@ -1009,105 +1027,93 @@ def decode_report(T: dict) -> str:
                T.get("gpu_decode_slot_retries", 0), T.get("chain_runs", 0), T["batches"]))
 
 
+# What polish_fused asks of a chain passed in, in the order it asks: (option = the chain's attribute, the value of a chain
+# without the attribute, refused when (run's value, chain's value), what the chain does: %r the chain's value, %d the run's)
+_MADE_FOR = (
+    ("min_depth", None, lambda want, have: want >= 1 and have != want, "masks below depth %r, not %d"),
+    ("min_qual", None, lambda want, have: want >= 1 and have != want, "filters below quality %r, not %d"),
+    ("min_support", None, lambda want, have: want >= 1 and have != want, "filters below support %r, not %d"),
+    ("vote", False, lambda want, have: want and not have, "does not vote"),
+    ("vote", False, lambda want, have: have and not want, "votes in the network's place"),
+    ("vote_runs", 0, lambda want, have: want != int(have or 0), "votes runs from length %r, not %d"),
+    ("use_hp", False, lambda want, have: want and not have, "does not select reads by haplotype"),
+)
+_NOT_MADE = "polish_fused: the chain%s: it was not made for this run"
+
+
 def polish_fused(bam: str, fasta: str, model_path: str, out_prefix: str, region: Optional[str] = None, batch_size: int = 2048,
                  threads: int = 5, dtype: int = _ffi.PV_DTYPE_F32, ctx=None, timers: Optional[dict] = None,
-                 realign: bool = False, chain=None, gpu_decode: bool = False, qualities: bool = False, edits: bool = False,
-                 min_depth: int = 0, min_qual: int = 0, use_hp: bool = False, evidence: bool = False,
-                 min_support: int = 0, vote: bool = False, vote_runs: int = 0) -> str:
+                 realign: bool = False, chain=None, gpu_decode: bool = False, **options) -> str:
     """-> path of the polished FASTA (use_hp: of haplotype 1's). batch_size: chunks per device launch (a region of up to 1201 columns gives about two).
     realign: realign every read to the draft on the device before the builder, as the reference always does.
     chain: a chain with the weights already loaded (open_device_chain; the caller closes it), else one is made on `ctx`
     (default: a context on device 0) from model_path. gpu_decode: polish_pieces' device read path.
+    options: the ChainOptions of the run. They make this function's own chain and pick the files and the VCF's header
+    lines; a chain passed in must have been made for them (_MADE_FOR), and one whose results lack a plane they need is
+    refused too (ValueError), before any file is written.
     qualities: also write the FASTQ beside the FASTA (output_fastq_path).
     edits: also write the edits VCF and its index beside the FASTA (polish_edits.output_vcf_path). The VCF is composed
     before any file is written, so a run it refuses (overlapping -r ranges of one contig) leaves nothing.
-    The two flags make this function's own chain and pick the files; a chain passed in whose results lack a plane they
-    need is refused (ValueError) before any file is written.
-    min_depth >= 1: this function's own chain masks the rows below it (a chain passed in must have been made for it), the
-    regions without reads are filled from the draft (draft_pieces), and the VCF names the threshold.
-    min_qual >= 1: this function's own chain takes back the runs of edits below it (a chain passed in must have been made
-    for it), and the VCF names the threshold.
-    min_support >= 1: this function's own chain takes back the runs of edits that fewer reads spell (a chain passed in must
-    have been made for it), and the VCF names the threshold.
-    use_hp: one set of files per haplotype (hp_path) in place of the un-suffixed ones; this function's own chain selects the
-    reads by haplotype (a chain passed in must have been made with use_hp).
-    evidence (with edits): every VCF record carries DP, AD, SAF and SAR of its weakest column (polish_edits.compose_records);
-    this function's own chain attaches the evidence (a chain passed in must have been made for it).
-    vote: the labels come from the reads' majority: model_path is not read (it may be None), this function's own chain votes
-    (a chain passed in must have been made for it), and the VCF names the consensus.
-    vote_runs = min_run >= 2 (with vote): this function's own chain also votes every homopolymer run's length read by read
-    (a chain passed in must have been made with the same min_run), and the VCF names the consensus vote+runs and min_run."""
+    evidence (with edits): every VCF record carries DP, AD, SAF and SAR of its weakest column (polish_edits.compose_records).
+    min_depth >= 1: the rows below it are masked, the regions without reads are filled from the draft (draft_pieces), and
+    the VCF names the threshold. min_qual >= 1, min_support >= 1: the runs of edits below them are taken back, and the VCF
+    names the threshold.
+    use_hp: one set of files per haplotype (hp_path) in place of the un-suffixed ones.
+    vote: the labels come from the reads' majority: model_path is not read (it may be None), and the VCF names the consensus.
+    vote_runs = min_run >= 2 (with vote): every homopolymer run's length is voted read by read too (a chain passed in must
+    have been made with the same min_run), and the VCF names the consensus vote+runs and min_run."""
     from .bamio import BamHandler, FastaHandler
     from .runtime import Context
     t_start = time.perf_counter()
-    T = dict(read_s=0.0, device_s=0.0, regions=0, batches=0, bases_in=0, bases_out=0, masked_rows=0, unmaskable_rows=0, draft_regions=0,
-             reverted_rows=0, pinned_rows=0, unsupported_rows=0, pinned_unsupported_rows=0, voted_rows=0, no_read_rows=0,
-             runs_seen=0, runs_decided=0, runs_changed=0, runs_skipped=0)
+    if chain is not None and options.get("evidence") and not options.get("edits"):
+        raise ValueError("polish_fused: evidence needs edits: the numbers go into the edits VCF")
+    o = ChainOptions(**options)
+    T = dict(read_s=0.0, device_s=0.0, regions=0, batches=0, bases_in=0, bases_out=0, draft_regions=0, **dict.fromkeys(PASS_TIMERS, 0))
     own = None
     if chain is None:
-        state_dict = None if vote else load_polish_model(model_path)
+        state_dict = None if o.vote else load_polish_model(model_path)
         if ctx is None:
             ctx = own = Context(0)
-        if not vote:
+        if not o.vote:
             ctx.load_p2(state_dict, dtype)
-        chain = _DeviceChain(ctx, qualities=qualities, edits=edits, min_depth=min_depth, min_qual=min_qual, use_hp=use_hp,
-                             **({"evidence": True} if evidence else {}), **({"min_support": min_support} if min_support else {}),
-                             **({"vote": True} if vote else {}), **({"vote_runs": vote_runs} if vote_runs else {}))
-    if evidence and not edits:
-        raise ValueError("polish_fused: evidence needs edits: the numbers go into the edits VCF")
+        chain = _DeviceChain(ctx, **o.keywords())
     try:
         fa, bm = FastaHandler(fasta), BamHandler(bam)
         work, T["bases_in"] = polish_work(fa, bm, region)
         out_path = output_fasta_path(out_prefix)
         log("POLISHING %d REGIONS, OUTPUT: %s" % (len(work), out_path))
-        if min_depth >= 1 and getattr(chain, "min_depth", None) != min_depth:
-            raise ValueError("polish_fused: the chain masks below depth %r, not %d: it was not made for this run"
-                             % (getattr(chain, "min_depth", None), min_depth))
-        if min_qual >= 1 and getattr(chain, "min_qual", None) != min_qual:
-            raise ValueError("polish_fused: the chain filters below quality %r, not %d: it was not made for this run"
-                             % (getattr(chain, "min_qual", None), min_qual))
-        if min_support >= 1 and getattr(chain, "min_support", None) != min_support:
-            raise ValueError("polish_fused: the chain filters below support %r, not %d: it was not made for this run"
-                             % (getattr(chain, "min_support", None), min_support))
-        if bool(vote) != bool(getattr(chain, "vote", False)):
-            raise ValueError("polish_fused: the chain %s: it was not made for this run"
-                             % ("does not vote" if vote else "votes in the network's place"))
-        if int(vote_runs) != int(getattr(chain, "vote_runs", 0) or 0):
-            raise ValueError("polish_fused: the chain votes runs from length %r, not %d: it was not made for this run"
-                             % (getattr(chain, "vote_runs", 0), vote_runs))
-        if use_hp and not getattr(chain, "use_hp", False):
-            raise ValueError("polish_fused: the chain does not select reads by haplotype: it was not made for this run")
-        if use_hp:
+        for option, default, refused, does in _MADE_FOR:
+            want, have = getattr(o, option), getattr(chain, option, default)
+            if refused(want, have):
+                raise ValueError(_NOT_MADE % (" " + (does % (have, want) if "%" in does else does)))
+        if o.use_hp:
             pairs = list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode, use_hp=True))
             outputs = [(h, hp_path(out_path, h), [p for k, p in pairs if k == h]) for h in (1, 2)]
         else:
             outputs = [(0, out_path, list(polish_pieces(bam, fasta, work, chain, batch_size, threads, realign, T, gpu_decode=gpu_decode)))]
         vcfs = []
         for _, _, pieces in outputs:
-            for want, plane in ((qualities, "qual"), (edits, "edits"), (evidence, "evidence")):
+            for want, plane in ((o.qualities, "qual"), (o.edits, "edits"), (o.evidence, "evidence")):
                 if want and pieces and getattr(pieces[0], plane) is None:
-                    raise ValueError("polish_fused: the chain's results have no %s plane: it was not made for this run" % plane)
-            if min_depth >= 1:
-                filled = draft_pieces(fa, work, pieces, qualities, edits, *((True,) if evidence else ()))
+                    raise ValueError(_NOT_MADE % ("'s results have no %s plane" % plane))
+            if o.min_depth >= 1:
+                filled = draft_pieces(fa, work, pieces, o.qualities, o.edits, o.evidence)
                 T["draft_regions"] += len(filled)
                 pieces += filled
-            vcfs.append(_edits_vcf(fa, fasta, work, pieces, qualities, min_depth, min_qual, *((True,) if evidence else ()))
-                        if edits else None)
+            vcfs.append(_edits_vcf(fa, fasta, work, pieces, o.qualities, o.min_depth, o.min_qual, o.evidence) if o.edits else None)
     finally:
         if own is not None:
             own.close()
     for (h, path, pieces), vcf in zip(outputs, vcfs):
         seqs = write_polished_fasta(path, pieces)
-        if qualities:
+        if o.qualities:
             write_fastq(output_fastq_path(path), seqs, merge_pieces(pieces, part=4))
-        if edits:
+        if o.edits:
             from . import polish_edits
-            polish_edits.write_edits_vcf(polish_edits.output_vcf_path(path), *vcf, **({"haplotype": h} if h else {}),
-                                         **({"evidence": True} if evidence else {}),
-                                         **({"min_support": min_support} if min_support else {}),
-                                         **({"consensus": "vote+runs" if vote_runs else "vote"} if vote else {}),
-                                         **({"min_run": vote_runs} if vote_runs else {}))
-            if evidence:   # records whose alt support (of their weakest column) stands on one strand only
+            polish_edits.write_edits_vcf(polish_edits.output_vcf_path(path), *vcf, haplotype=h, evidence=o.evidence,
+                                         min_support=o.min_support, min_run=o.vote_runs,
+                                         consensus=("vote+runs" if o.vote_runs else "vote") if o.vote else "")
+            if o.evidence:   # records whose alt support (of their weakest column) stands on one strand only
                 T["one_strand_records"] = T.get("one_strand_records", 0) + sum(
                     (r.evidence[2] == 0) != (r.evidence[3] == 0) for recs in vcf[4].values() for r in recs)
             T["edit_records"] = T.get("edit_records", 0) + sum(len(p.edits) for p in pieces)
@@ -1146,6 +1152,44 @@ def _edits_vcf(fa, fasta_path: str, work: List[Work], pieces, qualities: bool, m
     return "pepper_thesis_amd polish", os.path.abspath(fasta_path), contigs, no_reads, records, int(min_depth), int(min_qual)
 
 
+def _one_device(option: str, flag: str, what: str) -> tuple:
+    """a refusal of the command: `option` is set and -d_ids lists several devices, between which `what` holds"""
+    return (lambda o, args, devices: getattr(o, option) and devices > 1,
+            "polish %s runs on one device (-d_ids %%(device_ids)s lists %%(devices)d): %s.\n" % (flag, what))
+
+
+# What the command refuses about its options, in the order it looks (the first that holds is reported): (refused when (the
+# unchecked ChainOptions, the namespace, the devices of -d_ids), the text behind "ERROR: ", filled from the options)
+_REFUSALS = (
+    _one_device("qualities", "--qualities", "the quality plane is not carried through the rank exchange yet"),
+    _one_device("edits", "--edits", "the edit records are not carried through the rank exchange yet"),
+    (lambda o, args, devices: o.evidence and not o.edits,
+     "polish --evidence needs --edits: the read support goes into the INFO column of the edits VCF.\n"),
+    (lambda o, args, devices: not 0 <= o.min_depth <= 65535,
+     "polish --min_depth %(min_depth)d: the minimum depth is a number of reads from 0 (off) to 65535.\n"),
+    _one_device("min_depth", "--min_depth", "the depth plane is not carried through the rank exchange yet"),
+    (lambda o, args, devices: not 0 <= o.min_qual <= 94,
+     "polish --min_qual %(min_qual)d: the minimum quality is a Phred value from 0 (off) to 94 (qualities stop at 93, so 94 takes "
+     "back every edit).\n"),
+    _one_device("min_qual", "--min_qual", "the row qualities are not carried through the rank exchange yet"),
+    (lambda o, args, devices: not 0 <= o.min_support <= 65535,
+     "polish --min_support %(min_support)d: the minimum support is a number of reads from 0 (off) to 65535.\n"),
+    _one_device("min_support", "--min_support", "the counts plane is not carried through the rank exchange yet"),
+    (lambda o, args, devices: getattr(args, "min_run", None) is not None and not o.vote_runs,
+     "polish --min_run needs --runs: it is the shortest homopolymer run the run vote looks at.\n"),
+    (lambda o, args, devices: o.vote_runs and not o.vote,
+     "polish --runs needs --vote: the run vote rewrites the rows the reads' column vote left; behind a model it has no meaning.\n"),
+    (lambda o, args, devices: o.vote_runs and not 2 <= o.vote_runs <= 48,
+     "polish --min_run %(vote_runs)d: the shortest run voted on is a length from 2 to 48.\n"),
+    _one_device("vote_runs", "--runs", "the reads are not carried through the rank exchange"),
+    (lambda o, args, devices: o.vote_runs and o.min_support,
+     "polish --runs takes no --min_support: that filter promises that at least K reads spell an edit in its own column, and a "
+     "run-voted column can be one that few reads delete there.\n"),
+    _one_device("vote", "--vote", "the counts plane is not carried through the rank exchange yet"),
+    _one_device("use_hp", "-hp", "the haplotypes are not carried through the rank exchange yet"),
+)
+
+
 def run(args, open_chain=open_device_chain) -> int:
     """the `polish` command. With several -d_ids: check the inputs here (no GPU API is touched), then start one rank per id
     and wait for them (polish_rank.launch). open_chain: see open_device_chain (CPU tests pass a stub)."""
@@ -1167,75 +1211,12 @@ def run(args, open_chain=open_device_chain) -> int:
     except ValueError as e:
         sys.stderr.write("ERROR: %s\n" % e)
         return 2
-    qualities = bool(getattr(args, "qualities", False))
-    if qualities and len(plan) > 1:
-        sys.stderr.write("ERROR: polish --qualities runs on one device (-d_ids %s lists %d): the quality plane is not carried "
-                         "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
-        return 2
-    edits = bool(getattr(args, "edits", False))
-    if edits and len(plan) > 1:
-        sys.stderr.write("ERROR: polish --edits runs on one device (-d_ids %s lists %d): the edit records are not carried "
-                         "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
-        return 2
-    evidence = bool(getattr(args, "evidence", False))
-    if evidence and not edits:
-        sys.stderr.write("ERROR: polish --evidence needs --edits: the read support goes into the INFO column of the edits VCF.\n")
-        return 2
-    min_depth = int(getattr(args, "min_depth", 0) or 0)
-    if not 0 <= min_depth <= 65535:
-        sys.stderr.write("ERROR: polish --min_depth %d: the minimum depth is a number of reads from 0 (off) to 65535.\n" % min_depth)
-        return 2
-    if min_depth and len(plan) > 1:
-        sys.stderr.write("ERROR: polish --min_depth runs on one device (-d_ids %s lists %d): the depth plane is not carried "
-                         "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
-        return 2
-    min_qual = int(getattr(args, "min_qual", 0) or 0)
-    if not 0 <= min_qual <= 94:
-        sys.stderr.write("ERROR: polish --min_qual %d: the minimum quality is a Phred value from 0 (off) to 94 (qualities stop at "
-                         "93, so 94 takes back every edit).\n" % min_qual)
-        return 2
-    if min_qual and len(plan) > 1:
-        sys.stderr.write("ERROR: polish --min_qual runs on one device (-d_ids %s lists %d): the row qualities are not carried "
-                         "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
-        return 2
-    min_support = int(getattr(args, "min_support", 0) or 0)
-    if not 0 <= min_support <= 65535:
-        sys.stderr.write("ERROR: polish --min_support %d: the minimum support is a number of reads from 0 (off) to 65535.\n"
-                         % min_support)
-        return 2
-    if min_support and len(plan) > 1:
-        sys.stderr.write("ERROR: polish --min_support runs on one device (-d_ids %s lists %d): the counts plane is not carried "
-                         "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
-        return 2
-    runs = bool(getattr(args, "runs", False))
-    min_run = int(getattr(args, "min_run", None) or 3) if runs else 0
-    if getattr(args, "min_run", None) is not None and not runs:
-        sys.stderr.write("ERROR: polish --min_run needs --runs: it is the shortest homopolymer run the run vote looks at.\n")
-        return 2
-    if runs and not vote:
-        sys.stderr.write("ERROR: polish --runs needs --vote: the run vote rewrites the rows the reads' column vote left; behind a "
-                         "model it has no meaning.\n")
-        return 2
-    if runs and not 2 <= min_run <= 48:
-        sys.stderr.write("ERROR: polish --min_run %d: the shortest run voted on is a length from 2 to 48.\n" % min_run)
-        return 2
-    if runs and len(plan) > 1:
-        sys.stderr.write("ERROR: polish --runs runs on one device (-d_ids %s lists %d): the reads are not carried through the "
-                         "rank exchange.\n" % (args.device_ids, len(plan)))
-        return 2
-    if runs and min_support:
-        sys.stderr.write("ERROR: polish --runs takes no --min_support: that filter promises that at least K reads spell an edit in "
-                         "its own column, and a run-voted column can be one that few reads delete there.\n")
-        return 2
-    if vote and len(plan) > 1:
-        sys.stderr.write("ERROR: polish --vote runs on one device (-d_ids %s lists %d): the counts plane is not carried "
-                         "through the rank exchange yet.\n" % (args.device_ids, len(plan)))
-        return 2
-    use_hp = bool(getattr(args, "use_hp_info", False))
-    if use_hp and len(plan) > 1:
-        sys.stderr.write("ERROR: polish -hp runs on one device (-d_ids %s lists %d): the haplotypes are not carried through the "
-                         "rank exchange yet.\n" % (args.device_ids, len(plan)))
-        return 2
+    o = ChainOptions.from_args(args)
+    said = dict(dataclasses.asdict(o), device_ids=args.device_ids, devices=len(plan))
+    for refused, text in _REFUSALS:
+        if refused(o, args, len(plan)):
+            sys.stderr.write("ERROR: " + text % said)
+            return 2
     for what, path in (("BAM", args.bam), ("FASTA", args.fasta)) + (() if vote else (("MODEL", args.model_path),)):
         if not os.path.isfile(path):
             sys.stderr.write("ERROR: CAN NOT LOCATE %s FILE.\n" % what)
@@ -1251,35 +1232,14 @@ def run(args, open_chain=open_device_chain) -> int:
     if len(plan) > 1:
         return polish_rank.launch(args, plan)
     dtype = _ffi.PV_DTYPE_BF16_INPUT_GEMM if args.bf16 else _ffi.PV_DTYPE_F32
-    kw = dict(qualities=True) if qualities else {}   # (only the keywords that are set: stub chains keep their signatures)
-    if edits:
-        kw["edits"] = True
-    if min_depth:
-        kw["min_depth"] = min_depth
-    if min_qual:
-        kw["min_qual"] = min_qual
-    if use_hp:
-        kw["use_hp"] = True
-    if evidence:
-        kw["evidence"] = True
-    if min_support:
-        kw["min_support"] = min_support
-    if vote:
-        kw["vote"] = True
-    if runs:
-        kw["vote_runs"] = min_run
-    chain = open_chain(device, False, state_dict, dtype, **kw)
+    chain = open_chain(device, False, state_dict, dtype, **o.keywords())   # (only those that are set: stub chains keep their signatures)
     try:
         T = {}
         path = polish_fused(args.bam, args.fasta, args.model_path, args.output_file, args.region, args.batch_size, args.threads,
                             timers=T, realign=bool(getattr(args, "realign", False)), chain=chain,
-                            gpu_decode=bool(getattr(args, "gpu_decode", False)), qualities=qualities, edits=edits,
-                            min_depth=min_depth, min_qual=min_qual, **({"use_hp": True} if use_hp else {}),
-                            **({"evidence": True} if evidence else {}),
-                            **({"min_support": min_support} if min_support else {}), **({"vote": True} if vote else {}),
-                            **({"vote_runs": min_run} if runs else {}))
+                            gpu_decode=bool(getattr(args, "gpu_decode", False)), **o.keywords())
     except ValueError as e:
-        if not edits:
+        if not o.edits:
             raise
         sys.stderr.write("ERROR: %s\n" % e)
         return 2
@@ -1289,34 +1249,22 @@ def run(args, open_chain=open_device_chain) -> int:
         log(decode_report(T))
     log("POLISHED FASTA: %s (%d REGIONS, %d BASES IN %.2f SEC)" % (path, T["regions"], T["bases_out"], T["wall_s"]))
     paths = [path]
-    if use_hp:
+    if o.use_hp:
         paths.append(hp_path(path[:-len("_hp1.fa")] + ".fa", 2))
         log("POLISHED FASTA: " + paths[1])
         log("HAPLOTYPES: %d READS SEEN, %d UNTAGGED, %d HP1, %d HP2, %d WITH OTHER TAG VALUES (IN NEITHER HAPLOTYPE)"
             % tuple(T.get(k, 0) for k in HP_TIMERS))
         if T.get("hp_reads", 0) == T.get("hp_untagged", 0):
             sys.stderr.write("WARNING: polish -hp: no read carries an HP tag; both haplotypes are the plain polish of all reads.\n")
-    if vote:
-        log("VOTE: %d CHUNK ROWS WHERE THE READS' MAJORITY IS NOT THE DRAFT, %d BASE ROWS WITHOUT READS (THE DRAFT IS KEPT, OR "
-            "DROPPED WHERE ITS BYTE IS NOT ACGT)" % (T["voted_rows"], T["no_read_rows"]))
-    if runs:
-        log("RUNS (MIN RUN %d): %d CANDIDATE RUNS SEEN, %d DECIDED BY THEIR READS, %d OF THEM WITH A LENGTH THAT IS NOT THE DRAFT'S, "
-            "%d SKIPPED AS ADJACENT" % (min_run, T["runs_seen"], T["runs_decided"], T["runs_changed"], T["runs_skipped"]))
-    if min_depth:
-        log("MIN DEPTH %d: %d CHUNK ROWS KEPT THE DRAFT, %d COULD NOT (DRAFT BYTE NOT ACGT), %d REGIONS WITHOUT READS FILLED FROM THE DRAFT"
-            % (min_depth, T["masked_rows"], T["unmaskable_rows"], T["draft_regions"]))
-    if min_qual:
-        log("MIN QUAL %d: %d CHUNK ROWS OF EDITS TAKEN BACK, %d ROWS OF LOW RUNS KEPT (DRAFT BYTE NOT ACGT)"
-            % (min_qual, T["reverted_rows"], T["pinned_rows"]))
-    if min_support:
-        log("MIN SUPPORT %d: %d CHUNK ROWS OF EDITS TAKEN BACK, %d ROWS OF WEAK RUNS KEPT (DRAFT BYTE NOT ACGT)"
-            % (min_support, T["unsupported_rows"], T["pinned_unsupported_rows"]))
-    if qualities:
+    for p in sorted(PASSES, key=lambda p: p.in_place is not None):   # in launch order: the votes, then the in-place passes
+        if getattr(o, p.option):
+            log(p.report % dict(dataclasses.asdict(o), **T))
+    if o.qualities:
         log("POLISHED FASTQ: " + ", ".join(output_fastq_path(p) for p in paths))
-    if edits:
+    if o.edits:
         from .polish_edits import output_vcf_path
         log("EDITS VCF: %s (%d RECORDS FROM %d EDITED COLUMNS)" % (", ".join(output_vcf_path(p) for p in paths), T["vcf_records"],
                                                                    T["edit_records"]))
-    if evidence:
+    if o.evidence:
         log("EVIDENCE: %d OF %d RECORDS HAVE THEIR ALT SUPPORT ON ONE STRAND ONLY" % (T.get("one_strand_records", 0), T["vcf_records"]))
     return 0

@@ -368,15 +368,50 @@ class Context:
             _ffi.check(self.lib.pv_polish_stitch_dev(*args))
 
     @staticmethod
-    def _host_polish_out(out):
+    def _host_polish_out(out, seq_length: int = None, depth: bool = False, counts: bool = False):
         """the host pv_polish_out view of a PolishOut's position, index, region and chunk_id -> (n_chunks, struct, the
-        arrays it points into: keep them until the call returns)"""
+        arrays it points into: keep them until the call returns). depth, counts: and of its depth / counts plane, uint16
+        [n, seq_length] / [n, seq_length, 10]; one the PolishOut lacks stays null, for the call to refuse."""
         keep = [np.ascontiguousarray(a, t) for a, t in ((out.position, np.int64), (out.index, np.int32), (out.region, np.int32),
                                                         (out.chunk_id, np.int32))]
         c = _ffi.pv_polish_out()
         c.chunk_capacity = n = int(len(out.chunk_id))
         c.position, c.index, c.region, c.chunk_id = (_ffi.ptr(a) for a in keep)
+        for want, field, more in ((depth, "depth", ()), (counts, "counts", (10,))):
+            if want and getattr(out, field, None) is not None:
+                plane = np.ascontiguousarray(getattr(out, field), np.uint16)
+                assert plane.shape == (n, seq_length) + more, plane.shape
+                setattr(c, field, _ffi.ptr(plane))
+                keep.append(plane)
         return n, c, keep
+
+    @staticmethod
+    def _host_draft(batch):
+        """the draft triple of the batch the chunks were built from (a RegionBatch's ref_start, ref_off, ref) as contiguous
+        arrays -> (region starts int64, draft offsets int64 [n_regions+1], draft bytes or None)"""
+        rs = np.ascontiguousarray(batch.ref_start, np.int64)
+        ro = np.ascontiguousarray(batch.ref_off, np.int64)
+        ref = None if batch.ref is None else np.ascontiguousarray(batch.ref, np.uint8)
+        assert len(ro) == len(rs) + 1 and (ref is None or len(ref) >= int(ro[-1])), (len(ro), len(rs))
+        return rs, ro, ref
+
+    def _label_pass(self, call, out, labels, row_qual, batch, sizes, level, counts, in_place, depth=False, rowcounts=False):
+        """one pass that rewrites labels and row qualities (pv_polish_mask_low_depth and the two filters; sizes: seq_length
+        [, seq_overlap]) -> (labels, row_qual or None) after it. in_place: the arrays given (C-contiguous uint8) are rewritten
+        and returned; else copies are."""
+        n, c, keep = self._host_polish_out(out, sizes[0], depth, rowcounts)
+        lab = labels if in_place else np.ascontiguousarray(labels, np.uint8)
+        rq = row_qual if in_place or row_qual is None else np.ascontiguousarray(row_qual, np.uint8)
+        assert lab.dtype == np.uint8 and (rq is None or rq.dtype == np.uint8)
+        assert lab.shape == (n, sizes[0]) and (rq is None or rq.shape == lab.shape), lab.shape
+        rs, ro, ref = self._host_draft(batch)
+        lab_out = lab if in_place else np.zeros_like(lab)
+        rq_out = rq if in_place or rq is None else np.zeros_like(rq)
+        if counts is None:
+            counts = (C.c_int64 * 4)()
+        _ffi.check(call(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rq), _ffi.ptr(rs), _ffi.ptr(ro), _ffi.ptr(ref), len(rs),
+                        *(int(v) for v in sizes), int(level), _ffi.ptr(lab_out), _ffi.ptr(rq_out), counts))
+        return lab_out, rq_out
 
     def _polish_stitch(self, out, labels, row_qual, region_start, seq_capacity, seq_length, seq_overlap, counts):
         """polish_stitch (row_qual None) / polish_stitch_qual -> (region_off, seq bytes[, qual bytes])"""
@@ -457,25 +492,33 @@ class Context:
         edit_capacity None: one record per chunk row; a smaller one raises PepperHipError(PV_ERR_CAPACITY).
         counts: optional ctypes int64[4] that receives {edits, status, first bad chunk, 0}, and region_edit_off an optional
         int64 [n_regions+1] array that receives the offsets, also when the call raises."""
-        from .polish_edits import EDIT_DTYPE
-        n, c, keep = self._host_polish_out(out)
+        return self._polish_edits(out, labels, batch, row_qual, edit_capacity, seq_length, seq_overlap, counts, region_edit_off)
+
+    def _polish_edits(self, out, labels, batch, row_qual, edit_capacity, seq_length, seq_overlap, counts, region_edit_off,
+                      with_ev=False, evidence=None):
+        """polish_edits / (with_ev) polish_edits_evidence"""
+        from .polish_edits import EDIT_DTYPE, EVIDENCE_DTYPE
+        n, c, keep = self._host_polish_out(out, seq_length, depth=with_ev, counts=with_ev)
         lab = np.ascontiguousarray(labels, np.uint8)
         rq = None if row_qual is None else np.ascontiguousarray(row_qual, np.uint8)
-        rs = np.ascontiguousarray(batch.ref_start, np.int64)
-        ro = np.ascontiguousarray(batch.ref_off, np.int64)
-        ref = None if batch.ref is None else np.ascontiguousarray(batch.ref, np.uint8)
         assert lab.shape == (n, seq_length) and (rq is None or rq.shape == lab.shape), lab.shape
-        assert len(ro) == len(rs) + 1 and (ref is None or len(ref) >= int(ro[-1])), (len(ro), len(rs))
+        rs, ro, ref = self._host_draft(batch)
         cap = n * seq_length if edit_capacity is None else int(edit_capacity)
         if region_edit_off is None:
             region_edit_off = np.zeros(len(rs) + 1, np.int64)
         edits = np.zeros(max(cap, 1), EDIT_DTYPE)
         if counts is None:
             counts = (C.c_int64 * 4)()
-        _ffi.check(self.lib.pv_polish_edits(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rq), _ffi.ptr(rs), _ffi.ptr(ro),
-                                            _ffi.ptr(ref), len(rs), seq_length, seq_overlap, _ffi.ptr(region_edit_off),
-                                            _ffi.ptr(edits), cap, counts))
-        return region_edit_off, edits[:int(counts[0])].copy()
+        args = (self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rq), _ffi.ptr(rs), _ffi.ptr(ro), _ffi.ptr(ref), len(rs),
+                seq_length, seq_overlap, _ffi.ptr(region_edit_off), _ffi.ptr(edits))
+        if not with_ev:
+            _ffi.check(self.lib.pv_polish_edits(*args, cap, counts))
+            return region_edit_off, edits[:int(counts[0])].copy()
+        if evidence is None:
+            evidence = np.zeros(max(cap, 1), EVIDENCE_DTYPE)
+        assert evidence.dtype == EVIDENCE_DTYPE and len(evidence) >= cap and evidence.flags.c_contiguous
+        _ffi.check(self.lib.pv_polish_edits_evidence(*args, _ffi.ptr(evidence), cap, counts))
+        return region_edit_off, edits[:int(counts[0])].copy(), evidence[:int(counts[0])].copy()
 
     def polish_edits_evidence_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_row_qual: int, d_region_start: int,
                                   d_ref_off: int, d_ref: int, n_regions: int, d_region_edit_off: int, d_edits: int, d_evidence: int,
@@ -494,33 +537,8 @@ class Context:
         edit records, evidence records as a polish_edits.EVIDENCE_DTYPE array). The other arguments are polish_edits';
         evidence: an optional EVIDENCE_DTYPE array of at least the capacity that receives the records (tests look at what
         the call left alone)."""
-        from .polish_edits import EDIT_DTYPE, EVIDENCE_DTYPE
-        n, c, keep = self._host_polish_out(out)
-        depth = None if getattr(out, "depth", None) is None else np.ascontiguousarray(out.depth, np.uint16)
-        rowc = None if getattr(out, "counts", None) is None else np.ascontiguousarray(out.counts, np.uint16)
-        c.depth, c.counts = _ffi.ptr(depth), _ffi.ptr(rowc)
-        lab = np.ascontiguousarray(labels, np.uint8)
-        rq = None if row_qual is None else np.ascontiguousarray(row_qual, np.uint8)
-        rs = np.ascontiguousarray(batch.ref_start, np.int64)
-        ro = np.ascontiguousarray(batch.ref_off, np.int64)
-        ref = None if batch.ref is None else np.ascontiguousarray(batch.ref, np.uint8)
-        assert lab.shape == (n, seq_length) and (rq is None or rq.shape == lab.shape), lab.shape
-        assert depth is None or depth.shape == lab.shape, depth.shape
-        assert rowc is None or rowc.shape == lab.shape + (10,), rowc.shape
-        assert len(ro) == len(rs) + 1 and (ref is None or len(ref) >= int(ro[-1])), (len(ro), len(rs))
-        cap = n * seq_length if edit_capacity is None else int(edit_capacity)
-        if region_edit_off is None:
-            region_edit_off = np.zeros(len(rs) + 1, np.int64)
-        edits = np.zeros(max(cap, 1), EDIT_DTYPE)
-        if evidence is None:
-            evidence = np.zeros(max(cap, 1), EVIDENCE_DTYPE)
-        assert evidence.dtype == EVIDENCE_DTYPE and len(evidence) >= cap and evidence.flags.c_contiguous
-        if counts is None:
-            counts = (C.c_int64 * 4)()
-        _ffi.check(self.lib.pv_polish_edits_evidence(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rq), _ffi.ptr(rs),
-                                                     _ffi.ptr(ro), _ffi.ptr(ref), len(rs), seq_length, seq_overlap,
-                                                     _ffi.ptr(region_edit_off), _ffi.ptr(edits), _ffi.ptr(evidence), cap, counts))
-        return region_edit_off, edits[:int(counts[0])].copy(), evidence[:int(counts[0])].copy()
+        return self._polish_edits(out, labels, batch, row_qual, edit_capacity, seq_length, seq_overlap, counts, region_edit_off,
+                                  True, evidence)
 
     def polish_mask_low_depth_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_row_qual: int, d_region_start: int,
                                   d_ref_off: int, d_ref: int, n_regions: int, min_depth: int, d_labels_out: int,
@@ -540,26 +558,8 @@ class Context:
         arrays given (C-contiguous uint8) are rewritten and returned; else copies are.
         counts: optional ctypes int64[4] that receives {masked rows, status, first bad chunk, unmaskable rows}, also when the
         call raises."""
-        n, c, keep = self._host_polish_out(out)
-        depth = None if getattr(out, "depth", None) is None else np.ascontiguousarray(out.depth, np.uint16)
-        c.depth = _ffi.ptr(depth)
-        lab = labels if in_place else np.ascontiguousarray(labels, np.uint8)
-        rq = row_qual if in_place or row_qual is None else np.ascontiguousarray(row_qual, np.uint8)
-        assert lab.dtype == np.uint8 and (rq is None or rq.dtype == np.uint8)
-        rs = np.ascontiguousarray(batch.ref_start, np.int64)
-        ro = np.ascontiguousarray(batch.ref_off, np.int64)
-        ref = None if batch.ref is None else np.ascontiguousarray(batch.ref, np.uint8)
-        assert lab.shape == (n, seq_length) and (rq is None or rq.shape == lab.shape), lab.shape
-        assert depth is None or depth.shape == lab.shape, depth.shape
-        assert len(ro) == len(rs) + 1 and (ref is None or len(ref) >= int(ro[-1])), (len(ro), len(rs))
-        lab_out = lab if in_place else np.zeros_like(lab)
-        rq_out = rq if in_place or rq is None else np.zeros_like(rq)
-        if counts is None:
-            counts = (C.c_int64 * 4)()
-        _ffi.check(self.lib.pv_polish_mask_low_depth(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rq), _ffi.ptr(rs),
-                                                     _ffi.ptr(ro), _ffi.ptr(ref), len(rs), seq_length, int(min_depth),
-                                                     _ffi.ptr(lab_out), _ffi.ptr(rq_out), counts))
-        return lab_out, rq_out
+        return self._label_pass(self.lib.pv_polish_mask_low_depth, out, labels, row_qual, batch, (seq_length,), min_depth, counts,
+                                in_place, depth=True)
 
     def polish_filter_low_qual_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_row_qual: int, d_region_start: int,
                                    d_ref_off: int, d_ref: int, n_regions: int, min_qual: int, d_labels_out: int,
@@ -581,23 +581,8 @@ class Context:
         given (C-contiguous uint8) are rewritten and returned; else copies are.
         counts: optional ctypes int64[4] that receives {rows reverted, status, first bad chunk, rows of pinned runs below
         min_qual}, also when the call raises."""
-        n, c, keep = self._host_polish_out(out)
-        lab = labels if in_place else np.ascontiguousarray(labels, np.uint8)
-        rq = row_qual if in_place or row_qual is None else np.ascontiguousarray(row_qual, np.uint8)
-        assert lab.dtype == np.uint8 and (rq is None or rq.dtype == np.uint8)
-        rs = np.ascontiguousarray(batch.ref_start, np.int64)
-        ro = np.ascontiguousarray(batch.ref_off, np.int64)
-        ref = None if batch.ref is None else np.ascontiguousarray(batch.ref, np.uint8)
-        assert lab.shape == (n, seq_length) and (rq is None or rq.shape == lab.shape), lab.shape
-        assert len(ro) == len(rs) + 1 and (ref is None or len(ref) >= int(ro[-1])), (len(ro), len(rs))
-        lab_out = lab if in_place else np.zeros_like(lab)
-        rq_out = rq if in_place or rq is None else np.zeros_like(rq)
-        if counts is None:
-            counts = (C.c_int64 * 4)()
-        _ffi.check(self.lib.pv_polish_filter_low_qual(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rq), _ffi.ptr(rs),
-                                                      _ffi.ptr(ro), _ffi.ptr(ref), len(rs), seq_length, int(seq_overlap),
-                                                      int(min_qual), _ffi.ptr(lab_out), _ffi.ptr(rq_out), counts))
-        return lab_out, rq_out
+        return self._label_pass(self.lib.pv_polish_filter_low_qual, out, labels, row_qual, batch, (seq_length, seq_overlap), min_qual,
+                                counts, in_place)
 
     def polish_filter_low_support_dev(self, dout: "DevicePolishOut", n_chunks: int, d_labels: int, d_row_qual: int,
                                       d_region_start: int, d_ref_off: int, d_ref: int, n_regions: int, min_support: int,
@@ -621,28 +606,8 @@ class Context:
         copies are.
         counts: optional ctypes int64[4] that receives {rows reverted, status, first bad chunk, rows of pinned runs below
         min_support}, also when the call raises."""
-        n, c, keep = self._host_polish_out(out)
-        depth = None if getattr(out, "depth", None) is None else np.ascontiguousarray(out.depth, np.uint16)
-        rowc = None if getattr(out, "counts", None) is None else np.ascontiguousarray(out.counts, np.uint16)
-        c.depth, c.counts = _ffi.ptr(depth), _ffi.ptr(rowc)
-        lab = labels if in_place else np.ascontiguousarray(labels, np.uint8)
-        rq = row_qual if in_place or row_qual is None else np.ascontiguousarray(row_qual, np.uint8)
-        assert lab.dtype == np.uint8 and (rq is None or rq.dtype == np.uint8)
-        rs = np.ascontiguousarray(batch.ref_start, np.int64)
-        ro = np.ascontiguousarray(batch.ref_off, np.int64)
-        ref = None if batch.ref is None else np.ascontiguousarray(batch.ref, np.uint8)
-        assert lab.shape == (n, seq_length) and (rq is None or rq.shape == lab.shape), lab.shape
-        assert depth is None or depth.shape == lab.shape, depth.shape
-        assert rowc is None or rowc.shape == lab.shape + (10,), rowc.shape
-        assert len(ro) == len(rs) + 1 and (ref is None or len(ref) >= int(ro[-1])), (len(ro), len(rs))
-        lab_out = lab if in_place else np.zeros_like(lab)
-        rq_out = rq if in_place or rq is None else np.zeros_like(rq)
-        if counts is None:
-            counts = (C.c_int64 * 4)()
-        _ffi.check(self.lib.pv_polish_filter_low_support(self.handle, C.byref(c), n, _ffi.ptr(lab), _ffi.ptr(rq), _ffi.ptr(rs),
-                                                         _ffi.ptr(ro), _ffi.ptr(ref), len(rs), seq_length, int(seq_overlap),
-                                                         int(min_support), _ffi.ptr(lab_out), _ffi.ptr(rq_out), counts))
-        return lab_out, rq_out
+        return self._label_pass(self.lib.pv_polish_filter_low_support, out, labels, row_qual, batch, (seq_length, seq_overlap),
+                                min_support, counts, in_place, depth=True, rowcounts=True)
 
     def polish_vote_dev(self, dout: "DevicePolishOut", n_chunks: int, d_region_start: int, d_ref_off: int, d_ref: int,
                         n_regions: int, d_labels: int, d_acc: int, d_counts: int, stream: int = 0):
@@ -661,16 +626,8 @@ class Context:
         counts: optional ctypes int64[4] that receives {rows whose winner is not the draft's, status, first bad chunk, base
         rows without reads}, also when the call raises. labels, acc: optional C-contiguous arrays that receive the planes
         (tests look at what the call left alone); acc implies want_acc."""
-        n, c, keep = self._host_polish_out(out)
-        depth = None if getattr(out, "depth", None) is None else np.ascontiguousarray(out.depth, np.uint16)
-        rowc = None if getattr(out, "counts", None) is None else np.ascontiguousarray(out.counts, np.uint16)
-        c.depth, c.counts = _ffi.ptr(depth), _ffi.ptr(rowc)
-        rs = np.ascontiguousarray(batch.ref_start, np.int64)
-        ro = np.ascontiguousarray(batch.ref_off, np.int64)
-        ref = None if batch.ref is None else np.ascontiguousarray(batch.ref, np.uint8)
-        assert depth is None or depth.shape == (n, seq_length), depth.shape
-        assert rowc is None or rowc.shape == (n, seq_length, 10), rowc.shape
-        assert len(ro) == len(rs) + 1 and (ref is None or len(ref) >= int(ro[-1])), (len(ro), len(rs))
+        n, c, keep = self._host_polish_out(out, seq_length, depth=True, counts=True)
+        rs, ro, ref = self._host_draft(batch)
         if labels is None:
             labels = np.zeros((n, seq_length), np.uint8)
         if acc is None and want_acc:

@@ -145,28 +145,11 @@ def stitch_leg(reps=20):
                                      "stitch_ms": round(t_host * 1e3, 1)}}
 
 
-def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False, qualities=False, edits=False, min_depth=0,
-             min_qual=0, use_hp=False, evidence=False, min_support=0, vote=False, vote_runs=0):
+def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decode=False, **options):
+    """options: the polish.ChainOptions of the run"""
+    o = polish.ChainOptions(**options)
+    kw = dict(o.keywords(), gpu_decode=True) if gpu_decode else o.keywords()
     # warm-up on a small region (code objects, allocator), then the timed run
-    kw = {"gpu_decode": True} if gpu_decode else {}
-    if use_hp:
-        kw["use_hp"] = True
-    if min_depth:
-        kw["min_depth"] = min_depth
-    if min_qual:
-        kw["min_qual"] = min_qual
-    if min_support:
-        kw["min_support"] = min_support
-    if qualities:
-        kw["qualities"] = True
-    if edits:
-        kw["edits"] = True
-    if evidence:
-        kw["evidence"] = True
-    if vote:
-        kw["vote"] = True
-    if vote_runs:
-        kw["vote_runs"] = vote_runs
     polish.polish_fused(bam, fa, model, out + "_warm", region="chr20:0-50000", threads=threads, ctx=ctx, realign=realign, **kw)
     T = {}
     t0 = time.perf_counter()
@@ -177,31 +160,24 @@ def _e2e_run(polish, ctx, bam, fa, model, out, threads, realign, info, gpu_decod
            "polished_bp": T["bases_out"], "fasta_bytes": size, "wall_s": round(wall, 3),
            "read_s": round(T["read_s"], 3), "device_s": round(T["device_s"], 3),
            "draft_mbp_per_s": round(T["bases_in"] / wall / 1e6, 4), "reader_threads": threads}
-    if use_hp:
+    if o.use_hp:
         res.update(use_hp=True, fasta_bytes_hp2=os.path.getsize(polish.hp_path(path[:-len("_hp1.fa")] + ".fa", 2)),
                    tags={k: T[k] for k in polish.HP_TIMERS})
-    if min_depth:
-        res.update(min_depth=min_depth, masked_rows=T["masked_rows"], unmaskable_rows=T["unmaskable_rows"],
-                   draft_regions=T["draft_regions"])
-    if min_qual:
-        res.update(min_qual=min_qual, reverted_rows=T["reverted_rows"], pinned_rows=T["pinned_rows"])
-    if min_support:
-        res.update(min_support=min_support, unsupported_rows=T["unsupported_rows"], pinned_unsupported_rows=T["pinned_unsupported_rows"])
-    if vote:
-        res.update(vote=True, voted_rows=T["voted_rows"], no_read_rows=T["no_read_rows"])
-    if vote_runs:
-        res.update(min_run=vote_runs, **{k: T[k] for k in ("runs_seen", "runs_decided", "runs_changed", "runs_skipped")})
-    if qualities:
+    for p in polish.PASSES:   # the option's value (the run vote's as min_run) and the pass's counts
+        if getattr(o, p.option):
+            res[{"vote_runs": "min_run"}.get(p.option, p.option)] = getattr(o, p.option)
+            res.update({k: T[k] for k in p.timers + (("draft_regions",) if p.option == "min_depth" else ())})
+    if o.qualities:
         fq = polish.output_fastq_path(path)
         res["qualities"], res["fastq_bytes"] = True, os.path.getsize(fq)
-    if edits:
+    if o.edits:
         from pepper_thesis_amd import polish_edits
         vcf = polish_edits.output_vcf_path(path)
         res.update(edits=True, edit_records=T["edit_records"], vcf_records=T["vcf_records"], vcf_bytes=os.path.getsize(vcf),
                    tbi_bytes=os.path.getsize(vcf + ".tbi"),
                    # 16 bytes a record and the region offsets of every launch
                    edits_readback_bytes=16 * T["edit_records"] + 8 * (T["regions"] + T["batches"]))
-    if evidence:
+    if o.evidence:
         res.update(evidence=True, evidence_readback_bytes=8 * T["edit_records"], one_strand_records=T.get("one_strand_records", 0))
     if gpu_decode:
         import hashlib
