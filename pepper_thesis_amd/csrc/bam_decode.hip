@@ -155,7 +155,8 @@ __global__ __launch_bounds__(WV) void k_bam_walk(pv_bam_decode_in a, Ws w) {
         }
     }
     // chunks past the linear-index bound were left out of the plan: only a walk that met its end before them is complete
-    if (!done && status == PV_BAMDEC_OK && a.iv_dropped[iv]) { status = PV_BAMDEC_PAST_PLAN; err_at = -1; }
+    if (status == PV_BAMDEC_OK) err_at = -1;   // (err_at followed the walk: no offender, no offset)
+    if (!done && status == PV_BAMDEC_OK && a.iv_dropped[iv]) status = PV_BAMDEC_PAST_PLAN;
     if (writer) {
         w.iv_nrec[iv] = (int32_t)n;
         w.iv_wstatus[iv] = status;

@@ -44,9 +44,49 @@ def ref_len(cigar):
     return sum(l for op, l in cigar if op in (0, 2, 3, 7, 8))
 
 
-def write_bam(path, refs, records, block_records=40, deflate=None):
-    """refs: [(name, length)]; records: dicts(tid,pos,mapq,flag,cigar[(op,len)],seq(str),qual(list),name,hp)
-    sorted by (tid,pos). Writes path and path+'.bai'. deflate: bytes -> raw DEFLATE stream of one block, instead of zlib's."""
+def record_aux(rec):
+    """the aux bytes of a record: rec['aux'] as given, else HP:C (rec['hp']) + NM:i + RG:Z; a CG:B,I tag behind either for rec['cg']"""
+    if rec.get("aux") is not None:
+        aux = bytes(rec["aux"])
+    else:
+        aux = b""
+        if rec.get("hp") is not None:
+            aux += b"HPC" + struct.pack("<B", rec["hp"])
+        aux += b"NMi" + struct.pack("<i", 3) + b"RGZgrp1\x00"
+    if rec.get("cg"):
+        cig = rec["cigar"]
+        aux += b"CGBI" + struct.pack("<I", len(cig)) + b"".join(struct.pack("<I", (l << 4) | op) for op, l in cig)
+    return aux
+
+
+def record_cigar(rec):
+    """the CIGAR in the record's own field: SAMv1 4.2.2, a CIGAR too long for the 16-bit count lives in the CG:B,I tag behind a
+    <l_seq>S<rlen>N placeholder (rec['cg'])"""
+    if rec.get("cg"):
+        return [(4, len(rec["seq"])), (3, ref_len(rec["cigar"]))]
+    return rec["cigar"]
+
+
+def record_bytes(rec):
+    """one alignment record as it lies in the uncompressed stream: block_size + body"""
+    seq = rec["seq"]
+    end = rec["pos"] + max(ref_len(rec["cigar"]), 1)
+    name = rec.get("name", "r").encode() + b"\x00"
+    packed = bytearray((len(seq) + 1) // 2)
+    for i, c in enumerate(seq):
+        packed[i >> 1] |= NT16_CODE[c] << (4 if i % 2 == 0 else 0)
+    cig_rec = record_cigar(rec)
+    body = struct.pack("<iiBBHHHIiii", rec["tid"], rec["pos"], len(name), rec["mapq"], reg2bin(rec["pos"], end) if rec["pos"] >= 0 else 4680,
+                       len(cig_rec), rec["flag"], len(seq), -1, -1, 0)
+    body += name + b"".join(struct.pack("<I", (l << 4) | op) for op, l in cig_rec) + bytes(packed) + bytes(rec["qual"]) + record_aux(rec)
+    return struct.pack("<I", len(body)) + body
+
+
+def write_bam(path, refs, records, block_records=40, deflate=None, block_bytes=None):
+    """refs: [(name, length)]; records: dicts(tid,pos,mapq,flag,cigar[(op,len)],seq(str),qual(list),name,hp,aux(bytes),cg)
+    sorted by (tid,pos). Writes path and path+'.bai'. deflate: bytes -> raw DEFLATE stream of one block, instead of zlib's.
+    block_bytes: blocks of exactly that many bytes that split records wherever the limit falls (tiny blocks: a record
+    straddles several), instead of block_records records per block."""
     text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % r for r in refs)
     hdr = b"BAM\x01" + struct.pack("<I", len(text)) + text.encode() + struct.pack("<I", len(refs))
     for name, ln in refs:
@@ -64,40 +104,26 @@ def write_bam(path, refs, records, block_records=40, deflate=None):
 
     n_in_block = 0
     for rec in records:
-        if n_in_block >= block_records:
+        if block_bytes is None and n_in_block >= block_records:
             flush()
             n_in_block = 0
-        cig = rec["cigar"]
-        seq = rec["seq"]
-        end = rec["pos"] + max(ref_len(cig), 1)
-        b = reg2bin(rec["pos"], end)
-        name = rec.get("name", "r").encode() + b"\x00"
-        packed = bytearray((len(seq) + 1) // 2)
-        for i, c in enumerate(seq):
-            packed[i >> 1] |= NT16_CODE[c] << (4 if i % 2 == 0 else 0)
-        aux = b""
-        if rec.get("hp") is not None:
-            aux += b"HPC" + struct.pack("<B", rec["hp"])
-        aux += b"NMi" + struct.pack("<i", 3) + b"RGZgrp1\x00"
-        cig_rec = cig
-        if rec.get("cg"):
-            # SAMv1 4.2.2: a CIGAR too long for the 16-bit count lives in the CG:B,I tag behind a <l_seq>S<rlen>N placeholder
-            cig_rec = [(4, len(seq)), (3, ref_len(cig))]
-            aux += b"CGBI" + struct.pack("<I", len(cig)) + b"".join(struct.pack("<I", (l << 4) | op) for op, l in cig)
-        body = struct.pack("<iiBBHHHIiii", rec["tid"], rec["pos"], len(name), rec["mapq"], b, len(cig_rec), rec["flag"], len(seq), -1, -1, 0)
-        body += name + b"".join(struct.pack("<I", (l << 4) | op) for op, l in cig_rec) + bytes(packed) + bytes(rec["qual"]) + aux
-        data = struct.pack("<I", len(body)) + body
-        if cur and len(cur) + len(data) > 0xFF00:  # a BGZF block holds at most 64 KiB: start the record in a fresh block
+        end = rec["pos"] + max(ref_len(rec["cigar"]), 1)
+        b = reg2bin(rec["pos"], end) if rec["pos"] >= 0 else 4680
+        data = record_bytes(rec)
+        if block_bytes is None and cur and len(cur) + len(data) > 0xFF00:  # a BGZF block holds at most 64 KiB: start the record in a fresh block
             flush()
             n_in_block = 0
         vbeg = (len(out) << 16) | len(cur)
         cur += data
-        while len(cur) > 0xFF00:                   # a record longer than a block spans blocks
-            head, rest = bytes(cur[:0xFF00]), cur[0xFF00:]
+        limit = 0xFF00 if block_bytes is None else block_bytes
+        while len(cur) > limit or (block_bytes is not None and len(cur) == limit):   # a record longer than a block spans blocks
+            head, rest = bytes(cur[:limit]), cur[limit:]
             out.extend(_bgzf_block(head, deflate))
             cur = bytearray(rest)
         n_in_block += 1
         vend = (len(out) << 16) | len(cur)
+        if rec["tid"] < 0:   # unplaced reads at the end of the file are not indexed
+            continue
         ix = index[rec["tid"]]
         ix["bins"].setdefault(b, []).append([vbeg, vend])
         for w in range(rec["pos"] >> 14, ((end - 1) >> 14) + 1):

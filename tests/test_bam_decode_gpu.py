@@ -74,68 +74,11 @@ def test_contig_end_start_at_zero_several_intervals_and_empty_ones(hip_ctx, file
 
 # ---- hand-made records ---------------------------------------------------------------------------------------------------
 
-def write_bam_aux(path, refs, records, block_bytes=0xFF00):
-    """bam_writer.write_bam with the aux bytes given per record (rec['aux']) and blocks of at most block_bytes bytes that
-    split records wherever the limit falls (tiny blocks: a record straddles several). bam_writer.py may not carry these two
-    options, so this is a copy of its write_bam: the header, the record body layout, the bin / linear-index bookkeeping and
-    the BAI serialisation (chunk merge, linear fill) are taken from there line for line and must follow any change made
-    there; only the aux bytes and the block cutting differ."""
-    text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % r for r in refs)
-    hdr = b"BAM\x01" + struct.pack("<I", len(text)) + text.encode() + struct.pack("<I", len(refs))
-    for name, ln in refs:
-        hdr += struct.pack("<I", len(name) + 1) + name.encode() + b"\x00" + struct.pack("<I", ln)
-    out = bytearray(bw._bgzf_block(hdr))
-    index = [dict(bins={}, linear={}) for _ in refs]
-    cur = bytearray()
-    for rec in records:
-        cig, seq = rec["cigar"], rec["seq"]
-        end = rec["pos"] + max(bw.ref_len(cig), 1)
-        b = bw.reg2bin(rec["pos"], end)
-        name = rec.get("name", "r").encode() + b"\x00"
-        packed = bytearray((len(seq) + 1) // 2)
-        for i, c in enumerate(seq):
-            packed[i >> 1] |= bw.NT16_CODE[c] << (4 if i % 2 == 0 else 0)
-        body = struct.pack("<iiBBHHHIiii", rec["tid"], rec["pos"], len(name), rec["mapq"], b, len(cig), rec["flag"], len(seq), -1, -1, 0)
-        body += name + b"".join(struct.pack("<I", (l << 4) | op) for op, l in cig) + bytes(packed) + bytes(rec["qual"]) + rec.get("aux", b"")
-        vbeg = (len(out) << 16) | len(cur)
-        cur += struct.pack("<I", len(body)) + body
-        while len(cur) >= block_bytes:
-            out.extend(bw._bgzf_block(bytes(cur[:block_bytes])))
-            cur = bytearray(cur[block_bytes:])
-        vend = (len(out) << 16) | len(cur)
-        ix = index[rec["tid"]]
-        ix["bins"].setdefault(b, []).append([vbeg, vend])
-        for w in range(rec["pos"] >> 14, ((end - 1) >> 14) + 1):
-            if w not in ix["linear"] or vbeg < ix["linear"][w]:
-                ix["linear"][w] = vbeg
-    if cur:
-        out.extend(bw._bgzf_block(bytes(cur)))
-    out += bw.BGZF_EOF
-    open(path, "wb").write(out)
-    bai = bytearray(b"BAI\x01" + struct.pack("<I", len(refs)))
-    for ix in index:
-        bai += struct.pack("<I", len(ix["bins"]))
-        for b, chunks in sorted(ix["bins"].items()):
-            merged = []
-            for c in chunks:
-                if merged and c[0] <= merged[-1][1]:
-                    merged[-1][1] = max(merged[-1][1], c[1])
-                else:
-                    merged.append(list(c))
-            bai += struct.pack("<II", b, len(merged)) + b"".join(struct.pack("<QQ", c[0], c[1]) for c in merged)
-        n_intv = (max(ix["linear"]) + 1) if ix["linear"] else 0
-        bai += struct.pack("<I", n_intv)
-        last = 0
-        for w in range(n_intv):
-            last = ix["linear"].get(w, last)
-            bai += struct.pack("<Q", last)
-    open(path + ".bai", "wb").write(bai)
-
-
 def _rec(pos, cigar, seq=None, **kw):
     qn = sum(l for op, l in cigar if op in (0, 1, 4, 7, 8))
     seq = seq if seq is not None else ("ACGTTGCA" * (qn // 8 + 1))[:qn]
-    r = dict(tid=0, pos=pos, mapq=60, flag=0, cigar=cigar, seq=seq, qual=[(7 * i + 3) % 60 for i in range(len(seq))], name="h%d" % pos)
+    r = dict(tid=0, pos=pos, mapq=60, flag=0, cigar=cigar, seq=seq, qual=[(7 * i + 3) % 60 for i in range(len(seq))], name="h%d" % pos,
+             aux=b"")
     r.update(kw)
     return r
 
@@ -180,7 +123,7 @@ def test_hand_made_records(hip_ctx, tmp_path):
     fa = _fasta(tmp_path)
     for blk, nm in ((0xFF00, "a"), (97, "tiny")):   # tiny blocks: every record straddles several block boundaries
         bam = str(tmp_path / (nm + ".bam"))
-        write_bam_aux(bam, [("c1", 6000)], recs, blk)
+        bw.write_bam(bam, [("c1", 6000)], recs, block_bytes=blk)
         for supp, mq in ((False, 5), (True, 0)):
             assert same_as_host(hip_ctx, bam, fa, [("c1", 1000, 2000)], mq, supp) >= 20
         assert same_as_host(hip_ctx, bam, fa, [("c1", 0, 500), ("c1", 1290, 1295), ("c1", 2100, 2300)], 0, True) > 3

@@ -132,7 +132,6 @@ def long_files(tmp_path_factory):
     """one contig of 60 kb in BGZF blocks of 256 bytes. A read of 600 bases at 500 skips 50 kb of the draft (an N operation):
     it is the first record over the index window three past region 0's, so the plan of the regions of window 0 ends two blocks
     past the block the read starts in, while its record (about 950 bytes) and the records behind it lie further on."""
-    from test_bam_decode_gpu import write_bam_aux
     build.build_io()
     tmp = tmp_path_factory.mktemp("plong")
     rng = np.random.default_rng(78)
@@ -140,12 +139,12 @@ def long_files(tmp_path_factory):
     bw.write_fasta(str(tmp / "d.fa"), [("c1", "".join(rng.choice(list("ACGT"), size=L)))])
     recs = [r for r in _reads(rng, 500, L, 0, 50, 600)]
     for r in recs:
-        r["flag"], r["hp"] = r["flag"] & 0x10, None
+        r["flag"], r["hp"], r["aux"] = r["flag"] & 0x10, None, b""
     long = dict(tid=0, pos=500, mapq=60, flag=0, cigar=[(0, 300), (3, 50_000), (0, 300)], seq="".join(rng.choice(list("ACGT"), size=600)),
-                qual=[30] * 600, name="skip50k")
+                qual=[30] * 600, name="skip50k", aux=b"")
     recs = sorted(recs + [long], key=lambda r: r["pos"])
     assert sum(1 for r in recs if 500 < r["pos"] < 1000) >= 2   # records behind the long one that region 0's walk has to reach
-    write_bam_aux(str(tmp / "r.bam"), [("c1", L)], recs, block_bytes=256)
+    bw.write_bam(str(tmp / "r.bam"), [("c1", L)], recs, block_bytes=256)
     np.savez(str(tmp / "model.npz"), **synth.make_weights_p2(31, 3.0))
     return tmp
 
