@@ -101,15 +101,16 @@ def walk_segment(A, B, a0, b0, n, m, Q=None, pair=0, segment=0):
     return ALIGNED, cnt, recs[::-1]
 
 
-def errors_pair(A, B, L, max_shift, Q=None, pair=0):
+def errors_pair(A, B, L, max_shift, Q=None, pair=0, walk=None):
     """A, B upper-cased; Q the assembly's raw Phred bytes or None -> (records, qhist [QBINS][4] or None, totals dict of
-    match / sub / ins / del with the anchors' matches, number of unaligned segments)"""
+    match / sub / ins / del with the anchors' matches, number of unaligned segments). walk: what stands in for walk_segment"""
+    walk = walk or walk_segment
     kept = R.chain(R.find_anchors(A, B, L, max_shift))
     recs, tot, unaligned = [], dict(match=0, sub=0, ins=0), 0
     tot["del"] = 0
     hist = None if Q is None else np.zeros((QBINS, 4), np.int64)
     for k, (a0, b0, n, m, anc) in enumerate(R.segments(len(A), len(B), kept)):
-        status, cnt, rs = walk_segment(A, B, a0, b0, n, m, Q, pair, k)
+        status, cnt, rs = walk(A, B, a0, b0, n, m, Q, pair, k)
         recs += rs
         tot["match"] += anc
         unaligned += status == UNALIGNED
@@ -124,11 +125,11 @@ def errors_pair(A, B, L, max_shift, Q=None, pair=0):
     return recs, hist, tot, unaligned
 
 
-def errors_batch(pairs, L, max_shift, quals=None):
+def errors_batch(pairs, L, max_shift, quals=None, walk=None):
     """-> (records as an int64 array [n, len(ERR_FIELDS)], pair_err_off, qhist [n_pairs][QBINS][4] or None)"""
     rows, off, hists = [], [0], []
     for p, (A, B) in enumerate(pairs):
-        recs, hist, _, _ = errors_pair(A, B, L, max_shift, None if quals is None else quals[p], p)
+        recs, hist, _, _ = errors_pair(A, B, L, max_shift, None if quals is None else quals[p], p, walk)
         rows += [[r[f] for f in ERR_FIELDS] for r in recs]
         off.append(len(rows))
         hists.append(hist)

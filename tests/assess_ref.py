@@ -138,15 +138,17 @@ def align_segment(A: bytes, B: bytes, a0: int, b0: int, n: int, m: int):
     return r
 
 
-def assess_pair(A: bytes, B: bytes, L: int, max_shift: int, pair: int = 0):
-    """A, B already upper-cased -> (list of segment dicts with SEG_FIELDS, totals dict with TOTAL_FIELDS)"""
+def assess_pair(A: bytes, B: bytes, L: int, max_shift: int, pair: int = 0, align=None):
+    """A, B already upper-cased -> (list of segment dicts with SEG_FIELDS, totals dict with TOTAL_FIELDS). align: what stands
+    in for align_segment (the limits cases write the record of a byte-equal segment directly)"""
+    align = align or align_segment
     found = find_anchors(A, B, L, max_shift)
     kept = chain(found)
     segs = []
     tot = {f: 0 for f in TOTAL_FIELDS}
     tot["anchors_found"], tot["anchors_kept"] = len(found), len(kept)
     for a0, b0, n, m, anc in segments(len(A), len(B), kept):
-        r = align_segment(A, B, a0, b0, n, m)
+        r = align(A, B, a0, b0, n, m)
         r.update(a_start=a0, b_start=b0, n_rows=n, n_cols=m, anchor=anc, pair=pair)
         segs.append(r)
         tot["segments"] += 1
@@ -163,11 +165,11 @@ def assess_pair(A: bytes, B: bytes, L: int, max_shift: int, pair: int = 0):
     return segs, tot
 
 
-def assess_batch(pairs, L: int, max_shift: int):
+def assess_batch(pairs, L: int, max_shift: int, align=None):
     """pairs: [(A, B)] upper-cased -> (seg array [n_seg, len(SEG_FIELDS)] int64, pair_seg_off, totals [n_pairs, 16] int64)"""
     rows, off, totals = [], [0], []
     for p, (A, B) in enumerate(pairs):
-        segs, tot = assess_pair(A, B, L, max_shift, p)
+        segs, tot = assess_pair(A, B, L, max_shift, p, align)
         rows += [[s[f] for f in SEG_FIELDS] for s in segs]
         off.append(len(rows))
         totals.append([tot[f] for f in TOTAL_FIELDS] + [0, 0])
