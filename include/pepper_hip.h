@@ -1086,6 +1086,69 @@ int pv_assess_errors(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, const 
                      int64_t* qhist, int64_t* counts);
 int64_t pv_assess_errors_scratch_bytes(int64_t n_pairs, const int64_t* a_off, int segment);
 
+/* ---- assess, placement: which truth contig, strand and interval an assembly contig lies on (`pepper assess --place`) -------
+ * pv_assess pairs contigs by the caller's word, in the truth's orientation, end to end. A real assembly's contigs have names
+ * of their own, either strand, and each covers a piece of a chromosome. This stage decides, from content alone, where each
+ * assembly contig belongs; the caller then orients the contig, slices the truth and hands the pair to pv_assess /
+ * pv_assess_errors as they are. No rearrangement is looked for: one interval per contig.
+ * A, a_off[n_asm+1]: the assembly contigs; B, b_off[n_truth+1]: the truth contigs; both with a..z upper-cased by the caller.
+ * step: a multiple of 32 in [32, 65536]; min_hits in [1, 65535]; contigs shorter than 2^31 bytes; n_truth at most
+ * PV_ASSESS_PLACE_MAX_TRUTH = 8192 (a workgroup tallies a contig's hits per truth contig and strand in LDS: 2 x 8192 uint32).
+ * Keys. K = PV_ASSESS_K = 32. A 32-mer of A, C, G, T only has a 64-bit key: two bits per byte, A=0, C=1, G=2, T=3, the first
+ *   byte in the highest bits; rc(x) is the key of its reverse complement. A 32-mer with any other byte has no key.
+ * Samples. For assembly contig p the sample positions are a = k * step, k = 0, 1, ..., while a + K <= n_A. A sample is tried
+ *   iff its 32-mer has a key x and x != rc(x) (a palindrome cannot tell the strand).
+ * Occurrences are counted over every truth contig t and every j with j + K <= n_B[t] whose 32-mer has a key: f(x) is the
+ *   number of (t, j) whose key is x, r(x) the number whose key is rc(x). A 32-mer never spans two truth contigs.
+ * Hits. A tried sample is a hit iff f + r = 1; its record is (t, s, j) with strand s = 0 if f = 1 and s = 1 if r = 1. Its
+ *   position in the oriented contig is a' = a for s = 0 and a' = n_A - K - a for s = 1. Two samples with the same key are two
+ *   samples, each a hit or not on its own.
+ * Decision. The contig's hits are counted per (t, s); the winner has the most, ties go to the smaller t, then to s = 0. With H
+ *   the winner's count and N the number of all hits of the contig, the status is PV_ASSESS_PLACED iff H >= min_hits and
+ *   2 H > N, else PV_ASSESS_UNPLACED.
+ * Interval of a placed contig. Among the winner's hits, first has the smallest a' and last the largest:
+ *   b_lo = clamp(j_first - a'_first, 0, n_B[t]), b_hi = clamp(j_last + (n_A - a'_last), 0, n_B[t]). If first != last and
+ *   j_last <= j_first, or if b_hi <= b_lo, the status is PV_ASSESS_MISPLACED: the hits agree on a contig and a strand but not
+ *   on an order. Such a contig is reported and never scored.
+ * Out: one pv_assess_placement per assembly contig. An unplaced contig has truth = strand = b_lo = b_hi = -1; a misplaced one
+ *   keeps what was computed. d_counts = {records written, status, first bad contig or -1, scratch bytes needed}.
+ *
+ * pv_assess_place_dev: DEVICE pointers; recs[n_asm] aligned to 8 bytes; scratch: scratch_bytes of device memory, 256-byte
+ * aligned, at least pv_assess_place_scratch_bytes() (the contigs' sample offsets, a directory of 4097 uint32, and 56 bytes per
+ * sample: two sorted table entries of key and tag, and per entry a count and a smallest position).
+ * Status: null pointers, negative sizes, a step or min_hits out of range are refused with PV_ERR_INVALID by the call itself.
+ * Offsets that decrease or a contig of 2^31 bytes or more are status PV_ERR_INVALID, d_counts[2] naming the first such contig
+ * (assembly contig p as p, truth contig t as n_asm + t). scratch_bytes below the need, or 2^30 samples or more, are status
+ * PV_ERR_LIMIT. More than PV_ASSESS_PLACE_MAX_TRUTH truth contigs, or a scratch that cannot hold even the sample offsets, are
+ * PV_ERR_LIMIT too, in d_counts and as the call's own return value. Under any status but PV_OK every record is poisoned (-1 in
+ * every field) and d_counts[0] = 0. With n_asm = 0 nothing is looked at: d_counts = {0, PV_OK, -1, 0}.
+ * Asynchronous on `stream`, no host read-back, no dependence on the launch geometry (the counts and minima are integer
+ * atomics). Launches: setup, keys, the sort, directory, the pass over the truth (workgroups of PV_ASSESS_PLACE_TILE truth
+ * bytes each), decision: 5 + the sort's 1 + m + m (m + 1) / 2 with m = max(0, ceil(log2(entries)) - 11), where entries is two
+ * per sample that scratch_bytes could hold (6 launches for a thousand samples, 26 for thirty thousand). */
+#define PV_ASSESS_PLACE_TILE 4096
+#define PV_ASSESS_PLACE_MAX_TRUTH 8192
+#define PV_ASSESS_PLACED 0
+#define PV_ASSESS_UNPLACED 1
+#define PV_ASSESS_MISPLACED 2
+typedef struct pv_assess_placement {   /* 40 bytes, little-endian */
+    int64_t b_lo, b_hi;                /* the interval [b_lo, b_hi) of truth contig `truth`, in its coordinates */
+    int32_t truth;                     /* index of the truth contig; -1 unless placed or misplaced */
+    int32_t strand;                    /* 0: as given, 1: reverse-complemented */
+    int32_t status;                    /* PV_ASSESS_PLACED / _UNPLACED / _MISPLACED */
+    int32_t tried, hits, agree;        /* samples tried, hits N, hits of the winner H */
+} pv_assess_placement;
+int pv_assess_place_dev(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, int64_t n_asm, const uint8_t* B,
+                        const int64_t* b_off, int64_t n_truth, int step, int min_hits, pv_assess_placement* recs, void* scratch,
+                        int64_t scratch_bytes, int64_t* d_counts, void* stream);
+/* HOST buffers in and out (a_off[0] = b_off[0] = 0; b_off holds one entry even with n_truth = 0); the scratch is the context's
+ * own. counts[4] as d_counts above; returns the status. The offsets are checked on the host, with the same status, counts and
+ * poison as the device form gives. */
+int pv_assess_place(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, int64_t n_asm, const uint8_t* B, const int64_t* b_off,
+                    int64_t n_truth, int step, int min_hits, pv_assess_placement* recs, int64_t* counts);
+/* bytes of scratch a call needs, from the HOST offsets of the assembly (negative: PV_ERR_INVALID) */
+int64_t pv_assess_place_scratch_bytes(int64_t n_asm, const int64_t* a_off, int step);
+
 /* bytes of device workspace the context currently holds (diagnostics) */
 int64_t pv_workspace_bytes(pv_ctx* ctx);
 /* library/ABI version: major*10000 + minor*100 + patch */

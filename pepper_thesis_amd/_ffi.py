@@ -78,6 +78,12 @@ PV_ASSESS_QBINS = 94
 PV_ASSESS_ERR_SUB = 1
 PV_ASSESS_ERR_INS = 2
 PV_ASSESS_ERR_DEL = 3
+# pv_assess_place
+PV_ASSESS_PLACE_TILE = 4096
+PV_ASSESS_PLACE_MAX_TRUTH = 8192
+PV_ASSESS_PLACED = 0
+PV_ASSESS_UNPLACED = 1
+PV_ASSESS_MISPLACED = 2
 
 PV_PLAN_P1_LSTM = 1
 PV_PLAN_P2_GRU = 2
@@ -208,6 +214,11 @@ class pv_assess_seg(C.Structure):
 class pv_assess_error(C.Structure):
     _fields_ = [("a_pos", C.c_int64), ("b_pos", C.c_int64), ("pair", C.c_int32), ("segment", C.c_int32), ("kind", C.c_uint8),
                 ("a_base", C.c_uint8), ("b_base", C.c_uint8), ("hp", C.c_uint8), ("qual", C.c_uint8), ("pad", C.c_uint8 * 3)]
+
+
+class pv_assess_placement(C.Structure):
+    _fields_ = [("b_lo", C.c_int64), ("b_hi", C.c_int64), ("truth", C.c_int32), ("strand", C.c_int32), ("status", C.c_int32),
+                ("tried", C.c_int32), ("hits", C.c_int32), ("agree", C.c_int32)]
 
 
 class pv_select_out(C.Structure):
@@ -399,6 +410,13 @@ SYMBOLS = [
      [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     ("pv_assess_errors_scratch_bytes", C.c_int64, [C.c_int64, C.c_void_p, C.c_int]),
+    ("pv_assess_place_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+      C.c_int64, C.c_void_p, C.c_void_p]),
+    ("pv_assess_place", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+      C.POINTER(C.c_int64)]),
+    ("pv_assess_place_scratch_bytes", C.c_int64, [C.c_int64, C.c_void_p, C.c_int]),
     ("pv_workspace_bytes", C.c_int64, [C.c_void_p]),
     ("pv_version", C.c_int, []),
 ]

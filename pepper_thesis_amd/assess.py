@@ -11,6 +11,12 @@ touched the band's rim) are the warning signs of a line. The reference has no co
 (<o>_assess.errors.tsv). -q FILE reads the qualities `polish --qualities` wrote for the assembly and tabulates, per contig and
 quality value, how many bases carry it and how many errors were charged to it (<o>_assess.calibration.tsv): predicted quality
 against observed error rate (the rule: include/pepper_hip.h, pv_assess_errors). The tool reports; it recommends no threshold.
+
+--place drops the pairing by name: one device call places every assembly contig on the truth by content - truth contig, strand
+and interval, from sampled 32-mers that occur once in the truth (the rule: include/pepper_hip.h, pv_assess_place). A placed
+contig is reverse-complemented if need be and scored, as above, against its interval of the truth; truth positions in every
+table are truth-contig coordinates, and the assembly positions and bases of a contig on the minus strand refer to the
+reverse-complemented contig (<o>_assess.placement.tsv says which those are). One interval per contig: no rearrangement search.
 """
 import math
 import os
@@ -22,6 +28,7 @@ import numpy as np
 
 MAX_CONTIG = 1 << 31
 DEFAULT_WORKSPACE = 4 << 30
+DEFAULT_PLACE_STEP, DEFAULT_MIN_HITS = 1024, 3
 TOTAL_FIELDS = ("segments", "aligned", "unaligned", "edge", "match", "sub", "ins", "del", "hp_ins", "hp_del", "unaligned_a",
                 "unaligned_b", "anchors_kept", "anchors_found")
 CONTIG_HEADER = ("#name\tstatus\tassembly_length\ttruth_length\taligned_columns\tmatches\tsubstitutions\tinsertions\tdeletions\t"
@@ -29,6 +36,7 @@ CONTIG_HEADER = ("#name\tstatus\tassembly_length\ttruth_length\taligned_columns\
                  "unaligned_truth_bases\tidentity\tQV\n")
 SEGMENT_HEADER = ("#name\tsegment\tassembly_start\tassembly_end\ttruth_start\ttruth_end\tstatus\tedge\tanchor_matches\tmatches\t"
                   "substitutions\tinsertions\tdeletions\thp_ins\thp_del\n")
+PLACEMENT_HEADER = "#name\tstatus\ttruth\tstrand\ttruth_start\ttruth_end\tsamples\thits\tagreeing\n"
 ERRORS_HEADER = "#name\tkind\tassembly_pos\ttruth_pos\tassembly_base\ttruth_base\thp\tqual\tsegment\n"
 CALIBRATION_HEADER = "#name\tqual\tbases\tsubstitutions\tinsertions\tdeletions\terrors\tcolumns\tobserved_QV\n"
 QBINS = 94
@@ -171,10 +179,11 @@ def assess_pairs_errors(ctx, pairs, quals, segment: int, max_shift: int, budget:
     return res
 
 
-def error_line(name: str, r) -> str:
+def error_line(name: str, r, shift: int = 0) -> str:
+    """shift: where the pair's truth begins in its truth contig"""
     def base(x):
         return chr(x) if x else "."
-    return "\t".join([name, KIND_NAME[int(r["kind"])], str(int(r["a_pos"])), str(int(r["b_pos"])), base(int(r["a_base"])),
+    return "\t".join([name, KIND_NAME[int(r["kind"])], str(int(r["a_pos"])), str(int(r["b_pos"]) + shift), base(int(r["a_base"])),
                       base(int(r["b_base"])), str(int(r["hp"])), "." if int(r["qual"]) == 255 else str(int(r["qual"])),
                       str(int(r["segment"]))]) + "\n"
 
@@ -245,48 +254,156 @@ def _tables(ctx, asm, truth, segment: int, max_shift: int, budget: int, errors: 
     for n in paired:
         if len(am[n]) >= MAX_CONTIG or len(tr[n]) >= MAX_CONTIG:
             raise AssessError("contig %s holds 2^31 bytes or more" % n)
-    pairs = [(upper(am[n]), upper(tr[n])) for n in paired]
-    if errors:
-        q = None if quals is None else [quals.get(n, np.zeros(0, np.uint8)) for n in paired]
-        res = dict(zip(paired, assess_pairs_errors(ctx, pairs, q, segment, max_shift, budget)))
-    else:
-        res = dict(zip(paired, assess_pairs(ctx, pairs, segment, max_shift, budget)))
-    err_txt, cal_txt, cal_total = [ERRORS_HEADER], [CALIBRATION_HEADER], np.zeros((QBINS, 4), np.int64)
-    zero = {f: 0 for f in TOTAL_FIELDS}
-    total, la_sum, lb_sum = dict(zero), 0, 0
-    contig, seg_txt = [CONTIG_HEADER], [SEGMENT_HEADER]
-    lone_asm = {n: ln for n, in_asm, ln in lone if in_asm}
+    rows = []
     for name, a in asm:
-        if name in lone_asm:
-            contig.append(contig_line(name, "unpaired", len(a), 0, zero))
+        if name in tr:
+            q = None if quals is None else quals.get(name, np.zeros(0, np.uint8))
+            rows.append((name, "paired", upper(a), upper(tr[name]), 0, q))
+        else:
+            rows.append((name, "unpaired", a, None, 0, None))
+    tail = [contig_line(name, "unpaired", 0, ln, ZERO_TOTALS) for name, in_asm, ln in lone if not in_asm]
+    return _score_rows(ctx, rows, tail, segment, max_shift, budget, errors, quals is not None)
+
+
+ZERO_TOTALS = {f: 0 for f in TOTAL_FIELDS}
+
+
+def _score_rows(ctx, rows, tail, segment: int, max_shift: int, budget: int, errors: bool, with_quals: bool):
+    """rows: one per assembly contig, in order: (name, status, assembly, truth or None, truth offset, qualities or None). A row
+    with a truth is scored against it (bytes already upper-cased, oriented and sliced) and the truth offset is added to its
+    truth positions; a row without one gives a line of lengths only. tail: the contig lines behind the assembly's. -> as
+    error_tables (without errors: as tables)"""
+    scored = [r for r in rows if r[3] is not None]
+    pairs = [(a, b) for _, _, a, b, _, _ in scored]
+    if errors:
+        res = assess_pairs_errors(ctx, pairs, [r[5] for r in scored] if with_quals else None, segment, max_shift, budget)
+    else:
+        res = assess_pairs(ctx, pairs, segment, max_shift, budget)
+    res = iter(res)
+    err_txt, cal_txt, cal_total = [ERRORS_HEADER], [CALIBRATION_HEADER], np.zeros((QBINS, 4), np.int64)
+    total, la_sum, lb_sum = dict(ZERO_TOTALS), 0, 0
+    contig, seg_txt = [CONTIG_HEADER], [SEGMENT_HEADER]
+    for name, status, a, b, shift, _ in rows:
+        if b is None:
+            contig.append(contig_line(name, status, len(a), 0, ZERO_TOTALS))
             continue
-        segs, t = res[name][:2]
+        r = next(res)
+        segs, t = r[:2]
         if errors:
-            err_txt += [error_line(name, r) for r in res[name][2]]
-            if quals is not None:
-                cal_txt.append(calibration_lines(name, res[name][3]))
-                cal_total += res[name][3]
-        contig.append(contig_line(name, "paired", len(a), len(tr[name]), t))
+            err_txt += [error_line(name, e, shift) for e in r[2]]
+            if with_quals:
+                cal_txt.append(calibration_lines(name, r[3]))
+                cal_total += r[3]
+        contig.append(contig_line(name, status, len(a), len(b), t))
         la_sum += len(a)
-        lb_sum += len(tr[name])
+        lb_sum += len(b)
         for f in TOTAL_FIELDS:
             total[f] += t[f]
-        for k, s in enumerate(segs):
-            a0, b0 = int(s["a_start"]), int(s["b_start"])
-            vals = (k, a0, a0 + int(s["n_rows"]), b0, b0 + int(s["n_cols"]), "unaligned" if int(s["status"]) else "aligned",
-                    int(s["edge"]), int(s["anchor"]), int(s["match"]), int(s["sub"]), int(s["ins"]), int(s["del"]), int(s["hp_ins"]),
-                    int(s["hp_del"]))
+        for k, sg in enumerate(segs):
+            a0, b0 = int(sg["a_start"]), int(sg["b_start"]) + shift
+            vals = (k, a0, a0 + int(sg["n_rows"]), b0, b0 + int(sg["n_cols"]), "unaligned" if int(sg["status"]) else "aligned",
+                    int(sg["edge"]), int(sg["anchor"]), int(sg["match"]), int(sg["sub"]), int(sg["ins"]), int(sg["del"]),
+                    int(sg["hp_ins"]), int(sg["hp_del"]))
             seg_txt.append("\t".join([name] + [str(v) for v in vals]) + "\n")
-    for name, in_asm, ln in lone:
-        if not in_asm:
-            contig.append(contig_line(name, "unpaired", 0, ln, zero))
+    contig += tail
     contig.append(contig_line("TOTAL", "total", la_sum, lb_sum, total))
     if not errors:
         return "".join(contig), "".join(seg_txt), total
-    if quals is None:
+    if not with_quals:
         return "".join(contig), "".join(seg_txt), total, "".join(err_txt), None, None
     cal_txt.append(calibration_lines("TOTAL", cal_total))
     return "".join(contig), "".join(seg_txt), total, "".join(err_txt), "".join(cal_txt), cal_total
+
+
+# ---- --place: contigs placed on the truth by content (the rule: include/pepper_hip.h, pv_assess_place) ------------------------
+
+def check_place_options(step: int, min_hits: int) -> None:
+    if not (32 <= step <= 65536 and step % 32 == 0):
+        raise AssessError("--place_step %d: must be a multiple of 32 in [32, 65536]" % step)
+    if not 1 <= min_hits <= 65535:
+        raise AssessError("--min_hits %d: must lie in [1, 65535]" % min_hits)
+
+
+_COMPLEMENT = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+def revcomp(seq: bytes) -> bytes:
+    """the reverse complement of an upper-cased sequence; bytes other than A, C, G, T keep their value"""
+    return bytes(seq).translate(_COMPLEMENT)[::-1]
+
+
+def place_rows(ctx, asm, truth, step: int, min_hits: int, quals=None):
+    """one placement call for the whole assembly against the whole truth -> (the rows _score_rows takes, the placement records).
+    A placed contig is reverse-complemented if it lies on the minus strand (its qualities reversed with it) and set against
+    the truth's bytes [b_lo, b_hi); an unplaced or misplaced one gives a line of lengths only."""
+    from . import _ffi
+    if len(truth) > _ffi.PV_ASSESS_PLACE_MAX_TRUTH:
+        raise AssessError("the truth holds %d contigs: --place takes at most %d" % (len(truth), _ffi.PV_ASSESS_PLACE_MAX_TRUTH))
+    for n, seq in list(asm) + list(truth):
+        if len(seq) >= MAX_CONTIG:
+            raise AssessError("contig %s holds 2^31 bytes or more" % n)
+    A, B = [upper(seq) for _, seq in asm], [upper(seq) for _, seq in truth]
+    recs = ctx.assess_place(A, B, step, min_hits)
+    rows = []
+    for (name, _), a, r in zip(asm, A, recs):
+        status = int(r["status"])
+        if status != _ffi.PV_ASSESS_PLACED:
+            rows.append((name, "misplaced" if status == _ffi.PV_ASSESS_MISPLACED else "unplaced", a, None, 0, None))
+            continue
+        minus, lo, hi = int(r["strand"]) == 1, int(r["b_lo"]), int(r["b_hi"])
+        q = None if quals is None else quals.get(name, np.zeros(0, np.uint8))
+        if minus:
+            a, q = revcomp(a), (None if q is None else np.ascontiguousarray(q[::-1]))
+        rows.append((name, "paired", a, B[int(r["truth"])][lo:hi], lo, q))
+    return rows, recs
+
+
+def placement_text(asm, truth, recs) -> str:
+    """<o>_assess.placement.tsv: one line per assembly contig. For a contig on the minus strand every assembly position and
+    base of the other tables refers to the reverse-complemented contig."""
+    from . import _ffi
+    word = {_ffi.PV_ASSESS_PLACED: "placed", _ffi.PV_ASSESS_UNPLACED: "unplaced", _ffi.PV_ASSESS_MISPLACED: "misplaced"}
+    out = [PLACEMENT_HEADER]
+    for (name, _), r in zip(asm, recs):
+        t = int(r["truth"])
+        where = [truth[t][0], "-" if int(r["strand"]) else "+", str(int(r["b_lo"])), str(int(r["b_hi"]))] if t >= 0 else ["."] * 4
+        out.append("\t".join([name, word[int(r["status"])]] + where + [str(int(r[f])) for f in ("tried", "hits", "agree")]) + "\n")
+    return "".join(out)
+
+
+def truth_cover(truth, recs) -> Tuple[int, int]:
+    """-> (truth bases that no placed interval covers, truth bases that more than one covers)"""
+    from . import _ffi
+    events = {}
+    for r in recs:
+        if int(r["status"]) == _ffi.PV_ASSESS_PLACED:
+            events.setdefault(int(r["truth"]), []).extend([(int(r["b_lo"]), 1), (int(r["b_hi"]), -1)])
+    bare = twice = 0
+    for t, (_, seq) in enumerate(truth):
+        depth, at, once = 0, 0, 0
+        for x, d in sorted(events.get(t, [])):
+            once += x - at if depth >= 1 else 0
+            twice += x - at if depth >= 2 else 0
+            depth, at = depth + d, x
+        bare += len(seq) - once
+    return bare, twice
+
+
+def place_tables(ctx, asm, truth, step: int, min_hits: int, segment: int, max_shift: int, errors: bool = False, quals=None,
+                 budget: int = DEFAULT_WORKSPACE, label: str = "assembly"):
+    """--place: -> (what error_tables gives, or without errors and quals what tables gives) + (text of the placement table,)"""
+    from . import _ffi
+    rows, recs = place_rows(ctx, asm, truth, step, min_hits, quals)
+    for (name, _), r in zip(asm, recs):
+        if int(r["status"]) != _ffi.PV_ASSESS_PLACED:
+            log("assess: contig %s of the %s is %s: %d samples tried, %d hits, %d agreeing" % (
+                name, label, "misplaced" if int(r["status"]) == _ffi.PV_ASSESS_MISPLACED else "unplaced", int(r["tried"]),
+                int(r["hits"]), int(r["agree"])))
+    if all(b is None for _, _, _, b, _, _ in rows):
+        raise AssessError("no contig of the %s could be placed on the truth" % label)
+    bare, twice = truth_cover(truth, recs)
+    log("assess: truth: %d bases lie in no placed interval of the %s, %d in more than one" % (bare, label, twice))
+    return _score_rows(ctx, rows, [], segment, max_shift, budget, errors, quals is not None) + (placement_text(asm, truth, recs),)
 
 
 def write_text(path: str, text: str) -> None:
@@ -312,6 +429,12 @@ def run(args) -> int:
     try:
         check_options(int(args.segment), int(args.max_shift))
         want_errors, fastq = bool(getattr(args, "errors", False)), getattr(args, "fastq", None)
+        place, step, min_hits = bool(getattr(args, "place", False)), getattr(args, "place_step", None), getattr(args, "min_hits", None)
+        if not place and (step is not None or min_hits is not None):
+            raise AssessError("--place_step and --min_hits belong to --place")
+        step, min_hits = int(DEFAULT_PLACE_STEP if step is None else step), int(DEFAULT_MIN_HITS if min_hits is None else min_hits)
+        if place:
+            check_place_options(step, min_hits)
         for what, p in (("assembly", args.assembly), ("truth", args.truth), ("draft", args.draft)):
             if p is not None and not os.path.isfile(p):
                 raise AssessError("cannot find the %s FASTA %s" % (what, p))
@@ -321,21 +444,32 @@ def run(args) -> int:
         draft = read_fasta(args.draft) if args.draft else None
         quals = read_fastq(fastq, asm) if fastq is not None else None
         for label, seqs in (("assembly", asm), ("draft", draft)):
-            for n, in_asm, _ in (pair_names(seqs, truth)[1] if seqs is not None else ()):
+            for n, in_asm, _ in (pair_names(seqs, truth)[1] if seqs is not None and not place else ()):
                 log("assess: contig %s is only in the %s FASTA: unpaired" % (n, label if in_asm else "truth"))
         from . import runtime
         ctx = runtime.Context(int(args.device_id))
         try:
-            err_txt = cal_txt = cal_total = draft_err_txt = None
-            if want_errors or quals is not None:
+            err_txt = cal_txt = cal_total = draft_err_txt = place_txt = draft_place_txt = None
+            draft_txt = draft_total = None
+            if place:
+                seg, shift = int(args.segment), int(args.max_shift)
+                if want_errors or quals is not None:
+                    contig_txt, seg_txt, total, err_txt, cal_txt, cal_total, place_txt = place_tables(
+                        ctx, asm, truth, step, min_hits, seg, shift, True, quals)
+                else:
+                    contig_txt, seg_txt, total, place_txt = place_tables(ctx, asm, truth, step, min_hits, seg, shift)
+                if draft is not None:
+                    r = place_tables(ctx, draft, truth, step, min_hits, seg, shift, want_errors, label="draft")
+                    draft_txt, draft_total, draft_place_txt = r[0], r[2], r[-1]
+                    draft_err_txt = r[3] if want_errors else None
+            elif want_errors or quals is not None:
                 contig_txt, seg_txt, total, err_txt, cal_txt, cal_total = error_tables(ctx, asm, truth, int(args.segment),
                                                                                        int(args.max_shift), quals)
             else:
                 contig_txt, seg_txt, total = tables(ctx, asm, truth, int(args.segment), int(args.max_shift))
-            draft_txt = draft_total = None
-            if draft is not None and want_errors:
+            if draft is not None and want_errors and not place:
                 draft_txt, _, draft_total, draft_err_txt = error_tables(ctx, draft, truth, int(args.segment), int(args.max_shift))[:4]
-            elif draft is not None:
+            elif draft is not None and not place:
                 draft_txt, _, draft_total = tables(ctx, draft, truth, int(args.segment), int(args.max_shift))
         finally:
             ctx.close()
@@ -347,6 +481,10 @@ def run(args) -> int:
         os.makedirs(d, exist_ok=True)
     write_text(args.output + "_assess.tsv", contig_txt)
     write_text(args.output + "_assess.segments.tsv", seg_txt)
+    if place_txt is not None:
+        write_text(args.output + "_assess.placement.tsv", place_txt)
+    if draft_place_txt is not None:
+        write_text(args.output + "_assess_draft.placement.tsv", draft_place_txt)
     if want_errors:
         write_text(args.output + "_assess.errors.tsv", err_txt)
         if draft_err_txt is not None:

@@ -26,12 +26,12 @@
 //   k_as_epoison  under PV_ERR_INVALID / PV_ERR_LIMIT: 0xFF over errs, pair_err_off and qhist
 #include <algorithm>
 
+#include "assess_scan.hpp"
 #include "pv_common.hpp"
 
 namespace {
 
 constexpr int AS_K = PV_ASSESS_K, AS_W = PV_ASSESS_W, AS_DMAX = PV_ASSESS_MAX_DIFF;
-constexpr int AS_THREADS = 256;
 constexpr uint32_t AS_INF = 0xF0000000u;   // above every distance (< 2^31 + 128); + 129 still fits
 enum { DIR_DIAG = 0, DIR_UP = 1, DIR_LEFT = 2 };
 
@@ -41,7 +41,6 @@ struct Anchor { int64_t a, b; };            // a < 0: slot without an anchor
 // the scratch area: offsets in bytes, all multiples of 256
 struct Layout { int64_t slot_off, pair_cnt, anchors, segs, dirs, err_cnt, err_off, qpart, total; };
 constexpr int AS_QTAB = PV_ASSESS_QBINS * 4;   // a slot's partial table: uint32 {bases, sub, ins, del} per quality
-__host__ __device__ inline int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 // with_err: the per-slot error counts and offsets and the partial quality tables of pv_assess_errors_dev, behind the rest
 __host__ __device__ inline Layout as_layout(int64_t n_pairs, int64_t slots, int64_t total_a, int with_err) {
     Layout y;
@@ -91,38 +90,6 @@ __device__ inline int64_t pair_of_slot(const int64_t* slot_off, int64_t n_pairs,
         if (slot_off[mid] <= s) lo = mid; else hi = mid - 1;
     }
     return lo;
-}
-
-template <typename T>
-__device__ inline T wave_sum(T v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// one block: exclusive scan of f(p) over p < n into out[0..n] (out[n] = the sum); returns the sum to every thread
-template <typename F>
-__device__ inline int64_t block_scan_to(int64_t n, int64_t* out, int64_t* lds, F f) {
-    const int64_t per = (n + AS_THREADS - 1) / AS_THREADS;
-    const int64_t k0 = min(n, (int64_t)threadIdx.x * per), k1 = min(n, k0 + per);
-    int64_t s = 0;
-    for (int64_t k = k0; k < k1; k++) s += f(k);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int64_t x = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) lds[w] = x;
-    __syncthreads();
-    int64_t off = 0, sum = 0;
-    for (int i = 0; i < AS_THREADS / 64; i++) { off += i < w ? lds[i] : 0; sum += lds[i]; }
-    __syncthreads();
-    off += x - s;
-    for (int64_t k = k0; k < k1; k++) { out[k] = off; off += f(k); }
-    if (threadIdx.x == 0) out[n] = sum;
-    return sum;
 }
 
 __global__ __launch_bounds__(AS_THREADS) void k_as_setup(Args g) {

@@ -76,7 +76,8 @@ def assess_parser(ap=None):
     ap.add_argument("-a", "--assembly", type=str, required=True, help="FASTA of the assembly to score (the polished one)")
     ap.add_argument("-t", "--truth", type=str, required=True,
                     help="FASTA of the true sequence. Contigs are paired by name, in the same orientation, and taken to be "
-                         "colinear: no reverse complement and no rearrangement is looked for")
+                         "colinear: no reverse complement and no rearrangement is looked for (--place drops the names and "
+                         "finds contig, strand and interval by content)")
     ap.add_argument("-o", "--output", type=str, required=True,
                     help="output prefix: <output>_assess.tsv (one line per contig and TOTAL) and <output>_assess.segments.tsv "
                          "(one line per segment); parent directories are created")
@@ -95,6 +96,15 @@ def assess_parser(ap=None):
                     help="bases between anchors, a multiple of 32 in [256, 65536]; the windowed error track has this resolution")
     ap.add_argument("--max_shift", type=int, default=8192,
                     help="how far from its proportional place an anchor is searched in the truth, in [32, 1048576]")
+    ap.add_argument("--place", action="store_true", default=False,
+                    help="do not pair contigs by name: place every assembly contig on the truth by content (which truth contig, "
+                         "which strand, which interval, from 32-mers that occur once in the truth), reverse-complement it if "
+                         "need be and score it against that interval; <output>_assess.placement.tsv lists the placements. One "
+                         "interval per contig, no rearrangement search")
+    ap.add_argument("--place_step", type=int, default=None,
+                    help="with --place: bases between the sampled 32-mers, a multiple of 32 in [32, 65536] (default 1024)")
+    ap.add_argument("--min_hits", type=int, default=None,
+                    help="with --place: the fewest agreeing unique 32-mers that place a contig, in [1, 65535] (default 3)")
     ap.add_argument("-d_id", "--device_id", type=int, default=0, help="the device")
     return ap
 

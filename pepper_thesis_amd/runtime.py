@@ -778,6 +778,42 @@ class Context:
             break
         return segs[:int(counts[0])], seg_off, totals, errs[:int(counts[4])], err_off, qhist
 
+    def assess_place_scratch_bytes(self, a_off: np.ndarray, step: int) -> int:
+        """bytes of scratch pv_assess_place_dev needs for an assembly with these (host) offsets"""
+        ao = np.ascontiguousarray(a_off, np.int64)
+        n = int(self.lib.pv_assess_place_scratch_bytes(len(ao) - 1, _ffi.ptr(ao), int(step)))
+        if n < 0:
+            raise _ffi.PepperHipError(n, "assess place: bad offsets or step")
+        return n
+
+    def assess_place_dev(self, d_a: int, d_a_off: int, n_asm: int, d_b: int, d_b_off: int, n_truth: int, step: int, min_hits: int,
+                         d_recs: int, d_scratch: int, scratch_bytes: int, d_counts: int, stream: int = 0):
+        """asynchronous, device-resident pv_assess_place_dev: every array is a device pointer; {records, status, first bad contig
+        or -1, scratch needed} in d_counts. Under a status other than PV_OK the records hold -1 in every field."""
+        _ffi.check(self.lib.pv_assess_place_dev(self.handle, d_a or None, d_a_off or None, int(n_asm), d_b or None, d_b_off or None,
+                                                int(n_truth), int(step), int(min_hits), d_recs or None, d_scratch or None,
+                                                int(scratch_bytes), d_counts, stream or None))
+
+    def assess_place(self, asm, truth, step: int = 1024, min_hits: int = 3, counts=None, out=None):
+        """host-buffer pv_assess_place of [assembly contig bytes] on [truth contig bytes], both upper-cased -> a numpy record
+        array of pv_assess_placement [len(asm)]. counts: optional ctypes int64[4]; out: an optional record array that receives
+        the records, also when the call raises."""
+        n, m = len(asm), len(truth)
+        a_off = np.zeros(n + 1, np.int64)
+        b_off = np.zeros(m + 1, np.int64)
+        a_off[1:] = np.cumsum([len(a) for a in asm])
+        b_off[1:] = np.cumsum([len(b) for b in truth])
+        A = np.frombuffer(b"".join(bytes(a) for a in asm) or b"\0", np.uint8)   # (never a null pointer: one unread byte)
+        B = np.frombuffer(b"".join(bytes(b) for b in truth) or b"\0", np.uint8)
+        if out is None:
+            out = np.zeros(n, np.dtype(_ffi.pv_assess_placement))
+        assert out.dtype.itemsize == 40 and len(out) == n
+        if counts is None:
+            counts = (C.c_int64 * 4)()
+        _ffi.check(self.lib.pv_assess_place(self.handle, _ffi.ptr(A), _ffi.ptr(a_off), n, _ffi.ptr(B), _ffi.ptr(b_off), m, int(step),
+                                            int(min_hits), _ffi.ptr(out) if n else None, counts))
+        return out
+
     def profile_begin(self, only: str = None):
         """bracket every kernel launch of this context with HIP events (only: just the kernels whose profile name starts
         with it - two events per launch put a few microseconds between kernels)"""
