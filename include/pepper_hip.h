@@ -1149,6 +1149,78 @@ int pv_assess_place(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, int64_t
 /* bytes of scratch a call needs, from the HOST offsets of the assembly (negative: PV_ERR_INVALID) */
 int64_t pv_assess_place_scratch_bytes(int64_t n_asm, const int64_t* a_off, int step);
 
+/* ---- kmer_qv: score an assembly by the support of its k-mers in the reads (`pepper kmer_qv`) ---------------------------------
+ * Where no truth exists, a k-mer of the assembly that no read (or too few reads) contains is taken to be an error; from the
+ * share of such k-mers follow an error rate and a QV, and their positions say where to look (the rule of Merqury and yak). The
+ * reference has no counterpart.
+ * Keys. k is odd, PV_KMER_MIN_K = 11 <= k <= PV_KMER_MAX_K = 31 (an odd k-mer is never its own reverse complement). A k-mer of
+ *   upper-case A, C, G, T has a 2k-bit key: A=0, C=1, G=2, T=3, the first byte in the highest bits; rc(x) is the key of its
+ *   reverse complement and canon(x) = min(x, rc(x)). A k-mer holding any other byte has no key; lower case is "other" (the
+ *   caller upper-cases the assembly, as for pv_assess). A k-mer never spans two assembly contigs and never spans two reads.
+ * Table. One entry per assembly position (p, i) with i + k <= n_p whose k-mer has a key. Duplicates, within a contig, across
+ *   contigs or on the other strand, are entries of their own; each reports the full count of its canonical key.
+ * Count. c(p, i) = min(cap, number of (read r, offset j) with j + k <= len_r whose k-mer has a key with the same canonical
+ *   form), summed over every counting call made on the table since it was built; 1 <= cap <= PV_KMER_MAX_CAP = 2^30. The
+ *   counters are integer atomics, and one that has reached cap is left alone (it cannot wrap): the value is exactly the one
+ *   above, whatever the tile size, the workgroup count or the order of the calls. A position with i + k <= n_p whose k-mer has
+ *   no key reports PV_KMER_NO_KEY.
+ * Support. A keyed position is unsupported iff c < min_count, 1 <= min_count <= cap. The summary gives
+ *   contig_counts int64 [n_asm][3] = {keyed positions, unsupported positions, positions without a key};
+ *   segs: one int64 per `segment` bases of every contig (ceil(n_p / segment) of them, contig p's from seg_off[p]; segment a
+ *     multiple of 32 in [32, 65536]): the unsupported positions that start in that segment;
+ *   runs int64 [run_capacity][3] = {contig, first, last}: the maximal stretches of consecutive unsupported positions of one
+ *     contig, in contig order, then by position; a position without a key ends a run;
+ *   hist int64 [PV_KMER_HIST = 256]: keyed positions by count, hist[255] for c >= 255;
+ *   pos_counts uint32 [summed assembly length], optional: c by flat position, PV_KMER_NO_KEY also for the last k - 1 bytes of
+ *     a contig, which start no k-mer.
+ *
+ * pv_kmer_table_build_dev: DEVICE pointers. A, a_off[n_asm+1]: the assembly; table: table_bytes of device memory, 256-byte
+ * aligned, at least pv_kmer_table_bytes() (a head, a directory of 4097 uint32 over the keys' own top 12 bits, 20 bytes per
+ * assembly byte - sorted key, position, counter, gathered count - and four int64 per 2048 bytes for the run compaction).
+ * d_counts int64[4] = {keyed entries, status, first bad contig or -1, table bytes needed}. Launches: setup, keys, the sort
+ * (bitonic, spans of PV_KMER_SORT_SPAN entries in LDS: 1 + m + m (m + 1) / 2 launches with m = max(0, ceil(log2(entries)) -
+ * 11), entries being the positions table_bytes could hold), directory.
+ * pv_kmer_count_reads_dev: bases and base_off[n_reads+1] as pv_batch_in has them (a batch staged with pv_upload_batch can be
+ * passed as it lies), n_bases the bytes `bases` holds, below 2^31: nothing outside them is read whatever the offsets hold. One
+ * launch, workgroups of PV_KMER_TILE read bytes. On a table whose build did not end PV_OK nothing is counted.
+ * pv_kmer_support_dev: a_off, n_asm as given to the build. d_counts int64[8] = {runs written, status, runs needed, segment
+ * slots needed, summed assembly length (0 if the offsets decrease or it is 2^31 or more), 0, 0, 0}. Seven launches; the run list is a flag-and-scan
+ * compaction, so it is ordered and takes no global atomics. May be called again after further counting calls.
+ * Status. Null pointers and scalars out of range (k, cap, min_count, segment, negative sizes) are refused with PV_ERR_INVALID
+ * by the call itself. Build: offsets that decrease are status PV_ERR_INVALID, d_counts[2] naming the first such contig; a
+ * summed length of 2^31 or more, or table_bytes below the need, are PV_ERR_LIMIT with the need in d_counts[3] (a table too
+ * small for its head is PV_ERR_LIMIT as the call's own return value, too). Support: a table that was not built with PV_OK or
+ * that does not belong to these offsets, and min_count above the table's cap, are PV_ERR_INVALID; seg_capacity below the need
+ * is PV_ERR_LIMIT. Under any of these every output of the summary holds -1 in every field (pos_counts PV_KMER_NO_KEY, over the
+ * summed length where the offsets give one). PV_ERR_CAPACITY when run_capacity is below the runs needed: d_counts[0] = 0,
+ * d_counts[2] holds the need, no run record is written and every other output is valid. Empty input (n_asm = 0, no reads) is
+ * PV_OK with zero counts. Asynchronous on `stream`, no host read-back, capturable as one linear chain. */
+#define PV_KMER_MIN_K 11
+#define PV_KMER_MAX_K 31
+#define PV_KMER_MAX_CAP (1 << 30)
+#define PV_KMER_TILE 4096
+#define PV_KMER_SORT_SPAN 2048
+#define PV_KMER_HIST 256
+#define PV_KMER_NO_KEY 0xFFFFFFFFu
+int pv_kmer_table_build_dev(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, int64_t n_asm, int k, int64_t cap, void* table,
+                            int64_t table_bytes, int64_t* d_counts, void* stream);
+int pv_kmer_count_reads_dev(pv_ctx* ctx, void* table, int64_t table_bytes, const uint8_t* bases, const int64_t* base_off,
+                            int64_t n_reads, int64_t n_bases, void* stream);
+int pv_kmer_support_dev(pv_ctx* ctx, void* table, int64_t table_bytes, const int64_t* a_off, int64_t n_asm, int64_t min_count,
+                        int segment, int64_t* contig_counts, int64_t* seg_off, int64_t seg_capacity, int64_t* segs,
+                        int64_t run_capacity, int64_t* runs, int64_t* hist, uint32_t* pos_counts, int64_t* d_counts, void* stream);
+/* HOST buffers in and out (a_off[0] = base_off[0] = 0; base_off holds one entry even with n_reads = 0): build, count this one
+ * batch of reads, summarise; the table is the context's own. counts int64[8] = {runs written, status, runs needed, segment
+ * slots needed, keyed entries, first bad contig or -1, table bytes needed, 0}; returns the status. The offsets are checked on
+ * the host, with the status and the poison the device forms give (pos_counts is then left as it was). On PV_ERR_CAPACITY
+ * `runs` is left as it was and every other output is filled. */
+int pv_kmer_support(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, int64_t n_asm, const uint8_t* bases,
+                    const int64_t* base_off, int64_t n_reads, int k, int64_t cap, int64_t min_count, int segment,
+                    int64_t* contig_counts, int64_t* seg_off, int64_t seg_capacity, int64_t* segs, int64_t run_capacity,
+                    int64_t* runs, int64_t* hist, uint32_t* pos_counts, int64_t* counts);
+/* bytes of table an assembly needs, from its HOST offsets (negative: PV_ERR_INVALID) */
+int64_t pv_kmer_table_bytes(int64_t n_asm, const int64_t* a_off);
+
 /* bytes of device workspace the context currently holds (diagnostics) */
 int64_t pv_workspace_bytes(pv_ctx* ctx);
 /* library/ABI version: major*10000 + minor*100 + patch */

@@ -84,6 +84,14 @@ PV_ASSESS_PLACE_MAX_TRUTH = 8192
 PV_ASSESS_PLACED = 0
 PV_ASSESS_UNPLACED = 1
 PV_ASSESS_MISPLACED = 2
+# pv_kmer_support
+PV_KMER_MIN_K = 11
+PV_KMER_MAX_K = 31
+PV_KMER_MAX_CAP = 1 << 30
+PV_KMER_TILE = 4096
+PV_KMER_SORT_SPAN = 2048
+PV_KMER_HIST = 256
+PV_KMER_NO_KEY = 0xFFFFFFFF
 
 PV_PLAN_P1_LSTM = 1
 PV_PLAN_P2_GRU = 2
@@ -417,6 +425,17 @@ SYMBOLS = [
      [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
       C.POINTER(C.c_int64)]),
     ("pv_assess_place_scratch_bytes", C.c_int64, [C.c_int64, C.c_void_p, C.c_int]),
+    ("pv_kmer_table_build_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("pv_kmer_count_reads_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    ("pv_kmer_support_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pv_kmer_support", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int,
+      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    ("pv_kmer_table_bytes", C.c_int64, [C.c_int64, C.c_void_p]),
     ("pv_workspace_bytes", C.c_int64, [C.c_void_p]),
     ("pv_version", C.c_int, []),
 ]

@@ -6,6 +6,7 @@
   call_consensus  image files -> prediction HDF5 files         (polish_steps.call_consensus_run)
   stitch          prediction files -> polished FASTA           (polish_steps.stitch_run)
   assess          polished FASTA + truth FASTA -> identity, QV and error tables, on the device (assess.run)
+  kmer_qv         polished FASTA + BAM + draft -> reference-free k-mer QV and where the unsupported k-mers lie (kmer_qv.run)
 
 A program of its own, as in the reference: its `make_images` is the polisher's, not the variant caller's sub-command of the
 same name (`python -m pepper_thesis_amd make_images`). download_models and torch_stat are not part of this build.
@@ -109,6 +110,43 @@ def assess_parser(ap=None):
     return ap
 
 
+KMER_QV_IS_NOT = ("What it is not: an error that the reads share is supported and invisible (ONT homopolymer lengths are the main "
+                  "case); a true k-mer in a coverage hole is counted as an error; with noisy reads and --min_count 1 an error "
+                  "k-mer can be carried by a chance read error, so the figure is an upper bound of the true QV and the "
+                  "histogram is the evidence for a larger --min_count; it compares assemblies on the same reads and does not "
+                  "replace `assess` where a truth exists; no value of --min_count is recommended.")
+
+
+def kmer_qv_parser(ap=None):
+    """`kmer_qv`: the reference has no counterpart"""
+    ap = ap or argparse.ArgumentParser(prog="kmer_qv")
+    ap.description = ("Reference-free QV of an assembly: a k-mer of the assembly that fewer than --min_count read k-mers contain "
+                      "is taken to be an error (the rule of Merqury and yak, on the device). The reads are the aligned part of "
+                      "the BAM's primary reads as the polisher sees them, soft clips and leading insertions gone, clipped at "
+                      "the --interval edges (a read k-mer across an edge is not counted: about k / interval of them).")
+    ap.epilog = KMER_QV_IS_NOT
+    ap.add_argument("-a", "--assembly", type=str, required=True, help="FASTA of the assembly to score (the polished one)")
+    ap.add_argument("-b", "--bam", type=str, required=True, help="BAM of the reads, as given to polish")
+    ap.add_argument("-f", "--fasta", type=str, required=True,
+                    help="FASTA the BAM was aligned to (the draft): the reader wants its bytes; with -d it is scored too")
+    ap.add_argument("-o", "--output", type=str, required=True,
+                    help="output prefix: <output>_kmer_qv.tsv (one line per contig and TOTAL), .segments.tsv (unsupported k-mers "
+                         "per --segment bases), .runs.bed (stretches of unsupported k-mers and the bases all of them cover) and "
+                         ".hist.tsv (assembly k-mers by read count); parent directories are created")
+    ap.add_argument("-d", "--draft", action="store_true", default=False,
+                    help="score the -f FASTA the same way into <output>_kmer_qv_draft.*, in the same pass over the reads; the log "
+                         "gives unsupported k-mers and QV before -> after")
+    ap.add_argument("-k", "--kmer", type=int, default=21, help="k-mer length, odd, in [11, 31]")
+    ap.add_argument("--min_count", type=int, default=1,
+                    help="a k-mer with fewer read occurrences is unsupported; choose it by <output>_kmer_qv.hist.tsv, no value is "
+                         "recommended")
+    ap.add_argument("--segment", type=int, default=1024, help="bases per line of the segment track, a multiple of 32 in [32, 65536]")
+    ap.add_argument("--interval", type=int, default=1000000, help="bases of a contig read at a time, at least 1000")
+    ap.add_argument("-t", "--threads", type=int, default=5, help="reader threads; the output does not depend on them")
+    ap.add_argument("-d_id", "--device_id", type=int, default=0, help="the device")
+    return ap
+
+
 def parser():
     ap = argparse.ArgumentParser(prog="pepper", description="PEPPER polisher on the MI355X-native hot path: polish, or its three "
                                                             "steps make_images -> call_consensus -> stitch through files")
@@ -119,6 +157,7 @@ def parser():
     call_consensus_parser(sub.add_parser("call_consensus", help="prediction HDF5 files from the image files and a model"))
     stitch_parser(sub.add_parser("stitch", help="the polished FASTA from the prediction files"))
     assess_parser(sub.add_parser("assess", help="identity, QV and error breakdown of an assembly against a truth FASTA"))
+    kmer_qv_parser(sub.add_parser("kmer_qv", help="reference-free QV of an assembly from its k-mers' support in the reads"))
     return ap
 
 
@@ -134,6 +173,9 @@ def main(argv=None) -> int:
     if args.sub_command == "assess":
         from . import assess
         return assess.run(args)
+    if args.sub_command == "kmer_qv":
+        from . import kmer_qv
+        return kmer_qv.run(args)
     from . import polish_steps
     if args.sub_command == "make_images":
         return polish_steps.make_images_run(args)

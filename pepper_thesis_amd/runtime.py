@@ -814,6 +814,76 @@ class Context:
                                             int(min_hits), _ffi.ptr(out) if n else None, counts))
         return out
 
+    def kmer_table_bytes(self, a_off: np.ndarray) -> int:
+        """bytes of table pv_kmer_table_build_dev needs for an assembly with these (host) offsets"""
+        ao = np.ascontiguousarray(a_off, np.int64)
+        n = int(self.lib.pv_kmer_table_bytes(len(ao) - 1, _ffi.ptr(ao)))
+        if n < 0:
+            raise _ffi.PepperHipError(n, "kmer table: bad offsets")
+        return n
+
+    def kmer_table_build_dev(self, d_a: int, d_a_off: int, n_asm: int, k: int, cap: int, d_table: int, table_bytes: int,
+                             d_counts: int, stream: int = 0):
+        """asynchronous, device-resident pv_kmer_table_build_dev: {keyed entries, status, first bad contig or -1, table bytes
+        needed} in d_counts"""
+        _ffi.check(self.lib.pv_kmer_table_build_dev(self.handle, d_a or None, d_a_off or None, int(n_asm), int(k), int(cap),
+                                                    d_table or None, int(table_bytes), d_counts, stream or None))
+
+    def kmer_count_reads_dev(self, d_table: int, table_bytes: int, d_bases: int, d_base_off: int, n_reads: int, n_bases: int,
+                             stream: int = 0):
+        """asynchronous pv_kmer_count_reads_dev: the reads' k-mers added to the table's counters"""
+        _ffi.check(self.lib.pv_kmer_count_reads_dev(self.handle, d_table or None, int(table_bytes), d_bases or None,
+                                                    d_base_off or None, int(n_reads), int(n_bases), stream or None))
+
+    def kmer_support_dev(self, d_table: int, table_bytes: int, d_a_off: int, n_asm: int, min_count: int, segment: int, d_contig: int,
+                         d_seg_off: int, seg_capacity: int, d_segs: int, run_capacity: int, d_runs: int, d_hist: int,
+                         d_pos_counts: int, d_counts: int, stream: int = 0):
+        """asynchronous pv_kmer_support_dev: {runs written, status, runs needed, segment slots needed, summed length, 0, 0, 0} in
+        d_counts (int64[8])"""
+        _ffi.check(self.lib.pv_kmer_support_dev(self.handle, d_table or None, int(table_bytes), d_a_off or None, int(n_asm),
+                                                int(min_count), int(segment), d_contig or None, d_seg_off or None, int(seg_capacity),
+                                                d_segs or None, int(run_capacity), d_runs or None, d_hist or None,
+                                                d_pos_counts or None, d_counts, stream or None))
+
+    def kmer_support(self, asm, reads, k: int = 21, cap: int = _ffi.PV_KMER_MAX_CAP, min_count: int = 1, segment: int = 1024,
+                     run_capacity=None, seg_capacity=None, want_positions: bool = True, counts=None, out=None):
+        """host-buffer pv_kmer_support of [assembly contig bytes] (upper-cased) against [read bytes] -> (contig counts int64
+        [n][3], seg_off int64 [n+1], segs int64, runs int64 [r][3], hist int64 [256], pos_counts uint32 or None). run_capacity
+        None: a second call is made with the capacity the first reports. counts: optional ctypes int64[8]; out: optional
+        (contig, seg_off, segs, runs, hist, pos_counts) arrays that receive the result, also when the call raises."""
+        n = len(asm)
+        a_off = np.zeros(n + 1, np.int64)
+        b_off = np.zeros(len(reads) + 1, np.int64)
+        a_off[1:] = np.cumsum([len(a) for a in asm])
+        b_off[1:] = np.cumsum([len(r) for r in reads])
+        A = np.frombuffer(b"".join(bytes(a) for a in asm) or b"\0", np.uint8)   # (never a null pointer: one unread byte)
+        B = np.frombuffer(b"".join(bytes(r) for r in reads) or b"\0", np.uint8)
+        if seg_capacity is None:
+            seg_capacity = int(sum((len(a) + int(segment) - 1) // max(int(segment), 1) for a in asm))
+        sized = run_capacity is not None
+        if not sized:
+            run_capacity = 1024
+        if counts is None:
+            counts = (C.c_int64 * 8)()
+        for attempt in (0, 1):
+            if out is None or attempt:
+                out = (np.zeros((n, 3), np.int64), np.zeros(n + 1, np.int64), np.zeros(seg_capacity, np.int64),
+                       np.zeros((run_capacity, 3), np.int64), np.zeros(_ffi.PV_KMER_HIST, np.int64),
+                       np.zeros(int(a_off[n]), np.uint32) if want_positions else None)
+            ctg, seg_off, segs, runs, hist, plane = out
+            assert ctg.shape == (n, 3) and len(seg_off) == n + 1 and len(segs) >= seg_capacity and len(runs) >= run_capacity
+            rc = self.lib.pv_kmer_support(self.handle, _ffi.ptr(A), _ffi.ptr(a_off), n, _ffi.ptr(B), _ffi.ptr(b_off), len(reads),
+                                          int(k), int(cap), int(min_count), int(segment), _ffi.ptr(ctg) if n else None,
+                                          _ffi.ptr(seg_off), int(seg_capacity), _ffi.ptr(segs) if len(segs) else None,
+                                          int(run_capacity), _ffi.ptr(runs) if len(runs) else None, _ffi.ptr(hist),
+                                          _ffi.ptr(plane) if plane is not None and len(plane) else None, counts)
+            if rc == _ffi.PV_ERR_CAPACITY and not sized and attempt == 0:
+                run_capacity = int(counts[2])   # the one sized second call
+                continue
+            _ffi.check(rc)
+            break
+        return ctg, seg_off, segs[:int(counts[3])], runs[:int(counts[0])], hist, plane
+
     def profile_begin(self, only: str = None):
         """bracket every kernel launch of this context with HIP events (only: just the kernels whose profile name starts
         with it - two events per launch put a few microseconds between kernels)"""
