@@ -1221,6 +1221,70 @@ int pv_kmer_support(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, int64_t
 /* bytes of table an assembly needs, from its HOST offsets (negative: PV_ERR_INVALID) */
 int64_t pv_kmer_table_bytes(int64_t n_asm, const int64_t* a_off);
 
+/* ---- kmer_qv --completeness: the reads' k-mers that the assembly lacks ---------------------------------------------------------
+ * The section above says which k-mers of the assembly the reads do not support; this one says which k-mers of the reads the
+ * assembly does not hold (Merqury's completeness beside its QV). Keys, k, canonical form and "a k-mer lies inside one read" are
+ * those of the section above; the assembly table is the one pv_kmer_table_build_dev makes. Restated on dicts in
+ * tests/kmer_spectrum_ref.py.
+ * Hash. mix is the splitmix64 finaliser on 64 bits: x ^= x >> 30; x *= 0xbf58476d1ce4e5b9; x ^= x >> 27;
+ *   x *= 0x94d049bb133111eb; x ^= x >> 31.
+ * Parts. A keyed read k-mer with canonical key x belongs to part (mix of x >> 32) % n_parts, 1 <= n_parts <= PV_KMER_MAX_PARTS =
+ *   4096. A counting call with (part, n_parts) processes the instances of its part and ignores the rest, hits included: after one
+ *   call per part over the same reads the assembly table's counters equal those of pv_kmer_count_reads_dev on these reads.
+ * Reads-only table. `slots` entries, a power of two in [PV_KMER_READS_MIN_SLOTS = 1024, PV_KMER_READS_MAX_SLOTS = 2^34]: a
+ *   256-byte head, keys uint64 [slots] (empty = all ones), counts uint32 [slots]; 256 + 12 slots bytes. Home slot: mix of x &
+ *   (slots - 1); probing is linear, wraps at the end and tries at most PV_KMER_READS_PROBES = 1024 slots. An instance whose key
+ *   is in the assembly table adds to that table as pv_kmer_count_reads_dev does. Any other instance claims or finds its key's
+ *   slot (one 64-bit compare-and-swap on an empty slot; keys are never removed during a pass) and adds 1 there under the cap
+ *   rule of the section above: load, add only below the cap, value = min(cap, instances). The cap is the one given to the init
+ *   call: give it the build's.
+ * Overflow. A key that finds no slot within the probe limit sets status PV_ERR_CAPACITY in the head and adds to a `dropped`
+ *   counter. Lanes read the status once per tile; once they see it set they only count dropped instances (a full table costs a
+ *   bounded amount of work, never a scan per instance). After an overflow the table's content is unspecified: only the status
+ *   and dropped > 0 are promised.
+ * Flush. For every occupied slot 1 is added to ro_hist[min(count, cap, 255)] (int64 [PV_KMER_HIST], accumulating over calls:
+ *   the caller zeroes it once); d_counts int64[4] = {distinct keys flushed, status, dropped instances, slots}; the table is
+ *   emptied and its status and dropped counter reset, so the next part can be counted. Under PV_ERR_CAPACITY ro_hist is left as
+ *   it was.
+ * Assembly spectrum. For every distinct key of the assembly table, with its multiplicity m (equal sorted entries) and its count
+ *   c = min(cap, counter) as the summary gathers it, 1 is added to spectrum[min(m, 4) - 1][min(c, 255)] (int64 [4][PV_KMER_HIST],
+ *   accumulating: the caller zeroes it). Column 0 holds the assembly k-mers that no read has. d_counts int64[2] = {distinct
+ *   keys, status}.
+ * Completeness at threshold s, 1 <= s <= 255, is the host's: found = the sum of spectrum[m][c] over all rows and c >= s; total =
+ *   found + the sum of ro_hist[c] over c >= s; completeness = found / total.
+ *
+ * pv_kmer_reads_table_init_dev: rtable 256-byte aligned, rtable_bytes at least pv_kmer_reads_table_bytes of slots; one launch.
+ * pv_kmer_count_reads_all_dev: pv_kmer_count_reads_dev's arguments, the reads-only table and (part, n_parts); one launch of
+ * k_km_count_all, the tile, halo and directory staging of k_km_count. pv_kmer_reads_flush_dev: two launches.
+ * pv_kmer_spectrum_dev: two launches; the table's counters are read, not changed.
+ * Status. Null pointers and scalars out of range (slots, cap, part, n_parts, negative sizes, rtable_bytes below the head or
+ * below what slots need) are refused with PV_ERR_INVALID by the call itself. A reads-only table that was not initialised, or
+ * whose rtable_bytes contradict its head, counts nothing and makes the flush report status PV_ERR_INVALID, {0, status, 0, 0},
+ * with ro_hist untouched. An assembly table not built PV_OK counts nothing, in either table, and gives the spectrum status
+ * PV_ERR_INVALID with `spectrum` untouched. Empty input is PV_OK with zeros. Asynchronous on `stream`, no host read-back,
+ * capturable as one linear chain. */
+#define PV_KMER_READS_MIN_SLOTS 1024
+#define PV_KMER_READS_MAX_SLOTS (1ll << 34)
+#define PV_KMER_READS_PROBES 1024
+#define PV_KMER_MAX_PARTS 4096
+/* bytes of a reads-only table of `slots` entries (negative: PV_ERR_INVALID) */
+int64_t pv_kmer_reads_table_bytes(int64_t slots);
+int pv_kmer_reads_table_init_dev(pv_ctx* ctx, void* rtable, int64_t rtable_bytes, int64_t slots, int64_t cap, void* stream);
+int pv_kmer_count_reads_all_dev(pv_ctx* ctx, void* table, int64_t table_bytes, void* rtable, int64_t rtable_bytes,
+                                const uint8_t* bases, const int64_t* base_off, int64_t n_reads, int64_t n_bases, int part,
+                                int n_parts, void* stream);
+int pv_kmer_reads_flush_dev(pv_ctx* ctx, void* rtable, int64_t rtable_bytes, int64_t* ro_hist, int64_t* d_counts, void* stream);
+int pv_kmer_spectrum_dev(pv_ctx* ctx, void* table, int64_t table_bytes, int64_t* spectrum, int64_t* d_counts, void* stream);
+/* HOST buffers in and out, as pv_kmer_support takes them: build, this one batch of reads counted part by part with a flush after
+ * each, the spectrum; both tables are the context's own. spectrum int64 [4][256] and ro_hist int64 [256] are overwritten.
+ * counts int64[8] = {distinct reads-only keys, status, dropped instances, slots, keyed entries, distinct assembly keys, 0, 0};
+ * the status is the first of: the build's, a flush's, the spectrum's; it is returned too. Offsets that do not start at 0 or
+ * decrease, and 2^31 bytes or more on either side, are refused on the host (PV_ERR_INVALID, PV_ERR_LIMIT) with the outputs left
+ * as they were. */
+int pv_kmer_spectrum(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, int64_t n_asm, const uint8_t* bases,
+                     const int64_t* base_off, int64_t n_reads, int k, int64_t cap, int64_t slots, int n_parts, int64_t* spectrum,
+                     int64_t* ro_hist, int64_t* counts);
+
 /* bytes of device workspace the context currently holds (diagnostics) */
 int64_t pv_workspace_bytes(pv_ctx* ctx);
 /* library/ABI version: major*10000 + minor*100 + patch */

@@ -92,6 +92,10 @@ PV_KMER_TILE = 4096
 PV_KMER_SORT_SPAN = 2048
 PV_KMER_HIST = 256
 PV_KMER_NO_KEY = 0xFFFFFFFF
+PV_KMER_READS_MIN_SLOTS = 1024
+PV_KMER_READS_MAX_SLOTS = 1 << 34
+PV_KMER_READS_PROBES = 1024
+PV_KMER_MAX_PARTS = 4096
 
 PV_PLAN_P1_LSTM = 1
 PV_PLAN_P2_GRU = 2
@@ -436,6 +440,16 @@ SYMBOLS = [
      [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int,
       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     ("pv_kmer_table_bytes", C.c_int64, [C.c_int64, C.c_void_p]),
+    ("pv_kmer_reads_table_bytes", C.c_int64, [C.c_int64]),
+    ("pv_kmer_reads_table_init_dev", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    ("pv_kmer_count_reads_all_dev", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
+      C.c_void_p]),
+    ("pv_kmer_reads_flush_dev", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pv_kmer_spectrum_dev", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pv_kmer_spectrum", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int,
+      C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     ("pv_workspace_bytes", C.c_int64, [C.c_void_p]),
     ("pv_version", C.c_int, []),
 ]

@@ -25,6 +25,18 @@
 //     k_km_run_scan     one block: the tiles' offsets, the number of runs, PV_ERR_CAPACITY, the contigs' positions without a key
 //     k_km_run_write    the j-th start and the j-th end of the flat order are one run: (contig, first) and (last) written apart
 //     k_km_poison       under a status other than PV_OK and PV_ERR_CAPACITY: -1 in every output
+// --completeness (the second section of the header): the read k-mers the assembly lacks, in an open-addressing table of their own
+//   pv_kmer_reads_table_init_dev
+//     k_kr_init         every slot empty, the head
+//   pv_kmer_count_reads_all_dev
+//     k_km_count_all    k_km_count with a part filter and a miss path: a key the assembly lacks claims or finds its slot (linear
+//                       probing from mix(key), one 64-bit compare-and-swap on an empty slot) and adds one there under the cap
+//   pv_kmer_reads_flush_dev
+//     k_kr_flush_setup  one lane: the head checked, {0, status, dropped, slots}, status and dropped reset
+//     k_kr_flush        a lane per slot: the histogram of the counts in LDS, the table emptied
+//   pv_kmer_spectrum_dev
+//     k_km_spec_setup   one lane: the table's status
+//     k_km_spectrum     a lane per sorted entry: the first of equal keys adds its (multiplicity, count) to the spectrum in LDS
 // The counters are integer atomics: the result does not depend on tile size, workgroup count or the order of the calls.
 #include <algorithm>
 
@@ -507,6 +519,186 @@ __global__ __launch_bounds__(AS_THREADS) void k_km_poison(SupArgs g, int64_t sta
         for (int64_t i = t; i < L; i += step) g.plane[i] = KM_NO_KEY;
 }
 
+// ---- the reads' k-mers that the assembly lacks (--completeness) ----------------------------------------------------------------
+// the reads-only table: head int64 [32] {magic, slots, cap, status, dropped}, keys uint64 [slots], cnt uint32 [slots]
+constexpr int64_t KR_MAGIC = 0x5651524D4B5652ll;
+constexpr int KR_PROBES = PV_KMER_READS_PROBES;
+enum { R_MAGIC, R_SLOTS, R_CAP, R_STATUS, R_DROPPED };
+
+struct Reads { int64_t slots; uint32_t cap; uint64_t* keys; uint32_t* cnt; int64_t* head; };
+__host__ __device__ inline bool slots_ok(int64_t s) {
+    return s >= PV_KMER_READS_MIN_SLOTS && s <= PV_KMER_READS_MAX_SLOTS && (s & (s - 1)) == 0;
+}
+__host__ __device__ inline int64_t reads_bytes(int64_t slots) { return KM_HEAD + slots * 12; }
+// initialised, and no larger than the memory the caller says it has
+__device__ inline bool reads_ok(const void* rtable, int64_t rtable_bytes) {
+    const int64_t* h = (const int64_t*)rtable;
+    return h[R_MAGIC] == KR_MAGIC && slots_ok(h[R_SLOTS]) && reads_bytes(h[R_SLOTS]) <= rtable_bytes && h[R_CAP] >= 1 &&
+           h[R_CAP] <= PV_KMER_MAX_CAP;
+}
+__device__ inline Reads reads_of(void* rtable) {
+    int64_t* h = (int64_t*)rtable;
+    uint8_t* b = (uint8_t*)rtable;
+    return {h[R_SLOTS], (uint32_t)h[R_CAP], (uint64_t*)(b + KM_HEAD), (uint32_t*)(b + KM_HEAD + h[R_SLOTS] * 8), h};
+}
+
+// the splitmix64 finaliser: its low bits choose the home slot, bits 32.. the part
+__host__ __device__ inline uint64_t km_mix(uint64_t x) {
+    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27; x *= 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+
+__global__ __launch_bounds__(AS_THREADS) void k_kr_init(void* rtable, int64_t slots, int64_t cap) {
+    uint64_t* keys = (uint64_t*)((uint8_t*)rtable + KM_HEAD);
+    uint32_t* cnt = (uint32_t*)((uint8_t*)rtable + KM_HEAD + slots * 8);
+    const int64_t t = (int64_t)blockIdx.x * AS_THREADS + threadIdx.x;
+    for (int64_t s = t; s < slots; s += (int64_t)gridDim.x * AS_THREADS) { keys[s] = KM_NONE; cnt[s] = 0; }
+    if (t < KM_HEAD / 8) {
+        int64_t* h = (int64_t*)rtable;
+        h[t] = t == R_MAGIC ? KR_MAGIC : t == R_SLOTS ? slots : t == R_CAP ? cap : 0;   // status PV_OK, nothing dropped
+    }
+}
+
+struct CountAllArgs {
+    void* table; void* rtable; int64_t rtable_bytes;
+    const uint8_t* bases; const int64_t* base_off; int64_t n_reads, n_bases;
+    uint32_t part, n_parts;
+};
+
+// k_km_count's tile, halo and directory staging; an instance of another part is passed over, a hit adds to the assembly table
+// as there, and a miss goes to the reads-only table: THE HOT PATH with noisy reads, where most instances are misses
+__global__ __launch_bounds__(AS_THREADS) void k_km_count_all(CountAllArgs g) {
+    __shared__ uint8_t s_code[KM_TILE + KM_HALO];
+    __shared__ uint32_t s_dir[KM_DIR + 1];
+    if (!table_ok(g.table) || !reads_ok(g.rtable, g.rtable_bytes)) return;
+    const Table tb = table_of(g.table);
+    const Reads rd = reads_of(g.rtable);
+    const bool look = head_of(g.table)[H_KEYED] != 0;   // a table without a key has no directory: every instance is a miss
+    const int64_t lo = max(g.base_off[0], (int64_t)0), hi = min(g.base_off[g.n_reads], g.n_bases);
+    if (lo + (int64_t)blockIdx.x * KM_TILE >= hi) return;
+    const int k = tb.k;
+    const uint64_t mask = (uint64_t)rd.slots - 1;
+    if (look)
+        for (int b = threadIdx.x; b <= KM_DIR; b += AS_THREADS) s_dir[b] = tb.dir[b];
+    int64_t dropped = 0;
+    bool full = false;
+    for (int64_t g0 = lo + (int64_t)blockIdx.x * KM_TILE; g0 < hi; g0 += (int64_t)gridDim.x * KM_TILE) {
+        __syncthreads();   // the previous tile has been read
+        for (int i = threadIdx.x; i < KM_TILE + k - 1; i += AS_THREADS) s_code[i] = g0 + i < hi ? code_of(g.bases[g0 + i]) : 4;
+        __syncthreads();
+        // once per tile: after an overflow nothing is probed any more
+        full = full || __hip_atomic_load(&rd.head[R_STATUS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != PV_OK;
+        const int i0 = threadIdx.x * KM_PER;
+        if (g0 + i0 >= hi) continue;
+        int64_t t = owner_of(g.base_off, g.n_reads, g0 + i0);
+        int64_t end = g.base_off[t + 1];
+        Roll r(k);
+        for (int q = 0; q < k - 1; q++) r.push(s_code[i0 + q]);
+        for (int m = 0; m < KM_PER; m++) {
+            r.push(s_code[i0 + k - 1 + m]);
+            const int64_t pos = g0 + i0 + m;
+            if (pos >= hi) break;
+            while (pos >= end && t + 1 < g.n_reads) { t++; end = g.base_off[t + 1]; }
+            if (!r.keyed() || pos + k > end) continue;
+            const uint64_t key = r.canon(), h = km_mix(key);
+            if (g.n_parts > 1 && (uint32_t)(h >> 32) % g.n_parts != g.part) continue;
+            if (look) {
+                const uint32_t b = (uint32_t)(key >> tb.shift);
+                const int64_t top = s_dir[b + 1], e = first_at_least(tb.keys, s_dir[b], top, key);
+                if (e < top && tb.keys[e] == key) {
+                    if (__hip_atomic_load(&tb.cnt[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < tb.cap) atomicAdd(&tb.cnt[e], 1u);
+                    continue;
+                }
+            }
+            if (full) { dropped++; continue; }
+            // a slot's key is written once and stays: a key seen there is final, and only an empty slot needs the compare-and-swap
+            uint64_t s = h & mask;
+            bool placed = false;
+            for (int p = 0; p < KR_PROBES; p++, s = (s + 1) & mask) {
+                uint64_t old = __hip_atomic_load(&rd.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (old == KM_NONE) old = atomicCAS((unsigned long long*)&rd.keys[s], (unsigned long long)KM_NONE, (unsigned long long)key);
+                if (old != KM_NONE && old != key) continue;
+                if (__hip_atomic_load(&rd.cnt[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < rd.cap) atomicAdd(&rd.cnt[s], 1u);
+                placed = true;
+                break;
+            }
+            if (!placed) {
+                full = true;
+                dropped++;
+                __hip_atomic_store(&rd.head[R_STATUS], (int64_t)PV_ERR_CAPACITY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+    dropped = wave_sum(dropped);
+    if ((threadIdx.x & 63) == 0 && dropped) atomicAdd((unsigned long long*)&rd.head[R_DROPPED], (unsigned long long)dropped);
+}
+
+struct FlushArgs { void* rtable; int64_t rtable_bytes; int64_t* ro_hist; int64_t* counts; };
+
+__global__ void k_kr_flush_setup(FlushArgs g) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const bool ok = reads_ok(g.rtable, g.rtable_bytes);
+    int64_t* h = (int64_t*)g.rtable;
+    g.counts[0] = 0; g.counts[1] = ok ? h[R_STATUS] : PV_ERR_INVALID; g.counts[2] = ok ? h[R_DROPPED] : 0; g.counts[3] = ok ? h[R_SLOTS] : 0;
+    if (ok) { h[R_STATUS] = PV_OK; h[R_DROPPED] = 0; }
+}
+
+// a lane per slot; the histogram in LDS, flushed by at most 256 atomic adds per workgroup
+__global__ __launch_bounds__(AS_THREADS) void k_kr_flush(FlushArgs g) {
+    __shared__ uint32_t s_hist[PV_KMER_HIST];
+    __shared__ int64_t lds[AS_THREADS / 64];
+    if (g.counts[1] == PV_ERR_INVALID) return;
+    const Reads rd = reads_of(g.rtable);
+    const bool add = g.counts[1] == PV_OK;
+    for (int i = threadIdx.x; i < PV_KMER_HIST; i += AS_THREADS) s_hist[i] = 0;
+    __syncthreads();
+    int64_t n = 0;
+    for (int64_t s = (int64_t)blockIdx.x * AS_THREADS + threadIdx.x; s < rd.slots; s += (int64_t)gridDim.x * AS_THREADS) {
+        if (rd.keys[s] == KM_NONE) continue;
+        n++;
+        if (add) atomicAdd(&s_hist[min(min(rd.cnt[s], rd.cap), (uint32_t)(PV_KMER_HIST - 1))], 1u);
+        rd.keys[s] = KM_NONE;
+        rd.cnt[s] = 0;
+    }
+    n = block_sum(n, lds);   // (its barriers: the LDS histogram is complete)
+    if (threadIdx.x == 0 && n) atomicAdd((unsigned long long*)&g.counts[0], (unsigned long long)n);
+    for (int i = threadIdx.x; i < PV_KMER_HIST; i += AS_THREADS)
+        if (s_hist[i]) atomicAdd((unsigned long long*)&g.ro_hist[i], (unsigned long long)s_hist[i]);
+}
+
+struct SpecArgs { void* table; int64_t* spectrum; int64_t* counts; };
+
+__global__ void k_km_spec_setup(SpecArgs g) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    g.counts[0] = 0; g.counts[1] = table_ok(g.table) ? PV_OK : PV_ERR_INVALID;
+}
+
+// a lane per sorted entry: the first of equal keys walks forward over at most three more (only min(m, 4) is asked for)
+__global__ __launch_bounds__(AS_THREADS) void k_km_spectrum(SpecArgs g) {
+    __shared__ uint32_t s_spec[4 * PV_KMER_HIST];
+    __shared__ int64_t lds[AS_THREADS / 64];
+    if (g.counts[1] != PV_OK) return;
+    const Table tb = table_of(g.table);
+    const int64_t keyed = head_of(g.table)[H_KEYED];
+    for (int i = threadIdx.x; i < 4 * PV_KMER_HIST; i += AS_THREADS) s_spec[i] = 0;
+    __syncthreads();
+    int64_t n = 0;
+    for (int64_t e = (int64_t)blockIdx.x * AS_THREADS + threadIdx.x; e < keyed; e += (int64_t)gridDim.x * AS_THREADS) {
+        const uint64_t key = tb.keys[e];
+        if (e > 0 && tb.keys[e - 1] == key) continue;
+        int m = 1;
+        while (m < 4 && e + m < keyed && tb.keys[e + m] == key) m++;
+        const uint32_t c = min(min(tb.cnt[e], tb.cap), (uint32_t)(PV_KMER_HIST - 1));
+        atomicAdd(&s_spec[(m - 1) * PV_KMER_HIST + c], 1u);
+        n++;
+    }
+    n = block_sum(n, lds);   // (its barriers: the LDS spectrum is complete)
+    if (threadIdx.x == 0 && n) atomicAdd((unsigned long long*)&g.counts[0], (unsigned long long)n);
+    for (int i = threadIdx.x; i < 4 * PV_KMER_HIST; i += AS_THREADS)
+        if (s_spec[i]) atomicAdd((unsigned long long*)&g.spectrum[i], (unsigned long long)s_spec[i]);
+}
+
 unsigned blocks_for(int64_t items, int64_t per_block, int64_t most) {
     return (unsigned)std::max<int64_t>(1, std::min(most, (items + per_block - 1) / per_block));
 }
@@ -709,5 +901,155 @@ extern "C" int pv_kmer_support(pv_ctx* ctx, const uint8_t* A, const int64_t* a_o
     counts[4] = h[8]; counts[5] = h[10]; counts[6] = h[11];
     PV_CHECK(counts[1] == PV_OK, (int)counts[1], "kmer support: device status %lld (%lld run records, %lld segment slots needed)",
              (long long)counts[1], (long long)counts[2], (long long)counts[3]);
+    return PV_OK;
+}
+
+// ---- --completeness: the reads-only table, the count of every part, the flush, the assembly's spectrum -------------------------
+namespace {
+
+int reads_check(const void* rtable, int64_t rtable_bytes) {
+    PV_CHECK(rtable, PV_ERR_INVALID, "kmer reads table: null argument");
+    PV_CHECK(rtable_bytes >= reads_bytes(PV_KMER_READS_MIN_SLOTS), PV_ERR_INVALID,
+             "kmer reads table: %lld bytes cannot hold the smallest table (%lld bytes)", (long long)rtable_bytes,
+             (long long)reads_bytes(PV_KMER_READS_MIN_SLOTS));
+    PV_CHECK(((uintptr_t)rtable & 255) == 0, PV_ERR_INVALID, "kmer reads table: the table must be aligned to 256 bytes");
+    return PV_OK;
+}
+// a bound of the slots a table of `bytes` can hold: it sizes the flush's grid, the kernel takes the slots from the head
+inline int64_t slots_bound(int64_t bytes) { return (bytes - KM_HEAD) / 12; }
+
+}  // namespace
+
+extern "C" int64_t pv_kmer_reads_table_bytes(int64_t slots) { return slots_ok(slots) ? reads_bytes(slots) : (int64_t)PV_ERR_INVALID; }
+
+extern "C" int pv_kmer_reads_table_init_dev(pv_ctx* ctx, void* rtable, int64_t rtable_bytes, int64_t slots, int64_t cap, void* stream) {
+    PV_CHECK(ctx, PV_ERR_INVALID, "kmer reads table: null argument");
+    int rc;
+    if ((rc = reads_check(rtable, rtable_bytes))) return rc;
+    PV_CHECK(slots_ok(slots), PV_ERR_INVALID, "kmer reads table: slots must be a power of two in [1024, 2^34] (got %lld)", (long long)slots);
+    PV_CHECK(reads_bytes(slots) <= rtable_bytes, PV_ERR_INVALID, "kmer reads table: %lld slots need %lld bytes (got %lld)",
+             (long long)slots, (long long)reads_bytes(slots), (long long)rtable_bytes);
+    PV_CHECK(cap >= 1 && cap <= PV_KMER_MAX_CAP, PV_ERR_INVALID, "kmer reads table: cap must lie in [1, 2^30] (got %lld)", (long long)cap);
+    PV_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = pv_pick_stream(ctx, stream);
+    pv_prof_scope ps(ctx, "k_kr_init", st);
+    k_kr_init<<<blocks_for(slots, 4ll * AS_THREADS, 16ll * ctx->num_cu), AS_THREADS, 0, st>>>(rtable, slots, cap);
+    PV_HIP(hipGetLastError());
+    return PV_OK;
+}
+
+extern "C" int pv_kmer_count_reads_all_dev(pv_ctx* ctx, void* table, int64_t table_bytes, void* rtable, int64_t rtable_bytes,
+                                           const uint8_t* bases, const int64_t* base_off, int64_t n_reads, int64_t n_bases, int part,
+                                           int n_parts, void* stream) {
+    PV_CHECK(ctx && table && base_off, PV_ERR_INVALID, "kmer count: null argument");
+    int rc;
+    if ((rc = reads_check(rtable, rtable_bytes))) return rc;
+    PV_CHECK(n_reads >= 0 && n_bases >= 0 && (n_bases == 0 || bases), PV_ERR_INVALID, "kmer count: reads missing or negative sizes");
+    PV_CHECK(n_parts >= 1 && n_parts <= PV_KMER_MAX_PARTS && part >= 0 && part < n_parts, PV_ERR_INVALID,
+             "kmer count: part %d of %d: the parts must lie in [1, %d] and the part below them", part, n_parts, PV_KMER_MAX_PARTS);
+    PV_CHECK(n_bases < (1ll << 31) && n_reads < (1ll << 31), PV_ERR_LIMIT, "kmer count: a batch holds at most 2^31 - 1 bases");
+    PV_CHECK(table_bytes >= km_layout(0).total, PV_ERR_LIMIT, "kmer count: the table of %lld bytes cannot hold its head",
+             (long long)table_bytes);
+    if (n_reads == 0 || n_bases == 0) return PV_OK;
+    PV_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = pv_pick_stream(ctx, stream);
+    pv_prof_scope ps(ctx, "k_km_count_all", st);
+    CountAllArgs g = {table, rtable, rtable_bytes, bases, base_off, n_reads, n_bases, (uint32_t)part, (uint32_t)n_parts};
+    k_km_count_all<<<blocks_for(n_bases, KM_TILE, 8ll * ctx->num_cu), AS_THREADS, 0, st>>>(g);
+    PV_HIP(hipGetLastError());
+    return PV_OK;
+}
+
+extern "C" int pv_kmer_reads_flush_dev(pv_ctx* ctx, void* rtable, int64_t rtable_bytes, int64_t* ro_hist, int64_t* d_counts,
+                                       void* stream) {
+    PV_CHECK(ctx && ro_hist && d_counts, PV_ERR_INVALID, "kmer reads flush: null argument");
+    int rc;
+    if ((rc = reads_check(rtable, rtable_bytes))) return rc;
+    PV_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = pv_pick_stream(ctx, stream);
+    pv_prof_scope ps(ctx, "kmer_reads_flush", st);
+    FlushArgs g = {rtable, rtable_bytes, ro_hist, d_counts};
+    k_kr_flush_setup<<<1, 64, 0, st>>>(g);
+    k_kr_flush<<<blocks_for(slots_bound(rtable_bytes), 4ll * AS_THREADS, 16ll * ctx->num_cu), AS_THREADS, 0, st>>>(g);
+    PV_HIP(hipGetLastError());
+    return PV_OK;
+}
+
+extern "C" int pv_kmer_spectrum_dev(pv_ctx* ctx, void* table, int64_t table_bytes, int64_t* spectrum, int64_t* d_counts, void* stream) {
+    PV_CHECK(ctx && table && spectrum && d_counts, PV_ERR_INVALID, "kmer spectrum: null argument");
+    PV_CHECK(table_bytes >= km_layout(0).total, PV_ERR_LIMIT, "kmer spectrum: the table of %lld bytes cannot hold its head",
+             (long long)table_bytes);
+    PV_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = pv_pick_stream(ctx, stream);
+    pv_prof_scope ps(ctx, "kmer_spectrum", st);
+    SpecArgs g = {table, spectrum, d_counts};
+    k_km_spec_setup<<<1, 64, 0, st>>>(g);
+    k_km_spectrum<<<blocks_for(positions_bound(table_bytes), AS_THREADS, 8ll * ctx->num_cu), AS_THREADS, 0, st>>>(g);
+    PV_HIP(hipGetLastError());
+    return PV_OK;
+}
+
+extern "C" int pv_kmer_spectrum(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, int64_t n_asm, const uint8_t* bases,
+                                const int64_t* base_off, int64_t n_reads, int k, int64_t cap, int64_t slots, int n_parts,
+                                int64_t* spectrum, int64_t* ro_hist, int64_t* counts) {
+    PV_CHECK(ctx && counts && spectrum && ro_hist && a_off && base_off, PV_ERR_INVALID, "kmer spectrum: null argument");
+    int rc;
+    if ((rc = build_check(n_asm, k, cap))) return rc;
+    PV_CHECK(n_reads >= 0 && n_reads < (1ll << 31), PV_ERR_INVALID, "kmer spectrum: the number of reads must lie in [0, 2^31)");
+    PV_CHECK(n_asm == 0 || A, PV_ERR_INVALID, "kmer spectrum: sequences missing");
+    PV_CHECK(slots_ok(slots), PV_ERR_INVALID, "kmer spectrum: slots must be a power of two in [1024, 2^34] (got %lld)", (long long)slots);
+    PV_CHECK(n_parts >= 1 && n_parts <= PV_KMER_MAX_PARTS, PV_ERR_INVALID, "kmer spectrum: the parts must lie in [1, %d] (got %d)",
+             PV_KMER_MAX_PARTS, n_parts);
+    for (int i = 0; i < 8; i++) counts[i] = 0;
+    bool bad = (n_asm && a_off[0] != 0) || base_off[0] != 0;
+    for (int64_t p = 0; p < n_asm && !bad; p++) bad = a_off[p + 1] < a_off[p];
+    for (int64_t r = 0; r < n_reads && !bad; r++) bad = base_off[r + 1] < base_off[r];
+    if (bad) counts[1] = PV_ERR_INVALID;
+    PV_CHECK(!bad, PV_ERR_INVALID, "kmer spectrum: offsets must start at 0 and not decrease");
+    const int64_t N = n_asm ? a_off[n_asm] : 0;
+    if (N >= (1ll << 31) || base_off[n_reads] >= (1ll << 31)) counts[1] = PV_ERR_LIMIT;
+    PV_CHECK(counts[1] == PV_OK, PV_ERR_LIMIT, "kmer spectrum: the assembly or the reads hold 2^31 bytes or more");
+    PV_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t na = (size_t)n_asm, nr = (size_t)n_reads, n_b = (size_t)base_off[n_reads], np = (size_t)n_parts;
+    const int64_t need = km_layout(N).total, rneed = reads_bytes(slots);
+    uint8_t *d_a = nullptr, *d_b = nullptr, *d_table = nullptr, *d_rtable = nullptr;
+    int64_t *d_ao = nullptr, *d_bo = nullptr, *d_out = nullptr, *d_counts = nullptr;
+    if ((rc = pv_get(ctx, "km.a", (size_t)N + 1, &d_a))) return rc;
+    if ((rc = pv_get(ctx, "km.b", n_b + 1, &d_b))) return rc;
+    if ((rc = pv_get(ctx, "km.a_off", na + 1, &d_ao))) return rc;
+    if ((rc = pv_get(ctx, "km.b_off", nr + 1, &d_bo))) return rc;
+    if ((rc = pv_get(ctx, "km.table", (size_t)need, &d_table))) return rc;
+    if ((rc = pv_get(ctx, "km.rtable", (size_t)rneed, &d_rtable))) return rc;
+    if ((rc = pv_get(ctx, "km.spectrum", (size_t)5 * PV_KMER_HIST, &d_out))) return rc;   // the spectrum, then ro_hist
+    if ((rc = pv_get(ctx, "km.fcounts", 4 * np + 8, &d_counts))) return rc;                // {build 4, spectrum 2, 0, 0}, a flush's 4 per part
+    if (N) PV_HIP(hipMemcpyAsync(d_a, A, (size_t)N, hipMemcpyHostToDevice, st));
+    if (n_b) PV_HIP(hipMemcpyAsync(d_b, bases, n_b, hipMemcpyHostToDevice, st));
+    PV_HIP(hipMemcpyAsync(d_ao, a_off, (na + 1) * 8, hipMemcpyHostToDevice, st));
+    PV_HIP(hipMemcpyAsync(d_bo, base_off, (nr + 1) * 8, hipMemcpyHostToDevice, st));
+    if ((rc = pv_zero_async(d_out, (size_t)5 * PV_KMER_HIST * 8, st))) return rc;
+    if ((rc = pv_kmer_table_build_dev(ctx, d_a, d_ao, n_asm, k, cap, d_table, need, d_counts, st))) return rc;
+    if ((rc = pv_kmer_reads_table_init_dev(ctx, d_rtable, rneed, slots, cap, st))) return rc;
+    for (int p = 0; p < n_parts; p++) {
+        if ((rc = pv_kmer_count_reads_all_dev(ctx, d_table, need, d_rtable, rneed, d_b, d_bo, n_reads, (int64_t)n_b, p, n_parts, st)))
+            return rc;
+        if ((rc = pv_kmer_reads_flush_dev(ctx, d_rtable, rneed, d_out + 4 * PV_KMER_HIST, d_counts + 8 + 4 * p, st))) return rc;
+    }
+    if ((rc = pv_kmer_spectrum_dev(ctx, d_table, need, d_out, d_counts + 4, st))) return rc;
+    std::vector<int64_t> h(4 * np + 8);
+    PV_HIP(hipMemcpyAsync(h.data(), d_counts, h.size() * 8, hipMemcpyDeviceToHost, st));
+    PV_HIP(hipMemcpyAsync(spectrum, d_out, (size_t)4 * PV_KMER_HIST * 8, hipMemcpyDeviceToHost, st));
+    PV_HIP(hipMemcpyAsync(ro_hist, d_out + 4 * PV_KMER_HIST, (size_t)PV_KMER_HIST * 8, hipMemcpyDeviceToHost, st));
+    PV_HIP(hipStreamSynchronize(st));
+    counts[1] = h[1];
+    for (size_t p = 0; p < np; p++) {
+        counts[0] += h[8 + 4 * p];
+        if (counts[1] == PV_OK) counts[1] = h[8 + 4 * p + 1];
+        counts[2] += h[8 + 4 * p + 2];
+    }
+    if (counts[1] == PV_OK) counts[1] = h[5];
+    counts[3] = slots; counts[4] = h[0]; counts[5] = h[4];
+    PV_CHECK(counts[1] == PV_OK, (int)counts[1], "kmer spectrum: device status %lld (%lld read k-mers dropped from %lld slots)",
+             (long long)counts[1], (long long)counts[2], (long long)slots);
     return PV_OK;
 }

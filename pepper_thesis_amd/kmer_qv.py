@@ -16,6 +16,12 @@ What it is not:
     the true QV, and <o>_kmer_qv.hist.tsv is the evidence for a larger --min_count;
   * it compares assemblies on the same reads; it does not replace `assess` where a truth exists;
   * no value of --min_count is recommended.
+
+--completeness asks the other question: which of the reads' k-mers the assembly lacks (Merqury's completeness; the rule: the
+second k-mer section of include/pepper_hip.h). The same reads, the same clipping; a read k-mer the assembly does not hold goes
+into a reads-only hash table on the device (--read_table_mb), part by part where the table cannot hold all of them (--passes,
+the reads streamed again for every part). With noisy reads the error k-mers dominate the reads-only side at low counts: the
+whole curve over the threshold is written, and it is read past them.
 """
 import concurrent.futures
 import math
@@ -36,6 +42,10 @@ CONTIG_HEADER = "#name\tlength\tkmers\tsupported\tunsupported\tno_key\terror_rat
 SEGMENT_HEADER = "#name\tstart\tend\tunsupported\n"
 RUNS_HEADER = "#name\tstart\tend\tkmers\tcore_start\tcore_end\n"
 HIST_HEADER = "#count\tkmers\n"
+SPECTRUM_HEADER = "#count\treads_only\tasm_x1\tasm_x2\tasm_x3\tasm_x4plus\n"
+COMPLETENESS_HEADER = "#solid\tread_kmers\tin_assembly\tcompleteness\n"
+READS_HEAD_BYTES, READS_SLOT_BYTES, READS_MIN_SLOTS, MAX_PASSES = 256, 12, 1024, 4096
+MAX_READ_TABLE_MB = float(1 << 20)
 
 
 class KmerQvError(ValueError):
@@ -51,6 +61,34 @@ def check_options(k: int, min_count: int, segment: int, interval: int) -> None:
         raise KmerQvError("--segment %d: must be a multiple of 32 in [32, 65536]" % segment)
     if interval < 1000:
         raise KmerQvError("--interval %d: must be at least 1000" % interval)
+
+
+def read_slots(read_table_mb: float) -> int:
+    """the largest power of two of slots whose reads-only table (a 256-byte head, 12 bytes per slot) fits in --read_table_mb"""
+    mb = float(read_table_mb)
+    if not (mb == mb and 0 < mb <= MAX_READ_TABLE_MB):
+        raise KmerQvError("--read_table_mb %s: must lie in (0, 2^20]" % read_table_mb)
+    fit = (int(mb * (1 << 20)) - READS_HEAD_BYTES) // READS_SLOT_BYTES
+    if fit < READS_MIN_SLOTS:
+        raise KmerQvError("--read_table_mb %s: the smallest table, %d slots, needs %d bytes" % (
+            read_table_mb, READS_MIN_SLOTS, READS_HEAD_BYTES + READS_SLOT_BYTES * READS_MIN_SLOTS))
+    return 1 << (fit.bit_length() - 1)
+
+
+def check_completeness_options(completeness: bool, read_table_mb, passes, solid) -> Tuple[int, int, int]:
+    """-> (slots, passes, solid), the defaults 1024 MB, 1 pass, solid 2 filled in; the three options belong to --completeness"""
+    if not completeness:
+        for name, v in (("--read_table_mb", read_table_mb), ("--passes", passes), ("--solid", solid)):
+            if v is not None:
+                raise KmerQvError("%s is an option of --completeness" % name)
+        return 0, 1, 2
+    passes = 1 if passes is None else int(passes)
+    solid = 2 if solid is None else int(solid)
+    if not 1 <= passes <= MAX_PASSES:
+        raise KmerQvError("--passes %d: must lie in [1, %d]" % (passes, MAX_PASSES))
+    if not 1 <= solid <= 255:
+        raise KmerQvError("--solid %d: must lie in [1, 255]" % solid)
+    return read_slots(1024 if read_table_mb is None else read_table_mb), passes, solid
 
 
 def error_qv(kmers: int, supported: int, k: int) -> Tuple[str, str]:
@@ -104,6 +142,31 @@ def hist_text(hist) -> str:
     return HIST_HEADER + "".join("%s\t%d\n" % (c if c < last else "%d+" % last, int(v)) for c, v in enumerate(hist))
 
 
+def completeness_at(ro_hist, spectrum, s: int) -> Tuple[int, int, str]:
+    """-> (read k-mers seen s times or more, those of them in the assembly, their share or `.` without any)"""
+    found = int(np.asarray(spectrum)[:, s:].sum())
+    total = found + int(np.asarray(ro_hist)[s:].sum())
+    return total, found, ("%.6f" % (found / total)) if total else "."
+
+
+def spectrum_text(ro_hist, spectrum) -> str:
+    """count, the distinct read k-mers the assembly lacks with that count, the assembly's distinct k-mers with that count that
+    it holds once, twice, three times, four times or more (the last line: that count or more)"""
+    last = len(ro_hist) - 1
+    return SPECTRUM_HEADER + "".join("%s\t%d\t%s\n" % (c if c < last else "%d+" % last, int(ro_hist[c]),
+                                                      "\t".join(str(int(row[c])) for row in spectrum)) for c in range(last + 1))
+
+
+def completeness_text(ro_hist, spectrum) -> str:
+    """the whole curve: one line for every threshold that leaves a read k-mer"""
+    out = [COMPLETENESS_HEADER]
+    for s in range(1, len(ro_hist)):
+        total, found, share = completeness_at(ro_hist, spectrum, s)
+        if total > 0:
+            out.append("%d\t%d\t%d\t%s\n" % (s, total, found, share))
+    return "".join(out)
+
+
 def read_intervals(contigs: Sequence[Tuple[str, int]], interval: int) -> List[Tuple[str, int, int]]:
     """every contig cut into pieces of `interval` bases: [(name, start, end)]"""
     return [(name, s, min(s + interval, ln)) for name, ln in contigs for s in range(0, ln, interval)]
@@ -112,7 +175,8 @@ def read_intervals(contigs: Sequence[Tuple[str, int]], interval: int) -> List[Tu
 class Scorer:
     """one assembly's table on the device: built once, counted into batch by batch, summarised at the end"""
 
-    def __init__(self, ctx, label: str, seqs: Sequence[Tuple[str, bytes]], k: int, segment: int):
+    def __init__(self, ctx, label: str, seqs: Sequence[Tuple[str, bytes]], k: int, segment: int, slots: int = 0):
+        """slots > 0: a reads-only table of that many slots beside the assembly's (--completeness)"""
         import torch
         self.torch, self.ctx, self.label, self.k, self.segment = torch, ctx, label, int(k), int(segment)
         self.names, self.lengths = [n for n, _ in seqs], [len(s) for _, s in seqs]
@@ -129,9 +193,47 @@ class Scorer:
         torch.cuda.synchronize()
         ctx.kmer_table_build_dev(self.A.data_ptr(), self.ao.data_ptr(), self.n, self.k, CAP, self.table.data_ptr(), self.table_bytes,
                                  self.bcnt.data_ptr())
+        self.slots = int(slots)
+        if self.slots:
+            self.rtable_bytes = ctx.kmer_reads_table_bytes(self.slots)
+            self.rtable = torch.empty(self.rtable_bytes, dtype=torch.uint8, device="cuda")
+            self.ro_hist = torch.zeros(256, dtype=torch.int64, device="cuda")
+            self.fcnt = torch.zeros(4, dtype=torch.int64, device="cuda")
+            self.ro_keys = self.dropped = 0
+            torch.cuda.synchronize()
+            ctx.kmer_reads_table_init_dev(self.rtable.data_ptr(), self.rtable_bytes, self.slots, CAP)
 
     def count(self, d_bases: int, d_base_off: int, n_reads: int, n_bases: int) -> None:
         self.ctx.kmer_count_reads_dev(self.table.data_ptr(), self.table_bytes, d_bases, d_base_off, n_reads, n_bases)
+
+    def count_all(self, d_bases: int, d_base_off: int, n_reads: int, n_bases: int, part: int, n_parts: int) -> None:
+        self.ctx.kmer_count_reads_all_dev(self.table.data_ptr(), self.table_bytes, self.rtable.data_ptr(), self.rtable_bytes, d_bases,
+                                          d_base_off, n_reads, n_bases, part, n_parts)
+
+    def flush(self) -> None:
+        """after a pass: the reads-only table into ro_hist, emptied for the next part; a full table is refused"""
+        from . import _ffi
+        self.ctx.kmer_reads_flush_dev(self.rtable.data_ptr(), self.rtable_bytes, self.ro_hist.data_ptr(), self.fcnt.data_ptr())
+        self.ctx.synchronize()
+        keys, status, dropped, _ = (int(v) for v in self.fcnt.cpu().numpy())
+        self.ro_keys, self.dropped = self.ro_keys + keys, self.dropped + dropped
+        if status == _ffi.PV_ERR_CAPACITY:
+            raise KmerQvError("the %s's table of read k-mers is full (%d slots, %d read k-mers dropped): choose a larger "
+                              "--read_table_mb or more --passes" % (self.label, self.slots, dropped))
+        if status != _ffi.PV_OK:
+            raise RuntimeError("kmer_qv: the %s's flush ended with device status %d" % (self.label, status))
+
+    def spectrum(self):
+        """-> (ro_hist [256], spectrum [4][256]) as numpy arrays, after the last flush"""
+        from . import _ffi
+        torch = self.torch
+        spec, cnt = torch.zeros((4, 256), dtype=torch.int64, device="cuda"), torch.zeros(2, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        self.ctx.kmer_spectrum_dev(self.table.data_ptr(), self.table_bytes, spec.data_ptr(), cnt.data_ptr())
+        self.ctx.synchronize()
+        if int(cnt.cpu().numpy()[1]) != _ffi.PV_OK:
+            raise RuntimeError("kmer_qv: the %s's spectrum ended with device status %d" % (self.label, int(cnt.cpu().numpy()[1])))
+        return self.ro_hist.cpu().numpy(), spec.cpu().numpy()
 
     def summary(self, min_count: int):
         """-> (contig counts [n][3], seg_off, segs, runs [r][3], hist [256]) as numpy arrays"""
@@ -166,11 +268,19 @@ class Scorer:
                  ".runs.bed": runs_text(self.names, runs, self.k), ".hist.tsv": hist_text(hist)}
         return files, (unsup, kmers, error_qv(kmers, kmers - unsup, self.k)[1])
 
+    def completeness_texts(self, solid: int):
+        """-> ({file suffix: text}, completeness at `solid` or `.`)"""
+        ro_hist, spec = self.spectrum()
+        return ({".spectrum.tsv": spectrum_text(ro_hist, spec), ".completeness.tsv": completeness_text(ro_hist, spec)},
+                completeness_at(ro_hist, spec, solid)[2])
 
-def stream_reads(ctx, bam: str, fasta: str, intervals, scorers: Sequence[Scorer], threads: int, timers: dict = None) -> None:
+
+def stream_reads(ctx, bam: str, fasta: str, intervals, scorers: Sequence[Scorer], threads: int, timers: dict = None,
+                 part: Tuple[int, int] = None) -> None:
     """every interval's reads through the host reader on `threads` reader threads, a few intervals ahead of the device; each
     batch goes up with the polisher's upload call and past every scorer's table. The counts are integer sums, so neither the
-    number of threads nor the order of the batches changes them."""
+    number of threads nor the order of the batches changes them. part = (p, P), with --completeness: the k-mers of part p of P
+    alone, and those the assembly lacks into the scorer's reads-only table."""
     from . import bamio
     from .polish import _read_ahead, _thread_handles
     T = timers if timers is not None else {}
@@ -197,7 +307,10 @@ def stream_reads(ctx, bam: str, fasta: str, intervals, scorers: Sequence[Scorer]
                     raise KmerQvError("interval %s:%d-%d holds %d read bases: choose a smaller --interval" % (iv + (n_bases,)))
                 dev, totals, keep = ctx.upload_batch(b)
                 for s in scorers:
-                    s.count(dev.bases, dev.base_off, totals[0], totals[1])
+                    if part is None:
+                        s.count(dev.bases, dev.base_off, totals[0], totals[1])
+                    else:
+                        s.count_all(dev.bases, dev.base_off, totals[0], totals[1], part[0], part[1])
                 ctx.synchronize()   # the copies out of the host batch are done: it may go, and the next may come
                 del keep
                 T["reads"] += n_reads
@@ -213,6 +326,8 @@ def run(args) -> int:
     try:
         k, min_count = int(args.kmer), int(args.min_count)
         check_options(k, min_count, int(args.segment), int(args.interval))
+        complete = bool(args.completeness)
+        slots, passes, solid = check_completeness_options(complete, args.read_table_mb, args.passes, args.solid)
         for what, p in (("assembly FASTA", args.assembly), ("BAM", args.bam), ("draft FASTA", args.fasta)):
             if not os.path.isfile(p):
                 raise KmerQvError("cannot find the %s %s" % (what, p))
@@ -232,12 +347,28 @@ def run(args) -> int:
         from . import runtime
         ctx = runtime.Context(int(args.device_id))
         try:
-            scorers = [Scorer(ctx, "assembly", asm, k, int(args.segment))]
+            scorers = [Scorer(ctx, "assembly", asm, k, int(args.segment), slots)]
             if draft is not None:
-                scorers.append(Scorer(ctx, "draft", draft, k, int(args.segment)))
+                scorers.append(Scorer(ctx, "draft", draft, k, int(args.segment), slots))
             T = {}
-            stream_reads(ctx, args.bam, args.fasta, read_intervals(contigs, int(args.interval)), scorers, int(args.threads), T)
+            intervals = read_intervals(contigs, int(args.interval))
+            if not complete:
+                stream_reads(ctx, args.bam, args.fasta, intervals, scorers, int(args.threads), T)
+            else:   # the passes are the outer loop: the reads are streamed again for every part
+                for p in range(passes):
+                    Tp = {}
+                    stream_reads(ctx, args.bam, args.fasta, intervals, scorers, int(args.threads), Tp, part=(p, passes))
+                    for s in scorers:
+                        s.flush()
+                    for key, v in Tp.items():   # the reads are the same in every pass: counted once, the times summed
+                        T[key] = T.get(key, 0) + v if key.endswith("_s") else v
             results = [s.texts(min_count) for s in scorers]
+            if complete:
+                shares = []
+                for s, (files, _) in zip(scorers, results):
+                    more, share = s.completeness_texts(solid)
+                    files.update(more)
+                    shares.append(share)
         finally:
             ctx.close()
     except KmerQvError as e:
@@ -258,4 +389,11 @@ def run(args) -> int:
             dunsup, unsup, dqv, qv, k, min_count))
     else:
         log("kmer_qv: unsupported k-mers %d of %d, QV %s, k = %d, min_count = %d" % (unsup, kmers, qv, k, min_count))
+    if complete:
+        keys = "%d distinct read k-mers the assembly lacks in %d slots, %d pass%s" % (
+            scorers[0].ro_keys, slots, passes, "" if passes == 1 else "es")
+        if draft is not None:
+            log("kmer_qv: completeness %s -> %s (draft -> assembly) at --solid %d; %s" % (shares[1], shares[0], solid, keys))
+        else:
+            log("kmer_qv: completeness %s at --solid %d; %s" % (shares[0], solid, keys))
     return 0

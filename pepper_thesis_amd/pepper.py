@@ -117,6 +117,11 @@ KMER_QV_IS_NOT = ("What it is not: an error that the reads share is supported an
                   "replace `assess` where a truth exists; no value of --min_count is recommended.")
 
 
+COMPLETENESS_IS_NOT = ("The same reads and the same interval clipping as the QV side. What it is not: with noisy reads the error "
+                       "k-mers dominate reads_only at low counts, and that is what the curve is read past; a k-mer the reads "
+                       "cover thinly is lost at a high threshold whether or not the assembly holds it.")
+
+
 def kmer_qv_parser(ap=None):
     """`kmer_qv`: the reference has no counterpart"""
     ap = ap or argparse.ArgumentParser(prog="kmer_qv")
@@ -143,6 +148,22 @@ def kmer_qv_parser(ap=None):
     ap.add_argument("--segment", type=int, default=1024, help="bases per line of the segment track, a multiple of 32 in [32, 65536]")
     ap.add_argument("--interval", type=int, default=1000000, help="bases of a contig read at a time, at least 1000")
     ap.add_argument("-t", "--threads", type=int, default=5, help="reader threads; the output does not depend on them")
+    ap.add_argument("--completeness", action="store_true", default=False,
+                    help="also count the reads' k-mers that the assembly lacks, in a table of their own on the device: "
+                         "<output>_kmer_qv.spectrum.tsv (by read count: the distinct read k-mers the assembly lacks, and its own "
+                         "distinct k-mers that it holds once, twice, three times, four times or more) and .completeness.tsv (for "
+                         "every threshold s: the distinct read k-mers seen s times or more, those of them in the assembly, their "
+                         "share). " + COMPLETENESS_IS_NOT)
+    ap.add_argument("--read_table_mb", type=float, default=None,
+                    help="with --completeness: megabytes of device memory for each scored FASTA's table of read k-mers (default "
+                         "1024); the largest power of two of 12-byte slots that fits is used. A full table ends the run with "
+                         "status 2")
+    ap.add_argument("--passes", type=int, default=None,
+                    help="with --completeness: read the BAM this many times, in [1, 4096] (default 1), each time counting one part "
+                         "of the k-mers, so that the table need only hold that part; the result does not depend on it")
+    ap.add_argument("--solid", type=int, default=None,
+                    help="with --completeness: the threshold, in [1, 255], of the completeness the log gives (default 2, a "
+                         "convention: a read k-mer seen twice is rarely a read error at low depth; the file holds every threshold)")
     ap.add_argument("-d_id", "--device_id", type=int, default=0, help="the device")
     return ap
 

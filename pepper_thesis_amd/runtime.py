@@ -884,6 +884,57 @@ class Context:
             break
         return ctg, seg_off, segs[:int(counts[3])], runs[:int(counts[0])], hist, plane
 
+    def kmer_reads_table_bytes(self, slots: int) -> int:
+        """bytes of a reads-only table of `slots` entries (a power of two from PV_KMER_READS_MIN_SLOTS up)"""
+        n = int(self.lib.pv_kmer_reads_table_bytes(int(slots)))
+        if n < 0:
+            raise _ffi.PepperHipError(n, "kmer reads table: slots must be a power of two in [1024, 2^34] (got %d)" % slots)
+        return n
+
+    def kmer_reads_table_init_dev(self, d_rtable: int, rtable_bytes: int, slots: int, cap: int, stream: int = 0):
+        """asynchronous pv_kmer_reads_table_init_dev: every slot empty, the head written"""
+        _ffi.check(self.lib.pv_kmer_reads_table_init_dev(self.handle, d_rtable or None, int(rtable_bytes), int(slots), int(cap),
+                                                         stream or None))
+
+    def kmer_count_reads_all_dev(self, d_table: int, table_bytes: int, d_rtable: int, rtable_bytes: int, d_bases: int,
+                                 d_base_off: int, n_reads: int, n_bases: int, part: int = 0, n_parts: int = 1, stream: int = 0):
+        """asynchronous pv_kmer_count_reads_all_dev: the k-mers of this part added to the assembly table where it holds them, to
+        the reads-only table where it does not"""
+        _ffi.check(self.lib.pv_kmer_count_reads_all_dev(self.handle, d_table or None, int(table_bytes), d_rtable or None,
+                                                        int(rtable_bytes), d_bases or None, d_base_off or None, int(n_reads),
+                                                        int(n_bases), int(part), int(n_parts), stream or None))
+
+    def kmer_reads_flush_dev(self, d_rtable: int, rtable_bytes: int, d_ro_hist: int, d_counts: int, stream: int = 0):
+        """asynchronous pv_kmer_reads_flush_dev: the table's counts added to ro_hist (int64[256]), {distinct keys, status, dropped
+        instances, slots} in d_counts (int64[4]), the table emptied"""
+        _ffi.check(self.lib.pv_kmer_reads_flush_dev(self.handle, d_rtable or None, int(rtable_bytes), d_ro_hist or None,
+                                                    d_counts or None, stream or None))
+
+    def kmer_spectrum_dev(self, d_table: int, table_bytes: int, d_spectrum: int, d_counts: int, stream: int = 0):
+        """asynchronous pv_kmer_spectrum_dev: the assembly's distinct keys by (multiplicity, count) added to spectrum
+        (int64[4][256]), {distinct keys, status} in d_counts (int64[2])"""
+        _ffi.check(self.lib.pv_kmer_spectrum_dev(self.handle, d_table or None, int(table_bytes), d_spectrum or None,
+                                                 d_counts or None, stream or None))
+
+    def kmer_spectrum(self, asm, reads, k: int = 21, cap: int = _ffi.PV_KMER_MAX_CAP, slots: int = _ffi.PV_KMER_READS_MIN_SLOTS,
+                      n_parts: int = 1, counts=None):
+        """host-buffer pv_kmer_spectrum of [assembly contig bytes] (upper-cased) against [read bytes] -> (ro_hist int64 [256],
+        spectrum int64 [4][256]). counts: optional ctypes int64[8], filled also when the call raises."""
+        n = len(asm)
+        a_off = np.zeros(n + 1, np.int64)
+        b_off = np.zeros(len(reads) + 1, np.int64)
+        a_off[1:] = np.cumsum([len(a) for a in asm])
+        b_off[1:] = np.cumsum([len(r) for r in reads])
+        A = np.frombuffer(b"".join(bytes(a) for a in asm) or b"\0", np.uint8)   # (never a null pointer: one unread byte)
+        B = np.frombuffer(b"".join(bytes(r) for r in reads) or b"\0", np.uint8)
+        spectrum, ro_hist = np.zeros((4, _ffi.PV_KMER_HIST), np.int64), np.zeros(_ffi.PV_KMER_HIST, np.int64)
+        if counts is None:
+            counts = (C.c_int64 * 8)()
+        _ffi.check(self.lib.pv_kmer_spectrum(self.handle, _ffi.ptr(A), _ffi.ptr(a_off), n, _ffi.ptr(B), _ffi.ptr(b_off), len(reads),
+                                             int(k), int(cap), int(slots), int(n_parts), _ffi.ptr(spectrum), _ffi.ptr(ro_hist),
+                                             counts))
+        return ro_hist, spectrum
+
     def profile_begin(self, only: str = None):
         """bracket every kernel launch of this context with HIP events (only: just the kernels whose profile name starts
         with it - two events per launch put a few microseconds between kernels)"""

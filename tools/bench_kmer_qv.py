@@ -11,7 +11,13 @@ scoring the draft itself.
   host     the same rule on the host: NumPy keys, one sort of the assembly's, searchsorted per batch, --threads threads; its
            per-position counts are compared with the device's
 
+  complete with --completeness, after the legs above (which run as they did): k_km_count_all with one part under HIP events, the
+           first pass over the reads (every key the assembly lacks claims its slot) and `n` further ones (every key finds it),
+           beside k_km_count of the same session; the flush and the spectrum; the distinct reads-only keys and the load factor;
+           the end-to-end wall with the flag
+
   python tools/bench_kmer_qv.py [--mbp 3.0] [--threads 16] [--reps 5] [-k 21] [--out profiles/kmer_qv_bench.json]
+  python tools/bench_kmer_qv.py --completeness [--read_table_mb 4096] --out profiles/kmer_qv_complete_bench.json
 """
 import argparse
 import concurrent.futures
@@ -79,6 +85,66 @@ def host_count(asm: bytes, batches, k: int, threads: int):
     return plane, time.perf_counter() - t0
 
 
+def complete_legs(ctx, kq, args, asm, k, bam, fa, ivs, reps, res):
+    """the legs of --completeness on the workload of the legs above; `reps`: the passes the count leg timed"""
+    from pepper_thesis_amd import bamio
+    slots = kq.read_slots(args.read_table_mb)
+    out = {"read_table_mb": args.read_table_mb, "slots": slots}
+    sc = kq.Scorer(ctx, "assembly", asm, k, 1024, slots)
+    ctx.synchronize()
+    hb, hf = bamio.BamHandler(bam), bamio.FastaHandler(fa)
+    filled = [bamio.fill_batch(hb, hf, [iv], 0, False, 1.0, 0, max_reads=kq.READ_LIMIT) for iv in ivs]
+    n_bases = sum(int(len(f.batch.bases)) for f in filled)
+    # the first pass claims the slots, the further ones find them: both under HIP events, each batch uploaded once per pass kind
+    first = again = launches = 0.0
+    for f in filled:
+        dev, totals, keep = ctx.upload_batch(f.batch)
+        ctx.profile_begin("k_km_count_all")
+        sc.count_all(dev.bases, dev.base_off, totals[0], totals[1], 0, 1)
+        ctx.synchronize()
+        first += ctx.profile_end()["k_km_count_all"][0]
+        ctx.profile_begin("k_km_count_all")
+        for _ in range(reps):
+            sc.count_all(dev.bases, dev.base_off, totals[0], totals[1], 0, 1)
+        ctx.synchronize()
+        ms, n = ctx.profile_end()["k_km_count_all"]
+        again, launches = again + ms, launches + n
+    for f in filled:
+        f.close()
+    count_ms = res["count"]["kernel_ms"] / res["count"]["passes"]
+    out["count_all"] = {"first_pass_ms": round(first, 3), "further_passes": reps, "further_kernel_ms": round(again, 3),
+                        "further_pass_ms": round(again / reps, 3), "launches": int(launches) + len(filled),
+                        "read_mbases_per_s_first": round(n_bases / (first * 1e-3) / 1e6, 1),
+                        "k_km_count_pass_ms": round(count_ms, 3), "first_over_k_km_count": round(first / count_ms, 2),
+                        "further_over_k_km_count": round(again / reps / count_ms, 2)}
+    ctx.profile_begin("kmer_reads_flush")
+    sc.flush()
+    out["flush_ms"] = round(ctx.profile_end()["kmer_reads_flush"][0], 3)
+    out["reads_only_keys"], out["load_factor"] = sc.ro_keys, round(sc.ro_keys / slots, 4)
+    ctx.profile_begin("kmer_spectrum")
+    for _ in range(args.reps):
+        sc.spectrum()
+    ms, n = ctx.profile_end()["kmer_spectrum"]
+    out["spectrum_ms"] = round(ms / n, 3)
+    ctx.profile_begin("k_kr_init")
+    ctx.kmer_reads_table_init_dev(sc.rtable.data_ptr(), sc.rtable_bytes, slots, kq.CAP)
+    ctx.synchronize()
+    out["init_ms"] = round(ctx.profile_end()["k_kr_init"][0], 3)
+    # end to end with the flag: a fresh scorer, one pass, the flush, the summary, the spectrum and the two texts
+    T = {}
+    t0 = time.perf_counter()
+    sc = kq.Scorer(ctx, "assembly", asm, k, 1024, slots)
+    kq.stream_reads(ctx, bam, fa, ivs, [sc], args.threads, T, part=(0, 1))
+    sc.flush()
+    sc.texts(1)
+    _, share = sc.completeness_texts(2)
+    wall = time.perf_counter() - t0
+    out["e2e"] = {"wall_s": round(wall, 3), "reader_wait_s": round(T["read_s"], 3), "device_s": round(T["device_s"], 3),
+                  "wall_without_flag_s": res["e2e"]["wall_s"], "ratio": round(wall / res["e2e"]["wall_s"], 2),
+                  "completeness_at_2": share, "reads_only_keys": sc.ro_keys}
+    return out
+
+
 def say(msg):
     print("[bench_kmer_qv] " + msg, file=sys.stderr, flush=True)
 
@@ -90,6 +156,10 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("-k", "--kmer", type=int, default=21)
     ap.add_argument("--interval", type=int, default=500000)
+    ap.add_argument("--completeness", action="store_true", default=False, help="add the legs of kmer_qv --completeness")
+    ap.add_argument("--read_table_mb", type=float, default=4096.0,
+                    help="with --completeness: the reads-only table, as the command's (its default of 1024 is too small for the "
+                         "default workload's read k-mers in one pass)")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON to this file")
     args = ap.parse_args()
     import torch
@@ -172,6 +242,9 @@ def main():
                                  outs[5].data_ptr())
             ctx.synchronize()
             dev_plane = plane.cpu().numpy().view(np.uint32)[:sc.N]
+            if args.completeness:
+                res["complete"] = complete_legs(ctx, kq, args, asm, k, bam, fa, ivs, reps, res)
+                say("complete: %s" % json.dumps(res["complete"]))
         finally:
             ctx.close()
         host_plane, host_s = host_count(b"".join(kq.upper(s) for _, s in asm), batches, k, args.threads)
