@@ -1255,7 +1255,8 @@ int64_t pv_kmer_table_bytes(int64_t n_asm, const int64_t* a_off);
  *
  * pv_kmer_reads_table_init_dev: rtable 256-byte aligned, rtable_bytes at least pv_kmer_reads_table_bytes of slots; one launch.
  * pv_kmer_count_reads_all_dev: pv_kmer_count_reads_dev's arguments, the reads-only table and (part, n_parts); one launch of
- * k_km_count_all, the tile, halo and directory staging of k_km_count. pv_kmer_reads_flush_dev: two launches.
+ * k_km_count_all, which walks the reads as k_km_count does (the tile walk of csrc/kmer_index.hpp, the tile and its halo staged
+ * there, the directory in the kernel). pv_kmer_reads_flush_dev: two launches.
  * pv_kmer_spectrum_dev: two launches; the table's counters are read, not changed.
  * Status. Null pointers and scalars out of range (slots, cap, part, n_parts, negative sizes, rtable_bytes below the head or
  * below what slots need) are refused with PV_ERR_INVALID by the call itself. A reads-only table that was not initialised, or

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libpepper_hip.so")
 SOURCES = ["pv_api.hip", "summary_front.hip", "summary_pileup.hip", "summary_builder.hip", "summary_polish.hip", "summary_host.hip", "rnn_p1.hip", "rnn_lstm.hip", "rnn_head.hip", "rnn_gemm.hip", "rnn_gru.hip", "rnn_rec_bf16.hip", "pv_comm.hip", "polish_stitch.hip", "polish_edits.hip", "polish_mask.hip", "polish_filter.hip", "polish_vote.hip", "polish_vote_runs.hip", "polish_qual.hip", "polish_realign.hip", "bgzf_inflate.hip", "bam_decode.hip", "batch_select.hip", "assess.hip", "assess_place.hip", "kmer_qv.hip"]
-HEADERS = ["pv_common.hpp", "mfma_tiles.hpp", "rnn_bf16.hpp", "rnn_f32.hpp", "rnn_math.hpp", "rnn_p2_head.hpp", "rnn_ring.hpp", "rnn_plan.hpp", "rnn_pack_host.hpp", "split3_host.hpp", "pv_opts.hpp", "polish_qual_table.hpp", "polish_stitch_common.hpp", "summary_types.hpp", "summary_scan.hpp", "summary_launch.hpp", "batch_check.hpp", "assess_scan.hpp", os.path.join("..", "..", "include", "pepper_hip.h")]
+HEADERS = ["pv_common.hpp", "mfma_tiles.hpp", "rnn_bf16.hpp", "rnn_f32.hpp", "rnn_math.hpp", "rnn_p2_head.hpp", "rnn_ring.hpp", "rnn_plan.hpp", "rnn_pack_host.hpp", "split3_host.hpp", "pv_opts.hpp", "polish_qual_table.hpp", "polish_stitch_common.hpp", "summary_types.hpp", "summary_scan.hpp", "summary_launch.hpp", "batch_check.hpp", "assess_scan.hpp", "kmer_index.hpp", os.path.join("..", "..", "include", "pepper_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc"]
 

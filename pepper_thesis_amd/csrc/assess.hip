@@ -82,15 +82,6 @@ __device__ inline int64_t* slot_off_of(const Args& g) { return (int64_t*)g.scrat
 __device__ inline Layout layout_of(const Args& g) {
     return as_layout(g.n_pairs, slot_off_of(g)[g.n_pairs], g.a_off[g.n_pairs] - g.a_off[0], g.with_err);
 }
-// the pair that owns slot s: the last p with slot_off[p] <= s
-__device__ inline int64_t pair_of_slot(const int64_t* slot_off, int64_t n_pairs, int64_t s) {
-    int64_t lo = 0, hi = n_pairs - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (slot_off[mid] <= s) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(AS_THREADS) void k_as_setup(Args g) {
     __shared__ int64_t lds[AS_THREADS / 64];
@@ -131,7 +122,7 @@ __global__ __launch_bounds__(AS_THREADS) void k_as_anchor(Args g) {
     if (slot >= slot_off[g.n_pairs]) return;
     const Layout y = layout_of(g);
     Anchor* anchors = (Anchor*)(g.scratch + y.anchors);
-    const int64_t p = pair_of_slot(slot_off, g.n_pairs, slot);
+    const int64_t p = owner_of(slot_off, g.n_pairs, slot);
     const int64_t k = slot - slot_off[p] + 1;
     const int64_t na = g.a_off[p + 1] - g.a_off[p], nb = g.b_off[p + 1] - g.b_off[p];
     const uint8_t* A = g.A + g.a_off[p];
@@ -228,7 +219,7 @@ struct SegRef { int64_t pair, idx, out; SegSlot s; uint32_t* dirs; };
 __device__ inline bool seg_of_slot(const Args& g, const Layout& y, int64_t slot, SegRef* r) {
     const int64_t* slot_off = slot_off_of(g);
     if (slot >= slot_off[g.n_pairs]) return false;
-    const int64_t p = pair_of_slot(slot_off, g.n_pairs, slot);
+    const int64_t p = owner_of(slot_off, g.n_pairs, slot);
     const int64_t* pair_cnt = (const int64_t*)(g.scratch + y.pair_cnt);
     const int64_t idx = slot - slot_off[p];
     if (idx >= pair_cnt[2 * p]) return false;

@@ -7,33 +7,29 @@
 //   k_pl_setup        one block: the offsets' check, the contigs' sample offsets, what the call needs, its status
 //   k_pl_keys         one lane per sample: the key and its reverse complement -> two table entries; their counts and smallest
 //                     positions start at 0 and "none"
-//   k_pl_sort_local   a bitonic network in which every comparison is ascending (the first step of a merge mirrors its partner),
-//   k_pl_sort_global  so that a table of any size sorts in place as if padded with infinite entries: spans of PL_SORT entries
-//                     in LDS, the wider steps one launch each
+//   k_pl_sort_local   the bitonic sort of kmer_index.hpp (spans of PL_SORT entries in LDS, the wider steps one launch each),
+//   k_pl_sort_global  ordered tried entries first, then by key
 //   k_pl_dir          where the keys of each value of the top 12 bits begin in the sorted table
-//   k_pl_scan         THE HOT PATH. A workgroup takes PV_ASSESS_PLACE_TILE truth bytes and a 31-byte halo into LDS as 2-bit
-//                     codes; a lane rolls the keys of 16 consecutive positions, finds each in the table (the directory, copied
-//                     to LDS, leaves a binary search of log2(entries / 4096) steps in L2) and, for every entry with that key,
-//                     adds one to the entry's count and keeps the smallest (truth contig, position). Integer atomics: counts
-//                     and minima do not depend on the order, nor on how many workgroups share the tiles
+//   k_pl_scan         THE HOT PATH. The tile walk of kmer_index.hpp over the truth, PV_ASSESS_PLACE_TILE bytes and a 31-byte
+//                     halo at a time; its visitor finds a position's forward key in the table (the directory, copied to LDS,
+//                     leaves a binary search of log2(entries / 4096) steps in L2) and, for every entry with that key, adds
+//                     one to the entry's count and keeps the smallest (truth contig, position). Integer atomics: counts and
+//                     minima do not depend on the order, nor on how many workgroups share the tiles
 //   k_pl_decide       one workgroup per assembly contig: its hits per (truth contig, strand) in LDS, the winner, the interval,
 //                     the record
 // 5 + the sort's launches: with P the table's capacity (two entries per sample the scratch could hold) rounded up to a power of
 // two and m = max(0, log2(P) - 11), the sort takes 1 + m + m (m + 1) / 2 launches (1 for a thousand samples, 21 for thirty
 // thousand).
 // A status other than PV_OK makes every later kernel return at once, and k_pl_decide poison the records (bytes 0xFF).
-#include <algorithm>
-
-#include "assess_scan.hpp"
+#include "kmer_index.hpp"
 #include "pv_common.hpp"
 
 namespace {
 
 constexpr int PL_K = PV_ASSESS_K;
-constexpr int PL_TILE = PV_ASSESS_PLACE_TILE;
-constexpr int PL_PER = PL_TILE / AS_THREADS;    // consecutive positions of a lane
+constexpr int PL_TILE = PV_ASSESS_PLACE_TILE;   // a lane takes PL_TILE / AS_THREADS consecutive positions
 constexpr int PL_SORT = 2048;                   // entries a workgroup sorts in LDS
-constexpr int PL_DIR_BITS = 12, PL_DIR = 1 << PL_DIR_BITS;
+constexpr int PL_DIR = KI_DIR, PL_SHIFT = 64 - KI_DIR_BITS;   // the directory indexes the top bits of all 64
 constexpr int PL_MAX_TRUTH = PV_ASSESS_PLACE_MAX_TRUTH;
 constexpr uint64_t PL_NONE = ~0ull;
 constexpr uint32_t PL_UNTRIED = 1u << 31;       // in an entry's tag: the sample is not tried; such entries sort behind all others
@@ -80,37 +76,12 @@ __device__ inline Table table_of(const Args& g) {
             (uint64_t*)(g.scratch + y.cnt), (uint64_t*)(g.scratch + y.pos)};
 }
 
-// the last p in [0, n) with off[p] <= s, for off[0] <= s < off[n]: empty ranges are passed over
-__device__ inline int64_t owner_of(const int64_t* off, int64_t n, int64_t s) {
-    int64_t lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= s) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-__device__ inline uint32_t code_of(uint8_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; }
-
 // the key of the reverse complement: the complement of a code is its bitwise not, and the 32 codes change places
 __device__ inline uint64_t rc_key(uint64_t x) {
     uint64_t y = ~x;
     y = ((y >> 2) & 0x3333333333333333ull) | ((y & 0x3333333333333333ull) << 2);
     y = ((y >> 4) & 0x0F0F0F0F0F0F0F0Full) | ((y & 0x0F0F0F0F0F0F0F0Full) << 4);
     return __builtin_bswap64(y);
-}
-
-// all threads of the block get op over every thread's v; lds: uint64 [AS_THREADS / 64]
-template <typename F>
-__device__ inline uint64_t block_reduce(uint64_t v, uint64_t* lds, F op) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = op(v, (uint64_t)__shfl_xor((unsigned long long)v, d, 64));
-    __syncthreads();   // lds is free again
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = lds[0];
-    for (int i = 1; i < AS_THREADS / 64; i++) v = op(v, lds[i]);
-    return v;
 }
 
 __global__ __launch_bounds__(AS_THREADS) void k_pl_setup(Args g) {
@@ -168,76 +139,24 @@ __global__ __launch_bounds__(AS_THREADS) void k_pl_keys(Args g) {
 }
 
 // ---- the sort ---------------------------------------------------------------------------------------------------------------
-// entry order: tried before untried, then by key
-__device__ inline bool entry_less(uint64_t ka, uint32_t ta, uint64_t kb, uint32_t tb) {
-    const uint32_t ua = ta >> 31, ub = tb >> 31;
-    return ua != ub ? ua < ub : ka < kb;
-}
-// pair q of a step of width j: the lower index has bit j clear; its partner is mirrored in the block of 2 j (the first step of a
-// merge) or j higher (every other step)
-__device__ inline int64_t pair_low(int64_t q, int64_t j) { return ((q & ~(j - 1)) << 1) | (q & (j - 1)); }
-__device__ inline int64_t pair_high(int64_t i, int64_t j, bool mirror) { return mirror ? i ^ (2 * j - 1) : i | j; }
-
-// tail == 0: the merges of 2 .. PL_SORT entries, each in full; tail == 1: the steps of width PL_SORT / 2 .. 1 of a wider merge
 __global__ __launch_bounds__(AS_THREADS) void k_pl_sort_local(Args g, int tail) {
-    __shared__ uint64_t s_key[PL_SORT];
-    __shared__ uint32_t s_tag[PL_SORT];
     if (g.counts[1] != PV_OK) return;
     const Table tb = table_of(g);
-    for (int64_t base = (int64_t)blockIdx.x * PL_SORT; base < tb.n; base += (int64_t)gridDim.x * PL_SORT) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < PL_SORT; i += AS_THREADS) {
-            const bool in = base + i < tb.n;   // behind the table: infinite entries, which never move
-            s_key[i] = in ? tb.keys[base + i] : PL_NONE;
-            s_tag[i] = in ? tb.tags[base + i] : ~0u;
-        }
-        __syncthreads();
-        for (int k = tail ? PL_SORT : 2; k <= PL_SORT; k <<= 1) {
-            for (int j = k >> 1; j >= 1; j >>= 1) {
-                const bool mirror = !tail && j == (k >> 1);
-                for (int q = threadIdx.x; q < PL_SORT / 2; q += AS_THREADS) {
-                    const int i = (int)pair_low(q, j), l = (int)pair_high(i, j, mirror);
-                    const uint64_t ki = s_key[i], kl = s_key[l];
-                    const uint32_t ti = s_tag[i], tl = s_tag[l];
-                    if (entry_less(kl, tl, ki, ti)) { s_key[i] = kl; s_tag[i] = tl; s_key[l] = ki; s_tag[l] = ti; }
-                }
-                __syncthreads();
-            }
-        }
-        for (int i = threadIdx.x; i < PL_SORT; i += AS_THREADS)
-            if (base + i < tb.n) { tb.keys[base + i] = s_key[i]; tb.tags[base + i] = s_tag[i]; }
-    }
+    sort_spans<PL_SORT, TriedThenKey>(tb.keys, tb.tags, tb.n, tail);
 }
 
-// one step of width j >= PL_SORT: a lane per pair, in global memory
 __global__ __launch_bounds__(AS_THREADS) void k_pl_sort_global(Args g, int64_t j, int mirror) {
     if (g.counts[1] != PV_OK) return;
     const Table tb = table_of(g);
-    for (int64_t q = (int64_t)blockIdx.x * AS_THREADS + threadIdx.x;; q += (int64_t)gridDim.x * AS_THREADS) {
-        const int64_t i = pair_low(q, j), l = pair_high(i, j, mirror);
-        if (i >= tb.n) break;   // (i grows with q)
-        if (l >= tb.n) continue;
-        const uint64_t ki = tb.keys[i], kl = tb.keys[l];
-        const uint32_t ti = tb.tags[i], tl = tb.tags[l];
-        if (entry_less(kl, tl, ki, ti)) { tb.keys[i] = kl; tb.tags[i] = tl; tb.keys[l] = ki; tb.tags[l] = ti; }
-    }
-}
-
-// the first e in [lo, hi) with keys[e] >= key, or hi
-__device__ inline int64_t first_at_least(const uint64_t* keys, int64_t lo, int64_t hi, uint64_t key) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+    sort_global_step<TriedThenKey>(tb.keys, tb.tags, tb.n, j, mirror);
 }
 
 __global__ __launch_bounds__(AS_THREADS) void k_pl_dir(Args g) {
     if (g.counts[1] != PV_OK) return;
     const Table tb = table_of(g);
     const int b = blockIdx.x * AS_THREADS + threadIdx.x;
-    if (b < PL_DIR) tb.dir[b] = (uint32_t)first_at_least(tb.keys, 0, tb.n, (uint64_t)b << (64 - PL_DIR_BITS));
-    else if (b == PL_DIR) tb.dir[b] = (uint32_t)tb.n;
+    if (b < PL_DIR) tb.dir[b] = dir_entry(tb.keys, tb.n, b, PL_SHIFT);
+    else if (b == PL_DIR) tb.dir[b] = (uint32_t)tb.n;   // (PL_DIR << PL_SHIFT is 2^64)
 }
 
 // ---- the pass over the truth -------------------------------------------------------------------------------------------------
@@ -250,41 +169,17 @@ __global__ __launch_bounds__(AS_THREADS) void k_pl_scan(Args g) {
     const Table tb = table_of(g);
     if (tb.n == 0) return;
     for (int b = threadIdx.x; b <= PL_DIR; b += AS_THREADS) s_dir[b] = tb.dir[b];
-    for (int64_t g0 = lo + (int64_t)blockIdx.x * PL_TILE; g0 < hi; g0 += (int64_t)gridDim.x * PL_TILE) {
-        __syncthreads();   // the previous tile has been read
-        for (int i = threadIdx.x; i < PL_TILE + PL_K - 1; i += AS_THREADS) s_code[i] = g0 + i < hi ? code_of(g.B[g0 + i]) : 4;
-        __syncthreads();
-        const int i0 = threadIdx.x * PL_PER;
-        if (g0 + i0 >= hi) continue;
-        // the truth contig of the lane's first position, then forward from it; a 32-mer lies inside one contig
-        int64_t t = owner_of(g.b_off, g.n_truth, g0 + i0);
-        int64_t start = g.b_off[t], end = g.b_off[t + 1];
-        uint64_t key = 0;
-        int run = 0;   // codes of A, C, G, T in a row, up to the window's last
-        for (int q = 0; q < PL_K - 1; q++) {
-            const uint32_t c = s_code[i0 + q];
-            key = (key << 2) | (c & 3);
-            run = c < 4 ? run + 1 : 0;
+    // a 32-mer lies inside one truth contig; only its forward key is looked up: the table holds both strands of a sample
+    tile_walk<PL_TILE>(g.B, g.b_off, g.n_truth, lo, hi, PL_K, s_code, [] {}, [&](const Roll& r, int64_t pos, int64_t t, int64_t start) {
+        const uint64_t key = r.fwd, packed = ((uint64_t)t << 32) | (uint64_t)(pos - start);
+        // equal keys: the same 32-mer sampled more than once
+        for (int64_t e = dir_find(s_dir, tb.keys, key, PL_SHIFT).e; e < tb.n && tb.keys[e] == key; e++) {
+            const uint32_t tag = tb.tags[e];
+            if (tag & PL_UNTRIED) break;   // (the untried entries' key is a real one, T x 32, and they follow the tried)
+            atomicAdd((unsigned long long*)&tb.cnt[tag], 1ull);
+            atomicMin((unsigned long long*)&tb.pos[tag], (unsigned long long)packed);
         }
-        for (int m = 0; m < PL_PER; m++) {
-            const uint32_t c = s_code[i0 + PL_K - 1 + m];
-            key = (key << 2) | (c & 3);
-            run = c < 4 ? run + 1 : 0;
-            const int64_t pos = g0 + i0 + m;
-            if (pos >= hi) break;
-            while (pos >= end) { t++; start = end; end = g.b_off[t + 1]; }   // pos < hi: t stays below n_truth
-            if (run < PL_K || pos + PL_K > end) continue;
-            const uint32_t b = (uint32_t)(key >> (64 - PL_DIR_BITS));
-            int64_t e = first_at_least(tb.keys, s_dir[b], s_dir[b + 1], key);
-            const uint64_t packed = ((uint64_t)t << 32) | (uint64_t)(pos - start);
-            for (; e < tb.n && tb.keys[e] == key; e++) {   // equal keys: the same 32-mer sampled more than once
-                const uint32_t tag = tb.tags[e];
-                if (tag & PL_UNTRIED) break;   // (the untried entries' key is a real one, T x 32, and they follow the tried)
-                atomicAdd((unsigned long long*)&tb.cnt[tag], 1ull);
-                atomicMin((unsigned long long*)&tb.pos[tag], (unsigned long long)packed);
-            }
-        }
-    }
+    });
 }
 
 // ---- the decision -----------------------------------------------------------------------------------------------------------
@@ -322,11 +217,10 @@ __global__ __launch_bounds__(AS_THREADS) void k_pl_decide(Args g) {
         }
     }
     __syncthreads();
-    const auto add = [](uint64_t a, uint64_t b) { return a + b; };
     const auto most = [](uint64_t a, uint64_t b) { return a > b ? a : b; };
     const auto least = [](uint64_t a, uint64_t b) { return a < b ? a : b; };
-    tried = block_reduce(tried, s_red, add);
-    hits = block_reduce(hits, s_red, add);
+    tried = block_reduce(tried, s_red, as_add());
+    hits = block_reduce(hits, s_red, as_add());
     // the winner: the most hits, ties to the smaller 2 t + strand (the smaller t, then the forward strand)
     uint64_t best = 0;
     for (uint32_t i = threadIdx.x; i < 2 * g.n_truth; i += AS_THREADS) best = most(best, ((uint64_t)s_tally[i] << 32) | (0xFFFFFFFFu - i));
@@ -382,10 +276,6 @@ int place_check(int64_t n_asm, int64_t n_truth, int step, int min_hits) {
              "assess place: step must be a multiple of 32 in [32, 65536] (got %d)", step);
     PV_CHECK(min_hits >= 1 && min_hits <= 65535, PV_ERR_INVALID, "assess place: min_hits must lie in [1, 65535] (got %d)", min_hits);
     return PV_OK;
-}
-
-unsigned blocks_for(int64_t items, int64_t per_block, int64_t most) {
-    return (unsigned)std::max<int64_t>(1, std::min(most, (items + per_block - 1) / per_block));
 }
 
 }  // namespace
@@ -446,11 +336,8 @@ extern "C" int pv_assess_place_dev(pv_ctx* ctx, const uint8_t* A, const int64_t*
     {
         pv_prof_scope ps(ctx, "k_pl_sort", st);
         const unsigned spans = blocks_for(entries, PL_SORT, wide), pairs = blocks_for(entries / 2, AS_THREADS, wide);
-        k_pl_sort_local<<<spans, AS_THREADS, 0, st>>>(g, 0);
-        for (int64_t k = 2 * PL_SORT; (k >> 1) < entries; k <<= 1) {
-            for (int64_t j = k >> 1; j >= PL_SORT; j >>= 1) k_pl_sort_global<<<pairs, AS_THREADS, 0, st>>>(g, j, j == (k >> 1));
-            k_pl_sort_local<<<spans, AS_THREADS, 0, st>>>(g, 1);
-        }
+        sort_schedule(entries, PL_SORT, [&](int tail) { k_pl_sort_local<<<spans, AS_THREADS, 0, st>>>(g, tail); },
+                      [&](int64_t j, int mirror) { k_pl_sort_global<<<pairs, AS_THREADS, 0, st>>>(g, j, mirror); });
     }
     k_pl_dir<<<PL_DIR / AS_THREADS + 1, AS_THREADS, 0, st>>>(g);
     { pv_prof_scope ps(ctx, "k_pl_scan", st); k_pl_scan<<<(unsigned)(4 * ctx->num_cu), AS_THREADS, 0, st>>>(g); }

@@ -9,14 +9,14 @@
 //     k_km_setup        one block: the offsets' check, the summed length, what the table needs, the header, the status
 //     k_km_keys         one lane per stretch of KM_STRETCH positions: rolling forward and reverse keys -> (canonical key,
 //                       position); a position without a key gets KM_NONE, which sorts behind every key; counters 0
-//     k_km_sort_local   the bitonic network of assess_place.hip (every comparison ascending, the first step of a merge
-//     k_km_sort_global  mirrored, so a table of any size sorts as if padded with infinite entries), ordered by key alone
+//     k_km_sort_local   the bitonic sort of kmer_index.hpp (spans of KM_SORT entries in LDS, the wider steps one launch each),
+//     k_km_sort_global  ordered by key alone
 //     k_km_dir          where the keys of each value of their own top 12 bits (of 2 k) begin, and the number of keyed entries
 //   pv_kmer_count_reads_dev
-//     k_km_count        THE HOT PATH. A workgroup takes PV_KMER_TILE read bytes and a (k - 1)-byte halo into LDS as codes
-//                       (0..3, 4 = no base); a lane rolls the keys of 16 consecutive offsets, skips what does not lie in one
-//                       read, finds the canonical key (directory in LDS, then a binary search in L2) and adds one to the
-//                       counter of the first entry with that key, unless it has reached the cap
+//     k_km_count        THE HOT PATH. The tile walk of kmer_index.hpp over the reads, PV_KMER_TILE bytes and a (k - 1)-byte
+//                       halo at a time; its visitor is count_hit: the canonical key of an offset inside one read is found
+//                       (directory in LDS, then a binary search in L2) and one is added to the counter of the first entry
+//                       with that key, unless it has reached the cap
 //   pv_kmer_support_dev
 //     k_km_sup_setup    one block: the table and the offsets checked against each other, the segment offsets, zeroed sums
 //     k_km_gather       one lane per sorted entry: the count of its key (the first equal entry's, capped) to its position
@@ -29,8 +29,9 @@
 //   pv_kmer_reads_table_init_dev
 //     k_kr_init         every slot empty, the head
 //   pv_kmer_count_reads_all_dev
-//     k_km_count_all    k_km_count with a part filter and a miss path: a key the assembly lacks claims or finds its slot (linear
-//                       probing from mix(key), one 64-bit compare-and-swap on an empty slot) and adds one there under the cap
+//     k_km_count_all    the same walk with a second visitor: an instance of another part is passed over, count_hit takes the
+//                       keys the assembly has, and a key it lacks claims or finds its slot (linear probing from mix(key), one
+//                       64-bit compare-and-swap on an empty slot) and adds one there under the cap
 //   pv_kmer_reads_flush_dev
 //     k_kr_flush_setup  one lane: the head checked, {0, status, dropped, slots}, status and dropped reset
 //     k_kr_flush        a lane per slot: the histogram of the counts in LDS, the table emptied
@@ -38,19 +39,16 @@
 //     k_km_spec_setup   one lane: the table's status
 //     k_km_spectrum     a lane per sorted entry: the first of equal keys adds its (multiplicity, count) to the spectrum in LDS
 // The counters are integer atomics: the result does not depend on tile size, workgroup count or the order of the calls.
-#include <algorithm>
-
-#include "assess_scan.hpp"
+#include "kmer_index.hpp"
 #include "pv_common.hpp"
 
 namespace {
 
-constexpr int KM_TILE = PV_KMER_TILE;
-constexpr int KM_PER = KM_TILE / AS_THREADS;    // consecutive offsets of a lane of the count
+constexpr int KM_TILE = PV_KMER_TILE;           // a lane of the count takes KM_TILE / AS_THREADS consecutive offsets
 constexpr int KM_HALO = PV_KMER_MAX_K - 1;
 constexpr int KM_STRETCH = 32;                  // consecutive positions of a lane of the key kernel
 constexpr int KM_SORT = PV_KMER_SORT_SPAN;      // entries a workgroup sorts in LDS
-constexpr int KM_DIR_BITS = 12, KM_DIR = 1 << KM_DIR_BITS;
+constexpr int KM_DIR_BITS = KI_DIR_BITS, KM_DIR = KI_DIR;
 constexpr int KM_RUN_PER = 8, KM_RUN_TILE = AS_THREADS * KM_RUN_PER;
 constexpr uint64_t KM_NONE = ~0ull;             // no key has more than 62 bits
 constexpr uint32_t KM_NO_KEY = PV_KMER_NO_KEY;
@@ -108,42 +106,6 @@ __device__ inline Table table_of(void* table) {
             (int64_t*)(b + y.tile_cs), (int64_t*)(b + y.tile_ce), (int64_t*)(b + y.tile_s), (int64_t*)(b + y.tile_e)};
 }
 
-// the last p in [0, n) with off[p] <= s, for off[0] <= s < off[n]: empty ranges are passed over
-__device__ inline int64_t owner_of(const int64_t* off, int64_t n, int64_t s) {
-    int64_t lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= s) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-__device__ inline uint32_t code_of(uint8_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; }
-
-// the rolling pair of keys of the last k codes: forward, first byte highest; reverse complement, last byte's complement highest
-struct Roll {
-    uint64_t fwd = 0, rev = 0, mask; int top, run = 0, k;
-    __device__ explicit Roll(int k_) : mask((1ull << (2 * k_)) - 1), top(2 * (k_ - 1)), k(k_) {}
-    __device__ inline void push(uint32_t c) {
-        fwd = ((fwd << 2) | (c & 3)) & mask;
-        rev = (rev >> 2) | ((uint64_t)(3 - (c & 3)) << top);
-        run = c < 4 ? run + 1 : 0;
-    }
-    __device__ inline bool keyed() const { return run >= k; }
-    __device__ inline uint64_t canon() const { return fwd < rev ? fwd : rev; }
-};
-
-// all threads of the block get the sum of every thread's v; lds: int64 [AS_THREADS / 64]
-__device__ inline int64_t block_sum(int64_t v, int64_t* lds) {
-    v = wave_sum(v);
-    __syncthreads();   // lds is free again
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = 0;
-    for (int i = 0; i < AS_THREADS / 64; i++) v += lds[i];
-    return v;
-}
-
 // ---- the table --------------------------------------------------------------------------------------------------------------
 struct BuildArgs {
     const uint8_t* A; const int64_t* a_off; int64_t n_asm;
@@ -194,67 +156,16 @@ __global__ __launch_bounds__(AS_THREADS) void k_km_keys(BuildArgs g) {
     }
 }
 
-// pair q of a step of width j: the lower index has bit j clear; its partner is mirrored in the block of 2 j (the first step of a
-// merge) or j higher (every other step)
-__device__ inline int64_t pair_low(int64_t q, int64_t j) { return ((q & ~(j - 1)) << 1) | (q & (j - 1)); }
-__device__ inline int64_t pair_high(int64_t i, int64_t j, bool mirror) { return mirror ? i ^ (2 * j - 1) : i | j; }
-
-// tail == 0: the merges of 2 .. KM_SORT entries, each in full; tail == 1: the steps of width KM_SORT / 2 .. 1 of a wider merge
 __global__ __launch_bounds__(AS_THREADS) void k_km_sort_local(void* table, int tail) {
-    __shared__ uint64_t s_key[KM_SORT];
-    __shared__ uint32_t s_tag[KM_SORT];
     if (!table_ok(table)) return;
     const Table tb = table_of(table);
-    for (int64_t base = (int64_t)blockIdx.x * KM_SORT; base < tb.N; base += (int64_t)gridDim.x * KM_SORT) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < KM_SORT; i += AS_THREADS) {
-            const bool in = base + i < tb.N;   // behind the table: infinite entries, which never move
-            s_key[i] = in ? tb.keys[base + i] : KM_NONE;
-            s_tag[i] = in ? tb.tags[base + i] : ~0u;
-        }
-        __syncthreads();
-        for (int k = tail ? KM_SORT : 2; k <= KM_SORT; k <<= 1) {
-            for (int j = k >> 1; j >= 1; j >>= 1) {
-                const bool mirror = !tail && j == (k >> 1);
-                for (int q = threadIdx.x; q < KM_SORT / 2; q += AS_THREADS) {
-                    const int i = (int)pair_low(q, j), l = (int)pair_high(i, j, mirror);
-                    const uint64_t ki = s_key[i], kl = s_key[l];
-                    if (kl < ki) {
-                        const uint32_t ti = s_tag[i];
-                        s_key[i] = kl; s_tag[i] = s_tag[l]; s_key[l] = ki; s_tag[l] = ti;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        for (int i = threadIdx.x; i < KM_SORT; i += AS_THREADS)
-            if (base + i < tb.N) { tb.keys[base + i] = s_key[i]; tb.tags[base + i] = s_tag[i]; }
-    }
+    sort_spans<KM_SORT, ByKey>(tb.keys, tb.tags, tb.N, tail);
 }
 
-// one step of width j >= KM_SORT: a lane per pair, in global memory
 __global__ __launch_bounds__(AS_THREADS) void k_km_sort_global(void* table, int64_t j, int mirror) {
     if (!table_ok(table)) return;
     const Table tb = table_of(table);
-    for (int64_t q = (int64_t)blockIdx.x * AS_THREADS + threadIdx.x;; q += (int64_t)gridDim.x * AS_THREADS) {
-        const int64_t i = pair_low(q, j), l = pair_high(i, j, mirror);
-        if (i >= tb.N) break;   // (i grows with q)
-        if (l >= tb.N) continue;
-        const uint64_t ki = tb.keys[i], kl = tb.keys[l];
-        if (kl < ki) {
-            const uint32_t ti = tb.tags[i];
-            tb.keys[i] = kl; tb.tags[i] = tb.tags[l]; tb.keys[l] = ki; tb.tags[l] = ti;
-        }
-    }
-}
-
-// the first e in [lo, hi) with keys[e] >= key, or hi
-__device__ inline int64_t first_at_least(const uint64_t* keys, int64_t lo, int64_t hi, uint64_t key) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+    sort_global_step<ByKey>(tb.keys, tb.tags, tb.N, j, mirror);
 }
 
 // the directory indexes the key's own top bits: bucket b holds the keys in [b << shift, (b + 1) << shift), shift = 2 k - 12
@@ -263,7 +174,7 @@ __global__ __launch_bounds__(AS_THREADS) void k_km_dir(BuildArgs g) {
     const Table tb = table_of(g.table);
     const int b = blockIdx.x * AS_THREADS + threadIdx.x;
     if (b > KM_DIR) return;
-    const uint32_t e = (uint32_t)first_at_least(tb.keys, 0, tb.N, (uint64_t)b << tb.shift);
+    const uint32_t e = dir_entry(tb.keys, tb.N, b, tb.shift);
     tb.dir[b] = e;
     if (b == KM_DIR) { head_of(g.table)[H_KEYED] = e; g.counts[0] = e; }   // every key lies below 1 << 2 k, KM_NONE above
 }
@@ -281,6 +192,14 @@ __global__ void k_km_build_finish(BuildArgs g, int64_t status, int64_t need, int
 // ---- the pass over the reads ------------------------------------------------------------------------------------------------
 struct CountArgs { void* table; const uint8_t* bases; const int64_t* base_off; int64_t n_reads, n_bases; };
 
+// a key the table holds: one more on the counter of the first entry with it; s_dir: the table's directory
+__device__ inline bool count_hit(const Table& tb, const uint32_t* s_dir, uint64_t key) {
+    const DirHit h = dir_find(s_dir, tb.keys, key, tb.shift);
+    if (h.e >= h.top || tb.keys[h.e] != key) return false;
+    add_capped(&tb.cnt[h.e], tb.cap);
+    return true;
+}
+
 __global__ __launch_bounds__(AS_THREADS) void k_km_count(CountArgs g) {
     __shared__ uint8_t s_code[KM_TILE + KM_HALO];
     __shared__ uint32_t s_dir[KM_DIR + 1];
@@ -290,33 +209,9 @@ __global__ __launch_bounds__(AS_THREADS) void k_km_count(CountArgs g) {
     // the reads' bytes [lo, hi): nothing outside the caller's n_bases is read, whatever the offsets hold
     const int64_t lo = max(g.base_off[0], (int64_t)0), hi = min(g.base_off[g.n_reads], g.n_bases);
     if (keyed == 0 || lo + (int64_t)blockIdx.x * KM_TILE >= hi) return;
-    const int k = tb.k;
     for (int b = threadIdx.x; b <= KM_DIR; b += AS_THREADS) s_dir[b] = tb.dir[b];
-    for (int64_t g0 = lo + (int64_t)blockIdx.x * KM_TILE; g0 < hi; g0 += (int64_t)gridDim.x * KM_TILE) {
-        __syncthreads();   // the previous tile has been read
-        for (int i = threadIdx.x; i < KM_TILE + k - 1; i += AS_THREADS) s_code[i] = g0 + i < hi ? code_of(g.bases[g0 + i]) : 4;
-        __syncthreads();
-        const int i0 = threadIdx.x * KM_PER;
-        if (g0 + i0 >= hi) continue;
-        // the read of the lane's first offset, then forward from it: a k-mer lies inside one read
-        int64_t t = owner_of(g.base_off, g.n_reads, g0 + i0);
-        int64_t end = g.base_off[t + 1];
-        Roll r(k);
-        for (int q = 0; q < k - 1; q++) r.push(s_code[i0 + q]);
-        for (int m = 0; m < KM_PER; m++) {
-            r.push(s_code[i0 + k - 1 + m]);
-            const int64_t pos = g0 + i0 + m;
-            if (pos >= hi) break;
-            while (pos >= end && t + 1 < g.n_reads) { t++; end = g.base_off[t + 1]; }
-            if (!r.keyed() || pos + k > end) continue;   // a byte that is no base, or the k bytes are not all in one read
-            const uint64_t key = r.canon();
-            const uint32_t b = (uint32_t)(key >> tb.shift);
-            const int64_t top = s_dir[b + 1], e = first_at_least(tb.keys, s_dir[b], top, key);
-            if (e >= top || tb.keys[e] != key) continue;
-            // a counter at the cap is left alone, so it cannot wrap: the overshoot is bounded by the lanes in flight
-            if (__hip_atomic_load(&tb.cnt[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < tb.cap) atomicAdd(&tb.cnt[e], 1u);
-        }
-    }
+    tile_walk<KM_TILE>(g.bases, g.base_off, g.n_reads, lo, hi, tb.k, s_code, [] {},
+                       [&](const Roll& r, int64_t, int64_t, int64_t) { count_hit(tb, s_dir, r.canon()); });
 }
 
 // ---- the summary ------------------------------------------------------------------------------------------------------------
@@ -398,15 +293,14 @@ __global__ __launch_bounds__(AS_THREADS) void k_km_sums(SupArgs g) {
             unsup += c < g.min_count;
             atomicAdd(&s_hist[min(c, (uint32_t)(PV_KMER_HIST - 1))], 1u);
         }
-        keyed = block_sum(keyed, lds);
-        unsup = block_sum(unsup, lds);   // (its barriers: the LDS histogram is complete)
+        keyed = block_reduce(keyed, lds, as_add());
+        unsup = block_reduce(unsup, lds, as_add());   // (its barriers: the LDS histogram is complete)
         if (threadIdx.x == 0) {
             g.segs[s] = unsup;
             atomicAdd((unsigned long long*)&g.ctg[3 * p], (unsigned long long)keyed);
             atomicAdd((unsigned long long*)&g.ctg[3 * p + 1], (unsigned long long)unsup);
         }
-        for (int i = threadIdx.x; i < PV_KMER_HIST; i += AS_THREADS)
-            if (s_hist[i]) atomicAdd((unsigned long long*)&g.hist[i], (unsigned long long)s_hist[i]);
+        lds_hist_flush(s_hist, PV_KMER_HIST, g.hist);
     }
 }
 
@@ -434,7 +328,7 @@ __global__ __launch_bounds__(AS_THREADS) void k_km_run_count(SupArgs g) {
     for (int64_t t = blockIdx.x; t < T; t += gridDim.x) {
         uint32_t st, en;
         run_flags(tb, t * KM_RUN_TILE + (int64_t)threadIdx.x * KM_RUN_PER, g.min_count, &st, &en);
-        const int64_t ns = block_sum(__popc(st), lds), ne = block_sum(__popc(en), lds);
+        const int64_t ns = block_reduce((int64_t)__popc(st), lds, as_add()), ne = block_reduce((int64_t)__popc(en), lds, as_add());
         if (threadIdx.x == 0) { tb.tile_cs[t] = ns; tb.tile_ce[t] = ne; }
     }
 }
@@ -478,25 +372,18 @@ __global__ __launch_bounds__(AS_THREADS) void k_km_run_write(SupArgs g) {
         __syncthreads();
         int64_t js = tb.tile_s[t] + xs - own_s, je = tb.tile_e[t] + xe - own_e;
         for (int i = 0; i < w; i++) { js += lds_s[i]; je += lds_e[i]; }
-        if (st) {
+        // put(contig, offset in it) for every set bit of the lane's starts or ends, in order
+        const auto each = [&](uint32_t bits, auto put) {
+            if (!bits) return;
             int64_t p = owner_of(g.a_off, g.n_asm, base + f0);
             for (int m = 0; m < KM_RUN_PER; m++) {
-                if (!(st >> m & 1)) continue;
-                while (base + f0 + m >= g.a_off[p + 1]) p++;   // a start is a position of a contig: p stays below n_asm
-                g.runs[3 * js] = p;
-                g.runs[3 * js + 1] = base + f0 + m - g.a_off[p];
-                js++;
+                if (!(bits >> m & 1)) continue;
+                while (base + f0 + m >= g.a_off[p + 1]) p++;   // a set bit is a position of a contig: p stays below n_asm
+                put(p, base + f0 + m - g.a_off[p]);
             }
-        }
-        if (en) {
-            int64_t p = owner_of(g.a_off, g.n_asm, base + f0);
-            for (int m = 0; m < KM_RUN_PER; m++) {
-                if (!(en >> m & 1)) continue;
-                while (base + f0 + m >= g.a_off[p + 1]) p++;
-                g.runs[3 * je + 2] = base + f0 + m - g.a_off[p];
-                je++;
-            }
-        }
+        };
+        each(st, [&](int64_t p, int64_t at) { g.runs[3 * js] = p; g.runs[3 * js + 1] = at; js++; });
+        each(en, [&](int64_t, int64_t at) { g.runs[3 * je + 2] = at; je++; });
     }
 }
 
@@ -566,8 +453,8 @@ struct CountAllArgs {
     uint32_t part, n_parts;
 };
 
-// k_km_count's tile, halo and directory staging; an instance of another part is passed over, a hit adds to the assembly table
-// as there, and a miss goes to the reads-only table: THE HOT PATH with noisy reads, where most instances are misses
+// k_km_count's walk and directory; an instance of another part is passed over, a hit adds to the assembly table as there, and
+// a miss goes to the reads-only table: THE HOT PATH with noisy reads, where most instances are misses
 __global__ __launch_bounds__(AS_THREADS) void k_km_count_all(CountAllArgs g) {
     __shared__ uint8_t s_code[KM_TILE + KM_HALO];
     __shared__ uint32_t s_dir[KM_DIR + 1];
@@ -577,59 +464,35 @@ __global__ __launch_bounds__(AS_THREADS) void k_km_count_all(CountAllArgs g) {
     const bool look = head_of(g.table)[H_KEYED] != 0;   // a table without a key has no directory: every instance is a miss
     const int64_t lo = max(g.base_off[0], (int64_t)0), hi = min(g.base_off[g.n_reads], g.n_bases);
     if (lo + (int64_t)blockIdx.x * KM_TILE >= hi) return;
-    const int k = tb.k;
     const uint64_t mask = (uint64_t)rd.slots - 1;
     if (look)
         for (int b = threadIdx.x; b <= KM_DIR; b += AS_THREADS) s_dir[b] = tb.dir[b];
     int64_t dropped = 0;
     bool full = false;
-    for (int64_t g0 = lo + (int64_t)blockIdx.x * KM_TILE; g0 < hi; g0 += (int64_t)gridDim.x * KM_TILE) {
-        __syncthreads();   // the previous tile has been read
-        for (int i = threadIdx.x; i < KM_TILE + k - 1; i += AS_THREADS) s_code[i] = g0 + i < hi ? code_of(g.bases[g0 + i]) : 4;
-        __syncthreads();
-        // once per tile: after an overflow nothing is probed any more
-        full = full || __hip_atomic_load(&rd.head[R_STATUS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != PV_OK;
-        const int i0 = threadIdx.x * KM_PER;
-        if (g0 + i0 >= hi) continue;
-        int64_t t = owner_of(g.base_off, g.n_reads, g0 + i0);
-        int64_t end = g.base_off[t + 1];
-        Roll r(k);
-        for (int q = 0; q < k - 1; q++) r.push(s_code[i0 + q]);
-        for (int m = 0; m < KM_PER; m++) {
-            r.push(s_code[i0 + k - 1 + m]);
-            const int64_t pos = g0 + i0 + m;
-            if (pos >= hi) break;
-            while (pos >= end && t + 1 < g.n_reads) { t++; end = g.base_off[t + 1]; }
-            if (!r.keyed() || pos + k > end) continue;
-            const uint64_t key = r.canon(), h = km_mix(key);
-            if (g.n_parts > 1 && (uint32_t)(h >> 32) % g.n_parts != g.part) continue;
-            if (look) {
-                const uint32_t b = (uint32_t)(key >> tb.shift);
-                const int64_t top = s_dir[b + 1], e = first_at_least(tb.keys, s_dir[b], top, key);
-                if (e < top && tb.keys[e] == key) {
-                    if (__hip_atomic_load(&tb.cnt[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < tb.cap) atomicAdd(&tb.cnt[e], 1u);
-                    continue;
-                }
-            }
-            if (full) { dropped++; continue; }
-            // a slot's key is written once and stays: a key seen there is final, and only an empty slot needs the compare-and-swap
-            uint64_t s = h & mask;
-            bool placed = false;
-            for (int p = 0; p < KR_PROBES; p++, s = (s + 1) & mask) {
-                uint64_t old = __hip_atomic_load(&rd.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (old == KM_NONE) old = atomicCAS((unsigned long long*)&rd.keys[s], (unsigned long long)KM_NONE, (unsigned long long)key);
-                if (old != KM_NONE && old != key) continue;
-                if (__hip_atomic_load(&rd.cnt[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < rd.cap) atomicAdd(&rd.cnt[s], 1u);
-                placed = true;
-                break;
-            }
-            if (!placed) {
-                full = true;
-                dropped++;
-                __hip_atomic_store(&rd.head[R_STATUS], (int64_t)PV_ERR_CAPACITY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+    // once per tile: after an overflow nothing is probed any more
+    const auto per_tile = [&] { full = full || __hip_atomic_load(&rd.head[R_STATUS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != PV_OK; };
+    tile_walk<KM_TILE>(g.bases, g.base_off, g.n_reads, lo, hi, tb.k, s_code, per_tile, [&](const Roll& r, int64_t, int64_t, int64_t) {
+        const uint64_t key = r.canon(), h = km_mix(key);
+        if (g.n_parts > 1 && (uint32_t)(h >> 32) % g.n_parts != g.part) return;
+        if (look && count_hit(tb, s_dir, key)) return;
+        if (full) { dropped++; return; }
+        // a slot's key is written once and stays: a key seen there is final, and only an empty slot needs the compare-and-swap
+        uint64_t s = h & mask;
+        bool placed = false;   // (a flag, not a return out of the loop, which compiles to twice the compare-and-swap sites)
+        for (int p = 0; p < KR_PROBES; p++, s = (s + 1) & mask) {
+            uint64_t old = __hip_atomic_load(&rd.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (old == KM_NONE) old = atomicCAS((unsigned long long*)&rd.keys[s], (unsigned long long)KM_NONE, (unsigned long long)key);
+            if (old != KM_NONE && old != key) continue;
+            add_capped(&rd.cnt[s], rd.cap);
+            placed = true;
+            break;
         }
-    }
+        if (!placed) {
+            full = true;
+            dropped++;
+            __hip_atomic_store(&rd.head[R_STATUS], (int64_t)PV_ERR_CAPACITY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    });
     dropped = wave_sum(dropped);
     if ((threadIdx.x & 63) == 0 && dropped) atomicAdd((unsigned long long*)&rd.head[R_DROPPED], (unsigned long long)dropped);
 }
@@ -661,10 +524,9 @@ __global__ __launch_bounds__(AS_THREADS) void k_kr_flush(FlushArgs g) {
         rd.keys[s] = KM_NONE;
         rd.cnt[s] = 0;
     }
-    n = block_sum(n, lds);   // (its barriers: the LDS histogram is complete)
+    n = block_reduce(n, lds, as_add());   // (its barriers: the LDS histogram is complete)
     if (threadIdx.x == 0 && n) atomicAdd((unsigned long long*)&g.counts[0], (unsigned long long)n);
-    for (int i = threadIdx.x; i < PV_KMER_HIST; i += AS_THREADS)
-        if (s_hist[i]) atomicAdd((unsigned long long*)&g.ro_hist[i], (unsigned long long)s_hist[i]);
+    lds_hist_flush(s_hist, PV_KMER_HIST, g.ro_hist);
 }
 
 struct SpecArgs { void* table; int64_t* spectrum; int64_t* counts; };
@@ -693,14 +555,9 @@ __global__ __launch_bounds__(AS_THREADS) void k_km_spectrum(SpecArgs g) {
         atomicAdd(&s_spec[(m - 1) * PV_KMER_HIST + c], 1u);
         n++;
     }
-    n = block_sum(n, lds);   // (its barriers: the LDS spectrum is complete)
+    n = block_reduce(n, lds, as_add());   // (its barriers: the LDS spectrum is complete)
     if (threadIdx.x == 0 && n) atomicAdd((unsigned long long*)&g.counts[0], (unsigned long long)n);
-    for (int i = threadIdx.x; i < 4 * PV_KMER_HIST; i += AS_THREADS)
-        if (s_spec[i]) atomicAdd((unsigned long long*)&g.spectrum[i], (unsigned long long)s_spec[i]);
-}
-
-unsigned blocks_for(int64_t items, int64_t per_block, int64_t most) {
-    return (unsigned)std::max<int64_t>(1, std::min(most, (items + per_block - 1) / per_block));
+    lds_hist_flush(s_spec, 4 * PV_KMER_HIST, g.spectrum);
 }
 
 int build_check(int64_t n_asm, int k, int64_t cap) {
@@ -719,6 +576,57 @@ int support_check(int64_t n_asm, int64_t min_count, int segment, int64_t seg_cap
              (long long)min_count);
     PV_CHECK(segment >= 32 && segment <= 65536 && segment % 32 == 0, PV_ERR_INVALID,
              "kmer support: segment must be a multiple of 32 in [32, 65536] (got %d)", segment);
+    return PV_OK;
+}
+
+// what both passes over the reads ask of a batch; pv_kmer_count_reads_dev is part 0 of 1
+int count_check(int64_t table_bytes, const uint8_t* bases, int64_t n_reads, int64_t n_bases, int part, int n_parts) {
+    PV_CHECK(n_reads >= 0 && n_bases >= 0 && (n_bases == 0 || bases), PV_ERR_INVALID, "kmer count: reads missing or negative sizes");
+    PV_CHECK(n_parts >= 1 && n_parts <= PV_KMER_MAX_PARTS && part >= 0 && part < n_parts, PV_ERR_INVALID,
+             "kmer count: part %d of %d: the parts must lie in [1, %d] and the part below them", part, n_parts, PV_KMER_MAX_PARTS);
+    PV_CHECK(n_bases < (1ll << 31) && n_reads < (1ll << 31), PV_ERR_LIMIT, "kmer count: a batch holds at most 2^31 - 1 bases");
+    PV_CHECK(table_bytes >= km_layout(0).total, PV_ERR_LIMIT, "kmer count: the table of %lld bytes cannot hold its head",
+             (long long)table_bytes);
+    return PV_OK;
+}
+
+// The host forms' way to the device. The offsets size the copies, so they are looked at first: what the device would report.
+// With offsets that are in order (ok()), the assembly, the reads and both offset arrays are on the device, next to a table.
+struct Staged {
+    int64_t bad_contig = -1;   // the first contig whose offsets decrease
+    bool bad_start = false, bad_reads = false, too_long = false;
+    int64_t N = 0, need = 0;   // the summed assembly length, the table's bytes
+    size_t n_b = 0;            // the reads' bytes
+    uint8_t *a = nullptr, *b = nullptr, *table = nullptr;
+    int64_t *a_off = nullptr, *b_off = nullptr;
+    bool invalid() const { return bad_contig >= 0 || bad_start || bad_reads; }
+    bool ok() const { return !invalid() && !too_long; }
+};
+int km_stage(pv_ctx* ctx, const uint8_t* A, const int64_t* a_off, int64_t n_asm, const uint8_t* bases, const int64_t* base_off,
+             int64_t n_reads, Staged* s) {
+    for (int64_t p = 0; p < n_asm && s->bad_contig < 0; p++)
+        if (a_off[p + 1] < a_off[p]) s->bad_contig = p;
+    s->bad_start = n_asm && a_off[0] != 0;
+    s->bad_reads = base_off[0] != 0;
+    for (int64_t r = 0; r < n_reads && !s->bad_reads; r++) s->bad_reads = base_off[r + 1] < base_off[r];
+    s->N = s->bad_contig < 0 && n_asm ? a_off[n_asm] : 0;
+    s->too_long = s->N >= (1ll << 31) || (!s->bad_reads && base_off[n_reads] >= (1ll << 31));
+    if (!s->ok()) return PV_OK;
+    PV_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t na = (size_t)n_asm, nr = (size_t)n_reads;
+    s->n_b = (size_t)base_off[n_reads];
+    s->need = km_layout(s->N).total;
+    int rc;
+    if ((rc = pv_get(ctx, "km.a", (size_t)s->N + 1, &s->a))) return rc;
+    if ((rc = pv_get(ctx, "km.b", s->n_b + 1, &s->b))) return rc;
+    if ((rc = pv_get(ctx, "km.a_off", na + 1, &s->a_off))) return rc;
+    if ((rc = pv_get(ctx, "km.b_off", nr + 1, &s->b_off))) return rc;
+    if ((rc = pv_get(ctx, "km.table", (size_t)s->need, &s->table))) return rc;
+    if (s->N) PV_HIP(hipMemcpyAsync(s->a, A, (size_t)s->N, hipMemcpyHostToDevice, st));
+    if (s->n_b) PV_HIP(hipMemcpyAsync(s->b, bases, s->n_b, hipMemcpyHostToDevice, st));
+    PV_HIP(hipMemcpyAsync(s->a_off, a_off, (na + 1) * 8, hipMemcpyHostToDevice, st));
+    PV_HIP(hipMemcpyAsync(s->b_off, base_off, (nr + 1) * 8, hipMemcpyHostToDevice, st));
     return PV_OK;
 }
 
@@ -762,11 +670,8 @@ extern "C" int pv_kmer_table_build_dev(pv_ctx* ctx, const uint8_t* A, const int6
     {
         pv_prof_scope ps(ctx, "k_km_sort", st);
         const unsigned spans = blocks_for(entries, KM_SORT, wide), pairs = blocks_for(entries / 2, AS_THREADS, wide);
-        k_km_sort_local<<<spans, AS_THREADS, 0, st>>>(table, 0);
-        for (int64_t w = 2 * KM_SORT; (w >> 1) < entries; w <<= 1) {
-            for (int64_t j = w >> 1; j >= KM_SORT; j >>= 1) k_km_sort_global<<<pairs, AS_THREADS, 0, st>>>(table, j, j == (w >> 1));
-            k_km_sort_local<<<spans, AS_THREADS, 0, st>>>(table, 1);
-        }
+        sort_schedule(entries, KM_SORT, [&](int tail) { k_km_sort_local<<<spans, AS_THREADS, 0, st>>>(table, tail); },
+                      [&](int64_t j, int mirror) { k_km_sort_global<<<pairs, AS_THREADS, 0, st>>>(table, j, mirror); });
     }
     k_km_dir<<<KM_DIR / AS_THREADS + 1, AS_THREADS, 0, st>>>(g);
     PV_HIP(hipGetLastError());
@@ -776,10 +681,8 @@ extern "C" int pv_kmer_table_build_dev(pv_ctx* ctx, const uint8_t* A, const int6
 extern "C" int pv_kmer_count_reads_dev(pv_ctx* ctx, void* table, int64_t table_bytes, const uint8_t* bases, const int64_t* base_off,
                                        int64_t n_reads, int64_t n_bases, void* stream) {
     PV_CHECK(ctx && table && base_off, PV_ERR_INVALID, "kmer count: null argument");
-    PV_CHECK(n_reads >= 0 && n_bases >= 0 && (n_bases == 0 || bases), PV_ERR_INVALID, "kmer count: reads missing or negative sizes");
-    PV_CHECK(n_bases < (1ll << 31) && n_reads < (1ll << 31), PV_ERR_LIMIT, "kmer count: a batch holds at most 2^31 - 1 bases");
-    PV_CHECK(table_bytes >= km_layout(0).total, PV_ERR_LIMIT, "kmer count: the table of %lld bytes cannot hold its head",
-             (long long)table_bytes);
+    int rc;
+    if ((rc = count_check(table_bytes, bases, n_reads, n_bases, 0, 1))) return rc;
     if (n_reads == 0 || n_bases == 0) return PV_OK;
     PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = pv_pick_stream(ctx, stream);
@@ -836,40 +739,26 @@ extern "C" int pv_kmer_support(pv_ctx* ctx, const uint8_t* A, const int64_t* a_o
     PV_CHECK(n_asm == 0 || (A && contig_counts), PV_ERR_INVALID, "kmer support: sequences or counts missing");
     PV_CHECK((seg_capacity == 0 || segs) && (run_capacity == 0 || runs), PV_ERR_INVALID, "kmer support: an output is missing");
     for (int i = 0; i < 8; i++) counts[i] = 0;
-    counts[5] = -1;
-    // the offsets size the copies, so they are looked at here first: what the device would report, reported the same way
-    for (int64_t p = 0; p < n_asm && counts[5] < 0; p++)
-        if (a_off[p + 1] < a_off[p]) counts[5] = p;
-    bool reads_bad = base_off[0] != 0;
-    for (int64_t r = 0; r < n_reads && !reads_bad; r++) reads_bad = base_off[r + 1] < base_off[r];
-    const int64_t N = counts[5] < 0 && n_asm ? a_off[n_asm] : 0;
-    const bool too_long = N >= (1ll << 31) || (!reads_bad && base_off[n_reads] >= (1ll << 31));
-    if (counts[5] >= 0 || (n_asm && a_off[0] != 0) || reads_bad || too_long) {
-        const int status = counts[5] >= 0 || (n_asm && a_off[0] != 0) || reads_bad ? PV_ERR_INVALID : PV_ERR_LIMIT;
-        counts[1] = status;
+    Staged s;
+    if ((rc = km_stage(ctx, A, a_off, n_asm, bases, base_off, n_reads, &s))) return rc;
+    counts[5] = s.bad_contig;
+    if (!s.ok()) {   // reported the way the device reports it
+        counts[1] = s.invalid() ? PV_ERR_INVALID : PV_ERR_LIMIT;
         memset(contig_counts, 0xFF, (size_t)n_asm * 24);
         memset(seg_off, 0xFF, (size_t)(n_asm + 1) * 8);
         memset(segs, 0xFF, (size_t)seg_capacity * 8);
         memset(runs, 0xFF, (size_t)run_capacity * 24);
         memset(hist, 0xFF, PV_KMER_HIST * 8);
         PV_CHECK(counts[5] < 0, PV_ERR_INVALID, "kmer support: the offsets of contig %lld decrease", (long long)counts[5]);
-        PV_CHECK(!(n_asm && a_off[0] != 0) && !reads_bad, PV_ERR_INVALID, "kmer support: offsets must start at 0 and not decrease");
+        PV_CHECK(!s.bad_start && !s.bad_reads, PV_ERR_INVALID, "kmer support: offsets must start at 0 and not decrease");
         counts[6] = km_layout(1ll << 31).total;
         PV_CHECK(false, PV_ERR_LIMIT, "kmer support: the assembly or the reads hold 2^31 bytes or more");
     }
-    PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const size_t na = (size_t)n_asm, nr = (size_t)n_reads, n_b = (size_t)base_off[n_reads];
-    const int64_t need = km_layout(N).total;
-    uint8_t *d_a = nullptr, *d_b = nullptr, *d_table = nullptr;
-    int64_t *d_ao = nullptr, *d_bo = nullptr, *d_ctg = nullptr, *d_so = nullptr, *d_segs = nullptr, *d_runs = nullptr, *d_hist = nullptr;
-    int64_t* d_counts = nullptr;
+    const size_t na = (size_t)n_asm;
+    const int64_t N = s.N;
+    int64_t *d_ctg = nullptr, *d_so = nullptr, *d_segs = nullptr, *d_runs = nullptr, *d_hist = nullptr, *d_counts = nullptr;
     uint32_t* d_plane = nullptr;
-    if ((rc = pv_get(ctx, "km.a", (size_t)N + 1, &d_a))) return rc;
-    if ((rc = pv_get(ctx, "km.b", n_b + 1, &d_b))) return rc;
-    if ((rc = pv_get(ctx, "km.a_off", na + 1, &d_ao))) return rc;
-    if ((rc = pv_get(ctx, "km.b_off", nr + 1, &d_bo))) return rc;
-    if ((rc = pv_get(ctx, "km.table", (size_t)need, &d_table))) return rc;
     if ((rc = pv_get(ctx, "km.ctg", 3 * na + 1, &d_ctg))) return rc;
     if ((rc = pv_get(ctx, "km.seg_off", na + 1, &d_so))) return rc;
     if ((rc = pv_get(ctx, "km.segs", (size_t)seg_capacity + 1, &d_segs))) return rc;
@@ -877,15 +766,11 @@ extern "C" int pv_kmer_support(pv_ctx* ctx, const uint8_t* A, const int64_t* a_o
     if ((rc = pv_get(ctx, "km.hist", (size_t)PV_KMER_HIST, &d_hist))) return rc;
     if ((rc = pv_get(ctx, "km.counts", (size_t)12, &d_counts))) return rc;
     if (pos_counts && (rc = pv_get(ctx, "km.plane", (size_t)N + 1, &d_plane))) return rc;
-    if (N) PV_HIP(hipMemcpyAsync(d_a, A, (size_t)N, hipMemcpyHostToDevice, st));
-    if (n_b) PV_HIP(hipMemcpyAsync(d_b, bases, n_b, hipMemcpyHostToDevice, st));
-    PV_HIP(hipMemcpyAsync(d_ao, a_off, (na + 1) * 8, hipMemcpyHostToDevice, st));
-    PV_HIP(hipMemcpyAsync(d_bo, base_off, (nr + 1) * 8, hipMemcpyHostToDevice, st));
     // the caller's run records stay as they were where none is written (PV_ERR_CAPACITY)
     if (run_capacity) PV_HIP(hipMemcpyAsync(d_runs, runs, (size_t)run_capacity * 24, hipMemcpyHostToDevice, st));
-    if ((rc = pv_kmer_table_build_dev(ctx, d_a, d_ao, n_asm, k, cap, d_table, need, d_counts + 8, st))) return rc;
-    if ((rc = pv_kmer_count_reads_dev(ctx, d_table, need, d_b, d_bo, n_reads, (int64_t)n_b, st))) return rc;
-    if ((rc = pv_kmer_support_dev(ctx, d_table, need, d_ao, n_asm, min_count, segment, d_ctg, d_so, seg_capacity, d_segs,
+    if ((rc = pv_kmer_table_build_dev(ctx, s.a, s.a_off, n_asm, k, cap, s.table, s.need, d_counts + 8, st))) return rc;
+    if ((rc = pv_kmer_count_reads_dev(ctx, s.table, s.need, s.b, s.b_off, n_reads, (int64_t)s.n_b, st))) return rc;
+    if ((rc = pv_kmer_support_dev(ctx, s.table, s.need, s.a_off, n_asm, min_count, segment, d_ctg, d_so, seg_capacity, d_segs,
                                   run_capacity, d_runs, d_hist, pos_counts ? d_plane : nullptr, d_counts, st)))
         return rc;
     int64_t h[12];
@@ -944,12 +829,7 @@ extern "C" int pv_kmer_count_reads_all_dev(pv_ctx* ctx, void* table, int64_t tab
     PV_CHECK(ctx && table && base_off, PV_ERR_INVALID, "kmer count: null argument");
     int rc;
     if ((rc = reads_check(rtable, rtable_bytes))) return rc;
-    PV_CHECK(n_reads >= 0 && n_bases >= 0 && (n_bases == 0 || bases), PV_ERR_INVALID, "kmer count: reads missing or negative sizes");
-    PV_CHECK(n_parts >= 1 && n_parts <= PV_KMER_MAX_PARTS && part >= 0 && part < n_parts, PV_ERR_INVALID,
-             "kmer count: part %d of %d: the parts must lie in [1, %d] and the part below them", part, n_parts, PV_KMER_MAX_PARTS);
-    PV_CHECK(n_bases < (1ll << 31) && n_reads < (1ll << 31), PV_ERR_LIMIT, "kmer count: a batch holds at most 2^31 - 1 bases");
-    PV_CHECK(table_bytes >= km_layout(0).total, PV_ERR_LIMIT, "kmer count: the table of %lld bytes cannot hold its head",
-             (long long)table_bytes);
+    if ((rc = count_check(table_bytes, bases, n_reads, n_bases, part, n_parts))) return rc;
     if (n_reads == 0 || n_bases == 0) return PV_OK;
     PV_HIP(hipSetDevice(ctx->device));
     hipStream_t st = pv_pick_stream(ctx, stream);
@@ -1001,37 +881,24 @@ extern "C" int pv_kmer_spectrum(pv_ctx* ctx, const uint8_t* A, const int64_t* a_
     PV_CHECK(n_parts >= 1 && n_parts <= PV_KMER_MAX_PARTS, PV_ERR_INVALID, "kmer spectrum: the parts must lie in [1, %d] (got %d)",
              PV_KMER_MAX_PARTS, n_parts);
     for (int i = 0; i < 8; i++) counts[i] = 0;
-    bool bad = (n_asm && a_off[0] != 0) || base_off[0] != 0;
-    for (int64_t p = 0; p < n_asm && !bad; p++) bad = a_off[p + 1] < a_off[p];
-    for (int64_t r = 0; r < n_reads && !bad; r++) bad = base_off[r + 1] < base_off[r];
-    if (bad) counts[1] = PV_ERR_INVALID;
-    PV_CHECK(!bad, PV_ERR_INVALID, "kmer spectrum: offsets must start at 0 and not decrease");
-    const int64_t N = n_asm ? a_off[n_asm] : 0;
-    if (N >= (1ll << 31) || base_off[n_reads] >= (1ll << 31)) counts[1] = PV_ERR_LIMIT;
-    PV_CHECK(counts[1] == PV_OK, PV_ERR_LIMIT, "kmer spectrum: the assembly or the reads hold 2^31 bytes or more");
-    PV_HIP(hipSetDevice(ctx->device));
+    Staged s;
+    if ((rc = km_stage(ctx, A, a_off, n_asm, bases, base_off, n_reads, &s))) return rc;
+    if (!s.ok()) counts[1] = s.invalid() ? PV_ERR_INVALID : PV_ERR_LIMIT;
+    PV_CHECK(!s.invalid(), PV_ERR_INVALID, "kmer spectrum: offsets must start at 0 and not decrease");
+    PV_CHECK(s.ok(), PV_ERR_LIMIT, "kmer spectrum: the assembly or the reads hold 2^31 bytes or more");
     hipStream_t st = ctx->stream;
-    const size_t na = (size_t)n_asm, nr = (size_t)n_reads, n_b = (size_t)base_off[n_reads], np = (size_t)n_parts;
-    const int64_t need = km_layout(N).total, rneed = reads_bytes(slots);
-    uint8_t *d_a = nullptr, *d_b = nullptr, *d_table = nullptr, *d_rtable = nullptr;
-    int64_t *d_ao = nullptr, *d_bo = nullptr, *d_out = nullptr, *d_counts = nullptr;
-    if ((rc = pv_get(ctx, "km.a", (size_t)N + 1, &d_a))) return rc;
-    if ((rc = pv_get(ctx, "km.b", n_b + 1, &d_b))) return rc;
-    if ((rc = pv_get(ctx, "km.a_off", na + 1, &d_ao))) return rc;
-    if ((rc = pv_get(ctx, "km.b_off", nr + 1, &d_bo))) return rc;
-    if ((rc = pv_get(ctx, "km.table", (size_t)need, &d_table))) return rc;
+    const size_t np = (size_t)n_parts;
+    const int64_t need = s.need, rneed = reads_bytes(slots);
+    uint8_t *d_table = s.table, *d_rtable = nullptr;
+    int64_t *d_out = nullptr, *d_counts = nullptr;
     if ((rc = pv_get(ctx, "km.rtable", (size_t)rneed, &d_rtable))) return rc;
     if ((rc = pv_get(ctx, "km.spectrum", (size_t)5 * PV_KMER_HIST, &d_out))) return rc;   // the spectrum, then ro_hist
     if ((rc = pv_get(ctx, "km.fcounts", 4 * np + 8, &d_counts))) return rc;                // {build 4, spectrum 2, 0, 0}, a flush's 4 per part
-    if (N) PV_HIP(hipMemcpyAsync(d_a, A, (size_t)N, hipMemcpyHostToDevice, st));
-    if (n_b) PV_HIP(hipMemcpyAsync(d_b, bases, n_b, hipMemcpyHostToDevice, st));
-    PV_HIP(hipMemcpyAsync(d_ao, a_off, (na + 1) * 8, hipMemcpyHostToDevice, st));
-    PV_HIP(hipMemcpyAsync(d_bo, base_off, (nr + 1) * 8, hipMemcpyHostToDevice, st));
     if ((rc = pv_zero_async(d_out, (size_t)5 * PV_KMER_HIST * 8, st))) return rc;
-    if ((rc = pv_kmer_table_build_dev(ctx, d_a, d_ao, n_asm, k, cap, d_table, need, d_counts, st))) return rc;
+    if ((rc = pv_kmer_table_build_dev(ctx, s.a, s.a_off, n_asm, k, cap, d_table, need, d_counts, st))) return rc;
     if ((rc = pv_kmer_reads_table_init_dev(ctx, d_rtable, rneed, slots, cap, st))) return rc;
     for (int p = 0; p < n_parts; p++) {
-        if ((rc = pv_kmer_count_reads_all_dev(ctx, d_table, need, d_rtable, rneed, d_b, d_bo, n_reads, (int64_t)n_b, p, n_parts, st)))
+        if ((rc = pv_kmer_count_reads_all_dev(ctx, d_table, need, d_rtable, rneed, s.b, s.b_off, n_reads, (int64_t)s.n_b, p, n_parts, st)))
             return rc;
         if ((rc = pv_kmer_reads_flush_dev(ctx, d_rtable, rneed, d_out + 4 * PV_KMER_HIST, d_counts + 8 + 4 * p, st))) return rc;
     }
